@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- images/sec of Engine::Forward() for YOLOv5s 640x640 fp32 on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1: one process per GPU.  Under torch.distributed.run (RANK / WORLD_SIZE in the environment) this process IS a rank;
 started plainly, it spawns the N ranks itself as child processes (simpleinfer_amd/launch.py) before anything touches
@@ -16,11 +16,19 @@ scaling, global batch 32*N (N = 8 is BASELINE.json's "batch=256 sharded across 8
 total instead (strong scaling: B/N per GPU, BASELINE.json's "batch=32 at 1/2/4/8 GPUs").  Inputs are resident in HBM before
 the timed region; weights are random-init (portable splitmix64 stream), data is synthetic.
 
-The timed region is exactly K steps between two fences (barrier + device sync); it is repeated until `--min-time` seconds
-of timed work have accumulated and `value` / `ms_per_step` are those of the MEDIAN window (`windows` carries count /
-min / max / first).
+The timed region is exactly K steps between two fences (barrier + device sync), after W untimed warm-up steps and at least
+SETTLE_S (1 s) of further untimed steps, so that it starts at steady state.  A plain run
+times it once and measures nothing else: `ms_per_step` is that window over K.  `--min-time S` repeats the window
+until S seconds of timed work have accumulated and `value` / `ms_per_step` are those of the MEDIAN window (`windows`
+carries count / min / max / first); `--full` defaults S to 10.
 
-One JSON line on stdout from rank 0.  Besides the contract's fields it carries
+`--dump-outputs DIR` writes what the timed path computed in its last step -- the output a caller receives (for N > 1 the
+gathered one, from rank 0) -- as DIR/<output name>.npy, float32.  An output larger than 60 MB is written as a fixed sample
+of its rows (last axis kept whole, row indices drawn by numpy's default_rng(0) and sorted), so two builds run with
+the same arguments write the same elements.
+
+One JSON line on stdout from rank 0.  `--full` adds every measurement beyond the headline (a plain run carries none of
+them):
   roofline     -- the dominant kernel (the conv kernel TEMPLATE with the largest total time, all its instantiations):
                   algorithmic direct-conv FLOPs per launch / average launch duration, measured live with HIP
                   events on the engine's stream in an instrumented pass right after the timed region
@@ -49,13 +57,14 @@ if ROOT not in sys.path:
 
 PEAK_FP32_MFMA_TFLOPS = 157.3  # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, 64 FLOP/clk/SIMD
 PEAK_HBM_GBS = 8000.0
+SETTLE_S = 1.0   # untimed steps after the W warm-up steps: clocks and caches reach steady state before the timed window
 
 
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--warmup", type=int, default=3, help="untimed steps before the timed region (then >= SETTLE_S more, untimed)")
     ap.add_argument("--batch", type=int, default=32, help="per-GPU batch (images per Forward); weak scaling")
     ap.add_argument("--global-batch", type=int, default=0, help="total images per step over all GPUs (strong scaling): per-GPU batch = B / N")
     ap.add_argument("--gather", default="auto", choices=["auto", "p2p", "rccl", "both", "torch"],
@@ -63,26 +72,36 @@ def parse():
                          "rccl = ncclAllGather through si_rccl_* (librccl.so by dlopen, no torch), auto = p2p with a collective fallback to "
                          "rccl, both = the timed region twice, p2p then rccl, in ONE run (`value` is p2p's, `gather_ab` carries both), "
                          "torch = torch.distributed all_gather_into_tensor (the round-1 path, kept for A/B)")
-    ap.add_argument("--min-time", type=float, default=10.0, help="repeat the K-step timed window until this many seconds are accumulated (BASELINE.md section 3: >= 10 s)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: CPU baselines, roofline / per-kernel profile, host-I/O, post-processing and "
+                         "application pipeline figures, secondary configurations, and --min-time 10 unless given")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32; a fixed seeded row sample above 60 MB)")
+    ap.add_argument("--min-time", type=float, default=None,
+                    help="repeat the K-step timed window until this many seconds are accumulated; default 0 (one window of exactly "
+                         "--steps steps), 10 with --full (BASELINE.md section 3: >= 10 s)")
     ap.add_argument("--max-windows", type=int, default=200)
     ap.add_argument("--size", type=int, default=640)
     ap.add_argument("--model", default="yolov5s", choices=["yolov5s", "resnet18", "mobilenetv3"])
     ap.add_argument("--graph", type=int, default=0, help="replay Forward() as a hipGraph")
     ap.add_argument("--winograd", type=int, default=1, help="3x3 s1 convs: 0 implicit GEMM everywhere, 1 fused Winograd F(2,3) where faster (default), 2 fused Winograd F(4,3) on those layers")
     ap.add_argument("--fp16", type=int, default=0, help="1: fp16 storage / fp16 MFMA path (BASELINE.json configs[3]); the headline metric is fp32 (default 0)")
-    ap.add_argument("--no-aux", action="store_true", help="skip the host-I/O and post-processing side measurements")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the bounded secondary configurations (fp16, ResNet18 b64, batch 8 / 4)")
+    ap.add_argument("--no-aux", action="store_true", help="with --full: skip the host-I/O and post-processing side measurements")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the bounded secondary configurations (fp16, ResNet18 b64, batch 8 / 4)")
     ap.add_argument("--secondary-time", type=float, default=1.0, help="seconds of timed windows per secondary configuration")
     ap.add_argument("--secondary-warmup", type=float, default=0.3, help="seconds of untimed forwards in front of them")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-images", type=int, default=24, help="images in the batch-1 CPU baseline sample")
     ap.add_argument("--cpu-batch", type=int, default=16, help="batch of the batched CPU baseline samples (BASELINE.md section 3); the three CPU legs together are bounded to ~20 s")
     ap.add_argument("--cpu-threads", type=int, default=16, help="oracle threads (reference uses 16 intra-op)")
     ap.add_argument("--profile-passes", type=int, default=3)
-    ap.add_argument("--layers", action="store_true", help="print the per-layer table to stderr")
+    ap.add_argument("--layers", action="store_true", help="print the per-layer table to stderr (runs the profile passes without --full too)")
     ap.add_argument("--engine-opt", action="append", default=[], metavar="KEY=VALUE",
                     help="extra Engine::SetOption for A/B runs (e.g. arena=0, fuse_upsample=0); recorded in config.engine_options")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.min_time is None:
+        args.min_time = 10.0 if args.full else 0.0
+    return args
 
 
 def workload_key(args, shape):
@@ -97,6 +116,26 @@ def build_model(mg, name, batch, size):
     if name == "mobilenetv3":
         return mg.build_mobilenetv3_small(batch, sz), (batch, sz, sz, 3)
     return mg.build_resnet18(batch, sz), (batch, sz, sz, 3)
+
+
+DUMP_LIMIT_BYTES = 60_000_000   # per dump; the .npy header and a margin keep a dump under 64 MB
+
+
+def dump_output(out_dir, name, a):
+    """--dump-outputs: `a` as out_dir/<name>.npy in float32; above 60 MB a fixed sample of its rows -- the last axis whole, the
+    row indices drawn by default_rng(0) and sorted -- so that the same arguments select the same elements in every run and build."""
+    os.makedirs(out_dir, exist_ok=True)
+    a = np.asarray(a, np.float32)
+    note = "whole"
+    if a.nbytes > DUMP_LIMIT_BYTES:
+        rows = a.reshape(-1, a.shape[-1])
+        k = DUMP_LIMIT_BYTES // (rows.shape[1] * 4)
+        idx = np.sort(np.random.default_rng(0).choice(rows.shape[0], k, replace=False))
+        a = rows[idx]
+        note = "%d of %d rows (default_rng(0), sorted)" % (k, rows.shape[0])
+    fname = "".join(c if c.isalnum() or c in "._-" else "_" for c in name) + ".npy"
+    np.save(os.path.join(out_dir, fname), a)
+    print("bench.py: wrote %s %s: %s" % (fname, list(a.shape), note), file=sys.stderr)
 
 
 def _physical_cores():
@@ -723,7 +762,7 @@ def main():
     with tempfile.TemporaryDirectory(prefix="si_bench_r%d_" % rank) as td:
         # the CPU legs run FIRST (bounded, ~20 s): the GPU leg is then the long, uninterrupted tail of the run
         cpu = {"cpu_baseline": None}
-        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline(args, mg, td)
 
         builder, shape = build_model(mg, args.model, args.batch, args.size)
@@ -874,6 +913,18 @@ def main():
         if use_dist and args.warmup > 0:
             slab_checksums()
             fence()
+        # then untimed steps until SETTLE_S seconds of them have run (the first forward -- pipeline build, code-object load -- not
+        # counted): a 20-step window after 3 warm-up steps read 1.1 % above the steady-state median, 100 steps after 10 within 0.1 %.
+        # Batches of 1, 2, 4, ... steps, the stop decided on the slowest rank's clock, so every rank runs the same count
+        if args.warmup == 0:
+            step()
+            fence()
+        t0, n = time.perf_counter(), 1
+        while max_over_ranks(time.perf_counter() - t0) < SETTLE_S:
+            for _ in range(n):
+                step()
+            fence()
+            n *= 2
 
         def timed_region():
             """K steps between two fences, repeated until --min-time of timed work has accumulated"""
@@ -914,6 +965,16 @@ def main():
             return w[len(w) // 2] if len(w) % 2 else 0.5 * (w[len(w) // 2 - 1] + w[len(w) // 2])
 
         windows, fwd_ms, total, gather_diag = timed_region()
+        if args.dump_outputs and rank == 0:
+            # the last timed step's output as its caller receives it, before anything else runs on the engine
+            if sf is not None:
+                gshape = sf.gathered_shape()
+                last = hipops.DeviceBuffer.view(sf.gathered_ptr(), int(np.prod(gshape)) * 4).to_numpy(gshape)
+            elif og is not None:
+                last = og.latest().cpu().numpy()
+            else:
+                last = e.extract(oname)
+            dump_output(args.dump_outputs, oname, last)
         gather_ab = None
         if use_dist and args.gather == "both" and sf is not None:
             # the same engine, the same run: the direct fan-out was timed above, now RCCL's all-gather through the C-ABI
@@ -943,7 +1004,8 @@ def main():
         fwd_ms_per_step = fwd_ms / (args.steps * len(windows))
 
         roof, agg, layers = None, {}, None
-        if rank == 0:
+        profiled = rank == 0 and (args.full or args.layers)
+        if profiled:
             if sf is not None:
                 e.bind_output(oname, None)
             passes = [e.profile() for _ in range(max(args.profile_passes, 1))]
@@ -969,13 +1031,13 @@ def main():
                 print("sum of layer times %.3f ms" % sum(L["ms"] for L in layers), file=sys.stderr)
 
         aux = {}
-        if rank == 0 and world == 1 and not args.no_aux:
+        if args.full and rank == 0 and world == 1 and not args.no_aux:
             aux = aux_measurements(args, si, hipops, H, e, oname, oshape, pp, bp, dev, x, extra_opts)
             if args.model == "yolov5s" and len(oshape) == 3 and not args.fp16:
                 aux["app_pipeline"] = app_pipeline(args, si, hipops, H, e, iname, oname, oshape, args.batch * args.steps / dt)
                 e.input_device(iname, dx.ptr)
         secondary = None
-        if rank == 0 and world == 1 and not args.no_secondary and args.model == "yolov5s" and args.batch == 32 and args.size == 640 and not args.fp16:
+        if args.full and rank == 0 and world == 1 and not args.no_secondary and args.model == "yolov5s" and args.batch == 32 and args.size == 640 and not args.fp16:
             # the headline engine is done (nothing below reads it): released first.  Measured (profiles/r05_secondary_gap.txt): with it
             # still alive the fp16 / f32_split engines created behind it read 3 % / 1.5 % low (25.5 -> 24.7 k, 9.48 -> 9.33 k; the fp32 cases
             # do not move), in front of it or with it released they read what a process of their own reads
@@ -1032,11 +1094,12 @@ def main():
                         "compute")),
         "gflop_per_image": round(flops_step / args.batch / 1e9, 3),
         "frac_of_mfma_ceiling": round(value / world / ceiling, 4),
-        "roofline": roof,
-        "conv_kernels": {k: {"ms_per_step": round(v["ms"] / max(args.profile_passes, 1), 3),
-                             "tflops": round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 2) if v["ms"] > 0 else 0}
-                         for k, v in agg.items()},
     }
+    if profiled:
+        out["roofline"] = roof
+        out["conv_kernels"] = {k: {"ms_per_step": round(v["ms"] / max(args.profile_passes, 1), 3),
+                                   "tflops": round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 2) if v["ms"] > 0 else 0}
+                               for k, v in agg.items()}
     out.update(cpu)
     out.update(aux)
     if secondary is not None:

@@ -1,4 +1,5 @@
-"""Generates tests/golden/*.npz -- seeded inputs and expected outputs for the operator set.
+"""Generates tests/golden/*.npz -- seeded inputs and expected outputs for the operator set -- and the pnnx loader fixtures
+(*.refdump.txt, loader_refdumps.json.gz).
 
 Run in the build container only:  python tests/golden/make_golden.py
 Expected outputs come from torch-CPU in float64 (PyTorch ops are the semantics pnnx / the reference
@@ -6,9 +7,12 @@ mirror: nn.Conv2d, nn.MaxPool2d, nn.Upsample(nearest), torch.cat, ...), converte
 pnnx loader fixtures come from the REFERENCE's own loader (oracle/_ref/ref_pnnx_dump, compiled from
 /root/reference/src/pnnx).  Nothing of the reference's source text is stored: fixtures are data.
 """
+import gzip
+import json
 import os
 import subprocess
 import sys
+import tempfile
 
 import numpy as np
 import torch
@@ -109,6 +113,34 @@ def main():
             with open(os.path.join(HERE, "%s.%s.refdump.txt" % (name, tag)), "w") as f:
                 f.write(txt)
     print("reference loader dumps written")
+    loader_reference_dumps()
+
+
+def loader_reference_dumps():
+    """loader_refdumps.json.gz: the reference loader's dump of every model tests/test_pnnx_loader.py hands it (the builders are
+    that module's own), keyed as the tests look them up"""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import test_pnnx_loader as t
+    from simpleinfer_amd import engine
+    tag = {False: "raw", True: "expanded"}
+    out = {}
+    with tempfile.TemporaryDirectory() as td:
+        pp, bp = os.path.join(td, "m.pnnx.param"), os.path.join(td, "m.pnnx.bin")
+        for which, build in sorted(t.LIVE_MODELS.items()):
+            build().save(pp, bp)
+            for expand in (False, True):
+                out["%s.%s" % (which, tag[expand])] = t.run_reference_loader(pp, bp, expand)
+        t.expression_model().save(pp, bp)
+        out["expressions.expanded"] = t.run_reference_loader(pp, bp, True)
+        for which, build in sorted(t.WRITER_MODELS.items()):
+            build().save(pp, bp)
+            for expand in (False, True):
+                qp, qb = os.path.join(td, "q.pnnx.param"), os.path.join(td, "q.pnnx.bin")
+                engine.pnnx_save(pp, bp, qp, qb, expand=expand)
+                out["saved.%s.%s" % (which, tag[expand])] = t.run_reference_loader(qp, qb, False)
+    with gzip.GzipFile(os.path.join(HERE, "loader_refdumps.json.gz"), "wb", 9, mtime=0) as f:
+        f.write(json.dumps(out, indent=0, sort_keys=True).encode())
+    print("loader_refdumps.json.gz:", len(out), "dumps")
 
 
 if __name__ == "__main__":

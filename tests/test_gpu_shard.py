@@ -102,7 +102,7 @@ def _bench(*args, env_extra=None, timeout=600):
 
 
 def test_bench_line_single_gpu(gpu):
-    p, r = _bench("--steps", 3, "--warmup", 1, "--size", 160, "--batch", 4, "--min-time", 0.2, "--cpu-images", 1, "--cpu-batch", 2)
+    p, r = _bench("--full", "--steps", 3, "--warmup", 1, "--size", 160, "--batch", 4, "--min-time", 0.2, "--cpu-images", 1, "--cpu-batch", 2)
     assert p.returncode == 0 and r is not None, p.stderr[-3000:]
     assert len([ln for ln in p.stdout.splitlines() if ln.strip()]) == 1          # ONE line on stdout
     assert r["n_gpus"] == 1 and r["steps"] == 3 and r["scaling"] == "weak" and r["dtype"] == "f32" and r["unit"] == "images/sec"
@@ -115,6 +115,31 @@ def test_bench_line_single_gpu(gpu):
     for k in ("cpu_baseline", "cpu_baseline_batched"):
         assert r[k]["kind"] == "port" and r[k]["value"] > 0 and r[k]["cores"] >= 1
     assert r["config"]["gather"] is None
+
+
+def test_bench_plain_run_times_exactly_its_steps_and_dumps_the_last_output(gpu, orc, tmp_path):
+    """A plain run (no --full): ONE window of exactly --steps steps, and nothing beyond the headline in its line.
+    --dump-outputs writes the last timed step's output (whole at this size): it matches the CPU oracle on the same seeded model
+    and input, and a second run with the same arguments writes the same bits."""
+    import numpy as np
+    from simpleinfer_amd import modelgen as mg
+    from util import assert_detect_parity
+    dumps = []
+    for k in range(2):
+        d = tmp_path / ("out%d" % k)
+        p, r = _bench("--steps", 4, "--warmup", 1, "--size", 160, "--batch", 2, "--dump-outputs", d)
+        assert p.returncode == 0 and r is not None, p.stderr[-3000:]
+        assert r["steps"] == 4 and r["windows"]["count"] == 1 and r["windows"]["steps_each"] == 4
+        assert r["higher_is_better"] is True and r["dtype"] == "f32" and r["unit"] == "images/sec" and r["ms_per_step"] > 0
+        assert r["cpu_baseline"] is None and not {"roofline", "conv_kernels", "host_io", "postprocess", "app_pipeline", "secondary"} & set(r)
+        (f,) = os.listdir(d)
+        dumps.append(np.load(d / f))
+    pp, bp = str(tmp_path / "m.pnnx.param"), str(tmp_path / "m.pnnx.bin")
+    mg.build_yolov5s(2, 160).save(pp, bp)
+    (ref,) = orc.run_graph(pp, bp, {"0": mg.synth_input((2, 160, 160, 3), seed=1)}).values()
+    assert dumps[0].dtype == np.float32 and dumps[0].shape == ref.shape
+    assert_detect_parity(dumps[0], ref, what="bench.py --dump-outputs vs oracle")
+    assert np.array_equal(dumps[0], dumps[1])
 
 
 def test_bench_self_launches_two_ranks_sharing_the_device(gpu):

@@ -86,6 +86,23 @@ def test_bench_self_launches_and_fails_cleanly_without_devices(native_libs):
     assert not [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
 
 
+def test_bench_dump_samples_an_output_above_the_limit_the_same_way_every_run(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: an output above the size limit is written as a fixed sample of whole rows (sorted, seeded): the
+    same elements in every run; one within the limit is written whole."""
+    import numpy as np
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 100 * 85 * 4)
+    a = np.arange(2 * 300 * 85, dtype=np.float32).reshape(2, 300, 85)
+    for d in ("a", "b"):
+        bench.dump_output(str(tmp_path / d), "out/0", a)
+    x, y = np.load(tmp_path / "a" / "out_0.npy"), np.load(tmp_path / "b" / "out_0.npy")
+    assert x.dtype == np.float32 and x.shape == (100, 85) and np.array_equal(x, y)
+    idx = (x[:, 0] // 85).astype(np.int64)
+    assert (np.diff(idx) > 0).all() and np.array_equal(a.reshape(-1, 85)[idx], x)
+    bench.dump_output(str(tmp_path / "c"), "small", a[:1, :50])
+    assert np.array_equal(np.load(tmp_path / "c" / "small.npy"), a[:1, :50])
+
+
 def test_rccl_entry_points_fail_cleanly_without_the_library(native_libs, tmp_path):
     """include/si_shard.h si_rccl_*: librccl.so is dlopen()ed on first use, nothing links against it.  With SI_RCCL_LIB naming a
     file that does not exist every entry point reports SI_SHARD_E_SYS (-102) / "not available" instead of failing to load the

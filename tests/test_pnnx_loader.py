@@ -1,6 +1,9 @@
 """CPU: the product's pnnx loader (C++, through the C-ABI si_pnnx_dump) against the REFERENCE's own
-loader -- live (oracle/_ref/ref_pnnx_dump, compiled from /root/reference/src/pnnx) when that binary is
-present, and always against the committed dumps it produced (tests/golden/*.refdump.txt)."""
+loader: always against the committed dumps it produced (tests/golden/*.refdump.txt and
+tests/golden/loader_refdumps.json.gz, written by tests/golden/make_golden.py), and live as well
+(oracle/_ref/ref_pnnx_dump, compiled from the reference sources) where that binary is built."""
+import gzip
+import json
 import os
 import subprocess
 
@@ -11,8 +14,23 @@ from simpleinfer_amd import engine, modelgen as mg
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 REF_BIN = os.path.join(ROOT, "oracle", "_ref", "ref_pnnx_dump")
+REF_DUMPS = os.path.join(HERE, "golden", "loader_refdumps.json.gz")
 
 MODELS = {"toy_yolo": lambda: mg.build_toy_yolo(2, 64), "toy_classifier": lambda: mg.build_toy_classifier(2, 32)}
+
+
+def run_reference_loader(pp, bp, expand):
+    return subprocess.run([REF_BIN, pp, bp] + (["--expand"] if expand else []), check=True, capture_output=True, text=True).stdout
+
+
+def _reference(key, pp, bp, expand):
+    """The reference loader's dump of (pp, bp) as recorded under `key` in REF_DUMPS; where oracle/_ref is built, it is also taken
+    live and must agree with the record."""
+    with gzip.open(REF_DUMPS, "rt") as f:
+        gold = json.load(f)[key]
+    if os.path.exists(REF_BIN):
+        assert run_reference_loader(pp, bp, expand) == gold, "%s: the recorded reference dump is stale (make_golden.py)" % key
+    return gold
 
 
 def _ours(tmp_path, builder, expand):
@@ -30,21 +48,19 @@ def test_loader_matches_committed_reference_dump(native_libs, tmp_path, name, ex
     assert ours == gold
 
 
-@pytest.mark.skipif(not os.path.exists(REF_BIN), reason="oracle/_ref not built (reference sources absent)")
-@pytest.mark.parametrize("which", ["yolov5s", "resnet18", "toy_classifier"])
+LIVE_MODELS = {"yolov5s": lambda: mg.build_yolov5s(1, 64), "resnet18": lambda: mg.build_resnet18(1, 32),
+               "toy_classifier": lambda: mg.build_toy_classifier(1, 16)}
+
+
+@pytest.mark.parametrize("which", sorted(LIVE_MODELS))
 def test_loader_matches_live_reference_loader(native_libs, tmp_path, which):
-    b = {"yolov5s": lambda: mg.build_yolov5s(1, 64), "resnet18": lambda: mg.build_resnet18(1, 32),
-         "toy_classifier": lambda: mg.build_toy_classifier(1, 16)}[which]()
+    b = LIVE_MODELS[which]()
     for expand in (False, True):
         pp, bp, ours = _ours(tmp_path, b, expand)
-        ref = subprocess.run([REF_BIN, pp, bp] + (["--expand"] if expand else []), check=True, capture_output=True,
-                             text=True).stdout
-        assert ours == ref
+        assert ours == _reference("%s.%s" % (which, "expanded" if expand else "raw"), pp, bp, expand)
 
 
-@pytest.mark.skipif(not os.path.exists(REF_BIN), reason="oracle/_ref not built")
-def test_nested_and_scalar_expressions_lower_like_the_reference(native_libs, tmp_path):
-    """expand_expression corner cases: nesting, scalar operands, pow->square, unsupported tokens."""
+def expression_model():
     b = mg.PnnxBuilder()
     x = b.input((1, 4, 8, 8))
     y = b.relu(x)
@@ -52,9 +68,13 @@ def test_nested_and_scalar_expressions_lower_like_the_reference(native_libs, tmp
         z = b.expression(expr, [x, y])
         x = b.relu(z)
     b.output(x)
-    pp, bp, ours = _ours(tmp_path, b, True)
-    ref = subprocess.run([REF_BIN, pp, bp, "--expand"], check=True, capture_output=True, text=True).stdout
-    assert ours == ref
+    return b
+
+
+def test_nested_and_scalar_expressions_lower_like_the_reference(native_libs, tmp_path):
+    """expand_expression corner cases: nesting, scalar operands, pow->square, unsupported tokens."""
+    pp, bp, ours = _ours(tmp_path, expression_model(), True)
+    assert ours == _reference("expressions.expanded", pp, bp, True)
     assert "pnnx.Expression" in ours  # the size() expression is left in place, as the reference leaves it
 
 
@@ -117,9 +137,8 @@ def test_saved_model_loads_back_to_the_same_graph(native_libs, tmp_path, which):
             for n in zb.namelist():
                 if n in za.namelist():
                     assert za.read(n) == zb.read(n), n
-        if os.path.exists(REF_BIN):  # and the reference's own loader reads what we wrote
-            ref = subprocess.run([REF_BIN, qp, qb], check=True, capture_output=True, text=True).stdout
-            assert ref == got
+        # and the reference's own loader reads what we wrote
+        assert _reference("saved.%s.%s" % (which, "expanded" if expand else "raw"), qp, qb, False) == got
 
 
 def test_save_rebatches_every_operand(native_libs, tmp_path):

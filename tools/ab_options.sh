@@ -5,7 +5,7 @@ A="$1"; B="$2"; R=${3:-3}
 for i in $(seq 1 $R); do
   for tag in A B; do
     if [ $tag = A ]; then O="$A"; else O="$B"; fi
-    python bench.py --no-cpu-baseline --no-aux --min-time 1.5 $O 2>/dev/null | python -c "
+    python bench.py --full --no-cpu-baseline --no-aux --min-time 1.5 $O 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('$tag', d['value'], d['ms_per_step'])"
   done
 done

@@ -5,7 +5,7 @@ cp simpleinfer_amd/libsi_hip.so /tmp/libsi_hip_orig.so
 for f in build_variants/libsi_hip_*.so; do
   tag=$(basename $f .so); tag=${tag#libsi_hip_}
   cp $f simpleinfer_amd/libsi_hip.so
-  python bench.py --no-cpu-baseline --no-aux "$@" 2>/dev/null | python -c "
+  python bench.py --full --no-cpu-baseline --no-aux "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 print('$tag', d['value'], d['ms_per_step'], {k: v['ms_per_step'] for k, v in d['conv_kernels'].items()})"

@@ -35,19 +35,19 @@ rocm-smi --showmeminfo vram 2>/dev/null | grep -E "Total Memory|Used" | tee -a "
 run() { name=$1; shift; echo "== $name: $*" | tee -a "$O/log.txt"; timeout 600 "$@" > "$O/$name.json" 2>> "$O/log.txt"; echo "rc=$?" >> "$O/log.txt"; }
 
 # A: strong scaling, batch 32 total
-for n in 1 2 4 8; do run strong_$n python3 bench.py --gpus $n --global-batch 32 $B; done
+for n in 1 2 4 8; do run strong_$n python3 bench.py --full --gpus $n --global-batch 32 $B; done
 # B: weak scaling, 32 per GPU
-for n in 1 8; do run weak_$n python3 bench.py --gpus $n $B; done
+for n in 1 8; do run weak_$n python3 bench.py --full --gpus $n $B; done
 # C: both transports, same run
-run both_8 python3 bench.py --gpus 8 --gather both $B
-run both_8_strong python3 bench.py --gpus 8 --global-batch 32 --gather both $B
+run both_8 python3 bench.py --full --gpus 8 --gather both $B
+run both_8_strong python3 bench.py --full --gpus 8 --global-batch 32 --gather both $B
 # D: SDMA off
-HSA_ENABLE_SDMA=0 run weak_8_sdma0 python3 bench.py --gpus 8 $B
+HSA_ENABLE_SDMA=0 run weak_8_sdma0 python3 bench.py --full --gpus 8 $B
 # E: kernel trace, one GPU, program directly after --
-( cd /tmp && rocprofv3 --kernel-trace --stats -d "$OLDPWD/$O/prof1" -o r04 -- python3 "$OLDPWD/bench.py" --gpus 1 --steps 20 --warmup 3 --min-time 2 --no-cpu-baseline --no-aux --no-secondary > "$OLDPWD/$O/prof1.json" 2>> "$OLDPWD/$O/log.txt" )
+( cd /tmp && rocprofv3 --kernel-trace --stats -d "$OLDPWD/$O/prof1" -o r04 -- python3 "$OLDPWD/bench.py" --full --gpus 1 --steps 20 --warmup 3 --min-time 2 --no-cpu-baseline --no-aux --no-secondary > "$OLDPWD/$O/prof1.json" 2>> "$OLDPWD/$O/log.txt" )
 # F: per-rank HIP_VISIBLE_DEVICES (launch.py gives every rank LOCAL_RANK; SI_LAUNCH_PIN_VISIBLE=1 makes it export
 #    HIP_VISIBLE_DEVICES=<local rank> so that every rank calls its GPU "device 0")
-SI_LAUNCH_PIN_VISIBLE=1 run weak_8_pinned python3 bench.py --gpus 8 --gather p2p $B
+SI_LAUNCH_PIN_VISIBLE=1 run weak_8_pinned python3 bench.py --full --gpus 8 --gather p2p $B
 
 python3 - "$O" <<'PY'
 import json, sys, glob, os

@@ -9,7 +9,7 @@ rm -f /tmp/stop
     sleep 0.2
   done ) > $OUT/power_$TAG.txt &
 SPID=$!
-python bench.py --no-cpu-baseline --no-aux "$@" > $OUT/power_$TAG.json 2>/dev/null
+python bench.py --full --no-cpu-baseline --no-aux "$@" > $OUT/power_$TAG.json 2>/dev/null
 touch /tmp/stop; wait $SPID 2>/dev/null
 python - <<PY
 import json

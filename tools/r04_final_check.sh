@@ -7,7 +7,7 @@ mkdir -p $O
 timeout 3000 python -m pytest tests -m gpu -q > $O/pytest_gpu.txt 2>&1; echo "pytest rc=$?" >> $O/pytest_gpu.txt
 tail -8 $O/pytest_gpu.txt
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -3
-( time python bench.py ) > $O/bench_default.json 2> $O/bench_default.err; tail -3 $O/bench_default.err
+( time python bench.py --full ) > $O/bench_default.json 2> $O/bench_default.err; tail -3 $O/bench_default.err
 python - <<'PY'
 import json
 d=json.loads([l for l in open("gpurun_out/r04_final_check/bench_default.json") if l.startswith("{")][-1])

@@ -9,7 +9,7 @@ for b in 32 8 4; do
   echo "== fp16 batch $b"
   for i in 1 2 3; do
     for o in 0 1; do
-      python bench.py --no-cpu-baseline --no-aux --no-secondary --min-time 1.5 --fp16 1 --batch $b --engine-opt fuse_pw=$o 2>/dev/null | python -c "
+      python bench.py --full --no-cpu-baseline --no-aux --no-secondary --min-time 1.5 --fp16 1 --batch $b --engine-opt fuse_pw=$o 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('fuse_pw=$o', d['value'], d['ms_per_step'])"
     done
   done

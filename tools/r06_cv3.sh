@@ -10,15 +10,15 @@ tail -6 $O/tests.txt
 B="--fp16 1 --no-cpu-baseline --no-aux --no-secondary --min-time 3"
 for rep in 1 2 3; do
   for fp in 1 2; do
-    timeout 300 python3 bench.py $B --engine-opt fuse_pw=$fp > $O/fp16_pw${fp}_$rep.json 2>> $O/err.txt
+    timeout 300 python3 bench.py --full $B --engine-opt fuse_pw=$fp > $O/fp16_pw${fp}_$rep.json 2>> $O/err.txt
     python3 -c "import json,sys; d=json.loads([l for l in open('$O/fp16_pw${fp}_$rep.json') if l.startswith('{')][-1]); print('fuse_pw=$fp rep $rep', d['value'], d['ms_per_step'])"
   done
 done
-timeout 300 python3 bench.py $B --layers > $O/fp16_layers.json 2> $O/fp16_layers.txt
+timeout 300 python3 bench.py --full $B --layers > $O/fp16_layers.json 2> $O/fp16_layers.txt
 grep -E "conv_12 |conv_14 |conv_42 |conv_44 |sum of" $O/fp16_layers.txt
 for b in 8 4; do
   for fp in 1 2; do
-    timeout 300 python3 bench.py $B --batch $b --engine-opt fuse_pw=$fp > $O/fp16_b${b}_pw${fp}.json 2>> $O/err.txt
+    timeout 300 python3 bench.py --full $B --batch $b --engine-opt fuse_pw=$fp > $O/fp16_b${b}_pw${fp}.json 2>> $O/err.txt
     python3 -c "import json,sys; d=json.loads([l for l in open('$O/fp16_b${b}_pw${fp}.json') if l.startswith('{')][-1]); print('batch $b fuse_pw=$fp', d['value'], d['ms_per_step'])"
   done
 done

@@ -20,12 +20,12 @@ B="--no-cpu-baseline --no-aux --no-secondary --min-time 2 --layers"
 for b in 4 8; do
   for v in base nokloop empty; do
     lib=""; [ $v != base ] && lib=$PWD/build_variants/libsi_hip_$v.so
-    SI_HIP_LIB=$lib timeout 300 python3 bench.py --batch $b $B > $O/floor_b${b}_$v.json 2> $O/floor_b${b}_$v.txt
-    SI_HIP_LIB=$lib timeout 300 python3 bench.py --batch $b --graph 1 $B > $O/floor_b${b}_${v}_graph.json 2> $O/floor_b${b}_${v}_graph.txt
+    SI_HIP_LIB=$lib timeout 300 python3 bench.py --full --batch $b $B > $O/floor_b${b}_$v.json 2> $O/floor_b${b}_$v.txt
+    SI_HIP_LIB=$lib timeout 300 python3 bench.py --full --batch $b --graph 1 $B > $O/floor_b${b}_${v}_graph.json 2> $O/floor_b${b}_${v}_graph.txt
   done
 done
 # 3
-SI_BENCH_SHARE_DEVICE=1 timeout 900 python3 bench.py --gpus 8 --gather both --steps 3 --warmup 1 --min-time 0 --max-windows 1 --no-cpu-baseline --no-aux --no-secondary > $O/bench_y256_shared_device.json 2> $O/bench_y256_shared_device.err
-SI_BENCH_FORCE_DIST=1 timeout 300 python3 bench.py --gpus 1 --gather both --steps 5 --warmup 2 --min-time 1 --no-cpu-baseline --no-aux --no-secondary > $O/bench_world1_both_b32.json 2> $O/bench_world1_both_b32.err
+SI_BENCH_SHARE_DEVICE=1 timeout 900 python3 bench.py --full --gpus 8 --gather both --steps 3 --warmup 1 --min-time 0 --max-windows 1 --no-cpu-baseline --no-aux --no-secondary > $O/bench_y256_shared_device.json 2> $O/bench_y256_shared_device.err
+SI_BENCH_FORCE_DIST=1 timeout 300 python3 bench.py --full --gpus 1 --gather both --steps 5 --warmup 2 --min-time 1 --no-cpu-baseline --no-aux --no-secondary > $O/bench_world1_both_b32.json 2> $O/bench_world1_both_b32.err
 rocm-smi --showmeminfo vram 2>/dev/null | head > $O/vram_after.txt
 tail -3 $O/busy_fp32.txt; tail -c 600 $O/bench_y256_shared_device.json; tail -5 $O/bench_y256_shared_device.err

@@ -11,7 +11,7 @@ for rep in 1 2; do for b in 0 1; do SI_HIP_LIB=$PWD/build_variants/libsi_hip_exp
 unset SI_FUSED_ONLY
 B="--no-cpu-baseline --no-aux --no-secondary --min-time 3 --fp16 1"
 for rep in 1 2 3; do
-  python3 bench.py $B > $O/fp16_$rep.json 2>/dev/null
+  python3 bench.py --full $B > $O/fp16_$rep.json 2>/dev/null
   python3 -c "import json; d=json.loads([l for l in open('$O/fp16_$rep.json') if l.startswith('{')][-1]); print('fp16 rep $rep', d['value'], d['ms_per_step'])"
 done
-python3 bench.py $B --layers > $O/l.json 2> $O/l.txt; grep -E "^conv_2 |^conv_0 |^conv_1 " $O/l.txt | cut -c1-150
+python3 bench.py --full $B --layers > $O/l.json 2> $O/l.txt; grep -E "^conv_2 |^conv_0 |^conv_1 " $O/l.txt | cut -c1-150

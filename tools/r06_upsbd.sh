@@ -5,4 +5,4 @@ cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 timeout 900 python3 -m pytest tests -m gpu -q -x -k "upsampled or upsample or fp16_graph or full_size_properties_yolov5s" 2>&1 | tail -3
 bash tools/ab_prev.sh "--fp16 1" 5
-python3 bench.py --no-cpu-baseline --no-aux --no-secondary --min-time 2 --fp16 1 --layers 2>&1 >/dev/null | grep -E "^conv_34 |^conv_40 " | cut -c1-160
+python3 bench.py --full --no-cpu-baseline --no-aux --no-secondary --min-time 2 --fp16 1 --layers 2>&1 >/dev/null | grep -E "^conv_34 |^conv_40 " | cut -c1-160

@@ -6,7 +6,7 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 REPO=$PWD
 cd /tmp
-timeout 300 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS --kernel-trace --output-format csv -d "$OUT/raw" -- python3 "$REPO/bench.py" --steps 2 --warmup 1 --min-time 0 --max-windows 1 --no-cpu-baseline --no-aux --profile-passes 1 "$@" > "$OUT/bench.json" 2> "$OUT/stderr.txt" || true
+timeout 300 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS --kernel-trace --output-format csv -d "$OUT/raw" -- python3 "$REPO/bench.py" --full --steps 2 --warmup 1 --min-time 0 --max-windows 1 --no-cpu-baseline --no-aux --profile-passes 1 "$@" > "$OUT/bench.json" 2> "$OUT/stderr.txt" || true
 cd "$REPO"
 find "$OUT/raw" -name "*counter_collection.csv" -exec cp {} "$OUT/counters.csv" \;
 rm -rf "$OUT/raw"
