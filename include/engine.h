@@ -78,6 +78,7 @@ public:
     //                          Which layers: "f32_split_policy" 1..4 (4, the default: the K-heavy dense convs, sibling-fused and wide 1x1
     //                          layers, the layers that read upsample + concat at the source, the Winograd layers, the Detect levels and
     //                          the RGB stem; lower levels are the earlier rounds' sets, kept for A/B runs).
+    //                          nn.ConvTranspose2d is not among them: it stays on its true-fp32 kernel under f32_split.
     //                          RANGE GUARD (round 6): the reference convolves any finite fp32; a value that rounds to fp16 infinity
     //                          (|x| >= 65520; in the Winograd layers a transformed value, i.e. a sum of four inputs) cannot be split.
     //                          Weights are checked at load (such a layer never leaves the fp32 kernels); activations by the split

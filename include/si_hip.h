@@ -294,6 +294,30 @@ int si_hip_conv2d_split3_yolo_f32(const SiConv2dDesc* d, const float* in, const 
                                   const SiYoloLevel* level, const float* grid_hwa2, const float* anchor_hwa2,
                                   float* detect_out, si_stream_t stream);
 
+/* ---- ConvTranspose2d ---------------------------------------------------- */
+/* nn.ConvTranspose2d with torch's semantics (no reference counterpart: SimpleInfer registers no transposed convolution):
+ *   out[n, oy, ox, oc] = act( bias[oc] + sum x[n, iy, ix, ic] * W[ic, oc, ky, kx] )  over oy = iy*sh - ph + ky*dh, ox = ix*sw - pw + kx*dw,
+ *   oh = (ih - 1)*sh - 2*ph + dh*(kh - 1) + oph + 1 (likewise ow).
+ * Gather form on v_mfma_f32_32x32x2_f32 (csrc/hip/conv_transpose.hip): every output element is computed and stored by one lane, once
+ * (no atomics, no zero-fill pass: the same bits on every run, safe in a captured graph); the sub-pixel phases of the output run as dense
+ * implicit GEMMs in one launch, and the one-tap case (kh = sh, kw = sw, no padding, dilation 1, no output padding) as ONE GEMM with a
+ * pixel-shuffle store.  NHWC fp32, pixel strides in_ld / out_ld (concat slices on either side).  groups != 1: SI_E_UNSUPPORTED; an oh / ow
+ * that disagrees with the formula, or output padding >= max(stride, dilation): SI_E_BADARG -- both before any device call. */
+typedef struct SiConvTranspose2dDesc {
+    int n, ih, iw, ic, in_ld;
+    int oh, ow, oc, out_ld;
+    int kh, kw, sh, sw, ph, pw, oph, opw, dh, dw;
+    int groups, has_bias, act;
+    float act_param; /* leaky-relu slope */
+} SiConvTranspose2dDesc;
+/* weights: the pnnx / torch attribute [ic][oc][kh][kw] re-laid on the host (no device needed) into the kernel's [kh][kw][oc][ic padded to 4] */
+size_t si_hip_conv_transpose2d_weight_elems(const SiConvTranspose2dDesc* d);
+int si_hip_conv_transpose2d_pack_weight_host(const SiConvTranspose2dDesc* d, const float* w_iohw, float* w_packed);
+int si_hip_conv_transpose2d_f32(const SiConvTranspose2dDesc* d, const float* in, const float* w_packed, const float* bias, float* out,
+                                si_stream_t stream);
+/* the kernel instantiation si_hip_conv_transpose2d_f32 launches for this problem, as rocprofv3 prints it minus the namespace */
+const char* si_hip_conv_transpose2d_kernel_name(const SiConvTranspose2dDesc* d);
+
 /* ---- Linear ------------------------------------------------------------ */
 /* y[n,out] = x[n,in] W[out,in]^T + b   (src/layer/linear.cpp:74-117) */
 int si_hip_linear_f32(const float* x, int n, int in_features, const float* w, const float* bias, int out_features,

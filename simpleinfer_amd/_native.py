@@ -57,6 +57,12 @@ class SiConv2dDesc(C.Structure):
                      ("act_param", C.c_float), ("plan", C.POINTER(SiConvPlan)), ("range_flag", C.c_void_p)]
 
 
+class SiConvTranspose2dDesc(C.Structure):
+    _fields_ = [(k, C.c_int) for k in
+                ("n", "ih", "iw", "ic", "in_ld", "oh", "ow", "oc", "out_ld", "kh", "kw", "sh", "sw", "ph", "pw", "oph", "opw", "dh", "dw",
+                 "groups", "has_bias", "act")] + [("act_param", C.c_float)]
+
+
 class SiConv2dUpsampledSource(C.Structure):
     _fields_ = [("src", C.c_void_p), ("ih", C.c_int), ("iw", C.c_int), ("c", C.c_int), ("ld", C.c_int), ("c0", C.c_int),
                 ("inv_scale_h", C.c_float), ("inv_scale_w", C.c_float)]
@@ -148,6 +154,10 @@ def hip():
         "si_hip_conv2d_upcat_supported": (i, [C.POINTER(SiConv2dDesc), C.POINTER(SiConv2dUpsampledSource)]),
         "si_hip_conv2d_kernel_name": (C.c_char_p, [C.POINTER(SiConv2dDesc), vp]),
         "si_hip_conv2d_kernel_name_form": (C.c_char_p, [C.POINTER(SiConv2dDesc), vp, i]),
+        "si_hip_conv_transpose2d_weight_elems": (sz, [C.POINTER(SiConvTranspose2dDesc)]),
+        "si_hip_conv_transpose2d_pack_weight_host": (i, [C.POINTER(SiConvTranspose2dDesc), vp, vp]),
+        "si_hip_conv_transpose2d_f32": (i, [C.POINTER(SiConvTranspose2dDesc), vp, vp, vp, vp, vp]),
+        "si_hip_conv_transpose2d_kernel_name": (C.c_char_p, [C.POINTER(SiConvTranspose2dDesc)]),
         "si_hip_linear_f32": (i, [vp, i, i, vp, vp, i, vp, vp]),
         "si_hip_maxpool2d_f32": (i, [C.POINTER(SiPool2dDesc), vp, vp, vp]),
         "si_hip_adaptive_avgpool2d_f32": (i, [vp, i, i, i, i, i, vp, i, i, i, vp]),

@@ -8,6 +8,7 @@
 #include "layer/binary_op.h"
 #include "layer/cat.h"
 #include "layer/conv_2d.h"
+#include "layer/conv_transpose_2d.h"
 #include "layer/linear.h"
 #include "layer/max_pool_2d.h"
 #include "layer/output_cast.h"
@@ -24,7 +25,7 @@ namespace {
 // built-in operator types whose kernels honour a pixel stride on inputs and outputs
 bool HonoursPixelStride(const std::string& type) {
     static const std::set<std::string> ok = {
-        "nn.Conv2d", "nn.SiLU", "nn.ReLU", "nn.Sigmoid", "nn.Hardsigmoid", "nn.Hardswish", "nn.LeakyReLU",
+        "nn.Conv2d", "nn.ConvTranspose2d", "nn.SiLU", "nn.ReLU", "nn.Sigmoid", "nn.Hardsigmoid", "nn.Hardswish", "nn.LeakyReLU",
         "nn.MaxPool2d", "nn.AdaptiveAvgPool2d", "nn.Upsample", "torch.cat", "BinaryOp", "UnaryOp", "nn.BatchNorm2d",
         "torch.flatten", "models.yolo.Detect", "pnnx.Output"};
     return ok.count(type) > 0;
@@ -523,6 +524,20 @@ Status EngineImpl::FuseEpilogues(std::vector<Step>& order) {
 
     for (size_t i = 0; i < order.size(); ++i) {
         if (removed[i]) continue;
+        // transposed conv -> act  ==>  one launch (its epilogue has the activation only: a residual add stays a launch of its own)
+        if (ConvTranspose2d* ct = dynamic_cast<ConvTranspose2d*>(order[i].layer)) {
+            if (order[i].op->type != "nn.ConvTranspose2d" || order[i].op->outputs.size() != 1) continue;
+            const pnnx::Operand* out = order[i].op->outputs[0];
+            const pnnx::Operator* c = sole_consumer(out);
+            ActivationLayer* a = c ? dynamic_cast<ActivationLayer*>(order[index[c]].layer) : nullptr;
+            if (!a || c->inputs.size() != 1 || c->outputs.size() != 1) continue;
+            ct->SetFusion(a->ActCode(), a->ActCode() == SI_ACT_LEAKYRELU ? a->ActParam() : 0.0f);
+            ct->SetOutputNodes({tensor_nodes_[c->outputs[0]->name]});
+            removed[index[c]] = true;   // (the activation reads nothing else: the fused launch keeps the conv's slot)
+            fused_ops_.insert(c->name);
+            dead_operands_.insert(out->name);
+            continue;
+        }
         Conv2d* conv = dynamic_cast<Conv2d*>(order[i].layer);
         if (!conv || order[i].op->type != "nn.Conv2d" || order[i].op->outputs.size() != 1) continue;
 

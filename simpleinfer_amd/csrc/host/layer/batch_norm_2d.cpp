@@ -42,7 +42,8 @@ Status BatchNorm2d::Deinit() {
 Status BatchNorm2d::Validate() {
     CHECK_STATUS(Layer::Validate());
     CHECK_STATUS(ValidateShape(1, 1));
-    if (Status::kSuccess != ValidateFloat32()) {
+    // fp16 storage: accepted here so that the engine can run the layer in fp32 between casts (HalfStorageOk says it has no fp16 kernel)
+    if (Status::kSuccess != ValidateFloat()) {
         LOG(ERROR) << "BatchNorm2d::Validate fail [unsupport input/output data type]";
         return Status::kUnsupport;
     }
@@ -70,6 +71,7 @@ Status BatchNorm2d::PrepareDevice() {
 
 Status BatchNorm2d::Forward(const Tensor& input, Tensor& output) {
     return RunOnDevice({&input}, {&output}, [this](const std::vector<Tensor>& in, std::vector<Tensor>& out) {
+        if (IsHalf(in[0]) || IsHalf(out[0])) return Status::kUnsupport;   // (fp32 kernel only, see Validate)
         CHECK_STATUS(PrepareDevice());
         size_t pixels = 0;
         int c = 0;

@@ -14,6 +14,7 @@ SI_DECLARE_LAYER(BatchNorm2d)
 SI_DECLARE_LAYER(BinaryOp)
 SI_DECLARE_LAYER(Cat)
 SI_DECLARE_LAYER(Conv2d)
+SI_DECLARE_LAYER(ConvTranspose2d)
 SI_DECLARE_LAYER(Flatten)
 SI_DECLARE_LAYER(HardSigmoid)
 SI_DECLARE_LAYER(HardSwish)
@@ -32,13 +33,14 @@ SI_DECLARE_LAYER(YoloDetect)
 
 static std::map<std::string, LayerRegistryEntry>& Table() {
     // the 15 type strings of reference src/layer_registry.cpp:33-49, plus nn.LeakyReLU
-    // (north_star extension)
+    // (north_star extension) and nn.ConvTranspose2d (U-Net / segmentation decoders; no reference layer)
     static std::map<std::string, LayerRegistryEntry> table = {
         SI_ENTRY("nn.AdaptiveAvgPool2d", AdaptiveAvgPool2d),
         SI_ENTRY("nn.BatchNorm2d", BatchNorm2d),
         SI_ENTRY("BinaryOp", BinaryOp),
         SI_ENTRY("torch.cat", Cat),
         SI_ENTRY("nn.Conv2d", Conv2d),
+        SI_ENTRY("nn.ConvTranspose2d", ConvTranspose2d),
         SI_ENTRY("torch.flatten", Flatten),
         SI_ENTRY("nn.Hardsigmoid", HardSigmoid),
         SI_ENTRY("nn.Hardswish", HardSwish),

@@ -163,6 +163,71 @@ def conv2d(x, w_oihw, bias=None, stride=(1, 1), padding=(0, 0), dilation=(1, 1),
     return y[..., out_c_off:out_c_off + oc].copy() if out_ld != oc else y
 
 
+def conv_transpose_out_hw(ih, iw, k, s, p, op, d):
+    """torch's output size of a transposed convolution"""
+    return ((ih - 1) * s[0] - 2 * p[0] + d[0] * (k[0] - 1) + op[0] + 1,
+            (iw - 1) * s[1] - 2 * p[1] + d[1] * (k[1] - 1) + op[1] + 1)
+
+
+def conv_transpose2d_desc(x_shape, w_shape, bias=True, stride=(1, 1), padding=(0, 0), output_padding=(0, 0), dilation=(1, 1),
+                          act1="none", act_param=0.0, in_ld=None, out_ld=None, groups=1):
+    """SiConvTranspose2dDesc for an NHWC input of x_shape and a torch weight of w_shape [Cin][Cout/groups][kh][kw]"""
+    n, ih, iw, ic = x_shape
+    _, ocg, kh, kw = w_shape
+    oc = ocg * groups
+    oh, ow = conv_transpose_out_hw(ih, iw, (kh, kw), stride, padding, output_padding, dilation)
+    return _native.SiConvTranspose2dDesc(n, ih, iw, ic, in_ld or ic, oh, ow, oc, out_ld or oc, kh, kw, stride[0], stride[1], padding[0],
+                                         padding[1], output_padding[0], output_padding[1], dilation[0], dilation[1], groups,
+                                         1 if bias else 0, ACT[act1], float(act_param))
+
+
+def conv_transpose2d_pack(d, w_iohw) -> np.ndarray:
+    """the kernel's weight image of a torch [Cin][Cout][kh][kw] weight (host only)"""
+    H = _native.hip()
+    w_iohw = _f32(w_iohw)
+    packed = np.zeros(H.si_hip_conv_transpose2d_weight_elems(C.byref(d)), np.float32)
+    _chk(H.si_hip_conv_transpose2d_pack_weight_host(C.byref(d), w_iohw.ctypes.data_as(C.c_void_p), packed.ctypes.data_as(C.c_void_p)),
+         "pack transposed-conv weight")
+    return packed
+
+
+def conv_transpose2d(x_nhwc, w_iohw, bias=None, stride=(1, 1), padding=(0, 0), output_padding=(0, 0), dilation=(1, 1), act1="none",
+                     act_param=0.0, in_ld: Optional[int] = None, out_ld: Optional[int] = None, out_c_off: int = 0, in_fill: float = 0.0,
+                     out_fill: float = 0.0, full: bool = False):
+    """si_hip_conv_transpose2d_f32 (nn.ConvTranspose2d, groups = 1; w_iohw in torch's [Cin][Cout][kh][kw] layout).  As conv2d:
+    in_ld > Cin embeds the input in a wider buffer whose other channels hold in_fill; out_ld > Cout writes channels
+    [out_c_off, out_c_off + Cout) of a wider output buffer pre-filled with out_fill.  full=True returns that whole buffer."""
+    H = _native.hip()
+    x, w_iohw = _f32(x_nhwc), _f32(w_iohw)
+    n, ih, iw, ic = x.shape
+    assert w_iohw.shape[0] == ic, (x.shape, w_iohw.shape)
+    oc = w_iohw.shape[1]
+    in_ld = in_ld or ic
+    out_ld = out_ld or oc
+    assert out_c_off >= 0 and out_c_off + oc <= out_ld, (out_c_off, oc, out_ld)
+    d = conv_transpose2d_desc(x.shape, w_iohw.shape, bias is not None, stride, padding, output_padding, dilation, act1, act_param, in_ld, out_ld)
+    packed = conv_transpose2d_pack(d, w_iohw)
+    if in_ld != ic:
+        xw = np.full((n, ih, iw, in_ld), in_fill, np.float32)
+        xw[..., :ic] = x
+        x = xw
+    oh, ow = d.oh, d.ow
+    dx, dw = DeviceBuffer.from_numpy(x), DeviceBuffer.from_numpy(packed)
+    db = DeviceBuffer.from_numpy(_f32(bias)) if bias is not None else None
+    dy = DeviceBuffer.from_numpy(np.full((n, oh, ow, out_ld), out_fill, np.float32))
+    _chk(H.si_hip_conv_transpose2d_f32(C.byref(d), dx.ptr, dw.ptr, db.ptr if db else None, dy.ptr + 4 * out_c_off, None),
+         "si_hip_conv_transpose2d_f32")
+    y = dy.to_numpy((n, oh, ow, out_ld))
+    if full or out_ld == oc:
+        return y
+    return y[..., out_c_off:out_c_off + oc].copy()
+
+
+def conv_transpose2d_kernel_name(x_shape, w_shape, stride=(1, 1), padding=(0, 0), output_padding=(0, 0), dilation=(1, 1)) -> str:
+    d = conv_transpose2d_desc(x_shape, w_shape, True, stride, padding, output_padding, dilation)
+    return _native.hip().si_hip_conv_transpose2d_kernel_name(C.byref(d)).decode()
+
+
 def _range_flag(d, want):
     """a zeroed device word handed to an f32_split launch as SiConv2dDesc::range_flag (the kernel writes 1 when an operand left fp16's range)"""
     if not want:

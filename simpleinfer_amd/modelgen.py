@@ -150,6 +150,26 @@ class PnnxBuilder:
                         padding_mode="zeros", stride=(sh, sw)), attrs)
         return out
 
+    def conv_transpose(self, x: str, cout: int, k, s=1, p=0, output_padding=0, d=1, bias: bool = True,
+                       name: str = None) -> str:
+        """pnnx's nn.ConvTranspose2d line; weight [Cin][Cout][kh][kw] (torch's layout), groups 1"""
+        n, cin, h, w = self.shapes[x]
+        pair = lambda v: (v, v) if isinstance(v, int) else tuple(v)
+        (kh, kw), (sh, sw), (ph, pw), (oph, opw), (dh, dw) = pair(k), pair(s), pair(p), pair(output_padding), pair(d)
+        oh = (h - 1) * sh - 2 * ph + dh * (kh - 1) + oph + 1
+        ow = (w - 1) * sw - 2 * pw + dw * (kw - 1) + opw + 1
+        name = name or self._opname("convtranspose")
+        a = math.sqrt(3.0 / (cin * kh * kw))
+        attrs = {"weight": seeded_uniform(name + ".weight", (cin, cout, kh, kw), -a, a, self.seed)}
+        if bias:
+            attrs["bias"] = seeded_uniform(name + ".bias", (cout,), -0.1, 0.1, self.seed)
+        out = self._new_operand((n, cout, oh, ow))
+        self._emit("nn.ConvTranspose2d", name, [x], [out],
+                   dict(bias=bool(bias), dilation=(dh, dw), groups=1, in_channels=cin, kernel_size=(kh, kw),
+                        out_channels=cout, output_padding=(oph, opw), padding=(ph, pw), padding_mode="zeros",
+                        stride=(sh, sw)), attrs)
+        return out
+
     def _unary(self, typ: str, prefix: str, x: str, params=None) -> str:
         out = self._new_operand(self.shapes[x])
         self._emit(typ, self._opname(prefix), [x], [out], params or {})
@@ -383,6 +403,34 @@ def build_toy_classifier(batch: int = 2, size: int = 32, seed: int = 0) -> PnnxB
     x = b.adaptive_avgpool(x, (1, 1))
     x = b.flatten(x)
     x = b.linear(x, 10)
+    b.output(x)
+    return b
+
+
+def build_toy_unet(batch: int = 2, size: int = 64, base: int = 16, depth: int = 3, ncls: int = 4, seed: int = 0) -> PnnxBuilder:
+    """A small U-Net: per encoder level two [conv3x3 -> BatchNorm2d -> ReLU] then MaxPool2d(2, 2); the same block as bottleneck;
+    per decoder level an up-conv, torch.cat([skip, up]) and two blocks; a 1x1 conv head.  The up-convs alternate k2 s2 p0 (one
+    tap per output pixel) and k3 s2 p1 output_padding 1 (four sub-pixel phases of 4 / 2 / 2 / 1 taps)."""
+    b = PnnxBuilder(seed)
+    x = b.input((batch, 3, size, size))
+
+    def block(x, c):
+        for _ in range(2):
+            x = b.relu(b.batchnorm(b.conv(x, c, 3, 1, 1)))
+        return x
+
+    skips, c = [], base
+    for _ in range(depth):
+        x = block(x, c)
+        skips.append(x)
+        x = b.maxpool(x, 2, 2, 0)
+        c *= 2
+    x = block(x, c)
+    for i, skip in enumerate(reversed(skips)):
+        c //= 2
+        up = b.conv_transpose(x, c, 2, 2, 0) if i % 2 == 0 else b.conv_transpose(x, c, 3, 2, 1, output_padding=1)
+        x = block(b.cat([skip, up]), c)
+    x = b.conv(x, ncls, 1, 1, 0)
     b.output(x)
     return b
 
