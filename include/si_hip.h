@@ -337,6 +337,46 @@ int si_hip_adaptive_avgpool2d_f32(const float* in, int n, int ih, int iw, int c,
 /* nearest: src = clamp((int)((float)dst * (1.0f/scale)))   (src/layer/upsample.cpp:76-99,164-165) */
 int si_hip_upsample_nearest_f32(const float* in, int n, int ih, int iw, int c, int in_ld, float scale_h,
                                 float scale_w, float* out, int oh, int ow, int out_ld, si_stream_t stream);
+/* ... with the source steps given instead of scale factors (nn.Upsample / F.interpolate with size=, torch's rule:
+ * step = (float)in / (float)out from si_upsample_step): src = min((int)((float)dst * step), in - 1).  Same kernel. */
+int si_hip_upsample_nearest_steps_f32(const float* in, int n, int ih, int iw, int c, int in_ld, float step_h,
+                                      float step_w, float* out, int oh, int ow, int out_ld, si_stream_t stream);
+
+/* ---- bilinear upsample and the segmentation label map (csrc/hip/upsample_bilinear.hip; no reference counterpart: its
+ * upsample.cpp is nearest only) ------------------------------------------------------------------------------------
+ * torch.nn.functional.interpolate(mode="bilinear") on NHWC tensors.  Per axis, with `in` source and `out` destination
+ * samples and a float32 step s formed on the host (si_upsample_step):
+ *   align_corners:      s = out > 1 ? (float)(in - 1) / (float)(out - 1) : 0          src = s * (float)d
+ *   otherwise:          s = (float)(1.0 / scale_factor) when a scale factor is given  src = max(0, fmaf(s, (float)d + 0.5f, -0.5f))
+ *                       (and not recomputed), else (float)in / (float)out
+ *   nearest by size:    s = (float)in / (float)out                                    index min((int)((float)d * s), in - 1)
+ *   i0 = min((int)src, in - 1), i1 = i0 + (i0 < in - 1), l1 = src - (float)i0, l0 = 1 - l1
+ *   out = l0h * (l0w * v00 + l1w * v01) + l1h * (l0w * v10 + l1w * v11)   in fp32, one rounding at an fp16 store (nearest-even)
+ * The coordinate is an explicit fused multiply-add on the device.  Pixel strides in_ld / out_ld >= c on both sides; channels
+ * outside the view are never touched.  16 bytes per lane where c, both strides and both pointers allow it, narrower vectors or
+ * scalars otherwise (any c).  Non-positive sizes, ld < c, a step that is not finite and >= 0: SI_E_BADARG; a tensor whose element
+ * offsets do not fit 31 bits: SI_E_UNSUPPORTED -- both before any device call. */
+#define SI_UPSAMPLE_NEAREST 0
+#define SI_UPSAMPLE_BILINEAR 1
+typedef struct SiUpsampleDesc {
+    int n, ih, iw, c, in_ld;
+    int oh, ow, out_ld;
+    int align_corners;
+    float step_h, step_w;
+} SiUpsampleDesc;
+/* host half of the rule (no device): the step of one axis; scale_factor = 0: not given (or recompute_scale_factor=True).
+ * mode SI_UPSAMPLE_NEAREST with align_corners: SI_E_BADARG, as torch */
+int si_upsample_step(int mode, int in, int out, int align_corners, double scale_factor, float* step);
+/* floor((double)in * scale_factor): the output size torch derives from a scale factor; < 0: SI_E_BADARG */
+int si_upsample_out_size(int in, double scale_factor);
+int si_hip_upsample_bilinear_f32(const SiUpsampleDesc* d, const float* in, float* out, si_stream_t stream);
+int si_hip_upsample_bilinear_f16(const SiUpsampleDesc* d, const void* in, void* out, si_stream_t stream);
+/* the instantiation the call above launches for these operands (the pointers' alignment picks the vector width) */
+const char* si_hip_upsample_bilinear_kernel_name(const SiUpsampleDesc* d, const void* in, const void* out, int half);
+/* labels[n][y][x] = argmax_c of the bilinear upsample of logits [n][ih][iw][c] (pixel stride in_ld; out_ld is ignored), uint8,
+ * lowest class on an exact tie; same rule and blend as above, the upsampled logits are never written.  c > 256: SI_E_UNSUPPORTED */
+int si_hip_segment_labels_f32(const SiUpsampleDesc* d, const float* logits, unsigned char* labels, si_stream_t stream);
+int si_hip_segment_labels_f16(const SiUpsampleDesc* d, const void* logits, unsigned char* labels, si_stream_t stream);
 
 /* ---- data movement ----------------------------------------------------- */
 /* strided channel-slice copy: out[p*out_ld + i] = in[p*in_ld + i], i < c  -- one slice-assign of

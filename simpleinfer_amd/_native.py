@@ -63,6 +63,11 @@ class SiConvTranspose2dDesc(C.Structure):
                  "groups", "has_bias", "act")] + [("act_param", C.c_float)]
 
 
+class SiUpsampleDesc(C.Structure):
+    _fields_ = [(k, C.c_int) for k in ("n", "ih", "iw", "c", "in_ld", "oh", "ow", "out_ld", "align_corners")] + [
+        ("step_h", C.c_float), ("step_w", C.c_float)]
+
+
 class SiConv2dUpsampledSource(C.Structure):
     _fields_ = [("src", C.c_void_p), ("ih", C.c_int), ("iw", C.c_int), ("c", C.c_int), ("ld", C.c_int), ("c0", C.c_int),
                 ("inv_scale_h", C.c_float), ("inv_scale_w", C.c_float)]
@@ -162,6 +167,14 @@ def hip():
         "si_hip_maxpool2d_f32": (i, [C.POINTER(SiPool2dDesc), vp, vp, vp]),
         "si_hip_adaptive_avgpool2d_f32": (i, [vp, i, i, i, i, i, vp, i, i, i, vp]),
         "si_hip_upsample_nearest_f32": (i, [vp, i, i, i, i, i, f, f, vp, i, i, i, vp]),
+        "si_hip_upsample_nearest_steps_f32": (i, [vp, i, i, i, i, i, f, f, vp, i, i, i, vp]),
+        "si_upsample_step": (i, [i, i, i, i, C.c_double, C.POINTER(C.c_float)]),
+        "si_upsample_out_size": (i, [i, C.c_double]),
+        "si_hip_upsample_bilinear_f32": (i, [C.POINTER(SiUpsampleDesc), vp, vp, vp]),
+        "si_hip_upsample_bilinear_f16": (i, [C.POINTER(SiUpsampleDesc), vp, vp, vp]),
+        "si_hip_upsample_bilinear_kernel_name": (C.c_char_p, [C.POINTER(SiUpsampleDesc), vp, vp, i]),
+        "si_hip_segment_labels_f32": (i, [C.POINTER(SiUpsampleDesc), vp, vp, vp]),
+        "si_hip_segment_labels_f16": (i, [C.POINTER(SiUpsampleDesc), vp, vp, vp]),
         "si_hip_copy_channels_f32": (i, [vp, sz, i, i, vp, i, vp]),
         "si_hip_cat_axis_f32": (i, [vp, ip, vp, ip, i, i, vp]),
         "si_hip_nhwc_to_nchw_f32": (i, [vp, i, i, i, i, i, vp, vp]),

@@ -557,6 +557,29 @@ int si_hip_upsample_nearest_f32(const float* in, int n, int ih, int iw, int c, i
     return (int)hipGetLastError();
 }
 
+int si_hip_upsample_nearest_steps_f32(const float* in, int n, int ih, int iw, int c, int in_ld, float step_h, float step_w,
+                                      float* out, int oh, int ow, int out_ld, si_stream_t stream) {
+    if (!in || !out || n <= 0 || ih <= 0 || iw <= 0 || c <= 0 || oh <= 0 || ow <= 0 || in_ld < c || out_ld < c) return SI_E_BADARG;
+    if (!(step_h >= 0.f) || !(step_w >= 0.f) || step_h > FLT_MAX || step_w > FLT_MAX) return SI_E_BADARG;
+    // as the bilinear entries: element offsets must fit 31 bits (the kernel indexes pixels in int).  A step beyond the source
+    // extent only ever clamps, so it is cut there; then dst * step < out * in, which must stay inside int before the clamp
+    if ((unsigned long long)n * ih * iw * (unsigned long long)in_ld > 0x7fffffffull ||
+        (unsigned long long)n * oh * ow * (unsigned long long)out_ld > 0x7fffffffull ||
+        (unsigned long long)oh * ih > 0x7fffffffull || (unsigned long long)ow * iw > 0x7fffffffull)
+        return SI_E_UNSUPPORTED;
+    step_h = fminf(step_h, (float)ih);
+    step_w = fminf(step_w, (float)iw);
+    const bool vec = (c % 4 == 0) && (in_ld % 4 == 0) && (out_ld % 4 == 0) && aligned16(in) && aligned16(out);
+    const size_t px = (size_t)n * oh * ow;
+    if (vec)
+        hipLaunchKernelGGL(upsample_kernel<true>, dim3(si_grid_for(px * (c / 4))), dim3(256), 0, (hipStream_t)stream, in,
+                           n, ih, iw, c, in_ld, step_h, step_w, out, oh, ow, out_ld);
+    else
+        hipLaunchKernelGGL(upsample_kernel<false>, dim3(si_grid_for(px * c)), dim3(256), 0, (hipStream_t)stream, in, n,
+                           ih, iw, c, in_ld, step_h, step_w, out, oh, ow, out_ld);
+    return (int)hipGetLastError();
+}
+
 int si_hip_copy_channels_f32(const float* in, size_t pixels, int c, int in_ld, float* out, int out_ld,
                              si_stream_t stream) {
     if (!in || !out || c <= 0) return SI_E_BADARG;

@@ -26,7 +26,7 @@ namespace {
 bool HonoursPixelStride(const std::string& type) {
     static const std::set<std::string> ok = {
         "nn.Conv2d", "nn.ConvTranspose2d", "nn.SiLU", "nn.ReLU", "nn.Sigmoid", "nn.Hardsigmoid", "nn.Hardswish", "nn.LeakyReLU",
-        "nn.MaxPool2d", "nn.AdaptiveAvgPool2d", "nn.Upsample", "torch.cat", "BinaryOp", "UnaryOp", "nn.BatchNorm2d",
+        "nn.MaxPool2d", "nn.AdaptiveAvgPool2d", "nn.Upsample", "F.interpolate", "F.upsample", "torch.cat", "BinaryOp", "UnaryOp", "nn.BatchNorm2d",
         "torch.flatten", "models.yolo.Detect", "pnnx.Output"};
     return ok.count(type) > 0;
 }
@@ -690,6 +690,7 @@ Status EngineImpl::FuseUpsampleIntoConvs(std::vector<Step>& order) {
     for (size_t i = 0; i < order.size(); ++i) {
         Upsample* up = dynamic_cast<Upsample*>(order[i].layer);
         if (!up || order[i].op->type != "nn.Upsample" || up->InputNodes().size() != 1 || up->OutputNodes().size() != 1) continue;
+        if (!up->IsNearestByScale()) continue;   // (bilinear, size=: the dual-source conv kernels implement the nearest-by-scale index rule only)
         const pnnx::Operand* u = up->OutputNodes()[0]->operand;
         if (!u || u->consumers.size() != 1 || output_tensor_nodes_.count(u->name)) continue;
         const pnnx::Operator* cat = u->consumers[0];

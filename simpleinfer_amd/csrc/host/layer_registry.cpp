@@ -33,7 +33,8 @@ SI_DECLARE_LAYER(YoloDetect)
 
 static std::map<std::string, LayerRegistryEntry>& Table() {
     // the 15 type strings of reference src/layer_registry.cpp:33-49, plus nn.LeakyReLU
-    // (north_star extension) and nn.ConvTranspose2d (U-Net / segmentation decoders; no reference layer)
+    // (north_star extension) nn.ConvTranspose2d (U-Net / segmentation decoders; no reference layer)
+    // and F.interpolate / F.upsample, the functional spellings of nn.Upsample
     static std::map<std::string, LayerRegistryEntry> table = {
         SI_ENTRY("nn.AdaptiveAvgPool2d", AdaptiveAvgPool2d),
         SI_ENTRY("nn.BatchNorm2d", BatchNorm2d),
@@ -52,6 +53,8 @@ static std::map<std::string, LayerRegistryEntry>& Table() {
         SI_ENTRY("nn.SiLU", SiLU),
         SI_ENTRY("UnaryOp", UnaryOp),   // emitted by expand_expression, never registered by the reference
         SI_ENTRY("nn.Upsample", Upsample),
+        SI_ENTRY("F.interpolate", Upsample),
+        SI_ENTRY("F.upsample", Upsample),
         SI_ENTRY("models.yolo.Detect", YoloDetect),
     };
     return table;

@@ -531,6 +531,111 @@ def upsample_nearest(x, scale_h, scale_w, out_hw=None):
     return dy.to_numpy((n, oh, ow, c))
 
 
+UPSAMPLE_MODE = {"nearest": 0, "bilinear": 1}
+
+
+def upsample_out_hw(ih, iw, scale):
+    """torch's output size of a scale factor: floor((double)in * scale) per axis (si_upsample_out_size, host only)"""
+    H = _native.hip()
+    sh, sw = (scale, scale) if np.isscalar(scale) else scale
+    oh, ow = H.si_upsample_out_size(ih, float(sh)), H.si_upsample_out_size(iw, float(sw))
+    if oh <= 0 or ow <= 0:
+        raise ValueError("upsample: scale factor %r on %dx%d" % (scale, ih, iw))
+    return oh, ow
+
+
+def upsample_step(mode, n_in, n_out, align_corners=False, scale=None) -> np.float32:
+    """the float32 source step of one axis (si_upsample_step, host only); scale None: not given, or recompute_scale_factor=True"""
+    st = C.c_float()
+    rc = _native.hip().si_upsample_step(UPSAMPLE_MODE[mode], n_in, n_out, 1 if align_corners else 0, float(scale or 0.0), C.byref(st))
+    if rc != 0:
+        raise ValueError("si_upsample_step(%s, %d, %d, align_corners=%s, scale=%r): code %d" % (mode, n_in, n_out, align_corners, scale, rc))
+    return np.float32(st.value)
+
+
+def upsample_desc(x_shape, out_hw=None, scale=None, align_corners=False, mode="bilinear", in_ld=None, out_ld=None):
+    """SiUpsampleDesc of an NHWC input: out_hw (size=) or scale (scale_factor=, a number or a pair), exactly one of them"""
+    assert (out_hw is None) != (scale is None), "give out_hw or scale"
+    n, ih, iw, c = x_shape
+    if scale is not None:
+        sh, sw = (scale, scale) if np.isscalar(scale) else scale
+        oh, ow = upsample_out_hw(ih, iw, (sh, sw))
+    else:
+        sh = sw = None
+        oh, ow = out_hw
+    return _native.SiUpsampleDesc(n, ih, iw, c, in_ld or c, oh, ow, out_ld or c, 1 if align_corners else 0,
+                                  upsample_step(mode, ih, oh, align_corners, sh), upsample_step(mode, iw, ow, align_corners, sw))
+
+
+def _embed(x, ld, fill):
+    """x's channels at the front of a buffer of pixel stride ld whose other channels hold `fill`"""
+    if ld == x.shape[-1]:
+        return x
+    w = np.full(x.shape[:-1] + (ld,), fill, x.dtype)
+    w[..., :x.shape[-1]] = x
+    return w
+
+
+def _float_storage(x):
+    x = np.asarray(x)
+    return np.ascontiguousarray(x) if x.dtype == np.float16 else _f32(x)
+
+
+def upsample_bilinear(x, out_hw=None, scale=None, align_corners=False, in_ld: Optional[int] = None, in_fill: float = 0.0,
+                      out_ld: Optional[int] = None, out_c_off: int = 0, out_fill: float = 0.0, full: bool = False):
+    """si_hip_upsample_bilinear_f32 / _f16 (by the array's dtype) on an NHWC array; out_hw = torch's size=, scale = its
+    scale_factor= (recompute_scale_factor=True is out_hw=upsample_out_hw(...)).  The strided-view hooks are conv_transpose2d's."""
+    H = _native.hip()
+    x = _float_storage(x)
+    half = x.dtype == np.float16
+    n, ih, iw, c = x.shape
+    in_ld, out_ld = in_ld or c, out_ld or c
+    assert out_c_off >= 0 and out_c_off + c <= out_ld, (out_c_off, c, out_ld)
+    d = upsample_desc(x.shape, out_hw, scale, align_corners, "bilinear", in_ld, out_ld)
+    dx = DeviceBuffer.from_numpy(_embed(x, in_ld, in_fill))
+    dy = DeviceBuffer.from_numpy(np.full((n, d.oh, d.ow, out_ld), out_fill, x.dtype))
+    fn = H.si_hip_upsample_bilinear_f16 if half else H.si_hip_upsample_bilinear_f32
+    _chk(fn(C.byref(d), dx.ptr, dy.ptr + x.itemsize * out_c_off, None), "si_hip_upsample_bilinear")
+    y = dy.to_numpy((n, d.oh, d.ow, out_ld), x.dtype)
+    if full or out_ld == c:
+        return y
+    return y[..., out_c_off:out_c_off + c].copy()
+
+
+def upsample_bilinear_kernel_name(x_shape, out_hw=None, scale=None, half=False, in_ld=None, out_ld=None) -> str:
+    """the instantiation for 16-byte aligned buffers of these shapes"""
+    d = upsample_desc(x_shape, out_hw, scale, False, "bilinear", in_ld, out_ld)
+    return _native.hip().si_hip_upsample_bilinear_kernel_name(C.byref(d), C.c_void_p(256), C.c_void_p(256), 1 if half else 0).decode()
+
+
+def upsample_nearest_size(x, out_hw, in_ld: Optional[int] = None, in_fill: float = 0.0):
+    """si_hip_upsample_nearest_steps_f32 with the steps of size= (torch's nearest rule)"""
+    H = _native.hip()
+    x = _f32(x)
+    n, ih, iw, c = x.shape
+    in_ld = in_ld or c
+    d = upsample_desc(x.shape, out_hw, None, False, "nearest", in_ld)
+    dx, dy = DeviceBuffer.from_numpy(_embed(x, in_ld, in_fill)), DeviceBuffer(n * d.oh * d.ow * c * 4)
+    _chk(H.si_hip_upsample_nearest_steps_f32(dx.ptr, n, ih, iw, c, in_ld, d.step_h, d.step_w, dy.ptr, d.oh, d.ow, c, None),
+         "si_hip_upsample_nearest_steps_f32")
+    return dy.to_numpy((n, d.oh, d.ow, c))
+
+
+def segment_labels(logits, out_hw, align_corners=False, in_ld: Optional[int] = None, in_fill: float = 0.0):
+    """si_hip_segment_labels_f32 / _f16: uint8 [N, oh, ow] argmax over classes of the bilinear upsample of NHWC logits (the
+    upsampled logits are never written)"""
+    H = _native.hip()
+    x = _float_storage(logits)
+    n, ih, iw, c = x.shape
+    in_ld = in_ld or c
+    d = upsample_desc(x.shape, out_hw, None, align_corners, "bilinear", in_ld, 1)
+    dx = DeviceBuffer.from_numpy(_embed(x, in_ld, in_fill))
+    dy = DeviceBuffer(n * d.oh * d.ow)
+    fn = H.si_hip_segment_labels_f16 if x.dtype == np.float16 else H.si_hip_segment_labels_f32
+    _chk(fn(C.byref(d), dx.ptr, dy.ptr, None), "si_hip_segment_labels")
+    return dy.to_numpy((n, d.oh, d.ow), np.uint8)
+
+
 def cat(xs, axis):
     H = _native.hip()
     xs = [_f32(x) for x in xs]

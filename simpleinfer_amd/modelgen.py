@@ -198,11 +198,55 @@ class PnnxBuilder:
                    dict(output_size=(int(out_hw[0]), int(out_hw[1]))))
         return out
 
-    def upsample(self, x: str, scale: float = 2.0) -> str:
+    def _resized(self, x: str, scale, size):
+        """output operand of a resize: size=(h, w), or torch's floor(in * scale_factor)"""
         n, c, h, w = self.shapes[x]
-        out = self._new_operand((n, c, int(h * scale), int(w * scale)))
-        self._emit("nn.Upsample", self._opname("upsample"), [x], [out],
-                   dict(mode="nearest", scale_factor=(float(scale), float(scale)), size="None"))
+        if size is not None:
+            return self._new_operand((n, c, int(size[0]), int(size[1])))
+        sh, sw = (scale, scale) if isinstance(scale, (int, float)) else scale
+        return self._new_operand((n, c, int(math.floor(h * float(sh))), int(math.floor(w * float(sw)))))
+
+    def upsample(self, x: str, scale: float = 2.0, mode: str = "nearest", align_corners=None, size=None) -> str:
+        """pnnx's nn.Upsample line.  size=(h, w) replaces the scale factor (scale_factor=None in the file); align_corners is
+        written for the modes that have it (pnnx omits it for nearest)."""
+        if mode == "nearest" and align_corners is None and size is None:
+            n, c, h, w = self.shapes[x]
+            out = self._new_operand((n, c, int(h * scale), int(w * scale)))
+            self._emit("nn.Upsample", self._opname("upsample"), [x], [out],
+                       dict(mode="nearest", scale_factor=(float(scale), float(scale)), size="None"))
+            return out
+        out = self._resized(x, scale, size)
+        params = {}
+        if mode != "nearest" or align_corners is not None:
+            params["align_corners"] = "None" if align_corners is None else bool(align_corners)
+        params["mode"] = mode
+        if size is not None:
+            params.update(scale_factor="None", size=(int(size[0]), int(size[1])))
+        else:
+            sh, sw = (scale, scale) if isinstance(scale, (int, float)) else scale
+            params.update(scale_factor=(float(sh), float(sw)), size="None")
+        self._emit("nn.Upsample", self._opname("upsample"), [x], [out], params)
+        return out
+
+    def interpolate(self, x: str, scale=None, mode: str = "nearest", align_corners=None, size=None, recompute_scale_factor=None,
+                    functional: str = "F.interpolate") -> str:
+        """pnnx's F.interpolate line (functional="F.upsample": the older spelling, which has no recompute_scale_factor)"""
+        assert (scale is None) != (size is None), "give scale or size"
+        if recompute_scale_factor and scale is not None:
+            n, c, h, w = self.shapes[x]
+            sh, sw = (scale, scale) if isinstance(scale, (int, float)) else scale
+            out = self._new_operand((n, c, int(math.floor(h * float(sh))), int(math.floor(w * float(sw)))))
+        else:
+            out = self._resized(x, scale, size)
+        params = dict(align_corners="None" if align_corners is None else bool(align_corners), mode=mode)
+        if functional == "F.interpolate":
+            params["recompute_scale_factor"] = "None" if recompute_scale_factor is None else bool(recompute_scale_factor)
+        if size is not None:
+            params.update(scale_factor="None", size=(int(size[0]), int(size[1])))
+        else:
+            sh, sw = (scale, scale) if isinstance(scale, (int, float)) else scale
+            params.update(scale_factor=(float(sh), float(sw)), size="None")
+        self._emit(functional, self._opname(functional.replace(".", "_")), [x], [out], params)
         return out
 
     def cat(self, xs: Sequence[str], dim: int = 1) -> str:
@@ -407,10 +451,13 @@ def build_toy_classifier(batch: int = 2, size: int = 32, seed: int = 0) -> PnnxB
     return b
 
 
-def build_toy_unet(batch: int = 2, size: int = 64, base: int = 16, depth: int = 3, ncls: int = 4, seed: int = 0) -> PnnxBuilder:
+def build_toy_unet(batch: int = 2, size: int = 64, base: int = 16, depth: int = 3, ncls: int = 4, seed: int = 0,
+                   up: str = "convtranspose") -> PnnxBuilder:
     """A small U-Net: per encoder level two [conv3x3 -> BatchNorm2d -> ReLU] then MaxPool2d(2, 2); the same block as bottleneck;
     per decoder level an up-conv, torch.cat([skip, up]) and two blocks; a 1x1 conv head.  The up-convs alternate k2 s2 p0 (one
-    tap per output pixel) and k3 s2 p1 output_padding 1 (four sub-pixel phases of 4 / 2 / 2 / 1 taps)."""
+    tap per output pixel) and k3 s2 p1 output_padding 1 (four sub-pixel phases of 4 / 2 / 2 / 1 taps).  up="bilinear": each up-conv
+    is nn.Upsample(scale_factor=2, mode="bilinear", align_corners=True) + conv3x3 instead (the other widely used decoder)."""
+    assert up in ("convtranspose", "bilinear"), up
     b = PnnxBuilder(seed)
     x = b.input((batch, 3, size, size))
 
@@ -428,9 +475,34 @@ def build_toy_unet(batch: int = 2, size: int = 64, base: int = 16, depth: int = 
     x = block(x, c)
     for i, skip in enumerate(reversed(skips)):
         c //= 2
-        up = b.conv_transpose(x, c, 2, 2, 0) if i % 2 == 0 else b.conv_transpose(x, c, 3, 2, 1, output_padding=1)
-        x = block(b.cat([skip, up]), c)
+        if up == "bilinear":
+            u = b.conv(b.upsample(x, 2.0, mode="bilinear", align_corners=True), c, 3, 1, 1)
+        else:
+            u = b.conv_transpose(x, c, 2, 2, 0) if i % 2 == 0 else b.conv_transpose(x, c, 3, 2, 1, output_padding=1)
+        x = block(b.cat([skip, u]), c)
     x = b.conv(x, ncls, 1, 1, 0)
+    b.output(x)
+    return b
+
+
+def build_toy_segnet(batch: int = 2, size: int = 64, ncls: int = 21, seed: int = 0) -> PnnxBuilder:
+    """A small FCN-style segmentation net: a stride-8 conv / BatchNorm2d / ReLU backbone with an FPN-style lateral in the middle
+    (F.interpolate x2, align_corners=False, + add), ending in a dilated 3x3 (d = 2); a 1x1 classifier to ncls classes; then
+    F.interpolate(size=(size, size), mode="bilinear", align_corners=False), the last line of torchvision's FCN / DeepLabV3 heads."""
+    b = PnnxBuilder(seed)
+    x = b.input((batch, 3, size, size))
+
+    def cbr(x, c, k=3, s=1, p=1, d=1):
+        return b.relu(b.batchnorm(b.conv(x, c, k, s, p, d)))
+
+    c2 = cbr(cbr(x, 16, 3, 2), 32, 3, 2)       # stride 4
+    c3 = cbr(c2, 64, 3, 2)                     # stride 8
+    c4 = cbr(c3, 64, 3, 2)                     # stride 16
+    top = b.interpolate(b.conv(c4, 64, 1, 1, 0), scale=2.0, mode="bilinear", align_corners=False)
+    x = b.add(b.conv(c3, 64, 1, 1, 0), top)    # stride 8
+    x = cbr(x, 64, 3, 1, 2, 2)                 # dilated
+    x = b.conv(x, ncls, 1, 1, 0)
+    x = b.interpolate(x, mode="bilinear", align_corners=False, size=(size, size))
     b.output(x)
     return b
 
