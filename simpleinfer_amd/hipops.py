@@ -45,6 +45,10 @@ def SiConv2dDesc(*a):
         d.plan = C.pointer(_PLAN)
     return d
 
+# entry -> the kernel instantiation its *_kernel_name query named for the LAST launch through this module, asked with the pointers of that launch
+# (the launchers choose kernels by pointer alignment: a guarded call must take the kernel of the plain one, tests/test_gpu_containment.py)
+LAST_KERNEL_NAME = {}
+
 ACT = {"none": 0, "relu": 1, "silu": 2, "sigmoid": 3, "hardsigmoid": 4, "hardswish": 5, "leakyrelu": 6}
 
 
@@ -52,9 +56,129 @@ class HipError(RuntimeError):
     pass
 
 
+LAST_ENTRIES = []   # every si_hip_* function called through _chk since the list was last cleared, runtime calls included: the containment test
+                    # keeps the compute entries of it (tests/containment.py is_exempt) and requires each label to be a function of the header
+
+
 def _chk(rc: int, what: str):
+    if what.startswith("si_hip_"):
+        LAST_ENTRIES.append(what)
     if rc != 0:
         raise HipError("%s: %s (code %d)" % (what, _native.hip().si_hip_error_string(rc).decode(), rc))
+
+
+class ContainmentError(RuntimeError):
+    """a kernel touched memory outside the buffer it was given (guard_bands), or wrote to one of its inputs"""
+
+
+class ByteFill:
+    """a fill given as a byte pattern instead of a value: ByteFill(0xFF) is a NaN as fp32 and as fp16, 255 as u8; ByteFill(0x7B) is 1.3e36 as
+    fp32, 61280 as fp16, 123 as u8 -- the two patterns of the containment tests (tests/containment.py)"""
+
+    def __init__(self, byte: int):
+        assert 0 <= int(byte) <= 255, byte
+        self.byte = int(byte)
+
+    def __repr__(self):
+        return "ByteFill(0x%02X)" % self.byte
+
+
+def _full(shape, dtype, fill) -> np.ndarray:
+    """np.full for a value or a ByteFill"""
+    if isinstance(fill, ByteFill):
+        dt = np.dtype(dtype)
+        return np.full(int(np.prod(shape, dtype=np.int64)) * dt.itemsize, fill.byte, np.uint8).view(dt).reshape(shape)
+    return np.full(shape, fill, dtype)
+
+
+_GUARD = None   # the active guard_bands() context, or None: state of this Python test helper only
+
+
+def _creation_site() -> str:
+    """function:line of the first frame outside DeviceBuffer / the view helpers: names a guarded buffer in a ContainmentError"""
+    import sys
+    f = sys._getframe(1)
+    while f is not None and (f.f_code.co_name in ("__init__", "from_numpy", "_creation_site", "_view_in", "_view_out", "_range_flag", "<listcomp>")
+                             and f.f_code.co_filename == __file__):
+        f = f.f_back
+    return "%s:%d" % (f.f_code.co_name, f.f_lineno) if f is not None else "?"
+
+
+class GuardBands:
+    """What guard_bands() yields: every DeviceBuffer created while it is active, with the bytes that must not change around (and, for inputs,
+    inside) each of them.  check() compares; the first difference raises ContainmentError."""
+
+    def __init__(self, pattern: int, nbytes: int):
+        assert 0 <= pattern <= 255 and nbytes > 0 and nbytes % 256 == 0, "bands are whole multiples of 256 bytes: the payload keeps hipMalloc's alignment"
+        self.pattern, self.nbytes = int(pattern), int(nbytes)
+        self.buffers = []
+        self.checked = 0
+
+    def shorten(self, buf: "DeviceBuffer", nbytes: int):
+        """tell the guard that buf's payload is `nbytes` shorter than what was allocated: the back band then starts that much earlier (the
+        positive control of the containment tests; the bytes given up already hold the pattern in a buffer nobody has written yet)"""
+        assert buf._guard is self and 0 <= nbytes <= buf.nbytes
+        buf._guard_payload = buf.nbytes - int(nbytes)
+
+    def _band(self, buf, side):
+        H = _native.hip()
+        lo = buf._base if side == "front" else buf.ptr + buf._guard_payload
+        n = buf.ptr - buf._base if side == "front" else (buf._base + buf._alloc) - lo
+        got = np.empty(n, np.uint8)
+        _chk(H.si_hip_memcpy_d2h(got.ctypes.data_as(C.c_void_p), lo, n, None), "d2h")
+        _chk(H.si_hip_stream_sync(None), "sync")
+        return got
+
+    def check_buffer(self, buf: "DeviceBuffer"):
+        if buf._guard_checked:
+            return
+        buf._guard_checked = True
+        self.checked += 1
+        _chk(_native.hip().si_hip_device_sync(), "device sync")
+        for side in ("front", "back"):
+            got = self._band(buf, side)
+            bad = np.nonzero(got != self.pattern)[0]
+            if bad.size:
+                # offsets from the payload edge: the byte just before the payload is -1, the first byte behind it +0
+                first, last = int(bad[0]), int(bad[-1])
+                rel = (lambda o: o - got.size) if side == "front" else (lambda o: o)
+                raise ContainmentError("%s band of buffer #%d (%s, %s, %d bytes) overwritten: %d bytes differ from 0x%02X, offsets %+d .. %+d from the "
+                                       "payload's %s" % (side, buf._guard_id, buf._guard_site, buf._guard_role(), buf._guard_payload, bad.size,
+                                                         self.pattern, rel(first), rel(last), "start" if side == "front" else "end"))
+        if buf._guard_host is not None:
+            ref = np.frombuffer(buf._guard_host, np.uint8)
+            got = buf.to_numpy((ref.size,), np.uint8)
+            bad = np.nonzero(got != ref)[0]
+            if bad.size:
+                raise ContainmentError("input buffer #%d (%s, %d bytes) was written: %d bytes differ, first at byte %d" % (
+                    buf._guard_id, buf._guard_site, buf.nbytes, bad.size, int(bad[0])))
+
+    def check(self):
+        """compare every live buffer created under this guard (also done when the context exits)"""
+        for b in self.buffers:
+            if b.ptr:
+                self.check_buffer(b)
+
+
+@contextlib.contextmanager
+def guard_bands(pattern: int = 0xFF, nbytes: int = 4096):
+    """with hipops.guard_bands(0xFF) as g: ...  -- every DeviceBuffer created inside (not DeviceBuffer.view) is allocated with `nbytes` more on
+    either side of its payload, the whole allocation pre-filled with the byte `pattern`; the payload starts 256-byte aligned as without the guard
+    and the back band starts at the payload's last byte + 1.  When a buffer is freed and when the block ends both bands are read back and
+    compared with the pattern, and a buffer uploaded as an input (from_numpy) is compared with what was uploaded: ContainmentError names the
+    buffer, the side and the offsets.  The bands are part of the test's own allocation: an overrun is observed, never provoked or trapped."""
+    global _GUARD
+    assert _GUARD is None, "guard_bands does not nest"
+    g = _GUARD = GuardBands(pattern, nbytes)
+    try:
+        yield g
+        g.check()
+    finally:
+        _GUARD = None
+        for b in g.buffers:
+            b._guard_checked = True
+            b.free()
+        g.buffers = []
 
 
 class DeviceBuffer:
@@ -62,23 +186,40 @@ class DeviceBuffer:
 
     def __init__(self, nbytes: int):
         self.nbytes = int(nbytes)
+        g = _GUARD
+        pad = g.nbytes if g is not None else 0
+        self._alloc = max(self.nbytes + 2 * pad, 16)
         p = C.c_void_p()
-        _chk(_native.hip().si_hip_malloc(C.byref(p), max(self.nbytes, 16)), "si_hip_malloc")
-        self.ptr = p.value
+        _chk(_native.hip().si_hip_malloc(C.byref(p), self._alloc), "si_hip_malloc")
+        self._base = p.value
+        self.ptr = self._base + pad
+        self._guard = g
+        if g is not None:
+            self._guard_id, self._guard_site, self._guard_payload = len(g.buffers), _creation_site(), self.nbytes
+            self._guard_host, self._guard_checked = None, False
+            _chk(_native.hip().si_hip_memset_async(self._base, g.pattern, self._alloc, None), "memset")
+            _chk(_native.hip().si_hip_stream_sync(None), "sync")
+            g.buffers.append(self)
+
+    def _guard_role(self):
+        return "input" if self._guard_host is not None else "output / workspace"
 
     @classmethod
-    def from_numpy(cls, a: np.ndarray, stream=None) -> "DeviceBuffer":
+    def from_numpy(cls, a: np.ndarray, stream=None, out: bool = False) -> "DeviceBuffer":
+        """out: the buffer is a destination pre-filled with `a` (a kernel may write it); else an input, which guard_bands() holds to its bytes"""
         a = np.ascontiguousarray(a)
         b = cls(a.nbytes)
         _chk(_native.hip().si_hip_memcpy_h2d(b.ptr, a.ctypes.data_as(C.c_void_p), a.nbytes, stream), "h2d")
         _chk(_native.hip().si_hip_stream_sync(stream), "sync")
+        if b._guard is not None and not out:
+            b._guard_host = a.tobytes()
         return b
 
     @classmethod
     def view(cls, ptr: int, nbytes: int) -> "DeviceBuffer":
         """Non-owning handle on device memory somebody else allocated (an engine output, a gathered buffer)."""
         b = cls.__new__(cls)
-        b.nbytes, b.ptr, b._borrowed = int(nbytes), int(ptr), True
+        b.nbytes, b.ptr, b._borrowed, b._guard = int(nbytes), int(ptr), True, None
         return b
 
     def to_numpy(self, shape, dtype=np.float32, stream=None) -> np.ndarray:
@@ -91,11 +232,16 @@ class DeviceBuffer:
     def fill(self, byte: int = 0):
         _chk(_native.hip().si_hip_memset_async(self.ptr, byte, self.nbytes, None), "memset")
         _chk(_native.hip().si_hip_stream_sync(None), "sync")
+        if getattr(self, "_guard", None) is not None:
+            self._guard_host = None   # a buffer that is memset is a destination
 
     def free(self):
         if getattr(self, "ptr", None):
             if not getattr(self, "_borrowed", False):
-                _native.hip().si_hip_free(self.ptr)
+                g = getattr(self, "_guard", None)
+                if g is not None and not self._guard_checked:
+                    g.check_buffer(self)
+                _native.hip().si_hip_free(self._base)
             self.ptr = None
 
     def __del__(self):
@@ -130,11 +276,46 @@ def conv_out_hw(ih, iw, k, s, p, d):
     return oh, ow
 
 
+# The strided-view hooks every wrapper below shares (the view contract: DESIGN.md "Views").  A tensor handed to a kernel as (ptr, ld, c) is the
+# channel slice [c_off, c_off + c) of rows of ld elements; the wrappers build that row buffer, fill what is NOT the slice with a value or a
+# ByteFill, hand the kernel the slice's pointer and -- full=True -- return the whole row buffer so that a test can look at the outside:
+#   in_ld / in_c_off / in_fill      the input (the buffer is exactly pixels * in_ld elements: with in_c_off + ic == in_ld the slice ends at its end)
+#   res_ld / res_c_off / res_fill   the fused residual
+#   out_ld / out_c_off / out_fill   the destination, pre-filled with out_fill; full=True returns all out_ld channels
+def _view_in(x, ld, c_off, fill):
+    """(buffer, pointer to the slice) of x uploaded as channels [c_off, c_off + C) of rows of `ld` elements whose other channels hold `fill`"""
+    c = x.shape[-1]
+    ld = ld or c
+    assert c_off >= 0 and c_off + c <= ld, (c_off, c, ld)
+    if ld != c:
+        w = _full(x.shape[:-1] + (ld,), x.dtype, fill)
+        w[..., c_off:c_off + c] = x
+        x = w
+    b = DeviceBuffer.from_numpy(x)
+    return b, b.ptr + x.itemsize * c_off
+
+
+def _view_out(pixel_shape, c, ld, c_off, fill, dtype=np.float32):
+    """(buffer, pointer to the slice) of a destination of rows of `ld` elements pre-filled with `fill`"""
+    ld = ld or c
+    assert c_off >= 0 and c_off + c <= ld, (c_off, c, ld)
+    b = DeviceBuffer.from_numpy(_full(tuple(pixel_shape) + (ld,), dtype, fill), out=True)
+    return b, b.ptr + np.dtype(dtype).itemsize * c_off
+
+
+def _ret(y, c, c_off, full):
+    """the wrappers' return value: the destination slice (as before), or with full=True the whole row buffer"""
+    if full or y.shape[-1] == c:
+        return y
+    return y[..., c_off:c_off + c].copy()
+
+
 def conv2d(x, w_oihw, bias=None, stride=(1, 1), padding=(0, 0), dilation=(1, 1), groups=1, act1="none",
            residual=None, act2="none", act_param=0.0, in_ld: Optional[int] = None, out_ld: Optional[int] = None,
-           out_c_off: int = 0, in_fill: float = 0.0):
+           out_c_off: int = 0, in_fill=0.0, in_c_off: int = 0, res_ld: Optional[int] = None, res_c_off: int = 0, res_fill=0.0,
+           out_fill=0.0, full: bool = False):
     """si_hip_conv2d_f32.  in_ld/out_ld > C exercise the strided (concat-slice) addressing: the input is
-    embedded in / the output is written into a wider zero-filled buffer and sliced back."""
+    embedded in / the output is written into a wider buffer and sliced back (the view hooks above)."""
     H = _native.hip()
     x, w_oihw = _f32(x), _f32(w_oihw)
     n, ih, iw, ic = x.shape
@@ -144,23 +325,17 @@ def conv2d(x, w_oihw, bias=None, stride=(1, 1), padding=(0, 0), dilation=(1, 1),
     out_ld = out_ld or oc
     d = SiConv2dDesc(n, ih, iw, ic, in_ld, oh, ow, oc, out_ld, kh, kw, stride[0], stride[1], dilation[0], dilation[1],
                      padding[0], padding[1], groups, 1 if bias is not None else 0, ACT[act1],
-                     1 if residual is not None else 0, oc, ACT[act2], float(act_param))
+                     1 if residual is not None else 0, res_ld or oc, ACT[act2], float(act_param))
     packed = np.zeros(H.si_hip_conv2d_weight_elems(C.byref(d)), np.float32)
     _chk(H.si_hip_conv2d_pack_weight_host(C.byref(d), w_oihw.ctypes.data_as(C.c_void_p), packed.ctypes.data_as(C.c_void_p)),
          "pack weight")
-    if in_ld != ic:
-        xw = np.full((n, ih, iw, in_ld), in_fill, np.float32)  # in_fill: what lies between the pixels' channels
-        xw[..., :ic] = x
-        x = xw
-    dx, dw = DeviceBuffer.from_numpy(x), DeviceBuffer.from_numpy(packed)
+    (dx, px), dw = _view_in(x, in_ld, in_c_off, in_fill), DeviceBuffer.from_numpy(packed)
     db = DeviceBuffer.from_numpy(_f32(bias)) if bias is not None else None
-    dr = DeviceBuffer.from_numpy(_f32(residual)) if residual is not None else None
-    dy = DeviceBuffer(n * oh * ow * out_ld * 4)
-    dy.fill(0)
-    _chk(H.si_hip_conv2d_f32(C.byref(d), dx.ptr, dw.ptr, db.ptr if db else None, dr.ptr if dr else None,
-                             dy.ptr + 4 * out_c_off, None), "si_hip_conv2d_f32")
-    y = dy.to_numpy((n, oh, ow, out_ld))
-    return y[..., out_c_off:out_c_off + oc].copy() if out_ld != oc else y
+    dr, pr = _view_in(_f32(residual), res_ld, res_c_off, res_fill) if residual is not None else (None, None)
+    dy, py = _view_out((n, oh, ow), oc, out_ld, out_c_off, out_fill)
+    LAST_KERNEL_NAME["si_hip_conv2d_f32"] = H.si_hip_conv2d_kernel_name(C.byref(d), C.c_void_p(px)).decode()
+    _chk(H.si_hip_conv2d_f32(C.byref(d), px, dw.ptr, db.ptr if db else None, pr, py, None), "si_hip_conv2d_f32")
+    return _ret(dy.to_numpy((n, oh, ow, out_ld)), oc, out_c_off, full)
 
 
 def conv_transpose_out_hw(ih, iw, k, s, p, op, d):
@@ -192,8 +367,8 @@ def conv_transpose2d_pack(d, w_iohw) -> np.ndarray:
 
 
 def conv_transpose2d(x_nhwc, w_iohw, bias=None, stride=(1, 1), padding=(0, 0), output_padding=(0, 0), dilation=(1, 1), act1="none",
-                     act_param=0.0, in_ld: Optional[int] = None, out_ld: Optional[int] = None, out_c_off: int = 0, in_fill: float = 0.0,
-                     out_fill: float = 0.0, full: bool = False):
+                     act_param=0.0, in_ld: Optional[int] = None, out_ld: Optional[int] = None, out_c_off: int = 0, in_fill=0.0,
+                     out_fill=0.0, full: bool = False, in_c_off: int = 0):
     """si_hip_conv_transpose2d_f32 (nn.ConvTranspose2d, groups = 1; w_iohw in torch's [Cin][Cout][kh][kw] layout).  As conv2d:
     in_ld > Cin embeds the input in a wider buffer whose other channels hold in_fill; out_ld > Cout writes channels
     [out_c_off, out_c_off + Cout) of a wider output buffer pre-filled with out_fill.  full=True returns that whole buffer."""
@@ -207,15 +382,11 @@ def conv_transpose2d(x_nhwc, w_iohw, bias=None, stride=(1, 1), padding=(0, 0), o
     assert out_c_off >= 0 and out_c_off + oc <= out_ld, (out_c_off, oc, out_ld)
     d = conv_transpose2d_desc(x.shape, w_iohw.shape, bias is not None, stride, padding, output_padding, dilation, act1, act_param, in_ld, out_ld)
     packed = conv_transpose2d_pack(d, w_iohw)
-    if in_ld != ic:
-        xw = np.full((n, ih, iw, in_ld), in_fill, np.float32)
-        xw[..., :ic] = x
-        x = xw
     oh, ow = d.oh, d.ow
-    dx, dw = DeviceBuffer.from_numpy(x), DeviceBuffer.from_numpy(packed)
+    (dx, px), dw = _view_in(x, in_ld, in_c_off, in_fill), DeviceBuffer.from_numpy(packed)
     db = DeviceBuffer.from_numpy(_f32(bias)) if bias is not None else None
-    dy = DeviceBuffer.from_numpy(np.full((n, oh, ow, out_ld), out_fill, np.float32))
-    _chk(H.si_hip_conv_transpose2d_f32(C.byref(d), dx.ptr, dw.ptr, db.ptr if db else None, dy.ptr + 4 * out_c_off, None),
+    dy = DeviceBuffer.from_numpy(_full((n, oh, ow, out_ld), np.float32, out_fill), out=True)
+    _chk(H.si_hip_conv_transpose2d_f32(C.byref(d), px, dw.ptr, db.ptr if db else None, dy.ptr + 4 * out_c_off, None),
          "si_hip_conv_transpose2d_f32")
     y = dy.to_numpy((n, oh, ow, out_ld))
     if full or out_ld == oc:
@@ -237,7 +408,8 @@ def _range_flag(d, want):
     return f
 
 
-def conv2d_split3(x, w_oihw, bias=None, stride=(1, 1), padding=(0, 0), act1="none", residual=None, act2="none", return_flag=False, in_ld=None):
+def conv2d_split3(x, w_oihw, bias=None, stride=(1, 1), padding=(0, 0), act1="none", residual=None, act2="none", return_flag=False, in_ld=None,
+                  in_fill=np.nan, in_c_off=0, res_ld=None, res_c_off=0, res_fill=0.0, out_ld=None, out_c_off=0, out_fill=0.0, full=False):
     """si_hip_conv2d_split3_f32: fp32 conv on the fp16 matrix cores by operand splitting (three fp16 MFMAs per product, fp32 accumulate).
     return_flag: also return the range-guard word (1: an operand overflowed fp16 on its way through the split).  in_ld: the input as a channel
     slice of a wider tensor (pixel stride in_ld > ic; what lies between is NaN)"""
@@ -246,134 +418,120 @@ def conv2d_split3(x, w_oihw, bias=None, stride=(1, 1), padding=(0, 0), act1="non
     n, ih, iw, ic = x.shape
     oc, _, kh, kw = w_oihw.shape
     oh, ow = conv_out_hw(ih, iw, (kh, kw), stride, padding, (1, 1))
-    if in_ld and in_ld != ic:
-        xw = np.full((n, ih, iw, in_ld), np.nan, np.float32)
-        xw[..., :ic] = x
-        x = xw
-    d = SiConv2dDesc(n, ih, iw, ic, in_ld or ic, oh, ow, oc, oc, kh, kw, stride[0], stride[1], 1, 1, padding[0], padding[1], 1,
-                     1 if bias is not None else 0, ACT[act1], 1 if residual is not None else 0, oc, ACT[act2], 0.0)
+    d = SiConv2dDesc(n, ih, iw, ic, in_ld or ic, oh, ow, oc, out_ld or oc, kh, kw, stride[0], stride[1], 1, 1, padding[0], padding[1], 1,
+                     1 if bias is not None else 0, ACT[act1], 1 if residual is not None else 0, res_ld or oc, ACT[act2], 0.0)
     if not H.si_hip_conv2d_split3_supported(C.byref(d)):
         raise HipError("si_hip_conv2d_split3_f32: unsupported shape")
     packed = np.zeros(H.si_hip_conv2d_split3_weight_elems(C.byref(d)), np.float16)
     _chk(H.si_hip_conv2d_split3_pack_weight_host(C.byref(d), w_oihw.ctypes.data_as(C.c_void_p), packed.ctypes.data_as(C.c_void_p)), "pack split3")
-    dx, dw = DeviceBuffer.from_numpy(x), DeviceBuffer.from_numpy(packed)
+    (dx, px), dw = _view_in(x, in_ld, in_c_off, in_fill), DeviceBuffer.from_numpy(packed)
     db = DeviceBuffer.from_numpy(_f32(bias)) if bias is not None else None
-    dr = DeviceBuffer.from_numpy(_f32(residual)) if residual is not None else None
-    dy = DeviceBuffer(n * oh * ow * oc * 4)
+    dr, pr = _view_in(_f32(residual), res_ld, res_c_off, res_fill) if residual is not None else (None, None)
+    dy, py = _view_out((n, oh, ow), oc, out_ld, out_c_off, out_fill)
     flag = _range_flag(d, return_flag)
-    _chk(H.si_hip_conv2d_split3_f32(C.byref(d), dx.ptr, dw.ptr, db.ptr if db else None, dr.ptr if dr else None, dy.ptr, None), "si_hip_conv2d_split3_f32")
-    y = dy.to_numpy((n, oh, ow, oc))
+    _chk(H.si_hip_conv2d_split3_f32(C.byref(d), px, dw.ptr, db.ptr if db else None, pr, py, None), "si_hip_conv2d_split3_f32")
+    y = _ret(dy.to_numpy((n, oh, ow, out_ld or oc)), oc, out_c_off, full)
     return (y, int(flag.to_numpy((1,), np.uint32)[0])) if return_flag else y
 
 
-def conv2d_stem_split3(x, w_oihw, bias=None, stride=(2, 2), padding=(2, 2), act1="none", return_flag=False):
+def conv2d_stem_split3(x, w_oihw, bias=None, stride=(2, 2), padding=(2, 2), act1="none", return_flag=False, in_ld=None, in_c_off=0, in_fill=0.0,
+                       out_ld=None, out_c_off=0, out_fill=0.0, full=False):
     """si_hip_conv2d_stem_split3_f32: the RGB stem conv on the f32_split arithmetic (fp32 image in, fp32 activations out)"""
     H = _native.hip()
     x, w_oihw = _f32(x), _f32(w_oihw)
     n, ih, iw, ic = x.shape
     oc, _, kh, kw = w_oihw.shape
     oh, ow = conv_out_hw(ih, iw, (kh, kw), stride, padding, (1, 1))
-    d = SiConv2dDesc(n, ih, iw, ic, ic, oh, ow, oc, oc, kh, kw, stride[0], stride[1], 1, 1, padding[0], padding[1], 1,
+    d = SiConv2dDesc(n, ih, iw, ic, in_ld or ic, oh, ow, oc, out_ld or oc, kh, kw, stride[0], stride[1], 1, 1, padding[0], padding[1], 1,
                      1 if bias is not None else 0, ACT[act1], 0, oc, ACT["none"], 0.0)
     if H.si_hip_conv2d_f16_supported(C.byref(d)) != 2:
         raise HipError("si_hip_conv2d_stem_split3_f32: not a stem shape")
     packed = np.zeros(H.si_hip_conv2d_stem_split3_weight_elems(C.byref(d)), np.float16)
     _chk(H.si_hip_conv2d_stem_split3_pack_weight_host(C.byref(d), w_oihw.ctypes.data_as(C.c_void_p), packed.ctypes.data_as(C.c_void_p)), "pack stem split3")
-    dx, dw = DeviceBuffer.from_numpy(x), DeviceBuffer.from_numpy(packed)
+    (dx, px), dw = _view_in(x, in_ld, in_c_off, in_fill), DeviceBuffer.from_numpy(packed)
     db = DeviceBuffer.from_numpy(_f32(bias)) if bias is not None else None
-    dy = DeviceBuffer(n * oh * ow * oc * 4)
+    dy, py = _view_out((n, oh, ow), oc, out_ld, out_c_off, out_fill)
     flag = _range_flag(d, return_flag)
-    _chk(H.si_hip_conv2d_stem_split3_f32(C.byref(d), dx.ptr, dw.ptr, db.ptr if db else None, dy.ptr, None), "si_hip_conv2d_stem_split3_f32")
-    y = dy.to_numpy((n, oh, ow, oc))
+    _chk(H.si_hip_conv2d_stem_split3_f32(C.byref(d), px, dw.ptr, db.ptr if db else None, py, None), "si_hip_conv2d_stem_split3_f32")
+    y = _ret(dy.to_numpy((n, oh, ow, out_ld or oc)), oc, out_c_off, full)
     return (y, int(flag.to_numpy((1,), np.uint32)[0])) if return_flag else y
 
 
-def conv2d_wino23_split(x, w_oihw, bias=None, padding=(1, 1), act1="none", residual=None, act2="none", return_flag=False):
+def conv2d_wino23_split(x, w_oihw, bias=None, padding=(1, 1), act1="none", residual=None, act2="none", return_flag=False, in_ld=None, in_fill=0.0,
+                        in_c_off=0, res_ld=None, res_c_off=0, res_fill=0.0, out_ld=None, out_c_off=0, out_fill=0.0, full=False):
     """si_hip_conv2d_wino23_split_f32: fused Winograd F(2,3) with the plane GEMMs on the fp16 matrix cores by operand splitting"""
     H = _native.hip()
     x, w_oihw = _f32(x), _f32(w_oihw)
     n, ih, iw, ic = x.shape
     oc = w_oihw.shape[0]
     oh, ow = conv_out_hw(ih, iw, (3, 3), (1, 1), padding, (1, 1))
-    d = SiConv2dDesc(n, ih, iw, ic, ic, oh, ow, oc, oc, 3, 3, 1, 1, 1, 1, padding[0], padding[1], 1,
-                     1 if bias is not None else 0, ACT[act1], 1 if residual is not None else 0, oc, ACT[act2], 0.0)
+    d = SiConv2dDesc(n, ih, iw, ic, in_ld or ic, oh, ow, oc, out_ld or oc, 3, 3, 1, 1, 1, 1, padding[0], padding[1], 1,
+                     1 if bias is not None else 0, ACT[act1], 1 if residual is not None else 0, res_ld or oc, ACT[act2], 0.0)
     if not H.si_hip_conv2d_wino23_split_supported(C.byref(d)):
         raise HipError("si_hip_conv2d_wino23_split_f32: unsupported shape")
     packed = np.zeros(H.si_hip_conv2d_wino23_split_weight_elems(C.byref(d)), np.float16)
     _chk(H.si_hip_conv2d_wino23_split_pack_weight_host(C.byref(d), w_oihw.ctypes.data_as(C.c_void_p), packed.ctypes.data_as(C.c_void_p)), "pack wino split")
-    dx, dw = DeviceBuffer.from_numpy(x), DeviceBuffer.from_numpy(packed)
+    (dx, px), dw = _view_in(x, in_ld, in_c_off, in_fill), DeviceBuffer.from_numpy(packed)
     db = DeviceBuffer.from_numpy(_f32(bias)) if bias is not None else None
-    dr = DeviceBuffer.from_numpy(_f32(residual)) if residual is not None else None
-    dy = DeviceBuffer(n * oh * ow * oc * 4)
+    dr, pr = _view_in(_f32(residual), res_ld, res_c_off, res_fill) if residual is not None else (None, None)
+    dy, py = _view_out((n, oh, ow), oc, out_ld, out_c_off, out_fill)
     flag = _range_flag(d, return_flag)
-    _chk(H.si_hip_conv2d_wino23_split_f32(C.byref(d), dx.ptr, dw.ptr, db.ptr if db else None, dr.ptr if dr else None, dy.ptr, None),
+    _chk(H.si_hip_conv2d_wino23_split_f32(C.byref(d), px, dw.ptr, db.ptr if db else None, pr, py, None),
          "si_hip_conv2d_wino23_split_f32")
-    y = dy.to_numpy((n, oh, ow, oc))
+    y = _ret(dy.to_numpy((n, oh, ow, out_ld or oc)), oc, out_c_off, full)
     return (y, int(flag.to_numpy((1,), np.uint32)[0])) if return_flag else y
 
 
-def conv2d_upcat(low, skip, w_oihw, bias, scale=(2.0, 2.0), up_first=True, act1="none", split_oc=0, split3=False):
-    """si_hip_conv2d_upcat_f32: a 1x1 conv over cat([upsample(low), skip]) (or [skip, upsample(low)]) that reads `low` at the
-    source pixel.  Returns y, or (y, y2) for the sibling-split form.  split3: the same on the f32_split arithmetic (si_hip_conv2d_split3_upcat_f32)."""
+def _upcat(kind, low, skip, w_oihw, bias, scale, up_first, act1, split_oc, in_ld, in_c_off, in_fill, low_ld, low_c_off, out_ld, out_c_off,
+           out2_ld, out2_c_off, out_fill, full):
+    """the three dual-source entries (kind "f32" / "split3" / "f16") behind conv2d_upcat / conv2d_upcat_f16"""
     H = _native.hip()
-    low, skip, w_oihw = _f32(low), _f32(skip), _f32(w_oihw)
+    dt = np.float16 if kind == "f16" else np.float32
+    low, skip, w_oihw = np.ascontiguousarray(low, dtype=dt), np.ascontiguousarray(skip, dtype=dt), _f32(w_oihw)
     n, oh, ow, cs = skip.shape
     _, lh, lw, cl = low.shape
     ic, oc = cl + cs, w_oihw.shape[0]
     assert w_oihw.shape[1] == ic and w_oihw.shape[2:] == (1, 1)
-    d = SiConv2dDesc(n, oh, ow, ic, ic, oh, ow, oc, oc, 1, 1, 1, 1, 1, 1, 0, 0, 1, 1 if bias is not None else 0, ACT[act1], 0, oc, 0, 0.0)
-    if split3:
-        wp = np.zeros(H.si_hip_conv2d_split3_weight_elems(C.byref(d)), np.float16)
-        _chk(H.si_hip_conv2d_split3_pack_weight_host(C.byref(d), w_oihw.ctypes.data_as(C.c_void_p), wp.ctypes.data_as(C.c_void_p)), "pack split3")
-    else:
-        wn = H.si_hip_conv2d_weight_elems(C.byref(d))
-        wp = np.empty(wn, np.float32)
-        _chk(H.si_hip_conv2d_pack_weight_host(C.byref(d), w_oihw.ctypes.data_as(C.c_void_p), wp.ctypes.data_as(C.c_void_p)), "pack")
-    fn, fname = (H.si_hip_conv2d_split3_upcat_f32, "si_hip_conv2d_split3_upcat_f32") if split3 else (H.si_hip_conv2d_upcat_f32, "si_hip_conv2d_upcat_f32")
+    ca = split_oc or oc
+    d = SiConv2dDesc(n, oh, ow, ic, in_ld or ic, oh, ow, oc, out_ld or ca, 1, 1, 1, 1, 1, 1, 0, 0, 1, 1 if bias is not None else 0, ACT[act1], 0, oc, 0, 0.0)
+    elems, pack, wdt = {"f32": (H.si_hip_conv2d_weight_elems, H.si_hip_conv2d_pack_weight_host, np.float32),
+                        "split3": (H.si_hip_conv2d_split3_weight_elems, H.si_hip_conv2d_split3_pack_weight_host, np.float16),
+                        "f16": (H.si_hip_conv2d_f16_weight_elems, H.si_hip_conv2d_f16_pack_weight_host, np.float16)}[kind]
+    wp = np.zeros(elems(C.byref(d)), wdt)
+    _chk(pack(C.byref(d), w_oihw.ctypes.data_as(C.c_void_p), wp.ctypes.data_as(C.c_void_p)), "pack " + kind)
+    fname = {"f32": "si_hip_conv2d_upcat_f32", "split3": "si_hip_conv2d_split3_upcat_f32", "f16": "si_hip_conv2d_upcat_f16"}[kind]
+    fn = getattr(H, fname)
     # the concat buffer: only the skip channels are ever written; the upsampled range is poisoned to prove nobody reads it
-    cat = np.full((n, oh, ow, ic), np.nan, np.float32)
+    cat = np.full((n, oh, ow, ic), np.nan, dt)
     c0 = 0 if up_first else cs
     cat[..., (cl if up_first else 0):(cl if up_first else 0) + cs] = skip
-    dcat, dlow, dw = DeviceBuffer.from_numpy(cat), DeviceBuffer.from_numpy(low), DeviceBuffer.from_numpy(wp)
+    (dcat, pcat), (dlow, plow), dw = _view_in(cat, in_ld, in_c_off, in_fill), _view_in(low, low_ld, low_c_off, in_fill), DeviceBuffer.from_numpy(wp)
     db = DeviceBuffer.from_numpy(_f32(bias)) if bias is not None else None
-    up = _native.SiConv2dUpsampledSource(dlow.ptr, lh, lw, cl, cl, c0, np.float32(1.0) / np.float32(scale[0]), np.float32(1.0) / np.float32(scale[1]))
+    up = _native.SiConv2dUpsampledSource(plow, lh, lw, cl, low_ld or cl, c0, np.float32(1.0) / np.float32(scale[0]), np.float32(1.0) / np.float32(scale[1]))
+    dy, py = _view_out((n, oh, ow), ca, out_ld, out_c_off, out_fill, dt)
     if split_oc:
-        d.out_ld = split_oc
-        dy, dy2 = DeviceBuffer(n * oh * ow * split_oc * 4), DeviceBuffer(n * oh * ow * (oc - split_oc) * 4)
-        _chk(fn(C.byref(d), dcat.ptr, C.byref(up), dw.ptr, db.ptr if db else None, dy.ptr, split_oc, dy2.ptr, oc - split_oc, None), fname)
-        return dy.to_numpy((n, oh, ow, split_oc)), dy2.to_numpy((n, oh, ow, oc - split_oc))
-    dy = DeviceBuffer(n * oh * ow * oc * 4)
-    _chk(fn(C.byref(d), dcat.ptr, C.byref(up), dw.ptr, db.ptr if db else None, dy.ptr, 0, None, 0, None), fname)
-    return dy.to_numpy((n, oh, ow, oc))
+        dy2, py2 = _view_out((n, oh, ow), oc - split_oc, out2_ld, out2_c_off, out_fill, dt)
+        _chk(fn(C.byref(d), pcat, C.byref(up), dw.ptr, db.ptr if db else None, py, split_oc, py2, out2_ld or oc - split_oc, None), fname)
+        return (_ret(dy.to_numpy((n, oh, ow, out_ld or ca), dt), ca, out_c_off, full),
+                _ret(dy2.to_numpy((n, oh, ow, out2_ld or oc - split_oc), dt), oc - split_oc, out2_c_off, full))
+    _chk(fn(C.byref(d), pcat, C.byref(up), dw.ptr, db.ptr if db else None, py, 0, None, 0, None), fname)
+    return _ret(dy.to_numpy((n, oh, ow, out_ld or oc), dt), oc, out_c_off, full)
 
 
-def conv2d_upcat_f16(low, skip, w_oihw, bias, scale=(2.0, 2.0), up_first=True, act1="none", split_oc=0):
+def conv2d_upcat(low, skip, w_oihw, bias, scale=(2.0, 2.0), up_first=True, act1="none", split_oc=0, split3=False, in_ld=None, in_c_off=0, in_fill=0.0,
+                 low_ld=None, low_c_off=0, out_ld=None, out_c_off=0, out2_ld=None, out2_c_off=0, out_fill=0.0, full=False):
+    """si_hip_conv2d_upcat_f32: a 1x1 conv over cat([upsample(low), skip]) (or [skip, upsample(low)]) that reads `low` at the
+    source pixel.  Returns y, or (y, y2) for the sibling-split form.  split3: the same on the f32_split arithmetic (si_hip_conv2d_split3_upcat_f32).
+    in_ld / in_c_off: the concat buffer as a slice; low_ld / low_c_off: the low-resolution source as one (both gaps hold in_fill)."""
+    return _upcat("split3" if split3 else "f32", low, skip, w_oihw, bias, scale, up_first, act1, split_oc, in_ld, in_c_off, in_fill, low_ld, low_c_off,
+                  out_ld, out_c_off, out2_ld, out2_c_off, out_fill, full)
+
+
+def conv2d_upcat_f16(low, skip, w_oihw, bias, scale=(2.0, 2.0), up_first=True, act1="none", split_oc=0, in_ld=None, in_c_off=0, in_fill=0.0,
+                     low_ld=None, low_c_off=0, out_ld=None, out_c_off=0, out2_ld=None, out2_c_off=0, out_fill=0.0, full=False):
     """si_hip_conv2d_upcat_f16: conv2d_upcat with fp16 storage (half tensors in and out, fp32 bias)."""
-    H = _native.hip()
-    low, skip = np.asarray(low, np.float16), np.asarray(skip, np.float16)
-    w_oihw = _f32(w_oihw)
-    n, oh, ow, cs = skip.shape
-    _, lh, lw, cl = low.shape
-    ic, oc = cl + cs, w_oihw.shape[0]
-    d = SiConv2dDesc(n, oh, ow, ic, ic, oh, ow, oc, oc, 1, 1, 1, 1, 1, 1, 0, 0, 1, 1 if bias is not None else 0, ACT[act1], 0, oc, 0, 0.0)
-    wp = np.zeros(H.si_hip_conv2d_f16_weight_elems(C.byref(d)), np.float16)
-    _chk(H.si_hip_conv2d_f16_pack_weight_host(C.byref(d), w_oihw.ctypes.data_as(C.c_void_p), wp.ctypes.data_as(C.c_void_p)), "pack f16")
-    cat = np.full((n, oh, ow, ic), np.nan, np.float16)   # the upsampled range is poison: nobody may read it
-    c0 = 0 if up_first else cs
-    cat[..., (cl if up_first else 0):(cl if up_first else 0) + cs] = skip
-    dcat, dlow, dw = DeviceBuffer.from_numpy(cat), DeviceBuffer.from_numpy(np.ascontiguousarray(low)), DeviceBuffer.from_numpy(wp)
-    db = DeviceBuffer.from_numpy(_f32(bias)) if bias is not None else None
-    up = _native.SiConv2dUpsampledSource(dlow.ptr, lh, lw, cl, cl, c0, np.float32(1.0) / np.float32(scale[0]), np.float32(1.0) / np.float32(scale[1]))
-    if split_oc:
-        d.out_ld = split_oc
-        dy, dy2 = DeviceBuffer(n * oh * ow * split_oc * 2), DeviceBuffer(n * oh * ow * (oc - split_oc) * 2)
-        _chk(H.si_hip_conv2d_upcat_f16(C.byref(d), dcat.ptr, C.byref(up), dw.ptr, db.ptr if db else None, dy.ptr, split_oc, dy2.ptr,
-                                       oc - split_oc, None), "si_hip_conv2d_upcat_f16")
-        return dy.to_numpy((n, oh, ow, split_oc), np.float16), dy2.to_numpy((n, oh, ow, oc - split_oc), np.float16)
-    dy = DeviceBuffer(n * oh * ow * oc * 2)
-    _chk(H.si_hip_conv2d_upcat_f16(C.byref(d), dcat.ptr, C.byref(up), dw.ptr, db.ptr if db else None, dy.ptr, 0, None, 0, None),
-         "si_hip_conv2d_upcat_f16")
-    return dy.to_numpy((n, oh, ow, oc), np.float16)
+    return _upcat("f16", low, skip, w_oihw, bias, scale, up_first, act1, split_oc, in_ld, in_c_off, in_fill, low_ld, low_c_off, out_ld, out_c_off,
+                  out2_ld, out2_c_off, out_fill, full)
 
 
 def conv2d_kernel_name(x_shape, w_shape, stride=(1, 1), padding=(0, 0), groups=1) -> str:
@@ -388,7 +546,7 @@ def conv2d_kernel_name(x_shape, w_shape, stride=(1, 1), padding=(0, 0), groups=1
 
 
 def conv2d_winograd(x, w_oihw, bias=None, padding=(1, 1), act1="none", residual=None, act2="none", in_ld=None,
-                    out_ld=None, out_c_off=0, tile=2):
+                    out_ld=None, out_c_off=0, tile=2, in_fill=0.0, in_c_off=0, res_ld=None, res_c_off=0, res_fill=0.0, out_fill=0.0, full=False):
     """si_hip_conv2d_wino23_f32 (tile=2, fused Winograd F(2,3)) or si_hip_conv2d_wino43_f32 (tile=4, F(4,3)); raises
     HipError for ineligible shapes."""
     H = _native.hip()
@@ -402,27 +560,21 @@ def conv2d_winograd(x, w_oihw, bias=None, padding=(1, 1), act1="none", residual=
     in_ld = in_ld or ic
     out_ld = out_ld or oc
     d = SiConv2dDesc(n, ih, iw, ic, in_ld, oh, ow, oc, out_ld, 3, 3, 1, 1, 1, 1, padding[0], padding[1], 1,
-                     1 if bias is not None else 0, ACT[act1], 1 if residual is not None else 0, oc, ACT[act2], 0.0)
+                     1 if bias is not None else 0, ACT[act1], 1 if residual is not None else 0, res_ld or oc, ACT[act2], 0.0)
     if not f_elig(C.byref(d)):
         raise HipError("shape not eligible for Winograd")
     u = np.zeros(f_elems(C.byref(d)), np.float32)
     _chk(f_pack(C.byref(d), w_oihw.ctypes.data_as(C.c_void_p), u.ctypes.data_as(C.c_void_p)), "wino pack")
-    if in_ld != ic:
-        xw = np.zeros((n, ih, iw, in_ld), np.float32)
-        xw[..., :ic] = x
-        x = xw
-    dx, du = DeviceBuffer.from_numpy(x), DeviceBuffer.from_numpy(u)
+    (dx, px), du = _view_in(x, in_ld, in_c_off, in_fill), DeviceBuffer.from_numpy(u)
     db = DeviceBuffer.from_numpy(_f32(bias)) if bias is not None else None
-    dr = DeviceBuffer.from_numpy(_f32(residual)) if residual is not None else None
-    dy = DeviceBuffer(n * oh * ow * out_ld * 4)
-    dy.fill(0)
-    _chk(f_run(C.byref(d), dx.ptr, du.ptr, db.ptr if db else None, dr.ptr if dr else None,
-               dy.ptr + 4 * out_c_off, None), "si_hip_conv2d_%s_f32" % fam)
-    y = dy.to_numpy((n, oh, ow, out_ld))
-    return y[..., out_c_off:out_c_off + oc].copy() if out_ld != oc else y
+    dr, pr = _view_in(_f32(residual), res_ld, res_c_off, res_fill) if residual is not None else (None, None)
+    dy, py = _view_out((n, oh, ow), oc, out_ld, out_c_off, out_fill)
+    _chk(f_run(C.byref(d), px, du.ptr, db.ptr if db else None, pr, py, None), "si_hip_conv2d_%s_f32" % fam)
+    return _ret(dy.to_numpy((n, oh, ow, out_ld)), oc, out_c_off, full)
 
 
-def conv2d_split(x, w_a, b_a, w_b, b_b, act1="none", out2_ld=None, out2_c_off=0):
+def conv2d_split(x, w_a, b_a, w_b, b_b, act1="none", out2_ld=None, out2_c_off=0, in_ld=None, in_c_off=0, in_fill=0.0, out_ld=None, out_c_off=0,
+                 out_fill=0.0, full=False):
     """si_hip_conv2d_split_f32: two 1x1 convs on the same input in one launch; returns (y_a, y_b)."""
     H = _native.hip()
     x, w_a, w_b = _f32(x), _f32(w_a), _f32(w_b)
@@ -438,17 +590,17 @@ def conv2d_split(x, w_a, b_a, w_b, b_b, act1="none", out2_ld=None, out2_c_off=0)
 
     wcat = np.concatenate([packed(w_a), packed(w_b)])
     bcat = np.concatenate([_f32(b_a), _f32(b_b)])
-    d = SiConv2dDesc(n, ih, iw, ic, ic, ih, iw, oa + ob, oa, 1, 1, 1, 1, 1, 1, 0, 0, 1, 1, ACT[act1], 0, 0, 0, 0.0)
-    dx, dw, db = DeviceBuffer.from_numpy(x), DeviceBuffer.from_numpy(wcat), DeviceBuffer.from_numpy(bcat)
-    dya, dyb = DeviceBuffer(n * ih * iw * oa * 4), DeviceBuffer(n * ih * iw * out2_ld * 4)
-    dyb.fill(0)
-    _chk(H.si_hip_conv2d_split_f32(C.byref(d), dx.ptr, dw.ptr, db.ptr, dya.ptr, oa, dyb.ptr + 4 * out2_c_off, out2_ld, None),
-         "si_hip_conv2d_split_f32")
-    yb = dyb.to_numpy((n, ih, iw, out2_ld))
-    return dya.to_numpy((n, ih, iw, oa)), yb[..., out2_c_off:out2_c_off + ob].copy()
+    out_ld = out_ld or oa
+    d = SiConv2dDesc(n, ih, iw, ic, in_ld or ic, ih, iw, oa + ob, out_ld, 1, 1, 1, 1, 1, 1, 0, 0, 1, 1, ACT[act1], 0, 0, 0, 0.0)
+    (dx, px), dw, db = _view_in(x, in_ld, in_c_off, in_fill), DeviceBuffer.from_numpy(wcat), DeviceBuffer.from_numpy(bcat)
+    (dya, pa), (dyb, pb) = _view_out((n, ih, iw), oa, out_ld, out_c_off, out_fill), _view_out((n, ih, iw), ob, out2_ld, out2_c_off, out_fill)
+    _chk(H.si_hip_conv2d_split_f32(C.byref(d), px, dw.ptr, db.ptr, pa, oa, pb, out2_ld, None), "si_hip_conv2d_split_f32")
+    return (_ret(dya.to_numpy((n, ih, iw, out_ld)), oa, out_c_off, full),
+            _ret(dyb.to_numpy((n, ih, iw, out2_ld)), ob, out2_c_off, full or out2_ld == ob))
 
 
-def conv2d_split3_split(x, w_a, b_a, w_b, b_b, act1="none", out2_ld=None, out2_c_off=0):
+def conv2d_split3_split(x, w_a, b_a, w_b, b_b, act1="none", out2_ld=None, out2_c_off=0, in_ld=None, in_c_off=0, in_fill=0.0, out_ld=None, out_c_off=0,
+                        out_fill=0.0, full=False):
     """si_hip_conv2d_split3_split_f32: two sibling 1x1 convs as one launch on the f32_split arithmetic; returns (y_a, y_b)"""
     H = _native.hip()
     x, w_a, w_b = _f32(x), _f32(w_a), _f32(w_b)
@@ -457,16 +609,15 @@ def conv2d_split3_split(x, w_a, b_a, w_b, b_b, act1="none", out2_ld=None, out2_c
     out2_ld = out2_ld or ob
     wcat = _f32(np.concatenate([w_a, w_b], 0))
     bcat = np.concatenate([_f32(b_a), _f32(b_b)])
-    d = SiConv2dDesc(n, ih, iw, ic, ic, ih, iw, oa + ob, oa, 1, 1, 1, 1, 1, 1, 0, 0, 1, 1, ACT[act1], 0, 0, 0, 0.0)
+    out_ld = out_ld or oa
+    d = SiConv2dDesc(n, ih, iw, ic, in_ld or ic, ih, iw, oa + ob, out_ld, 1, 1, 1, 1, 1, 1, 0, 0, 1, 1, ACT[act1], 0, 0, 0, 0.0)
     packed = np.zeros(H.si_hip_conv2d_split3_weight_elems(C.byref(d)), np.float16)
     _chk(H.si_hip_conv2d_split3_pack_weight_host(C.byref(d), wcat.ctypes.data_as(C.c_void_p), packed.ctypes.data_as(C.c_void_p)), "pack split3")
-    dx, dw, db = DeviceBuffer.from_numpy(x), DeviceBuffer.from_numpy(packed), DeviceBuffer.from_numpy(bcat)
-    dya, dyb = DeviceBuffer(n * ih * iw * oa * 4), DeviceBuffer(n * ih * iw * out2_ld * 4)
-    dyb.fill(0)
-    _chk(H.si_hip_conv2d_split3_split_f32(C.byref(d), dx.ptr, dw.ptr, db.ptr, dya.ptr, oa, dyb.ptr + 4 * out2_c_off, out2_ld, None),
-         "si_hip_conv2d_split3_split_f32")
-    yb = dyb.to_numpy((n, ih, iw, out2_ld))
-    return dya.to_numpy((n, ih, iw, oa)), yb[..., out2_c_off:out2_c_off + ob].copy()
+    (dx, px), dw, db = _view_in(x, in_ld, in_c_off, in_fill), DeviceBuffer.from_numpy(packed), DeviceBuffer.from_numpy(bcat)
+    (dya, pa), (dyb, pb) = _view_out((n, ih, iw), oa, out_ld, out_c_off, out_fill), _view_out((n, ih, iw), ob, out2_ld, out2_c_off, out_fill)
+    _chk(H.si_hip_conv2d_split3_split_f32(C.byref(d), px, dw.ptr, db.ptr, pa, oa, pb, out2_ld, None), "si_hip_conv2d_split3_split_f32")
+    return (_ret(dya.to_numpy((n, ih, iw, out_ld)), oa, out_c_off, full),
+            _ret(dyb.to_numpy((n, ih, iw, out2_ld)), ob, out2_c_off, full or out2_ld == ob))
 
 
 def linear(x, w, b=None):
@@ -480,18 +631,18 @@ def linear(x, w, b=None):
     return dy.to_numpy((x.shape[0], w.shape[0]))
 
 
-def maxpool2d(x, k, s, p, d=(1, 1)):
+def maxpool2d(x, k, s, p, d=(1, 1), in_ld=None, in_c_off=0, in_fill=0.0, out_ld=None, out_c_off=0, out_fill=0.0, full=False):
     H = _native.hip()
     x = _f32(x)
     n, ih, iw, c = x.shape
     oh, ow = conv_out_hw(ih, iw, k, s, p, d)
-    desc = SiPool2dDesc(n, ih, iw, c, c, oh, ow, c, k[0], k[1], s[0], s[1], d[0], d[1], p[0], p[1])
-    dx, dy = DeviceBuffer.from_numpy(x), DeviceBuffer(n * oh * ow * c * 4)
-    _chk(H.si_hip_maxpool2d_f32(C.byref(desc), dx.ptr, dy.ptr, None), "si_hip_maxpool2d_f32")
-    return dy.to_numpy((n, oh, ow, c))
+    desc = SiPool2dDesc(n, ih, iw, c, in_ld or c, oh, ow, out_ld or c, k[0], k[1], s[0], s[1], d[0], d[1], p[0], p[1])
+    (dx, px), (dy, py) = _view_in(x, in_ld, in_c_off, in_fill), _view_out((n, oh, ow), c, out_ld, out_c_off, out_fill)
+    _chk(H.si_hip_maxpool2d_f32(C.byref(desc), px, py, None), "si_hip_maxpool2d_f32")
+    return _ret(dy.to_numpy((n, oh, ow, out_ld or c)), c, out_c_off, full)
 
 
-def maxpool5_chain3(x, half=False, out_ld=None, out_c_off=(0, 0, 0)):
+def maxpool5_chain3(x, half=False, out_ld=None, out_c_off=(0, 0, 0), in_ld=None, in_c_off=0, in_fill=0.0, out_fill=0.0, full=False):
     """si_hip_maxpool5_chain3_{f32,f16}: the three chained 5x5 s1 p2 pools of SPPF; the outputs may be channel slices of
     wider rows (out_ld elements per pixel, starting at out_c_off[k]), as the concat aliasing hands them over."""
     H = _native.hip()
@@ -499,36 +650,33 @@ def maxpool5_chain3(x, half=False, out_ld=None, out_c_off=(0, 0, 0)):
     n, h, w, c = x.shape
     esz = 2 if half else 4
     ld = out_ld or c
-    dx = DeviceBuffer.from_numpy(x)
-    outs = [DeviceBuffer(n * h * w * ld * esz) for _ in range(3)]
-    for o in outs:
-        o.fill(0)
-    fn = H.si_hip_maxpool5_chain3_f16 if half else H.si_hip_maxpool5_chain3_f32
-    _chk(fn(dx.ptr, n, h, w, c, c, outs[0].ptr + esz * out_c_off[0], ld, outs[1].ptr + esz * out_c_off[1], ld,
-            outs[2].ptr + esz * out_c_off[2], ld, None), "si_hip_maxpool5_chain3")
     dt = np.float16 if half else np.float32
-    return [o.to_numpy((n, h, w, ld), dt)[..., off:off + c].copy() for o, off in zip(outs, out_c_off)]
+    dx, px = _view_in(x, in_ld, in_c_off, in_fill)
+    outs = [_view_out((n, h, w), c, ld, off, out_fill, dt) for off in out_c_off]
+    fn = H.si_hip_maxpool5_chain3_f16 if half else H.si_hip_maxpool5_chain3_f32
+    _chk(fn(px, n, h, w, c, in_ld or c, outs[0][1], ld, outs[1][1], ld, outs[2][1], ld, None), "si_hip_maxpool5_chain3_f16" if half else "si_hip_maxpool5_chain3_f32")
+    return [_ret(o.to_numpy((n, h, w, ld), dt), c, off, full) for (o, _), off in zip(outs, out_c_off)]
 
 
-def adaptive_avgpool2d(x, out_hw):
+def adaptive_avgpool2d(x, out_hw, in_ld=None, in_c_off=0, in_fill=0.0, out_ld=None, out_c_off=0, out_fill=0.0, full=False):
     H = _native.hip()
     x = _f32(x)
     n, ih, iw, c = x.shape
-    dx, dy = DeviceBuffer.from_numpy(x), DeviceBuffer(n * out_hw[0] * out_hw[1] * c * 4)
-    _chk(H.si_hip_adaptive_avgpool2d_f32(dx.ptr, n, ih, iw, c, c, dy.ptr, out_hw[0], out_hw[1], c, None),
+    (dx, px), (dy, py) = _view_in(x, in_ld, in_c_off, in_fill), _view_out((n, out_hw[0], out_hw[1]), c, out_ld, out_c_off, out_fill)
+    _chk(H.si_hip_adaptive_avgpool2d_f32(px, n, ih, iw, c, in_ld or c, py, out_hw[0], out_hw[1], out_ld or c, None),
          "si_hip_adaptive_avgpool2d_f32")
-    return dy.to_numpy((n, out_hw[0], out_hw[1], c))
+    return _ret(dy.to_numpy((n, out_hw[0], out_hw[1], out_ld or c)), c, out_c_off, full)
 
 
-def upsample_nearest(x, scale_h, scale_w, out_hw=None):
+def upsample_nearest(x, scale_h, scale_w, out_hw=None, in_ld=None, in_c_off=0, in_fill=0.0, out_ld=None, out_c_off=0, out_fill=0.0, full=False):
     H = _native.hip()
     x = _f32(x)
     n, ih, iw, c = x.shape
     oh, ow = out_hw if out_hw else (int(ih * scale_h), int(iw * scale_w))
-    dx, dy = DeviceBuffer.from_numpy(x), DeviceBuffer(n * oh * ow * c * 4)
-    _chk(H.si_hip_upsample_nearest_f32(dx.ptr, n, ih, iw, c, c, scale_h, scale_w, dy.ptr, oh, ow, c, None),
+    (dx, px), (dy, py) = _view_in(x, in_ld, in_c_off, in_fill), _view_out((n, oh, ow), c, out_ld, out_c_off, out_fill)
+    _chk(H.si_hip_upsample_nearest_f32(px, n, ih, iw, c, in_ld or c, scale_h, scale_w, py, oh, ow, out_ld or c, None),
          "si_hip_upsample_nearest_f32")
-    return dy.to_numpy((n, oh, ow, c))
+    return _ret(dy.to_numpy((n, oh, ow, out_ld or c)), c, out_c_off, full)
 
 
 UPSAMPLE_MODE = {"nearest": 0, "bilinear": 1}
@@ -567,22 +715,13 @@ def upsample_desc(x_shape, out_hw=None, scale=None, align_corners=False, mode="b
                                   upsample_step(mode, ih, oh, align_corners, sh), upsample_step(mode, iw, ow, align_corners, sw))
 
 
-def _embed(x, ld, fill):
-    """x's channels at the front of a buffer of pixel stride ld whose other channels hold `fill`"""
-    if ld == x.shape[-1]:
-        return x
-    w = np.full(x.shape[:-1] + (ld,), fill, x.dtype)
-    w[..., :x.shape[-1]] = x
-    return w
-
-
 def _float_storage(x):
     x = np.asarray(x)
     return np.ascontiguousarray(x) if x.dtype == np.float16 else _f32(x)
 
 
-def upsample_bilinear(x, out_hw=None, scale=None, align_corners=False, in_ld: Optional[int] = None, in_fill: float = 0.0,
-                      out_ld: Optional[int] = None, out_c_off: int = 0, out_fill: float = 0.0, full: bool = False):
+def upsample_bilinear(x, out_hw=None, scale=None, align_corners=False, in_ld: Optional[int] = None, in_fill=0.0,
+                      out_ld: Optional[int] = None, out_c_off: int = 0, out_fill=0.0, full: bool = False, in_c_off: int = 0):
     """si_hip_upsample_bilinear_f32 / _f16 (by the array's dtype) on an NHWC array; out_hw = torch's size=, scale = its
     scale_factor= (recompute_scale_factor=True is out_hw=upsample_out_hw(...)).  The strided-view hooks are conv_transpose2d's."""
     H = _native.hip()
@@ -592,10 +731,12 @@ def upsample_bilinear(x, out_hw=None, scale=None, align_corners=False, in_ld: Op
     in_ld, out_ld = in_ld or c, out_ld or c
     assert out_c_off >= 0 and out_c_off + c <= out_ld, (out_c_off, c, out_ld)
     d = upsample_desc(x.shape, out_hw, scale, align_corners, "bilinear", in_ld, out_ld)
-    dx = DeviceBuffer.from_numpy(_embed(x, in_ld, in_fill))
-    dy = DeviceBuffer.from_numpy(np.full((n, d.oh, d.ow, out_ld), out_fill, x.dtype))
+    dx, px = _view_in(x, in_ld, in_c_off, in_fill)
+    dy = DeviceBuffer.from_numpy(_full((n, d.oh, d.ow, out_ld), x.dtype, out_fill), out=True)
     fn = H.si_hip_upsample_bilinear_f16 if half else H.si_hip_upsample_bilinear_f32
-    _chk(fn(C.byref(d), dx.ptr, dy.ptr + x.itemsize * out_c_off, None), "si_hip_upsample_bilinear")
+    LAST_KERNEL_NAME["si_hip_upsample_bilinear"] = H.si_hip_upsample_bilinear_kernel_name(
+        C.byref(d), C.c_void_p(px), C.c_void_p(dy.ptr + x.itemsize * out_c_off), 1 if half else 0).decode()
+    _chk(fn(C.byref(d), px, dy.ptr + x.itemsize * out_c_off, None), "si_hip_upsample_bilinear_f16" if half else "si_hip_upsample_bilinear_f32")
     y = dy.to_numpy((n, d.oh, d.ow, out_ld), x.dtype)
     if full or out_ld == c:
         return y
@@ -608,20 +749,20 @@ def upsample_bilinear_kernel_name(x_shape, out_hw=None, scale=None, half=False, 
     return _native.hip().si_hip_upsample_bilinear_kernel_name(C.byref(d), C.c_void_p(256), C.c_void_p(256), 1 if half else 0).decode()
 
 
-def upsample_nearest_size(x, out_hw, in_ld: Optional[int] = None, in_fill: float = 0.0):
+def upsample_nearest_size(x, out_hw, in_ld: Optional[int] = None, in_fill=0.0, in_c_off=0, out_ld=None, out_c_off=0, out_fill=0.0, full=False):
     """si_hip_upsample_nearest_steps_f32 with the steps of size= (torch's nearest rule)"""
     H = _native.hip()
     x = _f32(x)
     n, ih, iw, c = x.shape
     in_ld = in_ld or c
     d = upsample_desc(x.shape, out_hw, None, False, "nearest", in_ld)
-    dx, dy = DeviceBuffer.from_numpy(_embed(x, in_ld, in_fill)), DeviceBuffer(n * d.oh * d.ow * c * 4)
-    _chk(H.si_hip_upsample_nearest_steps_f32(dx.ptr, n, ih, iw, c, in_ld, d.step_h, d.step_w, dy.ptr, d.oh, d.ow, c, None),
+    (dx, px), (dy, py) = _view_in(x, in_ld, in_c_off, in_fill), _view_out((n, d.oh, d.ow), c, out_ld, out_c_off, out_fill)
+    _chk(H.si_hip_upsample_nearest_steps_f32(px, n, ih, iw, c, in_ld, d.step_h, d.step_w, py, d.oh, d.ow, out_ld or c, None),
          "si_hip_upsample_nearest_steps_f32")
-    return dy.to_numpy((n, d.oh, d.ow, c))
+    return _ret(dy.to_numpy((n, d.oh, d.ow, out_ld or c)), c, out_c_off, full)
 
 
-def segment_labels(logits, out_hw, align_corners=False, in_ld: Optional[int] = None, in_fill: float = 0.0):
+def segment_labels(logits, out_hw, align_corners=False, in_ld: Optional[int] = None, in_fill=0.0, in_c_off: int = 0):
     """si_hip_segment_labels_f32 / _f16: uint8 [N, oh, ow] argmax over classes of the bilinear upsample of NHWC logits (the
     upsampled logits are never written)"""
     H = _native.hip()
@@ -629,10 +770,10 @@ def segment_labels(logits, out_hw, align_corners=False, in_ld: Optional[int] = N
     n, ih, iw, c = x.shape
     in_ld = in_ld or c
     d = upsample_desc(x.shape, out_hw, None, align_corners, "bilinear", in_ld, 1)
-    dx = DeviceBuffer.from_numpy(_embed(x, in_ld, in_fill))
+    dx, px = _view_in(x, in_ld, in_c_off, in_fill)
     dy = DeviceBuffer(n * d.oh * d.ow)
     fn = H.si_hip_segment_labels_f16 if x.dtype == np.float16 else H.si_hip_segment_labels_f32
-    _chk(fn(C.byref(d), dx.ptr, dy.ptr, None), "si_hip_segment_labels")
+    _chk(fn(C.byref(d), px, dy.ptr, None), "si_hip_segment_labels_f16" if x.dtype == np.float16 else "si_hip_segment_labels_f32")
     return dy.to_numpy((n, d.oh, d.ow), np.uint8)
 
 
@@ -655,92 +796,106 @@ def cat(xs, axis):
     return dy.to_numpy(shp)
 
 
-def binary_op(op, a, b, out_shape=None):
+def copy_channels(x, in_ld=None, in_c_off=0, in_fill=0.0, out_ld=None, out_c_off=0, out_fill=0.0, full=False):
+    """si_hip_copy_channels_f32 on its own: the channels of x into channels [out_c_off, out_c_off + C) of rows of out_ld elements (one operand of
+    a channel concat)"""
+    H = _native.hip()
+    x = _f32(x)
+    c = x.shape[-1]
+    (dx, px), (dy, py) = _view_in(x, in_ld, in_c_off, in_fill), _view_out(x.shape[:-1], c, out_ld, out_c_off, out_fill)
+    _chk(H.si_hip_copy_channels_f32(px, x.size // c, c, in_ld or c, py, out_ld or c, None), "si_hip_copy_channels_f32")
+    return _ret(dy.to_numpy(x.shape[:-1] + (out_ld or c,)), c, out_c_off, full)
+
+
+def binary_op(op, a, b, out_shape=None, in_ld=None, in_c_off=0, in_fill=0.0, b_ld=None, b_c_off=0, out_ld=None, out_c_off=0, out_fill=0.0, full=False):
+    """si_hip_binary_f32; in_ld / in_c_off are a's view, b_ld / b_c_off b's (both gaps hold in_fill); full=True returns the rank-4 row buffer"""
     H = _native.hip()
     a, b = _f32(a), _f32(b)
     a4, b4 = pad4(a.shape), pad4(b.shape)
     o4 = pad4(out_shape) if out_shape is not None else [max(x, y) for x, y in zip(a4, b4)]
-    da, db_, dy = DeviceBuffer.from_numpy(a), DeviceBuffer.from_numpy(b), DeviceBuffer(int(np.prod(o4)) * 4)
-    _chk(H.si_hip_binary_f32(op, da.ptr, _i4(a4), a4[3], db_.ptr, _i4(b4), b4[3], dy.ptr, _i4(o4), o4[3], None),
+    (da, pa), (db_, pb) = _view_in(a.reshape(a4), in_ld, in_c_off, in_fill), _view_in(b.reshape(b4), b_ld, b_c_off, in_fill)
+    dy, py = _view_out(o4[:3], o4[3], out_ld, out_c_off, out_fill)
+    _chk(H.si_hip_binary_f32(op, pa, _i4(a4), in_ld or a4[3], pb, _i4(b4), b_ld or b4[3], py, _i4(o4), out_ld or o4[3], None),
          "si_hip_binary_f32")
-    return dy.to_numpy(o4).reshape(out_shape if out_shape is not None else o4)
+    y = dy.to_numpy(o4[:3] + [out_ld or o4[3]])
+    if full:
+        return y
+    return _ret(y, o4[3], out_c_off, False).reshape(out_shape if out_shape is not None else o4)
 
 
-def binary_scalar(op, x, scalar):
+def binary_scalar(op, x, scalar, in_ld=None, in_c_off=0, in_fill=0.0, out_ld=None, out_c_off=0, out_fill=0.0, full=False):
     """out = x (op) scalar -- BinaryOp's with_scalar form (op codes of include/si_hip.h; 7 / 8 / 9 / 11 put the scalar first)."""
     H = _native.hip()
     x = _f32(x)
     c = x.shape[-1]
-    dx, dy = DeviceBuffer.from_numpy(x), DeviceBuffer(x.nbytes)
-    _chk(H.si_hip_binary_scalar_f32(op, dx.ptr, x.size // c, c, c, float(scalar), dy.ptr, c, None), "si_hip_binary_scalar_f32")
-    return dy.to_numpy(x.shape)
+    (dx, px), (dy, py) = _view_in(x, in_ld, in_c_off, in_fill), _view_out(x.shape[:-1], c, out_ld, out_c_off, out_fill)
+    _chk(H.si_hip_binary_scalar_f32(op, px, x.size // c, c, in_ld or c, float(scalar), py, out_ld or c, None), "si_hip_binary_scalar_f32")
+    return _ret(dy.to_numpy(x.shape[:-1] + (out_ld or c,)), c, out_c_off, full)
 
 
-def unary_op(op, x, in_ld=None, out_ld=None):
+def unary_op(op, x, in_ld=None, out_ld=None, in_c_off=0, in_fill=np.nan, out_c_off=0, out_fill=0.0, full=False):
     """out = f(x) -- UnaryOp codes 0..17 (include/si_hip.h); optional pixel strides exercise the strided form."""
     H = _native.hip()
     x = _f32(x)
     c = x.shape[-1]
     pixels = x.size // c
     ild, old = in_ld or c, out_ld or c
-    xin = np.full((pixels, ild), np.nan, np.float32)
-    xin[:, :c] = x.reshape(pixels, c)
-    dx, dy = DeviceBuffer.from_numpy(xin), DeviceBuffer(pixels * old * 4)
-    dy.fill(0)
-    _chk(H.si_hip_unary_f32(op, dx.ptr, pixels, c, ild, dy.ptr, old, None), "si_hip_unary_f32")
-    return dy.to_numpy((pixels, old))[:, :c].reshape(x.shape)
+    (dx, px), (dy, py) = _view_in(x.reshape(pixels, c), ild, in_c_off, in_fill), _view_out((pixels,), c, old, out_c_off, out_fill, np.float32)
+    _chk(H.si_hip_unary_f32(op, px, pixels, c, ild, py, old, None), "si_hip_unary_f32")
+    if full:
+        return dy.to_numpy((pixels, old), np.float32)
+    return dy.to_numpy((pixels, old))[:, out_c_off:out_c_off + c].reshape(x.shape)
 
 
-def unary_op_f16(op, x, in_ld=None, out_ld=None):
+def unary_op_f16(op, x, in_ld=None, out_ld=None, in_c_off=0, in_fill=np.nan, out_c_off=0, out_fill=0.0, full=False):
     """si_hip_unary_f16: UnaryOp on fp16 tensors (the fp32 function on the widened value, one rounding)."""
     H = _native.hip()
     x = _f16(x)
     c = x.shape[-1]
     pixels = x.size // c
     ild, old = in_ld or c, out_ld or c
-    xin = np.full((pixels, ild), np.nan, np.float16)
-    xin[:, :c] = x.reshape(pixels, c)
-    dx, dy = DeviceBuffer.from_numpy(xin), DeviceBuffer(pixels * old * 2)
-    dy.fill(0)
-    _chk(H.si_hip_unary_f16(op, dx.ptr, pixels, c, ild, dy.ptr, old, None), "si_hip_unary_f16")
-    return dy.to_numpy((pixels, old), np.float16)[:, :c].reshape(x.shape)
+    (dx, px), (dy, py) = _view_in(x.reshape(pixels, c), ild, in_c_off, in_fill), _view_out((pixels,), c, old, out_c_off, out_fill, np.float16)
+    _chk(H.si_hip_unary_f16(op, px, pixels, c, ild, py, old, None), "si_hip_unary_f16")
+    if full:
+        return dy.to_numpy((pixels, old), np.float16)
+    return dy.to_numpy((pixels, old), np.float16)[:, out_c_off:out_c_off + c].reshape(x.shape)
 
 
-def activation(kind, x, param=0.0):
+def activation(kind, x, param=0.0, in_ld=None, in_c_off=0, in_fill=0.0, out_ld=None, out_c_off=0, out_fill=0.0, full=False):
     H = _native.hip()
     x = _f32(x)
     c = x.shape[-1]
-    dx, dy = DeviceBuffer.from_numpy(x), DeviceBuffer(x.nbytes)
-    _chk(H.si_hip_activation_f32(ACT[kind], param, dx.ptr, x.size // c, c, c, dy.ptr, c, None), "si_hip_activation_f32")
-    return dy.to_numpy(x.shape)
+    (dx, px), (dy, py) = _view_in(x, in_ld, in_c_off, in_fill), _view_out(x.shape[:-1], c, out_ld, out_c_off, out_fill)
+    _chk(H.si_hip_activation_f32(ACT[kind], param, px, x.size // c, c, in_ld or c, py, out_ld or c, None), "si_hip_activation_f32")
+    return _ret(dy.to_numpy(x.shape[:-1] + (out_ld or c,)), c, out_c_off, full)
 
 
-def batchnorm2d(x, mean, var, gamma, beta, eps):
+def batchnorm2d(x, mean, var, gamma, beta, eps, in_ld=None, in_c_off=0, in_fill=0.0, out_ld=None, out_c_off=0, out_fill=0.0, full=False):
     H = _native.hip()
     x = _f32(x)
     c = x.shape[-1]
     bufs = [DeviceBuffer.from_numpy(_f32(v)) for v in (mean, var, gamma, beta)]
-    dx, dy = DeviceBuffer.from_numpy(x), DeviceBuffer(x.nbytes)
-    _chk(H.si_hip_batchnorm2d_f32(dx.ptr, x.size // c, c, c, bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, bufs[3].ptr, eps,
-                                  dy.ptr, c, None), "si_hip_batchnorm2d_f32")
-    return dy.to_numpy(x.shape)
+    (dx, px), (dy, py) = _view_in(x, in_ld, in_c_off, in_fill), _view_out(x.shape[:-1], c, out_ld, out_c_off, out_fill)
+    _chk(H.si_hip_batchnorm2d_f32(px, x.size // c, c, in_ld or c, bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, bufs[3].ptr, eps,
+                                  py, out_ld or c, None), "si_hip_batchnorm2d_f32")
+    return _ret(dy.to_numpy(x.shape[:-1] + (out_ld or c,)), c, out_c_off, full)
 
 
-def flatten_nhwc(x):
+def flatten_nhwc(x, in_ld=None, in_c_off=0, in_fill=0.0):
     H = _native.hip()
     x = _f32(x)
     n, h, w, c = x.shape
-    dx, dy = DeviceBuffer.from_numpy(x), DeviceBuffer(x.nbytes)
-    _chk(H.si_hip_nhwc_to_nchw_f32(dx.ptr, n, h, w, c, c, dy.ptr, None), "si_hip_nhwc_to_nchw_f32")
+    (dx, px), dy = _view_in(x, in_ld, in_c_off, in_fill), DeviceBuffer(x.nbytes)
+    _chk(H.si_hip_nhwc_to_nchw_f32(px, n, h, w, c, in_ld or c, dy.ptr, None), "si_hip_nhwc_to_nchw_f32")
     return dy.to_numpy((n, c * h * w))
 
 
-def yolo_detect(feats, weights, biases, grids, anchor_grids, strides, na=3, fused=False):
+def yolo_detect(feats, weights, biases, grids, anchor_grids, strides, na=3, fused=False, in_pad=0, in_c_off=0, in_fill=0.0):
     """Detect head exactly as the YoloDetect layer runs it: per level 1x1 conv kernel + decode kernel, or (fused)
     si_hip_conv2d_yolo_f32 -- the conv with the decode + concat in its epilogue."""
     H = _native.hip()
     if fused:
-        return _yolo_detect_fused(feats, weights, biases, grids, anchor_grids, strides, na)
+        return _yolo_detect_fused(feats, weights, biases, grids, anchor_grids, strides, na, in_pad=in_pad, in_c_off=in_c_off, in_fill=in_fill)
     feats = [_f32(f) for f in feats]
     n = feats[0].shape[0]
     ne = weights[0].shape[0] // na
@@ -760,13 +915,15 @@ def yolo_detect(feats, weights, biases, grids, anchor_grids, strides, na=3, fuse
     return dout.to_numpy((n, rows_total, ne))
 
 
-def yolo_detect_split3(feats, weights, biases, grids, anchor_grids, strides, na=3, return_flags=False):
+def yolo_detect_split3(feats, weights, biases, grids, anchor_grids, strides, na=3, return_flags=False, in_pad=0, in_c_off=0, in_fill=0.0):
     """si_hip_conv2d_split3_yolo_f32 per level: the Detect head on the f32_split arithmetic (fp32 features, three fp16 MFMA products per
     fp32 product), decode + concat in the epilogue.  return_flags: also the per-level range-guard words."""
-    return _yolo_detect_fused(feats, weights, biases, grids, anchor_grids, strides, na, split3=True, return_flags=return_flags)
+    return _yolo_detect_fused(feats, weights, biases, grids, anchor_grids, strides, na, split3=True, return_flags=return_flags, in_pad=in_pad,
+                              in_c_off=in_c_off, in_fill=in_fill)
 
 
-def _yolo_detect_fused(feats, weights, biases, grids, anchor_grids, strides, na, split3=False, return_flags=False):
+def _yolo_detect_fused(feats, weights, biases, grids, anchor_grids, strides, na, split3=False, return_flags=False, in_pad=0, in_c_off=0, in_fill=0.0):
+    """in_pad / in_c_off: every level's features as channels [in_c_off, in_c_off + C) of rows of C + in_pad elements (the gap holds in_fill)"""
     from ._native import SiYoloLevel
     H = _native.hip()
     feats = [_f32(f) for f in feats]
@@ -780,7 +937,7 @@ def _yolo_detect_fused(feats, weights, biases, grids, anchor_grids, strides, na,
     for f, w, b, g, a, s in zip(feats, weights, biases, grids, anchor_grids, strides):
         _, h, wd, cin = f.shape
         w = _f32(w)
-        d = SiConv2dDesc(n, h, wd, cin, cin, h, wd, na * ne, na * ne, 1, 1, 1, 1, 1, 1, 0, 0, 1, 1, 0, 0, na * ne, 0, 0.0)
+        d = SiConv2dDesc(n, h, wd, cin, cin + in_pad, h, wd, na * ne, na * ne, 1, 1, 1, 1, 1, 1, 0, 0, 1, 1, 0, 0, na * ne, 0, 0.0)
         if split3:
             packed = np.zeros(H.si_hip_conv2d_split3_weight_elems(C.byref(d)), np.float16)
             _chk(H.si_hip_conv2d_split3_pack_weight_host(C.byref(d), w.ctypes.data_as(C.c_void_p), packed.ctypes.data_as(C.c_void_p)), "pack")
@@ -789,11 +946,12 @@ def _yolo_detect_fused(feats, weights, biases, grids, anchor_grids, strides, na,
             _chk(H.si_hip_conv2d_pack_weight_host(C.byref(d), w.ctypes.data_as(C.c_void_p), packed.ctypes.data_as(C.c_void_p)), "pack")
         g2 = _f32(np.transpose(_f32(g)[0], (1, 2, 0, 3)))
         a2 = _f32(np.transpose(_f32(a)[0], (1, 2, 0, 3)))
-        bufs = [DeviceBuffer.from_numpy(v) for v in (f, packed, _f32(b), g2, a2)]
+        bufs = [None] + [DeviceBuffer.from_numpy(v) for v in (packed, _f32(b), g2, a2)]
+        bufs[0], pf = _view_in(f, cin + in_pad, in_c_off, in_fill)
         lv = SiYoloLevel(na, ne, rows_total, off, float(s))
         fn = H.si_hip_conv2d_split3_yolo_f32 if split3 else H.si_hip_conv2d_yolo_f32
         flag = _range_flag(d, return_flags and split3)
-        _chk(fn(C.byref(d), bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, C.byref(lv), bufs[3].ptr, bufs[4].ptr, dout.ptr, None),
+        _chk(fn(C.byref(d), pf, bufs[1].ptr, bufs[2].ptr, C.byref(lv), bufs[3].ptr, bufs[4].ptr, dout.ptr, None),
              "si_hip_conv2d_split3_yolo_f32" if split3 else "si_hip_conv2d_yolo_f32")
         sync()
         if flag is not None:
@@ -895,7 +1053,8 @@ def _f16(a) -> np.ndarray:
 
 
 def conv2d_f16(x, w_oihw, bias=None, stride=(1, 1), padding=(0, 0), dilation=(1, 1), groups=1, act1="none",
-               residual=None, act2="none", act_param=0.0, in_ld=None, out_ld=None, out_c_off=0, out_f32=False, in_fill=0.0):
+               residual=None, act2="none", act_param=0.0, in_ld=None, out_ld=None, out_c_off=0, out_f32=False, in_fill=0.0, in_c_off=0,
+               res_ld=None, res_c_off=0, res_fill=0.0, out_fill=0.0, full=False):
     """si_hip_conv2d_f16, si_hip_conv2d_stem_f16 when the shape is a stem (fp32 image in, fp16 out), or si_hip_conv2d_depthwise_f16.
     in_fill: what lies between the pixels' channels of a strided (in_ld > ic) input."""
     H = _native.hip()
@@ -907,141 +1066,131 @@ def conv2d_f16(x, w_oihw, bias=None, stride=(1, 1), padding=(0, 0), dilation=(1,
     out_ld = out_ld or oc
     d = SiConv2dDesc(n, ih, iw, ic, in_ld, oh, ow, oc, out_ld, kh, kw, stride[0], stride[1], dilation[0], dilation[1],
                      padding[0], padding[1], groups, 1 if bias is not None else 0, ACT[act1],
-                     1 if residual is not None else 0, oc, ACT[act2], float(act_param))
+                     1 if residual is not None else 0, res_ld or oc, ACT[act2], float(act_param))
     kind = H.si_hip_conv2d_f16_supported(C.byref(d))
     if kind == 0:
         raise HipError("no fp16 conv kernel for this shape")
     db = DeviceBuffer.from_numpy(_f32(bias)) if bias is not None else None
-    osz = 4 if out_f32 else 2
-    dy = DeviceBuffer(n * oh * ow * out_ld * osz)
-    dy.fill(0)
+    odt = np.float32 if out_f32 else np.float16
+    dy, py = _view_out((n, oh, ow), oc, out_ld, out_c_off, out_fill, odt)
     if kind == 2:
         packed = np.zeros(H.si_hip_conv2d_stem_f16_weight_elems(C.byref(d)), np.float16)
         _chk(H.si_hip_conv2d_stem_f16_pack_weight_host(C.byref(d), w_oihw.ctypes.data_as(C.c_void_p),
                                                        packed.ctypes.data_as(C.c_void_p)), "pack stem f16")
-        xs = _f32(x)
-        if in_ld != ic:
-            xs = np.zeros((n, ih, iw, in_ld), np.float32)
-            xs[..., :ic] = x
-        dx, dw = DeviceBuffer.from_numpy(xs), DeviceBuffer.from_numpy(packed)
-        _chk(H.si_hip_conv2d_stem_f16(C.byref(d), dx.ptr, dw.ptr, db.ptr if db else None, dy.ptr + 2 * out_c_off, None),
-             "si_hip_conv2d_stem_f16")
-        y = dy.to_numpy((n, oh, ow, out_ld), np.float16)
-        return y[..., out_c_off:out_c_off + oc].copy() if out_ld != oc else y
+        (dx, px), dw = _view_in(_f32(x), in_ld, in_c_off, in_fill), DeviceBuffer.from_numpy(packed)
+        _chk(H.si_hip_conv2d_stem_f16(C.byref(d), px, dw.ptr, db.ptr if db else None, py, None), "si_hip_conv2d_stem_f16")
+        return _ret(dy.to_numpy((n, oh, ow, out_ld), np.float16), oc, out_c_off, full)
     if kind == 3:   # depthwise: fp16 activations, the FP32 depthwise weight image
         packed = np.zeros(H.si_hip_conv2d_weight_elems(C.byref(d)), np.float32)
         _chk(H.si_hip_conv2d_pack_weight_host(C.byref(d), w_oihw.ctypes.data_as(C.c_void_p), packed.ctypes.data_as(C.c_void_p)), "pack depthwise")
         if out_f32:
             raise HipError("the fp16 depthwise kernel writes fp16")
-        xh = _f16(x)
-        if in_ld != ic:
-            xw = np.zeros((n, ih, iw, in_ld), np.float16)
-            xw[..., :ic] = xh
-            xh = xw
-        dx, dw = DeviceBuffer.from_numpy(xh), DeviceBuffer.from_numpy(packed)
-        dr = DeviceBuffer.from_numpy(_f16(residual)) if residual is not None else None
-        _chk(H.si_hip_conv2d_depthwise_f16(C.byref(d), dx.ptr, dw.ptr, db.ptr if db else None, dr.ptr if dr else None,
-                                           dy.ptr + 2 * out_c_off, None), "si_hip_conv2d_depthwise_f16")
-        y = dy.to_numpy((n, oh, ow, out_ld), np.float16)
-        return y[..., out_c_off:out_c_off + oc].copy() if out_ld != oc else y
+        (dx, px), dw = _view_in(_f16(x), in_ld, in_c_off, in_fill), DeviceBuffer.from_numpy(packed)
+        dr, pr = _view_in(_f16(residual), res_ld, res_c_off, res_fill) if residual is not None else (None, None)
+        _chk(H.si_hip_conv2d_depthwise_f16(C.byref(d), px, dw.ptr, db.ptr if db else None, pr, py, None), "si_hip_conv2d_depthwise_f16")
+        return _ret(dy.to_numpy((n, oh, ow, out_ld), np.float16), oc, out_c_off, full)
     packed = np.zeros(H.si_hip_conv2d_f16_weight_elems(C.byref(d)), np.float16)
     _chk(H.si_hip_conv2d_f16_pack_weight_host(C.byref(d), w_oihw.ctypes.data_as(C.c_void_p), packed.ctypes.data_as(C.c_void_p)), "pack f16")
-    x = _f16(x)
-    if in_ld != ic:
-        xw = np.full((n, ih, iw, in_ld), in_fill, np.float16)
-        xw[..., :ic] = x
-        x = xw
-    dx, dw = DeviceBuffer.from_numpy(x), DeviceBuffer.from_numpy(packed)
-    dr = DeviceBuffer.from_numpy(_f16(residual)) if residual is not None else None
-    _chk(H.si_hip_conv2d_f16(C.byref(d), dx.ptr, dw.ptr, db.ptr if db else None, dr.ptr if dr else None,
-                             dy.ptr + osz * out_c_off, 1 if out_f32 else 0, None), "si_hip_conv2d_f16")
-    y = dy.to_numpy((n, oh, ow, out_ld), np.float32 if out_f32 else np.float16)
-    return y[..., out_c_off:out_c_off + oc].copy() if out_ld != oc else y
+    (dx, px), dw = _view_in(_f16(x), in_ld, in_c_off, in_fill), DeviceBuffer.from_numpy(packed)
+    dr, pr = _view_in(_f16(residual), res_ld, res_c_off, res_fill) if residual is not None else (None, None)
+    LAST_KERNEL_NAME["si_hip_conv2d_f16"] = H.si_hip_conv2d_f16_kernel_name(C.byref(d), 0).decode()
+    LAST_KERNEL_NAME["f16_tile_variant"] = int(H.si_hip_conv2d_f16_tile_variant(C.byref(d)))
+    _chk(H.si_hip_conv2d_f16(C.byref(d), px, dw.ptr, db.ptr if db else None, pr, py, 1 if out_f32 else 0, None), "si_hip_conv2d_f16")
+    return _ret(dy.to_numpy((n, oh, ow, out_ld), odt), oc, out_c_off, full)
 
 
-def conv2d_split_f16(x, w_a, b_a, w_b, b_b, act1="none"):
+def conv2d_split_f16(x, w_a, b_a, w_b, b_b, act1="none", in_ld=None, in_c_off=0, in_fill=0.0, out_ld=None, out_c_off=0, out2_ld=None, out2_c_off=0,
+                     out_fill=0.0, full=False):
     H = _native.hip()
     x = _f16(x)
     n, h, w, ic = x.shape
     oa, ob = w_a.shape[0], w_b.shape[0]
     wcat = _f32(np.concatenate([w_a, w_b], 0))
     bcat = _f32(np.concatenate([b_a, b_b], 0))
-    d = SiConv2dDesc(n, h, w, ic, ic, h, w, oa + ob, oa, 1, 1, 1, 1, 1, 1, 0, 0, 1, 1, ACT[act1], 0, oa, 0, 0.0)
+    out_ld, out2_ld = out_ld or oa, out2_ld or ob
+    d = SiConv2dDesc(n, h, w, ic, in_ld or ic, h, w, oa + ob, out_ld, 1, 1, 1, 1, 1, 1, 0, 0, 1, 1, ACT[act1], 0, oa, 0, 0.0)
     packed = np.zeros(H.si_hip_conv2d_f16_weight_elems(C.byref(d)), np.float16)
     _chk(H.si_hip_conv2d_f16_pack_weight_host(C.byref(d), wcat.ctypes.data_as(C.c_void_p), packed.ctypes.data_as(C.c_void_p)), "pack f16")
-    dx, dw, db = DeviceBuffer.from_numpy(x), DeviceBuffer.from_numpy(packed), DeviceBuffer.from_numpy(bcat)
-    dy, dy2 = DeviceBuffer(n * h * w * oa * 2), DeviceBuffer(n * h * w * ob * 2)
-    _chk(H.si_hip_conv2d_split_f16(C.byref(d), dx.ptr, dw.ptr, db.ptr, dy.ptr, oa, dy2.ptr, ob, None), "si_hip_conv2d_split_f16")
-    return dy.to_numpy((n, h, w, oa), np.float16), dy2.to_numpy((n, h, w, ob), np.float16)
+    (dx, px), dw, db = _view_in(x, in_ld, in_c_off, in_fill), DeviceBuffer.from_numpy(packed), DeviceBuffer.from_numpy(bcat)
+    (dy, py), (dy2, py2) = (_view_out((n, h, w), oa, out_ld, out_c_off, out_fill, np.float16),
+                            _view_out((n, h, w), ob, out2_ld, out2_c_off, out_fill, np.float16))
+    _chk(H.si_hip_conv2d_split_f16(C.byref(d), px, dw.ptr, db.ptr, py, oa, py2, out2_ld, None), "si_hip_conv2d_split_f16")
+    return (_ret(dy.to_numpy((n, h, w, out_ld), np.float16), oa, out_c_off, full),
+            _ret(dy2.to_numpy((n, h, w, out2_ld), np.float16), ob, out2_c_off, full))
 
 
-def maxpool2d_f16(x, k, s, p, d=(1, 1)):
+def maxpool2d_f16(x, k, s, p, d=(1, 1), in_ld=None, in_c_off=0, in_fill=0.0, out_ld=None, out_c_off=0, out_fill=0.0, full=False):
     H = _native.hip()
     x = _f16(x)
     n, ih, iw, c = x.shape
     oh, ow = conv_out_hw(ih, iw, k, s, p, d)
-    desc = SiPool2dDesc(n, ih, iw, c, c, oh, ow, c, k[0], k[1], s[0], s[1], d[0], d[1], p[0], p[1])
-    dx, dy = DeviceBuffer.from_numpy(x), DeviceBuffer(n * oh * ow * c * 2)
-    _chk(H.si_hip_maxpool2d_f16(C.byref(desc), dx.ptr, dy.ptr, None), "si_hip_maxpool2d_f16")
-    return dy.to_numpy((n, oh, ow, c), np.float16)
+    desc = SiPool2dDesc(n, ih, iw, c, in_ld or c, oh, ow, out_ld or c, k[0], k[1], s[0], s[1], d[0], d[1], p[0], p[1])
+    (dx, px), (dy, py) = _view_in(x, in_ld, in_c_off, in_fill), _view_out((n, oh, ow), c, out_ld, out_c_off, out_fill, np.float16)
+    _chk(H.si_hip_maxpool2d_f16(C.byref(desc), px, py, None), "si_hip_maxpool2d_f16")
+    return _ret(dy.to_numpy((n, oh, ow, out_ld or c), np.float16), c, out_c_off, full)
 
 
-def adaptive_avgpool2d_f16(x, out_hw):
+def adaptive_avgpool2d_f16(x, out_hw, in_ld=None, in_c_off=0, in_fill=0.0, out_ld=None, out_c_off=0, out_fill=0.0, full=False):
     H = _native.hip()
     x = _f16(x)
     n, ih, iw, c = x.shape
-    dx, dy = DeviceBuffer.from_numpy(x), DeviceBuffer(n * out_hw[0] * out_hw[1] * c * 2)
-    _chk(H.si_hip_adaptive_avgpool2d_f16(dx.ptr, n, ih, iw, c, c, dy.ptr, out_hw[0], out_hw[1], c, None),
+    (dx, px), (dy, py) = _view_in(x, in_ld, in_c_off, in_fill), _view_out((n, out_hw[0], out_hw[1]), c, out_ld, out_c_off, out_fill, np.float16)
+    _chk(H.si_hip_adaptive_avgpool2d_f16(px, n, ih, iw, c, in_ld or c, py, out_hw[0], out_hw[1], out_ld or c, None),
          "si_hip_adaptive_avgpool2d_f16")
-    return dy.to_numpy((n, out_hw[0], out_hw[1], c), np.float16)
+    return _ret(dy.to_numpy((n, out_hw[0], out_hw[1], out_ld or c), np.float16), c, out_c_off, full)
 
 
-def activation_f16(kind, x, param=0.0):
+def activation_f16(kind, x, param=0.0, in_ld=None, in_c_off=0, in_fill=0.0, out_ld=None, out_c_off=0, out_fill=0.0, full=False):
     H = _native.hip()
     x = _f16(x)
     c = x.shape[-1]
     pixels = x.size // c
-    dx, dy = DeviceBuffer.from_numpy(x), DeviceBuffer(x.nbytes)
-    _chk(H.si_hip_activation_f16(ACT[kind], float(param), dx.ptr, pixels, c, c, dy.ptr, c, None), "si_hip_activation_f16")
-    return dy.to_numpy(x.shape, np.float16)
+    (dx, px), (dy, py) = _view_in(x, in_ld, in_c_off, in_fill), _view_out(x.shape[:-1], c, out_ld, out_c_off, out_fill, np.float16)
+    _chk(H.si_hip_activation_f16(ACT[kind], float(param), px, pixels, c, in_ld or c, py, out_ld or c, None), "si_hip_activation_f16")
+    return _ret(dy.to_numpy(x.shape[:-1] + (out_ld or c,), np.float16), c, out_c_off, full)
 
 
-def binary_same_f16(op, a, b):
+def binary_same_f16(op, a, b, in_ld=None, in_c_off=0, in_fill=0.0, out_ld=None, out_c_off=0, out_fill=0.0, full=False, b_ld=None, b_c_off=0):
+    """si_hip_binary_same_f16; in_ld / in_c_off are a's view, b_ld / b_c_off b's (both gaps hold in_fill)"""
     H = _native.hip()
     a, b = _f16(a), _f16(b)
     c = a.shape[-1]
     pixels = a.size // c
-    da, db, dy = DeviceBuffer.from_numpy(a), DeviceBuffer.from_numpy(b), DeviceBuffer(a.nbytes)
-    _chk(H.si_hip_binary_same_f16({"add": 0, "mul": 2}[op], da.ptr, c, db.ptr, c, dy.ptr, c, pixels, c, None),
+    (da, pa), (db, pb) = _view_in(a, in_ld, in_c_off, in_fill), _view_in(b, b_ld, b_c_off, in_fill)
+    dy, py = _view_out(a.shape[:-1], c, out_ld, out_c_off, out_fill, np.float16)
+    _chk(H.si_hip_binary_same_f16({"add": 0, "mul": 2}[op], pa, in_ld or c, pb, b_ld or c, py, out_ld or c, pixels, c, None),
          "si_hip_binary_same_f16")
-    return dy.to_numpy(a.shape, np.float16)
+    return _ret(dy.to_numpy(a.shape[:-1] + (out_ld or c,), np.float16), c, out_c_off, full)
 
 
-def binary_bcast_f16(op, a, s):
+def binary_bcast_f16(op, a, s, in_ld=None, in_c_off=0, in_fill=0.0, out_ld=None, out_c_off=0, out_fill=0.0, full=False):
     """si_hip_binary_bcast_f16: a [n][h][w][c] (op) s [n][c] broadcast over h, w (the squeeze-excite scale)."""
     H = _native.hip()
     a, s = _f16(a), _f16(s)
     n, c = a.shape[0], a.shape[-1]
     ppi = a.size // (n * c)
-    da, ds, dy = DeviceBuffer.from_numpy(a), DeviceBuffer.from_numpy(s), DeviceBuffer(a.nbytes)
-    _chk(H.si_hip_binary_bcast_f16({"add": 0, "mul": 2}[op], da.ptr, c, ds.ptr, c, dy.ptr, c, n, ppi, c, None), "si_hip_binary_bcast_f16")
-    return dy.to_numpy(a.shape, np.float16)
+    (da, pa), ds, (dy, py) = _view_in(a, in_ld, in_c_off, in_fill), DeviceBuffer.from_numpy(s), _view_out(a.shape[:-1], c, out_ld, out_c_off, out_fill, np.float16)
+    _chk(H.si_hip_binary_bcast_f16({"add": 0, "mul": 2}[op], pa, in_ld or c, ds.ptr, c, py, out_ld or c, n, ppi, c, None), "si_hip_binary_bcast_f16")
+    return _ret(dy.to_numpy(a.shape[:-1] + (out_ld or c,), np.float16), c, out_c_off, full)
 
 
-def convert_roundtrip_f16(x):
-    """fp32 -> fp16 -> fp32 on the device (si_hip_convert_f32_f16 / si_hip_convert_f16_f32)."""
+def convert_roundtrip_f16(x, in_ld=None, in_c_off=0, in_fill=0.0, out_ld=None, out_c_off=0, out_fill=0.0, full=False):
+    """fp32 -> fp16 -> fp32 on the device (si_hip_convert_f32_f16 / si_hip_convert_f16_f32); the views are those of the fp32 input and of BOTH
+    destinations (the fp16 intermediate is read back as the slice of its rows)."""
     H = _native.hip()
     x = _f32(x)
     c = x.shape[-1]
     pixels = x.size // c
-    dx, dh, dy = DeviceBuffer.from_numpy(x), DeviceBuffer(x.size * 2), DeviceBuffer(x.nbytes)
-    _chk(H.si_hip_convert_f32_f16(dx.ptr, pixels, c, c, dh.ptr, c, None), "si_hip_convert_f32_f16")
-    half = dh.to_numpy(x.shape, np.float16)
-    _chk(H.si_hip_convert_f16_f32(dh.ptr, pixels, c, c, dy.ptr, c, None), "si_hip_convert_f16_f32")
-    return half, dy.to_numpy(x.shape)
+    old = out_ld or c
+    dx, px = _view_in(x, in_ld, in_c_off, in_fill)
+    (dh, ph), (dy, py) = _view_out(x.shape[:-1], c, old, out_c_off, out_fill, np.float16), _view_out(x.shape[:-1], c, old, out_c_off, out_fill)
+    _chk(H.si_hip_convert_f32_f16(px, pixels, c, in_ld or c, ph, old, None), "si_hip_convert_f32_f16")
+    half = _ret(dh.to_numpy(x.shape[:-1] + (old,), np.float16), c, out_c_off, full)
+    _chk(H.si_hip_convert_f16_f32(ph, pixels, c, old, py, old, None), "si_hip_convert_f16_f32")
+    return half, _ret(dy.to_numpy(x.shape[:-1] + (old,)), c, out_c_off, full)
 
 
-def conv_stem_s2c32_f16(x, w0, b0, w1, b1):
+def conv_stem_s2c32_f16(x, w0, b0, w1, b1, out_ld=None, out_c_off=0, out_fill=0.0, full=False):
     """si_hip_conv2d_stem_s2c32_f16: YOLOv5's first two convs (6x6 s2 p2 3 -> 32 SiLU, 3x3 s2 p1 32 -> oc SiLU) in one launch.
     x fp32 [n][h][w][3]; returns fp16 [n][oh][ow][oc]."""
     H = _native.hip()
@@ -1051,7 +1200,7 @@ def conv_stem_s2c32_f16(x, w0, b0, w1, b1):
     oh, ow = conv_out_hw(sh_, sw_, (3, 3), (2, 2), (1, 1), (1, 1))
     oc = w1.shape[0]
     d0 = SiConv2dDesc(n, ih, iw, 3, 3, sh_, sw_, 32, 32, 6, 6, 2, 2, 1, 1, 2, 2, 1, 1 if b0 is not None else 0, ACT["silu"], 0, 32, 0, 0.0)
-    d1 = SiConv2dDesc(n, sh_, sw_, 32, 32, oh, ow, oc, oc, 3, 3, 2, 2, 1, 1, 1, 1, 1, 1 if b1 is not None else 0, ACT["silu"], 0, oc, 0, 0.0)
+    d1 = SiConv2dDesc(n, sh_, sw_, 32, 32, oh, ow, oc, out_ld or oc, 3, 3, 2, 2, 1, 1, 1, 1, 1, 1 if b1 is not None else 0, ACT["silu"], 0, oc, 0, 0.0)
     if not H.si_hip_conv2d_stem_s2c32_f16_supported(C.byref(d0), C.byref(d1)):
         raise HipError("si_hip_conv2d_stem_s2c32_f16: unsupported shape")
     p0 = np.zeros(H.si_hip_conv2d_stem_f16_weight_elems(C.byref(d0)), np.float16)
@@ -1061,15 +1210,14 @@ def conv_stem_s2c32_f16(x, w0, b0, w1, b1):
     dx, dp0, dp1 = DeviceBuffer.from_numpy(x), DeviceBuffer.from_numpy(p0), DeviceBuffer.from_numpy(p1)
     db0 = DeviceBuffer.from_numpy(_f32(b0)) if b0 is not None else None
     db1 = DeviceBuffer.from_numpy(_f32(b1)) if b1 is not None else None
-    dy = DeviceBuffer(n * oh * ow * oc * 2)
-    dy.fill(0)
+    dy, py = _view_out((n, oh, ow), oc, out_ld, out_c_off, out_fill, np.float16)
     _chk(H.si_hip_conv2d_stem_s2c32_f16(C.byref(d0), C.byref(d1), dx.ptr, dp0.ptr, db0.ptr if db0 else None, dp1.ptr,
-                                        db1.ptr if db1 else None, dy.ptr, None), "si_hip_conv2d_stem_s2c32_f16")
+                                        db1.ptr if db1 else None, py, None), "si_hip_conv2d_stem_s2c32_f16")
     sync()
-    return dy.to_numpy((n, oh, ow, oc), np.float16)
+    return _ret(dy.to_numpy((n, oh, ow, out_ld or oc), np.float16), oc, out_c_off, full)
 
 
-def conv_stem_s2c32_pw_f16(x, w0, b0, w1, b1, w2, b2, split_oc=32, out2_ld=None, out2_c_off=0):
+def conv_stem_s2c32_pw_f16(x, w0, b0, w1, b1, w2, b2, split_oc=32, out2_ld=None, out2_c_off=0, out_ld=None, out_c_off=0, out_fill=0.0, full=False):
     """si_hip_conv2d_stem_s2c32_pw_f16: YOLOv5's first two convs AND the 1x1 conv behind them (64 -> 64, SiLU: the first C3's cv1 | cv2 over the
     concatenated filters w2 [64][64][1][1]) in one launch.  x fp32 [n][h][w][3].  split_oc = 32: returns (fp16 [n][oh][ow][32], fp16
     [n][oh][ow][32]) -- the second one written at channel offset out2_c_off of a buffer with pixel stride out2_ld; split_oc = 0: one fp16
@@ -1082,7 +1230,8 @@ def conv_stem_s2c32_pw_f16(x, w0, b0, w1, b1, w2, b2, split_oc=32, out2_ld=None,
     oc = w1.shape[0]
     d0 = SiConv2dDesc(n, ih, iw, 3, 3, sh_, sw_, 32, 32, 6, 6, 2, 2, 1, 1, 2, 2, 1, 1 if b0 is not None else 0, ACT["silu"], 0, 32, 0, 0.0)
     d1 = SiConv2dDesc(n, sh_, sw_, 32, 32, oh, ow, oc, oc, 3, 3, 2, 2, 1, 1, 1, 1, 1, 1 if b1 is not None else 0, ACT["silu"], 0, oc, 0, 0.0)
-    ld_a = 32 if split_oc else 64
+    c_a = 32 if split_oc else 64
+    ld_a = out_ld or c_a
     d2 = SiConv2dDesc(n, oh, ow, oc, oc, oh, ow, 64, ld_a, 1, 1, 1, 1, 1, 1, 0, 0, 1, 1 if b2 is not None else 0, ACT["silu"], 0, 64, 0, 0.0)
     if not H.si_hip_conv2d_stem_s2c32_pw_f16_supported(C.byref(d0), C.byref(d1), C.byref(d2), split_oc):
         raise HipError("si_hip_conv2d_stem_s2c32_pw_f16: unsupported shape")
@@ -1095,21 +1244,20 @@ def conv_stem_s2c32_pw_f16(x, w0, b0, w1, b1, w2, b2, split_oc=32, out2_ld=None,
     bufs = [DeviceBuffer.from_numpy(v) for v in (x, p0, p1, p2)]
     db = [DeviceBuffer.from_numpy(_f32(b)) if b is not None else None for b in (b0, b1, b2)]
     out2_ld = out2_ld or 32
-    dy = DeviceBuffer(n * oh * ow * ld_a * 2)
-    dy.fill(0)
-    dy2 = DeviceBuffer(n * oh * ow * out2_ld * 2)
-    dy2.fill(0)
+    (dy, py), (dy2, py2) = (_view_out((n, oh, ow), c_a, ld_a, out_c_off, out_fill, np.float16),
+                            _view_out((n, oh, ow), 32, out2_ld, out2_c_off, out_fill, np.float16))
     _chk(H.si_hip_conv2d_stem_s2c32_pw_f16(C.byref(d0), C.byref(d1), C.byref(d2), bufs[0].ptr, bufs[1].ptr, db[0].ptr if db[0] else None, bufs[2].ptr,
-                                           db[1].ptr if db[1] else None, bufs[3].ptr, db[2].ptr if db[2] else None, dy.ptr, split_oc,
-                                           dy2.ptr + 2 * out2_c_off if split_oc else None, out2_ld, None), "si_hip_conv2d_stem_s2c32_pw_f16")
+                                           db[1].ptr if db[1] else None, bufs[3].ptr, db[2].ptr if db[2] else None, py, split_oc,
+                                           py2 if split_oc else None, out2_ld, None), "si_hip_conv2d_stem_s2c32_pw_f16")
     sync()
+    ya = _ret(dy.to_numpy((n, oh, ow, ld_a), np.float16), c_a, out_c_off, full)
     if not split_oc:
-        return dy.to_numpy((n, oh, ow, 64), np.float16)
-    y2 = dy2.to_numpy((n, oh, ow, out2_ld), np.float16)
-    return dy.to_numpy((n, oh, ow, 32), np.float16), y2[..., out2_c_off:out2_c_off + 32].copy()
+        return ya
+    return ya, _ret(dy2.to_numpy((n, oh, ow, out2_ld), np.float16), 32, out2_c_off, full)
 
 
-def conv_pw_slab_f16(x, w0, b0, w1, b1, residual=None, out_ld=None, out_c_off=0, in_ld=None):
+def conv_pw_slab_f16(x, w0, b0, w1, b1, residual=None, out_ld=None, out_c_off=0, in_ld=None, in_c_off=0, in_fill=0.0, res_ld=None, res_c_off=0,
+                     res_fill=0.0, out_fill=0.0, full=False):
     """si_hip_conv2d_pw_slab_f16: the C3 bottleneck's two convs (1x1 c -> c SiLU, 3x3 s1 p1 c -> oc SiLU, optional shortcut) in one
     launch.  x NHWC fp16; returns NHWC fp16."""
     H = _native.hip()
@@ -1120,31 +1268,26 @@ def conv_pw_slab_f16(x, w0, b0, w1, b1, residual=None, out_ld=None, out_c_off=0,
     out_ld = out_ld or oc
     d0 = SiConv2dDesc(n, ih, iw, c, in_ld, ih, iw, c, c, 1, 1, 1, 1, 1, 1, 0, 0, 1, 1 if b0 is not None else 0, ACT["silu"], 0, c, 0, 0.0)
     d1 = SiConv2dDesc(n, ih, iw, c, c, ih, iw, oc, out_ld, 3, 3, 1, 1, 1, 1, 1, 1, 1, 1 if b1 is not None else 0, ACT["silu"],
-                      1 if residual is not None else 0, oc, 0, 0.0)
+                      1 if residual is not None else 0, res_ld or oc, 0, 0.0)
     if not H.si_hip_conv2d_pw_slab_f16_supported(C.byref(d0), C.byref(d1)):
         raise HipError("si_hip_conv2d_pw_slab_f16: unsupported shape")
     p0 = np.zeros(H.si_hip_conv2d_f16_weight_elems(C.byref(d0)), np.float16)
     _chk(H.si_hip_conv2d_f16_pack_weight_host(C.byref(d0), w0.ctypes.data_as(C.c_void_p), p0.ctypes.data_as(C.c_void_p)), "pack 1x1")
     p1 = np.zeros(H.si_hip_conv2d_f16_weight_elems(C.byref(d1)), np.float16)
     _chk(H.si_hip_conv2d_f16_pack_weight_host(C.byref(d1), w1.ctypes.data_as(C.c_void_p), p1.ctypes.data_as(C.c_void_p)), "pack 3x3")
-    xs = x
-    if in_ld != c:
-        xs = np.zeros((n, ih, iw, in_ld), np.float16)
-        xs[..., :c] = x
-    dx, dp0, dp1 = DeviceBuffer.from_numpy(xs), DeviceBuffer.from_numpy(p0), DeviceBuffer.from_numpy(p1)
+    (dx, px), dp0, dp1 = _view_in(x, in_ld, in_c_off, in_fill), DeviceBuffer.from_numpy(p0), DeviceBuffer.from_numpy(p1)
     db0 = DeviceBuffer.from_numpy(_f32(b0)) if b0 is not None else None
     db1 = DeviceBuffer.from_numpy(_f32(b1)) if b1 is not None else None
-    dr = DeviceBuffer.from_numpy(_f16(residual)) if residual is not None else None
-    dy = DeviceBuffer(n * ih * iw * out_ld * 2)
-    dy.fill(0)
-    _chk(H.si_hip_conv2d_pw_slab_f16(C.byref(d0), C.byref(d1), dx.ptr, dp0.ptr, db0.ptr if db0 else None, dp1.ptr, db1.ptr if db1 else None,
-                                     dr.ptr if dr else None, dy.ptr + 2 * out_c_off, None), "si_hip_conv2d_pw_slab_f16")
+    dr, pr = _view_in(_f16(residual), res_ld, res_c_off, res_fill) if residual is not None else (None, None)
+    dy, py = _view_out((n, ih, iw), oc, out_ld, out_c_off, out_fill, np.float16)
+    _chk(H.si_hip_conv2d_pw_slab_f16(C.byref(d0), C.byref(d1), px, dp0.ptr, db0.ptr if db0 else None, dp1.ptr, db1.ptr if db1 else None,
+                                     pr, py, None), "si_hip_conv2d_pw_slab_f16")
     sync()
-    y = dy.to_numpy((n, ih, iw, out_ld), np.float16)
-    return y[..., out_c_off:out_c_off + oc].copy() if out_ld != oc else y
+    return _ret(dy.to_numpy((n, ih, iw, out_ld), np.float16), oc, out_c_off, full)
 
 
-def conv_pw_cv3_f16(x, w0, b0, w1, b1, z, w3, b3, residual=None, z_ld=None, z_c_off=0, out_ld=None, out_c_off=0):
+def conv_pw_cv3_f16(x, w0, b0, w1, b1, z, w3, b3, residual=None, z_ld=None, z_c_off=0, out_ld=None, out_c_off=0, z_fill=0.0, in_ld=None, in_c_off=0,
+                    in_fill=0.0, res_ld=None, res_c_off=0, res_fill=0.0, out_fill=0.0, full=False):
     """si_hip_conv2d_pw_cv3_f16: a C3's last bottleneck pair (1x1 c -> c SiLU, 3x3 c -> c SiLU, optional shortcut) AND the C3's closing 1x1
     conv over cat([pair output, z]) in one launch (c = 64, z 64 channels, w3 [128][128][1][1]).  x, z, residual NHWC fp16; returns NHWC fp16
     [n][h][w][128].  z_ld / z_c_off: z read as a channel slice of a wider buffer."""
@@ -1154,9 +1297,9 @@ def conv_pw_cv3_f16(x, w0, b0, w1, b1, z, w3, b3, residual=None, z_ld=None, z_c_
     oc3 = w3.shape[0]
     z_ld = z_ld or z.shape[-1]
     out_ld = out_ld or oc3
-    d0 = SiConv2dDesc(n, ih, iw, c, c, ih, iw, c, c, 1, 1, 1, 1, 1, 1, 0, 0, 1, 1 if b0 is not None else 0, ACT["silu"], 0, c, 0, 0.0)
+    d0 = SiConv2dDesc(n, ih, iw, c, in_ld or c, ih, iw, c, c, 1, 1, 1, 1, 1, 1, 0, 0, 1, 1 if b0 is not None else 0, ACT["silu"], 0, c, 0, 0.0)
     d1 = SiConv2dDesc(n, ih, iw, c, c, ih, iw, c, c, 3, 3, 1, 1, 1, 1, 1, 1, 1, 1 if b1 is not None else 0, ACT["silu"],
-                      1 if residual is not None else 0, c, 0, 0.0)
+                      1 if residual is not None else 0, res_ld or c, 0, 0.0)
     d2 = SiConv2dDesc(n, ih, iw, 2 * c, 2 * c, ih, iw, oc3, out_ld, 1, 1, 1, 1, 1, 1, 0, 0, 1, 1 if b3 is not None else 0, ACT["silu"], 0, oc3, 0, 0.0)
     if not H.si_hip_conv2d_pw_cv3_f16_supported(C.byref(d0), C.byref(d1), C.byref(d2)):
         raise HipError("si_hip_conv2d_pw_cv3_f16: unsupported shape")
@@ -1165,24 +1308,28 @@ def conv_pw_cv3_f16(x, w0, b0, w1, b1, z, w3, b3, residual=None, z_ld=None, z_c_
         p = np.zeros(H.si_hip_conv2d_f16_weight_elems(C.byref(d)), np.float16)
         _chk(H.si_hip_conv2d_f16_pack_weight_host(C.byref(d), w.ctypes.data_as(C.c_void_p), p.ctypes.data_as(C.c_void_p)), "pack f16")
         packs.append(DeviceBuffer.from_numpy(p))
-    zs = z
-    if z_ld != z.shape[-1] or z_c_off:
-        zs = np.zeros((n, ih, iw, z_ld), np.float16)
-        zs[..., z_c_off:z_c_off + z.shape[-1]] = z
-    dx, dz = DeviceBuffer.from_numpy(x), DeviceBuffer.from_numpy(zs)
+    (dx, px), (dz, pz) = _view_in(x, in_ld, in_c_off, in_fill), _view_in(z, z_ld, z_c_off, z_fill)
     db = [DeviceBuffer.from_numpy(_f32(b)) if b is not None else None for b in (b0, b1, b3)]
-    dr = DeviceBuffer.from_numpy(_f16(residual)) if residual is not None else None
-    dy = DeviceBuffer(n * ih * iw * out_ld * 2)
-    dy.fill(0)
-    _chk(H.si_hip_conv2d_pw_cv3_f16(C.byref(d0), C.byref(d1), C.byref(d2), dx.ptr, packs[0].ptr, db[0].ptr if db[0] else None, packs[1].ptr,
-                                    db[1].ptr if db[1] else None, dr.ptr if dr else None, dz.ptr + 2 * z_c_off, z_ld, packs[2].ptr,
-                                    db[2].ptr if db[2] else None, dy.ptr + 2 * out_c_off, None), "si_hip_conv2d_pw_cv3_f16")
+    dr, pr = _view_in(_f16(residual), res_ld, res_c_off, res_fill) if residual is not None else (None, None)
+    dy, py = _view_out((n, ih, iw), oc3, out_ld, out_c_off, out_fill, np.float16)
+    _chk(H.si_hip_conv2d_pw_cv3_f16(C.byref(d0), C.byref(d1), C.byref(d2), px, packs[0].ptr, db[0].ptr if db[0] else None, packs[1].ptr,
+                                    db[1].ptr if db[1] else None, pr, pz, z_ld, packs[2].ptr,
+                                    db[2].ptr if db[2] else None, py, None), "si_hip_conv2d_pw_cv3_f16")
     sync()
-    y = dy.to_numpy((n, ih, iw, out_ld), np.float16)
-    return y[..., out_c_off:out_c_off + oc3].copy() if out_ld != oc3 else y
+    return _ret(dy.to_numpy((n, ih, iw, out_ld), np.float16), oc3, out_c_off, full)
 
 
-def yolo_detect_f16(feats, weights, biases, grids, anchor_grids, strides, na=3):
+def yolo_f16_tile(x_shape, na, ne, rows_total=None) -> int:
+    """si_hip_conv2d_yolo_f16_tile: the form si_hip_conv2d_yolo_f16 launches for a Detect level over an NHWC feature map of x_shape
+    (1: the Detect tile, 0: the generic tiles)"""
+    n, h, w, cin = x_shape
+    d = SiConv2dDesc(n, h, w, cin, cin, h, w, na * ne, na * ne, 1, 1, 1, 1, 1, 1, 0, 0, 1, 1, 0, 0, na * ne, 0, 0.0)
+    lv = _native.SiYoloLevel(na, ne, rows_total or h * w * na, 0, 8.0)
+    LAST_ENTRIES.append("si_hip_conv2d_yolo_f16_tile")
+    return int(_native.hip().si_hip_conv2d_yolo_f16_tile(C.byref(d), C.byref(lv)))
+
+
+def yolo_detect_f16(feats, weights, biases, grids, anchor_grids, strides, na=3, in_pad=0, in_c_off=0, in_fill=0.0):
     """si_hip_conv2d_yolo_f16 per level: fp16 features, fp32 [n][rows_total][ne] detections."""
     H = _native.hip()
     feats = [_f16(f) for f in feats]
@@ -1194,14 +1341,15 @@ def yolo_detect_f16(feats, weights, biases, grids, anchor_grids, strides, na=3):
     for f, w, b, g, a, s in zip(feats, weights, biases, grids, anchor_grids, strides):
         _, h, wd, cin = f.shape
         w = _f32(w)
-        d = SiConv2dDesc(n, h, wd, cin, cin, h, wd, na * ne, na * ne, 1, 1, 1, 1, 1, 1, 0, 0, 1, 1, 0, 0, na * ne, 0, 0.0)
+        d = SiConv2dDesc(n, h, wd, cin, cin + in_pad, h, wd, na * ne, na * ne, 1, 1, 1, 1, 1, 1, 0, 0, 1, 1, 0, 0, na * ne, 0, 0.0)
         packed = np.zeros(H.si_hip_conv2d_f16_weight_elems(C.byref(d)), np.float16)
         _chk(H.si_hip_conv2d_f16_pack_weight_host(C.byref(d), w.ctypes.data_as(C.c_void_p), packed.ctypes.data_as(C.c_void_p)), "pack")
         g2 = _f32(np.transpose(_f32(g)[0], (1, 2, 0, 3)))
         a2 = _f32(np.transpose(_f32(a)[0], (1, 2, 0, 3)))
-        bufs = [DeviceBuffer.from_numpy(v) for v in (f, packed, _f32(b), g2, a2)]
+        bufs = [None] + [DeviceBuffer.from_numpy(v) for v in (packed, _f32(b), g2, a2)]
+        bufs[0], pf = _view_in(f, cin + in_pad, in_c_off, in_fill)
         lv = _native.SiYoloLevel(na, ne, rows_total, off, float(s))
-        _chk(H.si_hip_conv2d_yolo_f16(C.byref(d), bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, C.byref(lv), bufs[3].ptr, bufs[4].ptr,
+        _chk(H.si_hip_conv2d_yolo_f16(C.byref(d), pf, bufs[1].ptr, bufs[2].ptr, C.byref(lv), bufs[3].ptr, bufs[4].ptr,
                                       dout.ptr, None), "si_hip_conv2d_yolo_f16")
         sync()
         off += h * wd * na

@@ -5,7 +5,10 @@ and conversions are exact."""
 import numpy as np
 import pytest
 
+from containment import checked_dest
 from util import assert_detect_parity, assert_exact, assert_parity, rng_uniform
+
+SENTINEL = 0x7B   # the strided cases pre-fill the wider output row with this byte (61280 as fp16) and hold everything outside the slice to it
 
 pytestmark = pytest.mark.gpu
 
@@ -59,8 +62,8 @@ def test_conv_f16_fused_epilogue_strides_and_batch_invariance(hops, orc):
     assert_parity(got, orc.activation("silu", y) + r, F16_TOL, what="silu + residual")
     got = hops.conv2d_f16(x, w, b, (1, 1), (1, 1), residual=r, act2="relu").astype(np.float32)
     assert_parity(got, orc.activation("relu", y + r), F16_TOL, what="residual + relu")
-    got = hops.conv2d_f16(x, w, b, (1, 1), (1, 1), in_ld=96, out_ld=160, out_c_off=32).astype(np.float32)
-    assert_parity(got, y, F16_TOL, what="strided tensors")
+    wide = hops.conv2d_f16(x, w, b, (1, 1), (1, 1), in_ld=96, out_ld=160, out_c_off=32, out_fill=hops.ByteFill(SENTINEL), full=True)
+    assert_parity(checked_dest(wide, 32, 64, SENTINEL, "strided tensors").astype(np.float32), y, F16_TOL, what="strided tensors")
     full = hops.conv2d_f16(x, w, b, (1, 1), (1, 1), act1="silu")
     assert_exact(hops.conv2d_f16(x[1:2], w, b, (1, 1), (1, 1), act1="silu")[0], full[1], "an image's result does not depend on the batch")
     with pytest.raises(hops.HipError):
@@ -119,8 +122,8 @@ def test_conv_f16_depthwise(hops, orc, n, hw, c, k, s, p):
     r = h(rng_uniform(c + 3, ref.shape, -1, 1))
     assert_parity(hops.conv2d_f16(x, w, b, (s, s), (p, p), (1, 1), c, residual=r, act2="relu").astype(np.float32), orc.activation("relu", ref + r), F16_TOL,
                   what="residual + relu")
-    assert_parity(hops.conv2d_f16(x, w, b, (s, s), (p, p), (1, 1), c, in_ld=c + 8, out_ld=c + 16, out_c_off=8).astype(np.float32), ref, F16_TOL,
-                  what="strided tensors")
+    wide = hops.conv2d_f16(x, w, b, (s, s), (p, p), (1, 1), c, in_ld=c + 8, out_ld=c + 16, out_c_off=8, out_fill=hops.ByteFill(SENTINEL), full=True)
+    assert_parity(checked_dest(wide, 8, c, SENTINEL, "depthwise strided").astype(np.float32), ref, F16_TOL, what="strided tensors")
     if n > 1:
         assert_exact(hops.conv2d_f16(x[1:2], w, b, (s, s), (p, p), (1, 1), c)[0], got[1], "batch invariance")
 
@@ -191,17 +194,17 @@ def test_stem_f16_strided_output_and_two_channel_image(hops, orc):
     x = rng_uniform(33, (2, 32, 32, 3), 0, 1)
     w = rng_uniform(34, (32, 3, 6, 6), -0.3, 0.3)
     ref = orc.conv2d(h(x), h(w), None, (2, 2), (2, 2), path="naive")
-    got = hops.conv2d_f16(x, w, None, (2, 2), (2, 2), in_ld=4, out_ld=96, out_c_off=32)   # strided image: element-wise loads
-    assert_parity(got.astype(np.float32), ref, F16_TOL, what="strided stem")
+    wide = hops.conv2d_f16(x, w, None, (2, 2), (2, 2), in_ld=4, out_ld=96, out_c_off=32, out_fill=hops.ByteFill(SENTINEL), full=True)   # strided image: element-wise loads
+    assert_parity(checked_dest(wide, 32, 32, SENTINEL, "strided stem").astype(np.float32), ref, F16_TOL, what="strided stem")
 
 
 def test_maxpool5_chain3_f16_exact(hops, orc):
     x = h(rng_uniform(71, (2, 20, 20, 64), -3, 3))
     cur = x
-    got = hops.maxpool5_chain3(x, half=True, out_ld=256, out_c_off=(64, 128, 192))
+    got = hops.maxpool5_chain3(x, half=True, out_ld=256, out_c_off=(64, 128, 192), out_fill=hops.ByteFill(SENTINEL), full=True)
     for k in range(3):
         cur = orc.maxpool2d(cur, (5, 5), (1, 1), (2, 2))
-        assert_exact(got[k].astype(np.float32), cur, "fp16 stage %d" % k)
+        assert_exact(checked_dest(got[k], 64 * (k + 1), 64, SENTINEL, "fp16 stage %d" % k).astype(np.float32), cur, "fp16 stage %d" % k)
 
 
 def test_conv_split_f16(hops, orc):
@@ -323,7 +326,7 @@ def test_every_f16_tile_variant_same_bits_through_epilogues_split_and_detect(hop
     for v in F16_TILES:
         tile16(v)
         outs[v] = (
-            hops.conv2d_f16(x, w, b, (1, 1), (1, 1), act1="silu", residual=r, out_ld=128, out_c_off=16),
+            checked_dest(hops.conv2d_f16(x, w, b, (1, 1), (1, 1), act1="silu", residual=r, out_ld=128, out_c_off=16, out_fill=hops.ByteFill(SENTINEL), full=True), 16, 96, SENTINEL, "tile %d" % v),
             hops.conv2d_f16(x, w, b, (1, 1), (1, 1), residual=r, act2="relu"),
             hops.conv2d_f16(x, w, b, (1, 1), (1, 1), act1="hardswish"),
         ) + tuple(hops.conv2d_split_f16(xs, wa, ba, wb, bb, act1="silu")) + (
@@ -367,7 +370,7 @@ def test_s2c32_kernel_same_bits_as_generic_tiles(hops, orc, gpu, n, ih, iw, oc, 
     with hops.plan(f16_s2c32=0):
         base = hops.conv2d_f16(x, w, b, st, (1, 1), **kw)
     got = hops.conv2d_f16(x, w, b, st, (1, 1), **kw)
-    wide = hops.conv2d_f16(x, w, b, st, (1, 1), out_ld=oc + 32, out_c_off=16, **kw)   # into a slice of a wider tensor
+    wide = checked_dest(hops.conv2d_f16(x, w, b, st, (1, 1), out_ld=oc + 32, out_c_off=16, out_fill=hops.ByteFill(SENTINEL), full=True, **kw), 16, oc, SENTINEL, "c32 patch kernel")   # into a slice of a wider tensor
     assert_exact(got, base, "c32 patch kernel vs generic tiles")
     assert_exact(wide, base, "c32 patch kernel, strided output")
     ref = orc.conv2d(x, w, b, st, (1, 1), path="naive")
@@ -407,7 +410,7 @@ def test_slab_kernel_same_bits_as_generic_tiles(hops, orc, gpu, n, hh, ww, ic, o
     got = hops.conv2d_f16(x, w, b, (1, 1), (1, 1), **kw)
     with hops.plan(f16_slab_w2=0):   # the one-wave-per-SIMD form of the 128-channel slab kernel (round 6: every W2 / NBLK / residual combination)
         assert_exact(hops.conv2d_f16(x, w, b, (1, 1), (1, 1), **kw), base, "slab kernel, one wave per SIMD")
-    wide = hops.conv2d_f16(x, w, b, (1, 1), (1, 1), out_ld=oc + 32, out_c_off=16, **kw)   # into a slice of a wider tensor
+    wide = checked_dest(hops.conv2d_f16(x, w, b, (1, 1), (1, 1), out_ld=oc + 32, out_c_off=16, out_fill=hops.ByteFill(SENTINEL), full=True, **kw), 16, oc, SENTINEL, "slab kernel")   # into a slice of a wider tensor
     kw1 = dict(kw)
     if res:
         kw1["residual"] = kw["residual"][n - 1:]
@@ -453,7 +456,7 @@ def test_bottleneck_pair_in_one_launch_same_bits(hops, orc, gpu, n, hh, ww, c, r
     want = hops.conv2d_f16(mid, w1, b1, (1, 1), (1, 1), act1="silu", residual=r)
     got = hops.conv_pw_slab_f16(x, w0, b0, w1, b1, residual=r)
     assert_exact(got, want, "fused bottleneck pair vs two launches")
-    wide = hops.conv_pw_slab_f16(x, w0, b0, w1, b1, residual=r, out_ld=c + 32, out_c_off=16, in_ld=c + 8)
+    wide = checked_dest(hops.conv_pw_slab_f16(x, w0, b0, w1, b1, residual=r, out_ld=c + 32, out_c_off=16, in_ld=c + 8, out_fill=hops.ByteFill(SENTINEL), full=True), 16, c, SENTINEL, "fused pair")
     assert_exact(wide, want, "fused pair, strided tensors")
     last = hops.conv_pw_slab_f16(x[n - 1:], w0, b0, w1, b1, residual=None if r is None else r[n - 1:])
     assert_exact(last, got[n - 1:], "fused pair, batch position")
@@ -486,7 +489,8 @@ def test_c3_tail_pair_concat_cv3_in_one_launch_same_bits(hops, orc, gpu, n, hh, 
     want = hops.conv2d_f16(np.concatenate([y, z], -1), w3, b3, (1, 1), (0, 0), act1="silu")
     got = hops.conv_pw_cv3_f16(x, w0, b0, w1, b1, z, w3, b3, residual=r)
     assert_exact(got, want, "pair + concat + cv3 in one launch vs the launches it replaces")
-    wide = hops.conv_pw_cv3_f16(x, w0, b0, w1, b1, z, w3, b3, residual=r, z_ld=160, z_c_off=64, out_ld=192, out_c_off=32)
+    wide = checked_dest(hops.conv_pw_cv3_f16(x, w0, b0, w1, b1, z, w3, b3, residual=r, z_ld=160, z_c_off=64, out_ld=192, out_c_off=32, out_fill=hops.ByteFill(SENTINEL), full=True), 32, 2 * c,
+                        SENTINEL, "pair + cv3")
     assert_exact(wide, want, "... z and the output as channel slices of wider buffers")
     last = hops.conv_pw_cv3_f16(x[n - 1:], w0, b0, w1, b1, z[n - 1:], w3, b3, residual=None if r is None else r[n - 1:])
     assert_exact(last, got[n - 1:], "... batch position")

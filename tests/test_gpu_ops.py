@@ -10,7 +10,10 @@ import os
 import numpy as np
 import pytest
 
+from containment import checked_dest
 from util import assert_detect_parity, assert_exact, assert_parity, rng_uniform
+
+SENTINEL = 0x7B   # the strided cases pre-fill the wider output row with this byte (1.3e36 as fp32) and hold everything outside the slice to it
 
 pytestmark = pytest.mark.gpu
 
@@ -111,7 +114,8 @@ def test_conv_pointwise_padded_k(hops, orc, ic, oc):
     ref = orc.conv2d(x, w, b, (1, 1), (0, 0), path="naive")
     assert_parity(hops.conv2d(x, w, b), ref, what="dense")
     assert_parity(hops.conv2d(x, w, b, act1="hardswish"), orc.activation("hardswish", ref), what="hardswish")
-    assert_parity(hops.conv2d(x, w, b, in_ld=ic + 12, out_ld=oc + 8, out_c_off=4, in_fill=np.nan), ref, what="strided, NaN beyond the channels")
+    wide = hops.conv2d(x, w, b, in_ld=ic + 12, out_ld=oc + 8, out_c_off=4, in_fill=np.nan, out_fill=hops.ByteFill(SENTINEL), full=True)
+    assert_parity(checked_dest(wide, 4, oc, SENTINEL, "strided"), ref, what="strided, NaN beyond the channels")
     name = hops.conv2d_kernel_name(x.shape, w.shape)
     assert "fast" in name, name
 
@@ -123,8 +127,11 @@ def test_conv_strided_tensors(hops, orc):
     b = rng_uniform(13, (8,), -0.5, 0.5)
     ref = orc.conv2d(x, w, b)
     assert_parity(hops.conv2d(x, w, b, in_ld=40), ref, what="in_ld")
-    assert_parity(hops.conv2d(x, w, b, out_ld=24, out_c_off=12), ref, what="out_ld + offset")
-    assert_parity(hops.conv2d(x, w, b, in_ld=18, out_ld=11, out_c_off=3), ref, what="unaligned strides")
+    F = hops.ByteFill(SENTINEL)
+    assert_parity(checked_dest(hops.conv2d(x, w, b, out_ld=24, out_c_off=12, out_fill=F, full=True), 12, 8, SENTINEL, "out_ld + offset"), ref,
+                  what="out_ld + offset")
+    assert_parity(checked_dest(hops.conv2d(x, w, b, in_ld=18, out_ld=11, out_c_off=3, out_fill=F, full=True), 3, 8, SENTINEL, "unaligned strides"), ref,
+                  what="unaligned strides")
 
 
 # (n, h, w, ic, oc, pad): YOLOv5s / ResNet18 3x3 s1 families, odd sizes (clipped 2x2 stores), every tile-block shape
@@ -178,7 +185,8 @@ def test_winograd_fused_epilogue_and_strides(hops, orc):
     y = orc.conv2d(x, wt, b, (1, 1), (1, 1), path="naive")
     assert_parity(hops.conv2d_winograd(x, wt, b, act1="silu", residual=r), orc.activation("silu", y) + r, what="silu + residual")
     assert_parity(hops.conv2d_winograd(x, wt, b, residual=r, act2="relu"), orc.activation("relu", y + r), what="residual + relu")
-    assert_parity(hops.conv2d_winograd(x, wt, b, in_ld=48, out_ld=160, out_c_off=32), y, what="strided tensors")
+    wide = hops.conv2d_winograd(x, wt, b, in_ld=48, out_ld=160, out_c_off=32, out_fill=hops.ByteFill(SENTINEL), full=True)
+    assert_parity(checked_dest(wide, 32, 64, SENTINEL, "strided tensors"), y, what="strided tensors")
     # batch invariance: bit-identical per image
     full = hops.conv2d_winograd(x, wt, b, act1="silu")
     assert_exact(hops.conv2d_winograd(x[1:2], wt, b, act1="silu")[0], full[1])
@@ -203,7 +211,8 @@ def test_winograd_half_size_units_same_bits(hops, gpu, n, h, w, ic, oc, pad):
         with hops.plan(wino23_form=form):
             outs[form] = [hops.conv2d_winograd(x, wt, b, (pad, pad)),
                           hops.conv2d_winograd(x, wt, b, (pad, pad), act1="silu", residual=r),
-                          hops.conv2d_winograd(x, wt, b, (pad, pad), residual=r, act2="relu", in_ld=ic + 16, out_ld=oc + 32, out_c_off=16)]
+                          checked_dest(hops.conv2d_winograd(x, wt, b, (pad, pad), residual=r, act2="relu", in_ld=ic + 16, out_ld=oc + 32, out_c_off=16,
+                                                            out_fill=hops.ByteFill(SENTINEL), full=True), 16, oc, SENTINEL, "form %d" % form)]
     for a, c, what in zip(outs[32], outs[16], ("plain", "silu + residual", "residual + relu, strided")):
         assert_exact(c, a, "16-tile form vs 32-tile form: " + what)
 
@@ -242,7 +251,8 @@ def test_winograd43_fused_epilogue_and_strides(hops, orc):
     w4 = lambda *a, **k: hops.conv2d_winograd(*a, tile=4, **k)  # noqa: E731
     assert_parity(w4(x, wt, b, act1="silu", residual=r), orc.activation("silu", y) + r, what="silu + residual")
     assert_parity(w4(x, wt, b, residual=r, act2="relu"), orc.activation("relu", y + r), what="residual + relu")
-    assert_parity(w4(x, wt, b, in_ld=48, out_ld=160, out_c_off=32), y, what="strided tensors")
+    wide = w4(x, wt, b, in_ld=48, out_ld=160, out_c_off=32, out_fill=hops.ByteFill(SENTINEL), full=True)
+    assert_parity(checked_dest(wide, 32, 64, SENTINEL, "strided tensors"), y, what="strided tensors")
     full = w4(x, wt, b, act1="silu")
     assert_exact(w4(x[1:2], wt, b, act1="silu")[0], full[1])
     with pytest.raises(hops.HipError):
@@ -264,7 +274,8 @@ def test_conv_depthwise_kernel(hops, orc, n, h, w, c, k, s, p, d):
     got = hops.conv2d(x, wt, b, (s, s), (p, p), (d, d), c, act1="hardswish", residual=r, act2="relu")
     assert_parity(got, orc.activation("relu", orc.activation("hardswish", ref) + r), what="depthwise fused epilogue")
     if c % 4 == 0:
-        assert_parity(hops.conv2d(x, wt, b, (s, s), (p, p), (d, d), c, in_ld=c + 8, out_ld=2 * c, out_c_off=c), ref, what="strided")
+        wide = hops.conv2d(x, wt, b, (s, s), (p, p), (d, d), c, in_ld=c + 8, out_ld=2 * c, out_c_off=c, out_fill=hops.ByteFill(SENTINEL), full=True)
+        assert_parity(checked_dest(wide, c, c, SENTINEL, "depthwise strided"), ref, what="strided")
 
 
 @pytest.mark.parametrize("n,size,oc,k,s,p", [(2, 64, 16, 3, 2, 1), (1, 33, 32, 3, 1, 1), (2, 40, 48, 3, 2, 1)])
@@ -327,9 +338,9 @@ def test_maxpool5_chain3_exact(hops, orc, n, h, w, c):
     for k in range(3):
         assert_exact(got[k], want[k], "stage %d" % k)
     # outputs as channel slices of a wider concat row (what the engine's aliasing hands over)
-    got = hops.maxpool5_chain3(x, out_ld=4 * c, out_c_off=(c, 2 * c, 3 * c))
+    got = hops.maxpool5_chain3(x, out_ld=4 * c, out_c_off=(c, 2 * c, 3 * c), out_fill=hops.ByteFill(SENTINEL), full=True)
     for k in range(3):
-        assert_exact(got[k], want[k], "strided stage %d" % k)
+        assert_exact(checked_dest(got[k], (k + 1) * c, c, SENTINEL, "strided stage %d" % k), want[k], "strided stage %d" % k)
     with pytest.raises(hops.HipError):
         hops.maxpool5_chain3(rng_uniform(1, (1, 80, 80, 8), -1, 1))      # two map planes do not fit 64 KB of LDS
     with pytest.raises(hops.HipError):
@@ -651,14 +662,15 @@ def test_stem_rolling_window_kernel(hops, orc, n, ih, iw, oc, k, p, act, strided
     x = rng_uniform(300 + k, (n, ih, iw, 3))
     w = rng_uniform(301 + k, (oc, 3, k, k), -0.3, 0.3)
     b = rng_uniform(302 + k, (oc,), -0.5, 0.5)
-    kw = dict(out_ld=oc + 8, out_c_off=4) if strided else {}
-    got = hops.conv2d(x, w, b, (2, 2), (p, p), act1=act, **kw)
+    kw = dict(out_ld=oc + 8, out_c_off=4, out_fill=hops.ByteFill(SENTINEL), full=True) if strided else {}
+    conv = (lambda *a, **k: checked_dest(hops.conv2d(*a, **k), 4, oc, SENTINEL, "strided stem")) if strided else hops.conv2d
+    got = conv(x, w, b, (2, 2), (p, p), act1=act, **kw)
     ref = orc.conv2d(x, w, b, (2, 2), (p, p), path="naive")
     ref = orc.activation(act, ref) if act != "none" else ref
     assert_parity(got, ref, 2e-5, what="rolling stem vs fp64")
     assert "conv_stem_roll" in hops.conv2d_kernel_name(x.shape, w.shape, (2, 2), (p, p))
     if n > 1:
-        one = hops.conv2d(x[n - 1:n], w, b, (2, 2), (p, p), act1=act, **kw)
+        one = conv(x[n - 1:n], w, b, (2, 2), (p, p), act1=act, **kw)
         assert_exact(one[0], got[n - 1], "stem: batch position")
 
 

@@ -8,6 +8,7 @@ on the batch it rides in (reference: Engine::Forward is per-image arithmetic, sr
 import numpy as np
 import pytest
 
+from containment import checked_dest
 from util import rng_uniform
 
 pytestmark = pytest.mark.gpu
@@ -75,7 +76,8 @@ def test_every_tile_same_bits_through_the_fused_epilogues(hops, tile, act1, res,
     outs = {}
     for v in [4, 0, 10] + SMALL_TILES:
         tile(v)
-        outs[v] = hops.conv2d(x, w, b, (1, 1), (1, 1), act1=act1, residual=r, act2=act2, out_ld=128, out_c_off=16)
+        outs[v] = checked_dest(hops.conv2d(x, w, b, (1, 1), (1, 1), act1=act1, residual=r, act2=act2, out_ld=128, out_c_off=16,
+                                           out_fill=hops.ByteFill(0x7B), full=True), 16, 96, 0x7B, "tile %d" % v)
     for v, y in outs.items():
         assert np.array_equal(y.view(np.uint32), outs[4].view(np.uint32)), "tile %d differs from the 64x64 tile" % v
 
