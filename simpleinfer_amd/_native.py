@@ -68,6 +68,12 @@ class SiUpsampleDesc(C.Structure):
         ("step_h", C.c_float), ("step_w", C.c_float)]
 
 
+class SiGroupNormDesc(C.Structure):
+    """include/si_norm.h"""
+    _fields_ = [(k, C.c_int) for k in ("n", "h", "w", "c", "groups", "in_ld", "out_ld")] + [
+        ("eps", C.c_float), ("affine", C.c_int), ("act", C.c_int), ("act_param", C.c_float)]
+
+
 class SiConv2dUpsampledSource(C.Structure):
     _fields_ = [("src", C.c_void_p), ("ih", C.c_int), ("iw", C.c_int), ("c", C.c_int), ("ld", C.c_int), ("c0", C.c_int),
                 ("inv_scale_h", C.c_float), ("inv_scale_w", C.c_float)]
@@ -232,11 +238,19 @@ def hip():
         "si_hip_yolo_postprocess_workspace_bytes": (sz, [i, i, i]),
         "si_hip_yolo_postprocess_f32": (i, [vp, i, i, i, f, f, i, vp, vp, vp, i, vp, sz, vp]),
     }
-    for name, (res, args) in sig.items():
+    # include/si_norm.h: nn.GroupNorm / nn.InstanceNorm2d (a header and a table of their own, as si_shard.h has)
+    norm = {
+        "si_hip_groupnorm_workspace_bytes": (sz, [C.POINTER(SiGroupNormDesc)]),
+        "si_hip_groupnorm_f32": (i, [C.POINTER(SiGroupNormDesc), vp, vp, vp, vp, vp, vp]),
+        "si_hip_groupnorm_f16": (i, [C.POINTER(SiGroupNormDesc), vp, vp, vp, vp, vp, vp]),
+        "si_hip_groupnorm_kernel_name": (C.c_char_p, [C.POINTER(SiGroupNormDesc), vp, vp, i]),
+    }
+    for name, (res, args) in list(sig.items()) + list(norm.items()):
         fn = getattr(L, name)  # AttributeError here = header/library mismatch, which tests check
         fn.restype = res
         fn.argtypes = args
     L._si_signatures = sig
+    L._si_norm_signatures = norm
     _hip = L
     return L
 

@@ -9,6 +9,7 @@
 #include "layer/cat.h"
 #include "layer/conv_2d.h"
 #include "layer/conv_transpose_2d.h"
+#include "layer/group_norm.h"
 #include "layer/linear.h"
 #include "layer/max_pool_2d.h"
 #include "layer/output_cast.h"
@@ -27,7 +28,7 @@ bool HonoursPixelStride(const std::string& type) {
     static const std::set<std::string> ok = {
         "nn.Conv2d", "nn.ConvTranspose2d", "nn.SiLU", "nn.ReLU", "nn.Sigmoid", "nn.Hardsigmoid", "nn.Hardswish", "nn.LeakyReLU",
         "nn.MaxPool2d", "nn.AdaptiveAvgPool2d", "nn.Upsample", "F.interpolate", "F.upsample", "torch.cat", "BinaryOp", "UnaryOp", "nn.BatchNorm2d",
-        "torch.flatten", "models.yolo.Detect", "pnnx.Output"};
+        "nn.GroupNorm", "nn.InstanceNorm2d", "torch.flatten", "models.yolo.Detect", "pnnx.Output"};
     return ok.count(type) > 0;
 }
 
@@ -534,6 +535,20 @@ Status EngineImpl::FuseEpilogues(std::vector<Step>& order) {
             ct->SetFusion(a->ActCode(), a->ActCode() == SI_ACT_LEAKYRELU ? a->ActParam() : 0.0f);
             ct->SetOutputNodes({tensor_nodes_[c->outputs[0]->name]});
             removed[index[c]] = true;   // (the activation reads nothing else: the fused launch keeps the conv's slot)
+            fused_ops_.insert(c->name);
+            dead_operands_.insert(out->name);
+            continue;
+        }
+        // group / instance norm -> act  ==>  one launch (or the same two): the activation runs in the normalise pass's epilogue
+        if (GroupNorm* gn = dynamic_cast<GroupNorm*>(order[i].layer)) {
+            if ((order[i].op->type != "nn.GroupNorm" && order[i].op->type != "nn.InstanceNorm2d") || order[i].op->outputs.size() != 1) continue;
+            const pnnx::Operand* out = order[i].op->outputs[0];
+            const pnnx::Operator* c = sole_consumer(out);
+            ActivationLayer* a = c ? dynamic_cast<ActivationLayer*>(order[index[c]].layer) : nullptr;
+            if (!a || c->inputs.size() != 1 || c->outputs.size() != 1) continue;
+            gn->SetFusion(a->ActCode(), a->ActCode() == SI_ACT_LEAKYRELU ? a->ActParam() : 0.0f);
+            gn->SetOutputNodes({tensor_nodes_[c->outputs[0]->name]});
+            removed[index[c]] = true;
             fused_ops_.insert(c->name);
             dead_operands_.insert(out->name);
             continue;

@@ -16,6 +16,7 @@ SI_DECLARE_LAYER(Cat)
 SI_DECLARE_LAYER(Conv2d)
 SI_DECLARE_LAYER(ConvTranspose2d)
 SI_DECLARE_LAYER(Flatten)
+SI_DECLARE_LAYER(GroupNorm)
 SI_DECLARE_LAYER(HardSigmoid)
 SI_DECLARE_LAYER(HardSwish)
 SI_DECLARE_LAYER(LeakyReLU)
@@ -34,7 +35,8 @@ SI_DECLARE_LAYER(YoloDetect)
 static std::map<std::string, LayerRegistryEntry>& Table() {
     // the 15 type strings of reference src/layer_registry.cpp:33-49, plus nn.LeakyReLU
     // (north_star extension) nn.ConvTranspose2d (U-Net / segmentation decoders; no reference layer)
-    // and F.interpolate / F.upsample, the functional spellings of nn.Upsample
+    // F.interpolate / F.upsample, the functional spellings of nn.Upsample, and nn.GroupNorm / nn.InstanceNorm2d (one class: the
+    // instance norm is the group norm with one group per channel)
     static std::map<std::string, LayerRegistryEntry> table = {
         SI_ENTRY("nn.AdaptiveAvgPool2d", AdaptiveAvgPool2d),
         SI_ENTRY("nn.BatchNorm2d", BatchNorm2d),
@@ -43,8 +45,10 @@ static std::map<std::string, LayerRegistryEntry>& Table() {
         SI_ENTRY("nn.Conv2d", Conv2d),
         SI_ENTRY("nn.ConvTranspose2d", ConvTranspose2d),
         SI_ENTRY("torch.flatten", Flatten),
+        SI_ENTRY("nn.GroupNorm", GroupNorm),
         SI_ENTRY("nn.Hardsigmoid", HardSigmoid),
         SI_ENTRY("nn.Hardswish", HardSwish),
+        SI_ENTRY("nn.InstanceNorm2d", GroupNorm),
         SI_ENTRY("nn.LeakyReLU", LeakyReLU),
         SI_ENTRY("nn.Linear", Linear),
         SI_ENTRY("nn.MaxPool2d", MaxPool2d),

@@ -881,6 +881,46 @@ def batchnorm2d(x, mean, var, gamma, beta, eps, in_ld=None, in_c_off=0, in_fill=
     return _ret(dy.to_numpy(x.shape[:-1] + (out_ld or c,)), c, out_c_off, full)
 
 
+def group_norm_desc(x_shape, groups, eps=1e-5, affine=False, act1="none", act_param=0.0, in_ld=None, out_ld=None):
+    """SiGroupNormDesc (include/si_norm.h) of an NHWC input"""
+    n, h, w, c = x_shape
+    return _native.SiGroupNormDesc(n, h, w, c, int(groups), in_ld or c, out_ld or c, float(eps), 1 if affine else 0, ACT[act1], float(act_param))
+
+
+def group_norm(x, groups, gamma=None, beta=None, eps=1e-5, act1="none", act_param=0.0, half=False, in_ld=None, in_c_off=0, in_fill=0.0,
+               out_ld=None, out_c_off=0, out_fill=0.0, full=False, workspace=True):
+    """si_hip_groupnorm_f32 / _f16 (half=True, or an fp16 array) on an NHWC array: nn.GroupNorm(groups, C) in eval mode, nn.InstanceNorm2d
+    with groups = C.  gamma / beta: both or neither.  The view hooks are the common ones; the workspace of the two-launch form is a
+    DeviceBuffer of its own (guard_bands sees it); workspace=False hands the kernel a null workspace (the refusal test)."""
+    H = _native.hip()
+    x = np.asarray(x)
+    half = bool(half) or x.dtype == np.float16
+    x = _f16(x) if half else _f32(x)
+    n, h, w, c = x.shape
+    assert (gamma is None) == (beta is None), "gamma and beta: both or neither"
+    d = group_norm_desc(x.shape, groups, eps, gamma is not None, act1, act_param, in_ld, out_ld)
+    dg = DeviceBuffer.from_numpy(_f32(gamma)) if gamma is not None else None
+    db = DeviceBuffer.from_numpy(_f32(beta)) if beta is not None else None
+    (dx, px), (dy, py) = _view_in(x, in_ld, in_c_off, in_fill), _view_out(x.shape[:-1], c, out_ld, out_c_off, out_fill, x.dtype)
+    nbytes = H.si_hip_groupnorm_workspace_bytes(C.byref(d))
+    dw = DeviceBuffer(nbytes) if (nbytes and workspace) else None
+    LAST_KERNEL_NAME["si_hip_groupnorm"] = H.si_hip_groupnorm_kernel_name(C.byref(d), C.c_void_p(px), C.c_void_p(py), 1 if half else 0).decode()
+    fn, name = (H.si_hip_groupnorm_f16, "si_hip_groupnorm_f16") if half else (H.si_hip_groupnorm_f32, "si_hip_groupnorm_f32")
+    _chk(fn(C.byref(d), px, dg.ptr if dg else None, db.ptr if db else None, py, dw.ptr if dw else None, None), name)
+    return _ret(dy.to_numpy(x.shape[:-1] + (out_ld or c,), x.dtype), c, out_c_off, full)
+
+
+def group_norm_kernel_name(x_shape, groups, half=False, in_ld=None, out_ld=None) -> str:
+    """the kernel(s) for 16-byte aligned buffers of these shapes"""
+    d = group_norm_desc(x_shape, groups, in_ld=in_ld, out_ld=out_ld)
+    return _native.hip().si_hip_groupnorm_kernel_name(C.byref(d), C.c_void_p(256), C.c_void_p(256), 1 if half else 0).decode()
+
+
+def group_norm_workspace_bytes(x_shape, groups) -> int:
+    d = group_norm_desc(x_shape, groups)
+    return int(_native.hip().si_hip_groupnorm_workspace_bytes(C.byref(d)))
+
+
 def flatten_nhwc(x, in_ld=None, in_c_off=0, in_fill=0.0):
     H = _native.hip()
     x = _f32(x)

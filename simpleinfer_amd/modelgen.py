@@ -280,6 +280,30 @@ class PnnxBuilder:
         self._emit("nn.BatchNorm2d", name, [x], [out], dict(affine=True, eps=float(eps), num_features=c), attrs)
         return out
 
+    def _norm_affine(self, name: str, c: int) -> Dict[str, np.ndarray]:
+        return dict(weight=seeded_uniform(name + ".weight", (c,), 0.5, 1.5, self.seed),
+                    bias=seeded_uniform(name + ".bias", (c,), -0.5, 0.5, self.seed))
+
+    def group_norm(self, x: str, groups: int, eps: float = 1e-5, affine: bool = True) -> str:
+        """pnnx's nn.GroupNorm line: num_groups, num_channels, eps, affine and, when affine, weight / bias of shape (C)"""
+        n, c, h, w = self.shapes[x]
+        assert groups > 0 and c % groups == 0, (c, groups)
+        name = self._opname("gn")
+        out = self._new_operand((n, c, h, w))
+        self._emit("nn.GroupNorm", name, [x], [out], dict(affine=bool(affine), eps=float(eps), num_channels=c, num_groups=int(groups)),
+                   self._norm_affine(name, c) if affine else {})
+        return out
+
+    def instance_norm(self, x: str, eps: float = 1e-5, affine: bool = False, track_running_stats: bool = False) -> str:
+        """pnnx's nn.InstanceNorm2d line: num_features, eps, affine, track_running_stats and, when affine, weight / bias"""
+        n, c, h, w = self.shapes[x]
+        name = self._opname("in")
+        out = self._new_operand((n, c, h, w))
+        self._emit("nn.InstanceNorm2d", name, [x], [out],
+                   dict(affine=bool(affine), eps=float(eps), num_features=c, track_running_stats=bool(track_running_stats)),
+                   self._norm_affine(name, c) if affine else {})
+        return out
+
     def flatten(self, x: str) -> str:
         shp = self.shapes[x]
         out = self._new_operand((shp[0], int(np.prod(shp[1:]))))
@@ -452,18 +476,23 @@ def build_toy_classifier(batch: int = 2, size: int = 32, seed: int = 0) -> PnnxB
 
 
 def build_toy_unet(batch: int = 2, size: int = 64, base: int = 16, depth: int = 3, ncls: int = 4, seed: int = 0,
-                   up: str = "convtranspose") -> PnnxBuilder:
+                   up: str = "convtranspose", norm: str = "bn", act: str = "relu", norm_groups: int = 4) -> PnnxBuilder:
     """A small U-Net: per encoder level two [conv3x3 -> BatchNorm2d -> ReLU] then MaxPool2d(2, 2); the same block as bottleneck;
     per decoder level an up-conv, torch.cat([skip, up]) and two blocks; a 1x1 conv head.  The up-convs alternate k2 s2 p0 (one
     tap per output pixel) and k3 s2 p1 output_padding 1 (four sub-pixel phases of 4 / 2 / 2 / 1 taps).  up="bilinear": each up-conv
-    is nn.Upsample(scale_factor=2, mode="bilinear", align_corners=True) + conv3x3 instead (the other widely used decoder)."""
+    is nn.Upsample(scale_factor=2, mode="bilinear", align_corners=True) + conv3x3 instead (the other widely used decoder).
+    norm="gn": nn.GroupNorm(norm_groups, c) in place of every BatchNorm2d (the diffusion / modern segmentation U-Net block);
+    norm="in": nn.InstanceNorm2d(c), no affine (the pix2pix / CycleGAN generator block).  act="silu": nn.SiLU for every ReLU."""
     assert up in ("convtranspose", "bilinear"), up
+    assert norm in ("bn", "gn", "in") and act in ("relu", "silu"), (norm, act)
     b = PnnxBuilder(seed)
     x = b.input((batch, 3, size, size))
 
     def block(x, c):
         for _ in range(2):
-            x = b.relu(b.batchnorm(b.conv(x, c, 3, 1, 1)))
+            x = b.conv(x, c, 3, 1, 1)
+            x = b.batchnorm(x) if norm == "bn" else b.group_norm(x, norm_groups) if norm == "gn" else b.instance_norm(x)
+            x = b.relu(x) if act == "relu" else b.silu(x)
         return x
 
     skips, c = [], base
