@@ -74,6 +74,12 @@ class SiGroupNormDesc(C.Structure):
         ("eps", C.c_float), ("affine", C.c_int), ("act", C.c_int), ("act_param", C.c_float)]
 
 
+class SiPad2dDesc(C.Structure):
+    """include/si_pad.h"""
+    _fields_ = [(k, C.c_int) for k in ("n", "ih", "iw", "c", "in_ld", "oh", "ow", "out_ld", "pad_l", "pad_r", "pad_t", "pad_b", "mode")] + [
+        ("value", C.c_float)]
+
+
 class SiConv2dUpsampledSource(C.Structure):
     _fields_ = [("src", C.c_void_p), ("ih", C.c_int), ("iw", C.c_int), ("c", C.c_int), ("ld", C.c_int), ("c0", C.c_int),
                 ("inv_scale_h", C.c_float), ("inv_scale_w", C.c_float)]
@@ -245,12 +251,19 @@ def hip():
         "si_hip_groupnorm_f16": (i, [C.POINTER(SiGroupNormDesc), vp, vp, vp, vp, vp, vp]),
         "si_hip_groupnorm_kernel_name": (C.c_char_p, [C.POINTER(SiGroupNormDesc), vp, vp, i]),
     }
-    for name, (res, args) in list(sig.items()) + list(norm.items()):
+    # include/si_pad.h: the explicit 2-D pads (again a header and a table of their own)
+    pad = {
+        "si_hip_pad2d_f32": (i, [C.POINTER(SiPad2dDesc), vp, vp, vp]),
+        "si_hip_pad2d_f16": (i, [C.POINTER(SiPad2dDesc), vp, vp, vp]),
+        "si_hip_pad2d_kernel_name": (C.c_char_p, [C.POINTER(SiPad2dDesc), vp, vp, i]),
+    }
+    for name, (res, args) in list(sig.items()) + list(norm.items()) + list(pad.items()):
         fn = getattr(L, name)  # AttributeError here = header/library mismatch, which tests check
         fn.restype = res
         fn.argtypes = args
     L._si_signatures = sig
     L._si_norm_signatures = norm
+    L._si_pad_signatures = pad
     _hip = L
     return L
 

@@ -950,9 +950,12 @@ bool Conv2d::HalfStorageOk(std::string& why) const {
     memset(&d, 0, sizeof(d));
     d.ic = in_channels_; d.oc = out_channels_; d.kh = kernel_h_; d.kw = kernel_w_; d.groups = groups_;
     d.sh = stride_h_; d.sw = stride_w_; d.dh = dilation_h_; d.dw = dilation_w_; d.pt = padding_t_; d.pl = padding_l_;
-    if (si_hip_conv2d_f16_supported(&d) != 0) return true;
-    why = "no fp16 conv kernel for " + std::to_string(in_channels_) + " -> " + std::to_string(out_channels_) + " channels, groups " +
-          std::to_string(groups_) + " (needs ic / groups % 32 == 0, an ungrouped conv with ic % 8 == 0, a depthwise conv with ic % 8 == 0, or an RGB stem)";
+    // (2 is the stem kernel, which reads an fp32 image: PrecisionMode takes it under exactly these conditions, and a stem shape has no other fp16 kernel --
+    // behind a half producer, an explicit pad in front of a generator's 7x7 stem for one, the layer runs in fp32 between casts)
+    const int kind = si_hip_conv2d_f16_supported(&d);
+    if (2 == kind ? (!IsHalf(in) && !residual_node_ && !sibling_) : 0 != kind) return true;
+    why ="no fp16 conv kernel for " + std::to_string(in_channels_) + " -> " + std::to_string(out_channels_) + " channels, groups " +
+          std::to_string(groups_) + " (needs ic / groups % 32 == 0, an ungrouped conv with ic % 8 == 0, a depthwise conv with ic % 8 == 0, or an RGB stem on an fp32 image)";
     return false;
 }
 

@@ -8,6 +8,7 @@
 namespace SimpleInfer {
 
 DEFINE_LAYER_REGISTRY(UnaryOp);
+DEFINE_LAYER_REGISTRY(Tanh);
 
 Status UnaryOp::Init(const pnnx::Operator* op) {
     CHECK_STATUS(Layer::Init(op));
@@ -18,6 +19,16 @@ Status UnaryOp::Init(const pnnx::Operator* op) {
         return Status::kUnsupport;
     }
     return Status::kSuccess;
+}
+
+Status Tanh::Init(const pnnx::Operator* op) {
+    CHECK_STATUS(Layer::Init(op));
+    unary_op_type_ = 16;
+    return Status::kSuccess;
+}
+
+const char* Tanh::KernelName() const {
+    return !input_tensor_nodes_.empty() && IsHalf(input_tensor_nodes_[0]->tensor) ? "unary_h_kernel" : "unary_kernel";
 }
 
 Status UnaryOp::Validate() {

@@ -21,4 +21,12 @@ public:
                              // 14 atan 15 reciprocal 16 tanh 17 log10
 };
 
+// nn.Tanh as a module (the last layer of the CycleGAN / pix2pix generators): UnaryOp code 16 on the same kernels, fp32 and fp16
+// storage, pixel strides honoured.  Not an SI_ACT_*: it is fused into no epilogue.
+class Tanh : public UnaryOp {
+public:
+    virtual Status Init(const pnnx::Operator* op) override;
+    virtual const char* KernelName() const override;   // the kernel family of the bound storage type
+};
+
 }  // namespace SimpleInfer

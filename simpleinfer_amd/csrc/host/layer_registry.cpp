@@ -22,9 +22,11 @@ SI_DECLARE_LAYER(HardSwish)
 SI_DECLARE_LAYER(LeakyReLU)
 SI_DECLARE_LAYER(Linear)
 SI_DECLARE_LAYER(MaxPool2d)
+SI_DECLARE_LAYER(Pad2d)
 SI_DECLARE_LAYER(ReLU)
 SI_DECLARE_LAYER(Sigmoid)
 SI_DECLARE_LAYER(SiLU)
+SI_DECLARE_LAYER(Tanh)
 SI_DECLARE_LAYER(UnaryOp)
 SI_DECLARE_LAYER(Upsample)
 SI_DECLARE_LAYER(YoloDetect)
@@ -36,10 +38,13 @@ static std::map<std::string, LayerRegistryEntry>& Table() {
     // the 15 type strings of reference src/layer_registry.cpp:33-49, plus nn.LeakyReLU
     // (north_star extension) nn.ConvTranspose2d (U-Net / segmentation decoders; no reference layer)
     // F.interpolate / F.upsample, the functional spellings of nn.Upsample, and nn.GroupNorm / nn.InstanceNorm2d (one class: the
-    // instance norm is the group norm with one group per channel)
+    // instance norm is the group norm with one group per channel); the explicit pads (one class, layer/pad_2d.h) and nn.Tanh
+    // (UnaryOp code 16 as a module)
     static std::map<std::string, LayerRegistryEntry> table = {
         SI_ENTRY("nn.AdaptiveAvgPool2d", AdaptiveAvgPool2d),
         SI_ENTRY("nn.BatchNorm2d", BatchNorm2d),
+        SI_ENTRY("nn.CircularPad2d", Pad2d),
+        SI_ENTRY("nn.ConstantPad2d", Pad2d),
         SI_ENTRY("BinaryOp", BinaryOp),
         SI_ENTRY("torch.cat", Cat),
         SI_ENTRY("nn.Conv2d", Conv2d),
@@ -52,13 +57,18 @@ static std::map<std::string, LayerRegistryEntry>& Table() {
         SI_ENTRY("nn.LeakyReLU", LeakyReLU),
         SI_ENTRY("nn.Linear", Linear),
         SI_ENTRY("nn.MaxPool2d", MaxPool2d),
+        SI_ENTRY("nn.ReflectionPad2d", Pad2d),
         SI_ENTRY("nn.ReLU", ReLU),
+        SI_ENTRY("nn.ReplicationPad2d", Pad2d),
         SI_ENTRY("nn.Sigmoid", Sigmoid),
         SI_ENTRY("nn.SiLU", SiLU),
+        SI_ENTRY("nn.Tanh", Tanh),
         SI_ENTRY("UnaryOp", UnaryOp),   // emitted by expand_expression, never registered by the reference
         SI_ENTRY("nn.Upsample", Upsample),
+        SI_ENTRY("nn.ZeroPad2d", Pad2d),
         SI_ENTRY("F.interpolate", Upsample),
         SI_ENTRY("F.upsample", Upsample),
+        SI_ENTRY("F.pad", Pad2d),
         SI_ENTRY("models.yolo.Detect", YoloDetect),
     };
     return table;

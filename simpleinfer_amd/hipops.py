@@ -921,6 +921,39 @@ def group_norm_workspace_bytes(x_shape, groups) -> int:
     return int(_native.hip().si_hip_groupnorm_workspace_bytes(C.byref(d)))
 
 
+PAD_MODE = {"constant": 0, "reflect": 1, "replicate": 2, "circular": 3}
+
+
+def pad2d_desc(x_shape, pads, mode="constant", value=0.0, in_ld=None, out_ld=None):
+    """SiPad2dDesc (include/si_pad.h) of an NHWC input; pads = (left, right, top, bottom) as torch orders them, negative: crop"""
+    n, ih, iw, c = x_shape
+    pl, pr, pt, pb = (int(p) for p in pads)
+    return _native.SiPad2dDesc(n, ih, iw, c, in_ld or c, ih + pt + pb, iw + pl + pr, out_ld or c, pl, pr, pt, pb, PAD_MODE[mode], float(value))
+
+
+def pad2d(x, pads, mode="constant", value=0.0, in_ld=None, in_c_off=0, in_fill=0.0, out_ld=None, out_c_off=0, out_fill=0.0, full=False):
+    """si_hip_pad2d_f32 / _f16 (by the array's dtype) on an NHWC array: torch.nn.functional.pad(x, (l, r, t, b), mode, value) on the last
+    two dimensions of the NCHW tensor.  The array's bits travel as they are (a NaN payload, -0.0).  The view hooks are the common ones."""
+    H = _native.hip()
+    x = _float_storage(x)
+    half = x.dtype == np.float16
+    n, ih, iw, c = x.shape
+    d = pad2d_desc(x.shape, pads, mode, value, in_ld, out_ld)
+    if d.oh < 1 or d.ow < 1:
+        raise HipError("si_hip_pad2d: pads %r leave no output for a %dx%d input" % (tuple(pads), ih, iw))
+    (dx, px), (dy, py) = _view_in(x, in_ld, in_c_off, in_fill), _view_out((n, d.oh, d.ow), c, out_ld, out_c_off, out_fill, x.dtype)
+    LAST_KERNEL_NAME["si_hip_pad2d"] = H.si_hip_pad2d_kernel_name(C.byref(d), C.c_void_p(px), C.c_void_p(py), 1 if half else 0).decode()
+    fn, name = (H.si_hip_pad2d_f16, "si_hip_pad2d_f16") if half else (H.si_hip_pad2d_f32, "si_hip_pad2d_f32")
+    _chk(fn(C.byref(d), px, py, None), name)
+    return _ret(dy.to_numpy((n, d.oh, d.ow, out_ld or c), x.dtype), c, out_c_off, full)
+
+
+def pad2d_kernel_name(x_shape, pads, mode="constant", half=False, in_ld=None, out_ld=None) -> str:
+    """the instantiation for 16-byte aligned buffers of these shapes ("none": a descriptor the launch refuses)"""
+    d = pad2d_desc(x_shape, pads, mode, 0.0, in_ld, out_ld)
+    return _native.hip().si_hip_pad2d_kernel_name(C.byref(d), C.c_void_p(256), C.c_void_p(256), 1 if half else 0).decode()
+
+
 def flatten_nhwc(x, in_ld=None, in_c_off=0, in_fill=0.0):
     H = _native.hip()
     x = _f32(x)

@@ -180,6 +180,34 @@ class PnnxBuilder:
     def sigmoid(self, x): return self._unary("nn.Sigmoid", "sigmoid", x)
     def hardsigmoid(self, x): return self._unary("nn.Hardsigmoid", "hsigmoid", x)
     def hardswish(self, x): return self._unary("nn.Hardswish", "hswish", x)
+    def tanh(self, x): return self._unary("nn.Tanh", "tanh", x)
+
+    PAD_MODULES = {"reflect": "nn.ReflectionPad2d", "replicate": "nn.ReplicationPad2d", "circular": "nn.CircularPad2d"}
+
+    def pad(self, x: str, pads, mode: str = "constant", value=0.0, functional: bool = False, module: str = None) -> str:
+        """An explicit pad of H and W.  pads: one int (all four sides), (left, right) or (left, right, top, bottom), torch's order;
+        negative: crop.  functional=False: the module line with torch's constructor keys -- nn.ReflectionPad2d / nn.ReplicationPad2d /
+        nn.CircularPad2d by mode; mode "constant": nn.ZeroPad2d when value == 0, else nn.ConstantPad2d with its value (module=:
+        that type string instead) -- padding written as given (an int stays an int).  functional=True: the F.pad line with pad=,
+        mode= and value= (None when value is None or the mode is not constant, as torch's default)."""
+        n, c, h, w = self.shapes[x]
+        p4 = (pads,) * 4 if isinstance(pads, int) else tuple(int(p) for p in pads) + (0, 0) * (len(pads) == 2)
+        assert len(p4) == 4, pads
+        pl, pr, pt, pb = p4
+        out = self._new_operand((n, c, h + pt + pb, w + pl + pr))
+        if functional:
+            assert not isinstance(pads, int), "F.pad takes a tuple"
+            v = "None" if (value is None or mode != "constant") else value
+            self._emit("F.pad", self._opname("F_pad"), [x], [out], dict(mode=mode, pad=tuple(int(p) for p in pads), value=v))
+            return out
+        typ = module or self.PAD_MODULES.get(mode) or ("nn.ZeroPad2d" if not value else "nn.ConstantPad2d")
+        assert mode in self.PAD_MODULES or mode == "constant", mode
+        assert len(p4) == 4 and (isinstance(pads, int) or len(pads) == 4), "the 2-D modules take one int or four"
+        params = dict(padding=pads if isinstance(pads, int) else p4)
+        if typ == "nn.ConstantPad2d":
+            params["value"] = value
+        self._emit(typ, self._opname("pad"), [x], [out], params)
+        return out
 
     def maxpool(self, x: str, k: int, s: int, p: int) -> str:
         n, c, h, w = self.shapes[x]
@@ -510,6 +538,32 @@ def build_toy_unet(batch: int = 2, size: int = 64, base: int = 16, depth: int = 
             u = b.conv_transpose(x, c, 2, 2, 0) if i % 2 == 0 else b.conv_transpose(x, c, 3, 2, 1, output_padding=1)
         x = block(b.cat([skip, u]), c)
     x = b.conv(x, ncls, 1, 1, 0)
+    b.output(x)
+    return b
+
+
+def build_toy_cyclegan(batch: int = 2, size: int = 32, base: int = 8, blocks: int = 2, pad: str = "reflect", seed: int = 0) -> PnnxBuilder:
+    """The CycleGAN / Johnson style-transfer ResNet generator at toy width: ReflectionPad2d(3) -> conv7x7 (p = 0) -> InstanceNorm2d
+    (no affine) -> ReLU; two stride-2 conv3x3 -> IN -> ReLU; `blocks` residual blocks [pad 1 -> conv3x3 (p = 0) -> IN -> ReLU ->
+    pad 1 -> conv3x3 (p = 0) -> IN] + x; two ConvTranspose2d(3, s2, p1, op1) -> IN -> ReLU; ReflectionPad2d(3) -> conv7x7 -> Tanh.
+    pad: the mode of every explicit pad ("reflect", "replicate", "circular", "constant").  At size 32 the residual blocks run at
+    8 x 8: every reflect pad is below its input size."""
+    b = PnnxBuilder(seed)
+    x = b.input((batch, 3, size, size))
+
+    def cnr(x, c, k, s, p):
+        return b.relu(b.instance_norm(b.conv(x, c, k, s, p)))
+
+    x = cnr(b.pad(x, 3, pad), base, 7, 1, 0)
+    x = cnr(x, 2 * base, 3, 2, 1)
+    x = cnr(x, 4 * base, 3, 2, 1)
+    for _ in range(blocks):
+        y = cnr(b.pad(x, 1, pad), 4 * base, 3, 1, 0)
+        y = b.instance_norm(b.conv(b.pad(y, 1, pad), 4 * base, 3, 1, 0))
+        x = b.add(x, y)
+    for c in (2 * base, base):
+        x = b.relu(b.instance_norm(b.conv_transpose(x, c, 3, 2, 1, output_padding=1)))
+    x = b.tanh(b.conv(b.pad(x, 3, pad), 3, 7, 1, 0))
     b.output(x)
     return b
 
