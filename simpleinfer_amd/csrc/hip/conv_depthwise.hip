@@ -202,8 +202,26 @@ void si_conv_depthwise_pack(const SiConv2dDesc* d, const float* w_oihw, float* w
         for (int t = 0; t < taps; ++t) w_packed[(size_t)t * d->ic + c] = w_oihw[(size_t)c * taps + t];
 }
 
-const char* si_conv_depthwise_name(const SiConv2dDesc* d) {
-    return (d->ic % 4 == 0) ? "conv_depthwise_kernel<true, 4>" : "conv_depthwise_kernel<false, 4>";
+// The launch's own choice, shared with si_conv_depthwise_name so the two cannot drift.
+// the strides' part of the 4-channel-vector condition (the pointers' 16-byte alignment is the other part)
+static bool dw_vec_strides(const SiConv2dDesc* d) {
+    return (d->ic % 4 == 0) && (d->in_ld % 4 == 0) && (d->out_ld % 4 == 0) && (!d->has_residual || d->res_ld % 4 == 0);
+}
+// which conv_depthwise_cols_kernel<4, KW, SW> serves a vector launch: 0 <3, 1>, 1 <3, 2>, 2 <5, 1>, 3 <5, 2>; -1: the generic kernel.
+// Only the column axis (kw, sw) is compile-time; kh, sh, pt and pl are run-time values in that kernel.
+static int dw_cols_form(const SiConv2dDesc* d) {
+    if (d->dh != 1 || d->dw != 1 || (d->kw != 3 && d->kw != 5) || (d->sw != 1 && d->sw != 2)) return -1;
+    return (d->kw == 5 ? 2 : 0) + (d->sw == 2 ? 1 : 0);
+}
+
+// `in`: the input pointer of the launch; the other tensors are taken to be 16-byte aligned (device allocations are)
+const char* si_conv_depthwise_name(const SiConv2dDesc* d, const float* in) {
+    static const char* cols[4] = {"conv_depthwise_cols_kernel<4, 3, 1>", "conv_depthwise_cols_kernel<4, 3, 2>",
+                                  "conv_depthwise_cols_kernel<4, 5, 1>", "conv_depthwise_cols_kernel<4, 5, 2>"};
+    const bool vec = dw_vec_strides(d) && (reinterpret_cast<uintptr_t>(in) & 15) == 0;
+    if (!vec) return "conv_depthwise_kernel<false, 4>";
+    const int f = dw_cols_form(d);
+    return f >= 0 ? cols[f] : "conv_depthwise_kernel<true, 4>";
 }
 
 int si_conv_depthwise_launch(const SiConv2dDesc* d, const float* in, const float* w_packed, const float* bias,
@@ -215,16 +233,15 @@ int si_conv_depthwise_launch(const SiConv2dDesc* d, const float* in, const float
     a.kh = d->kh; a.kw = d->kw; a.sh = d->sh; a.sw = d->sw; a.dh = d->dh; a.dw = d->dw; a.pt = d->pt; a.pl = d->pl;
     a.act1 = d->act1; a.act2 = d->act2; a.act_param = d->act_param;
     auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    const bool vec = (d->ic % 4 == 0) && (d->in_ld % 4 == 0) && (d->out_ld % 4 == 0) && al16(in) && al16(out) && al16(w_packed) &&
-                     (!a.bias || al16(a.bias)) && (!a.res || (d->res_ld % 4 == 0 && al16(a.res)));
+    const bool vec = dw_vec_strides(d) && al16(in) && al16(out) && al16(w_packed) && (!a.bias || al16(a.bias)) && (!a.res || al16(a.res));
     constexpr int TW = 4;
     const size_t items = (size_t)d->n * d->oh * ((d->ow + TW - 1) / TW) * (vec ? d->ic / 4 : d->ic);
     if (items == 0) return 0;
-    if (vec && d->dh == 1 && d->dw == 1 && (d->kw == 3 || d->kw == 5) && (d->sw == 1 || d->sw == 2)) {
+    if (const int f = dw_cols_form(d); vec && f >= 0) {
         const dim3 g(si_grid_for(items)), blk(256);
-        if (d->kw == 3 && d->sw == 1) hipLaunchKernelGGL((conv_depthwise_cols_kernel<TW, 3, 1>), g, blk, 0, s, a);
-        else if (d->kw == 3) hipLaunchKernelGGL((conv_depthwise_cols_kernel<TW, 3, 2>), g, blk, 0, s, a);
-        else if (d->sw == 1) hipLaunchKernelGGL((conv_depthwise_cols_kernel<TW, 5, 1>), g, blk, 0, s, a);
+        if (f == 0) hipLaunchKernelGGL((conv_depthwise_cols_kernel<TW, 3, 1>), g, blk, 0, s, a);
+        else if (f == 1) hipLaunchKernelGGL((conv_depthwise_cols_kernel<TW, 3, 2>), g, blk, 0, s, a);
+        else if (f == 2) hipLaunchKernelGGL((conv_depthwise_cols_kernel<TW, 5, 1>), g, blk, 0, s, a);
         else hipLaunchKernelGGL((conv_depthwise_cols_kernel<TW, 5, 2>), g, blk, 0, s, a);
         return (int)hipGetLastError();
     }

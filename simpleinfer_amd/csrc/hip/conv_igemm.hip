@@ -58,7 +58,7 @@ int si_conv_smallc_launch(const SiConv2dDesc* d, const float* in, const float* w
 bool si_conv_depthwise_ok(const SiConv2dDesc* d);
 size_t si_conv_depthwise_weight_elems(const SiConv2dDesc* d);
 void si_conv_depthwise_pack(const SiConv2dDesc* d, const float* w_oihw, float* w_packed);
-const char* si_conv_depthwise_name(const SiConv2dDesc* d);
+const char* si_conv_depthwise_name(const SiConv2dDesc* d, const float* in);
 int si_conv_depthwise_launch(const SiConv2dDesc* d, const float* in, const float* w_packed, const float* bias,
                              const float* residual, float* out, hipStream_t s);
 
@@ -1354,7 +1354,7 @@ extern "C" const char* si_hip_conv2d_kernel_name_form(const SiConv2dDesc* d, con
     }();
     (void)named;
     if (si_conv_smallc_ok(d)) return si_conv_smallc_name(d);
-    if (si_conv_depthwise_ok(d)) return si_conv_depthwise_name(d);
+    if (si_conv_depthwise_ok(d)) return si_conv_depthwise_name(d, in);
     SiConv2dDesc eff = conv_effective(d);
     d = &eff;
     if (conv_fast_ok(d, in)) {

@@ -290,7 +290,11 @@ bool si_conv_smallc_ok(const SiConv2dDesc* d) {
     if (d->ic < 1 || d->ic > 3) return false;
     if (d->sh < 1 || d->sh > 2 || d->sw < 1 || d->sw > 2 || d->kh > 7 || d->kw > 7) return false;
     const int hp = smallc_hp(d);
-    return hp == 5 || hp == 9 || hp == 11;  // 3x3x3 (MobileNet stem), 6x6x3 (YOLOv5 stem), 7x7x3 (ResNet stem)
+    // The HP = 5 instantiations stage (RB - 1) * sh + kh = sh + kh input rows in PF / 4 = 7 prefetch registers per thread: a taller kernel
+    // (7x3 at any stride, 6x3 at sh = 2) has no instantiation here and runs on the implicit GEMM.  (HP = 9 and 11 hold kh + sh <= 9 rows, or
+    // kh <= 7 at RB = 1: every kh <= 7.)  kh and sh are shape fields: the predicate stays shape-only.
+    if (hp == 5) return d->kh + d->sh <= 7;
+    return hp == 9 || hp == 11;  // 3x3x3 (MobileNet stem), 6x6x3 (YOLOv5 stem), 7x7x3 (ResNet stem)
 }
 
 size_t si_conv_smallc_weight_elems(const SiConv2dDesc* d) {

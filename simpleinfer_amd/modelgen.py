@@ -209,14 +209,17 @@ class PnnxBuilder:
         self._emit(typ, self._opname("pad"), [x], [out], params)
         return out
 
-    def maxpool(self, x: str, k: int, s: int, p: int) -> str:
+    def maxpool(self, x: str, k, s, p) -> str:
+        """k, s, p: an int (both axes) or an (h, w) pair, as conv takes them"""
         n, c, h, w = self.shapes[x]
-        oh = (h + 2 * p - k) // s + 1
-        ow = (w + 2 * p - k) // s + 1
+        pair = lambda v: (v, v) if isinstance(v, int) else (int(v[0]), int(v[1]))
+        (kh, kw), (sh, sw), (ph, pw) = pair(k), pair(s), pair(p)
+        oh = (h + 2 * ph - kh) // sh + 1
+        ow = (w + 2 * pw - kw) // sw + 1
         out = self._new_operand((n, c, oh, ow))
         self._emit("nn.MaxPool2d", self._opname("maxpool"), [x], [out],
-                   dict(ceil_mode=False, dilation=(1, 1), kernel_size=(k, k), padding=(p, p),
-                        return_indices=False, stride=(s, s)))
+                   dict(ceil_mode=False, dilation=(1, 1), kernel_size=(kh, kw), padding=(ph, pw),
+                        return_indices=False, stride=(sh, sw)))
         return out
 
     def adaptive_avgpool(self, x: str, out_hw=(1, 1)) -> str:

@@ -136,15 +136,20 @@ def case(cid, entries, plan=None, refuse=None):
     return deco
 
 
+def _hw(v):
+    return (int(v), int(v)) if np.isscalar(v) else (int(v[0]), int(v[1]))
+
+
 def _conv(cid, entry, xs, oc, k=1, s=1, p=0, d=1, g=1, res=False, half=False, plan=None, seed=0, image=False, out_f32=False, **views):
     """a conv2d / conv2d_f16 case: input xs, ragged everything in `views` (in_ld, in_c_off, out_ld, out_c_off, res_ld, res_c_off)"""
     dt = np.float16 if half and not image else np.float32
-    oh = (xs[1] + 2 * p - ((k - 1) * d + 1)) // s + 1
-    ow = (xs[2] + 2 * p - ((k - 1) * d + 1)) // s + 1
+    k, s, p, d = _hw(k), _hw(s), _hw(p), _hw(d)     # each an int (both axes) or an (h, w) pair
+    oh = (xs[1] + 2 * p[0] - ((k[0] - 1) * d[0] + 1)) // s[0] + 1
+    ow = (xs[2] + 2 * p[1] - ((k[1] - 1) * d[1] + 1)) // s[1] + 1
 
     def run(hops, F):
         x = R(seed + 1, xs, 0.0 if image else -1.0, 1.0, dt)
-        w = R(seed + 2, (oc, xs[3] // g, k, k), -0.3, 0.3)
+        w = R(seed + 2, (oc, xs[3] // g) + k, -0.3, 0.3)
         b = R(seed + 3, (oc,), -0.5, 0.5)
         r = R(seed + 4, (xs[0], oh, ow, oc), -1, 1, np.float16 if half else np.float32) if res else None
         kw = dict(views)
@@ -153,7 +158,7 @@ def _conv(cid, entry, xs, oc, k=1, s=1, p=0, d=1, g=1, res=False, half=False, pl
         fn = hops.conv2d_f16 if half else hops.conv2d
         if out_f32:
             kw["out_f32"] = True
-        y = fn(x, w, b, (s, s), (p, p), (d, d), g, act1="silu", residual=r, in_fill=F, out_fill=F, full=True, **kw)
+        y = fn(x, w, b, s, p, d, g, act1="silu", residual=r, in_fill=F, out_fill=F, full=True, **kw)
         return [Out("y", y, views.get("out_c_off", 0), oc)]
     CASES.append(Case(cid, entry, run, plan))
 
@@ -185,6 +190,13 @@ _conv("stem_6x6_image_slice", "conv2d_f32", (1, 18, 20, 3), 32, 6, 2, 2, image=T
 _conv("stem_7x7", "conv2d_f32", (2, 15, 17, 3), 64, 7, 2, 3, image=True, out_ld=72, out_c_off=8)
 _conv("stem_3x3_oc16", "conv2d_f32", (2, 17, 13, 3), 16, 3, 2, 1, image=True, out_ld=24, out_c_off=4)
 _conv("conv_forced_tile4", "conv2d_f32", (2, 11, 9, 32), 48, 3, 2, 1, plan=dict(f32_tile=4), in_ld=64, in_c_off=32, out_ld=64, out_c_off=16)
+# rectangular kernels / strides / pads, one per family (values: tests/test_gpu_rect.py): the fast implicit GEMM's 1x7 strip, the zero-padded-K 1x1
+# at stride (2,1), the depthwise column kernel with kh != KW, the 6x7 stem on the small-channel kernel
+_conv("rect_conv_1x7_last_slice", "conv2d_f32", (1, 9, 11, 64), 64, (1, 7), 1, (0, 3), in_ld=96, in_c_off=32, out_ld=72, out_c_off=8)
+_conv("rect_conv_pw_k24_s2x1_last_slice", "conv2d_f32", (2, 9, 7, 24), 40, 1, (2, 1), 0, in_ld=56, in_c_off=32, out_ld=48, out_c_off=4)
+_conv("rect_depthwise_cols_3x5_s2x1_res", "conv2d_f32", (2, 9, 11, 16), 16, (3, 5), (2, 1), (1, 2), g=16, res=True, in_ld=24, in_c_off=8, res_ld=32,
+      res_c_off=16, out_ld=32, out_c_off=16)
+_conv("rect_stem_6x7_odd", "conv2d_f32", (2, 19, 21, 3), 32, (6, 7), 2, (2, 3), image=True, out_ld=40, out_c_off=4)
 
 
 def _wino(cid, entry, xs, oc, pad=1, tile=2, plan=None, split=False, **views):
@@ -221,13 +233,14 @@ _wino("wino23_split_unaligned_out", "conv2d_wino23_split_f32", (2, 7, 5, 32), 64
 
 
 def _split3(cid, xs, oc, k, s, plan=None, res=True, **views):
-    p = k // 2
-    oh, ow = (xs[1] + 2 * p - k) // s + 1, (xs[2] + 2 * p - k) // s + 1
+    k, s = _hw(k), _hw(s)
+    p = (k[0] // 2, k[1] // 2)
+    oh, ow = (xs[1] + 2 * p[0] - k[0]) // s[0] + 1, (xs[2] + 2 * p[1] - k[1]) // s[1] + 1
 
     def run(hops, F):
-        x, w, b = R(21, xs, -2, 2), R(22, (oc, xs[3], k, k), -0.2, 0.2), R(23, (oc,), -0.5, 0.5)
+        x, w, b = R(21, xs, -2, 2), R(22, (oc, xs[3]) + k, -0.2, 0.2), R(23, (oc,), -0.5, 0.5)
         r = R(24, (xs[0], oh, ow, oc)) if res else None
-        y, flag = hops.conv2d_split3(x, w, b, (s, s), (p, p), act1="silu", residual=r, return_flag=True, in_fill=F, res_fill=F, out_fill=F, full=True,
+        y, flag = hops.conv2d_split3(x, w, b, s, p, act1="silu", residual=r, return_flag=True, in_fill=F, res_fill=F, out_fill=F, full=True,
                                      **views)
         return [Out("y", y, views.get("out_c_off", 0), oc), Out("range_flag", np.array([flag], np.uint32))]
     CASES.append(Case(cid, "conv2d_split3_f32", run, plan))
@@ -235,6 +248,7 @@ def _split3(cid, xs, oc, k, s, plan=None, res=True, **views):
 
 _split3("split3_pw_ragged_oc40_last_slice", (3, 9, 9, 160), 40, 1, 1, in_ld=192, in_c_off=32, res_ld=48, res_c_off=8, out_ld=48, out_c_off=4)
 _split3("split3_3x3_s2_32ch", (2, 11, 13, 32), 64, 3, 2, in_ld=64, in_c_off=32, res_ld=96, res_c_off=32, out_ld=67, out_c_off=3)
+_split3("rect_split3_1x5_last_slice", (2, 9, 11, 64), 48, (1, 5), 1, in_ld=96, in_c_off=32, res_ld=64, res_c_off=16, out_ld=52, out_c_off=4)
 for _bm in (-1, 32, 64, 128):
     _split3("split3_3x3_s2_bm%d" % _bm, (2, 13, 11, 128), 96, 3, 2, plan=dict(split3_bm=_bm), in_ld=160, in_c_off=32, res_ld=128, res_c_off=32,
             out_ld=100, out_c_off=4)
@@ -384,6 +398,8 @@ for _dt, _sfx, _c, _vu, _va in ((np.float32, "f32", 6, dict(in_ld=9, in_c_off=3,
     _ac = "activation" if _sfx == "f32" else "activation_f16"
     _un = "unary_op" if _sfx == "f32" else "unary_op_f16"
     _pixelwise("maxpool_k3s2_" + _sfx, "maxpool2d_" + _sfx, lambda hops, x, _f=_mp, **kw: getattr(hops, _f)(x, (3, 3), (2, 2), (1, 1), **kw),
+               (2, 9, 7, 8), _dt, -3, -1, **_va)
+    _pixelwise("rect_maxpool_k3x2_s2x1_" + _sfx, "maxpool2d_" + _sfx, lambda hops, x, _f=_mp, **kw: getattr(hops, _f)(x, (3, 2), (2, 1), (1, 0), **kw),
                (2, 9, 7, 8), _dt, -3, -1, **_va)
     _pixelwise("maxpool_k5s1_unaligned_" + _sfx, "maxpool2d_" + _sfx, lambda hops, x, _f=_mp, **kw: getattr(hops, _f)(x, (5, 5), (1, 1), (2, 2), **kw),
                (2, 5, 7, _c), _dt, -3, -1, **_vu)
@@ -538,6 +554,8 @@ _conv("f16_depthwise_5x5_c72", "conv2d_depthwise_f16", (2, 9, 7, 72), 72, 5, 1, 
 _conv("f16_stem_6x6_odd", "conv2d_stem_f16", (2, 19, 21, 3), 32, 6, 2, 2, half=True, image=True, out_ld=40, out_c_off=8)
 _conv("f16_stem_6x6_image_slice_odd_out", "conv2d_stem_f16", (1, 18, 20, 3), 32, 6, 2, 2, half=True, image=True, in_ld=4, in_c_off=1, out_ld=37, out_c_off=5)
 _conv("f16_stem_7x7_odd_width", "conv2d_stem_f16", (1, 15, 17, 3), 64, 7, 2, 3, half=True, image=True, out_ld=96, out_c_off=32)
+_conv("rect_f16_7x1_last_slice", "conv2d_f16", (1, 11, 9, 64), 64, (7, 1), 1, (3, 0), half=True, in_ld=96, in_c_off=32, out_ld=80, out_c_off=16)
+_conv("rect_f16_stem_6x7_odd", "conv2d_stem_f16", (2, 19, 21, 3), 32, (6, 7), 2, (2, 3), half=True, image=True, out_ld=40, out_c_off=8)
 _conv("f16_stem_3x3_oc16", "conv2d_stem_f16", (2, 17, 13, 3), 16, 3, 2, 1, half=True, image=True, out_ld=24, out_c_off=8)
 
 
