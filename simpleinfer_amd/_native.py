@@ -80,6 +80,12 @@ class SiPad2dDesc(C.Structure):
         ("value", C.c_float)]
 
 
+class SiAvgPool2dDesc(C.Structure):
+    """include/si_pool.h"""
+    _fields_ = [(k, C.c_int) for k in ("n", "ih", "iw", "c", "in_ld", "oh", "ow", "out_ld", "kh", "kw", "sh", "sw", "pt", "pl", "adaptive",
+                                       "count_include_pad", "divisor_override")]
+
+
 class SiConv2dUpsampledSource(C.Structure):
     _fields_ = [("src", C.c_void_p), ("ih", C.c_int), ("iw", C.c_int), ("c", C.c_int), ("ld", C.c_int), ("c0", C.c_int),
                 ("inv_scale_h", C.c_float), ("inv_scale_w", C.c_float)]
@@ -257,13 +263,20 @@ def hip():
         "si_hip_pad2d_f16": (i, [C.POINTER(SiPad2dDesc), vp, vp, vp]),
         "si_hip_pad2d_kernel_name": (C.c_char_p, [C.POINTER(SiPad2dDesc), vp, vp, i]),
     }
-    for name, (res, args) in list(sig.items()) + list(norm.items()) + list(pad.items()):
+    # include/si_pool.h: nn.AvgPool2d and the general nn.AdaptiveAvgPool2d
+    pool = {
+        "si_hip_avgpool2d_f32": (i, [C.POINTER(SiAvgPool2dDesc), vp, vp, vp]),
+        "si_hip_avgpool2d_f16": (i, [C.POINTER(SiAvgPool2dDesc), vp, vp, vp]),
+        "si_hip_avgpool2d_kernel_name": (C.c_char_p, [C.POINTER(SiAvgPool2dDesc), vp, vp, i]),
+    }
+    for name, (res, args) in list(sig.items()) + list(norm.items()) + list(pad.items()) + list(pool.items()):
         fn = getattr(L, name)  # AttributeError here = header/library mismatch, which tests check
         fn.restype = res
         fn.argtypes = args
     L._si_signatures = sig
     L._si_norm_signatures = norm
     L._si_pad_signatures = pad
+    L._si_pool_signatures = pool
     _hip = L
     return L
 

@@ -1,7 +1,10 @@
 #include "adaptive_avg_pool_2d.h"
 
+#include <cstring>
+
 #include "layer_util.h"
 #include "si_hip.h"
+#include "si_pool.h"
 
 namespace SimpleInfer {
 
@@ -31,11 +34,14 @@ Status AdaptiveAvgPool2d::Forward(const Tensor& input, Tensor& output) {
     return RunOnDevice({&input}, {&output}, [this](const std::vector<Tensor>& in, std::vector<Tensor>& out) {
         Dims4 id, od;
         if (!GetDims4(in[0], id) || !GetDims4(out[0], od) || id.c != od.c || id.n != od.n) return Status::kErrorShape;
-        if (0 != id.h % od.h || 0 != id.w % od.w) {
-            LOG(ERROR) << "AdaptiveAvgPool2d::Forward fail [unsupport input/output shape]";
-            return Status::kUnsupport;
-        }
         if (IsHalf(in[0]) != IsHalf(out[0])) return Status::kUnsupport;
+        if (0 != id.h % od.h || 0 != id.w % od.w) {
+            // torch's general windows [floor(j i / o), ceil((j + 1) i / o)): include/si_pool.h (the divisible shapes keep the kernels below and their bits)
+            SiAvgPool2dDesc d;
+            MakeGeneralDesc(in[0], out[0], d);
+            if (IsHalf(in[0])) return CheckHip(si_hip_avgpool2d_f16(&d, in[0].RawData(), out[0].RawData(), Stream()), "AdaptiveAvgPool2d");
+            return CheckHip(si_hip_avgpool2d_f32(&d, in[0].Data<float>(), out[0].Data<float>(), Stream()), "AdaptiveAvgPool2d");
+        }
         if (IsHalf(in[0]))
             return CheckHip(si_hip_adaptive_avgpool2d_f16(in[0].RawData(), id.n, id.h, id.w, id.c, in[0].PixelStride(),
                                                           out[0].RawData(), od.h, od.w, out[0].PixelStride(), Stream()),
@@ -44,6 +50,27 @@ Status AdaptiveAvgPool2d::Forward(const Tensor& input, Tensor& output) {
                                                       out[0].Data<float>(), od.h, od.w, out[0].PixelStride(), Stream()),
                         "AdaptiveAvgPool2d");
     });
+}
+
+bool AdaptiveAvgPool2d::MakeGeneralDesc(const Tensor& input, const Tensor& output, SiAvgPool2dDesc& d) {
+    Dims4 id, od;
+    if (!GetDims4(input, id) || !GetDims4(output, od) || id.c != od.c || id.n != od.n) return false;
+    memset(&d, 0, sizeof(d));
+    d.n = id.n; d.ih = id.h; d.iw = id.w; d.c = id.c; d.in_ld = input.PixelStride();
+    d.oh = od.h; d.ow = od.w; d.out_ld = output.PixelStride();
+    d.adaptive = 1;
+    return 0 != id.h % od.h || 0 != id.w % od.w;
+}
+
+// "avgpool" for the divisible shapes, as before; the instantiation of include/si_pool.h for the others
+const char* AdaptiveAvgPool2d::KernelName() const {
+    SiAvgPool2dDesc d;
+    if (input_tensor_nodes_.empty() || output_tensor_nodes_.empty() ||
+        !MakeGeneralDesc(input_tensor_nodes_[0]->tensor, output_tensor_nodes_[0]->tensor, d))
+        return "avgpool";
+    const Tensor& in = input_tensor_nodes_[0]->tensor;
+    const Tensor& out = output_tensor_nodes_[0]->tensor;
+    return si_hip_avgpool2d_kernel_name(&d, in.RawData(), out.RawData(), IsHalf(out) ? 1 : 0);
 }
 
 }  // namespace SimpleInfer

@@ -1,0 +1,115 @@
+#include "avg_pool_2d.h"
+
+#include <cstring>
+
+namespace SimpleInfer {
+
+DEFINE_LAYER_REGISTRY(AvgPool2d);
+
+// A missing key is kFail; what the file asks for and this layer does not do is left for Validate (kUnsupport).
+Status AvgPool2d::Init(const pnnx::Operator* op) {
+    CHECK_STATUS(Layer::Init(op));
+    CHECK_BOOL(CheckParam(op, "ceil_mode", 1));
+    ceil_mode_ = op->params.at("ceil_mode").b;
+    CHECK_BOOL(CheckParam(op, "count_include_pad", 1));
+    count_include_pad_ = op->params.at("count_include_pad").b;
+
+    struct IntPair { const char* key; int* a; int* b; };
+    const IntPair pairs[] = {{"kernel_size", &kernel_h_, &kernel_w_}, {"stride", &stride_h_, &stride_w_}, {"padding", &padding_h_, &padding_w_}};
+    for (const IntPair& p : pairs) {
+        CHECK_BOOL(CheckParam(op, p.key, 5));
+        const std::vector<int>& v = op->params.at(p.key).ai;
+        CHECK_BOOL(2 == v.size());
+        *p.a = v[0];
+        *p.b = v[1];
+    }
+    // an int, or None (type 0)
+    CHECK_BOOL(op->params.count("divisor_override") > 0);
+    has_divisor_override_ = false;
+    divisor_override_ = 0;
+    if (0 != op->params.at("divisor_override").type) {
+        CHECK_BOOL(CheckParam(op, "divisor_override", 2));
+        has_divisor_override_ = true;
+        divisor_override_ = op->params.at("divisor_override").i;
+    }
+    return Status::kSuccess;
+}
+
+int AvgPool2d::OutSize(int i, int k, int s, int p, bool ceil_mode) {
+    const long long span = (long long)i + 2LL * p - k;
+    if (span < 0 || s < 1) return 0;
+    long long o = (ceil_mode ? (span + s - 1) / s : span / s) + 1;
+    if (ceil_mode && (o - 1) * s >= (long long)i + p) --o;
+    return (int)o;
+}
+
+Status AvgPool2d::Validate() {
+    CHECK_STATUS(Layer::Validate());
+    CHECK_STATUS(ValidateShape(1, 1));
+    if (Status::kSuccess != ValidateFloat()) {
+        LOG(ERROR) << "AvgPool2d::Validate fail [unsupport input/output data type]";
+        return Status::kUnsupport;
+    }
+    if (kernel_h_ < 1 || kernel_w_ < 1 || stride_h_ < 1 || stride_w_ < 1 || padding_h_ < 0 || padding_w_ < 0) {
+        LOG(ERROR) << "AvgPool2d::Validate fail [kernel_size and stride must be positive, padding non-negative]";
+        return Status::kFail;
+    }
+    if (padding_h_ > kernel_h_ / 2 || padding_w_ > kernel_w_ / 2) {
+        LOG(ERROR) << "AvgPool2d::Validate fail [padding (" << padding_h_ << ", " << padding_w_ << ") is more than half of kernel_size (" << kernel_h_
+                   << ", " << kernel_w_ << ")]";
+        return Status::kUnsupport;
+    }
+    if (has_divisor_override_ && 0 == divisor_override_) {
+        LOG(ERROR) << "AvgPool2d::Validate fail [divisor_override must not be 0]";
+        return Status::kUnsupport;
+    }
+    Dims4 in, out;
+    if (!GetDims4(input_tensor_nodes_[0]->tensor, in) || !GetDims4(output_tensor_nodes_[0]->tensor, out)) {
+        LOG(ERROR) << "AvgPool2d::Validate fail [input and output must be rank-4]";
+        return Status::kErrorShape;
+    }
+    const int oh = OutSize(in.h, kernel_h_, stride_h_, padding_h_, ceil_mode_), ow = OutSize(in.w, kernel_w_, stride_w_, padding_w_, ceil_mode_);
+    if (out.n != in.n || out.c != in.c || out.h != oh || out.w != ow) {
+        LOG(ERROR) << "AvgPool2d::Validate fail [output shape " << out.n << "x" << out.c << "x" << out.h << "x" << out.w << " for input " << in.n << "x"
+                   << in.c << "x" << in.h << "x" << in.w << ", kernel_size (" << kernel_h_ << ", " << kernel_w_ << "), stride (" << stride_h_ << ", "
+                   << stride_w_ << "), padding (" << padding_h_ << ", " << padding_w_ << "), ceil_mode " << (ceil_mode_ ? "True" : "False")
+                   << ": expected " << in.n << "x" << in.c << "x" << oh << "x" << ow << "]";
+        return Status::kErrorShape;
+    }
+    return Status::kSuccess;
+}
+
+bool AvgPool2d::MakeDesc(const Tensor& input, const Tensor& output, SiAvgPool2dDesc& d) const {
+    Dims4 id, od;
+    if (!GetDims4(input, id) || !GetDims4(output, od) || id.c != od.c || id.n != od.n) return false;
+    memset(&d, 0, sizeof(d));
+    d.n = id.n; d.ih = id.h; d.iw = id.w; d.c = id.c; d.in_ld = input.PixelStride();
+    d.oh = od.h; d.ow = od.w; d.out_ld = output.PixelStride();
+    d.kh = kernel_h_; d.kw = kernel_w_; d.sh = stride_h_; d.sw = stride_w_; d.pt = padding_h_; d.pl = padding_w_;
+    d.count_include_pad = count_include_pad_ ? 1 : 0;
+    d.divisor_override = has_divisor_override_ ? divisor_override_ : 0;
+    return true;
+}
+
+Status AvgPool2d::Forward(const Tensor& input, Tensor& output) {
+    return RunOnDevice({&input}, {&output}, [this](const std::vector<Tensor>& in, std::vector<Tensor>& out) {
+        if (IsHalf(in[0]) != IsHalf(out[0])) return Status::kUnsupport;
+        if (has_divisor_override_ && 0 == divisor_override_) return Status::kUnsupport;
+        SiAvgPool2dDesc d;
+        if (!MakeDesc(in[0], out[0], d)) return Status::kErrorShape;
+        if (IsHalf(in[0])) return CheckHip(si_hip_avgpool2d_f16(&d, in[0].RawData(), out[0].RawData(), Stream()), "AvgPool2d");
+        return CheckHip(si_hip_avgpool2d_f32(&d, in[0].Data<float>(), out[0].Data<float>(), Stream()), "AvgPool2d");
+    });
+}
+
+const char* AvgPool2d::KernelName() const {
+    SiAvgPool2dDesc d;
+    if (input_tensor_nodes_.empty() || output_tensor_nodes_.empty() ||
+        !MakeDesc(input_tensor_nodes_[0]->tensor, output_tensor_nodes_[0]->tensor, d))
+        return "avgpool2d_kernel";
+    const Tensor& in = input_tensor_nodes_[0]->tensor;
+    const Tensor& out = output_tensor_nodes_[0]->tensor;
+    return si_hip_avgpool2d_kernel_name(&d, in.RawData(), out.RawData(), IsHalf(out) ? 1 : 0);
+}
+
+}  // namespace SimpleInfer

@@ -10,6 +10,7 @@ namespace SimpleInfer {
     void type##_LayerDestroyer(Layer*);
 
 SI_DECLARE_LAYER(AdaptiveAvgPool2d)
+SI_DECLARE_LAYER(AvgPool2d)
 SI_DECLARE_LAYER(BatchNorm2d)
 SI_DECLARE_LAYER(BinaryOp)
 SI_DECLARE_LAYER(Cat)
@@ -39,9 +40,10 @@ static std::map<std::string, LayerRegistryEntry>& Table() {
     // (north_star extension) nn.ConvTranspose2d (U-Net / segmentation decoders; no reference layer)
     // F.interpolate / F.upsample, the functional spellings of nn.Upsample, and nn.GroupNorm / nn.InstanceNorm2d (one class: the
     // instance norm is the group norm with one group per channel); the explicit pads (one class, layer/pad_2d.h) and nn.Tanh
-    // (UnaryOp code 16 as a module)
+    // (UnaryOp code 16 as a module); nn.AvgPool2d / F.avg_pool2d (layer/avg_pool_2d.h) and the functional spelling of the adaptive pool
     static std::map<std::string, LayerRegistryEntry> table = {
         SI_ENTRY("nn.AdaptiveAvgPool2d", AdaptiveAvgPool2d),
+        SI_ENTRY("nn.AvgPool2d", AvgPool2d),
         SI_ENTRY("nn.BatchNorm2d", BatchNorm2d),
         SI_ENTRY("nn.CircularPad2d", Pad2d),
         SI_ENTRY("nn.ConstantPad2d", Pad2d),
@@ -69,6 +71,8 @@ static std::map<std::string, LayerRegistryEntry>& Table() {
         SI_ENTRY("F.interpolate", Upsample),
         SI_ENTRY("F.upsample", Upsample),
         SI_ENTRY("F.pad", Pad2d),
+        SI_ENTRY("F.avg_pool2d", AvgPool2d),
+        SI_ENTRY("F.adaptive_avg_pool2d", AdaptiveAvgPool2d),
         SI_ENTRY("models.yolo.Detect", YoloDetect),
     };
     return table;

@@ -954,6 +954,75 @@ def pad2d_kernel_name(x_shape, pads, mode="constant", half=False, in_ld=None, ou
     return _native.hip().si_hip_pad2d_kernel_name(C.byref(d), C.c_void_p(256), C.c_void_p(256), 1 if half else 0).decode()
 
 
+def _pair(v):
+    return (int(v), int(v)) if isinstance(v, (int, np.integer)) else (int(v[0]), int(v[1]))
+
+
+def avgpool_out_size(i, k, s, p, ceil_mode=False):
+    """torch's output size of one axis of an average pool (include/si_pool.h); 0: the window does not fit"""
+    span = i + 2 * p - k
+    if span < 0:
+        return 0
+    o = (-(-span // s) if ceil_mode else span // s) + 1
+    if ceil_mode and (o - 1) * s >= i + p:
+        o -= 1
+    return o
+
+
+def avgpool2d_desc(x_shape, k, s=None, p=0, ceil_mode=False, count_include_pad=True, divisor_override=None, in_ld=None, out_ld=None):
+    """SiAvgPool2dDesc (include/si_pool.h) of an NHWC input; k, s, p: an int or an (h, w) pair, s=None: the kernel size (torch's default)"""
+    n, ih, iw, c = x_shape
+    (kh, kw), (ph, pw) = _pair(k), _pair(p)
+    sh, sw = (kh, kw) if s is None else _pair(s)
+    oh = avgpool_out_size(ih, kh, sh, ph, ceil_mode) if sh > 0 else 0
+    ow = avgpool_out_size(iw, kw, sw, pw, ceil_mode) if sw > 0 else 0
+    return _native.SiAvgPool2dDesc(n, ih, iw, c, in_ld or c, oh, ow, out_ld or c, kh, kw, sh, sw, ph, pw, 0, 1 if count_include_pad else 0,
+                                   int(divisor_override or 0))
+
+
+def adaptive_avgpool2d_desc(x_shape, out_hw, in_ld=None, out_ld=None):
+    n, ih, iw, c = x_shape
+    return _native.SiAvgPool2dDesc(n, ih, iw, c, in_ld or c, int(out_hw[0]), int(out_hw[1]), out_ld or c, 0, 0, 0, 0, 0, 0, 1, 0, 0)
+
+
+def _avgpool2d_run(x, d, in_ld, in_c_off, in_fill, out_ld, out_c_off, out_fill, full):
+    H = _native.hip()
+    half = x.dtype == np.float16
+    n, c = x.shape[0], x.shape[3]
+    if d.oh < 1 or d.ow < 1:
+        raise HipError("si_hip_avgpool2d: no output for a %dx%d input" % (x.shape[1], x.shape[2]))
+    (dx, px), (dy, py) = _view_in(x, in_ld, in_c_off, in_fill), _view_out((n, d.oh, d.ow), c, out_ld, out_c_off, out_fill, x.dtype)
+    LAST_KERNEL_NAME["si_hip_avgpool2d"] = H.si_hip_avgpool2d_kernel_name(C.byref(d), C.c_void_p(px), C.c_void_p(py), 1 if half else 0).decode()
+    fn, name = (H.si_hip_avgpool2d_f16, "si_hip_avgpool2d_f16") if half else (H.si_hip_avgpool2d_f32, "si_hip_avgpool2d_f32")
+    _chk(fn(C.byref(d), px, py, None), name)
+    return _ret(dy.to_numpy((n, d.oh, d.ow, out_ld or c), x.dtype), c, out_c_off, full)
+
+
+def avgpool2d(x, k, s=None, p=0, ceil_mode=False, count_include_pad=True, divisor_override=None, in_ld=None, in_c_off=0, in_fill=0.0,
+              out_ld=None, out_c_off=0, out_fill=0.0, full=False):
+    """si_hip_avgpool2d_f32 / _f16 (by the array's dtype) on an NHWC array: torch.nn.functional.avg_pool2d(x, k, s, p, ceil_mode,
+    count_include_pad, divisor_override) of the NCHW tensor.  The view hooks are the common ones."""
+    x = _float_storage(x)
+    d = avgpool2d_desc(x.shape, k, s, p, ceil_mode, count_include_pad, divisor_override, in_ld, out_ld)
+    return _avgpool2d_run(x, d, in_ld, in_c_off, in_fill, out_ld, out_c_off, out_fill, full)
+
+
+def adaptive_avgpool2d_general(x, out_hw, in_ld=None, in_c_off=0, in_fill=0.0, out_ld=None, out_c_off=0, out_fill=0.0, full=False):
+    """si_hip_avgpool2d_f32 / _f16 with adaptive = 1: torch.nn.functional.adaptive_avg_pool2d for any output size (the engine sends the
+    non-divisible shapes here; adaptive_avgpool2d above keeps the divisible ones)"""
+    x = _float_storage(x)
+    d = adaptive_avgpool2d_desc(x.shape, out_hw, in_ld, out_ld)
+    return _avgpool2d_run(x, d, in_ld, in_c_off, in_fill, out_ld, out_c_off, out_fill, full)
+
+
+def avgpool2d_kernel_name(x_shape, k=None, s=None, p=0, ceil_mode=False, half=False, in_ld=None, out_ld=None, adaptive=None) -> str:
+    """the instantiation for 16-byte aligned buffers of these shapes ("none": a descriptor the launch refuses); adaptive=(oh, ow): the
+    adaptive windows instead of k / s / p"""
+    d = adaptive_avgpool2d_desc(x_shape, adaptive, in_ld, out_ld) if adaptive is not None else avgpool2d_desc(x_shape, k, s, p, ceil_mode, True, None,
+                                                                                                                 in_ld, out_ld)
+    return _native.hip().si_hip_avgpool2d_kernel_name(C.byref(d), C.c_void_p(256), C.c_void_p(256), 1 if half else 0).decode()
+
+
 def flatten_nhwc(x, in_ld=None, in_c_off=0, in_fill=0.0):
     H = _native.hip()
     x = _f32(x)

@@ -222,11 +222,39 @@ class PnnxBuilder:
                         return_indices=False, stride=(sh, sw)))
         return out
 
-    def adaptive_avgpool(self, x: str, out_hw=(1, 1)) -> str:
+    def adaptive_avgpool(self, x: str, out_hw=(1, 1), functional: bool = False) -> str:
+        """functional=True: the F.adaptive_avg_pool2d line (the same key)"""
         n, c, h, w = self.shapes[x]
         out = self._new_operand((n, c, out_hw[0], out_hw[1]))
-        self._emit("nn.AdaptiveAvgPool2d", self._opname("avgpool"), [x], [out],
-                   dict(output_size=(int(out_hw[0]), int(out_hw[1]))))
+        typ, prefix = ("F.adaptive_avg_pool2d", "F_adaptive_avg_pool2d") if functional else ("nn.AdaptiveAvgPool2d", "avgpool")
+        self._emit(typ, self._opname(prefix), [x], [out], dict(output_size=(int(out_hw[0]), int(out_hw[1]))))
+        return out
+
+    @staticmethod
+    def avgpool_out_size(i: int, k: int, s: int, p: int, ceil_mode: bool = False) -> int:
+        """torch's rule for one axis: floor or ceil of (i + 2p - k) / s, + 1; with ceil_mode the last window must start inside the input
+        or its left pad"""
+        span = i + 2 * p - k
+        assert span >= 0 and s >= 1, (i, k, s, p)
+        o = (-(-span // s) if ceil_mode else span // s) + 1
+        if ceil_mode and (o - 1) * s >= i + p:
+            o -= 1
+        return o
+
+    def avgpool(self, x: str, k, s=None, p=0, ceil_mode: bool = False, count_include_pad: bool = True, divisor_override=None,
+                functional: bool = False) -> str:
+        """pnnx's nn.AvgPool2d line (functional=True: F.avg_pool2d, the same keys).  k, s, p: an int (both axes) or an (h, w) pair;
+        s=None: the kernel size, torch's default.  The output shape is torch's rule."""
+        n, c, h, w = self.shapes[x]
+        pair = lambda v: (v, v) if isinstance(v, int) else (int(v[0]), int(v[1]))
+        (kh, kw), (ph, pw) = pair(k), pair(p)
+        sh, sw = (kh, kw) if s is None else pair(s)
+        out = self._new_operand((n, c, self.avgpool_out_size(h, kh, sh, ph, ceil_mode), self.avgpool_out_size(w, kw, sw, pw, ceil_mode)))
+        typ, prefix = ("F.avg_pool2d", "F_avg_pool2d") if functional else ("nn.AvgPool2d", "avgpool2d")
+        self._emit(typ, self._opname(prefix), [x], [out],
+                   dict(ceil_mode=bool(ceil_mode), count_include_pad=bool(count_include_pad),
+                        divisor_override="None" if divisor_override is None else int(divisor_override), kernel_size=(kh, kw),
+                        padding=(ph, pw), stride=(sh, sw)))
         return out
 
     def _resized(self, x: str, scale, size):
@@ -567,6 +595,54 @@ def build_toy_cyclegan(batch: int = 2, size: int = 32, base: int = 8, blocks: in
     for c in (2 * base, base):
         x = b.relu(b.instance_norm(b.conv_transpose(x, c, 3, 2, 1, output_padding=1)))
     x = b.tanh(b.conv(b.pad(x, 3, pad), 3, 7, 1, 0))
+    b.output(x)
+    return b
+
+
+def build_toy_densenet(batch: int = 2, size: int = 33, growth: int = 8, ncls: int = 10, seed: int = 0) -> PnnxBuilder:
+    """The average-pool idioms of the classification families at toy width: a conv3x3 stem (p = 0, 16 channels); two dense blocks (BN -> ReLU ->
+    conv3x3 to `growth` channels, concatenated onto their input: DenseNet); a transition BN -> ReLU -> conv1x1 -> AvgPool2d(2, 2); an
+    Inception-style block of three branches into one concat, the pool branch AvgPool2d(3, 1, 1, count_include_pad=False) -> conv1x1; a
+    ResNet-D downsampling block on the odd map -- main branch conv3x3 s2 p1, shortcut AvgPool2d(2, 2, ceil_mode=True,
+    count_include_pad=False) -> conv1x1, added; and the head AdaptiveAvgPool2d((1, 1)) -> flatten -> Linear.  The stem has no padding:
+    at size 33 the map is 31 -> 15 (transition, the last row and column dropped) -> 8 (ResNet-D: ceil_mode keeps the odd map's last
+    row and column, as a one-tap-wide window divided by its own extent)."""
+    b = PnnxBuilder(seed)
+    x = b.input((batch, 3, size, size))
+    x = b.relu(b.conv(x, 2 * growth, 3, 1, 0))
+    for _ in range(2):                                                   # dense blocks
+        y = b.conv(b.relu(b.batchnorm(x)), growth, 3, 1, 1)
+        x = b.cat([x, y])
+    x = b.avgpool(b.conv(b.relu(b.batchnorm(x)), 2 * growth, 1, 1, 0), 2, 2)     # transition
+    br1 = b.relu(b.conv(x, growth, 1, 1, 0))                             # Inception block
+    br3 = b.relu(b.conv(b.relu(b.conv(x, growth, 1, 1, 0)), 2 * growth, 3, 1, 1))
+    brp = b.conv(b.avgpool(x, 3, 1, 1, count_include_pad=False), growth, 1, 1, 0)
+    x = b.relu(b.cat([br1, br3, brp]))
+    main = b.conv(b.relu(b.conv(x, 4 * growth, 3, 2, 1)), 4 * growth, 3, 1, 1)   # ResNet-D block
+    short = b.conv(b.avgpool(x, 2, 2, 0, ceil_mode=True, count_include_pad=False), 4 * growth, 1, 1, 0)
+    x = b.relu(b.add(main, short))
+    x = b.linear(b.flatten(b.adaptive_avgpool(x, (1, 1))), ncls)
+    b.output(x)
+    return b
+
+
+def build_toy_pspnet(batch: int = 2, size: int = 52, ncls: int = 5, width: int = 16, bins=(1, 2, 3, 6), seed: int = 0) -> PnnxBuilder:
+    """PSPNet's pyramid pooling module at toy width: two stride-2 conv3x3 -> ReLU to a size / 4 map (13 x 13 at size 52); per bin
+    AdaptiveAvgPool2d((bin, bin)) -> conv1x1 -> ReLU -> F.interpolate(size=map, bilinear, align_corners=False); the four results
+    concatenated with the map -> conv3x3 -> ReLU -> conv1x1 to ncls classes -> F.interpolate(size=input, bilinear).  Bins 2, 3 and 6 do not
+    divide 13: the general adaptive windows."""
+    b = PnnxBuilder(seed)
+    x = b.input((batch, 3, size, size))
+    x = b.relu(b.conv(x, width, 3, 2, 1))
+    x = b.relu(b.conv(x, 2 * width, 3, 2, 1))
+    h, w = b.shapes[x][2:]
+    pyramid = [x]
+    for bin_ in bins:
+        y = b.relu(b.conv(b.adaptive_avgpool(x, (bin_, bin_)), width // 2, 1, 1, 0))
+        pyramid.append(b.interpolate(y, mode="bilinear", align_corners=False, size=(h, w)))
+    x = b.relu(b.conv(b.cat(pyramid), 2 * width, 3, 1, 1))
+    x = b.conv(x, ncls, 1, 1, 0)
+    x = b.interpolate(x, mode="bilinear", align_corners=False, size=(size, size))
     b.output(x)
     return b
 
