@@ -86,6 +86,11 @@ class SiAvgPool2dDesc(C.Structure):
                                        "count_include_pad", "divisor_override")]
 
 
+class SiSoftmaxDesc(C.Structure):
+    """include/si_softmax.h"""
+    _fields_ = [(k, C.c_int) for k in ("n", "h", "w", "c", "in_ld", "out_ld", "axis", "log")]
+
+
 class SiConv2dUpsampledSource(C.Structure):
     _fields_ = [("src", C.c_void_p), ("ih", C.c_int), ("iw", C.c_int), ("c", C.c_int), ("ld", C.c_int), ("c0", C.c_int),
                 ("inv_scale_h", C.c_float), ("inv_scale_w", C.c_float)]
@@ -269,7 +274,13 @@ def hip():
         "si_hip_avgpool2d_f16": (i, [C.POINTER(SiAvgPool2dDesc), vp, vp, vp]),
         "si_hip_avgpool2d_kernel_name": (C.c_char_p, [C.POINTER(SiAvgPool2dDesc), vp, vp, i]),
     }
-    for name, (res, args) in list(sig.items()) + list(norm.items()) + list(pad.items()) + list(pool.items()):
+    # include/si_softmax.h: nn.Softmax / nn.LogSoftmax / nn.Softmax2d and the functional spellings
+    softmax = {
+        "si_hip_softmax_f32": (i, [C.POINTER(SiSoftmaxDesc), vp, vp, vp]),
+        "si_hip_softmax_f16": (i, [C.POINTER(SiSoftmaxDesc), vp, vp, vp]),
+        "si_hip_softmax_kernel_name": (C.c_char_p, [C.POINTER(SiSoftmaxDesc), vp, vp, i]),
+    }
+    for name, (res, args) in list(sig.items()) + list(norm.items()) + list(pad.items()) + list(pool.items()) + list(softmax.items()):
         fn = getattr(L, name)  # AttributeError here = header/library mismatch, which tests check
         fn.restype = res
         fn.argtypes = args
@@ -277,6 +288,7 @@ def hip():
     L._si_norm_signatures = norm
     L._si_pad_signatures = pad
     L._si_pool_signatures = pool
+    L._si_softmax_signatures = softmax
     _hip = L
     return L
 

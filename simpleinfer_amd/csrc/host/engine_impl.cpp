@@ -29,7 +29,8 @@ bool HonoursPixelStride(const std::string& type) {
         "nn.Conv2d", "nn.ConvTranspose2d", "nn.SiLU", "nn.ReLU", "nn.Sigmoid", "nn.Hardsigmoid", "nn.Hardswish", "nn.LeakyReLU",
         "nn.MaxPool2d", "nn.AdaptiveAvgPool2d", "nn.Upsample", "F.interpolate", "F.upsample", "torch.cat", "BinaryOp", "UnaryOp", "nn.BatchNorm2d",
         "nn.GroupNorm", "nn.InstanceNorm2d", "nn.ReflectionPad2d", "nn.ReplicationPad2d", "nn.ZeroPad2d", "nn.ConstantPad2d", "nn.CircularPad2d",
-        "F.pad", "nn.Tanh", "nn.AvgPool2d", "F.avg_pool2d", "F.adaptive_avg_pool2d", "torch.flatten", "models.yolo.Detect", "pnnx.Output"};
+        "F.pad", "nn.Tanh", "nn.AvgPool2d", "F.avg_pool2d", "F.adaptive_avg_pool2d", "nn.Softmax", "nn.LogSoftmax", "nn.Softmax2d",
+        "F.softmax", "F.log_softmax", "torch.flatten", "models.yolo.Detect", "pnnx.Output"};
     return ok.count(type) > 0;
 }
 

@@ -27,6 +27,7 @@ SI_DECLARE_LAYER(Pad2d)
 SI_DECLARE_LAYER(ReLU)
 SI_DECLARE_LAYER(Sigmoid)
 SI_DECLARE_LAYER(SiLU)
+SI_DECLARE_LAYER(Softmax)
 SI_DECLARE_LAYER(Tanh)
 SI_DECLARE_LAYER(UnaryOp)
 SI_DECLARE_LAYER(Upsample)
@@ -40,7 +41,8 @@ static std::map<std::string, LayerRegistryEntry>& Table() {
     // (north_star extension) nn.ConvTranspose2d (U-Net / segmentation decoders; no reference layer)
     // F.interpolate / F.upsample, the functional spellings of nn.Upsample, and nn.GroupNorm / nn.InstanceNorm2d (one class: the
     // instance norm is the group norm with one group per channel); the explicit pads (one class, layer/pad_2d.h) and nn.Tanh
-    // (UnaryOp code 16 as a module); nn.AvgPool2d / F.avg_pool2d (layer/avg_pool_2d.h) and the functional spelling of the adaptive pool
+    // (UnaryOp code 16 as a module); nn.AvgPool2d / F.avg_pool2d (layer/avg_pool_2d.h) and the functional spelling of the adaptive pool;
+    // nn.Softmax / nn.LogSoftmax / nn.Softmax2d / F.softmax / F.log_softmax (one class, layer/softmax.h)
     static std::map<std::string, LayerRegistryEntry> table = {
         SI_ENTRY("nn.AdaptiveAvgPool2d", AdaptiveAvgPool2d),
         SI_ENTRY("nn.AvgPool2d", AvgPool2d),
@@ -57,6 +59,7 @@ static std::map<std::string, LayerRegistryEntry>& Table() {
         SI_ENTRY("nn.Hardswish", HardSwish),
         SI_ENTRY("nn.InstanceNorm2d", GroupNorm),
         SI_ENTRY("nn.LeakyReLU", LeakyReLU),
+        SI_ENTRY("nn.LogSoftmax", Softmax),
         SI_ENTRY("nn.Linear", Linear),
         SI_ENTRY("nn.MaxPool2d", MaxPool2d),
         SI_ENTRY("nn.ReflectionPad2d", Pad2d),
@@ -64,6 +67,8 @@ static std::map<std::string, LayerRegistryEntry>& Table() {
         SI_ENTRY("nn.ReplicationPad2d", Pad2d),
         SI_ENTRY("nn.Sigmoid", Sigmoid),
         SI_ENTRY("nn.SiLU", SiLU),
+        SI_ENTRY("nn.Softmax", Softmax),
+        SI_ENTRY("nn.Softmax2d", Softmax),
         SI_ENTRY("nn.Tanh", Tanh),
         SI_ENTRY("UnaryOp", UnaryOp),   // emitted by expand_expression, never registered by the reference
         SI_ENTRY("nn.Upsample", Upsample),
@@ -73,6 +78,8 @@ static std::map<std::string, LayerRegistryEntry>& Table() {
         SI_ENTRY("F.pad", Pad2d),
         SI_ENTRY("F.avg_pool2d", AvgPool2d),
         SI_ENTRY("F.adaptive_avg_pool2d", AdaptiveAvgPool2d),
+        SI_ENTRY("F.softmax", Softmax),
+        SI_ENTRY("F.log_softmax", Softmax),
         SI_ENTRY("models.yolo.Detect", YoloDetect),
     };
     return table;

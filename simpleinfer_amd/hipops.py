@@ -1023,6 +1023,34 @@ def avgpool2d_kernel_name(x_shape, k=None, s=None, p=0, ceil_mode=False, half=Fa
     return _native.hip().si_hip_avgpool2d_kernel_name(C.byref(d), C.c_void_p(256), C.c_void_p(256), 1 if half else 0).decode()
 
 
+def softmax_desc(x_shape, axis, log=False, in_ld=None, out_ld=None):
+    """SiSoftmaxDesc (include/si_softmax.h) of an NHWC input; axis: the NHWC axis reduced over"""
+    n, h, w, c = x_shape
+    return _native.SiSoftmaxDesc(n, h, w, c, in_ld or c, out_ld or c, int(axis), int(log))
+
+
+def softmax(x, axis, log=False, in_ld=None, in_c_off=0, in_fill=0.0, out_ld=None, out_c_off=0, out_fill=0.0, full=False):
+    """si_hip_softmax_f32 / _f16 (by the array's dtype) on an NHWC array: torch's softmax / log_softmax (log=True) along the NHWC axis
+    `axis` (0 n, 1 h, 2 w, 3 c; negative counts from the end).  The view hooks are the common ones."""
+    H = _native.hip()
+    x = _float_storage(x)
+    half = x.dtype == np.float16
+    assert x.ndim == 4, "NHWC (a rank-2 [N, F] array is [N, 1, 1, F])"
+    c = x.shape[3]
+    d = softmax_desc(x.shape, axis + 4 if axis < 0 else axis, log, in_ld, out_ld)
+    (dx, px), (dy, py) = _view_in(x, in_ld, in_c_off, in_fill), _view_out(x.shape[:-1], c, out_ld, out_c_off, out_fill, x.dtype)
+    LAST_KERNEL_NAME["si_hip_softmax"] = H.si_hip_softmax_kernel_name(C.byref(d), C.c_void_p(px), C.c_void_p(py), 1 if half else 0).decode()
+    fn, name = (H.si_hip_softmax_f16, "si_hip_softmax_f16") if half else (H.si_hip_softmax_f32, "si_hip_softmax_f32")
+    _chk(fn(C.byref(d), px, py, None), name)
+    return _ret(dy.to_numpy(x.shape[:-1] + (out_ld or c,), x.dtype), c, out_c_off, full)
+
+
+def softmax_kernel_name(x_shape, axis, half=False, in_ld=None, out_ld=None) -> str:
+    """the instantiation for 16-byte aligned buffers of these shapes ("none": a descriptor the launch refuses)"""
+    d = softmax_desc(x_shape, axis, False, in_ld, out_ld)
+    return _native.hip().si_hip_softmax_kernel_name(C.byref(d), C.c_void_p(256), C.c_void_p(256), 1 if half else 0).decode()
+
+
 def flatten_nhwc(x, in_ld=None, in_c_off=0, in_fill=0.0):
     H = _native.hip()
     x = _f32(x)

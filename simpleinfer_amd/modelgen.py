@@ -182,6 +182,26 @@ class PnnxBuilder:
     def hardswish(self, x): return self._unary("nn.Hardswish", "hswish", x)
     def tanh(self, x): return self._unary("nn.Tanh", "tanh", x)
 
+    def softmax(self, x: str, dim: int, functional: bool = False, log: bool = False) -> str:
+        """pnnx's nn.Softmax line with torch's key `dim` (functional=True: F.softmax; log=True: nn.LogSoftmax / F.log_softmax)"""
+        if log:
+            typ, prefix = ("F.log_softmax", "F_log_softmax") if functional else ("nn.LogSoftmax", "logsoftmax")
+        else:
+            typ, prefix = ("F.softmax", "F_softmax") if functional else ("nn.Softmax", "softmax")
+        return self._unary(typ, prefix, x, dict(dim=int(dim)))
+
+    def log_softmax(self, x: str, dim: int, functional: bool = False) -> str:
+        return self.softmax(x, dim, functional, log=True)
+
+    def softmax2d(self, x: str) -> str:
+        """nn.Softmax2d: no parameter (softmax over the channels of a rank-4 tensor)"""
+        return self._unary("nn.Softmax2d", "softmax2d", x)
+
+    def _head(self, x: str, head) -> str:
+        """the optional last layer of the toy builders: None, "softmax" or "log_softmax" over dim 1"""
+        assert head in (None, "softmax", "log_softmax"), head
+        return x if head is None else self.softmax(x, 1, log=head == "log_softmax")
+
     PAD_MODULES = {"reflect": "nn.ReflectionPad2d", "replicate": "nn.ReplicationPad2d", "circular": "nn.CircularPad2d"}
 
     def pad(self, x: str, pads, mode: str = "constant", value=0.0, functional: bool = False, module: str = None) -> str:
@@ -513,9 +533,9 @@ def build_toy_yolo(batch: int = 2, size: int = 64, seed: int = 0) -> PnnxBuilder
     return build_yolov5s(batch, size, seed, width=0.125, depth=1.0 / 3.0, nc=3)
 
 
-def build_toy_classifier(batch: int = 2, size: int = 32, seed: int = 0) -> PnnxBuilder:
+def build_toy_classifier(batch: int = 2, size: int = 32, seed: int = 0, head=None) -> PnnxBuilder:
     """Small net touching the MobileNet-side ops: BN, hardswish, hardsigmoid, SE-style broadcast mul,
-    grouped conv, sigmoid, avgpool, flatten, linear."""
+    grouped conv, sigmoid, avgpool, flatten, linear.  head="softmax" / "log_softmax": nn.Softmax(dim=1) / nn.LogSoftmax(dim=1) on the logits."""
     b = PnnxBuilder(seed)
     x = b.input((batch, 3, size, size))
     x = b.hardswish(b.batchnorm(b.conv(x, 16, 3, 2, 1, bias=False)))
@@ -530,18 +550,19 @@ def build_toy_classifier(batch: int = 2, size: int = 32, seed: int = 0) -> PnnxB
     x = b.adaptive_avgpool(x, (1, 1))
     x = b.flatten(x)
     x = b.linear(x, 10)
-    b.output(x)
+    b.output(b._head(x, head))
     return b
 
 
 def build_toy_unet(batch: int = 2, size: int = 64, base: int = 16, depth: int = 3, ncls: int = 4, seed: int = 0,
-                   up: str = "convtranspose", norm: str = "bn", act: str = "relu", norm_groups: int = 4) -> PnnxBuilder:
+                   up: str = "convtranspose", norm: str = "bn", act: str = "relu", norm_groups: int = 4, head=None) -> PnnxBuilder:
     """A small U-Net: per encoder level two [conv3x3 -> BatchNorm2d -> ReLU] then MaxPool2d(2, 2); the same block as bottleneck;
     per decoder level an up-conv, torch.cat([skip, up]) and two blocks; a 1x1 conv head.  The up-convs alternate k2 s2 p0 (one
     tap per output pixel) and k3 s2 p1 output_padding 1 (four sub-pixel phases of 4 / 2 / 2 / 1 taps).  up="bilinear": each up-conv
     is nn.Upsample(scale_factor=2, mode="bilinear", align_corners=True) + conv3x3 instead (the other widely used decoder).
     norm="gn": nn.GroupNorm(norm_groups, c) in place of every BatchNorm2d (the diffusion / modern segmentation U-Net block);
-    norm="in": nn.InstanceNorm2d(c), no affine (the pix2pix / CycleGAN generator block).  act="silu": nn.SiLU for every ReLU."""
+    norm="in": nn.InstanceNorm2d(c), no affine (the pix2pix / CycleGAN generator block).  act="silu": nn.SiLU for every ReLU.
+    head="softmax" / "log_softmax": nn.Softmax(dim=1) / nn.LogSoftmax(dim=1) over the classes of the 1x1 conv head."""
     assert up in ("convtranspose", "bilinear"), up
     assert norm in ("bn", "gn", "in") and act in ("relu", "silu"), (norm, act)
     b = PnnxBuilder(seed)
@@ -569,7 +590,7 @@ def build_toy_unet(batch: int = 2, size: int = 64, base: int = 16, depth: int = 
             u = b.conv_transpose(x, c, 2, 2, 0) if i % 2 == 0 else b.conv_transpose(x, c, 3, 2, 1, output_padding=1)
         x = block(b.cat([skip, u]), c)
     x = b.conv(x, ncls, 1, 1, 0)
-    b.output(x)
+    b.output(b._head(x, head))
     return b
 
 
@@ -647,10 +668,11 @@ def build_toy_pspnet(batch: int = 2, size: int = 52, ncls: int = 5, width: int =
     return b
 
 
-def build_toy_segnet(batch: int = 2, size: int = 64, ncls: int = 21, seed: int = 0) -> PnnxBuilder:
+def build_toy_segnet(batch: int = 2, size: int = 64, ncls: int = 21, seed: int = 0, head=None) -> PnnxBuilder:
     """A small FCN-style segmentation net: a stride-8 conv / BatchNorm2d / ReLU backbone with an FPN-style lateral in the middle
     (F.interpolate x2, align_corners=False, + add), ending in a dilated 3x3 (d = 2); a 1x1 classifier to ncls classes; then
-    F.interpolate(size=(size, size), mode="bilinear", align_corners=False), the last line of torchvision's FCN / DeepLabV3 heads."""
+    F.interpolate(size=(size, size), mode="bilinear", align_corners=False), the last line of torchvision's FCN / DeepLabV3 heads.
+    head="softmax" / "log_softmax": nn.Softmax(dim=1) / nn.LogSoftmax(dim=1) over the classes of the resized map."""
     b = PnnxBuilder(seed)
     x = b.input((batch, 3, size, size))
 
@@ -665,7 +687,7 @@ def build_toy_segnet(batch: int = 2, size: int = 64, ncls: int = 21, seed: int =
     x = cbr(x, 64, 3, 1, 2, 2)                 # dilated
     x = b.conv(x, ncls, 1, 1, 0)
     x = b.interpolate(x, mode="bilinear", align_corners=False, size=(size, size))
-    b.output(x)
+    b.output(b._head(x, head))
     return b
 
 
