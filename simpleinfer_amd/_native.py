@@ -91,6 +91,11 @@ class SiSoftmaxDesc(C.Structure):
     _fields_ = [(k, C.c_int) for k in ("n", "h", "w", "c", "in_ld", "out_ld", "axis", "log")]
 
 
+class SiPixelShuffleDesc(C.Structure):
+    """include/si_superres.h"""
+    _fields_ = [(k, C.c_int) for k in ("n", "ih", "iw", "ic", "in_ld", "oh", "ow", "oc", "out_ld", "r", "inverse")]
+
+
 class SiConv2dUpsampledSource(C.Structure):
     _fields_ = [("src", C.c_void_p), ("ih", C.c_int), ("iw", C.c_int), ("c", C.c_int), ("ld", C.c_int), ("c0", C.c_int),
                 ("inv_scale_h", C.c_float), ("inv_scale_w", C.c_float)]
@@ -280,7 +285,17 @@ def hip():
         "si_hip_softmax_f16": (i, [C.POINTER(SiSoftmaxDesc), vp, vp, vp]),
         "si_hip_softmax_kernel_name": (C.c_char_p, [C.POINTER(SiSoftmaxDesc), vp, vp, i]),
     }
-    for name, (res, args) in list(sig.items()) + list(norm.items()) + list(pad.items()) + list(pool.items()) + list(softmax.items()):
+    # include/si_superres.h: nn.PixelShuffle / nn.PixelUnshuffle and nn.PReLU
+    superres = {
+        "si_hip_pixel_shuffle_f32": (i, [C.POINTER(SiPixelShuffleDesc), vp, vp, vp]),
+        "si_hip_pixel_shuffle_f16": (i, [C.POINTER(SiPixelShuffleDesc), vp, vp, vp]),
+        "si_hip_pixel_shuffle_kernel_name": (C.c_char_p, [C.POINTER(SiPixelShuffleDesc), vp, vp, i]),
+        "si_hip_prelu_f32": (i, [vp, sz, i, i, vp, i, vp, i, vp]),
+        "si_hip_prelu_f16": (i, [vp, sz, i, i, vp, i, vp, i, vp]),
+        "si_hip_prelu_kernel_name": (C.c_char_p, [vp, sz, i, i, i, vp, i, i]),
+    }
+    for name, (res, args) in (list(sig.items()) + list(norm.items()) + list(pad.items()) + list(pool.items()) + list(softmax.items()) +
+                              list(superres.items())):
         fn = getattr(L, name)  # AttributeError here = header/library mismatch, which tests check
         fn.restype = res
         fn.argtypes = args
@@ -289,6 +304,7 @@ def hip():
     L._si_pad_signatures = pad
     L._si_pool_signatures = pool
     L._si_softmax_signatures = softmax
+    L._si_superres_signatures = superres
     _hip = L
     return L
 

@@ -24,6 +24,8 @@ SI_DECLARE_LAYER(LeakyReLU)
 SI_DECLARE_LAYER(Linear)
 SI_DECLARE_LAYER(MaxPool2d)
 SI_DECLARE_LAYER(Pad2d)
+SI_DECLARE_LAYER(PixelShuffle)
+SI_DECLARE_LAYER(PReLU)
 SI_DECLARE_LAYER(ReLU)
 SI_DECLARE_LAYER(Sigmoid)
 SI_DECLARE_LAYER(SiLU)
@@ -42,7 +44,8 @@ static std::map<std::string, LayerRegistryEntry>& Table() {
     // F.interpolate / F.upsample, the functional spellings of nn.Upsample, and nn.GroupNorm / nn.InstanceNorm2d (one class: the
     // instance norm is the group norm with one group per channel); the explicit pads (one class, layer/pad_2d.h) and nn.Tanh
     // (UnaryOp code 16 as a module); nn.AvgPool2d / F.avg_pool2d (layer/avg_pool_2d.h) and the functional spelling of the adaptive pool;
-    // nn.Softmax / nn.LogSoftmax / nn.Softmax2d / F.softmax / F.log_softmax (one class, layer/softmax.h)
+    // nn.Softmax / nn.LogSoftmax / nn.Softmax2d / F.softmax / F.log_softmax (one class, layer/softmax.h); nn.PixelShuffle / nn.PixelUnshuffle /
+    // F.pixel_shuffle / F.pixel_unshuffle (one class, layer/pixel_shuffle.h) and nn.PReLU (layer/prelu.h)
     static std::map<std::string, LayerRegistryEntry> table = {
         SI_ENTRY("nn.AdaptiveAvgPool2d", AdaptiveAvgPool2d),
         SI_ENTRY("nn.AvgPool2d", AvgPool2d),
@@ -62,6 +65,9 @@ static std::map<std::string, LayerRegistryEntry>& Table() {
         SI_ENTRY("nn.LogSoftmax", Softmax),
         SI_ENTRY("nn.Linear", Linear),
         SI_ENTRY("nn.MaxPool2d", MaxPool2d),
+        SI_ENTRY("nn.PixelShuffle", PixelShuffle),
+        SI_ENTRY("nn.PixelUnshuffle", PixelShuffle),
+        SI_ENTRY("nn.PReLU", PReLU),
         SI_ENTRY("nn.ReflectionPad2d", Pad2d),
         SI_ENTRY("nn.ReLU", ReLU),
         SI_ENTRY("nn.ReplicationPad2d", Pad2d),
@@ -80,6 +86,8 @@ static std::map<std::string, LayerRegistryEntry>& Table() {
         SI_ENTRY("F.adaptive_avg_pool2d", AdaptiveAvgPool2d),
         SI_ENTRY("F.softmax", Softmax),
         SI_ENTRY("F.log_softmax", Softmax),
+        SI_ENTRY("F.pixel_shuffle", PixelShuffle),
+        SI_ENTRY("F.pixel_unshuffle", PixelShuffle),
         SI_ENTRY("models.yolo.Detect", YoloDetect),
     };
     return table;

@@ -1051,6 +1051,63 @@ def softmax_kernel_name(x_shape, axis, half=False, in_ld=None, out_ld=None) -> s
     return _native.hip().si_hip_softmax_kernel_name(C.byref(d), C.c_void_p(256), C.c_void_p(256), 1 if half else 0).decode()
 
 
+def pixel_shuffle_desc(x_shape, r, inverse=False, in_ld=None, out_ld=None):
+    """SiPixelShuffleDesc (include/si_superres.h) of an NHWC input; the output shape is the rule's (floor division: a height, width or
+    channel count the factor does not divide gives a descriptor the entry refuses)"""
+    n, ih, iw, ic = (int(v) for v in x_shape)
+    r = int(r)
+    q = max(r, 1)
+    oh, ow, oc = (ih // q, iw // q, ic * r * r) if inverse else (ih * r, iw * r, ic // (q * q))
+    return _native.SiPixelShuffleDesc(n, ih, iw, ic, in_ld or ic, oh, ow, oc, out_ld or oc, r, 1 if inverse else 0)
+
+
+def pixel_shuffle(x_nhwc, r, inverse=False, in_ld=None, in_c_off=0, in_fill=0.0, out_ld=None, out_c_off=0, out_fill=0.0, full=False):
+    """si_hip_pixel_shuffle_f32 / _f16 (by the array's dtype) on an NHWC array: torch.nn.functional.pixel_shuffle(x, r) of the NCHW
+    tensor, or pixel_unshuffle with inverse=True.  The array's bits travel as they are.  The view hooks are the common ones."""
+    H = _native.hip()
+    x = _float_storage(x_nhwc)
+    half = x.dtype == np.float16
+    d = pixel_shuffle_desc(x.shape, r, inverse, in_ld, out_ld)
+    if d.oh < 1 or d.ow < 1 or d.oc < 1:
+        raise HipError("si_hip_pixel_shuffle: factor %d leaves no output for a %r input" % (r, tuple(x.shape)))
+    (dx, px), (dy, py) = _view_in(x, in_ld, in_c_off, in_fill), _view_out((d.n, d.oh, d.ow), d.oc, out_ld, out_c_off, out_fill, x.dtype)
+    LAST_KERNEL_NAME["si_hip_pixel_shuffle"] = H.si_hip_pixel_shuffle_kernel_name(C.byref(d), C.c_void_p(px), C.c_void_p(py), 1 if half else 0).decode()
+    fn, name = (H.si_hip_pixel_shuffle_f16, "si_hip_pixel_shuffle_f16") if half else (H.si_hip_pixel_shuffle_f32, "si_hip_pixel_shuffle_f32")
+    _chk(fn(C.byref(d), px, py, None), name)
+    return _ret(dy.to_numpy((d.n, d.oh, d.ow, out_ld or d.oc), x.dtype), d.oc, out_c_off, full)
+
+
+def pixel_shuffle_kernel_name(x_shape, r, inverse=False, half=False, in_ld=None, out_ld=None) -> str:
+    """the form for 16-byte aligned buffers of these shapes ("none": a descriptor the launch refuses)"""
+    d = pixel_shuffle_desc(x_shape, r, inverse, in_ld, out_ld)
+    return _native.hip().si_hip_pixel_shuffle_kernel_name(C.byref(d), C.c_void_p(256), C.c_void_p(256), 1 if half else 0).decode()
+
+
+def prelu(x, slope, in_ld=None, in_c_off=0, in_fill=0.0, out_ld=None, out_c_off=0, out_fill=0.0, full=False):
+    """si_hip_prelu_f32 / _f16 (by the array's dtype) on an array whose last axis is the channels (NHWC, or [N, F]):
+    torch.nn.functional.prelu with `slope` of 1 or C fp32 elements.  The view hooks are the common ones."""
+    H = _native.hip()
+    x = _float_storage(x)
+    half = x.dtype == np.float16
+    c = x.shape[-1]
+    slope = _f32(slope).reshape(-1)
+    ds = DeviceBuffer.from_numpy(slope)
+    (dx, px), (dy, py) = _view_in(x, in_ld, in_c_off, in_fill), _view_out(x.shape[:-1], c, out_ld, out_c_off, out_fill, x.dtype)
+    LAST_KERNEL_NAME["si_hip_prelu"] = H.si_hip_prelu_kernel_name(C.c_void_p(px), x.size // c, c, in_ld or c, slope.size, C.c_void_p(py), out_ld or c,
+                                                                  1 if half else 0).decode()
+    fn, name = (H.si_hip_prelu_f16, "si_hip_prelu_f16") if half else (H.si_hip_prelu_f32, "si_hip_prelu_f32")
+    _chk(fn(px, x.size // c, c, in_ld or c, ds.ptr, slope.size, py, out_ld or c, None), name)
+    return _ret(dy.to_numpy(x.shape[:-1] + (out_ld or c,), x.dtype), c, out_c_off, full)
+
+
+def prelu_kernel_name(x_shape, slope_count=1, half=False, in_ld=None, out_ld=None) -> str:
+    """the instantiation for 16-byte aligned buffers of this shape ("none": arguments the launch refuses)"""
+    c = int(x_shape[-1])
+    pixels = int(np.prod(x_shape[:-1], dtype=np.int64))
+    return _native.hip().si_hip_prelu_kernel_name(C.c_void_p(256), pixels, c, in_ld or c, int(slope_count), C.c_void_p(256), out_ld or c,
+                                                  1 if half else 0).decode()
+
+
 def flatten_nhwc(x, in_ld=None, in_c_off=0, in_fill=0.0):
     H = _native.hip()
     x = _f32(x)

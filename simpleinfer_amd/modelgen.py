@@ -182,6 +182,42 @@ class PnnxBuilder:
     def hardswish(self, x): return self._unary("nn.Hardswish", "hswish", x)
     def tanh(self, x): return self._unary("nn.Tanh", "tanh", x)
 
+    def leaky_relu(self, x, negative_slope: float = 0.01):
+        return self._unary("nn.LeakyReLU", "leakyrelu", x, dict(negative_slope=float(negative_slope)))
+
+    def pixel_shuffle(self, x: str, r: int, functional: bool = False) -> str:
+        """pnnx's nn.PixelShuffle line with torch's key `upscale_factor` (functional=True: F.pixel_shuffle, the same key):
+        [n, c r r, h, w] -> [n, c, h r, w r]"""
+        n, c, h, w = self.shapes[x]
+        r = int(r)
+        assert r >= 1 and c % (r * r) == 0, (c, r)
+        out = self._new_operand((n, c // (r * r), h * r, w * r))
+        typ, prefix = ("F.pixel_shuffle", "F_pixel_shuffle") if functional else ("nn.PixelShuffle", "pixelshuffle")
+        self._emit(typ, self._opname(prefix), [x], [out], dict(upscale_factor=r))
+        return out
+
+    def pixel_unshuffle(self, x: str, r: int, functional: bool = False) -> str:
+        """pnnx's nn.PixelUnshuffle line with torch's key `downscale_factor` (functional=True: F.pixel_unshuffle):
+        [n, c, h r, w r] -> [n, c r r, h, w]"""
+        n, c, h, w = self.shapes[x]
+        r = int(r)
+        assert r >= 1 and h % r == 0 and w % r == 0, (h, w, r)
+        out = self._new_operand((n, c * r * r, h // r, w // r))
+        typ, prefix = ("F.pixel_unshuffle", "F_pixel_unshuffle") if functional else ("nn.PixelUnshuffle", "pixelunshuffle")
+        self._emit(typ, self._opname(prefix), [x], [out], dict(downscale_factor=r))
+        return out
+
+    def prelu(self, x: str, num_parameters: int = 1) -> str:
+        """pnnx's nn.PReLU line: num_parameters (1, or the channel count) and weight of shape (num_parameters), seeded slopes in
+        [0.05, 0.4) (torch's initial value is 0.25)"""
+        c = self.shapes[x][1]
+        assert num_parameters in (1, c), (num_parameters, c)
+        name = self._opname("prelu")
+        out = self._new_operand(self.shapes[x])
+        self._emit("nn.PReLU", name, [x], [out], dict(num_parameters=int(num_parameters)),
+                   dict(weight=seeded_uniform(name + ".weight", (int(num_parameters),), 0.05, 0.4, self.seed)))
+        return out
+
     def softmax(self, x: str, dim: int, functional: bool = False, log: bool = False) -> str:
         """pnnx's nn.Softmax line with torch's key `dim` (functional=True: F.softmax; log=True: nn.LogSoftmax / F.log_softmax)"""
         if log:
@@ -616,6 +652,48 @@ def build_toy_cyclegan(batch: int = 2, size: int = 32, base: int = 8, blocks: in
     for c in (2 * base, base):
         x = b.relu(b.instance_norm(b.conv_transpose(x, c, 3, 2, 1, output_padding=1)))
     x = b.tanh(b.conv(b.pad(x, 3, pad), 3, 7, 1, 0))
+    b.output(x)
+    return b
+
+
+def build_toy_espcn(batch: int = 2, size: int = 16, r: int = 2, channels: int = 3, width: int = 16, seed: int = 0) -> PnnxBuilder:
+    """ESPCN (sub-pixel CNN) at toy width: conv5x5 -> Tanh -> conv3x3 -> Tanh -> conv3x3 to channels * r * r -> PixelShuffle(r)"""
+    b = PnnxBuilder(seed)
+    x = b.input((batch, channels, size, size))
+    x = b.tanh(b.conv(x, width, 5, 1, 2))
+    x = b.tanh(b.conv(x, width // 2, 3, 1, 1))
+    x = b.pixel_shuffle(b.conv(x, channels * r * r, 3, 1, 1), r)
+    b.output(x)
+    return b
+
+
+def build_toy_srresnet(batch: int = 2, size: int = 12, width: int = 16, blocks: int = 2, seed: int = 0) -> PnnxBuilder:
+    """SRResNet (the SRGAN generator) at toy width, x4: conv9x9 -> PReLU; `blocks` residual blocks [conv3x3 -> BN -> PReLU -> conv3x3 ->
+    BN] + x; conv3x3 -> BN, + the long skip from the first PReLU; two upsampling stages conv3x3 to 4 * width -> PixelShuffle(2) ->
+    PReLU; conv9x9 to RGB -> Tanh.  The PReLUs alternate between one shared slope (torch's default, what SRGAN uses) and one per
+    channel."""
+    b = PnnxBuilder(seed)
+    x = b.input((batch, 3, size, size))
+    x = first = b.prelu(b.conv(x, width, 9, 1, 4))
+    for k in range(blocks):
+        y = b.prelu(b.batchnorm(b.conv(x, width, 3, 1, 1)), width if k % 2 else 1)
+        y = b.batchnorm(b.conv(y, width, 3, 1, 1))
+        x = b.add(x, y)
+    x = b.add(first, b.batchnorm(b.conv(x, width, 3, 1, 1)))
+    for k in range(2):
+        x = b.prelu(b.pixel_shuffle(b.conv(x, 4 * width, 3, 1, 1), 2), 1 if k % 2 else width)
+    x = b.tanh(b.conv(x, 3, 9, 1, 4))
+    b.output(x)
+    return b
+
+
+def build_toy_esrgan_head(batch: int = 2, size: int = 16, width: int = 16, seed: int = 0) -> PnnxBuilder:
+    """The x2 head and tail of Real-ESRGAN's generator at toy width: PixelUnshuffle(2) (3 -> 12 channels at half the size) -> conv3x3 ->
+    LeakyReLU(0.2) -> nearest Upsample x2 -> conv3x3 to RGB"""
+    b = PnnxBuilder(seed)
+    x = b.input((batch, 3, size, size))
+    x = b.leaky_relu(b.conv(b.pixel_unshuffle(x, 2), width, 3, 1, 1), 0.2)
+    x = b.conv(b.upsample(x, 2.0), 3, 3, 1, 1)
     b.output(x)
     return b
 
