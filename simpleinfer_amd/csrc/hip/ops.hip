@@ -17,13 +17,17 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
+// The standalone activation operator passes a NaN on, as torch does: fmaxf / fminf alone (v_max_f32 / v_min_f32) return the OTHER operand for
+// a NaN, which turned relu(NaN) and hardsigmoid(NaN) into 0.  Every other input keeps the bits fmaxf / fminf gave it.
+__device__ __forceinline__ float act_relu(float v) { return v != v ? v : fmaxf(v, 0.0f); }
+__device__ __forceinline__ float act_clamp01(float t) { return t != t ? t : fminf(fmaxf(t, 0.0f), 1.0f); }
 __device__ __forceinline__ float act_apply(int act, float v, float p) {
     switch (act) {
-        case SI_ACT_RELU: return fmaxf(v, 0.0f);
+        case SI_ACT_RELU: return act_relu(v);
         case SI_ACT_SILU: return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v));
         case SI_ACT_SIGMOID: return __builtin_amdgcn_rcpf(1.0f + __expf(-v));
-        case SI_ACT_HARDSIGMOID: return fminf(fmaxf(v * (1.0f / 6.0f) + 0.5f, 0.0f), 1.0f);
-        case SI_ACT_HARDSWISH: return v * fminf(fmaxf(v * (1.0f / 6.0f) + 0.5f, 0.0f), 1.0f);
+        case SI_ACT_HARDSIGMOID: return act_clamp01(v * (1.0f / 6.0f) + 0.5f);
+        case SI_ACT_HARDSWISH: return v * act_clamp01(v * (1.0f / 6.0f) + 0.5f);
         case SI_ACT_LEAKYRELU: return v > 0.0f ? v : v * p;
         default: return v;
     }

@@ -17,14 +17,29 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
+// v * p rounded to odd.  The slope is an fp32 value, so the product of a widened half and the slope has up to 35 significant bits: rounded to
+// fp32's 24 and then to fp16's 11 it can differ from the product rounded once (it lands on an fp16 tie that the exact product only came
+// near: 103 of the 65536 inputs at slope 0.1).  Rounding the fp32 product to odd keeps a sticky last bit, and the store's round-to-nearest-even
+// then gives the exact product rounded once.  fmaf returns the rounding error of `hi` exactly.
+__device__ __forceinline__ float mul_round_odd(float v, float p) {
+    const float hi = v * p;
+    const float lo = fmaf(v, p, -hi);
+    unsigned u = __builtin_bit_cast(unsigned, hi);
+    if (lo != 0.0f && !(u & 1u) && fabsf(hi) < __builtin_inff()) u += ((lo < 0.0f) == (hi < 0.0f)) ? 1u : ~0u;
+    return __builtin_bit_cast(float, u);
+}
+
+// (a NaN goes through relu and the clamp: see act_apply in ops.hip)
+__device__ __forceinline__ float act_relu(float v) { return v != v ? v : fmaxf(v, 0.0f); }
+__device__ __forceinline__ float act_clamp01(float t) { return t != t ? t : fminf(fmaxf(t, 0.0f), 1.0f); }
 __device__ __forceinline__ float act_f(int act, float v, float p) {
     switch (act) {
-        case SI_ACT_RELU: return fmaxf(v, 0.0f);
+        case SI_ACT_RELU: return act_relu(v);
         case SI_ACT_SILU: return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v));
         case SI_ACT_SIGMOID: return __builtin_amdgcn_rcpf(1.0f + __expf(-v));
-        case SI_ACT_HARDSIGMOID: return fminf(fmaxf(v * (1.0f / 6.0f) + 0.5f, 0.0f), 1.0f);
-        case SI_ACT_HARDSWISH: return v * fminf(fmaxf(v * (1.0f / 6.0f) + 0.5f, 0.0f), 1.0f);
-        case SI_ACT_LEAKYRELU: return v > 0.0f ? v : v * p;
+        case SI_ACT_HARDSIGMOID: return act_clamp01(v * (1.0f / 6.0f) + 0.5f);
+        case SI_ACT_HARDSWISH: return v * act_clamp01(v * (1.0f / 6.0f) + 0.5f);
+        case SI_ACT_LEAKYRELU: return v > 0.0f ? v : mul_round_odd(v, p);
         default: return v;
     }
 }

@@ -25,6 +25,7 @@
     } while (0)
 
 // memory-bound kernels: cap the grid at ~8 workgroups per CU and grid-stride the rest
+// (2048 x 256 = 524288 items per pass: tests/test_gpu_elementwise_edges.py test_grid_stride_* make every capped launch go round three times)
 static inline unsigned si_grid_for(size_t work_items, unsigned block = 256) {
     size_t blocks = (work_items + block - 1) / block;
     const size_t cap = 256u * 8u;

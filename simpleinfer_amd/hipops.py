@@ -777,12 +777,13 @@ def segment_labels(logits, out_hw, align_corners=False, in_ld: Optional[int] = N
     return dy.to_numpy((n, d.oh, d.ow), np.uint8)
 
 
-def cat(xs, axis):
+def cat(xs, axis, out_fill=None):
+    """out_fill: the destination is pre-filled with this value or ByteFill (an element no kernel wrote then shows as the fill)"""
     H = _native.hip()
     xs = [_f32(x) for x in xs]
     shp = list(xs[0].shape)
     shp[axis] = sum(x.shape[axis] for x in xs)
-    dy = DeviceBuffer(int(np.prod(shp)) * 4)
+    dy = DeviceBuffer(int(np.prod(shp)) * 4) if out_fill is None else DeviceBuffer.from_numpy(_full(tuple(shp), np.float32, out_fill), out=True)
     off = 0
     for x in xs:
         dx = DeviceBuffer.from_numpy(x)
@@ -1108,11 +1109,13 @@ def prelu_kernel_name(x_shape, slope_count=1, half=False, in_ld=None, out_ld=Non
                                                   1 if half else 0).decode()
 
 
-def flatten_nhwc(x, in_ld=None, in_c_off=0, in_fill=0.0):
+def flatten_nhwc(x, in_ld=None, in_c_off=0, in_fill=0.0, out_fill=None):
+    """out_fill: as cat()"""
     H = _native.hip()
     x = _f32(x)
     n, h, w, c = x.shape
-    (dx, px), dy = _view_in(x, in_ld, in_c_off, in_fill), DeviceBuffer(x.nbytes)
+    (dx, px), dy = _view_in(x, in_ld, in_c_off, in_fill), (DeviceBuffer(x.nbytes) if out_fill is None else
+                                                           DeviceBuffer.from_numpy(_full((x.size,), np.float32, out_fill), out=True))
     _chk(H.si_hip_nhwc_to_nchw_f32(px, n, h, w, c, in_ld or c, dy.ptr, None), "si_hip_nhwc_to_nchw_f32")
     return dy.to_numpy((n, c * h * w))
 
