@@ -4,47 +4,13 @@
 
 #include <algorithm>
 
-#include "layer/activation.h"
-#include "layer/binary_op.h"
-#include "layer/cat.h"
 #include "layer/conv_2d.h"
-#include "layer/conv_transpose_2d.h"
-#include "layer/group_norm.h"
-#include "layer/linear.h"
-#include "layer/max_pool_2d.h"
-#include "layer/output_cast.h"
-#include "layer/upsample.h"
 #include "layer/yolo_detect.h"
+#include "engine_internal.h"
 #include "layer_registry.h"
-#include "logger.h"
 #include "pnnx/expand_expression.h"
 
 namespace SimpleInfer {
-
-namespace {
-
-// built-in operator types whose kernels honour a pixel stride on inputs and outputs
-bool HonoursPixelStride(const std::string& type) {
-    static const std::set<std::string> ok = {
-        "nn.Conv2d", "nn.ConvTranspose2d", "nn.SiLU", "nn.ReLU", "nn.Sigmoid", "nn.Hardsigmoid", "nn.Hardswish", "nn.LeakyReLU",
-        "nn.MaxPool2d", "nn.AdaptiveAvgPool2d", "nn.Upsample", "F.interpolate", "F.upsample", "torch.cat", "BinaryOp", "UnaryOp", "nn.BatchNorm2d",
-        "nn.GroupNorm", "nn.InstanceNorm2d", "nn.ReflectionPad2d", "nn.ReplicationPad2d", "nn.ZeroPad2d", "nn.ConstantPad2d", "nn.CircularPad2d",
-        "F.pad", "nn.Tanh", "nn.AvgPool2d", "F.avg_pool2d", "F.adaptive_avg_pool2d", "nn.Softmax", "nn.LogSoftmax", "nn.Softmax2d",
-        "F.softmax", "F.log_softmax", "nn.PixelShuffle", "nn.PixelUnshuffle", "F.pixel_shuffle", "F.pixel_unshuffle", "nn.PReLU", "torch.flatten",
-        "models.yolo.Detect", "pnnx.Output"};
-    return ok.count(type) > 0;
-}
-
-#define SI_TRY_HIP(expr, what)                                             \
-    {                                                                      \
-        const int _rc = (expr);                                            \
-        if (_rc != 0) {                                                    \
-            LOG(ERROR) << what << ": " << si_hip_error_string(_rc);        \
-            return Status::kFail;                                          \
-        }                                                                  \
-    }
-
-}  // namespace
 
 EngineImpl::EngineImpl() {}
 
@@ -390,107 +356,6 @@ Status EngineImpl::DestroyLayers() {
     return Status::kSuccess;
 }
 
-// ---- schedule ------------------------------------------------------------------------------------
-Status EngineImpl::CreatePipeline() {
-    // Kahn topological order over layer operators, stable w.r.t. file order (pnnx writes operators
-    // in execution order, and expression lowering inserts before the expression op)
-    std::vector<Step> order;
-    std::set<const pnnx::Operand*> ready;
-    for (auto& kv : input_tensor_nodes_) ready.insert(kv.second->operand);
-    std::vector<const pnnx::Operator*> pending;
-    for (pnnx::Operator* op : graph_->ops)
-        if (layers_.count(op->name)) pending.push_back(op);
-    while (!pending.empty()) {
-        bool progressed = false;
-        for (auto it = pending.begin(); it != pending.end();) {
-            const pnnx::Operator* op = *it;
-            bool ok = true;
-            for (pnnx::Operand* r : op->inputs) ok = ok && ready.count(r) > 0;
-            if (!ok) {
-                ++it;
-                continue;
-            }
-            Step s;
-            s.layer = layers_[op->name];
-            s.op = op;
-            order.push_back(s);
-            for (pnnx::Operand* r : op->outputs) ready.insert(r);
-            it = pending.erase(it);
-            progressed = true;
-        }
-        if (!progressed) {
-            LOG(ERROR) << "graph has a cycle or an operand without producer near [" << pending.front()->name << "]";
-            return Status::kFail;
-        }
-    }
-
-    if (opt_fuse_) {
-        CHECK_STATUS(FuseEpilogues(order));
-        CHECK_STATUS(FuseSiblingConvs(order));
-        CHECK_STATUS(FusePoolChains(order));
-        if (opt_fuse_upsample_ && opt_alias_cat_) CHECK_STATUS(FuseUpsampleIntoConvs(order));   // (fp16 storage too since round 4)
-        if (opt_fp16_ && opt_fuse_stem_) CHECK_STATUS(FuseStemPairs(order));
-        if (opt_fp16_ && opt_fuse_stem_ > 1) CHECK_STATUS(FuseStemTriples(order));
-        if (opt_fp16_ && opt_fuse_pw_) CHECK_STATUS(FuseBottleneckPairs(order));
-        if (opt_fp16_ && opt_fuse_pw_ > 1 && opt_alias_cat_) CHECK_STATUS(FuseCv3IntoPairs(order));
-    }
-    if (opt_fp16_) {
-        CHECK_STATUS(InsertOutputCasts(order));
-        // every layer is asked NOW whether it has a kernel for the storage types it ended up with.  One that has none (a 3x3 conv
-        // whose channel count is not a multiple of 32, UnaryOp ...) runs its fp32 kernel between two casts (round 4); only what
-        // even that cannot serve makes LoadModel fail -- at load, with the layer and the reason, never at the first Forward
-        CHECK_STATUS(InsertFp32Fallbacks(order));
-    }
-    plan_ = order;
-    if (opt_alias_cat_) CHECK_STATUS(AliasConcats());
-    if (opt_detect_stream_) CHECK_STATUS(PlanDetectStream());
-    return Status::kSuccess;
-}
-
-// Option "detect_stream": a Detect level only needs its own feature map, and the two finer maps are final well before the last
-// PAN layer.  Each such level is launched on a second stream right after the step that completes its input (fork: an event on
-// the main stream), beside the layers that follow; the Detect step launches the remaining level and joins (the main stream
-// waits for the side stream's event).  The output tensor is a graph output with its own allocation, so early writes into it
-// touch nothing the arena shares.  Under hipGraph capture the side stream joins the capture through the same events.
-Status EngineImpl::PlanDetectStream() {
-    for (size_t di = 0; di < plan_.size(); ++di) {
-        YoloDetect* det = dynamic_cast<YoloDetect*>(plan_[di].layer);
-        if (!det) continue;
-        if (det->OutputNodes().size() != 1 || !det->OutputNodes()[0]->operand ||
-            !output_tensor_nodes_.count(det->OutputNodes()[0]->operand->name))
-            continue;   // only when Detect writes a graph output (own buffer)
-        unsigned mask = 0;
-        std::vector<int> producer(det->InputNodes().size(), -1);
-        for (size_t k = 0; k < det->InputNodes().size(); ++k) {
-            TensorNode* n = det->InputNodes()[k];
-            if (!n || !n->operand || aliases_.count(n->operand->name)) continue;   // a view into a concat buffer has several writers
-            bool aliased_into = false;
-            for (auto& kv : aliases_) aliased_into = aliased_into || kv.second.parent == n;
-            if (aliased_into) continue;
-            for (size_t j = 0; j < di; ++j) {
-                std::vector<TensorNode*> outs = plan_[j].layer->OutputNodes();
-                if (std::find(outs.begin(), outs.end(), n) != outs.end()) producer[k] = (int)j;
-            }
-            // Worth a fork / join only for a level with real work (MI355X, YOLOv5s same-box A/B: batch 32 +1.3 %, batch 8 +-0,
-            // batch 1 -3 %: two more graph edges against launches of a few microseconds)
-            const double level_flops = 2.0 * (double)n->tensor.NumElements() * det->num_elements_;
-            if (producer[k] >= 0 && producer[k] + 1 < (int)di && (level_flops >= 4e9 || opt_detect_stream_ >= 2)) mask |= 1u << k;   // something runs in between
-        }
-        if (!mask) continue;
-        if (!side_context_) {
-            side_context_ = new Context;
-            CHECK_STATUS(side_context_->Init(context_->device(), opt_detect_priority_));
-            SI_TRY_HIP(si_hip_event_create(&ev_fork_), "event create");
-            SI_TRY_HIP(si_hip_event_create(&ev_join_), "event create");
-        }
-        det->SetEarlyLevels(side_context_, mask);
-        for (size_t k = 0; k < producer.size(); ++k)
-            if ((mask >> k) & 1u) plan_[producer[k]].detect_levels.push_back((int)k);
-        LOG(INFO) << "detect_stream: levels mask " << mask << " of [" << plan_[di].op->name << "] launch on the side stream";
-    }
-    return Status::kSuccess;
-}
-
 // A cached graph exec may still be in flight (ForwardAsync without Sync): wait for the stream before destroying any.
 Status EngineImpl::DestroyGraphCache() {
     if (!graph_cache_.empty() && context_ && context_->stream()) si_hip_stream_sync(context_->stream());
@@ -511,562 +376,12 @@ Status EngineImpl::DestroyPipeline() {
     return Status::kSuccess;
 }
 
-// conv -> [act] -> [add residual -> [act]]  ==>  one conv launch.  The fused conv runs at the slot of
-// the LAST operator of the chain, so a residual produced between the conv and the add is ready.
-Status EngineImpl::FuseEpilogues(std::vector<Step>& order) {
-    std::map<const pnnx::Operator*, size_t> index;
-    for (size_t i = 0; i < order.size(); ++i) index[order[i].op] = i;
-    std::vector<bool> removed(order.size(), false);
-
-    auto sole_consumer = [&](const pnnx::Operand* r) -> const pnnx::Operator* {
-        if (output_tensor_nodes_.count(r->name)) return nullptr;
-        if (r->consumers.size() != 1) return nullptr;
-        const pnnx::Operator* c = r->consumers[0];
-        if (!index.count(c) || removed[index[c]]) return nullptr;  // not a layer, or already absorbed
-        return c;
-    };
-
-    for (size_t i = 0; i < order.size(); ++i) {
-        if (removed[i]) continue;
-        // transposed conv -> act  ==>  one launch (its epilogue has the activation only: a residual add stays a launch of its own)
-        if (ConvTranspose2d* ct = dynamic_cast<ConvTranspose2d*>(order[i].layer)) {
-            if (order[i].op->type != "nn.ConvTranspose2d" || order[i].op->outputs.size() != 1) continue;
-            const pnnx::Operand* out = order[i].op->outputs[0];
-            const pnnx::Operator* c = sole_consumer(out);
-            ActivationLayer* a = c ? dynamic_cast<ActivationLayer*>(order[index[c]].layer) : nullptr;
-            if (!a || c->inputs.size() != 1 || c->outputs.size() != 1) continue;
-            ct->SetFusion(a->ActCode(), a->ActCode() == SI_ACT_LEAKYRELU ? a->ActParam() : 0.0f);
-            ct->SetOutputNodes({tensor_nodes_[c->outputs[0]->name]});
-            removed[index[c]] = true;   // (the activation reads nothing else: the fused launch keeps the conv's slot)
-            fused_ops_.insert(c->name);
-            dead_operands_.insert(out->name);
-            continue;
-        }
-        // group / instance norm -> act  ==>  one launch (or the same two): the activation runs in the normalise pass's epilogue
-        if (GroupNorm* gn = dynamic_cast<GroupNorm*>(order[i].layer)) {
-            if ((order[i].op->type != "nn.GroupNorm" && order[i].op->type != "nn.InstanceNorm2d") || order[i].op->outputs.size() != 1) continue;
-            const pnnx::Operand* out = order[i].op->outputs[0];
-            const pnnx::Operator* c = sole_consumer(out);
-            ActivationLayer* a = c ? dynamic_cast<ActivationLayer*>(order[index[c]].layer) : nullptr;
-            if (!a || c->inputs.size() != 1 || c->outputs.size() != 1) continue;
-            gn->SetFusion(a->ActCode(), a->ActCode() == SI_ACT_LEAKYRELU ? a->ActParam() : 0.0f);
-            gn->SetOutputNodes({tensor_nodes_[c->outputs[0]->name]});
-            removed[index[c]] = true;
-            fused_ops_.insert(c->name);
-            dead_operands_.insert(out->name);
-            continue;
-        }
-        Conv2d* conv = dynamic_cast<Conv2d*>(order[i].layer);
-        if (!conv || order[i].op->type != "nn.Conv2d" || order[i].op->outputs.size() != 1) continue;
-
-        const pnnx::Operand* cur = order[i].op->outputs[0];
-        size_t last = i;
-        int act1 = SI_ACT_NONE, act2 = SI_ACT_NONE;
-        float act_param = 0.f;
-        TensorNode* residual = nullptr;
-        std::vector<const pnnx::Operator*> absorbed;
-        std::vector<const pnnx::Operand*> dead;
-
-        auto try_act = [&](int& slot) {
-            const pnnx::Operator* c = sole_consumer(cur);
-            if (!c) return;
-            ActivationLayer* a = dynamic_cast<ActivationLayer*>(order[index[c]].layer);
-            if (!a || c->inputs.size() != 1 || c->outputs.size() != 1) return;
-            if (slot != SI_ACT_NONE) return;
-            if (a->ActCode() == SI_ACT_LEAKYRELU && (act1 == SI_ACT_LEAKYRELU) && act_param != a->ActParam()) return;
-            slot = a->ActCode();
-            if (a->ActCode() == SI_ACT_LEAKYRELU) act_param = a->ActParam();
-            absorbed.push_back(c);
-            dead.push_back(cur);
-            cur = c->outputs[0];
-            last = index[c];
-        };
-
-        try_act(act1);
-        {
-            const pnnx::Operator* c = sole_consumer(cur);
-            BinaryOp* b = c ? dynamic_cast<BinaryOp*>(order[index[c]].layer) : nullptr;
-            if (b && b->binary_op_type_ == BinaryOp::BinaryOpType::kAdd && c->inputs.size() == 2 && c->outputs.size() == 1 &&
-                c->inputs[0] != c->inputs[1]) {
-                const pnnx::Operand* other = c->inputs[0] == cur ? c->inputs[1] : c->inputs[0];
-                const std::vector<int>& so = tensor_nodes_[c->outputs[0]->name]->tensor.Shape();
-                const bool same = IsSameShape(tensor_nodes_[other->name]->tensor.Shape(), so) &&
-                                  IsSameShape(tensor_nodes_[cur->name]->tensor.Shape(), so);
-                if (same) {
-                    residual = tensor_nodes_[other->name];
-                    absorbed.push_back(c);
-                    dead.push_back(cur);
-                    cur = c->outputs[0];
-                    last = index[c];
-                    try_act(act2);
-                }
-            }
-        }
-        if (absorbed.empty()) continue;
-
-        conv->SetFusion(act1, residual, act2, act_param);
-        conv->SetOutputNodes({tensor_nodes_[cur->name]});
-        for (const pnnx::Operator* c : absorbed) {
-            removed[index[c]] = true;
-            fused_ops_.insert(c->name);
-        }
-        for (const pnnx::Operand* r : dead) dead_operands_.insert(r->name);
-        if (last != i) {
-            order[last] = order[i];
-            removed[last] = false;
-            removed[i] = true;
-        }
-    }
-
-    std::vector<Step> out;
-    for (size_t i = 0; i < order.size(); ++i)
-        if (!removed[i]) out.push_back(order[i]);
-    order.swap(out);
-    return Status::kSuccess;
-}
-
-// Two 1x1 convs reading the same operand with the same geometry (YOLOv5 C3: cv1 and cv2) become one launch with
-// twice the output channels and a split destination: the input is read once and the launch has twice the tiles.
-Status EngineImpl::FuseSiblingConvs(std::vector<Step>& order) {
-    std::vector<bool> removed(order.size(), false);
-    for (size_t i = 0; i < order.size(); ++i) {
-        if (removed[i]) continue;
-        Conv2d* a = dynamic_cast<Conv2d*>(order[i].layer);
-        if (!a || order[i].op->type != "nn.Conv2d" || a->InputNodes().size() != 1 || a->OutputNodes().size() != 1) continue;
-        for (size_t j = i + 1; j < order.size(); ++j) {
-            if (removed[j]) continue;
-            Conv2d* b = dynamic_cast<Conv2d*>(order[j].layer);
-            if (!b || order[j].op->type != "nn.Conv2d" || b->InputNodes().size() != 1 || b->OutputNodes().size() != 1) continue;
-            if (a->InputNodes()[0] != b->InputNodes()[0] || !a->CanFuseSibling(*b)) continue;
-            const std::vector<int>& sa = a->OutputNodes()[0]->tensor.Shape();
-            const std::vector<int>& sb = b->OutputNodes()[0]->tensor.Shape();
-            if (sa.size() != 4 || sb.size() != 4 || sa[0] != sb[0] || sa[1] != sb[1] || sa[2] != sb[2]) continue;
-            a->SetSibling(b);
-            a->SetOutputNodes({a->OutputNodes()[0], b->OutputNodes()[0]});
-            removed[j] = true;
-            sibling_ops_.insert(order[j].op->name);
-            break;
-        }
-    }
-    std::vector<Step> out;
-    for (size_t i = 0; i < order.size(); ++i)
-        if (!removed[i]) out.push_back(order[i]);
-    order.swap(out);
-    return Status::kSuccess;
-}
-
-// SPPF: maxpool5 -> maxpool5 -> maxpool5 (each fed by the previous one, every intermediate also read by the concat)
-// ==> one launch at the first pool's slot that reads the input once and writes all three operands.
-Status EngineImpl::FusePoolChains(std::vector<Step>& order) {
-    std::vector<bool> removed(order.size(), false);
-    auto pool_at = [&](size_t i) -> MaxPool2d* {
-        if (removed[i]) return nullptr;
-        MaxPool2d* p = dynamic_cast<MaxPool2d*>(order[i].layer);
-        return (p && p->InputNodes().size() == 1 && p->OutputNodes().size() == 1 && p->chain_.empty()) ? p : nullptr;
-    };
-    auto follower = [&](size_t from, MaxPool2d* head) -> size_t {
-        for (size_t j = from + 1; j < order.size(); ++j) {
-            MaxPool2d* p = pool_at(j);
-            if (p && p->InputNodes()[0] == head->OutputNodes()[0] && head->ChainHead(*p) &&
-                IsSameShape(p->OutputNodes()[0]->tensor.Shape(), head->OutputNodes()[0]->tensor.Shape()))
-                return j;
-        }
-        return 0;
-    };
-    for (size_t i = 0; i < order.size(); ++i) {
-        MaxPool2d* a = pool_at(i);
-        if (!a || !IsSameShape(a->InputNodes()[0]->tensor.Shape(), a->OutputNodes()[0]->tensor.Shape())) continue;
-        const size_t j = follower(i, a);
-        if (j == 0) continue;
-        MaxPool2d* b = pool_at(j);
-        const size_t k = follower(j, b);
-        if (k == 0) continue;
-        MaxPool2d* c = pool_at(k);
-        a->SetChain(b, c);
-        a->SetOutputNodes({a->OutputNodes()[0], b->OutputNodes()[0], c->OutputNodes()[0]});
-        removed[j] = removed[k] = true;
-        fused_ops_.insert(order[j].op->name);
-        fused_ops_.insert(order[k].op->name);
-    }
-    std::vector<Step> out;
-    for (size_t i = 0; i < order.size(); ++i)
-        if (!removed[i]) out.push_back(order[i]);
-    order.swap(out);
-    return Status::kSuccess;
-}
-
-// nn.Upsample(nearest) -> torch.cat(dim = channels) -> 1x1 convs only  ==>  the upsample launch disappears: every consumer conv
-// reads the upsampled channel range from the LOW-RESOLUTION tensor at the nearest-neighbour source pixel (dual-source A rows,
-// si_hip_conv2d_upcat_f32), with the reference's index rule (src/layer/upsample.cpp:85-92), so the results are bit-identical to
-// the unfused schedule.  YOLOv5s: both upsamples of the PAN top-down path (20x20x256 -> 40x40, 40x40x128 -> 80x80): 131 MB per
-// batch-32 forward that are neither written nor read back.  Requires concat aliasing (the cat then has nothing to copy for that
-// input) and fp32 storage.
-Status EngineImpl::FuseUpsampleIntoConvs(std::vector<Step>& order) {
-    std::map<const pnnx::Operator*, size_t> index;
-    for (size_t i = 0; i < order.size(); ++i) index[order[i].op] = i;
-    std::vector<bool> removed(order.size(), false);
-    for (size_t i = 0; i < order.size(); ++i) {
-        Upsample* up = dynamic_cast<Upsample*>(order[i].layer);
-        if (!up || order[i].op->type != "nn.Upsample" || up->InputNodes().size() != 1 || up->OutputNodes().size() != 1) continue;
-        if (!up->IsNearestByScale()) continue;   // (bilinear, size=: the dual-source conv kernels implement the nearest-by-scale index rule only)
-        const pnnx::Operand* u = up->OutputNodes()[0]->operand;
-        if (!u || u->consumers.size() != 1 || output_tensor_nodes_.count(u->name)) continue;
-        const pnnx::Operator* cat = u->consumers[0];
-        if (!cat || cat->type != "torch.cat" || cat->outputs.size() != 1 || !index.count(cat)) continue;
-        Cat* cat_layer = dynamic_cast<Cat*>(order[index[cat]].layer);
-        if (!cat_layer || cat_layer->NhwcAxis() != 3) continue;
-        const std::vector<int>& us = up->OutputNodes()[0]->tensor.Shape();
-        if (us.size() != 4) continue;
-        // channel offset of the upsampled tensor inside the concat
-        int c0 = 0;
-        bool found = false;
-        for (const pnnx::Operand* r : cat->inputs) {
-            if (r == u) { found = true; break; }
-            const std::vector<int>& rs = tensor_nodes_[r->name]->tensor.Shape();
-            if (rs.size() != 4) { found = false; break; }
-            c0 += rs[3];
-        }
-        if (!found) continue;
-        const pnnx::Operand* co = cat->outputs[0];
-        if (output_tensor_nodes_.count(co->name) || co->consumers.empty()) continue;
-        // every reader of the concat must be a pointwise conv that can take the dual-source form (a sibling-fused secondary has
-        // left the order: its primary reads the same operand)
-        std::vector<Conv2d*> readers;
-        bool ok = true;
-        for (const pnnx::Operator* c : co->consumers) {
-            if (!c || c->type != "nn.Conv2d") { ok = false; break; }
-            if (sibling_ops_.count(c->name)) continue;
-            Conv2d* conv = index.count(c) ? dynamic_cast<Conv2d*>(order[index[c]].layer) : nullptr;
-            if (!conv || conv->UpsampledSource() || !conv->CanReadUpsampledFrom(up->InputNodes()[0], c0, up->scale_factor_h_, up->scale_factor_w_)) { ok = false; break; }
-            readers.push_back(conv);
-        }
-        // ... and every sibling-fused secondary must have its primary among them
-        for (const pnnx::Operator* c : co->consumers) {
-            if (!ok || !c || !sibling_ops_.count(c->name)) continue;
-            bool has_primary = false;
-            for (Conv2d* r : readers) has_primary = has_primary || (r->Sibling() && r->Sibling()->GetOp() == c);
-            ok = has_primary;
-        }
-        if (!ok || readers.empty()) continue;
-        for (Conv2d* r : readers) r->SetUpsampledSource(up->InputNodes()[0], c0, up->scale_factor_h_, up->scale_factor_w_);
-        removed[i] = true;
-        fused_ops_.insert(order[i].op->name);
-    }
-    std::vector<Step> out;
-    for (size_t i = 0; i < order.size(); ++i)
-        if (!removed[i]) out.push_back(order[i]);
-    order.swap(out);
-    return Status::kSuccess;
-}
-
-// fp16 storage (round 4): the RGB stem conv (fp32 image in, 32 half channels out) whose ONLY reader is a 3x3 stride-2 conv over those
-// 32 channels -- YOLOv5's conv_0 -> conv_1 -- becomes one launch at the second conv's slot (si_hip_conv2d_stem_s2c32_f16): the
-// intermediate (210 MB at batch 32) is computed tile by tile in LDS and never written.  The stem's step leaves the order, its
-// operand is never allocated; the kernel is asked NOW, with the bound shapes, whether it takes the pair.
-Status EngineImpl::FuseStemPairs(std::vector<Step>& order) {
-    std::map<const pnnx::Operator*, size_t> index;
-    for (size_t i = 0; i < order.size(); ++i) index[order[i].op] = i;
-    std::vector<bool> removed(order.size(), false);
-    for (size_t i = 0; i < order.size(); ++i) {
-        Conv2d* stem = dynamic_cast<Conv2d*>(order[i].layer);
-        if (!stem || order[i].op->type != "nn.Conv2d" || stem->InputNodes().size() != 1 || stem->OutputNodes().size() != 1) continue;
-        const pnnx::Operand* img = stem->InputNodes()[0]->operand;
-        const pnnx::Operand* mid = stem->OutputNodes()[0]->operand;
-        if (!img || !mid || !input_tensor_nodes_.count(img->name) || output_tensor_nodes_.count(mid->name) || mid->consumers.size() != 1) continue;
-        const pnnx::Operator* c = mid->consumers[0];
-        if (!c || c->type != "nn.Conv2d" || !index.count(c) || sibling_ops_.count(c->name)) continue;
-        Conv2d* conv = dynamic_cast<Conv2d*>(order[index[c]].layer);
-        if (!conv || !conv->CanFuseStemProducer(*stem)) continue;
-        conv->SetStemProducer(stem);
-        dead_operands_.insert(mid->name);
-        removed[i] = true;
-        fused_ops_.insert(order[i].op->name);
-    }
-    std::vector<Step> out;
-    for (size_t i = 0; i < order.size(); ++i)
-        if (!removed[i]) out.push_back(order[i]);
-    order.swap(out);
-    return Status::kSuccess;
-}
-
-// fp16 storage (round 6): the conv that took the stem (FuseStemPairs) and the 1x1 conv over its 64 channels that is its only reader -- with the
-// sibling that conv computes as well: YOLOv5's first C3 reads the tensor twice, cv1 and cv2, which FuseSiblingConvs has made ONE conv -- become
-// one launch at the 1x1 conv's slot (si_hip_conv2d_stem_s2c32_pw_f16); the 64-channel tensor between them is never allocated.
-Status EngineImpl::FuseStemTriples(std::vector<Step>& order) {
-    std::map<const pnnx::Operator*, size_t> index;
-    for (size_t i = 0; i < order.size(); ++i) index[order[i].op] = i;
-    std::vector<bool> removed(order.size(), false);
-    for (size_t i = 0; i < order.size(); ++i) {
-        Conv2d* c1 = dynamic_cast<Conv2d*>(order[i].layer);
-        if (!c1 || order[i].op->type != "nn.Conv2d" || !c1->StemProducer() || c1->OutputNodes().size() != 1) continue;
-        const pnnx::Operand* mid = c1->OutputNodes()[0]->operand;
-        if (!mid || output_tensor_nodes_.count(mid->name) || mid->consumers.empty()) continue;
-        // every reader of `mid` is the same scheduled 1x1 conv or the sibling it computes
-        Conv2d* pw = nullptr;
-        bool ok = true;
-        for (const pnnx::Operator* c : mid->consumers) {
-            if (!c || c->type != "nn.Conv2d") { ok = false; break; }
-            if (sibling_ops_.count(c->name)) continue;
-            if (!index.count(c) || pw) { ok = false; break; }
-            pw = dynamic_cast<Conv2d*>(order[index[c]].layer);
-        }
-        if (!ok || !pw) continue;
-        for (const pnnx::Operator* c : mid->consumers)
-            if (sibling_ops_.count(c->name) && (!pw->Sibling() || pw->Sibling()->GetOp() != c)) ok = false;
-        if (!ok || !pw->CanFuseStemPairProducer(*c1)) continue;
-        pw->SetStemPairProducer(c1);
-        dead_operands_.insert(mid->name);
-        removed[i] = true;
-        fused_ops_.insert(order[i].op->name);
-    }
-    std::vector<Step> out;
-    for (size_t i = 0; i < order.size(); ++i)
-        if (!removed[i]) out.push_back(order[i]);
-    order.swap(out);
-    return Status::kSuccess;
-}
-
-// fp16 storage (round 5): conv A (1x1, c -> c, SiLU) whose ONLY consumer is conv B (3x3 s1 p1 over c channels that the slab kernel
-// serves, SiLU, optional shortcut) -- the C3 bottleneck's pair -- becomes one launch at B's slot; A's output is never allocated.
-Status EngineImpl::FuseBottleneckPairs(std::vector<Step>& order) {
-    std::map<const pnnx::Operator*, size_t> index;
-    for (size_t i = 0; i < order.size(); ++i) index[order[i].op] = i;
-    std::vector<bool> removed(order.size(), false);
-    for (size_t i = 0; i < order.size(); ++i) {
-        Conv2d* pw = dynamic_cast<Conv2d*>(order[i].layer);
-        if (!pw || order[i].op->type != "nn.Conv2d" || pw->InputNodes().size() != 1 || pw->OutputNodes().size() != 1) continue;
-        const pnnx::Operand* mid = pw->OutputNodes()[0]->operand;
-        if (!mid || output_tensor_nodes_.count(mid->name) || mid->consumers.size() != 1 || sibling_ops_.count(order[i].op->name)) continue;
-        const pnnx::Operator* c = mid->consumers[0];
-        if (!c || c->type != "nn.Conv2d" || !index.count(c) || sibling_ops_.count(c->name)) continue;
-        Conv2d* conv = dynamic_cast<Conv2d*>(order[index[c]].layer);
-        if (!conv || !conv->CanFusePointwiseProducer(*pw)) continue;
-        conv->SetPointwiseProducer(pw);
-        dead_operands_.insert(mid->name);
-        removed[i] = true;
-        fused_ops_.insert(order[i].op->name);
-    }
-    std::vector<Step> out;
-    for (size_t i = 0; i < order.size(); ++i)
-        if (!removed[i]) out.push_back(order[i]);
-    order.swap(out);
-    return Status::kSuccess;
-}
-
-// fp16 storage (round 6): torch.cat([y, z], channels) -> 1x1 conv (a YOLOv5 C3's closing cv3) where y is the output of a fused bottleneck pair
-// (FuseBottleneckPairs) that only the concat reads: the pair, the concat and the conv become ONE launch at the conv's slot
-// (si_hip_conv2d_pw_cv3_f16); y and the concat operand are never allocated, z keeps a buffer of its own (nothing aliases into a concat
-// that no longer exists).
-Status EngineImpl::FuseCv3IntoPairs(std::vector<Step>& order) {
-    std::map<const pnnx::Operator*, size_t> index;
-    for (size_t i = 0; i < order.size(); ++i) index[order[i].op] = i;
-    std::vector<bool> removed(order.size(), false);
-    for (size_t i = 0; i < order.size(); ++i) {
-        Cat* cat = dynamic_cast<Cat*>(order[i].layer);
-        if (!cat || order[i].op->type != "torch.cat" || cat->NhwcAxis() != 3 || order[i].op->inputs.size() != 2 || order[i].op->outputs.size() != 1) continue;
-        const pnnx::Operand* y = order[i].op->inputs[0];
-        const pnnx::Operand* z = order[i].op->inputs[1];
-        const pnnx::Operand* cc = order[i].op->outputs[0];
-        if (!y || !z || !cc || y == z || output_tensor_nodes_.count(y->name) || output_tensor_nodes_.count(cc->name)) continue;
-        if (y->consumers.size() != 1 || cc->consumers.size() != 1) continue;
-        // the scheduled step that WRITES y: after the epilogue fusion that is the conv whose output node y's is (y's pnnx producer is then the
-        // folded SiLU / add operator, which no longer has a step)
-        size_t pi = order.size();
-        for (size_t j = 0; j < i && pi == order.size(); ++j)
-            if (!removed[j])
-                for (TensorNode* n : order[j].layer->OutputNodes())
-                    if (n && n->operand == y) pi = j;
-        if (pi == order.size()) continue;
-        const pnnx::Operator* c3 = cc->consumers[0];
-        if (!c3 || c3->type != "nn.Conv2d" || !index.count(c3) || sibling_ops_.count(c3->name)) continue;
-        Conv2d* pair = dynamic_cast<Conv2d*>(order[pi].layer);
-        Conv2d* conv = dynamic_cast<Conv2d*>(order[index[c3]].layer);
-        if (!pair || !conv || !pair->PointwiseProducer() || pair->OutputNodes().size() != 1) continue;
-        TensorNode* zn = tensor_nodes_[z->name];
-        if (!conv->CanFuseCv3Pair(*pair, zn)) continue;
-        conv->SetCv3Pair(pair, zn);
-        dead_operands_.insert(y->name);
-        dead_operands_.insert(cc->name);
-        removed[pi] = true;
-        removed[i] = true;
-        fused_ops_.insert(order[pi].op->name);
-        fused_ops_.insert(order[i].op->name);
-    }
-    std::vector<Step> out;
-    for (size_t i = 0; i < order.size(); ++i)
-        if (!removed[i]) out.push_back(order[i]);
-    order.swap(out);
-    return Status::kSuccess;
-}
-
-// fp16 storage: graph outputs keep the file's fp32 type.  Conv2d / Linear / Detect write fp32 from their own epilogue;
-// any other producer fed by half operands writes a half staging operand instead, and a convert step follows it.
-Status EngineImpl::InsertOutputCasts(std::vector<Step>& order) {
-    for (auto& kv : output_tensor_nodes_) {
-        TensorNode* out = kv.second;
-        if (out->tensor.GetDataType() != DataType::kFloat32) continue;
-        for (size_t i = 0; i < order.size(); ++i) {
-            Layer* layer = order[i].layer;
-            std::vector<TensorNode*> outs = layer->OutputNodes();
-            auto slot = std::find(outs.begin(), outs.end(), out);
-            if (slot == outs.end()) continue;
-            if (dynamic_cast<Conv2d*>(layer) || dynamic_cast<Linear*>(layer) || dynamic_cast<YoloDetect*>(layer)) break;
-            bool half_in = false;
-            for (const TensorNode* in : layer->InputNodes()) half_in = half_in || in->tensor.GetDataType() == DataType::kFloat16;
-            if (!half_in) break;
-
-            const std::string staging_name = kv.first + "#f16";
-            TensorNode* staging = new TensorNode;
-            staging->operand = out->operand;
-            staging->tensor = Tensor(DataType::kFloat16, out->tensor.Shape(), MemoryType::kDevice, false);
-            tensor_nodes_[staging_name] = staging;
-            *slot = staging;
-            layer->SetOutputNodes(outs);
-
-            OutputCast* cast = new OutputCast(order[i].op->name);
-            layers_[cast->GetOp()->name] = cast;
-            cast->SetContext(context_);
-            cast->SetInputNodes({staging});
-            cast->SetOutputNodes({out});
-            CHECK_STATUS(cast->Validate());
-            Step s;
-            s.layer = cast;
-            s.op = cast->GetOp();
-            order.insert(order.begin() + i + 1, s);
-            break;
-        }
-    }
-    return Status::kSuccess;
-}
-
-// fp16 storage, a layer without an fp16 kernel: its half operands get fp32 SHADOW tensors -- a cast step in front of the layer
-// for every half tensor it reads (inputs, a fused residual), one behind it for every half tensor it writes -- and the layer runs
-// the kernel it has.  What the reference computes in fp32 (src/layer/conv_2d.cpp:94-101 rejects anything else) is then computed
-// in fp32 here too; the neighbours keep their fp16 storage.
-Status EngineImpl::InsertFp32Fallbacks(std::vector<Step>& order) {
-    int serial = 0;
-    for (size_t i = 0; i < order.size(); ++i) {
-        Layer* layer = order[i].layer;
-        std::string why;
-        if (layer->HalfStorageOk(why)) continue;
-        const std::string lname = order[i].op->name;
-        auto refuse = [&](const std::string& more) {
-            LOG(ERROR) << "fp16 storage: layer [" << lname << "] (" << order[i].op->type << ") cannot run: " << why << more
-                       << "; load the model without the fp16 option";
-            return Status::kUnsupport;
-        };
-        auto shadow_of = [&](TensorNode* n, const char* tag) {
-            TensorNode* sh = new TensorNode;
-            sh->operand = n->operand;
-            sh->tensor = Tensor(DataType::kFloat32, n->tensor.Shape(), MemoryType::kDevice, false);
-            tensor_nodes_[(n->operand ? n->operand->name : lname) + "#" + tag + std::to_string(serial++)] = sh;
-            return sh;
-        };
-        std::vector<Step> before, after;
-        auto cast_step = [&](TensorNode* from, TensorNode* to, const char* suffix, std::vector<Step>& where) -> Status {
-            OutputCast* cast = new OutputCast(lname, (std::string(suffix) + std::to_string(serial++)).c_str());
-            layers_[cast->GetOp()->name] = cast;
-            cast->SetContext(context_);
-            cast->SetInputNodes({from});
-            cast->SetOutputNodes({to});
-            CHECK_STATUS(cast->Validate());
-            Step s;
-            s.layer = cast;
-            s.op = cast->GetOp();
-            where.push_back(s);
-            return Status::kSuccess;
-        };
-        std::map<TensorNode*, TensorNode*> in_shadow;
-        std::vector<TensorNode*> ins = layer->InputNodes(), outs = layer->OutputNodes(), extra;
-        layer->ExtraReads(extra);
-        for (TensorNode*& n : ins) {
-            if (n->tensor.GetDataType() != DataType::kFloat16) continue;
-            if (!in_shadow.count(n)) {
-                in_shadow[n] = shadow_of(n, "f32in");
-                CHECK_STATUS(cast_step(n, in_shadow[n], ".in_to_f32.", before));
-            }
-            n = in_shadow[n];
-        }
-        for (TensorNode* n : extra) {
-            if (n->tensor.GetDataType() != DataType::kFloat16) continue;
-            if (!in_shadow.count(n)) {
-                in_shadow[n] = shadow_of(n, "f32in");
-                CHECK_STATUS(cast_step(n, in_shadow[n], ".in_to_f32.", before));
-            }
-            if (!layer->ReplaceExtraRead(n, in_shadow[n])) return refuse(" (and its fused extra operand cannot be rebound to an fp32 copy)");
-        }
-        for (TensorNode*& n : outs) {
-            if (n->tensor.GetDataType() != DataType::kFloat16) continue;
-            TensorNode* sh = shadow_of(n, "f32out");
-            CHECK_STATUS(cast_step(sh, n, ".out_to_f16.", after));
-            n = sh;
-        }
-        layer->SetInputNodes(ins);
-        layer->SetOutputNodes(outs);
-        std::string still;
-        if (Status::kSuccess != layer->Validate() || !layer->HalfStorageOk(still)) return refuse(still.empty() ? "" : " / with fp32 operands: " + still);
-        LOG(INFO) << "fp16 storage: layer [" << lname << "] has no fp16 kernel (" << why << "): it runs in fp32 between " << before.size()
-                  << " + " << after.size() << " casts";
-        order.insert(order.begin() + i + 1, after.begin(), after.end());
-        order.insert(order.begin() + i, before.begin(), before.end());
-        i += before.size() + after.size();
-    }
-    return Status::kSuccess;
-}
-
-// torch.cat on the channel axis: every eligible input operand becomes a view into the concat output
-// (same pixel grid, pixel stride = total channels), so its producer writes in place and Cat::Forward
-// finds nothing left to copy.
-Status EngineImpl::AliasConcats() {
-    for (const Step& s : plan_) {
-        Cat* cat = dynamic_cast<Cat*>(s.layer);
-        if (!cat || s.op->type != "torch.cat" || cat->NhwcAxis() != 3 || s.op->outputs.size() != 1) continue;
-        TensorNode* out = cat->OutputNodes()[0];  // the staging operand when an output cast follows
-        if (out->tensor.Shape().size() != 4) continue;
-        int offset = 0;
-        std::set<const pnnx::Operand*> seen;
-        for (const pnnx::Operand* r : s.op->inputs) {
-            const std::vector<int>& rs = tensor_nodes_[r->name]->tensor.Shape();
-            const int c = rs.empty() ? 0 : rs.back();
-            bool ok = rs.size() == 4 && !seen.count(r) && !aliases_.count(r->name) &&
-                      !input_tensor_nodes_.count(r->name) && !output_tensor_nodes_.count(r->name) && r->producer &&
-                      r->producer->type != "torch.cat" && HonoursPixelStride(r->producer->type) &&
-                      tensor_nodes_[r->name]->tensor.GetDataType() == out->tensor.GetDataType() &&
-                      (offset * ElementSize(out->tensor.GetDataType()) % 16 == 0);
-            for (const pnnx::Operator* c2 : r->consumers) ok = ok && c2 && HonoursPixelStride(c2->type);
-            // flatten writes dense NCHW and Detect writes rank-3 rows: they never feed a rank-4 cat
-            if (ok && (r->producer->type == "torch.flatten" || r->producer->type == "models.yolo.Detect")) ok = false;
-            seen.insert(r);
-            if (ok) {
-                Alias a;
-                a.parent = out;
-                a.channel_offset = offset;
-                aliases_[r->name] = a;
-            }
-            offset += c;
-        }
-    }
-    return Status::kSuccess;
-}
-
 // ---- memory --------------------------------------------------------------------------------------
 Status EngineImpl::AllocateTensorMemory() {
     // 1. Every live operand that is not an alias gets HBM.  The reference mallocs each operand separately and never reuses
     //    (src/engine_impl.cpp:465-482, "TODO" at :466).  Here graph inputs / outputs keep their own buffers (they outlive the
-    //    forward), and the intermediates are packed into ONE arena: two buffers may overlap in memory iff no launch of the plan
-    //    needs both -- a buffer lives from the first step that writes it (or any alias into it) to the last step that reads it.
-    struct Buf {
-        TensorNode* node;
-        size_t bytes, offset;
-        int first, last;
-    };
-    std::map<TensorNode*, size_t> buf_of;   // root buffer node -> index in bufs
-    std::vector<Buf> bufs;
-    auto root_of = [&](TensorNode* n) -> TensorNode* {
-        if (!n || !n->operand) return n;
-        auto al = aliases_.find(n->operand->name);
-        return al != aliases_.end() ? al->second.parent : n;
-    };
+    //    forward), and the intermediates share ONE arena by lifetime (PlanArena, engine_plan.cpp).
+    std::vector<TensorNode*> arena_nodes;
     unshared_bytes_ = arena_bytes_ = 0;
     for (auto& kv : tensor_nodes_) {
         const std::string& name = kv.first;
@@ -1089,59 +404,10 @@ Status EngineImpl::AllocateTensorMemory() {
             if (!io) unshared_bytes_ += bytes, arena_bytes_ += bytes;
             continue;
         }
-        buf_of[kv.second] = bufs.size();
-        bufs.push_back(Buf{kv.second, (bytes + 255) & ~size_t(255), 0, -1, -1});
+        arena_nodes.push_back(kv.second);
         unshared_bytes_ += bytes;
     }
-    if (!bufs.empty()) {
-        auto touch = [&](TensorNode* n, int step) {
-            auto it = buf_of.find(root_of(n));
-            if (it == buf_of.end()) return;
-            Buf& b = bufs[it->second];
-            if (b.first < 0) b.first = step;
-            b.last = step;
-        };
-        for (size_t i = 0; i < plan_.size(); ++i) {
-            Layer* L = plan_[i].layer;
-            std::vector<TensorNode*> extra;
-            L->ExtraReads(extra);
-            for (TensorNode* n : L->InputNodes()) touch(n, (int)i);
-            for (TensorNode* n : extra) touch(n, (int)i);
-            for (TensorNode* n : L->OutputNodes()) touch(n, (int)i);
-        }
-        // buffers no step of the plan touches (operands only a fused-away operator produced) live for the whole forward
-        for (Buf& b : bufs)
-            if (b.first < 0) { b.first = 0; b.last = (int)plan_.size(); }
-        // greedy by size: place each buffer at the lowest offset that is free during its whole life
-        std::vector<size_t> order(bufs.size());
-        for (size_t i = 0; i < order.size(); ++i) order[i] = i;
-        std::sort(order.begin(), order.end(), [&](size_t x, size_t y) { return bufs[x].bytes != bufs[y].bytes ? bufs[x].bytes > bufs[y].bytes : x < y; });
-        std::vector<size_t> placed;
-        size_t total = 0;
-        for (size_t bi : order) {
-            Buf& b = bufs[bi];
-            std::vector<std::pair<size_t, size_t>> busy;   // [offset, end) of placed buffers alive at the same time
-            for (size_t pj : placed) {
-                const Buf& o = bufs[pj];
-                if (o.first <= b.last && b.first <= o.last) busy.push_back(std::make_pair(o.offset, o.offset + o.bytes));
-            }
-            std::sort(busy.begin(), busy.end());
-            size_t off = 0;
-            for (auto& iv : busy) {
-                if (off + b.bytes <= iv.first) break;
-                if (iv.second > off) off = iv.second;
-            }
-            b.offset = off;
-            if (off + b.bytes > total) total = off + b.bytes;
-            placed.push_back(bi);
-        }
-        arena_bytes_ = total;
-        arena_plan_.clear();
-        for (Buf& b : bufs) arena_plan_.push_back(ArenaSlot{b.node, b.offset});
-        arena_plan_bytes_ = total;
-        arena_pending_ = true;
-        LOG(INFO) << "activation arena: " << total << " bytes for " << bufs.size() << " operands (" << unshared_bytes_ << " without sharing)";
-    }
+    if (!arena_nodes.empty()) PlanArena(arena_nodes);
     // An engine whose forwards may all be served by the sliced host pipeline (host outputs, slicing not switched off, not a lane)
     // leaves the arena to the first forward that runs its OWN plan: the slicer has an arena of its own, and this one would be a
     // second, never-touched allocation.  Everyone else allocates now, so LoadModel reports an arena that does not fit.

@@ -94,7 +94,10 @@ private:
         const pnnx::Operator* op = nullptr;
         std::vector<int> detect_levels;   // Detect levels whose input this step completes (option "detect_stream")
     };
+    // the planner (engine_plan.cpp)
+    struct Pass;   // what the fusion passes share: positions, the retired mask, the consumer rules
     Status PlanDetectStream();
+    void PlanArena(const std::vector<TensorNode*>& nodes);
 
     Status FuseEpilogues(std::vector<Step>& order);
     Status FuseSiblingConvs(std::vector<Step>& order);
