@@ -96,6 +96,12 @@ class SiPixelShuffleDesc(C.Structure):
     _fields_ = [(k, C.c_int) for k in ("n", "ih", "iw", "ic", "in_ld", "oh", "ow", "oc", "out_ld", "r", "inverse")]
 
 
+class SiSliceDesc(C.Structure):
+    """include/si_slice.h; start / step in NHWC order"""
+    _fields_ = [(k, C.c_int) for k in ("n", "ih", "iw", "ic", "in_ld")] + [("start", C.c_int * 4), ("step", C.c_int * 4)] + [
+        (k, C.c_int) for k in ("on", "oh", "ow", "oc", "out_ld")]
+
+
 class SiConv2dUpsampledSource(C.Structure):
     _fields_ = [("src", C.c_void_p), ("ih", C.c_int), ("iw", C.c_int), ("c", C.c_int), ("ld", C.c_int), ("c0", C.c_int),
                 ("inv_scale_h", C.c_float), ("inv_scale_w", C.c_float)]
@@ -294,8 +300,18 @@ def hip():
         "si_hip_prelu_f16": (i, [vp, sz, i, i, vp, i, vp, i, vp]),
         "si_hip_prelu_kernel_name": (C.c_char_p, [vp, sz, i, i, i, vp, i, i]),
     }
+    # include/si_slice.h: torch.chunk / torch.split / Tensor.slice
+    split_args = [vp, sz, i, i, i, ip, ip, C.POINTER(vp), ip]
+    slice_ = {
+        "si_hip_slice_f32": (i, [C.POINTER(SiSliceDesc), vp, vp, vp]),
+        "si_hip_slice_f16": (i, [C.POINTER(SiSliceDesc), vp, vp, vp]),
+        "si_hip_slice_kernel_name": (C.c_char_p, [C.POINTER(SiSliceDesc), vp, vp, i]),
+        "si_hip_split_channels_f32": (i, split_args + [vp]),
+        "si_hip_split_channels_f16": (i, split_args + [vp]),
+        "si_hip_split_channels_kernel_name": (C.c_char_p, split_args + [i]),
+    }
     for name, (res, args) in (list(sig.items()) + list(norm.items()) + list(pad.items()) + list(pool.items()) + list(softmax.items()) +
-                              list(superres.items())):
+                              list(superres.items()) + list(slice_.items())):
         fn = getattr(L, name)  # AttributeError here = header/library mismatch, which tests check
         fn.restype = res
         fn.argtypes = args
@@ -305,6 +321,7 @@ def hip():
     L._si_pool_signatures = pool
     L._si_softmax_signatures = softmax
     L._si_superres_signatures = superres
+    L._si_slice_signatures = slice_
     _hip = L
     return L
 

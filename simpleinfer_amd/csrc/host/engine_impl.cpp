@@ -20,6 +20,7 @@ Status EngineImpl::SetOption(const std::string& key, int value) {
     if (key == "device") opt_device_ = value;
     else if (key == "fuse") opt_fuse_ = value != 0;
     else if (key == "alias_cat") opt_alias_cat_ = value != 0;
+    else if (key == "alias_split") opt_alias_split_ = value != 0;   // chunk / split / slice outputs on the channel axis as views of the input (default 1)
     else if (key == "graph") opt_graph_ = value != 0;
     else if (key == "outputs_to_host") opt_outputs_to_host_ = value != 0;
     else if (key == "fp16") opt_fp16_ = value != 0;
@@ -424,7 +425,7 @@ Status EngineImpl::AllocateTensorMemory() {
     return Status::kSuccess;
 }
 
-// allocate the planned arena (once) and point the operands -- and the concat aliases, which hang off them -- into it
+// allocate the planned arena (once) and point the operands -- and the aliases (concat inputs, split outputs), which hang off them -- into it
 Status EngineImpl::EnsureArena() {
     if (arena_pending_) {
         void* arena = nullptr;
@@ -438,8 +439,9 @@ Status EngineImpl::EnsureArena() {
             Tensor& t = tensor_nodes_[kv.first]->tensor;
             Tensor& parent = kv.second.parent->tensor;
             if (parent.RawData() == nullptr) continue;
+            // (the parent is a root buffer -- ResolveAliases -- and the view takes ITS pixel stride)
             t.SetView(static_cast<char*>(parent.RawData()) + (size_t)kv.second.channel_offset * ElementSize(parent.GetDataType()),
-                      MemoryType::kDevice, parent.Shape().back());
+                      MemoryType::kDevice, parent.PixelStride());
         }
         aliases_bound_ = true;
     }
@@ -510,6 +512,7 @@ Status EngineImpl::LoadLanes(int lanes) {
         lane->opt_device_ = context_->device();
         lane->opt_fuse_ = opt_fuse_;
         lane->opt_alias_cat_ = opt_alias_cat_;
+        lane->opt_alias_split_ = opt_alias_split_;
         lane->opt_fuse_upsample_ = opt_fuse_upsample_;
         lane->opt_fuse_stem_ = opt_fuse_stem_;
         lane->opt_fuse_pw_ = opt_fuse_pw_;
@@ -650,6 +653,7 @@ Status EngineImpl::SetupSlicer(int slices) {
     slicer_->opt_device_ = context_->device();
     slicer_->opt_fuse_ = opt_fuse_;
     slicer_->opt_alias_cat_ = opt_alias_cat_;
+    slicer_->opt_alias_split_ = opt_alias_split_;
     slicer_->opt_fuse_upsample_ = opt_fuse_upsample_;
     slicer_->opt_fuse_stem_ = opt_fuse_stem_;
     slicer_->opt_fuse_pw_ = opt_fuse_pw_;

@@ -110,6 +110,8 @@ private:
     Status InsertOutputCasts(std::vector<Step>& order);
     Status InsertFp32Fallbacks(std::vector<Step>& order);
     Status AliasConcats();
+    Status AliasSplits();
+    void ResolveAliases();
     Status UploadInputs();
     Status BindOutputs();
     Status LaunchAll();
@@ -136,6 +138,7 @@ private:
     int opt_device_ = -1;
     bool opt_fuse_ = true;
     bool opt_alias_cat_ = true;
+    bool opt_alias_split_ = true;   // torch.chunk / torch.split / Tensor.slice outputs that are channel ranges become views of the input (0: always copied)
     bool opt_fuse_upsample_ = true;
     int opt_fuse_stem_ = 2;
     int opt_fuse_pw_ = 1;   // (2: ... and the C3's closing conv behind its last 64-channel pair -- built in round 6, bit-identical, 0.74-0.84x of the launches
@@ -207,7 +210,7 @@ private:
         TensorNode* parent = nullptr;
         int channel_offset = 0;
     };
-    std::map<std::string, Alias> aliases_;   // operand name -> slice of a concat buffer
+    std::map<std::string, Alias> aliases_;   // operand name -> channel slice of another operand's buffer (a concat output, a split's input)
 
     std::vector<void*> device_allocs_;
     size_t arena_bytes_ = 0, unshared_bytes_ = 0;   // footprint with / without lifetime sharing (statistics)

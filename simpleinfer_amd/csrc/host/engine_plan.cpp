@@ -14,6 +14,7 @@
 #include "layer/linear.h"
 #include "layer/max_pool_2d.h"
 #include "layer/output_cast.h"
+#include "layer/slice.h"
 #include "layer/upsample.h"
 #include "layer/yolo_detect.h"
 
@@ -29,7 +30,7 @@ bool HonoursPixelStride(const std::string& type) {
         "nn.GroupNorm", "nn.InstanceNorm2d", "nn.ReflectionPad2d", "nn.ReplicationPad2d", "nn.ZeroPad2d", "nn.ConstantPad2d", "nn.CircularPad2d",
         "F.pad", "nn.Tanh", "nn.AvgPool2d", "F.avg_pool2d", "F.adaptive_avg_pool2d", "nn.Softmax", "nn.LogSoftmax", "nn.Softmax2d",
         "F.softmax", "F.log_softmax", "nn.PixelShuffle", "nn.PixelUnshuffle", "F.pixel_shuffle", "F.pixel_unshuffle", "nn.PReLU", "torch.flatten",
-        "models.yolo.Detect", "pnnx.Output"};
+        "torch.chunk", "torch.split", "Tensor.slice", "models.yolo.Detect", "pnnx.Output"};
     return ok.count(type) > 0;
 }
 
@@ -87,7 +88,9 @@ Status EngineImpl::CreatePipeline() {
         CHECK_STATUS(InsertFp32Fallbacks(order));
     }
     plan_ = order;
+    if (opt_alias_split_) CHECK_STATUS(AliasSplits());   // (first: a chunk that is a view stays one when its halves also feed a concat)
     if (opt_alias_cat_) CHECK_STATUS(AliasConcats());
+    ResolveAliases();
     if (opt_detect_stream_) CHECK_STATUS(PlanDetectStream());
     return Status::kSuccess;
 }
@@ -650,6 +653,55 @@ Status EngineImpl::AliasConcats() {
     return Status::kSuccess;
 }
 
+// torch.chunk / torch.split / Tensor.slice on the channel axis with step 1: every eligible output becomes a view of the input at its channel
+// offset (same pixel grid, the input's pixel stride), so the operator launches nothing for it and Slice::Forward skips it.  The input keeps its
+// buffer, which PlanArena keeps alive until the last reader of any view.  Only these three types: no existing plan changes.
+Status EngineImpl::AliasSplits() {
+    for (const Step& s : plan_) {
+        Slice* sl = dynamic_cast<Slice*>(s.layer);
+        if (!sl || s.op->inputs.size() != 1 || sl->InputNodes().size() != 1) continue;
+        const pnnx::Operand* x = s.op->inputs[0];
+        TensorNode* in = sl->InputNodes()[0];
+        // (an fp32 fallback rebinds the layer to shadow tensors: those are not the file's operands and nothing aliases them)
+        if (!x || tensor_nodes_[x->name] != in || input_tensor_nodes_.count(x->name) || output_tensor_nodes_.count(x->name)) continue;
+        const std::vector<int>& xs = in->tensor.Shape();
+        const std::vector<Slice::Piece>& pieces = sl->Pieces();
+        if (xs.size() != 4 || pieces.size() != s.op->outputs.size() || sl->OutputNodes().size() != pieces.size()) continue;
+        const int in_dims[4] = {xs[0], xs[1], xs[2], xs[3]};
+        for (size_t i = 0; i < pieces.size(); ++i) {
+            const pnnx::Operand* r = s.op->outputs[i];
+            TensorNode* out = sl->OutputNodes()[i];
+            bool ok = r && tensor_nodes_[r->name] == out && !aliases_.count(r->name) && !output_tensor_nodes_.count(r->name) &&
+                      !dead_operands_.count(r->name) && Slice::ChannelRange(pieces[i], in_dims) && out->tensor.Shape().size() == 4 &&
+                      out->tensor.GetDataType() == in->tensor.GetDataType() &&
+                      ((size_t)pieces[i].start[3] * ElementSize(in->tensor.GetDataType()) % 16 == 0);
+            if (ok)
+                for (const pnnx::Operator* c : r->consumers) ok = ok && c && HonoursPixelStride(c->type);
+            if (!ok) continue;
+            Alias a;
+            a.parent = in;
+            a.channel_offset = pieces[i].start[3];
+            aliases_[r->name] = a;
+        }
+    }
+    return Status::kSuccess;
+}
+
+// After the alias passes a parent may itself be an alias (a conv output that feeds a chunk and a concat: the chunk's views hang off an operand
+// that lives in the concat buffer; a chunk of a chunk).  Every alias is re-pointed at its ROOT buffer with the summed channel offset, so that
+// EnsureArena binds views to allocated memory only and PlanArena's lifetimes count every reader against the buffer that is really read.
+void EngineImpl::ResolveAliases() {
+    for (auto& kv : aliases_) {
+        Alias& a = kv.second;
+        for (size_t hops = 0; hops <= aliases_.size() && a.parent && a.parent->operand; ++hops) {
+            auto up = aliases_.find(a.parent->operand->name);
+            if (up == aliases_.end() || tensor_nodes_[up->first] != a.parent || &up->second == &a) break;
+            a.channel_offset += up->second.channel_offset;
+            a.parent = up->second.parent;
+        }
+    }
+}
+
 // ---- memory plan ---------------------------------------------------------------------------------
 // The intermediates (`nodes`: every live operand that is neither an alias nor a graph input / output) are packed into ONE arena: two buffers
 // may overlap in memory iff no launch of the plan needs both -- a buffer lives from the first step that writes it (or any alias into it) to
@@ -663,7 +715,7 @@ void EngineImpl::PlanArena(const std::vector<TensorNode*>& nodes) {
     }
     auto touch = [&](TensorNode* n, int step) {
         auto al = n && n->operand ? aliases_.find(n->operand->name) : aliases_.end();
-        auto it = buf_of.find(al != aliases_.end() ? al->second.parent : n);   // (an alias lives in its concat buffer)
+        auto it = buf_of.find(al != aliases_.end() ? al->second.parent : n);   // (an alias lives in its root buffer: a concat output, a split input)
         if (it == buf_of.end()) return;
         ArenaBuffer& b = bufs[it->second];
         if (b.first < 0) b.first = step;

@@ -2,6 +2,7 @@
 
 #include "layer_util.h"
 #include "si_hip.h"
+#include "si_slice.h"
 
 namespace SimpleInfer {
 
@@ -54,7 +55,7 @@ Status Cat::Forward(const std::vector<Tensor>& inputs, Tensor& output) {
         int offset = 0;
         int copies = 0;
         const bool half = IsHalf(out[0]);
-        // fp16 tensors are copied as 4-byte words (pure data movement): channel counts / strides / offsets must be even
+        // fp16 tensors are copied as 4-byte words (pure data movement) where channel counts / strides / offsets are even
         const int wd = half ? 2 : 1;
         for (const Tensor& t : in) {
             Dims4 id;
@@ -66,7 +67,16 @@ Status Cat::Forward(const std::vector<Tensor>& inputs, Tensor& output) {
                 // already in place: the engine pointed this input at its slice of our output
                 if (t.RawData() != dst || t.PixelStride() != out[0].PixelStride()) {
                     ++copies;
-                    if (id.c % wd || t.PixelStride() % wd || out[0].PixelStride() % wd || offset % wd) return Status::kUnsupport;
+                    if (id.c % wd || t.PixelStride() % wd || out[0].PixelStride() % wd || offset % wd) {
+                        // an odd count of halves (the 3-channel Focus slices of an RGB image): 2-byte elements through the split kernel
+                        const int first = 0, width = id.c, ld = out[0].PixelStride();
+                        void* to = dst;
+                        CHECK_STATUS(CheckHip(si_hip_split_channels_f16(t.RawData(), id.pixels(), id.c, t.PixelStride(), 1, &first, &width, &to, &ld,
+                                                                        Stream()),
+                                              "Cat"));
+                        offset += is[axis];
+                        continue;
+                    }
                     CHECK_STATUS(CheckHip(si_hip_copy_channels_f32(static_cast<const float*>(t.RawData()), id.pixels(), id.c / wd,
                                                                    t.PixelStride() / wd, reinterpret_cast<float*>(dst),
                                                                    out[0].PixelStride() / wd, Stream()),

@@ -540,6 +540,8 @@ Status Conv2d::HalfInput(const Tensor& input, Tensor& half) {
     size_t pixels = 0;
     int c = 0;
     if (!GetPixelsChannels(input, pixels, c)) return Status::kErrorShape;
+    // (a default-constructed Tensor is a HOST tensor: Allocate() would malloc, and the kernels below would be handed pageable host memory)
+    if (in_half_.GetMemoryType() != MemoryType::kDevice) in_half_ = Tensor(DataType::kFloat16, input.Shape(), MemoryType::kDevice, false);
     CHECK_STATUS(in_half_.Allocate(DataType::kFloat16, input.Shape()));
     CHECK_STATUS(CheckHip(si_hip_convert_f32_f16(input.Data<float>(), pixels, c, input.PixelStride(), in_half_.RawData(), c, Stream()),
                           "conv2d input fp32 -> fp16"));

@@ -29,6 +29,7 @@ SI_DECLARE_LAYER(PReLU)
 SI_DECLARE_LAYER(ReLU)
 SI_DECLARE_LAYER(Sigmoid)
 SI_DECLARE_LAYER(SiLU)
+SI_DECLARE_LAYER(Slice)
 SI_DECLARE_LAYER(Softmax)
 SI_DECLARE_LAYER(Tanh)
 SI_DECLARE_LAYER(UnaryOp)
@@ -45,7 +46,8 @@ static std::map<std::string, LayerRegistryEntry>& Table() {
     // instance norm is the group norm with one group per channel); the explicit pads (one class, layer/pad_2d.h) and nn.Tanh
     // (UnaryOp code 16 as a module); nn.AvgPool2d / F.avg_pool2d (layer/avg_pool_2d.h) and the functional spelling of the adaptive pool;
     // nn.Softmax / nn.LogSoftmax / nn.Softmax2d / F.softmax / F.log_softmax (one class, layer/softmax.h); nn.PixelShuffle / nn.PixelUnshuffle /
-    // F.pixel_shuffle / F.pixel_unshuffle (one class, layer/pixel_shuffle.h) and nn.PReLU (layer/prelu.h)
+    // F.pixel_shuffle / F.pixel_unshuffle (one class, layer/pixel_shuffle.h) and nn.PReLU (layer/prelu.h); torch.chunk / torch.split /
+    // Tensor.slice (one class, layer/slice.h)
     static std::map<std::string, LayerRegistryEntry> table = {
         SI_ENTRY("nn.AdaptiveAvgPool2d", AdaptiveAvgPool2d),
         SI_ENTRY("nn.AvgPool2d", AvgPool2d),
@@ -88,6 +90,9 @@ static std::map<std::string, LayerRegistryEntry>& Table() {
         SI_ENTRY("F.log_softmax", Softmax),
         SI_ENTRY("F.pixel_shuffle", PixelShuffle),
         SI_ENTRY("F.pixel_unshuffle", PixelShuffle),
+        SI_ENTRY("torch.chunk", Slice),
+        SI_ENTRY("torch.split", Slice),
+        SI_ENTRY("Tensor.slice", Slice),
         SI_ENTRY("models.yolo.Detect", YoloDetect),
     };
     return table;

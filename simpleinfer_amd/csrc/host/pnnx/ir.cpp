@@ -7,6 +7,7 @@
 #include "ir.h"
 
 #include <algorithm>
+#include <climits>
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -43,6 +44,14 @@ bool starts_number(const std::string& t) {
     return t[0] == '-' && t.size() > 1 && t[1] >= '0' && t[1] <= '9';
 }
 bool looks_float(const std::string& t) { return t.find('.') != std::string::npos || t.find('e') != std::string::npos; }
+
+// std::stoi that saturates instead of throwing std::out_of_range: pnnx writes an open slice end as INT_MAX or INT64_MAX, and a Parameter holds an int
+int to_int_saturated(const std::string& t) {
+    const long long v = std::strtoll(t.c_str(), nullptr, 10);   // (saturates at LLONG_MIN / LLONG_MAX by itself)
+    if (v > (long long)INT_MAX) return INT_MAX;
+    if (v < (long long)INT_MIN) return INT_MIN;
+    return (int)v;
+}
 
 std::vector<std::string> split(const std::string& s, char sep) {
     std::vector<std::string> out;
@@ -87,7 +96,7 @@ Parameter Parameter::parse_from_string(const std::string& value) {
                 p.af.push_back(std::stof(e));
             } else {
                 p.type = 5;
-                p.ai.push_back(std::stoi(e));
+                p.ai.push_back(to_int_saturated(e));
             }
         }
         return p;
@@ -100,7 +109,7 @@ Parameter Parameter::parse_from_string(const std::string& value) {
         p.f = std::stof(value);
     } else {
         p.type = 2;
-        p.i = std::stoi(value);
+        p.i = to_int_saturated(value);
     }
     return p;
 }

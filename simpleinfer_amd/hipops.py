@@ -1109,6 +1109,87 @@ def prelu_kernel_name(x_shape, slope_count=1, half=False, in_ld=None, out_ld=Non
                                                   1 if half else 0).decode()
 
 
+_ALL = slice(None)   # (the builtin: this module's own slice() is defined below)
+
+
+def slice_desc(x_shape, index, in_ld=None, out_ld=None):
+    """SiSliceDesc (include/si_slice.h) of an NHWC input (or [N, F]: taken as [N, 1, 1, F]) and `index`, one Python slice per axis in the
+    array's own order with steps >= 1 -- the descriptor of x[index]"""
+    shape = tuple(int(v) for v in x_shape)
+    index = tuple(index) + (_ALL,) * (len(shape) - len(index))
+    if len(shape) == 2:
+        shape, index = (shape[0], 1, 1, shape[1]), (index[0], _ALL, _ALL, index[1])
+    rng = [range(*s.indices(n)) for s, n in zip(index, shape)]
+    assert all(r.step >= 1 for r in rng), "steps are at least 1"
+    d = _native.SiSliceDesc()
+    d.n, d.ih, d.iw, d.ic = shape
+    d.on, d.oh, d.ow, d.oc = (len(r) for r in rng)
+    for a, r in enumerate(rng):
+        d.start[a], d.step[a] = r.start, r.step
+    d.in_ld, d.out_ld = in_ld or d.ic, out_ld or d.oc
+    return d
+
+
+def slice(x, index, in_ld=None, in_c_off=0, in_fill=0.0, out_ld=None, out_c_off=0, out_fill=0.0, full=False):
+    """si_hip_slice_f32 / _f16 (by the array's dtype): x[index] of an NHWC (or [N, F]) array, index as in slice_desc.  The array's bits
+    travel as they are.  The view hooks are the common ones."""
+    H = _native.hip()
+    x = _float_storage(x)
+    half = x.dtype == np.float16
+    d = slice_desc(x.shape, index, in_ld, out_ld)
+    if min(d.on, d.oh, d.ow, d.oc) < 1:
+        raise HipError("si_hip_slice: %r of a %r input is empty" % (index, tuple(x.shape)))
+    oshape = (d.on, d.oh, d.ow) if x.ndim == 4 else (d.on,)
+    (dx, px), (dy, py) = _view_in(x, in_ld, in_c_off, in_fill), _view_out(oshape, d.oc, out_ld, out_c_off, out_fill, x.dtype)
+    LAST_KERNEL_NAME["si_hip_slice"] = H.si_hip_slice_kernel_name(C.byref(d), C.c_void_p(px), C.c_void_p(py), 1 if half else 0).decode()
+    fn, name = (H.si_hip_slice_f16, "si_hip_slice_f16") if half else (H.si_hip_slice_f32, "si_hip_slice_f32")
+    _chk(fn(C.byref(d), px, py, None), name)
+    return _ret(dy.to_numpy(oshape + (out_ld or d.oc,), x.dtype), d.oc, out_c_off, full)
+
+
+def slice_kernel_name(x_shape, index, half=False, in_ld=None, out_ld=None) -> str:
+    """the form for 16-byte aligned buffers of these shapes ("none": a descriptor the launch refuses)"""
+    d = slice_desc(x_shape, index, in_ld, out_ld)
+    return _native.hip().si_hip_slice_kernel_name(C.byref(d), C.c_void_p(256), C.c_void_p(256), 1 if half else 0).decode()
+
+
+def _split_args(widths, offsets, out_lds, ptrs):
+    k = len(widths)
+    if offsets is None:
+        offsets = [int(sum(widths[:i])) for i in range(k)]
+    ia = lambda v: (C.c_int * k)(*[int(t) for t in v])
+    return k, ia(offsets), ia(widths), (C.c_void_p * k)(*ptrs), ia(out_lds)
+
+
+def split_channels(x, widths, offsets=None, in_ld=None, in_c_off=0, in_fill=0.0, out_lds=None, out_c_offs=None, out_fill=0.0, full=False):
+    """si_hip_split_channels_f32 / _f16 (by the array's dtype): one call that copies channels [offsets[i], offsets[i] + widths[i]) of an array
+    whose last axis is the channels into destination i (offsets default to the widths laid end to end: torch.split).  Returns the list of
+    destinations.  out_lds / out_c_offs: one pixel stride / channel offset per destination; the other view hooks are the common ones."""
+    H = _native.hip()
+    x = _float_storage(x)
+    half = x.dtype == np.float16
+    c, k = x.shape[-1], len(widths)
+    out_lds = [int(v) if v else int(w) for v, w in zip(out_lds or [None] * k, widths)]
+    out_c_offs = list(out_c_offs or [0] * k)
+    dx, px = _view_in(x, in_ld, in_c_off, in_fill)
+    outs = [_view_out(x.shape[:-1], int(w), ld, co, out_fill, x.dtype) for w, ld, co in zip(widths, out_lds, out_c_offs)]
+    args = (px, x.size // c, c, in_ld or c) + _split_args(widths, offsets, out_lds, [py for _, py in outs])
+    LAST_KERNEL_NAME["si_hip_split_channels"] = H.si_hip_split_channels_kernel_name(*(args + (1 if half else 0,))).decode()
+    fn, name = (H.si_hip_split_channels_f16, "si_hip_split_channels_f16") if half else (H.si_hip_split_channels_f32, "si_hip_split_channels_f32")
+    _chk(fn(*(args + (None,))), name)
+    return [_ret(dy.to_numpy(x.shape[:-1] + (ld,), x.dtype), int(w), co, full) for (dy, _), w, ld, co in zip(outs, widths, out_lds, out_c_offs)]
+
+
+def split_channels_kernel_name(x_shape, widths, offsets=None, half=False, in_ld=None, out_lds=None) -> str:
+    """the form for 16-byte aligned buffers of these shapes ("none": arguments the launch refuses)"""
+    c = int(x_shape[-1])
+    pixels = int(np.prod(x_shape[:-1], dtype=np.int64))
+    k = len(widths)
+    out_lds = [int(v) if v else int(w) for v, w in zip(out_lds or [None] * k, widths)]
+    args = (C.c_void_p(256), pixels, c, in_ld or c) + _split_args(widths, offsets, out_lds, [256] * k)
+    return _native.hip().si_hip_split_channels_kernel_name(*(args + (1 if half else 0,))).decode()
+
+
 def flatten_nhwc(x, in_ld=None, in_c_off=0, in_fill=0.0, out_fill=None):
     """out_fill: as cat()"""
     H = _native.hip()

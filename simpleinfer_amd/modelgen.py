@@ -371,6 +371,50 @@ class PnnxBuilder:
         self._emit("torch.cat", self._opname("cat"), list(xs), [out], dict(dim=dim))
         return out
 
+    def _pieces(self, typ: str, prefix: str, x: str, dim: int, lens: Sequence[int], params) -> List[str]:
+        shp = list(self.shapes[x])
+        outs = []
+        for n in lens:
+            shp[dim] = int(n)
+            outs.append(self._new_operand(shp))
+        self._emit(typ, self._opname(prefix), [x], outs, params)
+        return outs
+
+    def chunk(self, x: str, chunks: int, dim: int = 1) -> List[str]:
+        """pnnx's torch.chunk line (chunks=, dim=), one output operand per chunk: pieces of ceil(size / chunks), the last one may be smaller"""
+        size = self.shapes[x][dim]
+        each = -(-size // int(chunks))
+        lens = [min(each, size - at) for at in range(0, size, each)]
+        return self._pieces("torch.chunk", "torch_chunk", x, dim % len(self.shapes[x]), lens, dict(chunks=int(chunks), dim=int(dim)))
+
+    def split(self, x: str, split_size_or_sections, dim: int = 1) -> List[str]:
+        """pnnx's torch.split line (split_size_or_sections= an int or a list, dim=), one output operand per piece"""
+        size = self.shapes[x][dim]
+        if isinstance(split_size_or_sections, int):
+            each = int(split_size_or_sections)
+            lens, arg = [min(each, size - at) for at in range(0, size, each)], each
+        else:
+            lens = arg = tuple(int(v) for v in split_size_or_sections)
+            assert sum(lens) == size, (lens, size)
+        return self._pieces("torch.split", "torch_split", x, dim % len(self.shapes[x]), lens, dict(dim=int(dim), split_size_or_sections=arg))
+
+    def slice(self, x: str, dim, start=0, end=None, step=1) -> str:
+        """pnnx's Tensor.slice line.  An int `dim` writes the one-axis spelling dim= start= end= step=; a tuple writes dims= starts= ends=
+        steps= with several axes in one operator (start / end / step are then tuples too).  end=None is written as 2147483647, as pnnx
+        writes an open end; the string "None" is written as it is."""
+        shp = list(self.shapes[x])
+        many = not isinstance(dim, int)
+        dims = tuple(dim) if many else (dim,)
+        starts, ends, steps = (tuple(v) if many else (v,) for v in (start, end, step))
+        ends = tuple(2147483647 if e is None else e for e in ends)
+        for d, s0, e, st in zip(dims, starts, ends, steps):
+            shp[d] = len(range(*slice(s0, None if e == "None" else e, st).indices(shp[d])))
+            assert shp[d] > 0 and st >= 1, (d, s0, e, st)
+        out = self._new_operand(shp)
+        params = dict(dims=dims, ends=ends, starts=starts, steps=steps) if many else dict(dim=dims[0], end=ends[0], start=starts[0], step=steps[0])
+        self._emit("Tensor.slice", self._opname("Tensor_slice"), [x], [out], params)
+        return out
+
     def expression(self, expr: str, xs: Sequence[str], out_shape=None) -> str:
         out = self._new_operand(out_shape or self.shapes[xs[0]])
         self._emit("pnnx.Expression", self._opname("pnnx_expr"), list(xs), [out], dict(expr=expr))
@@ -695,6 +739,58 @@ def build_toy_esrgan_head(batch: int = 2, size: int = 16, width: int = 16, seed:
     x = b.leaky_relu(b.conv(b.pixel_unshuffle(x, 2), width, 3, 1, 1), 0.2)
     x = b.conv(b.upsample(x, 2.0), 3, 3, 1, 1)
     b.output(x)
+    return b
+
+
+def build_toy_c2f(batch: int = 2, size: int = 16, c1: int = 16, c2: int = 32, n: int = 2, shortcut: bool = True, seed: int = 0) -> PnnxBuilder:
+    """YOLOv8's C2f block: cv1 (1x1 to 2 c) -> chunk(2, 1) -> n bottlenecks (3x3 -> 3x3, + shortcut), each fed by the tensor before it ->
+    cat of both halves and every bottleneck output -> cv2 (1x1); c = c2 / 2, every conv with SiLU"""
+    b = PnnxBuilder(seed)
+    x = b.input((batch, c1, size, size))
+    c = c2 // 2
+    y = b.chunk(_Conv(b, x, 2 * c, 1), 2, 1)
+    for _ in range(n):
+        t = _Conv(b, _Conv(b, y[-1], c, 3), c, 3)
+        y.append(b.add(y[-1], t) if shortcut else t)
+    b.output(_Conv(b, b.cat(y, 1), c2, 1))
+    return b
+
+
+def build_toy_focus(batch: int = 2, size: int = 16, c2: int = 16, seed: int = 0) -> PnnxBuilder:
+    """The Focus stem of YOLOv5 v1 - v5: cat of x[..., ::2, ::2], x[..., 1::2, ::2], x[..., ::2, 1::2], x[..., 1::2, 1::2] (3 -> 12 channels at
+    half the size) -> conv3x3 with SiLU"""
+    b = PnnxBuilder(seed)
+    x = b.input((batch, 3, size, size))
+    parts = [b.slice(x, (2, 3), (i, j), (None, None), (2, 2)) for i, j in ((0, 0), (1, 0), (0, 1), (1, 1))]
+    b.output(_Conv(b, b.cat(parts, 1), c2, 3))
+    return b
+
+
+def build_toy_res2net_block(batch: int = 2, size: int = 12, width: int = 8, scale: int = 4, seed: int = 0) -> PnnxBuilder:
+    """A Res2Net bottleneck at toy width: conv3x3 stem -> conv1x1 to width * scale -> torch.split(width, 1) -> the hierarchical 3x3 convs
+    (piece i plus the output before it; the last piece passes through) -> cat -> conv1x1, + the block's input, ReLU"""
+    b = PnnxBuilder(seed)
+    x = b.input((batch, 3, size, size))
+    x = b.relu(b.conv(x, width * scale, 3, 1, 1))
+    xs = b.split(b.relu(b.conv(x, width * scale, 1)), width, 1)
+    outs, sp = [], None
+    for i in range(scale - 1):
+        sp = b.relu(b.conv(xs[i] if i == 0 else b.add(sp, xs[i]), width, 3, 1, 1))
+        outs.append(sp)
+    outs.append(xs[-1])
+    y = b.conv(b.cat(outs, 1), width * scale, 1)
+    b.output(b.relu(b.add(y, x)))
+    return b
+
+
+def build_toy_ghost(batch: int = 2, size: int = 16, oup: int = 27, seed: int = 0) -> PnnxBuilder:
+    """GhostNet's Ghost module: primary conv1x1 to ceil(oup / 2) channels -> cheap depthwise conv3x3 over them -> cat -> out[:, :oup]"""
+    b = PnnxBuilder(seed)
+    x = b.input((batch, 16, size, size))
+    init = -(-oup // 2)
+    x1 = b.relu(b.conv(x, init, 1))
+    x2 = b.relu(b.conv(x1, init, 3, 1, 1, groups=init))
+    b.output(b.slice(b.cat([x1, x2], 1), 1, 0, oup, 1))
     return b
 
 
