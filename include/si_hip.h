@@ -463,8 +463,22 @@ int si_hip_resize_letterbox_batch_u8_f32(const unsigned char* frames_bgr, int n,
  * pred [n][rows][ne] fp32 on the device (the Detect output).  adjust: NULL or device [n][5] floats
  * {padding_l, padding_t, scale, image cols, image rows}.  dets: device [n][max_det][6] floats
  * {x, y, width, height, confidence, label}, in picked order.  counts: device [n] ints = number of boxes picked (the
- * reference has no cap: when counts[b] > max_det only the first max_det were stored).  workspace: device scratch of
- * si_hip_yolo_postprocess_workspace_bytes(n, rows, ne) bytes. */
+ * reference has no cap: when counts[b] > max_det only the first max_det were stored; rows of dets behind them are not
+ * written).  workspace: device scratch of si_hip_yolo_postprocess_workspace_bytes(n, rows, ne) bytes; what it holds on entry
+ * does not matter.  Every fp32 result equals, bit for bit, the rule of tests/post_reference.py, which restates the reference
+ * (the box intersection as the oracle assumes it: simpleocv's `a & b` is not in the reference checkout).  Four rules:
+ *   1. Ties.  Confidences that compare equal keep their element (row) order.  One exception: the sort key is the BITS of the
+ *      confidence, so a +0 confidence goes ahead of a -0 one whatever their rows; both can only survive a prob_threshold <= 0.
+ *   2. Equalities.  A confidence EQUAL to prob_threshold is kept (>=); an IoU EQUAL to nms_threshold does not suppress (strict >,
+ *      on the correctly rounded fp32 quotient).  A NaN confidence is dropped; a NaN IoU (0 / 0 of two zero-area boxes, a NaN or
+ *      infinite coordinate) suppresses nothing: the intersection's min / max are the selects `a > b ? a : b` / `a < b ? a : b`
+ *      (candidate first), not fmaxf / fminf.  The clip is the reference's std::max(lo, std::min(v, hi)), first argument on a false
+ *      compare: a NaN coordinate clips to 0 and -0.0 to +0.0.
+ *   3. Label -1.  A row with no class maximum (every class score -inf, NaN or -FLT_MAX) has label -1 and class score -FLT_MAX;
+ *      it is kept when its box score makes the product reach the threshold, competes with other label -1 rows, and its dets
+ *      label is -1.0f.
+ *   4. Limits.  ne >= 6 (SI_E_BADARG below); ne <= 128 (128 rows of ne floats are staged in 64 KB of LDS) and n <= 65535 (a
+ *      grid's y extent): SI_E_UNSUPPORTED, before any device call. */
 size_t si_hip_yolo_postprocess_workspace_bytes(int n, int rows, int ne);
 int si_hip_yolo_postprocess_f32(const float* pred, int n, int rows, int ne, float prob_threshold, float nms_threshold,
                                 int agnostic, const float* adjust, float* dets, int* counts, int max_det,

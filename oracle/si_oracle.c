@@ -838,7 +838,11 @@ static void orc_qsort_descent(OrcObject* o, int left, int right) {
     if (i < right) orc_qsort_descent(o, i, right);
 }
 
-/* cv::Rect_<float> a & b, then area() (simpleocv) */
+/* cv::Rect_<float> a & b, then area() (simpleocv).  The submodule is absent from the reference checkout, so the select form below
+ * (`a > b ? a : b`, the SECOND operand on an unordered compare) is this restatement's ASSUMPTION, not a reading of the source.  Should
+ * simpleocv use std::max / std::min (the FIRST operand on an unordered compare), a NaN edge would propagate from the candidate instead
+ * of from the picked box; by the arithmetic of the filter (a NaN edge also makes the area NaN unless the width is infinite) that
+ * changes a pick only for infinite-width boxes under a negative nms_threshold (the post-processing matrix). */
 static float orc_intersection_area(const OrcObject* a, const OrcObject* b) {
     const float x1 = a->x > b->x ? a->x : b->x;
     const float y1 = a->y > b->y ? a->y : b->y;
@@ -850,9 +854,11 @@ static float orc_intersection_area(const OrcObject* a, const OrcObject* b) {
     return w * h;
 }
 
+/* test_yolo.cpp:188-191: (std::max)(lower, (std::min)(n, upper)).  std::min(a, b) is `b < a ? b : a` and std::max(a, b) is
+ * `a < b ? b : a`: both return their FIRST argument when the compare is false, so clip(-0.0, 0, hi) is +0.0 and clip(NaN, 0, hi) is 0 */
 static float orc_clipf(float v, float lo, float hi) {
-    const float m = v < hi ? v : hi;
-    return lo > m ? lo : m;
+    const float m = hi < v ? hi : v;
+    return lo < m ? m : lo;
 }
 
 int orc_yolo_postprocess(const float* pred, int rows, int ne, float prob_threshold, float nms_threshold, int agnostic,

@@ -292,16 +292,27 @@ __global__ __launch_bounds__(SORT_T) void yolo_rank_sort_kernel(int rows, PostWs
 
 // ---- 3. greedy NMS + un-letterbox (test_yolo.cpp:68-104, 379-416) -------------------------------
 // intersection of two rects as simpleocv's `a & b` gives it (3rdparty/simpleocv, from ncnn; an absent submodule):
-// empty (area 0) when width <= 0 or height <= 0.
+// empty (area 0) when width <= 0 or height <= 0.  a = the candidate, b = the picked box.  The selects are `a > b ? a : b` / `a < b ? a : b`, the form
+// the test suite's C restatement of the reference assumes (with simpleocv absent it cannot be read off the source; this kernel is held to it) and
+// NOT fmaxf / fminf: those return the other operand when one is NaN, so a picked box whose far edge x + w is NaN (x = -inf, w = +inf: its
+// area is +inf, not NaN) gave a finite intersection and an IoU of 0, which suppresses under a negative nms_threshold; the select hands the
+// NaN on and the oracle suppresses nothing (tests/post_reference.py geometry_negthr).
 __device__ __forceinline__ float inter_area(const float4 a, const float4 b) {
-    const float x1 = fmaxf(a.x, b.x), y1 = fmaxf(a.y, b.y);
-    const float w = fminf(a.x + a.z, b.x + b.z) - x1;
-    const float h = fminf(a.y + a.w, b.y + b.w) - y1;
+    const float x1 = a.x > b.x ? a.x : b.x, y1 = a.y > b.y ? a.y : b.y;
+    const float ax2 = a.x + a.z, bx2 = b.x + b.z, ay2 = a.y + a.w, by2 = b.y + b.w;
+    const float w = (ax2 < bx2 ? ax2 : bx2) - x1;
+    const float h = (ay2 < by2 ? ay2 : by2) - y1;
     if (w <= 0.0f || h <= 0.0f) return 0.0f;
     return w * h;
 }
 
-__device__ __forceinline__ float clipf(float v, float lo, float hi) { return fmaxf(lo, fminf(v, hi)); }
+// the reference's clip, (std::max)(lower, (std::min)(n, upper)) (test_yolo.cpp:188-191), spelled out: std::min(a, b) is `b < a ? b : a`,
+// std::max(a, b) is `a < b ? b : a`, each its FIRST argument when the compare is false.  So a NaN coordinate clips to lo (fmaxf / fminf
+// sent it to hi) and -0.0 to +0.0 (geometry with adjust holds both).
+__device__ __forceinline__ float clipf(float v, float lo, float hi) {
+    const float m = hi < v ? hi : v;
+    return lo < m ? m : lo;
+}
 
 // One workgroup (4 waves) per image walks the sorted candidates 64 at a time.  Phase 1: every wave tests the 64
 // candidates against its quarter of the boxes picked so far.  Phase 2 (wave 0): the in-chunk dependency chain is
@@ -601,7 +612,8 @@ int si_hip_yolo_postprocess_f32(const float* pred, int n, int rows, int ne, floa
         return 0;
     }
     if (!pred || !workspace) return SI_E_BADARG;
-    if ((size_t)RPB * ne * sizeof(float) > 64 * 1024) return SI_E_UNSUPPORTED;
+    // n is a grid's y extent (65535 at most), RPB rows of ne floats are the filter's LDS stage (64 KB at most: ne <= 128)
+    if (n > 65535 || (size_t)RPB * ne * sizeof(float) > 64 * 1024) return SI_E_UNSUPPORTED;
     PostWs ws;
     const size_t need = post_ws_layout(n, rows, ne - 5 + 1, (char*)workspace, &ws);
     if (workspace_bytes < need) return SI_E_BADARG;

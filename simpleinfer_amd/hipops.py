@@ -1293,47 +1293,76 @@ def letterbox(resized_bgr, height_new, width_new, padding_t, padding_l):
     return dout.to_numpy((height_new, width_new, 3))
 
 
-def letterbox_batch(resized_bgr, height_new, width_new, padding_t, padding_l):
-    """si_hip_letterbox_batch_u8_f32: u8 BGR [n][hr][wr][3] -> float RGB [n][height_new][width_new][3] in one launch."""
+def _strided_images(src, stride, fill):
+    """u8 images [n][...] -> host bytes [n][stride], image b at b * stride, the gap behind each image filled with the byte `fill`"""
+    n = int(src.shape[0])
+    per = int(src.size // n) if n else 0
+    if stride is None:
+        return src, per          # dense: uploaded as it is
+    stride = int(stride)
+    assert stride >= per, "an image stride shorter than the image"
+    host = np.full((n, stride), fill, np.uint8)
+    host[:, :per] = src.reshape(n, per)
+    return host, stride
+
+
+def letterbox_batch(resized_bgr, height_new, width_new, padding_t, padding_l, src_stride=None, src_fill=0):
+    """si_hip_letterbox_batch_u8_f32: u8 BGR [n][hr][wr][3] -> float RGB [n][height_new][width_new][3] in one launch.  src_stride: image
+    stride of the source in bytes (default: dense), the gaps filled with the byte src_fill."""
     H = _native.hip()
     src = np.ascontiguousarray(resized_bgr, dtype=np.uint8)
     n, hr, wr = int(src.shape[0]), int(src.shape[1]), int(src.shape[2])
-    dsrc = DeviceBuffer.from_numpy(src)
+    host, stride = _strided_images(src, src_stride, src_fill)
+    dsrc = DeviceBuffer.from_numpy(host)
     dout = DeviceBuffer(max(n * height_new * width_new * 3 * 4, 16))
-    _chk(H.si_hip_letterbox_batch_u8_f32(dsrc.ptr, n, hr * wr * 3, hr, wr, dout.ptr, height_new, width_new, padding_t, padding_l, None),
+    _chk(H.si_hip_letterbox_batch_u8_f32(dsrc.ptr, n, stride, hr, wr, dout.ptr, height_new, width_new, padding_t, padding_l, None),
          "si_hip_letterbox_batch_u8_f32")
     return dout.to_numpy((n, height_new, width_new, 3))
 
 
-def resize_bilinear_u8c3(images, dst_h, dst_w):
-    """si_hip_resize_bilinear_u8c3: u8 [n][h][w][3] -> u8 [n][dst_h][dst_w][3] (the cv::resize of PreProcess, test_yolo.cpp:213-216)."""
+def resize_bilinear_u8c3(images, dst_h, dst_w, src_stride=None, src_fill=0, dst_stride=None, dst_fill=0, full=False):
+    """si_hip_resize_bilinear_u8c3: u8 [n][h][w][3] -> u8 [n][dst_h][dst_w][3] (the cv::resize of PreProcess, test_yolo.cpp:213-216).
+    src_stride / dst_stride: image strides in bytes (default: dense), the gaps filled with the bytes src_fill / dst_fill before the launch;
+    full: return the destination as it lies in memory, bytes [n][dst_stride], gaps included."""
     H = _native.hip()
     src = np.ascontiguousarray(images, dtype=np.uint8)
     n, h, w = int(src.shape[0]), int(src.shape[1]), int(src.shape[2])
-    dsrc = DeviceBuffer.from_numpy(src)
-    dout = DeviceBuffer(max(n * dst_h * dst_w * 3, 16))
-    _chk(H.si_hip_resize_bilinear_u8c3(dsrc.ptr, n, h * w * 3, h, w, dout.ptr, dst_h * dst_w * 3, dst_h, dst_w, None), "si_hip_resize_bilinear_u8c3")
-    return dout.to_numpy((n, dst_h, dst_w, 3), np.uint8)
+    host, sstride = _strided_images(src, src_stride, src_fill)
+    per = dst_h * dst_w * 3
+    dstride = per if dst_stride is None else int(dst_stride)
+    assert dstride >= per, "an image stride shorter than the image"
+    dsrc = DeviceBuffer.from_numpy(host)
+    if dst_stride is None:
+        dout = DeviceBuffer(max(n * dstride, 16))          # dense: every byte is written, nothing to pre-fill
+    else:
+        dout = DeviceBuffer.from_numpy(np.full(max(n * dstride, 16), dst_fill, np.uint8), out=True)
+    _chk(H.si_hip_resize_bilinear_u8c3(dsrc.ptr, n, sstride, h, w, dout.ptr, dstride, dst_h, dst_w, None), "si_hip_resize_bilinear_u8c3")
+    raw = dout.to_numpy((n, dstride), np.uint8)
+    return raw if full else np.ascontiguousarray(raw[:, :per]).reshape(n, dst_h, dst_w, 3)
 
 
-def resize_letterbox_batch(frames_bgr, height_new, width_new):
+def resize_letterbox_batch(frames_bgr, height_new, width_new, src_stride=None, src_fill=0):
     """si_hip_resize_letterbox_batch_u8_f32: camera frames u8 BGR [n][h][w][3] -> float RGB [n][height_new][width_new][3]
-    (aspect-preserving bilinear resize + pad(114) + / 255: PreProcess whole, test_yolo.cpp:194-259) in one launch."""
+    (aspect-preserving bilinear resize + pad(114) + / 255: PreProcess whole, test_yolo.cpp:194-259) in one launch.  src_stride: image
+    stride of the frames in bytes (default: dense), the gaps filled with the byte src_fill."""
     H = _native.hip()
     src = np.ascontiguousarray(frames_bgr, dtype=np.uint8)
     n, h, w = int(src.shape[0]), int(src.shape[1]), int(src.shape[2])
-    dsrc = DeviceBuffer.from_numpy(src)
+    host, stride = _strided_images(src, src_stride, src_fill)
+    dsrc = DeviceBuffer.from_numpy(host)
     dout = DeviceBuffer(max(n * height_new * width_new * 3 * 4, 16))
-    _chk(H.si_hip_resize_letterbox_batch_u8_f32(dsrc.ptr, n, h * w * 3, h, w, dout.ptr, height_new, width_new, None),
+    _chk(H.si_hip_resize_letterbox_batch_u8_f32(dsrc.ptr, n, stride, h, w, dout.ptr, height_new, width_new, None),
          "si_hip_resize_letterbox_batch_u8_f32")
     return dout.to_numpy((n, height_new, width_new, 3))
 
 
 def yolo_postprocess(pred, prob_threshold=0.25, nms_threshold=0.45, agnostic=False, adjust=None, max_det=None,
-                     pred_dev=None):
+                     pred_dev=None, workspace=None, dets_dev=None):
     """Device post-processing of test_yolo.cpp:337-428.  pred [n][rows][ne] -> list (one per image) of float arrays
     [k][6] = {x, y, w, h, confidence, label} in picked order.  adjust: None or [n][5]
-    {padding_l, padding_t, scale, image cols, image rows}."""
+    {padding_l, padding_t, scale, image cols, image rows}.  workspace: a caller's DeviceBuffer to use as the scratch (at least
+    si_hip_yolo_postprocess_workspace_bytes; whatever it holds must not matter); dets_dev: a caller's DeviceBuffer for the
+    [n][max_det][6] output, so that the caller can see what the entry left untouched in it.  Both default to fresh buffers."""
     H = _native.hip()
     pred = _f32(pred)
     n, rows, ne = (int(v) for v in pred.shape)
@@ -1342,12 +1371,14 @@ def yolo_postprocess(pred, prob_threshold=0.25, nms_threshold=0.45, agnostic=Fal
     dpred = pred_dev if pred_dev is not None else DeviceBuffer.from_numpy(pred)
     dadj = DeviceBuffer.from_numpy(_f32(adjust).reshape(n, 5)) if adjust is not None else None
     wsb = H.si_hip_yolo_postprocess_workspace_bytes(n, rows, ne)
-    dws = DeviceBuffer(wsb)
-    ddets = DeviceBuffer(max(n * max_det * 6 * 4, 16))
+    dws = workspace if workspace is not None else DeviceBuffer(wsb)
+    assert dws.nbytes >= wsb, "workspace of %d bytes, the call needs %d" % (dws.nbytes, wsb)
+    ddets = dets_dev if dets_dev is not None else DeviceBuffer(max(n * max_det * 6 * 4, 16))
+    assert ddets.nbytes >= n * max_det * 6 * 4, "dets buffer of %d bytes, the call needs %d" % (ddets.nbytes, n * max_det * 6 * 4)
     dcnt = DeviceBuffer(max(n * 4, 16))
     _chk(H.si_hip_yolo_postprocess_f32(dpred.ptr, n, rows, ne, float(prob_threshold), float(nms_threshold),
                                        int(bool(agnostic)), dadj.ptr if dadj else None, ddets.ptr, dcnt.ptr, max_det,
-                                       dws.ptr, wsb, None), "si_hip_yolo_postprocess_f32")
+                                       dws.ptr, dws.nbytes, None), "si_hip_yolo_postprocess_f32")
     if n == 0:
         return [], np.zeros((0,), np.int32)
     cnt = dcnt.to_numpy((n,), np.int32)
