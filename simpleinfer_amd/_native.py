@@ -91,6 +91,11 @@ class SiSoftmaxDesc(C.Structure):
     _fields_ = [(k, C.c_int) for k in ("n", "h", "w", "c", "in_ld", "out_ld", "axis", "log")]
 
 
+class SiReduceDesc(C.Structure):
+    """include/si_reduce.h; axes: bit mask of the NHWC axes reduced over (1 n, 2 h, 4 w, 8 c)"""
+    _fields_ = [(k, C.c_int) for k in ("n", "h", "w", "c", "in_ld", "out_ld", "axes", "op")]
+
+
 class SiPixelShuffleDesc(C.Structure):
     """include/si_superres.h"""
     _fields_ = [(k, C.c_int) for k in ("n", "ih", "iw", "ic", "in_ld", "oh", "ow", "oc", "out_ld", "r", "inverse")]
@@ -310,8 +315,14 @@ def hip():
         "si_hip_split_channels_f16": (i, split_args + [vp]),
         "si_hip_split_channels_kernel_name": (C.c_char_p, split_args + [i]),
     }
+    # include/si_reduce.h: torch.sum / torch.mean / torch.amax / torch.amin
+    reduce_ = {
+        "si_hip_reduce_f32": (i, [C.POINTER(SiReduceDesc), vp, vp, vp]),
+        "si_hip_reduce_f16": (i, [C.POINTER(SiReduceDesc), vp, vp, vp]),
+        "si_hip_reduce_kernel_name": (C.c_char_p, [C.POINTER(SiReduceDesc), vp, vp, i]),
+    }
     for name, (res, args) in (list(sig.items()) + list(norm.items()) + list(pad.items()) + list(pool.items()) + list(softmax.items()) +
-                              list(superres.items()) + list(slice_.items())):
+                              list(superres.items()) + list(slice_.items()) + list(reduce_.items())):
         fn = getattr(L, name)  # AttributeError here = header/library mismatch, which tests check
         fn.restype = res
         fn.argtypes = args
@@ -322,6 +333,7 @@ def hip():
     L._si_softmax_signatures = softmax
     L._si_superres_signatures = superres
     L._si_slice_signatures = slice_
+    L._si_reduce_signatures = reduce_
     _hip = L
     return L
 

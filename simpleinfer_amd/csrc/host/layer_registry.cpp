@@ -26,6 +26,7 @@ SI_DECLARE_LAYER(MaxPool2d)
 SI_DECLARE_LAYER(Pad2d)
 SI_DECLARE_LAYER(PixelShuffle)
 SI_DECLARE_LAYER(PReLU)
+SI_DECLARE_LAYER(Reduce)
 SI_DECLARE_LAYER(ReLU)
 SI_DECLARE_LAYER(Sigmoid)
 SI_DECLARE_LAYER(SiLU)
@@ -47,7 +48,7 @@ static std::map<std::string, LayerRegistryEntry>& Table() {
     // (UnaryOp code 16 as a module); nn.AvgPool2d / F.avg_pool2d (layer/avg_pool_2d.h) and the functional spelling of the adaptive pool;
     // nn.Softmax / nn.LogSoftmax / nn.Softmax2d / F.softmax / F.log_softmax (one class, layer/softmax.h); nn.PixelShuffle / nn.PixelUnshuffle /
     // F.pixel_shuffle / F.pixel_unshuffle (one class, layer/pixel_shuffle.h) and nn.PReLU (layer/prelu.h); torch.chunk / torch.split /
-    // Tensor.slice (one class, layer/slice.h)
+    // Tensor.slice (one class, layer/slice.h); torch.mean / torch.sum / torch.amax / torch.amin (one class, layer/reduce.h)
     static std::map<std::string, LayerRegistryEntry> table = {
         SI_ENTRY("nn.AdaptiveAvgPool2d", AdaptiveAvgPool2d),
         SI_ENTRY("nn.AvgPool2d", AvgPool2d),
@@ -93,6 +94,10 @@ static std::map<std::string, LayerRegistryEntry>& Table() {
         SI_ENTRY("torch.chunk", Slice),
         SI_ENTRY("torch.split", Slice),
         SI_ENTRY("Tensor.slice", Slice),
+        SI_ENTRY("torch.mean", Reduce),
+        SI_ENTRY("torch.sum", Reduce),
+        SI_ENTRY("torch.amax", Reduce),
+        SI_ENTRY("torch.amin", Reduce),
         SI_ENTRY("models.yolo.Detect", YoloDetect),
     };
     return table;

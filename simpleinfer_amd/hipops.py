@@ -1052,6 +1052,44 @@ def softmax_kernel_name(x_shape, axis, half=False, in_ld=None, out_ld=None) -> s
     return _native.hip().si_hip_softmax_kernel_name(C.byref(d), C.c_void_p(256), C.c_void_p(256), 1 if half else 0).decode()
 
 
+REDUCE_OPS = {"sum": 0, "mean": 1, "amax": 2, "amin": 3}
+
+
+def reduce_out_shape(x_shape, axes):
+    """the NHWC output shape of a reduction over the mask `axes` (1 n, 2 h, 4 w, 8 c): every reduced axis has extent 1"""
+    return tuple(1 if (int(axes) >> a) & 1 else int(v) for a, v in enumerate(x_shape))
+
+
+def reduce_desc(x_shape, op, axes, in_ld=None, out_ld=None):
+    """SiReduceDesc (include/si_reduce.h) of an NHWC input; op: a name of REDUCE_OPS or the code; axes: the bit mask"""
+    n, h, w, c = x_shape
+    oc = 1 if int(axes) & 8 else c
+    return _native.SiReduceDesc(n, h, w, c, in_ld or c, out_ld or oc, int(axes), REDUCE_OPS[op] if isinstance(op, str) else int(op))
+
+
+def reduce(x, op, axes, in_ld=None, in_c_off=0, in_fill=0.0, out_ld=None, out_c_off=0, out_fill=0.0, full=False):
+    """si_hip_reduce_f32 / _f16 (by the array's dtype) on an NHWC array: torch.sum / mean / amax / amin (`op`) over the NHWC axes of the
+    bit mask `axes` (1 n, 2 h, 4 w, 8 c), keepdim=True.  The view hooks are the common ones."""
+    H = _native.hip()
+    x = _float_storage(x)
+    half = x.dtype == np.float16
+    assert x.ndim == 4, "NHWC (a rank-2 [N, F] array is [N, 1, 1, F])"
+    d = reduce_desc(x.shape, op, axes, in_ld, out_ld)
+    oshape = reduce_out_shape(x.shape, axes if 1 <= int(axes) <= 15 else 0)
+    oc = oshape[3]
+    (dx, px), (dy, py) = _view_in(x, in_ld, in_c_off, in_fill), _view_out(oshape[:-1], oc, out_ld, out_c_off, out_fill, x.dtype)
+    LAST_KERNEL_NAME["si_hip_reduce"] = H.si_hip_reduce_kernel_name(C.byref(d), C.c_void_p(px), C.c_void_p(py), 1 if half else 0).decode()
+    fn, name = (H.si_hip_reduce_f16, "si_hip_reduce_f16") if half else (H.si_hip_reduce_f32, "si_hip_reduce_f32")
+    _chk(fn(C.byref(d), px, py, None), name)
+    return _ret(dy.to_numpy(oshape[:-1] + (out_ld or oc,), x.dtype), oc, out_c_off, full)
+
+
+def reduce_kernel_name(x_shape, op, axes, half=False, in_ld=None, out_ld=None) -> str:
+    """the instantiation for 16-byte aligned buffers of these shapes ("none": a descriptor the launch refuses)"""
+    d = reduce_desc(x_shape, op, axes, in_ld, out_ld)
+    return _native.hip().si_hip_reduce_kernel_name(C.byref(d), C.c_void_p(256), C.c_void_p(256), 1 if half else 0).decode()
+
+
 def pixel_shuffle_desc(x_shape, r, inverse=False, in_ld=None, out_ld=None):
     """SiPixelShuffleDesc (include/si_superres.h) of an NHWC input; the output shape is the rule's (floor division: a height, width or
     channel count the factor does not divide gives a descriptor the entry refuses)"""

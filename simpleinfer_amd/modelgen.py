@@ -233,6 +233,25 @@ class PnnxBuilder:
         """nn.Softmax2d: no parameter (softmax over the channels of a rank-4 tensor)"""
         return self._unary("nn.Softmax2d", "softmax2d", x)
 
+    def _reduce(self, op: str, x: str, dim, keepdim: bool) -> str:
+        """pnnx's torch.mean / torch.sum / torch.amax / torch.amin line: dim= an int or a tuple as given ((2,3), (1,) is written (1)),
+        keepdim=; torch.mean and torch.sum also carry dtype=None.  The output shape is torch's rule."""
+        shp = self.shapes[x]
+        dims = sorted({d % len(shp) for d in ((dim,) if isinstance(dim, int) else dim)})
+        out_shape = [1 if i in dims else s for i, s in enumerate(shp)] if keepdim else [s for i, s in enumerate(shp) if i not in dims]
+        out = self._new_operand(out_shape)
+        params = dict(dim=int(dim) if isinstance(dim, int) else tuple(int(d) for d in dim))
+        if op in ("mean", "sum"):
+            params["dtype"] = "None"
+        params["keepdim"] = bool(keepdim)
+        self._emit("torch." + op, self._opname("torch_" + op), [x], [out], params)
+        return out
+
+    def mean(self, x: str, dim, keepdim: bool = False) -> str: return self._reduce("mean", x, dim, keepdim)
+    def sum(self, x: str, dim, keepdim: bool = False) -> str: return self._reduce("sum", x, dim, keepdim)
+    def amax(self, x: str, dim, keepdim: bool = False) -> str: return self._reduce("amax", x, dim, keepdim)
+    def amin(self, x: str, dim, keepdim: bool = False) -> str: return self._reduce("amin", x, dim, keepdim)
+
     def _head(self, x: str, head) -> str:
         """the optional last layer of the toy builders: None, "softmax" or "log_softmax" over dim 1"""
         assert head in (None, "softmax", "log_softmax"), head
@@ -631,6 +650,65 @@ def build_toy_classifier(batch: int = 2, size: int = 32, seed: int = 0, head=Non
     x = b.flatten(x)
     x = b.linear(x, 10)
     b.output(b._head(x, head))
+    return b
+
+
+def build_toy_timm_head(batch: int = 2, size: int = 32, seed: int = 0) -> PnnxBuilder:
+    """The head of a timm export: a conv stack, x.mean((2, 3)) -- torch.mean, keepdim=False, the [N, C] result -- and nn.Linear."""
+    b = PnnxBuilder(seed)
+    x = b.input((batch, 3, size, size))
+    x = b.relu(b.conv(x, 16, 3, 2, 1))
+    x = b.relu(b.conv(x, 32, 3, 2, 1))
+    x = b.mean(x, (2, 3))
+    b.output(b.linear(x, 10))
+    return b
+
+
+def build_toy_cbam(batch: int = 2, size: int = 16, seed: int = 0) -> PnnxBuilder:
+    """CBAM on one feature map.  Channel attention: mean and amax over (2, 3) with keepdim, the same two 1x1 convs (shared weights) on
+    both, add, sigmoid, broadcast mul.  Spatial attention: mean and amax over dim 1 with keepdim, cat, a 7x7 conv, sigmoid, broadcast
+    mul over the channels.  A 1x1 conv closes the file."""
+    b = PnnxBuilder(seed)
+    x = b.input((batch, 3, size, size))
+    f = b.relu(b.conv(x, 16, 3, 1, 1))
+    avg, mx = b.mean(f, (2, 3), True), b.amax(f, (2, 3), True)
+
+    def mlp(v, tag):
+        return b.conv(b.relu(b.conv(v, 4, 1, name="mlp0_" + tag)), 16, 1, name="mlp1_" + tag)
+
+    a, m = mlp(avg, "avg"), mlp(mx, "max")
+    for layer in ("mlp0_", "mlp1_"):   # one MLP: the second pair of lines carries the first pair's weights
+        for k in ("weight", "bias"):
+            b.attrs[layer + "max." + k] = b.attrs[layer + "avg." + k].copy()
+    f = b.mul(f, b.sigmoid(b.add(a, m)))
+    s = b.cat([b.mean(f, 1, True), b.amax(f, 1, True)], 1)
+    f = b.mul(f, b.sigmoid(b.conv(s, 1, 7, 1, 3)))
+    b.output(b.conv(f, 8, 1))
+    return b
+
+
+def build_toy_coordatt(batch: int = 2, height: int = 12, width: int = 20, seed: int = 0) -> PnnxBuilder:
+    """Coordinate attention: mean(3, keepdim) -> [N, C, H, 1] and mean(2, keepdim) -> [N, C, 1, W], each through a 1x1 conv and a
+    sigmoid, then two broadcast muls; a 1x1 conv closes the file."""
+    b = PnnxBuilder(seed)
+    x = b.input((batch, 3, height, width))
+    f = b.relu(b.conv(x, 16, 3, 1, 1))
+    ah = b.sigmoid(b.conv(b.mean(f, 3, True), 16, 1))
+    aw = b.sigmoid(b.conv(b.mean(f, 2, True), 16, 1))
+    b.output(b.conv(b.mul(b.mul(f, ah), aw), 8, 1))
+    return b
+
+
+def build_toy_layernorm2d(batch: int = 2, size: int = 16, seed: int = 0, eps: str = "1e-06") -> PnnxBuilder:
+    """ConvNeXt's channels-first LayerNorm as its export writes it: u = x.mean(1, keepdim), d = x - u, s = (d * d).mean(1, keepdim),
+    d / sqrt(s + eps) with the arithmetic in pnnx.Expression operators; a 1x1 conv follows."""
+    b = PnnxBuilder(seed)
+    x = b.input((batch, 3, size, size))
+    f = b.conv(x, 16, 3, 1, 1)
+    d = b.expression("sub(@0,@1)", [f, b.mean(f, 1, True)])
+    s = b.mean(b.expression("square(@0)", [d]), (1,), True)
+    y = b.expression("div(@0,sqrt(add(@1,%s)))" % eps, [d, s])
+    b.output(b.conv(y, 8, 1))
     return b
 
 
