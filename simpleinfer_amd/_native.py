@@ -96,6 +96,12 @@ class SiReduceDesc(C.Structure):
     _fields_ = [(k, C.c_int) for k in ("n", "h", "w", "c", "in_ld", "out_ld", "axes", "op")]
 
 
+class SiParamActDesc(C.Structure):
+    """include/si_act.h; op: 0 clamp (p0 lo, p1 hi), 1 softplus (p0 beta, p1 threshold), 2 mish"""
+    _fields_ = [("op", C.c_int), ("p0", C.c_float), ("p1", C.c_float), ("pixels", C.c_size_t), ("c", C.c_int), ("in_ld", C.c_int),
+                ("out_ld", C.c_int)]
+
+
 class SiPixelShuffleDesc(C.Structure):
     """include/si_superres.h"""
     _fields_ = [(k, C.c_int) for k in ("n", "ih", "iw", "ic", "in_ld", "oh", "ow", "oc", "out_ld", "r", "inverse")]
@@ -321,8 +327,14 @@ def hip():
         "si_hip_reduce_f16": (i, [C.POINTER(SiReduceDesc), vp, vp, vp]),
         "si_hip_reduce_kernel_name": (C.c_char_p, [C.POINTER(SiReduceDesc), vp, vp, i]),
     }
+    # include/si_act.h: clamp (nn.ReLU6 / nn.Hardtanh / torch.clamp), nn.Softplus, nn.Mish
+    act = {
+        "si_hip_param_act_f32": (i, [C.POINTER(SiParamActDesc), vp, vp, vp]),
+        "si_hip_param_act_f16": (i, [C.POINTER(SiParamActDesc), vp, vp, vp]),
+        "si_hip_param_act_kernel_name": (C.c_char_p, [C.POINTER(SiParamActDesc), vp, vp, i]),
+    }
     for name, (res, args) in (list(sig.items()) + list(norm.items()) + list(pad.items()) + list(pool.items()) + list(softmax.items()) +
-                              list(superres.items()) + list(slice_.items()) + list(reduce_.items())):
+                              list(superres.items()) + list(slice_.items()) + list(reduce_.items()) + list(act.items())):
         fn = getattr(L, name)  # AttributeError here = header/library mismatch, which tests check
         fn.restype = res
         fn.argtypes = args
@@ -334,6 +346,7 @@ def hip():
     L._si_superres_signatures = superres
     L._si_slice_signatures = slice_
     L._si_reduce_signatures = reduce_
+    L._si_act_signatures = act
     _hip = L
     return L
 

@@ -30,7 +30,9 @@ bool HonoursPixelStride(const std::string& type) {
         "nn.GroupNorm", "nn.InstanceNorm2d", "nn.ReflectionPad2d", "nn.ReplicationPad2d", "nn.ZeroPad2d", "nn.ConstantPad2d", "nn.CircularPad2d",
         "F.pad", "nn.Tanh", "nn.AvgPool2d", "F.avg_pool2d", "F.adaptive_avg_pool2d", "nn.Softmax", "nn.LogSoftmax", "nn.Softmax2d",
         "F.softmax", "F.log_softmax", "nn.PixelShuffle", "nn.PixelUnshuffle", "F.pixel_shuffle", "F.pixel_unshuffle", "nn.PReLU", "torch.flatten",
-        "torch.chunk", "torch.split", "Tensor.slice", "torch.mean", "torch.sum", "torch.amax", "torch.amin", "models.yolo.Detect", "pnnx.Output"};
+        "torch.chunk", "torch.split", "Tensor.slice", "torch.mean", "torch.sum", "torch.amax", "torch.amin", "nn.ReLU6", "F.relu6",
+        "nn.Hardtanh", "F.hardtanh", "torch.clamp", "nn.Softplus", "F.softplus", "nn.Mish", "F.mish", "F.relu", "F.silu", "F.sigmoid", "F.hardsigmoid",
+        "F.hardswish", "F.leaky_relu", "F.tanh", "models.yolo.Detect", "pnnx.Output"};
     return ok.count(type) > 0;
 }
 

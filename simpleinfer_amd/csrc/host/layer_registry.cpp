@@ -24,6 +24,7 @@ SI_DECLARE_LAYER(LeakyReLU)
 SI_DECLARE_LAYER(Linear)
 SI_DECLARE_LAYER(MaxPool2d)
 SI_DECLARE_LAYER(Pad2d)
+SI_DECLARE_LAYER(ParamActivation)
 SI_DECLARE_LAYER(PixelShuffle)
 SI_DECLARE_LAYER(PReLU)
 SI_DECLARE_LAYER(Reduce)
@@ -48,7 +49,9 @@ static std::map<std::string, LayerRegistryEntry>& Table() {
     // (UnaryOp code 16 as a module); nn.AvgPool2d / F.avg_pool2d (layer/avg_pool_2d.h) and the functional spelling of the adaptive pool;
     // nn.Softmax / nn.LogSoftmax / nn.Softmax2d / F.softmax / F.log_softmax (one class, layer/softmax.h); nn.PixelShuffle / nn.PixelUnshuffle /
     // F.pixel_shuffle / F.pixel_unshuffle (one class, layer/pixel_shuffle.h) and nn.PReLU (layer/prelu.h); torch.chunk / torch.split /
-    // Tensor.slice (one class, layer/slice.h); torch.mean / torch.sum / torch.amax / torch.amin (one class, layer/reduce.h)
+    // Tensor.slice (one class, layer/slice.h); torch.mean / torch.sum / torch.amax / torch.amin (one class, layer/reduce.h); nn.ReLU6 / nn.Hardtanh /
+    // torch.clamp / nn.Softplus / nn.Mish and their F.* spellings (one class, layer/param_activation.h: never folded into an epilogue); the
+    // functional spellings of the activations above, on the classes of their nn.* twins (they fuse as those do; F.tanh, like nn.Tanh, does not)
     static std::map<std::string, LayerRegistryEntry> table = {
         SI_ENTRY("nn.AdaptiveAvgPool2d", AdaptiveAvgPool2d),
         SI_ENTRY("nn.AvgPool2d", AvgPool2d),
@@ -98,6 +101,22 @@ static std::map<std::string, LayerRegistryEntry>& Table() {
         SI_ENTRY("torch.sum", Reduce),
         SI_ENTRY("torch.amax", Reduce),
         SI_ENTRY("torch.amin", Reduce),
+        SI_ENTRY("nn.ReLU6", ParamActivation),
+        SI_ENTRY("F.relu6", ParamActivation),
+        SI_ENTRY("nn.Hardtanh", ParamActivation),
+        SI_ENTRY("F.hardtanh", ParamActivation),
+        SI_ENTRY("torch.clamp", ParamActivation),
+        SI_ENTRY("nn.Softplus", ParamActivation),
+        SI_ENTRY("F.softplus", ParamActivation),
+        SI_ENTRY("nn.Mish", ParamActivation),
+        SI_ENTRY("F.mish", ParamActivation),
+        SI_ENTRY("F.relu", ReLU),
+        SI_ENTRY("F.silu", SiLU),
+        SI_ENTRY("F.sigmoid", Sigmoid),
+        SI_ENTRY("F.hardsigmoid", HardSigmoid),
+        SI_ENTRY("F.hardswish", HardSwish),
+        SI_ENTRY("F.leaky_relu", LeakyReLU),
+        SI_ENTRY("F.tanh", Tanh),
         SI_ENTRY("models.yolo.Detect", YoloDetect),
     };
     return table;

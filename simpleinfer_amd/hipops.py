@@ -1090,6 +1090,38 @@ def reduce_kernel_name(x_shape, op, axes, half=False, in_ld=None, out_ld=None) -
     return _native.hip().si_hip_reduce_kernel_name(C.byref(d), C.c_void_p(256), C.c_void_p(256), 1 if half else 0).decode()
 
 
+PARAM_ACT_OPS = {"clamp": 0, "softplus": 1, "mish": 2}
+
+
+def param_act_desc(x_shape, op, p0=0.0, p1=0.0, in_ld=None, out_ld=None):
+    """SiParamActDesc (include/si_act.h) of an array whose last axis is the channels; op: a name of PARAM_ACT_OPS or the code"""
+    c = int(x_shape[-1])
+    pixels = int(np.prod(x_shape[:-1], dtype=np.int64)) if len(x_shape) > 1 else 1
+    return _native.SiParamActDesc(PARAM_ACT_OPS[op] if isinstance(op, str) else int(op), float(p0), float(p1), pixels, c, in_ld or c, out_ld or c)
+
+
+def param_act(x, op, p0=0.0, p1=0.0, half=False, in_ld=None, in_c_off=0, in_fill=0.0, out_ld=None, out_c_off=0, out_fill=0.0, full=False):
+    """si_hip_param_act_f32 / _f16 (half=True, or a float16 array) on an array whose last axis is the channels: clamp (p0 lo, p1 hi),
+    softplus (p0 beta, p1 threshold) or mish.  The view hooks are the common ones."""
+    H = _native.hip()
+    x = np.asarray(x)
+    x = np.ascontiguousarray(x, dtype=np.float16) if (half or x.dtype == np.float16) else _f32(x)
+    half = x.dtype == np.float16
+    c = x.shape[-1]
+    d = param_act_desc(x.shape, op, p0, p1, in_ld, out_ld)
+    (dx, px), (dy, py) = _view_in(x, in_ld, in_c_off, in_fill), _view_out(x.shape[:-1], c, out_ld, out_c_off, out_fill, x.dtype)
+    LAST_KERNEL_NAME["si_hip_param_act"] = H.si_hip_param_act_kernel_name(C.byref(d), C.c_void_p(px), C.c_void_p(py), 1 if half else 0).decode()
+    fn, name = (H.si_hip_param_act_f16, "si_hip_param_act_f16") if half else (H.si_hip_param_act_f32, "si_hip_param_act_f32")
+    _chk(fn(C.byref(d), px, py, None), name)
+    return _ret(dy.to_numpy(x.shape[:-1] + (out_ld or c,), x.dtype), c, out_c_off, full)
+
+
+def param_act_kernel_name(x_shape, op, p0=0.0, p1=0.0, half=False, in_ld=None, out_ld=None) -> str:
+    """the instantiation for 16-byte aligned buffers of these shapes ("none": a descriptor the launch refuses)"""
+    d = param_act_desc(x_shape, op, p0, p1, in_ld, out_ld)
+    return _native.hip().si_hip_param_act_kernel_name(C.byref(d), C.c_void_p(256), C.c_void_p(256), 1 if half else 0).decode()
+
+
 def pixel_shuffle_desc(x_shape, r, inverse=False, in_ld=None, out_ld=None):
     """SiPixelShuffleDesc (include/si_superres.h) of an NHWC input; the output shape is the rule's (floor division: a height, width or
     channel count the factor does not divide gives a descriptor the entry refuses)"""

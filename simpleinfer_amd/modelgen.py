@@ -175,15 +175,38 @@ class PnnxBuilder:
         self._emit(typ, self._opname(prefix), [x], [out], params or {})
         return out
 
-    def silu(self, x): return self._unary("nn.SiLU", "silu", x)
-    def relu(self, x): return self._unary("nn.ReLU", "relu", x)
-    def sigmoid(self, x): return self._unary("nn.Sigmoid", "sigmoid", x)
-    def hardsigmoid(self, x): return self._unary("nn.Hardsigmoid", "hsigmoid", x)
-    def hardswish(self, x): return self._unary("nn.Hardswish", "hswish", x)
-    def tanh(self, x): return self._unary("nn.Tanh", "tanh", x)
+    def _act(self, module: str, prefix: str, fname: str, x: str, functional: bool, params=None) -> str:
+        """an activation as its module line, or (functional=True) as pnnx's F.<fname> line with the same keys"""
+        if functional:
+            return self._unary("F." + fname, "F_" + fname, x, params)
+        return self._unary(module, prefix, x, params)
 
-    def leaky_relu(self, x, negative_slope: float = 0.01):
-        return self._unary("nn.LeakyReLU", "leakyrelu", x, dict(negative_slope=float(negative_slope)))
+    def silu(self, x, functional=False): return self._act("nn.SiLU", "silu", "silu", x, functional)
+    def relu(self, x, functional=False): return self._act("nn.ReLU", "relu", "relu", x, functional)
+    def sigmoid(self, x, functional=False): return self._act("nn.Sigmoid", "sigmoid", "sigmoid", x, functional)
+    def hardsigmoid(self, x, functional=False): return self._act("nn.Hardsigmoid", "hsigmoid", "hardsigmoid", x, functional)
+    def hardswish(self, x, functional=False): return self._act("nn.Hardswish", "hswish", "hardswish", x, functional)
+    def tanh(self, x, functional=False): return self._act("nn.Tanh", "tanh", "tanh", x, functional)
+
+    def leaky_relu(self, x, negative_slope: float = 0.01, functional=False):
+        return self._act("nn.LeakyReLU", "leakyrelu", "leaky_relu", x, functional, dict(negative_slope=float(negative_slope)))
+
+    def relu6(self, x, functional=False): return self._act("nn.ReLU6", "relu6", "relu6", x, functional)
+    def mish(self, x, functional=False): return self._act("nn.Mish", "mish", "mish", x, functional)
+
+    def hardtanh(self, x, min_val: float = -1.0, max_val: float = 1.0, functional=False):
+        """pnnx's nn.Hardtanh / F.hardtanh line with torch's keys min_val / max_val"""
+        return self._act("nn.Hardtanh", "hardtanh", "hardtanh", x, functional, dict(max_val=float(max_val), min_val=float(min_val)))
+
+    def softplus(self, x, beta: float = 1.0, threshold: float = 20.0, functional=False):
+        """pnnx's nn.Softplus / F.softplus line with torch's keys beta / threshold"""
+        return self._act("nn.Softplus", "softplus", "softplus", x, functional, dict(beta=float(beta), threshold=float(threshold)))
+
+    def clamp(self, x, min=None, max=None, functional=True):
+        """pnnx's torch.clamp line: max= and min=, a bound that is None written None.  (A tensor function: there is no module spelling,
+        and `functional` is accepted for symmetry only.)"""
+        one = lambda v: "None" if v is None else float(v)
+        return self._unary("torch.clamp", "torch_clamp", x, dict(max=one(max), min=one(min)))
 
     def pixel_shuffle(self, x: str, r: int, functional: bool = False) -> str:
         """pnnx's nn.PixelShuffle line with torch's key `upscale_factor` (functional=True: F.pixel_shuffle, the same key):
@@ -709,6 +732,47 @@ def build_toy_layernorm2d(batch: int = 2, size: int = 16, seed: int = 0, eps: st
     s = b.mean(b.expression("square(@0)", [d]), (1,), True)
     y = b.expression("div(@0,sqrt(add(@1,%s)))" % eps, [d, s])
     b.output(b.conv(y, 8, 1))
+    return b
+
+
+def build_toy_mobilenetv2(batch: int = 2, size: int = 32, seed: int = 0, ncls: int = 10, functional: bool = False) -> PnnxBuilder:
+    """MobileNetV2 in small: a 3x3 s2 stem with ReLU6, three inverted-residual blocks -- 1x1 expand, ReLU6, 3x3 depthwise, ReLU6, 1x1 project
+    (linear), and the residual add where the stride is 1 and the widths match -- then the global pool, flatten and nn.Linear.
+    functional=True: F.relu6 lines."""
+    b = PnnxBuilder(seed)
+    x = b.input((batch, 3, size, size))
+    x = b.relu6(b.conv(x, 8, 3, 2, 1), functional)
+    for cout, stride, expand in ((8, 1, 2), (16, 2, 4), (16, 1, 4)):
+        cin = b.shapes[x][1]
+        y = b.relu6(b.conv(x, cin * expand, 1), functional)
+        y = b.relu6(b.conv(y, cin * expand, 3, stride, 1, groups=cin * expand), functional)
+        y = b.conv(y, cout, 1)
+        x = b.add(x, y) if stride == 1 and cin == cout else y
+    x = b.flatten(b.adaptive_avgpool(x, (1, 1)))
+    b.output(b.linear(x, ncls))
+    return b
+
+
+def build_toy_csp_mish(batch: int = 2, size: int = 16, seed: int = 0, functional: bool = False) -> PnnxBuilder:
+    """A CSPDarknet-Mish block (YOLOv4): a 3x3 s2 conv, two 1x1 branches, a 1x1 / 3x3 residual unit on one of them, torch.cat, a 1x1
+    conv -- nn.Mish after every convolution."""
+    b = PnnxBuilder(seed)
+    m = lambda v: b.mish(v, functional)
+    x = b.input((batch, 3, size, size))
+    x = m(b.conv(x, 16, 3, 2, 1))
+    left, right = m(b.conv(x, 8, 1)), m(b.conv(x, 8, 1))
+    r = m(b.conv(m(b.conv(right, 8, 1)), 8, 3, 1, 1))
+    right = m(b.conv(b.add(right, r), 8, 1))
+    b.output(m(b.conv(b.cat([right, left], 1), 16, 1)))
+    return b
+
+
+def build_toy_clamp_head(batch: int = 2, size: int = 16, seed: int = 0) -> PnnxBuilder:
+    """A positive-output head: conv, nn.Softplus, then x.clamp(min=0.1) -- torch.clamp with max=None."""
+    b = PnnxBuilder(seed)
+    x = b.input((batch, 3, size, size))
+    x = b.softplus(b.conv(x, 8, 3, 1, 1))
+    b.output(b.clamp(x, min=0.1))
     return b
 
 
