@@ -113,6 +113,16 @@ class SiSliceDesc(C.Structure):
         (k, C.c_int) for k in ("on", "oh", "ow", "oc", "out_ld")]
 
 
+class SiPermuteDesc(C.Structure):
+    """include/si_permute.h; the output loop nest, outermost first, with the input stride of every loop dimension"""
+    _fields_ = [("rank", C.c_int), ("dims", C.c_int * 4), ("in_stride", C.c_longlong * 4), ("out_ld", C.c_int), ("form", C.c_int)]
+
+
+class SiLayoutNest(C.Structure):
+    """include/si_layout.h; what si_layout_plan returns: view != 0, or the loop nest of the copy"""
+    _fields_ = [("view", C.c_int), ("rank", C.c_int), ("dims", C.c_int * 8), ("in_stride", C.c_longlong * 8)]
+
+
 class SiConv2dUpsampledSource(C.Structure):
     _fields_ = [("src", C.c_void_p), ("ih", C.c_int), ("iw", C.c_int), ("c", C.c_int), ("ld", C.c_int), ("c0", C.c_int),
                 ("inv_scale_h", C.c_float), ("inv_scale_w", C.c_float)]
@@ -333,8 +343,14 @@ def hip():
         "si_hip_param_act_f16": (i, [C.POINTER(SiParamActDesc), vp, vp, vp]),
         "si_hip_param_act_kernel_name": (C.c_char_p, [C.POINTER(SiParamActDesc), vp, vp, i]),
     }
+    # include/si_permute.h: the strided-gather copy behind Tensor.permute / reshape / view / torch.transpose
+    permute_ = {
+        "si_hip_permute_f32": (i, [C.POINTER(SiPermuteDesc), vp, vp, vp]),
+        "si_hip_permute_f16": (i, [C.POINTER(SiPermuteDesc), vp, vp, vp]),
+        "si_hip_permute_kernel_name": (C.c_char_p, [C.POINTER(SiPermuteDesc), vp, vp, i]),
+    }
     for name, (res, args) in (list(sig.items()) + list(norm.items()) + list(pad.items()) + list(pool.items()) + list(softmax.items()) +
-                              list(superres.items()) + list(slice_.items()) + list(reduce_.items()) + list(act.items())):
+                              list(superres.items()) + list(slice_.items()) + list(reduce_.items()) + list(act.items()) + list(permute_.items())):
         fn = getattr(L, name)  # AttributeError here = header/library mismatch, which tests check
         fn.restype = res
         fn.argtypes = args
@@ -347,6 +363,7 @@ def hip():
     L._si_slice_signatures = slice_
     L._si_reduce_signatures = reduce_
     L._si_act_signatures = act
+    L._si_permute_signatures = permute_
     _hip = L
     return L
 
@@ -417,11 +434,17 @@ def host():
         "si_gather_complete": (i, [vp, i]),
         "si_gather_stats": (i, [vp, C.POINTER(SiGatherStats), i]),
     }
-    for name, (res, args) in list(sig.items()) + list(shard.items()):
+    # include/si_layout.h: the layout algebra (pure host code: no device is touched)
+    ip = C.POINTER(C.c_int)
+    layout = {
+        "si_layout_plan": (i, [i, ip, i, i, ip, ip, ip, i, ip, C.POINTER(SiLayoutNest)]),
+    }
+    for name, (res, args) in list(sig.items()) + list(shard.items()) + list(layout.items()):
         fn = getattr(L, name)
         fn.restype = res
         fn.argtypes = args
     L._si_signatures = sig
     L._si_shard_signatures = shard
+    L._si_layout_signatures = layout
     _host = L
     return L

@@ -21,6 +21,8 @@ Status EngineImpl::SetOption(const std::string& key, int value) {
     else if (key == "fuse") opt_fuse_ = value != 0;
     else if (key == "alias_cat") opt_alias_cat_ = value != 0;
     else if (key == "alias_split") opt_alias_split_ = value != 0;   // chunk / split / slice outputs on the channel axis as views of the input (default 1)
+    else if (key == "fuse_layout") opt_fuse_layout_ = value != 0;   // runs of layout operators as one step (default 1)
+    else if (key == "alias_view") opt_alias_view_ = value != 0;     // layout steps that move no byte as views of their input (default 1)
     else if (key == "graph") opt_graph_ = value != 0;
     else if (key == "outputs_to_host") opt_outputs_to_host_ = value != 0;
     else if (key == "fp16") opt_fp16_ = value != 0;
@@ -439,9 +441,10 @@ Status EngineImpl::EnsureArena() {
             Tensor& t = tensor_nodes_[kv.first]->tensor;
             Tensor& parent = kv.second.parent->tensor;
             if (parent.RawData() == nullptr) continue;
-            // (the parent is a root buffer -- ResolveAliases -- and the view takes ITS pixel stride)
+            // (the parent is a root buffer -- ResolveAliases -- and a channel slice takes ITS pixel stride; a view of the whole buffer is dense
+            // under its own shape, and a slice of such a view has the view's rows)
             t.SetView(static_cast<char*>(parent.RawData()) + (size_t)kv.second.channel_offset * ElementSize(parent.GetDataType()),
-                      MemoryType::kDevice, parent.PixelStride());
+                      MemoryType::kDevice, kv.second.whole ? 0 : (kv.second.ld > 0 ? kv.second.ld : parent.PixelStride()));
         }
         aliases_bound_ = true;
     }
@@ -513,6 +516,8 @@ Status EngineImpl::LoadLanes(int lanes) {
         lane->opt_fuse_ = opt_fuse_;
         lane->opt_alias_cat_ = opt_alias_cat_;
         lane->opt_alias_split_ = opt_alias_split_;
+        lane->opt_fuse_layout_ = opt_fuse_layout_;
+        lane->opt_alias_view_ = opt_alias_view_;
         lane->opt_fuse_upsample_ = opt_fuse_upsample_;
         lane->opt_fuse_stem_ = opt_fuse_stem_;
         lane->opt_fuse_pw_ = opt_fuse_pw_;
@@ -654,6 +659,8 @@ Status EngineImpl::SetupSlicer(int slices) {
     slicer_->opt_fuse_ = opt_fuse_;
     slicer_->opt_alias_cat_ = opt_alias_cat_;
     slicer_->opt_alias_split_ = opt_alias_split_;
+    slicer_->opt_fuse_layout_ = opt_fuse_layout_;
+    slicer_->opt_alias_view_ = opt_alias_view_;
     slicer_->opt_fuse_upsample_ = opt_fuse_upsample_;
     slicer_->opt_fuse_stem_ = opt_fuse_stem_;
     slicer_->opt_fuse_pw_ = opt_fuse_pw_;

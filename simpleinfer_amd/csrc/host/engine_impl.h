@@ -102,6 +102,7 @@ private:
     Status FuseEpilogues(std::vector<Step>& order);
     Status FuseSiblingConvs(std::vector<Step>& order);
     Status FusePoolChains(std::vector<Step>& order);
+    Status FuseLayoutChains(std::vector<Step>& order);
     Status FuseUpsampleIntoConvs(std::vector<Step>& order);
     Status FuseStemPairs(std::vector<Step>& order);
     Status FuseStemTriples(std::vector<Step>& order);
@@ -111,6 +112,7 @@ private:
     Status InsertFp32Fallbacks(std::vector<Step>& order);
     Status AliasConcats();
     Status AliasSplits();
+    Status AliasViews();
     void ResolveAliases();
     Status UploadInputs();
     Status BindOutputs();
@@ -139,6 +141,8 @@ private:
     bool opt_fuse_ = true;
     bool opt_alias_cat_ = true;
     bool opt_alias_split_ = true;   // torch.chunk / torch.split / Tensor.slice outputs that are channel ranges become views of the input (0: always copied)
+    bool opt_fuse_layout_ = true;   // a run of permute / reshape / view / transpose / squeeze / unsqueeze operators is planned as ONE layout step (0: one step each)
+    bool opt_alias_view_ = true;    // a layout step that moves no byte makes its output a view of its input's buffer (0: one permute_rows copy)
     bool opt_fuse_upsample_ = true;
     int opt_fuse_stem_ = 2;
     int opt_fuse_pw_ = 1;   // (2: ... and the C3's closing conv behind its last 64-channel pair -- built in round 6, bit-identical, 0.74-0.84x of the launches
@@ -209,8 +213,10 @@ private:
     struct Alias {
         TensorNode* parent = nullptr;
         int channel_offset = 0;
+        bool whole = false;   // the parent's whole buffer under the operand's own shape, dense (a layout step that is a view)
+        int ld = 0;           // pixel stride of a channel slice; 0: the parent's own (set when the slice hangs off a view, whose rows are not the root's)
     };
-    std::map<std::string, Alias> aliases_;   // operand name -> channel slice of another operand's buffer (a concat output, a split's input)
+    std::map<std::string, Alias> aliases_;   // operand name -> channel slice of another operand's buffer (a concat output, a split's input), or a view of all of it
 
     std::vector<void*> device_allocs_;
     size_t arena_bytes_ = 0, unshared_bytes_ = 0;   // footprint with / without lifetime sharing (statistics)

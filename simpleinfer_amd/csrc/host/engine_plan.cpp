@@ -11,6 +11,7 @@
 #include "layer/conv_2d.h"
 #include "layer/conv_transpose_2d.h"
 #include "layer/group_norm.h"
+#include "layer/layout.h"
 #include "layer/linear.h"
 #include "layer/max_pool_2d.h"
 #include "layer/output_cast.h"
@@ -76,12 +77,16 @@ Status EngineImpl::CreatePipeline() {
         CHECK_STATUS(FuseEpilogues(order));
         CHECK_STATUS(FuseSiblingConvs(order));
         CHECK_STATUS(FusePoolChains(order));
+        if (opt_fuse_layout_) CHECK_STATUS(FuseLayoutChains(order));
         if (opt_fuse_upsample_ && opt_alias_cat_) CHECK_STATUS(FuseUpsampleIntoConvs(order));   // (fp16 storage too since round 4)
         if (opt_fp16_ && opt_fuse_stem_) CHECK_STATUS(FuseStemPairs(order));
         if (opt_fp16_ && opt_fuse_stem_ > 1) CHECK_STATUS(FuseStemTriples(order));
         if (opt_fp16_ && opt_fuse_pw_) CHECK_STATUS(FuseBottleneckPairs(order));
         if (opt_fp16_ && opt_fuse_pw_ > 1 && opt_alias_cat_) CHECK_STATUS(FuseCv3IntoPairs(order));
     }
+    // what a layout operator could not decide on its own (a tensor of rank > 4 that exists only inside a fused chain) is decided now
+    for (const Step& st : order)
+        if (Layout* lay = dynamic_cast<Layout*>(st.layer)) CHECK_STATUS(lay->Final());
     if (opt_fp16_) {
         CHECK_STATUS(InsertOutputCasts(order));
         // every layer is asked NOW whether it has a kernel for the storage types it ended up with.  One that has none (a 3x3 conv
@@ -91,6 +96,7 @@ Status EngineImpl::CreatePipeline() {
     }
     plan_ = order;
     if (opt_alias_split_) CHECK_STATUS(AliasSplits());   // (first: a chunk that is a view stays one when its halves also feed a concat)
+    if (opt_alias_view_) CHECK_STATUS(AliasViews());
     if (opt_alias_cat_) CHECK_STATUS(AliasConcats());
     ResolveAliases();
     if (opt_detect_stream_) CHECK_STATUS(PlanDetectStream());
@@ -340,6 +346,33 @@ Status EngineImpl::FusePoolChains(std::vector<Step>& order) {
         a->SetOutputNodes({a->OutputNodes()[0], b->OutputNodes()[0], c->OutputNodes()[0]});
         p.Retire(j);
         p.Retire(k);
+    }
+    p.Compact();
+    return Status::kSuccess;
+}
+
+// A maximal run of layout operators (Tensor.permute / reshape / view / torch.transpose / squeeze / unsqueeze / contiguous) in which every
+// intermediate has exactly one reader and is not a graph output  ==>  ONE layout step at the last operator's slot that reads the run's root
+// input and carries the composed chain (layer/layout.h).  The intermediates never exist in memory, so they may have any rank (the raw YOLOv5
+// head's view -> permute -> view passes through rank 5).  A chain the algebra cannot serve as a whole is left as it was.
+Status EngineImpl::FuseLayoutChains(std::vector<Step>& order) {
+    Pass p(*this, order);
+    for (size_t i = 0; i < order.size(); ++i) {
+        Layout* head = p.At<Layout>(i);
+        if (!head || head->InputNodes().size() != 1 || order[i].op->outputs.size() != 1) continue;
+        std::vector<LayoutOp> ops = head->Chain();
+        std::vector<size_t> run(1, i);
+        for (;;) {
+            const pnnx::Operator* c = p.SoleConsumer(order[run.back()].op->outputs[0]);
+            Layout* next = c ? dynamic_cast<Layout*>(p.LayerOf(c)) : nullptr;
+            if (!next || c->inputs.size() != 1 || c->outputs.size() != 1 || next->InputNodes().size() != 1) break;
+            ops.insert(ops.end(), next->Chain().begin(), next->Chain().end());
+            run.push_back(p.index[c]);
+        }
+        if (run.size() < 2) continue;
+        Layout* last = dynamic_cast<Layout*>(order[run.back()].layer);
+        if (!last->TryChain(head->InputNodes()[0], ops)) continue;
+        for (size_t k = 0; k + 1 < run.size(); ++k) p.Retire(run[k], order[run[k]].op->outputs[0]);
     }
     p.Compact();
     return Status::kSuccess;
@@ -689,6 +722,36 @@ Status EngineImpl::AliasSplits() {
     return Status::kSuccess;
 }
 
+// A layout step whose plan is "view" (conv -> permute(0,2,3,1) -> view(N,-1,K): the bytes the conv wrote, in order): the output becomes an
+// alias of the WHOLE input buffer under its own shape, dense, and Layout::Forward finds it in place.  Conditions as in AliasSplits: neither side
+// is a graph input or output, the types match, the parent is dense (layout operators are not in HonoursPixelStride, so nothing hands them a
+// strided operand).  Otherwise the step is one permute_rows copy.
+Status EngineImpl::AliasViews() {
+    for (const Step& s : plan_) {
+        Layout* lay = dynamic_cast<Layout*>(s.layer);
+        if (!lay || !lay->IsView() || lay->InputNodes().size() != 1 || lay->OutputNodes().size() != 1 || s.op->outputs.size() != 1) continue;
+        TensorNode* in = lay->InputNodes()[0];
+        TensorNode* out = lay->OutputNodes()[0];
+        const pnnx::Operand* x = in->operand;
+        const pnnx::Operand* r = s.op->outputs[0];
+        // (fp32 fallbacks and output casts rebind a layer to shadow / staging tensors: those are not the file's operands and nothing aliases them)
+        if (!x || !r || tensor_nodes_[x->name] != in || tensor_nodes_[r->name] != out) continue;
+        if (input_tensor_nodes_.count(x->name) || output_tensor_nodes_.count(x->name) || output_tensor_nodes_.count(r->name)) continue;
+        if (aliases_.count(r->name) || dead_operands_.count(r->name) || dead_operands_.count(x->name)) continue;
+        if (in->tensor.GetDataType() != out->tensor.GetDataType() || in->tensor.NumElements() != out->tensor.NumElements()) continue;
+        // the parent is dense: it is no channel slice of another buffer (a view of a view is fine: that alias is whole and dense itself) and
+        // carries no pixel stride.  Today nothing hands a layout step a strided operand; this holds the rule if that ever changes
+        auto up = aliases_.find(x->name);
+        if (up != aliases_.end() && !up->second.whole) continue;
+        if (in->tensor.Shape().empty() || in->tensor.PixelStride() != in->tensor.Shape().back()) continue;
+        Alias a;
+        a.parent = in;
+        a.whole = true;
+        aliases_[r->name] = a;
+    }
+    return Status::kSuccess;
+}
+
 // After the alias passes a parent may itself be an alias (a conv output that feeds a chunk and a concat: the chunk's views hang off an operand
 // that lives in the concat buffer; a chunk of a chunk).  Every alias is re-pointed at its ROOT buffer with the summed channel offset, so that
 // EnsureArena binds views to allocated memory only and PlanArena's lifetimes count every reader against the buffer that is really read.
@@ -698,6 +761,8 @@ void EngineImpl::ResolveAliases() {
         for (size_t hops = 0; hops <= aliases_.size() && a.parent && a.parent->operand; ++hops) {
             auto up = aliases_.find(a.parent->operand->name);
             if (up == aliases_.end() || tensor_nodes_[up->first] != a.parent || &up->second == &a) break;
+            // (a channel slice of a view keeps the view's rows: the root may be the same bytes under another shape)
+            if (up->second.whole && !a.whole && a.ld == 0 && !a.parent->tensor.Shape().empty()) a.ld = a.parent->tensor.Shape().back();
             a.channel_offset += up->second.channel_offset;
             a.parent = up->second.parent;
         }

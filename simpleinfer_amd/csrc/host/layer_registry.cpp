@@ -20,6 +20,7 @@ SI_DECLARE_LAYER(Flatten)
 SI_DECLARE_LAYER(GroupNorm)
 SI_DECLARE_LAYER(HardSigmoid)
 SI_DECLARE_LAYER(HardSwish)
+SI_DECLARE_LAYER(Layout)
 SI_DECLARE_LAYER(LeakyReLU)
 SI_DECLARE_LAYER(Linear)
 SI_DECLARE_LAYER(MaxPool2d)
@@ -51,7 +52,9 @@ static std::map<std::string, LayerRegistryEntry>& Table() {
     // F.pixel_shuffle / F.pixel_unshuffle (one class, layer/pixel_shuffle.h) and nn.PReLU (layer/prelu.h); torch.chunk / torch.split /
     // Tensor.slice (one class, layer/slice.h); torch.mean / torch.sum / torch.amax / torch.amin (one class, layer/reduce.h); nn.ReLU6 / nn.Hardtanh /
     // torch.clamp / nn.Softplus / nn.Mish and their F.* spellings (one class, layer/param_activation.h: never folded into an epilogue); the
-    // functional spellings of the activations above, on the classes of their nn.* twins (they fuse as those do; F.tanh, like nn.Tanh, does not)
+    // functional spellings of the activations above, on the classes of their nn.* twins (they fuse as those do; F.tanh, like nn.Tanh, does not);
+    // Tensor.permute / torch.permute / Tensor.reshape / Tensor.view / torch.transpose / torch.squeeze / torch.unsqueeze / Tensor.contiguous (one
+    // class, layer/layout.h: the layout algebra of layout_plan.h decides between a view and one permute launch)
     static std::map<std::string, LayerRegistryEntry> table = {
         SI_ENTRY("nn.AdaptiveAvgPool2d", AdaptiveAvgPool2d),
         SI_ENTRY("nn.AvgPool2d", AvgPool2d),
@@ -117,6 +120,14 @@ static std::map<std::string, LayerRegistryEntry>& Table() {
         SI_ENTRY("F.hardswish", HardSwish),
         SI_ENTRY("F.leaky_relu", LeakyReLU),
         SI_ENTRY("F.tanh", Tanh),
+        SI_ENTRY("Tensor.permute", Layout),
+        SI_ENTRY("torch.permute", Layout),
+        SI_ENTRY("Tensor.reshape", Layout),
+        SI_ENTRY("Tensor.view", Layout),
+        SI_ENTRY("torch.transpose", Layout),
+        SI_ENTRY("torch.squeeze", Layout),
+        SI_ENTRY("torch.unsqueeze", Layout),
+        SI_ENTRY("Tensor.contiguous", Layout),
         SI_ENTRY("models.yolo.Detect", YoloDetect),
     };
     return table;

@@ -1260,6 +1260,79 @@ def split_channels_kernel_name(x_shape, widths, offsets=None, half=False, in_ld=
     return _native.hip().si_hip_split_channels_kernel_name(*(args + (1 if half else 0,))).decode()
 
 
+PERMUTE_FORMS = {"auto": 0, "rows": 1, "tile": 2, "elem": 3}
+LAYOUT_OPS = {"permute": 0, "reshape": 1, "view": 1, "transpose": 2, "squeeze": 3, "unsqueeze": 4, "contiguous": 5}
+
+
+def permute_desc(dims, in_stride, out_ld=None, form=0):
+    """SiPermuteDesc (include/si_permute.h): the output loop nest `dims`, outermost first, with the input element stride of every loop
+    dimension; out_ld defaults to the dense pitch dims[-1]"""
+    d = _native.SiPermuteDesc()
+    d.rank = len(dims)
+    for k in range(min(len(dims), 4)):
+        d.dims[k], d.in_stride[k] = int(dims[k]), int(in_stride[k])
+    d.out_ld = int(out_ld) if out_ld else (int(dims[-1]) if len(dims) else 0)
+    d.form = PERMUTE_FORMS.get(form, form)
+    return d
+
+
+def permute_ref(src, desc, out_ld=None, out_fill=0):
+    """numpy statement of the descriptor on the flat source array: [runs, out_ld] with out_fill where nothing is written"""
+    dims = [desc.dims[k] for k in range(desc.rank)]
+    st = [desc.in_stride[k] for k in range(desc.rank)]
+    idx = np.zeros(dims, np.int64)
+    for k, (n, s) in enumerate(zip(dims, st)):
+        idx += (np.arange(n, dtype=np.int64) * s).reshape([n if j == k else 1 for j in range(len(dims))])
+    runs = int(np.prod(dims[:-1], dtype=np.int64))
+    out = _full((runs, out_ld or desc.out_ld), src.dtype, out_fill)
+    out[:, :dims[-1]] = np.asarray(src).reshape(-1)[idx.reshape(runs, dims[-1])]
+    return out
+
+
+def permute(src, desc, half=False, form=None, src_off=0, out_off=0, out_fill=0.0):
+    """si_hip_permute_f32 / _f16 (half, or a float16 array): the flat array `src` is uploaded as it is and the kernel is handed the pointer
+    src_off elements into it; the destination is out_off + runs * out_ld elements pre-filled with out_fill (a value or a ByteFill), the kernel
+    writing from out_off on.  Returns the [runs, out_ld] rows behind out_off: what lies between two runs must still hold out_fill.  form: a
+    key of PERMUTE_FORMS to force, None: the descriptor's.  The array's bits travel as they are; under guard_bands() both buffers are banded."""
+    H = _native.hip()
+    src = np.ascontiguousarray(np.asarray(src).reshape(-1))
+    if half and src.dtype != np.float16:
+        src = src.astype(np.float16)
+    src = _float_storage(src)
+    half = src.dtype == np.float16
+    if form is not None:
+        desc.form = PERMUTE_FORMS.get(form, form)
+    runs = int(np.prod([desc.dims[k] for k in range(desc.rank - 1)], dtype=np.int64))
+    dx = DeviceBuffer.from_numpy(src)
+    dy = DeviceBuffer.from_numpy(_full((int(out_off) + runs * desc.out_ld,), src.dtype, out_fill), out=True)
+    px, py = dx.ptr + src.itemsize * int(src_off), dy.ptr + src.itemsize * int(out_off)
+    LAST_KERNEL_NAME["si_hip_permute"] = H.si_hip_permute_kernel_name(C.byref(desc), C.c_void_p(px), C.c_void_p(py), 1 if half else 0).decode()
+    fn, name = (H.si_hip_permute_f16, "si_hip_permute_f16") if half else (H.si_hip_permute_f32, "si_hip_permute_f32")
+    _chk(fn(C.byref(desc), px, py, None), name)
+    return dy.to_numpy((int(out_off) + runs * desc.out_ld,), src.dtype)[int(out_off):].reshape(runs, desc.out_ld)
+
+
+def permute_kernel_name(desc, half=False, src_align=256, dst_align=256) -> str:
+    """the form for buffers at these addresses (256: 16-byte aligned; "none": a descriptor the launch refuses)"""
+    return _native.hip().si_hip_permute_kernel_name(C.byref(desc), C.c_void_p(src_align), C.c_void_p(dst_align), 1 if half else 0).decode()
+
+
+def layout_plan(in_shape, ops, out_shape=None, in_ld=0):
+    """si_layout_plan (include/si_layout.h): the layout algebra over file-order shapes.  ops: [(name, args)], name a key of LAYOUT_OPS.  Returns
+    (status, view, dims, in_stride): status 0 / 3 kErrorShape / 5 kUnsupport; for a nest of more than 4 dimensions (5) dims still holds it."""
+    L = _native.host()
+    ia = lambda v: (C.c_int * max(len(v), 1))(*[int(t) for t in v])
+    kinds = [LAYOUT_OPS[k] for k, _ in ops]
+    args = [int(a) for _, aa in ops for a in (aa if isinstance(aa, (tuple, list)) else [aa])]
+    nargs = [len(aa) if isinstance(aa, (tuple, list)) else 1 for _, aa in ops]
+    nest = _native.SiLayoutNest()
+    out_shape = list(out_shape) if out_shape is not None else []
+    rc = L.si_layout_plan(len(in_shape), ia(in_shape), int(in_ld), len(ops), ia(kinds), ia(nargs), ia(args), len(out_shape), ia(out_shape),
+                          C.byref(nest))
+    r = min(nest.rank, len(nest.dims))
+    return rc, bool(nest.view), [nest.dims[k] for k in range(r)], [nest.in_stride[k] for k in range(r)]
+
+
 def flatten_nhwc(x, in_ld=None, in_c_off=0, in_fill=0.0, out_fill=None):
     """out_fill: as cat()"""
     H = _native.hip()

@@ -457,6 +457,57 @@ class PnnxBuilder:
         self._emit("Tensor.slice", self._opname("Tensor_slice"), [x], [out], params)
         return out
 
+    # the layout operators (layer/layout.h): pnnx's lines for the tensor methods it passes through
+    def _layout(self, typ: str, x: str, shape: Sequence[int], params) -> str:
+        out = self._new_operand(shape)
+        self._emit(typ, self._opname(typ.replace(".", "_")), [x], [out], params)
+        return out
+
+    def permute(self, x: str, dims: Sequence[int], functional: bool = False) -> str:
+        """Tensor.permute (torch.permute with functional=True): dims="""
+        shp = self.shapes[x]
+        dims = tuple(int(d) for d in dims)
+        assert sorted(d % len(shp) for d in dims) == list(range(len(shp))), (dims, shp)
+        return self._layout("torch.permute" if functional else "Tensor.permute", x, [shp[d] for d in dims], dict(dims=dims))
+
+    def _reshaped(self, typ: str, x: str, shape: Sequence[int]) -> str:
+        shape = tuple(int(s) for s in shape)
+        count = int(np.prod(self.shapes[x], dtype=np.int64))
+        known = int(np.prod([s for s in shape if s != -1], dtype=np.int64))
+        assert shape.count(-1) <= 1 and known > 0 and count % known == 0 and (-1 in shape or known == count), (self.shapes[x], shape)
+        return self._layout(typ, x, [count // known if s == -1 else s for s in shape], dict(shape=shape))
+
+    def reshape(self, x: str, shape: Sequence[int]) -> str:
+        """Tensor.reshape: shape=, one entry may be -1 (it is written as it is; the output operand carries the resolved shape)"""
+        return self._reshaped("Tensor.reshape", x, shape)
+
+    def view(self, x: str, shape: Sequence[int]) -> str:
+        """Tensor.view: shape=, as reshape"""
+        return self._reshaped("Tensor.view", x, shape)
+
+    def transpose(self, x: str, dim0: int, dim1: int) -> str:
+        """torch.transpose: dim0= dim1="""
+        shp = list(self.shapes[x])
+        shp[dim0], shp[dim1] = shp[dim1], shp[dim0]
+        return self._layout("torch.transpose", x, shp, dict(dim0=int(dim0), dim1=int(dim1)))
+
+    def squeeze(self, x: str, dim: int) -> str:
+        """torch.squeeze: dim= (a dimension that is not 1 stays, torch's rule)"""
+        shp = list(self.shapes[x])
+        if shp[dim] == 1:
+            del shp[dim % len(shp)]
+        return self._layout("torch.squeeze", x, shp, dict(dim=int(dim)))
+
+    def unsqueeze(self, x: str, dim: int) -> str:
+        """torch.unsqueeze: dim="""
+        shp = list(self.shapes[x])
+        shp.insert(dim if dim >= 0 else dim + len(shp) + 1, 1)
+        return self._layout("torch.unsqueeze", x, shp, dict(dim=int(dim)))
+
+    def contiguous(self, x: str) -> str:
+        """Tensor.contiguous: no parameters"""
+        return self._layout("Tensor.contiguous", x, self.shapes[x], {})
+
     def expression(self, expr: str, xs: Sequence[str], out_shape=None) -> str:
         out = self._new_operand(out_shape or self.shapes[xs[0]])
         self._emit("pnnx.Expression", self._opname("pnnx_expr"), list(xs), [out], dict(expr=expr))
@@ -933,6 +984,72 @@ def build_toy_ghost(batch: int = 2, size: int = 16, oup: int = 27, seed: int = 0
     x1 = b.relu(b.conv(x, init, 1))
     x2 = b.relu(b.conv(x1, init, 3, 1, 1, groups=init))
     b.output(b.slice(b.cat([x1, x2], 1), 1, 0, oup, 1))
+    return b
+
+
+def _toy_pyramid(b: PnnxBuilder, batch: int, size: int, c: int = 16, levels: int = 2) -> List[str]:
+    """a stem and `levels` stride-2 feature maps (size / 4, size / 8, ..) of c, 2c, .. channels"""
+    x = b.relu(b.conv(b.input((batch, 3, size, size)), c, 3, 2, 1))
+    feats = []
+    for lv in range(levels):
+        x = b.relu(b.conv(x, c << lv, 3, 2, 1))
+        feats.append(x)
+    return feats
+
+
+def build_toy_ssd_head(batch: int = 2, size: int = 32, num_classes: int = 3, anchors: int = 2, seed: int = 0) -> PnnxBuilder:
+    """An SSD / RetinaFace style head on two levels: loc and conf convs, each conv -> permute(0,2,3,1) -> view(N,-1,4 | K) -- the bytes the conv
+    wrote, in order --, cat(dim=1) over the levels, sigmoid on the scores, cat(dim=2): [N, anchors, 4 + K]."""
+    b = PnnxBuilder(seed)
+    locs, confs = [], []
+    for f in _toy_pyramid(b, batch, size):
+        locs.append(b.view(b.permute(b.conv(f, anchors * 4, 3, 1, 1), (0, 2, 3, 1)), (batch, -1, 4)))
+        confs.append(b.view(b.permute(b.conv(f, anchors * num_classes, 3, 1, 1), (0, 2, 3, 1)), (batch, -1, num_classes)))
+    b.output(b.cat([b.cat(locs, 1), b.sigmoid(b.cat(confs, 1))], 2))
+    return b
+
+
+def build_toy_anchorfree_head(batch: int = 2, size: int = 64, no: int = 32, seed: int = 0) -> PnnxBuilder:
+    """A YOLOX / YOLOv8 style head: per level a conv to `no` channels -> view(N, no, -1); cat(dim=2) over the levels -> permute(0,2,1):
+    [N, cells, no]."""
+    b = PnnxBuilder(seed)
+    rows = [b.view(b.conv(f, no, 1), (batch, no, -1)) for f in _toy_pyramid(b, batch, size)]
+    b.output(b.permute(b.cat(rows, 2), (0, 2, 1)))
+    return b
+
+
+def build_toy_yolov5_raw_head(batch: int = 2, size: int = 32, na: int = 3, no: int = 7, seed: int = 0) -> PnnxBuilder:
+    """A raw YOLOv5 export's head: per level conv to na * no channels -> view(N, na, no, H, W) -> permute(0,1,3,4,2) -> view(N, -1, no) (the
+    rank-5 route), sigmoid, cat(dim=1) over the levels: [N, na * cells, no]."""
+    b = PnnxBuilder(seed)
+    rows = []
+    for f in _toy_pyramid(b, batch, size):
+        y = b.conv(f, na * no, 1)
+        _, _, h, w = b.shapes[y]
+        y = b.view(b.permute(b.view(y, (batch, na, no, h, w)), (0, 1, 3, 4, 2)), (batch, -1, no))
+        rows.append(b.sigmoid(y))
+    b.output(b.cat(rows, 1))
+    return b
+
+
+def build_toy_view_classifier(batch: int = 2, size: int = 32, pool: int = 1, ncls: int = 10, flatten: bool = False, seed: int = 0) -> PnnxBuilder:
+    """conv stack -> adaptive average pool to (pool, pool) -> x.view(N, -1) -> nn.Linear.  pool=1: the view moves no byte; pool=2: a transpose
+    of [4, C] per image.  flatten=True writes torch.flatten in place of the view (the same model, for the A/B)."""
+    b = PnnxBuilder(seed)
+    x = _toy_pyramid(b, batch, size)[-1]
+    x = b.adaptive_avgpool(x, (pool, pool))
+    x = b.flatten(x) if flatten else b.view(x, (batch, -1))
+    b.output(b.linear(x, ncls))
+    return b
+
+
+def build_toy_channel_shuffle(batch: int = 2, size: int = 16, c: int = 24, groups: int = 3, seed: int = 0) -> PnnxBuilder:
+    """ShuffleNet's channel shuffle written out: two convs -> view(N, g, C / g, H, W) -> transpose(1, 2) -> view(N, C, H, W) -> 1x1 conv"""
+    b = PnnxBuilder(seed)
+    x = b.relu(b.conv(b.input((batch, 3, size, size)), 16, 3, 1, 1))
+    x = b.relu(b.conv(x, c, 3, 1, 1))
+    y = b.view(b.transpose(b.view(x, (batch, groups, c // groups, size, size)), 1, 2), (batch, c, size, size))
+    b.output(b.conv(y, c, 1))
     return b
 
 
