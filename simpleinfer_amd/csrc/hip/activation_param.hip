@@ -115,9 +115,8 @@ int check_desc(const SiParamActDesc* d) {
         default: return SI_E_BADARG;
     }
     // offsets, and with them the item counts (at most one item per element, c <= ld)
-    const uint64_t lim = 0x7fffffffull;
     const uint64_t ld = (uint64_t)(d->in_ld > d->out_ld ? d->in_ld : d->out_ld);
-    if ((uint64_t)d->pixels > lim || (uint64_t)d->pixels * ld > lim) return SI_E_UNSUPPORTED;
+    if ((uint64_t)d->pixels > SI_INDEX_LIMIT || (uint64_t)d->pixels * ld > SI_INDEX_LIMIT) return SI_E_UNSUPPORTED;
     return 0;
 }
 

@@ -186,8 +186,6 @@ __global__ __launch_bounds__(AP_THREADS) void avgpool2d_coop_kernel(AvgArgs a) {
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------
-inline bool aligned_to(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 // the rule's output size with either rounding; 0: `o` is neither
 bool out_size_ok(int64_t i, int64_t k, int64_t s, int64_t p, int64_t o) {
     const int64_t span = i + 2 * p - k;
@@ -223,23 +221,22 @@ int check_desc(const SiAvgPool2dDesc* d) {
     if (!d) return SI_E_BADARG;
     if (d->n <= 0 || d->ih <= 0 || d->iw <= 0 || d->c <= 0 || d->oh <= 0 || d->ow <= 0) return SI_E_BADARG;
     if (d->in_ld < d->c || d->out_ld < d->c) return SI_E_BADARG;
-    const uint64_t lim = 0x7fffffffull;
     if (!d->adaptive) {
         if (d->kh < 1 || d->kw < 1 || d->sh < 1 || d->sw < 1 || d->pt < 0 || d->pl < 0) return SI_E_BADARG;
         if (d->pt > d->kh / 2 || d->pl > d->kw / 2) return SI_E_UNSUPPORTED;
         if (!out_size_ok(d->ih, d->kh, d->sh, d->pt, d->oh) || !out_size_ok(d->iw, d->kw, d->sw, d->pl, d->ow)) return SI_E_BADARG;
     } else {
         // (j + 1) * i + o - 1 is computed in 32 bits on the device
-        if ((uint64_t)d->ih * d->oh + (uint64_t)d->oh > lim || (uint64_t)d->iw * d->ow + (uint64_t)d->ow > lim) return SI_E_UNSUPPORTED;
+        if ((uint64_t)d->ih * d->oh + (uint64_t)d->oh > SI_INDEX_LIMIT || (uint64_t)d->iw * d->ow + (uint64_t)d->ow > SI_INDEX_LIMIT) return SI_E_UNSUPPORTED;
     }
     if (d->n > 65535) return SI_E_UNSUPPORTED;
     const uint64_t in_rows = (uint64_t)d->n * d->ih, out_rows = (uint64_t)d->n * d->oh;   // < 2^47
-    if (in_rows > lim || out_rows > lim) return SI_E_UNSUPPORTED;
+    if (in_rows > SI_INDEX_LIMIT || out_rows > SI_INDEX_LIMIT) return SI_E_UNSUPPORTED;
     const uint64_t in_pix = in_rows * d->iw, out_pix = out_rows * d->ow;                    // < 2^62
-    if (in_pix > lim || out_pix > lim) return SI_E_UNSUPPORTED;
-    if (in_pix * (uint64_t)d->in_ld > lim || out_pix * (uint64_t)d->out_ld > lim) return SI_E_UNSUPPORTED;
+    if (in_pix > SI_INDEX_LIMIT || out_pix > SI_INDEX_LIMIT) return SI_E_UNSUPPORTED;
+    if (in_pix * (uint64_t)d->in_ld > SI_INDEX_LIMIT || out_pix * (uint64_t)d->out_ld > SI_INDEX_LIMIT) return SI_E_UNSUPPORTED;
     // the windowed form's item count and the cooperative form's chunk count (c <= ld: both fit once the offsets do)
-    if ((uint64_t)d->oh * d->ow * (uint64_t)d->c > lim) return SI_E_UNSUPPORTED;
+    if ((uint64_t)d->oh * d->ow * (uint64_t)d->c > SI_INDEX_LIMIT) return SI_E_UNSUPPORTED;
     return 0;
 }
 
@@ -249,13 +246,8 @@ bool cooperative(const SiAvgPool2dDesc* d) {
     return taps >= (int64_t)SI_ENV_INT("SI_AVGPOOL_COOP_TAPS", SI_AVGPOOL_COOP_TAPS);
 }
 
-// 16-byte channel vectors when c, both strides and both pointers allow it; single elements otherwise
 template <typename T>
-int vector_width(const SiAvgPool2dDesc* d, const void* in, const void* out) {
-    const int full = (int)(16 / sizeof(T));
-    const bool vec = d->c % full == 0 && d->in_ld % full == 0 && d->out_ld % full == 0 && aligned_to(in, 16) && aligned_to(out, 16);
-    return vec ? full : 1;
-}
+int vector_width(const SiAvgPool2dDesc* d, const void* in, const void* out) { return si_vector_width<T>(d->c, d->in_ld, d->out_ld, in, out); }
 
 template <typename T, int VW>
 int launch(const SiAvgPool2dDesc* d, const T* in, T* out, hipStream_t stream) {

@@ -377,8 +377,6 @@ __global__ __launch_bounds__(GN_THREADS) void groupnorm_slab_kernel(const GnArgs
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------
-inline bool aligned_to(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 int gcd_int(int a, int b) {
     while (b) {
         const int r = a % b;
@@ -396,10 +394,9 @@ int check_desc(const SiGroupNormDesc* d) {
     if (d->in_ld < d->c || d->out_ld < d->c) return SI_E_BADARG;
     if (d->act < SI_ACT_NONE || d->act > SI_ACT_LEAKYRELU) return SI_E_BADARG;
     if (!(d->eps >= 0.0f)) return SI_E_BADARG;
-    const uint64_t lim = 0x7fffffffull;
     const uint64_t pixels = (uint64_t)d->n * d->h * d->w;
-    if (pixels > lim) return SI_E_UNSUPPORTED;
-    if (pixels * (uint64_t)d->in_ld > lim || pixels * (uint64_t)d->out_ld > lim) return SI_E_UNSUPPORTED;
+    if (pixels > SI_INDEX_LIMIT) return SI_E_UNSUPPORTED;
+    if (pixels * (uint64_t)d->in_ld > SI_INDEX_LIMIT || pixels * (uint64_t)d->out_ld > SI_INDEX_LIMIT) return SI_E_UNSUPPORTED;
     if (d->n > 65535) return SI_E_UNSUPPORTED;
     if (d->c / d->groups > GN_MAX_GROUP_C) return SI_E_UNSUPPORTED;
     return 0;
@@ -437,7 +434,7 @@ int make_plan(const SiGroupNormDesc* d, const void* in, const void* out, GnPlan&
     const int cg = d->c / d->groups;
     const int P = d->h * d->w;
     pl.vw = 1;
-    if (d->c % full == 0 && d->in_ld % full == 0 && d->out_ld % full == 0 && aligned_to(in, 16) && aligned_to(out, 16) &&
+    if (d->c % full == 0 && d->in_ld % full == 0 && d->out_ld % full == 0 && si_aligned_to(in, 16) && si_aligned_to(out, 16) &&
         (uint64_t)cg / gcd_int(cg, full) * full <= (uint64_t)GN_MAX_GROUP_C)
         pl.vw = full;
     const int unit = pl.vw / gcd_int(cg, pl.vw);   // groups per whole number of vectors

@@ -93,8 +93,6 @@ __global__ __launch_bounds__(PAD_THREADS) void pad2d_kernel(PadArgs a) {
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------
-inline bool aligned_to(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 // everything that can be decided without a device: SI_E_BADARG / SI_E_UNSUPPORTED / 0
 int check_desc(const SiPad2dDesc* d) {
     if (!d) return SI_E_BADARG;
@@ -108,23 +106,17 @@ int check_desc(const SiPad2dDesc* d) {
     const int64_t mw = pl > pr ? pl : pr, mh = pt > pb ? pt : pb;
     if (d->mode == SI_PAD_REFLECT && (mw >= d->iw || mh >= d->ih)) return SI_E_UNSUPPORTED;
     if (d->mode == SI_PAD_CIRCULAR && (pl < 0 || pr < 0 || pt < 0 || pb < 0 || mw > d->iw || mh > d->ih)) return SI_E_UNSUPPORTED;
-    const uint64_t lim = 0x7fffffffull;
     if (d->n > 65535) return SI_E_UNSUPPORTED;
     const uint64_t in_rows = (uint64_t)d->n * d->ih, out_rows = (uint64_t)d->n * d->oh;   // < 2^47
-    if (in_rows > lim || out_rows > lim) return SI_E_UNSUPPORTED;
+    if (in_rows > SI_INDEX_LIMIT || out_rows > SI_INDEX_LIMIT) return SI_E_UNSUPPORTED;
     const uint64_t in_pix = in_rows * d->iw, out_pix = out_rows * d->ow;                    // < 2^62
-    if (in_pix > lim || out_pix > lim) return SI_E_UNSUPPORTED;
-    if (in_pix * (uint64_t)d->in_ld > lim || out_pix * (uint64_t)d->out_ld > lim) return SI_E_UNSUPPORTED;
+    if (in_pix > SI_INDEX_LIMIT || out_pix > SI_INDEX_LIMIT) return SI_E_UNSUPPORTED;
+    if (in_pix * (uint64_t)d->in_ld > SI_INDEX_LIMIT || out_pix * (uint64_t)d->out_ld > SI_INDEX_LIMIT) return SI_E_UNSUPPORTED;
     return 0;
 }
 
-// 16-byte channel vectors when c, both strides and both pointers allow it; single elements otherwise
 template <typename T>
-int vector_width(const SiPad2dDesc* d, const void* in, const void* out) {
-    const int full = (int)(16 / sizeof(T));
-    const bool vec = d->c % full == 0 && d->in_ld % full == 0 && d->out_ld % full == 0 && aligned_to(in, 16) && aligned_to(out, 16);
-    return vec ? full : 1;
-}
+int vector_width(const SiPad2dDesc* d, const void* in, const void* out) { return si_vector_width<T>(d->c, d->in_ld, d->out_ld, in, out); }
 
 template <typename T, int VW>
 int launch(const SiPad2dDesc* d, const T* in, T* out, unsigned fill, hipStream_t stream) {

@@ -119,9 +119,6 @@ __global__ __launch_bounds__(PM_THREADS) void permute_tile(TileArgs a) {
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------
-inline bool aligned_to(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
-constexpr uint64_t LIM = 0x7fffffffull;
 
 // the nest padded to four dimensions: extents, input strides (0 where the extent is 1), output strides
 struct Nest {
@@ -144,18 +141,18 @@ int check_permute(const SiPermuteDesc* d, Nest& n) {
         n.s[k] = 0;
         if (n.d[k] > 1) {
             const uint64_t st = (uint64_t)d->in_stride[k - pad];
-            if (st > LIM) return SI_E_UNSUPPORTED;
+            if (st > SI_INDEX_LIMIT) return SI_E_UNSUPPORTED;
             max_in += (uint64_t)(n.d[k] - 1) * st;   // < 2^62 per term, checked after every term
-            if (max_in > LIM) return SI_E_UNSUPPORTED;
+            if (max_in > SI_INDEX_LIMIT) return SI_E_UNSUPPORTED;
             n.s[k] = (unsigned)st;
         }
         if (k < 3) {
             runs *= n.d[k];
-            if (runs > LIM) return SI_E_UNSUPPORTED;
+            if (runs > SI_INDEX_LIMIT) return SI_E_UNSUPPORTED;
         }
     }
     if (n.d[3] == 1) n.s[3] = 1;   // (a run of one element is contiguous whatever its stride says)
-    if (runs * (uint64_t)d->out_ld > LIM) return SI_E_UNSUPPORTED;   // covers the item count: items <= runs * dims[rank-1]
+    if (runs * (uint64_t)d->out_ld > SI_INDEX_LIMIT) return SI_E_UNSUPPORTED;   // covers the item count: items <= runs * dims[rank-1]
     n.o[3] = 1;
     n.o[2] = (unsigned)d->out_ld;
     n.o[1] = n.o[2] * n.d[2];   // (<= runs * out_ld)
@@ -186,8 +183,8 @@ int pick_form(const SiPermuteDesc* d, const Nest& n) {
 template <typename T>
 bool rows_is_vec(const Nest& n, const void* src, const void* dst) {
     constexpr unsigned V = (unsigned)(16 / sizeof(T));
-    return n.d[3] % V == 0 && n.s[0] % V == 0 && n.s[1] % V == 0 && n.s[2] % V == 0 && n.o[2] % V == 0 && aligned_to(src, 16) &&
-           aligned_to(dst, 16);
+    return n.d[3] % V == 0 && n.s[0] % V == 0 && n.s[1] % V == 0 && n.s[2] % V == 0 && n.o[2] % V == 0 && si_aligned_to(src, 16) &&
+           si_aligned_to(dst, 16);
 }
 
 template <typename T>

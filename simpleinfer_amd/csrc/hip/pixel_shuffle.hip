@@ -250,8 +250,6 @@ __global__ __launch_bounds__(PS_THREADS) void pixel_shuffle_lds(PsArgs a) {
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------
-inline bool aligned_to(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 // everything that can be decided without a device: SI_E_BADARG / SI_E_UNSUPPORTED / 0
 int check_desc(const SiPixelShuffleDesc* d) {
     if (!d) return SI_E_BADARG;
@@ -264,13 +262,12 @@ int check_desc(const SiPixelShuffleDesc* d) {
         if (d->ih % r != 0 || d->iw % r != 0) return SI_E_BADARG;
         if ((int64_t)d->ic * rr != d->oc || (int64_t)d->oh * r != d->ih || (int64_t)d->ow * r != d->iw) return SI_E_BADARG;
     }
-    const uint64_t lim = 0x7fffffffull;
     if (d->n > 65535) return SI_E_UNSUPPORTED;
     const uint64_t in_rows = (uint64_t)d->n * d->ih, out_rows = (uint64_t)d->n * d->oh;   // < 2^47
-    if (in_rows > lim || out_rows > lim) return SI_E_UNSUPPORTED;
+    if (in_rows > SI_INDEX_LIMIT || out_rows > SI_INDEX_LIMIT) return SI_E_UNSUPPORTED;
     const uint64_t in_pix = in_rows * d->iw, out_pix = out_rows * d->ow;                    // < 2^62
-    if (in_pix > lim || out_pix > lim) return SI_E_UNSUPPORTED;
-    if (in_pix * (uint64_t)d->in_ld > lim || out_pix * (uint64_t)d->out_ld > lim) return SI_E_UNSUPPORTED;
+    if (in_pix > SI_INDEX_LIMIT || out_pix > SI_INDEX_LIMIT) return SI_E_UNSUPPORTED;
+    if (in_pix * (uint64_t)d->in_ld > SI_INDEX_LIMIT || out_pix * (uint64_t)d->out_ld > SI_INDEX_LIMIT) return SI_E_UNSUPPORTED;
     return 0;
 }
 
@@ -284,7 +281,7 @@ int lds_form(const SiPixelShuffleDesc* d, const void* in, const void* out) {
     const int D = d->inverse ? d->oc : d->ic, C = d->inverse ? d->ic : d->oc;
     const int deep_ld = d->inverse ? d->out_ld : d->in_ld, wide_ld = d->inverse ? d->in_ld : d->out_ld;
     const int deep_w = d->inverse ? d->ow : d->iw, wide_w = d->inverse ? d->iw : d->ow;
-    if (d->r < 2 || !aligned_to(in, 16) || !aligned_to(out, 16)) return 0;
+    if (d->r < 2 || !si_aligned_to(in, 16) || !si_aligned_to(out, 16)) return 0;
     if ((size_t)D * sizeof(T) * 8 > (size_t)PS_LDS_BYTES) return 0;   // a run is at least 8 pixels
     if (!side_ok(D, deep_ld, deep_w, VW) || !side_ok(C, wide_ld, wide_w, VW)) return 0;
     return C % VW == 0 ? VW : 1;

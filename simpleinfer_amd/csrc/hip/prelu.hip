@@ -41,21 +41,12 @@ __global__ __launch_bounds__(PRELU_THREADS) void prelu_kernel(const T* in, unsig
     }
 }
 
-inline bool aligned_to(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 // SI_E_BADARG / SI_E_UNSUPPORTED / 0, without a device
 int check_args(const void* in, size_t pixels, int c, int in_ld, int slope_count, const void* out, int out_ld) {
     if (!in || !out || pixels == 0 || c <= 0 || in_ld < c || out_ld < c) return SI_E_BADARG;
     if (slope_count != 1 && slope_count != c) return SI_E_BADARG;
-    const uint64_t lim = 0x7fffffffull;
-    if (pixels > lim || pixels * (uint64_t)in_ld > lim || pixels * (uint64_t)out_ld > lim) return SI_E_UNSUPPORTED;
+    if (pixels > SI_INDEX_LIMIT || pixels * (uint64_t)in_ld > SI_INDEX_LIMIT || pixels * (uint64_t)out_ld > SI_INDEX_LIMIT) return SI_E_UNSUPPORTED;
     return 0;
-}
-
-template <typename T>
-int vector_width(const void* in, int c, int in_ld, const void* out, int out_ld) {
-    const int full = (int)(16 / sizeof(T));
-    return c % full == 0 && in_ld % full == 0 && out_ld % full == 0 && aligned_to(in, 16) && aligned_to(out, 16) ? full : 1;
 }
 
 template <typename T>
@@ -66,7 +57,7 @@ int run(const T* in, size_t pixels, int c, int in_ld, const float* slope, int sl
     constexpr int full = (int)(16 / sizeof(T));
     hipStream_t s = (hipStream_t)stream;
     const int per_channel = slope_count == c && c > 1 ? 1 : 0;
-    if (vector_width<T>(in, c, in_ld, out, out_ld) == full) {
+    if (si_vector_width<T>(c, in_ld, out_ld, in, out) == full) {
         const int cv = c / full;
         const unsigned items = (unsigned)pixels * (unsigned)cv;
         hipLaunchKernelGGL((prelu_kernel<T, full>), dim3(si_grid_for((size_t)items)), dim3(PRELU_THREADS), 0, s, in, items, cv, in_ld, slope,
@@ -95,8 +86,8 @@ int si_hip_prelu_f16(const void* in, size_t pixels, int c, int in_ld, const floa
 
 const char* si_hip_prelu_kernel_name(const void* in, size_t pixels, int c, int in_ld, int slope_count, const void* out, int out_ld, int half) {
     if (check_args(in, pixels, c, in_ld, slope_count, out, out_ld) != 0) return "none";
-    if (half) return vector_width<_Float16>(in, c, in_ld, out, out_ld) > 1 ? "prelu_kernel<_Float16, 8>" : "prelu_kernel<_Float16, 1>";
-    return vector_width<float>(in, c, in_ld, out, out_ld) > 1 ? "prelu_kernel<float, 4>" : "prelu_kernel<float, 1>";
+    if (half) return si_vector_width<_Float16>(c, in_ld, out_ld, in, out) > 1 ? "prelu_kernel<_Float16, 8>" : "prelu_kernel<_Float16, 1>";
+    return si_vector_width<float>(c, in_ld, out_ld, in, out) > 1 ? "prelu_kernel<float, 4>" : "prelu_kernel<float, 1>";
 }
 
 }  // extern "C"

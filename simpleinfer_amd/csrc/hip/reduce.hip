@@ -264,8 +264,6 @@ __global__ __launch_bounds__(RD_COOP_THREADS) void reduce_col_coop_kernel(RdArgs
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------
-inline bool aligned_to(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 constexpr int kSpatial = SI_REDUCE_AXIS_N | SI_REDUCE_AXIS_H | SI_REDUCE_AXIS_W;
 
 // everything that can be decided without a device or a pointer: SI_E_BADARG / SI_E_UNSUPPORTED / 0
@@ -276,14 +274,13 @@ int check_desc(const SiReduceDesc* d) {
     const int oc = (d->axes & SI_REDUCE_AXIS_C) ? 1 : d->c;
     if (d->in_ld < d->c || d->out_ld < oc) return SI_E_BADARG;
     if ((d->axes & SI_REDUCE_AXIS_C) && (d->axes & kSpatial)) return SI_E_UNSUPPORTED;
-    const uint64_t lim = 0x7fffffffull;
     const uint64_t rows = (uint64_t)d->n * (uint64_t)d->h;   // < 2^62
-    if (rows > lim || rows * (uint64_t)d->w > lim) return SI_E_UNSUPPORTED;
+    if (rows > SI_INDEX_LIMIT || rows * (uint64_t)d->w > SI_INDEX_LIMIT) return SI_E_UNSUPPORTED;
     const uint64_t pix = rows * (uint64_t)d->w;
     const uint64_t opix = (uint64_t)((d->axes & SI_REDUCE_AXIS_N) ? 1 : d->n) * (uint64_t)((d->axes & SI_REDUCE_AXIS_H) ? 1 : d->h) *
                           (uint64_t)((d->axes & SI_REDUCE_AXIS_W) ? 1 : d->w);
     // offsets, and with them the grids: at most one workgroup per pixel, at most one lane per element (c <= ld)
-    if (pix * (uint64_t)d->in_ld > lim || opix * (uint64_t)d->out_ld > lim) return SI_E_UNSUPPORTED;
+    if (pix * (uint64_t)d->in_ld > SI_INDEX_LIMIT || opix * (uint64_t)d->out_ld > SI_INDEX_LIMIT) return SI_E_UNSUPPORTED;
     return 0;
 }
 
@@ -358,8 +355,8 @@ Form form_of(const SiReduceDesc* d) {
 template <typename T>
 int vector_width(const SiReduceDesc* d, const void* in, const void* out) {
     const int full = (int)(16 / sizeof(T));
-    bool vec = d->c % full == 0 && d->in_ld % full == 0 && aligned_to(in, 16);
-    if (d->axes != SI_REDUCE_AXIS_C) vec = vec && d->out_ld % full == 0 && aligned_to(out, 16);
+    bool vec = d->c % full == 0 && d->in_ld % full == 0 && si_aligned_to(in, 16);
+    if (d->axes != SI_REDUCE_AXIS_C) vec = vec && d->out_ld % full == 0 && si_aligned_to(out, 16);
     return vec ? full : 1;
 }
 

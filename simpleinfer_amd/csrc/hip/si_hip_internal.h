@@ -65,6 +65,20 @@ static inline hipError_t si_allow_dynamic_lds(Kern kern, size_t lds) {
     return e;
 }
 
+// ---- host-side preamble of the descriptor operators (pad2d, avgpool, softmax, reduce, ...) --------------------------------
+static inline bool si_aligned_to(const void* p, size_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
+
+// kernels index with 32-bit element offsets: a view whose last element lies beyond this is SI_E_UNSUPPORTED
+constexpr uint64_t SI_INDEX_LIMIT = 0x7fffffffull;
+
+// 16-byte channel vectors when c, both strides and both pointers allow it; single elements otherwise
+template <typename T>
+static inline int si_vector_width(int c, int in_ld, int out_ld, const void* in, const void* out) {
+    const int full = (int)(16 / sizeof(T));
+    const bool vec = c % full == 0 && in_ld % full == 0 && out_ld % full == 0 && si_aligned_to(in, 16) && si_aligned_to(out, 16);
+    return vec ? full : 1;
+}
+
 // fp32 -> storage type. For _Float16 the empty asm keeps the value opaque so the compiler cannot fold the multiply / add
 // that produced it into v_fma_mix{lo,hi}_f16 for some unrolled elements and not others: the fused form rounds once, the
 // separate form twice, and an image's result would then depend on which accumulator slot (= batch position) it used.

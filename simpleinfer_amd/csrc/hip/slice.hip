@@ -113,9 +113,6 @@ template <typename T>
 __global__ __launch_bounds__(SL_THREADS) void split_elem(SplitArgs a) { split_body<T, 1>(a); }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------
-inline bool aligned_to(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
-constexpr uint64_t LIM = 0x7fffffffull;
 
 // everything that can be decided without a device: SI_E_BADARG / SI_E_UNSUPPORTED / 0
 int check_slice(const SiSliceDesc* d) {
@@ -129,10 +126,10 @@ int check_slice(const SiSliceDesc* d) {
     }
     if (d->n > 65535) return SI_E_UNSUPPORTED;
     const uint64_t in_rows = (uint64_t)d->n * d->ih, out_rows = (uint64_t)d->on * d->oh;   // < 2^47
-    if (in_rows > LIM || out_rows > LIM) return SI_E_UNSUPPORTED;
+    if (in_rows > SI_INDEX_LIMIT || out_rows > SI_INDEX_LIMIT) return SI_E_UNSUPPORTED;
     const uint64_t in_pix = in_rows * d->iw, out_pix = out_rows * d->ow;                    // < 2^62
-    if (in_pix > LIM || out_pix > LIM) return SI_E_UNSUPPORTED;
-    if (in_pix * (uint64_t)d->in_ld > LIM || out_pix * (uint64_t)d->out_ld > LIM) return SI_E_UNSUPPORTED;
+    if (in_pix > SI_INDEX_LIMIT || out_pix > SI_INDEX_LIMIT) return SI_E_UNSUPPORTED;
+    if (in_pix * (uint64_t)d->in_ld > SI_INDEX_LIMIT || out_pix * (uint64_t)d->out_ld > SI_INDEX_LIMIT) return SI_E_UNSUPPORTED;
     return 0;
 }
 
@@ -140,8 +137,8 @@ int check_slice(const SiSliceDesc* d) {
 template <typename T>
 bool slice_is_vec(const SiSliceDesc* d, const void* src, const void* dst) {
     constexpr int V = (int)(16 / sizeof(T));
-    return d->step[3] == 1 && d->start[3] % V == 0 && d->oc % V == 0 && d->in_ld % V == 0 && d->out_ld % V == 0 && aligned_to(src, 16) &&
-           aligned_to(dst, 16);
+    return d->step[3] == 1 && d->start[3] % V == 0 && d->oc % V == 0 && d->in_ld % V == 0 && d->out_ld % V == 0 && si_aligned_to(src, 16) &&
+           si_aligned_to(dst, 16);
 }
 
 template <typename T>
@@ -174,14 +171,14 @@ int check_split(const void* src, size_t pixels, int c, int in_ld, int k, const i
     for (int i = 0; i < k; ++i) {
         if (!dsts[i] || widths[i] < 1 || offsets[i] < 0 || (int64_t)offsets[i] + widths[i] > (int64_t)c || out_lds[i] < widths[i]) return SI_E_BADARG;
     }
-    if (pixels > LIM || (uint64_t)pixels * (uint64_t)in_ld > LIM) return SI_E_UNSUPPORTED;
+    if (pixels > SI_INDEX_LIMIT || (uint64_t)pixels * (uint64_t)in_ld > SI_INDEX_LIMIT) return SI_E_UNSUPPORTED;
     for (int i0 = 0; i0 < k; i0 += SI_SPLIT_MAX) {
         uint64_t per_pixel = 0;
         for (int i = i0; i < k && i < i0 + SI_SPLIT_MAX; ++i) {
-            if ((uint64_t)pixels * (uint64_t)out_lds[i] > LIM) return SI_E_UNSUPPORTED;
+            if ((uint64_t)pixels * (uint64_t)out_lds[i] > SI_INDEX_LIMIT) return SI_E_UNSUPPORTED;
             per_pixel += (uint64_t)widths[i];
         }
-        if ((uint64_t)pixels * per_pixel > LIM) return SI_E_UNSUPPORTED;   // one launch's items
+        if ((uint64_t)pixels * per_pixel > SI_INDEX_LIMIT) return SI_E_UNSUPPORTED;   // one launch's items
     }
     return 0;
 }
@@ -190,9 +187,9 @@ int check_split(const void* src, size_t pixels, int c, int in_ld, int k, const i
 template <typename T>
 bool split_is_vec(const void* src, int in_ld, int k, const int* offsets, const int* widths, void* const* dsts, const int* out_lds) {
     constexpr int V = (int)(16 / sizeof(T));
-    if (in_ld % V != 0 || !aligned_to(src, 16)) return false;
+    if (in_ld % V != 0 || !si_aligned_to(src, 16)) return false;
     for (int i = 0; i < k; ++i)
-        if (offsets[i] % V != 0 || widths[i] % V != 0 || out_lds[i] % V != 0 || !aligned_to(dsts[i], 16)) return false;
+        if (offsets[i] % V != 0 || widths[i] % V != 0 || out_lds[i] % V != 0 || !si_aligned_to(dsts[i], 16)) return false;
     return true;
 }
 

@@ -305,20 +305,17 @@ template <typename T, int VW>
 __global__ __launch_bounds__(SM_THREADS) void softmax_strided_online_kernel(SmArgs a) { sm_strided<T, VW, true>(a); }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------
-inline bool aligned_to(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 // everything that can be decided without a device: SI_E_BADARG / SI_E_UNSUPPORTED / 0
 int check_desc(const SiSoftmaxDesc* d) {
     if (!d) return SI_E_BADARG;
     if (d->n <= 0 || d->h <= 0 || d->w <= 0 || d->c <= 0) return SI_E_BADARG;
     if (d->in_ld < d->c || d->out_ld < d->c) return SI_E_BADARG;
     if (d->axis < 0 || d->axis > 3 || (d->log != 0 && d->log != 1)) return SI_E_BADARG;
-    const uint64_t lim = 0x7fffffffull;
     const uint64_t rows = (uint64_t)d->n * (uint64_t)d->h;   // < 2^62
-    if (rows > lim || rows * (uint64_t)d->w > lim) return SI_E_UNSUPPORTED;
+    if (rows > SI_INDEX_LIMIT || rows * (uint64_t)d->w > SI_INDEX_LIMIT) return SI_E_UNSUPPORTED;
     const uint64_t pix = rows * (uint64_t)d->w;
     // offsets, and with them the grids: at most one workgroup per pixel, at most one lane per element (c <= ld)
-    if (pix * (uint64_t)d->in_ld > lim || pix * (uint64_t)d->out_ld > lim) return SI_E_UNSUPPORTED;
+    if (pix * (uint64_t)d->in_ld > SI_INDEX_LIMIT || pix * (uint64_t)d->out_ld > SI_INDEX_LIMIT) return SI_E_UNSUPPORTED;
     return 0;
 }
 
@@ -332,13 +329,8 @@ Form form_of(const SiSoftmaxDesc* d) {
     return axis_len(d) <= SI_SOFTMAX_STRIDED_REG_A ? kStrided : kStridedOnline;
 }
 
-// 16-byte channel vectors when c, both strides and both pointers allow it; single elements otherwise
 template <typename T>
-int vector_width(const SiSoftmaxDesc* d, const void* in, const void* out) {
-    const int full = (int)(16 / sizeof(T));
-    const bool vec = d->c % full == 0 && d->in_ld % full == 0 && d->out_ld % full == 0 && aligned_to(in, 16) && aligned_to(out, 16);
-    return vec ? full : 1;
-}
+int vector_width(const SiSoftmaxDesc* d, const void* in, const void* out) { return si_vector_width<T>(d->c, d->in_ld, d->out_ld, in, out); }
 
 template <typename T, int VW>
 int launch(const SiSoftmaxDesc* d, const T* in, T* out, hipStream_t stream) {

@@ -189,17 +189,14 @@ __global__ __launch_bounds__(256) void segment_labels_kernel(const T* __restrict
     labels[((size_t)img * d.oh + y) * d.ow + x] = (unsigned char)arg;
 }
 
-inline bool aligned_to(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 // everything that can be decided without a device: SI_E_BADARG / SI_E_UNSUPPORTED / 0
 int check_desc(const SiUpsampleDesc* d, bool out_is_labels) {
     if (!d) return SI_E_BADARG;
     if (d->n <= 0 || d->ih <= 0 || d->iw <= 0 || d->c <= 0 || d->oh <= 0 || d->ow <= 0) return SI_E_BADARG;
     if (d->in_ld < d->c || (!out_is_labels && d->out_ld < d->c)) return SI_E_BADARG;
     if (!std::isfinite(d->step_h) || !std::isfinite(d->step_w) || d->step_h < 0.0f || d->step_w < 0.0f) return SI_E_BADARG;
-    const uint64_t lim = 0x7fffffffull;
-    if ((uint64_t)d->n * d->ih * d->iw * (uint64_t)d->in_ld > lim) return SI_E_UNSUPPORTED;
-    if ((uint64_t)d->n * d->oh * d->ow * (uint64_t)(out_is_labels ? 1 : d->out_ld) > lim) return SI_E_UNSUPPORTED;
+    if ((uint64_t)d->n * d->ih * d->iw * (uint64_t)d->in_ld > SI_INDEX_LIMIT) return SI_E_UNSUPPORTED;
+    if ((uint64_t)d->n * d->oh * d->ow * (uint64_t)(out_is_labels ? 1 : d->out_ld) > SI_INDEX_LIMIT) return SI_E_UNSUPPORTED;
     if (d->n > 65535) return SI_E_UNSUPPORTED;
     if (out_is_labels && (d->c > 256 || d->oh > 65535)) return SI_E_UNSUPPORTED;
     return 0;
@@ -212,7 +209,7 @@ int vec_width(const SiUpsampleDesc* d, const void* in, const void* out) {
     for (int w : widths) {
         if (w <= 1) break;
         const size_t bytes = w * sizeof(T);
-        if (d->c % w == 0 && d->in_ld % w == 0 && d->out_ld % w == 0 && aligned_to(in, bytes) && aligned_to(out, bytes)) return w;
+        if (d->c % w == 0 && d->in_ld % w == 0 && d->out_ld % w == 0 && si_aligned_to(in, bytes) && si_aligned_to(out, bytes)) return w;
     }
     return 1;
 }

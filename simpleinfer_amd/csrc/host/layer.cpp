@@ -99,6 +99,12 @@ Status Layer::ValidateFloat() {
     return Status::kSuccess;
 }
 
+Status Layer::ValidateFloatLogged(const char* layer) {
+    if (Status::kSuccess == ValidateFloat()) return Status::kSuccess;
+    LOG(ERROR) << layer << "::Validate fail [unsupport input/output data type]";
+    return Status::kUnsupport;
+}
+
 si_stream_t Layer::Stream() const { return context_ ? context_->stream() : Context::Default()->stream(); }
 
 Status Layer::CheckHip(int rc, const char* what) const {

@@ -20,6 +20,7 @@
 #include "layer_registry.h"
 #include "logger.h"
 #include "pnnx/ir.h"
+#include "pnnx/param_read.h"
 #include "pnnx/pnnx_helper.h"
 #include "tensor.h"
 #include "tensor_node.h"
@@ -79,6 +80,8 @@ protected:
     Status ValidateFloat32();
     // fp32 or fp16 storage (the fp16 engine path, SetOption("fp16", 1)); inputs / outputs may differ at the graph boundary
     Status ValidateFloat();
+    // the same, logging "<layer>::Validate fail [unsupport input/output data type]" on refusal
+    Status ValidateFloatLogged(const char* layer);
     static bool IsHalf(const Tensor& t) { return t.GetDataType() == DataType::kFloat16; }
 
     si_stream_t Stream() const;
@@ -91,6 +94,41 @@ protected:
 
     // maps a C-ABI return code to Status, logging the HIP error string
     Status CheckHip(int rc, const char* what) const;
+
+    // ---- descriptor operators: entries si_hip_X_f32 / si_hip_X_f16 / si_hip_X_kernel_name(&desc, in, out, ..), include/si_*.h ----
+    // `make(in, out, desc)` fills the descriptor for a pair of tensors and says whether it could.
+    //
+    // The launch on device tensors: inputs and outputs of one storage type or kUnsupport, the descriptor or `bad_desc`, then the entry of
+    // the type.  (The f32 entries take float pointers, the f16 ones void pointers, slice / permute void pointers for both.)
+    template <typename Desc, typename I32, typename O32, typename I16, typename O16, typename Make>
+    Status LaunchDesc(int (*f32)(const Desc*, I32*, O32*, si_stream_t), int (*f16)(const Desc*, I16*, O16*, si_stream_t), const char* label,
+                      const Tensor& in, const Tensor& out, const Make& make, Status bad_desc = Status::kErrorShape) const {
+        if (IsHalf(in) != IsHalf(out)) return Status::kUnsupport;
+        Desc d;
+        if (!make(in, out, d)) return bad_desc;
+        const int rc = IsHalf(in) ? f16(&d, static_cast<I16*>(in.RawData()), static_cast<O16*>(out.RawData()), Stream())
+                                  : f32(&d, static_cast<I32*>(in.RawData()), static_cast<O32*>(out.RawData()), Stream());
+        return CheckHip(rc, label);
+    }
+    // Forward(input, output) of a layer that is nothing but that launch
+    template <typename F32, typename F16, typename Make>
+    Status ForwardDesc(F32 f32, F16 f16, const char* label, const Tensor& input, Tensor& output, const Make& make) {
+        const auto launch = [&](const Tensor& in, const Tensor& out) { return LaunchDesc(f32, f16, label, in, out, make); };
+        // (one captured reference: the std::function holds it in place, no allocation)
+        return RunOnDevice({&input}, {&output}, [&launch](const std::vector<Tensor>& in, std::vector<Tensor>& out) { return launch(in[0], out[0]); });
+    }
+    // KernelName(): the entry's answer for the bound nodes; `fallback` while nothing is bound or the descriptor cannot be made.
+    // `half_of_output`: the storage type asked about is the output's (the pools), not the input's.
+    template <typename Desc, typename Make>
+    const char* DescKernelName(const char* (*name)(const Desc*, const void*, const void*, int), const char* fallback, const Make& make,
+                               bool half_of_output = false) const {
+        if (input_tensor_nodes_.empty() || output_tensor_nodes_.empty()) return fallback;
+        const Tensor& in = input_tensor_nodes_[0]->tensor;
+        const Tensor& out = output_tensor_nodes_[0]->tensor;
+        Desc d;
+        if (!make(in, out, d)) return fallback;
+        return name(&d, in.RawData(), out.RawData(), IsHalf(half_of_output ? out : in) ? 1 : 0);
+    }
 
 protected:
     Context* context_ = nullptr;

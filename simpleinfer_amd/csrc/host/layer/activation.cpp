@@ -15,17 +15,14 @@ Status ActivationLayer::Init(const pnnx::Operator* op) { return Layer::Init(op);
 
 Status LeakyReLU::Init(const pnnx::Operator* op) {
     CHECK_STATUS(Layer::Init(op));
-    if (CheckParam(op, "negative_slope", 3)) act_param_ = op->params.at("negative_slope").f;
+    Get(op, "negative_slope", act_param_);   // (optional: the default stays)
     return Status::kSuccess;
 }
 
 Status ActivationLayer::Validate() {
     CHECK_STATUS(Layer::Validate());
     CHECK_STATUS(ValidateShape(1, 1));
-    if (Status::kSuccess != ValidateFloat()) {
-        LOG(ERROR) << label_ << "::Validate fail [unsupport input/output data type]";
-        return Status::kUnsupport;
-    }
+    CHECK_STATUS(ValidateFloatLogged(label_));
     if (!IsSameShape(input_tensor_nodes_[0]->tensor.Shape(), output_tensor_nodes_[0]->tensor.Shape())) {
         LOG(ERROR) << label_ << "::Validate fail [error input/output shape]";
         return Status::kErrorShape;

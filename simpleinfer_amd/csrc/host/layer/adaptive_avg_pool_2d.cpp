@@ -12,9 +12,8 @@ DEFINE_LAYER_REGISTRY(AdaptiveAvgPool2d);
 
 Status AdaptiveAvgPool2d::Init(const pnnx::Operator* op) {
     CHECK_STATUS(Layer::Init(op));
-    CHECK_BOOL(CheckParam(op, "output_size", 5));
-    const std::vector<int>& v = op->params.at("output_size").ai;
-    CHECK_BOOL(2 == v.size());
+    std::vector<int> v;
+    CHECK_BOOL(Get(op, "output_size", v) && 2 == v.size());
     output_h_ = v[0];
     output_w_ = v[1];
     return Status::kSuccess;
@@ -23,10 +22,7 @@ Status AdaptiveAvgPool2d::Init(const pnnx::Operator* op) {
 Status AdaptiveAvgPool2d::Validate() {
     CHECK_STATUS(Layer::Validate());
     CHECK_STATUS(ValidateShape(1, 1));
-    if (Status::kSuccess != ValidateFloat()) {
-        LOG(ERROR) << "AdaptiveAvgPool2d::Validate fail [unsupport input/output data type]";
-        return Status::kUnsupport;
-    }
+    CHECK_STATUS(ValidateFloatLogged("AdaptiveAvgPool2d"));
     return Status::kSuccess;
 }
 
@@ -35,13 +31,9 @@ Status AdaptiveAvgPool2d::Forward(const Tensor& input, Tensor& output) {
         Dims4 id, od;
         if (!GetDims4(in[0], id) || !GetDims4(out[0], od) || id.c != od.c || id.n != od.n) return Status::kErrorShape;
         if (IsHalf(in[0]) != IsHalf(out[0])) return Status::kUnsupport;
-        if (0 != id.h % od.h || 0 != id.w % od.w) {
-            // torch's general windows [floor(j i / o), ceil((j + 1) i / o)): include/si_pool.h (the divisible shapes keep the kernels below and their bits)
-            SiAvgPool2dDesc d;
-            MakeGeneralDesc(in[0], out[0], d);
-            if (IsHalf(in[0])) return CheckHip(si_hip_avgpool2d_f16(&d, in[0].RawData(), out[0].RawData(), Stream()), "AdaptiveAvgPool2d");
-            return CheckHip(si_hip_avgpool2d_f32(&d, in[0].Data<float>(), out[0].Data<float>(), Stream()), "AdaptiveAvgPool2d");
-        }
+        // torch's general windows [floor(j i / o), ceil((j + 1) i / o)): include/si_pool.h (the divisible shapes keep the kernels below and their bits)
+        if (0 != id.h % od.h || 0 != id.w % od.w)
+            return LaunchDesc(si_hip_avgpool2d_f32, si_hip_avgpool2d_f16, "AdaptiveAvgPool2d", in[0], out[0], MakeGeneralDesc);
         if (IsHalf(in[0]))
             return CheckHip(si_hip_adaptive_avgpool2d_f16(in[0].RawData(), id.n, id.h, id.w, id.c, in[0].PixelStride(),
                                                           out[0].RawData(), od.h, od.w, out[0].PixelStride(), Stream()),
@@ -64,13 +56,7 @@ bool AdaptiveAvgPool2d::MakeGeneralDesc(const Tensor& input, const Tensor& outpu
 
 // "avgpool" for the divisible shapes, as before; the instantiation of include/si_pool.h for the others
 const char* AdaptiveAvgPool2d::KernelName() const {
-    SiAvgPool2dDesc d;
-    if (input_tensor_nodes_.empty() || output_tensor_nodes_.empty() ||
-        !MakeGeneralDesc(input_tensor_nodes_[0]->tensor, output_tensor_nodes_[0]->tensor, d))
-        return "avgpool";
-    const Tensor& in = input_tensor_nodes_[0]->tensor;
-    const Tensor& out = output_tensor_nodes_[0]->tensor;
-    return si_hip_avgpool2d_kernel_name(&d, in.RawData(), out.RawData(), IsHalf(out) ? 1 : 0);
+    return DescKernelName(si_hip_avgpool2d_kernel_name, "avgpool", MakeGeneralDesc, true);
 }
 
 }  // namespace SimpleInfer

@@ -9,28 +9,24 @@ DEFINE_LAYER_REGISTRY(AvgPool2d);
 // A missing key is kFail; what the file asks for and this layer does not do is left for Validate (kUnsupport).
 Status AvgPool2d::Init(const pnnx::Operator* op) {
     CHECK_STATUS(Layer::Init(op));
-    CHECK_BOOL(CheckParam(op, "ceil_mode", 1));
-    ceil_mode_ = op->params.at("ceil_mode").b;
-    CHECK_BOOL(CheckParam(op, "count_include_pad", 1));
-    count_include_pad_ = op->params.at("count_include_pad").b;
+    CHECK_BOOL(Get(op, "ceil_mode", ceil_mode_));
+    CHECK_BOOL(Get(op, "count_include_pad", count_include_pad_));
 
     struct IntPair { const char* key; int* a; int* b; };
     const IntPair pairs[] = {{"kernel_size", &kernel_h_, &kernel_w_}, {"stride", &stride_h_, &stride_w_}, {"padding", &padding_h_, &padding_w_}};
     for (const IntPair& p : pairs) {
-        CHECK_BOOL(CheckParam(op, p.key, 5));
-        const std::vector<int>& v = op->params.at(p.key).ai;
-        CHECK_BOOL(2 == v.size());
+        std::vector<int> v;
+        CHECK_BOOL(Get(op, p.key, v) && 2 == v.size());
         *p.a = v[0];
         *p.b = v[1];
     }
     // an int, or None (type 0)
-    CHECK_BOOL(op->params.count("divisor_override") > 0);
+    CHECK_BOOL(FindParam(op, "divisor_override") != nullptr);
     has_divisor_override_ = false;
     divisor_override_ = 0;
-    if (0 != op->params.at("divisor_override").type) {
-        CHECK_BOOL(CheckParam(op, "divisor_override", 2));
+    if (!IsNone(op, "divisor_override")) {
+        CHECK_BOOL(Get(op, "divisor_override", divisor_override_));
         has_divisor_override_ = true;
-        divisor_override_ = op->params.at("divisor_override").i;
     }
     return Status::kSuccess;
 }
@@ -46,10 +42,7 @@ int AvgPool2d::OutSize(int i, int k, int s, int p, bool ceil_mode) {
 Status AvgPool2d::Validate() {
     CHECK_STATUS(Layer::Validate());
     CHECK_STATUS(ValidateShape(1, 1));
-    if (Status::kSuccess != ValidateFloat()) {
-        LOG(ERROR) << "AvgPool2d::Validate fail [unsupport input/output data type]";
-        return Status::kUnsupport;
-    }
+    CHECK_STATUS(ValidateFloatLogged("AvgPool2d"));
     if (kernel_h_ < 1 || kernel_w_ < 1 || stride_h_ < 1 || stride_w_ < 1 || padding_h_ < 0 || padding_w_ < 0) {
         LOG(ERROR) << "AvgPool2d::Validate fail [kernel_size and stride must be positive, padding non-negative]";
         return Status::kFail;
@@ -93,23 +86,13 @@ bool AvgPool2d::MakeDesc(const Tensor& input, const Tensor& output, SiAvgPool2dD
 
 Status AvgPool2d::Forward(const Tensor& input, Tensor& output) {
     return RunOnDevice({&input}, {&output}, [this](const std::vector<Tensor>& in, std::vector<Tensor>& out) {
-        if (IsHalf(in[0]) != IsHalf(out[0])) return Status::kUnsupport;
         if (has_divisor_override_ && 0 == divisor_override_) return Status::kUnsupport;
-        SiAvgPool2dDesc d;
-        if (!MakeDesc(in[0], out[0], d)) return Status::kErrorShape;
-        if (IsHalf(in[0])) return CheckHip(si_hip_avgpool2d_f16(&d, in[0].RawData(), out[0].RawData(), Stream()), "AvgPool2d");
-        return CheckHip(si_hip_avgpool2d_f32(&d, in[0].Data<float>(), out[0].Data<float>(), Stream()), "AvgPool2d");
+        return LaunchDesc(si_hip_avgpool2d_f32, si_hip_avgpool2d_f16, "AvgPool2d", in[0], out[0], [this](auto&... a) { return MakeDesc(a...); });
     });
 }
 
 const char* AvgPool2d::KernelName() const {
-    SiAvgPool2dDesc d;
-    if (input_tensor_nodes_.empty() || output_tensor_nodes_.empty() ||
-        !MakeDesc(input_tensor_nodes_[0]->tensor, output_tensor_nodes_[0]->tensor, d))
-        return "avgpool2d_kernel";
-    const Tensor& in = input_tensor_nodes_[0]->tensor;
-    const Tensor& out = output_tensor_nodes_[0]->tensor;
-    return si_hip_avgpool2d_kernel_name(&d, in.RawData(), out.RawData(), IsHalf(out) ? 1 : 0);
+    return DescKernelName(si_hip_avgpool2d_kernel_name, "avgpool2d_kernel", [this](auto&... a) { return MakeDesc(a...); }, true);
 }
 
 }  // namespace SimpleInfer

@@ -8,23 +8,11 @@ namespace SimpleInfer {
 
 DEFINE_LAYER_REGISTRY(BatchNorm2d);
 
-static bool ReadVec(const pnnx::Operator* op, const char* key, std::vector<float>& dst) {
-    if (!CheckAttr(op, key, 1)) return false;
-    const pnnx::Attribute& a = op->attrs.at(key);
-    if (1 != a.shape.size() || a.data.size() != (size_t)a.shape[0] * sizeof(float)) return false;
-    dst.resize(a.shape[0]);
-    memcpy(dst.data(), a.data.data(), a.data.size());
-    return true;
-}
-
 Status BatchNorm2d::Init(const pnnx::Operator* op) {
     CHECK_STATUS(Layer::Init(op));
-    CHECK_BOOL(CheckParam(op, "eps", 3));
-    eps_ = op->params.at("eps").f;
-    CHECK_BOOL(CheckParam(op, "num_features", 2));
-    num_features_ = op->params.at("num_features").i;
-    CHECK_BOOL(CheckParam(op, "affine", 1));
-    use_affine_ = op->params.at("affine").b;
+    CHECK_BOOL(Get(op, "eps", eps_));
+    CHECK_BOOL(Get(op, "num_features", num_features_));
+    CHECK_BOOL(Get(op, "affine", use_affine_));
     CHECK_BOOL(ReadVec(op, "running_mean", running_mean_));
     CHECK_BOOL(ReadVec(op, "running_var", running_var_));
     CHECK_BOOL(ReadVec(op, "weight", weight_));
@@ -43,10 +31,7 @@ Status BatchNorm2d::Validate() {
     CHECK_STATUS(Layer::Validate());
     CHECK_STATUS(ValidateShape(1, 1));
     // fp16 storage: accepted here so that the engine can run the layer in fp32 between casts (HalfStorageOk says it has no fp16 kernel)
-    if (Status::kSuccess != ValidateFloat()) {
-        LOG(ERROR) << "BatchNorm2d::Validate fail [unsupport input/output data type]";
-        return Status::kUnsupport;
-    }
+    CHECK_STATUS(ValidateFloatLogged("BatchNorm2d"));
     if (!IsSameShape(input_tensor_nodes_[0]->tensor.Shape(), output_tensor_nodes_[0]->tensor.Shape())) {
         LOG(ERROR) << "BatchNorm2d::Validate fail [error input/output shape]";
         return Status::kErrorShape;

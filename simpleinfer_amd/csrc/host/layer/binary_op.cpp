@@ -10,8 +10,8 @@ DEFINE_LAYER_REGISTRY(BinaryOp);
 
 Status BinaryOp::Init(const pnnx::Operator* op) {
     CHECK_STATUS(Layer::Init(op));
-    CHECK_BOOL(CheckParam(op, "0", 2));
-    const int code = op->params.at("0").i;
+    int code = 0, scalar_form = 0;
+    CHECK_BOOL(Get(op, "0", code));
     switch (code) {
         case 0: case 1: case 2: case 3: case 6: case 7: case 8: case 9: case 10: case 11:
             binary_op_type_ = static_cast<BinaryOpType>(code);
@@ -21,11 +21,10 @@ Status BinaryOp::Init(const pnnx::Operator* op) {
             return Status::kUnsupport;
     }
     with_scalar_ = false;
-    if (CheckParam(op, "1", 2) && op->params.at("1").i != 0) {
+    if (Get(op, "1", scalar_form) && scalar_form != 0) {
         // scalar operand form (expand_expression.cpp:206-236): "1" = with_scalar, "2" = the literal as a float
-        CHECK_BOOL(CheckParam(op, "2", 3));
+        CHECK_BOOL(Get(op, "2", scalar_));
         with_scalar_ = true;
-        scalar_ = op->params.at("2").f;
     }
     return Status::kSuccess;
 }

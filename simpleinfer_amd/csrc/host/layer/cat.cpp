@@ -10,8 +10,7 @@ DEFINE_LAYER_REGISTRY(Cat);
 
 Status Cat::Init(const pnnx::Operator* op) {
     CHECK_STATUS(Layer::Init(op));
-    CHECK_BOOL(CheckParam(op, "dim", 2));
-    dim_ = op->params.at("dim").i;
+    CHECK_BOOL(Get(op, "dim", dim_));
     return Status::kSuccess;
 }
 

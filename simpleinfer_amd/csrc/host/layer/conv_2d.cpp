@@ -280,10 +280,7 @@ Status Conv2d::Deinit() {
 Status Conv2d::Validate() {
     CHECK_STATUS(Layer::Validate());
     CHECK_STATUS(ValidateShape(1, 1));
-    if (Status::kSuccess != ValidateFloat()) {
-        LOG(ERROR) << "Conv2d::Validate fail [unsupport input/output data type]";
-        return Status::kUnsupport;
-    }
+    CHECK_STATUS(ValidateFloatLogged("Conv2d"));
     return Status::kSuccess;
 }
 

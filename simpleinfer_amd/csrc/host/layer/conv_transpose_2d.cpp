@@ -80,10 +80,7 @@ Status ConvTranspose2d::Deinit() {
 Status ConvTranspose2d::Validate() {
     CHECK_STATUS(Layer::Validate());
     CHECK_STATUS(ValidateShape(1, 1));
-    if (Status::kSuccess != ValidateFloat()) {
-        LOG(ERROR) << "ConvTranspose2d::Validate fail [unsupport input/output data type]";
-        return Status::kUnsupport;
-    }
+    CHECK_STATUS(ValidateFloatLogged("ConvTranspose2d"));
     if (groups_ != 1) {
         LOG(ERROR) << "ConvTranspose2d::Validate fail [groups " << groups_ << ": grouped / depthwise transposed convolution is not supported]";
         return Status::kUnsupport;

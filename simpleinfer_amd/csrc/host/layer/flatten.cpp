@@ -9,20 +9,15 @@ DEFINE_LAYER_REGISTRY(Flatten);
 
 Status Flatten::Init(const pnnx::Operator* op) {
     CHECK_STATUS(Layer::Init(op));
-    CHECK_BOOL(CheckParam(op, "start_dim", 2));
-    start_dim_ = op->params.at("start_dim").i;
-    CHECK_BOOL(CheckParam(op, "end_dim", 2));
-    end_dim_ = op->params.at("end_dim").i;
+    CHECK_BOOL(Get(op, "start_dim", start_dim_));
+    CHECK_BOOL(Get(op, "end_dim", end_dim_));
     return Status::kSuccess;
 }
 
 Status Flatten::Validate() {
     CHECK_STATUS(Layer::Validate());
     CHECK_STATUS(ValidateShape(1, 1));
-    if (Status::kSuccess != ValidateFloat()) {
-        LOG(ERROR) << "Flatten::Validate fail [unsupport input/output data type]";
-        return Status::kUnsupport;
-    }
+    CHECK_STATUS(ValidateFloatLogged("Flatten"));
     return Status::kSuccess;
 }
 

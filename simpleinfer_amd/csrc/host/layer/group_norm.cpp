@@ -6,34 +6,19 @@ namespace SimpleInfer {
 
 DEFINE_LAYER_REGISTRY(GroupNorm);
 
-static bool ReadVec(const pnnx::Operator* op, const char* key, std::vector<float>& dst) {
-    if (!CheckAttr(op, key, 1)) return false;
-    const pnnx::Attribute& a = op->attrs.at(key);
-    if (1 != a.shape.size() || a.data.size() != (size_t)a.shape[0] * sizeof(float)) return false;
-    dst.resize(a.shape[0]);
-    memcpy(dst.data(), a.data.data(), a.data.size());
-    return true;
-}
-
 // nn.GroupNorm: num_groups, num_channels, eps, affine (+ weight, bias of shape (C) when affine);
 // nn.InstanceNorm2d: num_features, eps, affine, track_running_stats (+ weight, bias when affine).  A missing key is kFail.
 Status GroupNorm::Init(const pnnx::Operator* op) {
     CHECK_STATUS(Layer::Init(op));
-    CHECK_BOOL(CheckParam(op, "eps", 3));
-    eps_ = op->params.at("eps").f;
-    CHECK_BOOL(CheckParam(op, "affine", 1));
-    use_affine_ = op->params.at("affine").b;
+    CHECK_BOOL(Get(op, "eps", eps_));
+    CHECK_BOOL(Get(op, "affine", use_affine_));
     if (op->type == "nn.InstanceNorm2d") {
-        CHECK_BOOL(CheckParam(op, "num_features", 2));
-        num_channels_ = op->params.at("num_features").i;
+        CHECK_BOOL(Get(op, "num_features", num_channels_));
         num_groups_ = 0;
-        CHECK_BOOL(CheckParam(op, "track_running_stats", 1));
-        track_running_stats_ = op->params.at("track_running_stats").b;
+        CHECK_BOOL(Get(op, "track_running_stats", track_running_stats_));
     } else {
-        CHECK_BOOL(CheckParam(op, "num_groups", 2));
-        num_groups_ = op->params.at("num_groups").i;
-        CHECK_BOOL(CheckParam(op, "num_channels", 2));
-        num_channels_ = op->params.at("num_channels").i;
+        CHECK_BOOL(Get(op, "num_groups", num_groups_));
+        CHECK_BOOL(Get(op, "num_channels", num_channels_));
         CHECK_BOOL(num_groups_ > 0);
     }
     CHECK_BOOL(num_channels_ > 0 && eps_ >= 0.0f);
@@ -56,10 +41,7 @@ Status GroupNorm::Deinit() {
 Status GroupNorm::Validate() {
     CHECK_STATUS(Layer::Validate());
     CHECK_STATUS(ValidateShape(1, 1));
-    if (Status::kSuccess != ValidateFloat()) {
-        LOG(ERROR) << "GroupNorm::Validate fail [unsupport input/output data type]";
-        return Status::kUnsupport;
-    }
+    CHECK_STATUS(ValidateFloatLogged("GroupNorm"));
     if (track_running_stats_) {
         LOG(ERROR) << "GroupNorm::Validate fail [InstanceNorm2d with track_running_stats=True normalises with stored statistics in eval mode: "
                       "that is a BatchNorm, not this kernel]";
@@ -135,13 +117,7 @@ Status GroupNorm::Forward(const Tensor& input, Tensor& output) {
 }
 
 const char* GroupNorm::KernelName() const {
-    SiGroupNormDesc d;
-    if (input_tensor_nodes_.empty() || output_tensor_nodes_.empty() ||
-        !MakeDesc(input_tensor_nodes_[0]->tensor, output_tensor_nodes_[0]->tensor, d))
-        return "groupnorm";
-    const Tensor& in = input_tensor_nodes_[0]->tensor;
-    const Tensor& out = output_tensor_nodes_[0]->tensor;
-    return si_hip_groupnorm_kernel_name(&d, in.RawData(), out.RawData(), IsHalf(in) ? 1 : 0);
+    return DescKernelName(si_hip_groupnorm_kernel_name, "groupnorm", [this](auto&... a) { return MakeDesc(a...); });
 }
 
 // per element: the Welford update (subtract, multiply-add, subtract, multiply-add) and the normalise (subtract, multiply, add)
@@ -149,8 +125,5 @@ double GroupNorm::Flops() const {
     if (input_tensor_nodes_.empty()) return 0.0;
     return 9.0 * (double)input_tensor_nodes_[0]->tensor.NumElements();
 }
-
-// fp16 in and out run the fp16 kernel directly; a mixed pair does not exist for this layer
-bool GroupNorm::HalfStorageOk(std::string& why) const { return Layer::HalfStorageOk(why); }
 
 }  // namespace SimpleInfer

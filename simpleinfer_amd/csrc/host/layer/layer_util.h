@@ -2,8 +2,13 @@
 #ifndef SIMPLE_INFER_SRC_LAYER_UTIL_H_
 #define SIMPLE_INFER_SRC_LAYER_UTIL_H_
 
+#include <cstring>
+#include <sstream>
+#include <string>
 #include <vector>
 
+#include "pnnx/ir.h"
+#include "pnnx/pnnx_helper.h"
 #include "si_hip.h"
 #include "tensor.h"
 
@@ -30,6 +35,33 @@ inline bool GetPixelsChannels(const Tensor& t, size_t& pixels, int& c) {
     pixels = 1;
     for (size_t i = 0; i + 1 < s.size(); ++i) pixels *= (size_t)s[i];
     return c > 0 && pixels > 0;
+}
+
+// rank 4: NHWC; rank 2 [N, F]: [N, 1, 1, F]; no other rank
+static inline bool NhwcDims(const Tensor& t, int d[4]) {
+    const std::vector<int>& s = t.Shape();
+    if (s.size() != 4 && s.size() != 2) return false;
+    const bool r4 = s.size() == 4;
+    d[0] = s[0]; d[1] = r4 ? s[1] : 1; d[2] = r4 ? s[2] : 1; d[3] = s.back();
+    return d[0] > 0 && d[1] > 0 && d[2] > 0 && d[3] > 0;
+}
+
+// "2x3x4" for the log messages; TupleString: "(2,3,4)"
+static inline std::string ShapeString(const std::vector<int>& s, const char* sep = "x") {
+    std::ostringstream os;
+    for (size_t i = 0; i < s.size(); ++i) os << (i ? sep : "") << s[i];
+    return os.str();
+}
+static inline std::string TupleString(const std::vector<int>& s) { return "(" + ShapeString(s, ",") + ")"; }
+
+// a rank-1 fp32 attribute (weights, statistics) into a vector
+static inline bool ReadVec(const pnnx::Operator* op, const char* key, std::vector<float>& dst) {
+    if (!CheckAttr(op, key, 1)) return false;
+    const pnnx::Attribute& a = op->attrs.at(key);
+    if (1 != a.shape.size() || a.data.size() != (size_t)a.shape[0] * sizeof(float)) return false;
+    dst.resize(a.shape[0]);
+    memcpy(dst.data(), a.data.data(), a.data.size());
+    return true;
 }
 
 // HBM buffer for layer parameters (weights, bias, grids): uploaded once, freed with the layer.

@@ -1,23 +1,10 @@
 #include "layout.h"
 
 #include <cstring>
-#include <sstream>
 
 namespace SimpleInfer {
 
 DEFINE_LAYER_REGISTRY(Layout);
-
-namespace {
-
-std::string ShapeString(const std::vector<int>& s) {
-    std::ostringstream os;
-    os << "(";
-    for (size_t i = 0; i < s.size(); ++i) os << (i ? "," : "") << s[i];
-    os << ")";
-    return os.str();
-}
-
-}  // namespace
 
 // A missing or mistyped key is kFail; values the rule does not allow are left for Validate, which knows the shape.
 Status Layout::Init(const pnnx::Operator* op) {
@@ -28,22 +15,21 @@ Status Layout::Init(const pnnx::Operator* op) {
     const std::string& t = op->type;
     if (t == "Tensor.permute" || t == "torch.permute") {
         own_.kind = LayoutOp::kPermute;
-        CHECK_BOOL(CheckParam(op, "dims", 5));
-        own_.args = op->params.at("dims").ai;
+        CHECK_BOOL(Get(op, "dims", own_.args));
     } else if (t == "Tensor.reshape" || t == "Tensor.view") {
         own_.kind = LayoutOp::kReshape;
         if (op->inputs.size() > 1) return Status::kSuccess;   // (the shape as an operand: Validate refuses it with the reason)
-        CHECK_BOOL(CheckParam(op, "shape", 5));
-        own_.args = op->params.at("shape").ai;
+        CHECK_BOOL(Get(op, "shape", own_.args));
     } else if (t == "torch.transpose") {
         own_.kind = LayoutOp::kTranspose;
-        CHECK_BOOL(CheckParam(op, "dim0", 2));
-        CHECK_BOOL(CheckParam(op, "dim1", 2));
-        own_.args = {op->params.at("dim0").i, op->params.at("dim1").i};
+        int dim0 = 0, dim1 = 0;
+        CHECK_BOOL(Get(op, "dim0", dim0) && Get(op, "dim1", dim1));
+        own_.args = {dim0, dim1};
     } else if (t == "torch.squeeze" || t == "torch.unsqueeze") {
         own_.kind = t == "torch.squeeze" ? LayoutOp::kSqueeze : LayoutOp::kUnsqueeze;
-        CHECK_BOOL(CheckParam(op, "dim", 2));
-        own_.args = {op->params.at("dim").i};
+        int dim = 0;
+        CHECK_BOOL(Get(op, "dim", dim));
+        own_.args = {dim};
     } else {
         own_.kind = LayoutOp::kIdentity;   // Tensor.contiguous
     }
@@ -109,7 +95,7 @@ Status Layout::Validate() {
                    << "at the file's batch only]";
         return Status::kUnsupport;
     }
-    LOG(ERROR) << "Layout::Validate fail [" << name << ": " << final_why_ << "; input " << ShapeString(FileShape(in)) << "]";
+    LOG(ERROR) << "Layout::Validate fail [" << name << ": " << final_why_ << "; input " << TupleString(FileShape(in)) << "]";
     return s;
 }
 
@@ -166,11 +152,7 @@ Status Layout::Forward(const Tensor& input, Tensor& output) {
         if (IsHalf(in[0]) != IsHalf(out[0])) return Status::kUnsupport;
         // already in place: the engine pointed the output at the input's buffer (EngineImpl::AliasViews)
         if (plan_.view && in[0].RawData() && in[0].RawData() == out[0].RawData()) return Status::kSuccess;
-        SiPermuteDesc d;
-        if (!Desc(in[0], out[0], d)) return Status::kUnsupport;
-        const int rc = IsHalf(in[0]) ? si_hip_permute_f16(&d, in[0].RawData(), out[0].RawData(), Stream())
-                                     : si_hip_permute_f32(&d, in[0].RawData(), out[0].RawData(), Stream());
-        return CheckHip(rc, "Layout");
+        return LaunchDesc(si_hip_permute_f32, si_hip_permute_f16, "Layout", in[0], out[0], [this](auto&... a) { return Desc(a...); }, Status::kUnsupport);
     });
 }
 

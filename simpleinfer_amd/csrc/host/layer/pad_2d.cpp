@@ -7,20 +7,6 @@ namespace SimpleInfer {
 
 DEFINE_LAYER_REGISTRY(Pad2d);
 
-namespace {
-
-bool IsNone(const pnnx::Operator* op, const char* name) { return !op->params.count(name) || 0 == op->params.at(name).type; }
-
-// `value` as float or int
-bool ReadValue(const pnnx::Operator* op, float& v) {
-    if (CheckParam(op, "value", 3)) v = op->params.at("value").f;
-    else if (CheckParam(op, "value", 2)) v = (float)op->params.at("value").i;
-    else return false;
-    return true;
-}
-
-}  // namespace
-
 // A missing required key is kFail; what the file asks for and this layer does not do is remembered for Validate (kUnsupport).
 Status Pad2d::Init(const pnnx::Operator* op) {
     CHECK_STATUS(Layer::Init(op));
@@ -28,32 +14,31 @@ Status Pad2d::Init(const pnnx::Operator* op) {
     value_ = 0.0f;
     std::vector<int> pads;
     if (op->type == "F.pad") {
-        CHECK_BOOL(CheckParam(op, "pad", 5));
-        pads = op->params.at("pad").ai;
+        CHECK_BOOL(Get(op, "pad", pads));
         CHECK_BOOL(!pads.empty() && pads.size() % 2 == 0);
         if (pads.size() > 4) unsupported_ = "F.pad with " + std::to_string(pads.size()) + " entries pads the channels or the batch: the last two dimensions only";
         if (pads.size() == 2) pads.insert(pads.end(), {0, 0});   // W only
-        CHECK_BOOL(CheckParam(op, "mode", 4));
-        const std::string& mode = op->params.at("mode").s;
+        std::string mode;
+        CHECK_BOOL(Get(op, "mode", mode));
         if ("constant" == mode) mode_ = SI_PAD_CONSTANT;
         else if ("reflect" == mode) mode_ = SI_PAD_REFLECT;
         else if ("replicate" == mode) mode_ = SI_PAD_REPLICATE;
         else if ("circular" == mode) mode_ = SI_PAD_CIRCULAR;
         else if (unsupported_.empty()) unsupported_ = "unknown F.pad mode " + mode;
-        if (!IsNone(op, "value")) CHECK_BOOL(ReadValue(op, value_));
+        if (!IsNone(op, "value")) CHECK_BOOL(GetNumber(op, "value", value_));   // (IsNone is the narrow rule: "None" as text is a value, which this read refuses)
     } else {
-        if (CheckParam(op, "padding", 2)) {
-            pads.assign(4, op->params.at("padding").i);
+        int all = 0;
+        if (Get(op, "padding", all)) {
+            pads.assign(4, all);
         } else {
-            CHECK_BOOL(CheckParam(op, "padding", 5));
-            pads = op->params.at("padding").ai;
+            CHECK_BOOL(Get(op, "padding", pads));
             CHECK_BOOL(pads.size() == 4);
         }
         if (op->type == "nn.ReflectionPad2d") mode_ = SI_PAD_REFLECT;
         else if (op->type == "nn.ReplicationPad2d") mode_ = SI_PAD_REPLICATE;
         else if (op->type == "nn.CircularPad2d") mode_ = SI_PAD_CIRCULAR;
         else mode_ = SI_PAD_CONSTANT;   // nn.ZeroPad2d, nn.ConstantPad2d
-        if (op->type == "nn.ConstantPad2d") CHECK_BOOL(ReadValue(op, value_));
+        if (op->type == "nn.ConstantPad2d") CHECK_BOOL(GetNumber(op, "value", value_));
     }
     pad_l_ = pads[0]; pad_r_ = pads[1]; pad_t_ = pads[2]; pad_b_ = pads[3];
     return Status::kSuccess;
@@ -62,10 +47,7 @@ Status Pad2d::Init(const pnnx::Operator* op) {
 Status Pad2d::Validate() {
     CHECK_STATUS(Layer::Validate());
     CHECK_STATUS(ValidateShape(1, 1));
-    if (Status::kSuccess != ValidateFloat()) {
-        LOG(ERROR) << "Pad2d::Validate fail [unsupport input/output data type]";
-        return Status::kUnsupport;
-    }
+    CHECK_STATUS(ValidateFloatLogged("Pad2d"));
     if (!unsupported_.empty()) {
         LOG(ERROR) << "Pad2d::Validate fail [" << unsupported_ << "]";
         return Status::kUnsupport;
@@ -118,19 +100,17 @@ bool Pad2d::MakeDesc(const Tensor& input, const Tensor& output, SiPad2dDesc& d) 
 
 Status Pad2d::Forward(const Tensor& input, Tensor& output) {
     return RunOnDevice({&input}, {&output}, [this](const std::vector<Tensor>& in, std::vector<Tensor>& out) {
-        if (IsHalf(in[0]) && !IsHalf(out[0])) return Status::kUnsupport;  // (the engine puts a cast step in front of a graph output)
+        // the two plain cases; fp16 in and fp32 out is kUnsupport there (the engine puts a cast step in front of a graph output)
+        if (!StagesInput(in[0], out[0]))
+            return LaunchDesc(si_hip_pad2d_f32, si_hip_pad2d_f16, "Pad2d", in[0], out[0], [this](auto&... a) { return MakeDesc(a...); });
         SiPad2dDesc d;
         if (!MakeDesc(in[0], out[0], d)) return Status::kErrorShape;
-        if (StagesInput(in[0], out[0])) {
-            // (the engine's first Forward is never captured, and a shape change rebuilds the plan: nothing is allocated during a graph capture)
-            const size_t pixels = (size_t)d.n * d.ih * d.iw, need = pixels * d.c * 2;
-            if (need > staging_dev_.bytes()) CHECK_STATUS(CheckHip(staging_dev_.Alloc(need), "Pad2d input staging"));
-            CHECK_STATUS(CheckHip(si_hip_convert_f32_f16(in[0].Data<float>(), pixels, d.c, in[0].PixelStride(), staging_dev_.As<void>(), d.c, Stream()),
-                                  "Pad2d (fp32 input to half)"));
-            return CheckHip(si_hip_pad2d_f16(&d, staging_dev_.As<void>(), out[0].RawData(), Stream()), "Pad2d");
-        }
-        if (IsHalf(in[0])) return CheckHip(si_hip_pad2d_f16(&d, in[0].RawData(), out[0].RawData(), Stream()), "Pad2d");
-        return CheckHip(si_hip_pad2d_f32(&d, in[0].Data<float>(), out[0].Data<float>(), Stream()), "Pad2d");
+        // (the engine's first Forward is never captured, and a shape change rebuilds the plan: nothing is allocated during a graph capture)
+        const size_t pixels = (size_t)d.n * d.ih * d.iw, need = pixels * d.c * 2;
+        if (need > staging_dev_.bytes()) CHECK_STATUS(CheckHip(staging_dev_.Alloc(need), "Pad2d input staging"));
+        CHECK_STATUS(CheckHip(si_hip_convert_f32_f16(in[0].Data<float>(), pixels, d.c, in[0].PixelStride(), staging_dev_.As<void>(), d.c, Stream()),
+                              "Pad2d (fp32 input to half)"));
+        return CheckHip(si_hip_pad2d_f16(&d, staging_dev_.As<void>(), out[0].RawData(), Stream()), "Pad2d");
     });
 }
 

@@ -7,26 +7,6 @@ namespace SimpleInfer {
 
 DEFINE_LAYER_REGISTRY(ParamActivation);
 
-namespace {
-
-// a float the file may write as a float or an int; missing or None keeps `value` and leaves `have` false; another type is an error
-bool Number(const pnnx::Operator* op, const char* key, float& value, bool& have) {
-    have = false;
-    auto it = op->params.find(key);
-    if (it == op->params.end() || it->second.type == 0) return true;
-    if (it->second.type == 4 && it->second.s == "None") return true;
-    if (it->second.type == 3)
-        value = it->second.f;
-    else if (it->second.type == 2)
-        value = (float)it->second.i;
-    else
-        return false;
-    have = true;
-    return true;
-}
-
-}  // namespace
-
 Status ParamActivation::Init(const pnnx::Operator* op) {
     CHECK_STATUS(Layer::Init(op));
     const std::string& t = op->type;
@@ -79,10 +59,7 @@ Status ParamActivation::Init(const pnnx::Operator* op) {
 Status ParamActivation::Validate() {
     CHECK_STATUS(Layer::Validate());
     CHECK_STATUS(ValidateShape(1, 1));
-    if (Status::kSuccess != ValidateFloat()) {
-        LOG(ERROR) << "ParamActivation::Validate fail [unsupport input/output data type]";
-        return Status::kUnsupport;
-    }
+    CHECK_STATUS(ValidateFloatLogged("ParamActivation"));
     const Tensor& in = input_tensor_nodes_[0]->tensor;
     const Tensor& out = output_tensor_nodes_[0]->tensor;
     if (!IsSameShape(in.Shape(), out.Shape())) {
@@ -114,13 +91,7 @@ bool ParamActivation::MakeDesc(const Tensor& input, const Tensor& output, SiPara
 }
 
 Status ParamActivation::Forward(const Tensor& input, Tensor& output) {
-    return RunOnDevice({&input}, {&output}, [this](const std::vector<Tensor>& in, std::vector<Tensor>& out) {
-        if (IsHalf(in[0]) != IsHalf(out[0])) return Status::kUnsupport;
-        SiParamActDesc d;
-        if (!MakeDesc(in[0], out[0], d)) return Status::kErrorShape;
-        if (IsHalf(in[0])) return CheckHip(si_hip_param_act_f16(&d, in[0].RawData(), out[0].RawData(), Stream()), "ParamActivation");
-        return CheckHip(si_hip_param_act_f32(&d, in[0].Data<float>(), out[0].Data<float>(), Stream()), "ParamActivation");
-    });
+    return ForwardDesc(si_hip_param_act_f32, si_hip_param_act_f16, "ParamActivation", input, output, [this](auto&... a) { return MakeDesc(a...); });
 }
 
 }  // namespace SimpleInfer

@@ -1,7 +1,6 @@
 #include "pixel_shuffle.h"
 
 #include <cstring>
-#include <sstream>
 
 namespace SimpleInfer {
 
@@ -12,24 +11,14 @@ Status PixelShuffle::Init(const pnnx::Operator* op) {
     CHECK_STATUS(Layer::Init(op));
     inverse_ = op->type == "nn.PixelUnshuffle" || op->type == "F.pixel_unshuffle";
     const char* key = inverse_ ? "downscale_factor" : "upscale_factor";
-    CHECK_BOOL(CheckParam(op, key, 2));
-    factor_ = op->params.at(key).i;
+    CHECK_BOOL(Get(op, key, factor_));
     return Status::kSuccess;
-}
-
-static std::string ShapeString(const std::vector<int>& s) {
-    std::ostringstream os;
-    for (size_t i = 0; i < s.size(); ++i) os << (i ? "x" : "") << s[i];
-    return os.str();
 }
 
 Status PixelShuffle::Validate() {
     CHECK_STATUS(Layer::Validate());
     CHECK_STATUS(ValidateShape(1, 1));
-    if (Status::kSuccess != ValidateFloat()) {
-        LOG(ERROR) << "PixelShuffle::Validate fail [unsupport input/output data type]";
-        return Status::kUnsupport;
-    }
+    CHECK_STATUS(ValidateFloatLogged("PixelShuffle"));
     const Tensor& in = input_tensor_nodes_[0]->tensor;
     const Tensor& out = output_tensor_nodes_[0]->tensor;
     Dims4 id, od;
@@ -68,26 +57,11 @@ bool PixelShuffle::MakeDesc(const Tensor& input, const Tensor& output, SiPixelSh
 }
 
 Status PixelShuffle::Forward(const Tensor& input, Tensor& output) {
-    return RunOnDevice({&input}, {&output}, [this](const std::vector<Tensor>& in, std::vector<Tensor>& out) {
-        if (IsHalf(in[0]) != IsHalf(out[0])) return Status::kUnsupport;
-        SiPixelShuffleDesc d;
-        if (!MakeDesc(in[0], out[0], d)) return Status::kErrorShape;
-        if (IsHalf(in[0])) return CheckHip(si_hip_pixel_shuffle_f16(&d, in[0].RawData(), out[0].RawData(), Stream()), "PixelShuffle");
-        return CheckHip(si_hip_pixel_shuffle_f32(&d, in[0].Data<float>(), out[0].Data<float>(), Stream()), "PixelShuffle");
-    });
+    return ForwardDesc(si_hip_pixel_shuffle_f32, si_hip_pixel_shuffle_f16, "PixelShuffle", input, output, [this](auto&... a) { return MakeDesc(a...); });
 }
 
 const char* PixelShuffle::KernelName() const {
-    SiPixelShuffleDesc d;
-    if (input_tensor_nodes_.empty() || output_tensor_nodes_.empty() ||
-        !MakeDesc(input_tensor_nodes_[0]->tensor, output_tensor_nodes_[0]->tensor, d))
-        return "pixel_shuffle";
-    const Tensor& in = input_tensor_nodes_[0]->tensor;
-    const Tensor& out = output_tensor_nodes_[0]->tensor;
-    return si_hip_pixel_shuffle_kernel_name(&d, in.RawData(), out.RawData(), IsHalf(in) ? 1 : 0);
+    return DescKernelName(si_hip_pixel_shuffle_kernel_name, "pixel_shuffle", [this](auto&... a) { return MakeDesc(a...); });
 }
-
-// fp16 in and out run the fp16 kernel directly; a mixed pair does not exist for this layer
-bool PixelShuffle::HalfStorageOk(std::string& why) const { return Layer::HalfStorageOk(why); }
 
 }  // namespace SimpleInfer

@@ -18,7 +18,6 @@ public:
     virtual Status Forward(const Tensor& input, Tensor& output) override;
 
     virtual const char* KernelName() const override;
-    virtual bool HalfStorageOk(std::string& why) const override;
     // (Bytes: the base class's input bytes plus output bytes; no arithmetic: Flops stays 0)
 
 public:

@@ -6,20 +6,9 @@ namespace SimpleInfer {
 
 DEFINE_LAYER_REGISTRY(PReLU);
 
-// (BatchNorm2d's)
-static bool ReadVec(const pnnx::Operator* op, const char* key, std::vector<float>& dst) {
-    if (!CheckAttr(op, key, 1)) return false;
-    const pnnx::Attribute& a = op->attrs.at(key);
-    if (1 != a.shape.size() || a.data.size() != (size_t)a.shape[0] * sizeof(float)) return false;
-    dst.resize(a.shape[0]);
-    memcpy(dst.data(), a.data.data(), a.data.size());
-    return true;
-}
-
 Status PReLU::Init(const pnnx::Operator* op) {
     CHECK_STATUS(Layer::Init(op));
-    CHECK_BOOL(CheckParam(op, "num_parameters", 2));
-    num_parameters_ = op->params.at("num_parameters").i;
+    CHECK_BOOL(Get(op, "num_parameters", num_parameters_));
     CHECK_BOOL(ReadVec(op, "weight", weight_));
     device_ready_ = false;
     return Status::kSuccess;
@@ -34,10 +23,7 @@ Status PReLU::Deinit() {
 Status PReLU::Validate() {
     CHECK_STATUS(Layer::Validate());
     CHECK_STATUS(ValidateShape(1, 1));
-    if (Status::kSuccess != ValidateFloat()) {
-        LOG(ERROR) << "PReLU::Validate fail [unsupport input/output data type]";
-        return Status::kUnsupport;
-    }
+    CHECK_STATUS(ValidateFloatLogged("PReLU"));
     const std::vector<int>& is = input_tensor_nodes_[0]->tensor.Shape();
     if (!IsSameShape(is, output_tensor_nodes_[0]->tensor.Shape())) {
         LOG(ERROR) << "PReLU::Validate fail [error input/output shape]";
@@ -98,8 +84,5 @@ double PReLU::Flops() const {
     if (input_tensor_nodes_.empty()) return 0.0;
     return 2.0 * (double)input_tensor_nodes_[0]->tensor.NumElements();
 }
-
-// fp16 in and out run the fp16 kernel with the fp32 slopes
-bool PReLU::HalfStorageOk(std::string& why) const { return Layer::HalfStorageOk(why); }
 
 }  // namespace SimpleInfer

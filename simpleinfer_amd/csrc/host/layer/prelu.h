@@ -19,7 +19,6 @@ public:
     virtual Status Forward(const Tensor& input, Tensor& output) override;
 
     virtual const char* KernelName() const override;
-    virtual bool HalfStorageOk(std::string& why) const override;
     virtual double Flops() const override;
 
     Status PrepareDevice();

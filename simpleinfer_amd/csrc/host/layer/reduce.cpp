@@ -1,7 +1,6 @@
 #include "reduce.h"
 
 #include <cstring>
-#include <sstream>
 
 #include "softmax.h"
 
@@ -9,62 +8,25 @@ namespace SimpleInfer {
 
 DEFINE_LAYER_REGISTRY(Reduce);
 
-namespace {
-
-std::string ShapeString(const std::vector<int>& s) {
-    std::ostringstream os;
-    for (size_t i = 0; i < s.size(); ++i) os << (i ? "x" : "") << s[i];
-    return os.str();
-}
-
-std::string DimsString(const std::vector<int>& dims) {
-    std::ostringstream os;
-    os << "(";
-    for (size_t i = 0; i < dims.size(); ++i) os << (i ? "," : "") << dims[i];
-    os << ")";
-    return os.str();
-}
-
-// rank 4: NHWC; rank 2 [N, F]: [N, 1, 1, F]
-bool Dims(const Tensor& t, int d[4]) {
-    const std::vector<int>& s = t.Shape();
-    if (s.size() == 4) {
-        d[0] = s[0]; d[1] = s[1]; d[2] = s[2]; d[3] = s[3];
-    } else if (s.size() == 2) {
-        d[0] = s[0]; d[1] = 1; d[2] = 1; d[3] = s[1];
-    } else {
-        return false;
-    }
-    return d[0] > 0 && d[1] > 0 && d[2] > 0 && d[3] > 0;
-}
-
-}  // namespace
-
 // A mistyped key is kFail; a missing dim, and a dtype other than None, are kUnsupport; dims the shape does not allow are left for Validate.
 Status Reduce::Init(const pnnx::Operator* op) {
     CHECK_STATUS(Layer::Init(op));
     op_code_ = op->type == "torch.sum" ? SI_REDUCE_SUM : op->type == "torch.amax" ? SI_REDUCE_AMAX : op->type == "torch.amin" ? SI_REDUCE_AMIN : SI_REDUCE_MEAN;
     dims_.clear();
     axes_ = 0;
-    auto dim = op->params.find("dim");
-    if (dim == op->params.end() || dim->second.type == 0) {
+    if (IsNone(op, "dim")) {
         LOG(ERROR) << "Reduce::Init fail [" << op->type << " without dim: the reduction to a scalar is not served]";
         return Status::kUnsupport;
     }
-    if (dim->second.type == 2) {
-        dims_.push_back(dim->second.i);
+    int one = 0;
+    if (Get(op, "dim", one)) {
+        dims_.push_back(one);
     } else {
-        CHECK_BOOL(CheckParam(op, "dim", 5));
-        dims_ = dim->second.ai;
-        CHECK_BOOL(!dims_.empty());
+        CHECK_BOOL(Get(op, "dim", dims_) && !dims_.empty());
     }
     keepdim_ = false;
-    if (op->params.count("keepdim")) {
-        CHECK_BOOL(CheckParam(op, "keepdim", 1));
-        keepdim_ = op->params.at("keepdim").b;
-    }
-    auto dtype = op->params.find("dtype");
-    if (dtype != op->params.end() && dtype->second.type != 0 && !(dtype->second.type == 4 && dtype->second.s == "None")) {
+    if (FindParam(op, "keepdim")) CHECK_BOOL(Get(op, "keepdim", keepdim_));
+    if (!IsNoneOrText(op, "dtype")) {
         LOG(ERROR) << "Reduce::Init fail [" << op->type << " with a dtype: the result has the input's type here]";
         return Status::kUnsupport;
     }
@@ -76,11 +38,11 @@ Status Reduce::Mask(int rank, int& axes) const {
     for (int dim : dims_) {
         const int axis = Softmax::NhwcAxis(dim, rank);
         if (axis < 0) {
-            LOG(ERROR) << "Reduce: dim " << dim << " of " << DimsString(dims_) << " is out of range for a rank-" << rank << " tensor";
+            LOG(ERROR) << "Reduce: dim " << dim << " of " << TupleString(dims_) << " is out of range for a rank-" << rank << " tensor";
             return Status::kUnsupport;
         }
         if (axes & (1 << axis)) {
-            LOG(ERROR) << "Reduce: dim " << dim << " appears twice in " << DimsString(dims_);
+            LOG(ERROR) << "Reduce: dim " << dim << " appears twice in " << TupleString(dims_);
             return Status::kFail;
         }
         axes |= 1 << axis;
@@ -91,28 +53,25 @@ Status Reduce::Mask(int rank, int& axes) const {
 Status Reduce::Validate() {
     CHECK_STATUS(Layer::Validate());
     CHECK_STATUS(ValidateShape(1, 1));
-    if (Status::kSuccess != ValidateFloat()) {
-        LOG(ERROR) << "Reduce::Validate fail [unsupport input/output data type]";
-        return Status::kUnsupport;
-    }
+    CHECK_STATUS(ValidateFloatLogged("Reduce"));
     const Tensor& in = input_tensor_nodes_[0]->tensor;
     const Tensor& out = output_tensor_nodes_[0]->tensor;
     const std::vector<int>& is = in.Shape();
     const int rank = (int)is.size();
     int id[4];
-    if (!Dims(in, id)) {
-        LOG(ERROR) << "Reduce::Validate fail [dim " << DimsString(dims_) << " of a rank-" << rank << " tensor " << ShapeString(is) << ": ranks 2 and 4 only]";
+    if (!NhwcDims(in, id)) {
+        LOG(ERROR) << "Reduce::Validate fail [dim " << TupleString(dims_) << " of a rank-" << rank << " tensor " << ShapeString(is) << ": ranks 2 and 4 only]";
         return Status::kUnsupport;
     }
     CHECK_STATUS(Mask(rank, axes_));
     if ((axes_ & SI_REDUCE_AXIS_C) && axes_ != SI_REDUCE_AXIS_C) {
-        LOG(ERROR) << "Reduce::Validate fail [dim " << DimsString(dims_) << " of " << ShapeString(is)
+        LOG(ERROR) << "Reduce::Validate fail [dim " << TupleString(dims_) << " of " << ShapeString(is)
                    << " (NHWC) reduces the channels together with another axis: the channel dim alone, or any of the others]";
         return Status::kUnsupport;
     }
     const bool pool = rank == 4 && axes_ == (SI_REDUCE_AXIS_H | SI_REDUCE_AXIS_W);
     if (!keepdim_ && !pool) {
-        LOG(ERROR) << "Reduce::Validate fail [keepdim=False over dim " << DimsString(dims_) << " of a rank-" << rank
+        LOG(ERROR) << "Reduce::Validate fail [keepdim=False over dim " << TupleString(dims_) << " of a rank-" << rank
                    << " tensor: only dims (2,3) of a rank-4 tensor drop their axes here (the [N, C] result is the [N, 1, 1, C] memory)]";
         return Status::kUnsupport;
     }
@@ -127,12 +86,12 @@ Status Reduce::Validate() {
     }
     if (!IsSameShape(want, out.Shape())) {
         LOG(ERROR) << "Reduce::Validate fail [the file's output is " << ShapeString(out.Shape()) << ", the rule gives " << ShapeString(want)
-                   << " for dim " << DimsString(dims_) << (keepdim_ ? " keepdim=True" : " keepdim=False") << " of " << ShapeString(is) << " (NHWC)]";
+                   << " for dim " << TupleString(dims_) << (keepdim_ ? " keepdim=True" : " keepdim=False") << " of " << ShapeString(is) << " (NHWC)]";
         return Status::kErrorShape;
     }
     SiReduceDesc d;
     if (!MakeDesc(in, out, d) || 0 == strcmp("none", si_hip_reduce_kernel_name(&d, nullptr, nullptr, 0))) {
-        LOG(ERROR) << "Reduce::Validate fail [" << ShapeString(is) << " over dim " << DimsString(dims_) << ": the kernels refuse this tensor (element offsets beyond 31 bits)]";
+        LOG(ERROR) << "Reduce::Validate fail [" << ShapeString(is) << " over dim " << TupleString(dims_) << ": the kernels refuse this tensor (element offsets beyond 31 bits)]";
         return Status::kUnsupport;
     }
     return Status::kSuccess;
@@ -140,7 +99,7 @@ Status Reduce::Validate() {
 
 bool Reduce::MakeDesc(const Tensor& input, const Tensor& output, SiReduceDesc& d) const {
     int id[4], axes = 0;
-    if (!Dims(input, id) || Status::kSuccess != Mask((int)input.Shape().size(), axes)) return false;
+    if (!NhwcDims(input, id) || Status::kSuccess != Mask((int)input.Shape().size(), axes)) return false;
     memset(&d, 0, sizeof(d));
     d.n = id[0]; d.h = id[1]; d.w = id[2]; d.c = id[3];
     d.in_ld = input.PixelStride();
@@ -153,23 +112,11 @@ bool Reduce::MakeDesc(const Tensor& input, const Tensor& output, SiReduceDesc& d
 }
 
 Status Reduce::Forward(const Tensor& input, Tensor& output) {
-    return RunOnDevice({&input}, {&output}, [this](const std::vector<Tensor>& in, std::vector<Tensor>& out) {
-        if (IsHalf(in[0]) != IsHalf(out[0])) return Status::kUnsupport;
-        SiReduceDesc d;
-        if (!MakeDesc(in[0], out[0], d)) return Status::kErrorShape;
-        if (IsHalf(in[0])) return CheckHip(si_hip_reduce_f16(&d, in[0].RawData(), out[0].RawData(), Stream()), "Reduce");
-        return CheckHip(si_hip_reduce_f32(&d, in[0].Data<float>(), out[0].Data<float>(), Stream()), "Reduce");
-    });
+    return ForwardDesc(si_hip_reduce_f32, si_hip_reduce_f16, "Reduce", input, output, [this](auto&... a) { return MakeDesc(a...); });
 }
 
 const char* Reduce::KernelName() const {
-    SiReduceDesc d;
-    if (input_tensor_nodes_.empty() || output_tensor_nodes_.empty() ||
-        !MakeDesc(input_tensor_nodes_[0]->tensor, output_tensor_nodes_[0]->tensor, d))
-        return "reduce";
-    const Tensor& in = input_tensor_nodes_[0]->tensor;
-    const Tensor& out = output_tensor_nodes_[0]->tensor;
-    return si_hip_reduce_kernel_name(&d, in.RawData(), out.RawData(), IsHalf(in) ? 1 : 0);
+    return DescKernelName(si_hip_reduce_kernel_name, "reduce", [this](auto&... a) { return MakeDesc(a...); });
 }
 
 // one addition or one selection per input element

@@ -3,76 +3,42 @@
 #include <algorithm>
 #include <climits>
 #include <cstring>
-#include <sstream>
 
 namespace SimpleInfer {
 
 DEFINE_LAYER_REGISTRY(Slice);
 
-namespace {
-
-std::string ShapeString(const std::vector<int>& s) {
-    std::ostringstream os;
-    for (size_t i = 0; i < s.size(); ++i) os << (i ? "x" : "") << s[i];
-    return os.str();
-}
-
-// an int, or None / a missing key (`have` false)
-bool IntOrNone(const pnnx::Operator* op, const char* key, int& v, bool& have) {
-    auto it = op->params.find(key);
-    have = false;
-    if (it == op->params.end() || it->second.type == 0) return true;
-    if (it->second.type == 4 && it->second.s == "None") return true;
-    if (it->second.type != 2) return false;
-    v = it->second.i;
-    have = true;
-    return true;
-}
-
-}  // namespace
-
 // A missing or mistyped key is kFail; values the rule does not allow are left for Validate, which knows the shape.
 Status Slice::Init(const pnnx::Operator* op) {
     CHECK_STATUS(Layer::Init(op));
+    int dim = 0;
     dims_.clear(); starts_.clear(); ends_.clear(); steps_.clear(); has_end_.clear(); sections_.clear();
     if (op->type == "torch.chunk") {
         kind_ = Kind::kChunk;
-        CHECK_BOOL(CheckParam(op, "chunks", 2));
-        CHECK_BOOL(CheckParam(op, "dim", 2));
-        chunks_ = op->params.at("chunks").i;
-        dims_.push_back(op->params.at("dim").i);
+        CHECK_BOOL(Get(op, "chunks", chunks_) && Get(op, "dim", dim));
+        dims_.push_back(dim);
         return Status::kSuccess;
     }
     if (op->type == "torch.split") {
         kind_ = Kind::kSplit;
-        CHECK_BOOL(CheckParam(op, "dim", 2));
-        dims_.push_back(op->params.at("dim").i);
+        CHECK_BOOL(Get(op, "dim", dim));
+        dims_.push_back(dim);
         const char* key = "split_size_or_sections";
-        if (CheckParam(op, key, 2)) {
-            sections_.push_back(op->params.at(key).i);
-            sections_is_list_ = false;
-        } else {
-            CHECK_BOOL(CheckParam(op, key, 5));
-            sections_ = op->params.at(key).ai;
-            sections_is_list_ = true;
-        }
+        int size = 0;
+        sections_is_list_ = !Get(op, key, size);
+        if (!sections_is_list_) sections_.push_back(size);
+        CHECK_BOOL(!sections_is_list_ || Get(op, key, sections_));
         return Status::kSuccess;
     }
     kind_ = Kind::kSlice;
-    if (op->params.count("dims")) {
-        CHECK_BOOL(CheckParam(op, "dims", 5));
-        dims_ = op->params.at("dims").ai;
+    if (FindParam(op, "dims")) {
+        CHECK_BOOL(Get(op, "dims", dims_));
         const size_t k = dims_.size();
         auto list = [&](const char* key, std::vector<int>& v, int dflt, std::vector<bool>* have) {
-            auto it = op->params.find(key);
-            if (it == op->params.end() || it->second.type == 0) {
-                v.assign(k, dflt);
-                if (have) have->assign(k, false);
-                return true;
-            }
-            if (it->second.type != 5 || it->second.ai.size() != k) return false;
-            v = it->second.ai;
-            if (have) have->assign(k, true);
+            const bool given = !IsNone(op, key);   // (a list or nothing: the string "None" is refused)
+            if (given && !(Get(op, key, v) && v.size() == k)) return false;
+            if (!given) v.assign(k, dflt);
+            if (have) have->assign(k, given);
             return true;
         };
         CHECK_BOOL(list("starts", starts_, 0, nullptr));
@@ -80,30 +46,18 @@ Status Slice::Init(const pnnx::Operator* op) {
         CHECK_BOOL(list("steps", steps_, 1, nullptr));
         return Status::kSuccess;
     }
-    CHECK_BOOL(CheckParam(op, "dim", 2));
-    dims_.push_back(op->params.at("dim").i);
+    CHECK_BOOL(Get(op, "dim", dim));
+    dims_.push_back(dim);
     int start = 0, end = INT_MAX, step = 1;
     bool have = false, have_end = false;
-    CHECK_BOOL(IntOrNone(op, "start", start, have));
-    CHECK_BOOL(IntOrNone(op, "end", end, have_end));
-    CHECK_BOOL(IntOrNone(op, "step", step, have));
+    CHECK_BOOL(OptionalInt(op, "start", start, have));
+    CHECK_BOOL(OptionalInt(op, "end", end, have_end));
+    CHECK_BOOL(OptionalInt(op, "step", step, have));
     starts_.push_back(start);
     ends_.push_back(end);
     steps_.push_back(step);
     has_end_.push_back(have_end);
     return Status::kSuccess;
-}
-
-bool Slice::Dims(const Tensor& t, int d[4]) {
-    const std::vector<int>& s = t.Shape();
-    if (s.size() == 4) {
-        d[0] = s[0]; d[1] = s[1]; d[2] = s[2]; d[3] = s[3];
-    } else if (s.size() == 2) {
-        d[0] = s[0]; d[1] = 1; d[2] = 1; d[3] = s[1];
-    } else {
-        return false;
-    }
-    return d[0] > 0 && d[1] > 0 && d[2] > 0 && d[3] > 0;
 }
 
 bool Slice::ChannelRange(const Piece& p, const int in_dims[4]) {
@@ -211,13 +165,10 @@ Status Slice::Validate() {
     const Tensor& in = input_tensor_nodes_[0]->tensor;
     // fp32 or fp16 storage.  The kernels want the same type on every operand; at the graph boundary of an fp16 engine the types differ
     // (a slice of the caller's fp32 image), which the base class's HalfStorageOk reports and the engine answers with fp32 shadows and casts
-    if (Status::kSuccess != ValidateFloat()) {
-        LOG(ERROR) << "Slice::Validate fail [unsupport input/output data type]";
-        return Status::kUnsupport;
-    }
+    CHECK_STATUS(ValidateFloatLogged("Slice"));
     int id[4];
     const int rank = (int)in.Shape().size();
-    if (!Dims(in, id)) {
+    if (!NhwcDims(in, id)) {
         LOG(ERROR) << "Slice::Validate fail [a rank-" << rank << " input " << ShapeString(in.Shape()) << " (NHWC): rank 4, or rank 2 on dim 1]";
         return Status::kUnsupport;
     }
@@ -230,7 +181,7 @@ Status Slice::Validate() {
     for (size_t i = 0; i < pieces_.size(); ++i) {
         const Tensor& out = output_tensor_nodes_[i]->tensor;
         int od[4];
-        if ((int)out.Shape().size() != rank || !Dims(out, od)) {
+        if ((int)out.Shape().size() != rank || !NhwcDims(out, od)) {
             LOG(ERROR) << "Slice::Validate fail [output " << i << " " << ShapeString(out.Shape()) << " for a rank-" << rank << " input]";
             return Status::kUnsupport;
         }
@@ -254,7 +205,7 @@ Status Slice::Run(const Tensor& input, const std::vector<Tensor*>& outputs) {
     if (outputs.size() != pieces_.size()) return Status::kErrorShape;
     return RunOnDevice({&input}, outputs, [this](const std::vector<Tensor>& in, std::vector<Tensor>& out) {
         int id[4];
-        if (!Dims(in[0], id)) return Status::kErrorShape;
+        if (!NhwcDims(in[0], id)) return Status::kErrorShape;
         const bool half = IsHalf(in[0]);
         std::vector<int> offsets, widths, lds;
         std::vector<void*> dsts;
@@ -270,14 +221,13 @@ Status Slice::Run(const Tensor& input, const std::vector<Tensor*>& outputs) {
                 dsts.push_back(out[i].RawData());
                 continue;
             }
-            SiSliceDesc d;
-            memset(&d, 0, sizeof(d));
-            d.n = id[0]; d.ih = id[1]; d.iw = id[2]; d.ic = id[3]; d.in_ld = in[0].PixelStride();
-            for (int a = 0; a < 4; ++a) { d.start[a] = p.start[a]; d.step[a] = p.step[a]; }
-            d.on = p.dims[0]; d.oh = p.dims[1]; d.ow = p.dims[2]; d.oc = p.dims[3]; d.out_ld = out[i].PixelStride();
-            const int rc = half ? si_hip_slice_f16(&d, in[0].RawData(), out[i].RawData(), Stream())
-                                : si_hip_slice_f32(&d, in[0].RawData(), out[i].RawData(), Stream());
-            CHECK_STATUS(CheckHip(rc, "Slice"));
+            CHECK_STATUS(LaunchDesc(si_hip_slice_f32, si_hip_slice_f16, "Slice", in[0], out[i], [&](const Tensor& src, const Tensor& dst, SiSliceDesc& d) {
+                memset(&d, 0, sizeof(d));
+                d.n = id[0]; d.ih = id[1]; d.iw = id[2]; d.ic = id[3]; d.in_ld = src.PixelStride();
+                for (int a = 0; a < 4; ++a) { d.start[a] = p.start[a]; d.step[a] = p.step[a]; }
+                d.on = p.dims[0]; d.oh = p.dims[1]; d.ow = p.dims[2]; d.oc = p.dims[3]; d.out_ld = dst.PixelStride();
+                return true;
+            }));
         }
         if (dsts.empty()) return Status::kSuccess;
         const size_t pixels = (size_t)id[0] * id[1] * id[2];
@@ -300,7 +250,7 @@ Status Slice::Forward(const Tensor& input, std::vector<Tensor>& outputs) {
 
 const char* Slice::KernelName() const {
     int id[4];
-    if (input_tensor_nodes_.empty() || pieces_.size() != output_tensor_nodes_.size() || !Dims(input_tensor_nodes_[0]->tensor, id)) return "slice";
+    if (input_tensor_nodes_.empty() || pieces_.size() != output_tensor_nodes_.size() || !NhwcDims(input_tensor_nodes_[0]->tensor, id)) return "slice";
     bool split = false, slice = false;
     for (size_t i = 0; i < pieces_.size(); ++i) {
         const int route = Route(pieces_[i], id, input_tensor_nodes_[0]->tensor, output_tensor_nodes_[i]->tensor);

@@ -51,8 +51,6 @@ public:
     std::vector<bool> has_end_;
 
 private:
-    // rank 4: NHWC; rank 2 [N, F]: [N, 1, 1, F]
-    static bool Dims(const Tensor& t, int d[4]);
     Status MakePieces(const int in_dims[4], int rank, std::vector<Piece>& pieces) const;
     // 0: already in place, 1: a channel range to copy, 2: a strided slice
     static int Route(const Piece& p, const int in_dims[4], const Tensor& in, const Tensor& out);

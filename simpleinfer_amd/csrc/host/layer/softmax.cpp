@@ -1,7 +1,6 @@
 #include "softmax.h"
 
 #include <cstring>
-#include <sstream>
 
 namespace SimpleInfer {
 
@@ -14,8 +13,7 @@ Status Softmax::Init(const pnnx::Operator* op) {
     if (op->type == "nn.Softmax2d") {
         dim_ = -3;
     } else {
-        CHECK_BOOL(CheckParam(op, "dim", 2));
-        dim_ = op->params.at("dim").i;
+        CHECK_BOOL(Get(op, "dim", dim_));
     }
     axis_ = -1;
     return Status::kSuccess;
@@ -34,19 +32,10 @@ int Softmax::NhwcAxis(int dim, int rank) {
     }
 }
 
-static std::string ShapeString(const std::vector<int>& s) {
-    std::ostringstream os;
-    for (size_t i = 0; i < s.size(); ++i) os << (i ? "x" : "") << s[i];
-    return os.str();
-}
-
 Status Softmax::Validate() {
     CHECK_STATUS(Layer::Validate());
     CHECK_STATUS(ValidateShape(1, 1));
-    if (Status::kSuccess != ValidateFloat()) {
-        LOG(ERROR) << "Softmax::Validate fail [unsupport input/output data type]";
-        return Status::kUnsupport;
-    }
+    CHECK_STATUS(ValidateFloatLogged("Softmax"));
     const std::vector<int>& is = input_tensor_nodes_[0]->tensor.Shape();
     if (!IsSameShape(is, output_tensor_nodes_[0]->tensor.Shape())) {
         LOG(ERROR) << "Softmax::Validate fail [error input/output shape]";
@@ -71,11 +60,9 @@ bool Softmax::MakeDesc(const Tensor& input, const Tensor& output, SiSoftmaxDesc&
     const int axis = NhwcAxis(dim_, (int)is.size());
     if (axis < 0) return false;
     memset(&d, 0, sizeof(d));
-    if (2 == is.size()) {
-        d.n = is[0]; d.h = 1; d.w = 1; d.c = is[1];
-    } else {
-        d.n = is[0]; d.h = is[1]; d.w = is[2]; d.c = is[3];
-    }
+    int id[4] = {0, 0, 0, 0};
+    NhwcDims(input, id);   // (NhwcAxis has refused every rank but 2 and 4)
+    d.n = id[0]; d.h = id[1]; d.w = id[2]; d.c = id[3];
     d.in_ld = input.PixelStride();
     d.out_ld = output.PixelStride();
     d.axis = axis;
@@ -84,23 +71,11 @@ bool Softmax::MakeDesc(const Tensor& input, const Tensor& output, SiSoftmaxDesc&
 }
 
 Status Softmax::Forward(const Tensor& input, Tensor& output) {
-    return RunOnDevice({&input}, {&output}, [this](const std::vector<Tensor>& in, std::vector<Tensor>& out) {
-        if (IsHalf(in[0]) != IsHalf(out[0])) return Status::kUnsupport;
-        SiSoftmaxDesc d;
-        if (!MakeDesc(in[0], out[0], d)) return Status::kErrorShape;
-        if (IsHalf(in[0])) return CheckHip(si_hip_softmax_f16(&d, in[0].RawData(), out[0].RawData(), Stream()), "Softmax");
-        return CheckHip(si_hip_softmax_f32(&d, in[0].Data<float>(), out[0].Data<float>(), Stream()), "Softmax");
-    });
+    return ForwardDesc(si_hip_softmax_f32, si_hip_softmax_f16, "Softmax", input, output, [this](auto&... a) { return MakeDesc(a...); });
 }
 
 const char* Softmax::KernelName() const {
-    SiSoftmaxDesc d;
-    if (input_tensor_nodes_.empty() || output_tensor_nodes_.empty() ||
-        !MakeDesc(input_tensor_nodes_[0]->tensor, output_tensor_nodes_[0]->tensor, d))
-        return "softmax";
-    const Tensor& in = input_tensor_nodes_[0]->tensor;
-    const Tensor& out = output_tensor_nodes_[0]->tensor;
-    return si_hip_softmax_kernel_name(&d, in.RawData(), out.RawData(), IsHalf(in) ? 1 : 0);
+    return DescKernelName(si_hip_softmax_kernel_name, "softmax", [this](auto&... a) { return MakeDesc(a...); });
 }
 
 // per element: the maximum, the subtraction, the exponential, the sum and the scaling (or the second subtraction)
@@ -108,8 +83,5 @@ double Softmax::Flops() const {
     if (input_tensor_nodes_.empty()) return 0.0;
     return 5.0 * (double)input_tensor_nodes_[0]->tensor.NumElements();
 }
-
-// fp16 in and out run the fp16 kernel directly; a mixed pair does not exist for this layer
-bool Softmax::HalfStorageOk(std::string& why) const { return Layer::HalfStorageOk(why); }
 
 }  // namespace SimpleInfer

@@ -18,7 +18,6 @@ public:
     virtual Status Forward(const Tensor& input, Tensor& output) override;
 
     virtual const char* KernelName() const override;
-    virtual bool HalfStorageOk(std::string& why) const override;
     virtual double Flops() const override;
     // (Bytes: the base class's one read plus one write of the tensor -- the algorithmic traffic, whichever form runs)
 

@@ -12,8 +12,7 @@ DEFINE_LAYER_REGISTRY(Tanh);
 
 Status UnaryOp::Init(const pnnx::Operator* op) {
     CHECK_STATUS(Layer::Init(op));
-    CHECK_BOOL(CheckParam(op, "0", 2));
-    unary_op_type_ = op->params.at("0").i;
+    CHECK_BOOL(Get(op, "0", unary_op_type_));
     if (unary_op_type_ < 0 || unary_op_type_ > 17) {
         LOG(ERROR) << "unsupport UnaryOp type [" << unary_op_type_ << "]";
         return Status::kUnsupport;

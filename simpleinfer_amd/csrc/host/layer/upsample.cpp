@@ -23,14 +23,12 @@ double AsWritten(float f) {
     return (double)f;
 }
 
-bool IsNone(const pnnx::Operator* op, const char* name) { return !op->params.count(name) || 0 == op->params.at(name).type; }
-
 }  // namespace
 
 Status Upsample::Init(const pnnx::Operator* op) {
     CHECK_STATUS(Layer::Init(op));
-    CHECK_BOOL(CheckParam(op, "mode", 4));
-    const std::string& mode = op->params.at("mode").s;
+    std::string mode;
+    CHECK_BOOL(Get(op, "mode", mode));
     if ("nearest" == mode) {
         upsample_mode_ = UpsampleMode::kNearest;
     } else if ("bilinear" == mode) {
@@ -39,16 +37,14 @@ Status Upsample::Init(const pnnx::Operator* op) {
         LOG(ERROR) << "Upsample::Init fail [unsupport upsample mode " << mode << "]";
         return Status::kUnsupport;
     }
-    if (!IsNone(op, "align_corners")) {
-        CHECK_BOOL(CheckParam(op, "align_corners", 1));
-        align_corners_ = op->params.at("align_corners").b;
-    }
+    // (IsNone is the narrow rule, here and below: "None" as text is a value, which the typed read refuses)
+    if (!IsNone(op, "align_corners")) CHECK_BOOL(Get(op, "align_corners", align_corners_));
     if (align_corners_ && UpsampleMode::kNearest == upsample_mode_) {
         LOG(ERROR) << "Upsample::Init fail [align_corners=True is not defined for mode nearest]";
         return Status::kUnsupport;
     }
     if (!IsNone(op, "scale_factor")) {
-        const pnnx::Parameter& p = op->params.at("scale_factor");
+        const pnnx::Parameter& p = *FindParam(op, "scale_factor");
         std::vector<float> v;
         if (6 == p.type) v = p.af;
         else if (5 == p.type) v.assign(p.ai.begin(), p.ai.end());
@@ -69,8 +65,8 @@ Status Upsample::Init(const pnnx::Operator* op) {
         has_scale_ = true;
     }
     if (!IsNone(op, "size")) {
-        CHECK_BOOL(CheckParam(op, "size", 5));
-        const std::vector<int>& v = op->params.at("size").ai;
+        std::vector<int> v;
+        CHECK_BOOL(Get(op, "size", v));
         if (2 != v.size()) {
             LOG(ERROR) << "Upsample::Init fail [" << op->type << " with " << v.size() << " sizes: rank-4 tensors only]";
             return Status::kUnsupport;
@@ -83,9 +79,10 @@ Status Upsample::Init(const pnnx::Operator* op) {
     // (torch refuses both at once; a file that has both is not one it wrote)
     CHECK_BOOL(has_scale_ != by_size_);
     if (has_scale_ && !IsNone(op, "recompute_scale_factor")) {
-        CHECK_BOOL(CheckParam(op, "recompute_scale_factor", 1));
+        bool recompute = false;
+        CHECK_BOOL(Get(op, "recompute_scale_factor", recompute));
         // the output size from the scale factor, then the rule of size=
-        if (op->params.at("recompute_scale_factor").b) by_size_ = true;
+        if (recompute) by_size_ = true;
     }
     return Status::kSuccess;
 }
@@ -93,10 +90,7 @@ Status Upsample::Init(const pnnx::Operator* op) {
 Status Upsample::Validate() {
     CHECK_STATUS(Layer::Validate());
     CHECK_STATUS(ValidateShape(1, 1));
-    if (Status::kSuccess != ValidateFloat()) {
-        LOG(ERROR) << "Upsample::Validate fail [unsupport input/output data type]";
-        return Status::kUnsupport;
-    }
+    CHECK_STATUS(ValidateFloatLogged("Upsample"));
     const bool functional = op_ && (op_->type == "F.interpolate" || op_->type == "F.upsample");
     if (functional && (input_tensor_nodes_[0]->tensor.Shape().size() != 4 || output_tensor_nodes_[0]->tensor.Shape().size() != 4)) {
         LOG(ERROR) << "Upsample::Validate fail [" << op_->type << " on a rank-" << input_tensor_nodes_[0]->tensor.Shape().size()
@@ -144,12 +138,8 @@ Status Upsample::Forward(const Tensor& input, Tensor& output) {
         Dims4 id, od;
         if (!GetDims4(in[0], id) || !GetDims4(out[0], od) || id.c != od.c || id.n != od.n) return Status::kErrorShape;
         if (IsHalf(in[0]) != IsHalf(out[0])) return Status::kUnsupport;
-        if (UpsampleMode::kBilinear == upsample_mode_) {
-            SiUpsampleDesc d;
-            if (!MakeDesc(in[0], out[0], d)) return Status::kErrorShape;
-            if (IsHalf(in[0])) return CheckHip(si_hip_upsample_bilinear_f16(&d, in[0].RawData(), out[0].RawData(), Stream()), "Upsample (bilinear)");
-            return CheckHip(si_hip_upsample_bilinear_f32(&d, in[0].Data<float>(), out[0].Data<float>(), Stream()), "Upsample (bilinear)");
-        }
+        if (UpsampleMode::kBilinear == upsample_mode_)
+            return LaunchDesc(si_hip_upsample_bilinear_f32, si_hip_upsample_bilinear_f16, "Upsample (bilinear)", in[0], out[0], [this](auto&... a) { return MakeDesc(a...); });
         // nearest: by scale factor the reference's entry point, by size the same kernel with the steps of the sizes
         const bool steps = !IsNearestByScale();
         auto nearest = [&](const float* src, int c, int in_ld, float* dst, int out_ld) {
@@ -170,13 +160,7 @@ Status Upsample::Forward(const Tensor& input, Tensor& output) {
 
 const char* Upsample::KernelName() const {
     if (UpsampleMode::kBilinear != upsample_mode_) return "upsample_nearest";
-    SiUpsampleDesc d;
-    if (input_tensor_nodes_.empty() || output_tensor_nodes_.empty() ||
-        !MakeDesc(input_tensor_nodes_[0]->tensor, output_tensor_nodes_[0]->tensor, d))
-        return "upsample_bilinear_kernel";
-    const Tensor& in = input_tensor_nodes_[0]->tensor;
-    const Tensor& out = output_tensor_nodes_[0]->tensor;
-    return si_hip_upsample_bilinear_kernel_name(&d, in.RawData(), out.RawData(), IsHalf(in) ? 1 : 0);
+    return DescKernelName(si_hip_upsample_bilinear_kernel_name, "upsample_bilinear_kernel", [this](auto&... a) { return MakeDesc(a...); });
 }
 
 }  // namespace SimpleInfer

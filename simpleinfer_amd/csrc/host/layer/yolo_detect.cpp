@@ -113,10 +113,7 @@ Status YoloDetect::Deinit() {
 Status YoloDetect::Validate() {
     CHECK_STATUS(Layer::Validate());
     CHECK_STATUS(ValidateShape(3, 1));
-    if (Status::kSuccess != ValidateFloat()) {
-        LOG(ERROR) << "YoloDetect::Validate fail [unsupport input/output data type]";
-        return Status::kUnsupport;
-    }
+    CHECK_STATUS(ValidateFloatLogged("YoloDetect"));
     return Status::kSuccess;
 }
 

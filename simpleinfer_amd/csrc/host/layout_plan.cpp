@@ -2,6 +2,7 @@
 
 #include <sstream>
 
+#include "layer/layer_util.h"
 #include "si_layout.h"
 
 namespace SimpleInfer {
@@ -17,14 +18,6 @@ long long SizeOf(const Group& g) {
     long long n = 1;
     for (const Sub& s : g) n *= s.size;
     return n;
-}
-
-std::string ShapeString(const std::vector<int>& s) {
-    std::ostringstream os;
-    os << "(";
-    for (size_t i = 0; i < s.size(); ++i) os << (i ? "," : "") << s[i];
-    os << ")";
-    return os.str();
 }
 
 std::vector<int> ShapeOf(const std::vector<Group>& g) {
@@ -112,13 +105,13 @@ Status Apply(std::vector<Group>& g, const LayoutOp& op, std::string& why) {
                 shape.push_back(op.args[i]);
                 if (op.args[i] == -1 && hole < 0) hole = (int)i;
                 else if (op.args[i] < 1) {
-                    why = "reshape to " + ShapeString(op.args) + ": entries are positive, one may be -1";
+                    why = "reshape to " + TupleString(op.args) + ": entries are positive, one may be -1";
                     return Status::kErrorShape;
                 } else known *= op.args[i];
             }
             if (hole >= 0) {
                 if (count % known != 0) {
-                    os << "reshape of " << count << " elements to " << ShapeString(op.args);
+                    os << "reshape of " << count << " elements to " << TupleString(op.args);
                     why = os.str();
                     return Status::kErrorShape;
                 }
@@ -126,7 +119,7 @@ Status Apply(std::vector<Group>& g, const LayoutOp& op, std::string& why) {
                 known = count;
             }
             if (known != count || shape.empty()) {
-                os << "reshape of " << count << " elements to " << ShapeString(op.args);
+                os << "reshape of " << count << " elements to " << TupleString(op.args);
                 why = os.str();
                 return Status::kErrorShape;
             }
@@ -146,7 +139,7 @@ Status Apply(std::vector<Group>& g, const LayoutOp& op, std::string& why) {
                         s.size = k;
                         need = 1;
                     } else {
-                        os << "reshape to " << ShapeString(op.args) << ": a boundary falls inside a stored dimension of " << s.size
+                        os << "reshape to " << TupleString(op.args) << ": a boundary falls inside a stored dimension of " << s.size
                            << " that it does not divide (" << need << " elements are wanted there)";
                         why = os.str();
                         return Status::kUnsupport;
@@ -175,11 +168,11 @@ Status PlanLayout(const std::vector<int>& in_shape, int in_ld, const std::vector
     }
     for (int v : in_shape)
         if (v < 1) {
-            why = "input shape " + ShapeString(in_shape) + " has a non-positive dimension";
+            why = "input shape " + TupleString(in_shape) + " has a non-positive dimension";
             return Status::kErrorShape;
         }
     if (rank > 4) {
-        why = "an input of rank " + std::to_string(rank) + " " + ShapeString(in_shape) + " would have to exist in memory (rank <= 4 does)";
+        why = "an input of rank " + std::to_string(rank) + " " + TupleString(in_shape) + " would have to exist in memory (rank <= 4 does)";
         plan.late = true;
         return Status::kUnsupport;
     }
@@ -207,12 +200,12 @@ Status PlanLayout(const std::vector<int>& in_shape, int in_ld, const std::vector
     }
     plan.out_shape = ShapeOf(g);
     if (out_shape && *out_shape != plan.out_shape) {
-        why = "the operators give " + ShapeString(plan.out_shape) + ", the output operand is " + ShapeString(*out_shape);
+        why = "the operators give " + TupleString(plan.out_shape) + ", the output operand is " + TupleString(*out_shape);
         return Status::kErrorShape;
     }
     const int orank = (int)g.size();
     if (orank > 4 || orank < 1) {
-        why = "an output of rank " + std::to_string(orank) + " " + ShapeString(plan.out_shape) + " would have to exist in memory (rank 1..4 does)";
+        why = "an output of rank " + std::to_string(orank) + " " + TupleString(plan.out_shape) + " would have to exist in memory (rank 1..4 does)";
         plan.late = true;
         return Status::kUnsupport;
     }

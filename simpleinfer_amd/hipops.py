@@ -310,6 +310,25 @@ def _ret(y, c, c_off, full):
     return y[..., c_off:c_off + c].copy()
 
 
+def _run_desc_op(stem, d, x, out_pixel_shape, oc, in_ld, in_c_off, in_fill, out_ld, out_c_off, out_fill, full):
+    """what the descriptor wrappers share: si_hip_<stem>_f32 / _f16 (by x's dtype) with descriptor `d`, from the channel view of x to a fresh
+    view of `out_pixel_shape` pixels of `oc` channels; records LAST_KERNEL_NAME["si_hip_<stem>"] for the two pointers"""
+    H = _native.hip()
+    half = x.dtype == np.float16
+    name = "si_hip_%s_%s" % (stem, "f16" if half else "f32")
+    out_pixel_shape = tuple(out_pixel_shape)
+    (dx, px), (dy, py) = _view_in(x, in_ld, in_c_off, in_fill), _view_out(out_pixel_shape, oc, out_ld, out_c_off, out_fill, x.dtype)
+    kernel_name = getattr(H, "si_hip_%s_kernel_name" % stem)
+    LAST_KERNEL_NAME["si_hip_" + stem] = kernel_name(C.byref(d), C.c_void_p(px), C.c_void_p(py), 1 if half else 0).decode()
+    _chk(getattr(H, name)(C.byref(d), px, py, None), name)
+    return _ret(dy.to_numpy(out_pixel_shape + (out_ld or oc,), x.dtype), oc, out_c_off, full)
+
+
+def _desc_kernel_name(stem, d, half):
+    """si_hip_<stem>_kernel_name for 16-byte aligned buffers"""
+    return getattr(_native.hip(), "si_hip_%s_kernel_name" % stem)(C.byref(d), C.c_void_p(256), C.c_void_p(256), 1 if half else 0).decode()
+
+
 def conv2d(x, w_oihw, bias=None, stride=(1, 1), padding=(0, 0), dilation=(1, 1), groups=1, act1="none",
            residual=None, act2="none", act_param=0.0, in_ld: Optional[int] = None, out_ld: Optional[int] = None,
            out_c_off: int = 0, in_fill=0.0, in_c_off: int = 0, res_ld: Optional[int] = None, res_c_off: int = 0, res_fill=0.0,
@@ -746,7 +765,7 @@ def upsample_bilinear(x, out_hw=None, scale=None, align_corners=False, in_ld: Op
 def upsample_bilinear_kernel_name(x_shape, out_hw=None, scale=None, half=False, in_ld=None, out_ld=None) -> str:
     """the instantiation for 16-byte aligned buffers of these shapes"""
     d = upsample_desc(x_shape, out_hw, scale, False, "bilinear", in_ld, out_ld)
-    return _native.hip().si_hip_upsample_bilinear_kernel_name(C.byref(d), C.c_void_p(256), C.c_void_p(256), 1 if half else 0).decode()
+    return _desc_kernel_name("upsample_bilinear", d, half)
 
 
 def upsample_nearest_size(x, out_hw, in_ld: Optional[int] = None, in_fill=0.0, in_c_off=0, out_ld=None, out_c_off=0, out_fill=0.0, full=False):
@@ -914,7 +933,7 @@ def group_norm(x, groups, gamma=None, beta=None, eps=1e-5, act1="none", act_para
 def group_norm_kernel_name(x_shape, groups, half=False, in_ld=None, out_ld=None) -> str:
     """the kernel(s) for 16-byte aligned buffers of these shapes"""
     d = group_norm_desc(x_shape, groups, in_ld=in_ld, out_ld=out_ld)
-    return _native.hip().si_hip_groupnorm_kernel_name(C.byref(d), C.c_void_p(256), C.c_void_p(256), 1 if half else 0).decode()
+    return _desc_kernel_name("groupnorm", d, half)
 
 
 def group_norm_workspace_bytes(x_shape, groups) -> int:
@@ -935,24 +954,18 @@ def pad2d_desc(x_shape, pads, mode="constant", value=0.0, in_ld=None, out_ld=Non
 def pad2d(x, pads, mode="constant", value=0.0, in_ld=None, in_c_off=0, in_fill=0.0, out_ld=None, out_c_off=0, out_fill=0.0, full=False):
     """si_hip_pad2d_f32 / _f16 (by the array's dtype) on an NHWC array: torch.nn.functional.pad(x, (l, r, t, b), mode, value) on the last
     two dimensions of the NCHW tensor.  The array's bits travel as they are (a NaN payload, -0.0).  The view hooks are the common ones."""
-    H = _native.hip()
     x = _float_storage(x)
-    half = x.dtype == np.float16
     n, ih, iw, c = x.shape
     d = pad2d_desc(x.shape, pads, mode, value, in_ld, out_ld)
     if d.oh < 1 or d.ow < 1:
         raise HipError("si_hip_pad2d: pads %r leave no output for a %dx%d input" % (tuple(pads), ih, iw))
-    (dx, px), (dy, py) = _view_in(x, in_ld, in_c_off, in_fill), _view_out((n, d.oh, d.ow), c, out_ld, out_c_off, out_fill, x.dtype)
-    LAST_KERNEL_NAME["si_hip_pad2d"] = H.si_hip_pad2d_kernel_name(C.byref(d), C.c_void_p(px), C.c_void_p(py), 1 if half else 0).decode()
-    fn, name = (H.si_hip_pad2d_f16, "si_hip_pad2d_f16") if half else (H.si_hip_pad2d_f32, "si_hip_pad2d_f32")
-    _chk(fn(C.byref(d), px, py, None), name)
-    return _ret(dy.to_numpy((n, d.oh, d.ow, out_ld or c), x.dtype), c, out_c_off, full)
+    return _run_desc_op("pad2d", d, x, (n, d.oh, d.ow), c, in_ld, in_c_off, in_fill, out_ld, out_c_off, out_fill, full)
 
 
 def pad2d_kernel_name(x_shape, pads, mode="constant", half=False, in_ld=None, out_ld=None) -> str:
     """the instantiation for 16-byte aligned buffers of these shapes ("none": a descriptor the launch refuses)"""
     d = pad2d_desc(x_shape, pads, mode, 0.0, in_ld, out_ld)
-    return _native.hip().si_hip_pad2d_kernel_name(C.byref(d), C.c_void_p(256), C.c_void_p(256), 1 if half else 0).decode()
+    return _desc_kernel_name("pad2d", d, half)
 
 
 def _pair(v):
@@ -987,16 +1000,9 @@ def adaptive_avgpool2d_desc(x_shape, out_hw, in_ld=None, out_ld=None):
 
 
 def _avgpool2d_run(x, d, in_ld, in_c_off, in_fill, out_ld, out_c_off, out_fill, full):
-    H = _native.hip()
-    half = x.dtype == np.float16
-    n, c = x.shape[0], x.shape[3]
     if d.oh < 1 or d.ow < 1:
         raise HipError("si_hip_avgpool2d: no output for a %dx%d input" % (x.shape[1], x.shape[2]))
-    (dx, px), (dy, py) = _view_in(x, in_ld, in_c_off, in_fill), _view_out((n, d.oh, d.ow), c, out_ld, out_c_off, out_fill, x.dtype)
-    LAST_KERNEL_NAME["si_hip_avgpool2d"] = H.si_hip_avgpool2d_kernel_name(C.byref(d), C.c_void_p(px), C.c_void_p(py), 1 if half else 0).decode()
-    fn, name = (H.si_hip_avgpool2d_f16, "si_hip_avgpool2d_f16") if half else (H.si_hip_avgpool2d_f32, "si_hip_avgpool2d_f32")
-    _chk(fn(C.byref(d), px, py, None), name)
-    return _ret(dy.to_numpy((n, d.oh, d.ow, out_ld or c), x.dtype), c, out_c_off, full)
+    return _run_desc_op("avgpool2d", d, x, (x.shape[0], d.oh, d.ow), x.shape[3], in_ld, in_c_off, in_fill, out_ld, out_c_off, out_fill, full)
 
 
 def avgpool2d(x, k, s=None, p=0, ceil_mode=False, count_include_pad=True, divisor_override=None, in_ld=None, in_c_off=0, in_fill=0.0,
@@ -1021,7 +1027,7 @@ def avgpool2d_kernel_name(x_shape, k=None, s=None, p=0, ceil_mode=False, half=Fa
     adaptive windows instead of k / s / p"""
     d = adaptive_avgpool2d_desc(x_shape, adaptive, in_ld, out_ld) if adaptive is not None else avgpool2d_desc(x_shape, k, s, p, ceil_mode, True, None,
                                                                                                                  in_ld, out_ld)
-    return _native.hip().si_hip_avgpool2d_kernel_name(C.byref(d), C.c_void_p(256), C.c_void_p(256), 1 if half else 0).decode()
+    return _desc_kernel_name("avgpool2d", d, half)
 
 
 def softmax_desc(x_shape, axis, log=False, in_ld=None, out_ld=None):
@@ -1033,23 +1039,16 @@ def softmax_desc(x_shape, axis, log=False, in_ld=None, out_ld=None):
 def softmax(x, axis, log=False, in_ld=None, in_c_off=0, in_fill=0.0, out_ld=None, out_c_off=0, out_fill=0.0, full=False):
     """si_hip_softmax_f32 / _f16 (by the array's dtype) on an NHWC array: torch's softmax / log_softmax (log=True) along the NHWC axis
     `axis` (0 n, 1 h, 2 w, 3 c; negative counts from the end).  The view hooks are the common ones."""
-    H = _native.hip()
     x = _float_storage(x)
-    half = x.dtype == np.float16
     assert x.ndim == 4, "NHWC (a rank-2 [N, F] array is [N, 1, 1, F])"
-    c = x.shape[3]
     d = softmax_desc(x.shape, axis + 4 if axis < 0 else axis, log, in_ld, out_ld)
-    (dx, px), (dy, py) = _view_in(x, in_ld, in_c_off, in_fill), _view_out(x.shape[:-1], c, out_ld, out_c_off, out_fill, x.dtype)
-    LAST_KERNEL_NAME["si_hip_softmax"] = H.si_hip_softmax_kernel_name(C.byref(d), C.c_void_p(px), C.c_void_p(py), 1 if half else 0).decode()
-    fn, name = (H.si_hip_softmax_f16, "si_hip_softmax_f16") if half else (H.si_hip_softmax_f32, "si_hip_softmax_f32")
-    _chk(fn(C.byref(d), px, py, None), name)
-    return _ret(dy.to_numpy(x.shape[:-1] + (out_ld or c,), x.dtype), c, out_c_off, full)
+    return _run_desc_op("softmax", d, x, x.shape[:-1], x.shape[3], in_ld, in_c_off, in_fill, out_ld, out_c_off, out_fill, full)
 
 
 def softmax_kernel_name(x_shape, axis, half=False, in_ld=None, out_ld=None) -> str:
     """the instantiation for 16-byte aligned buffers of these shapes ("none": a descriptor the launch refuses)"""
     d = softmax_desc(x_shape, axis, False, in_ld, out_ld)
-    return _native.hip().si_hip_softmax_kernel_name(C.byref(d), C.c_void_p(256), C.c_void_p(256), 1 if half else 0).decode()
+    return _desc_kernel_name("softmax", d, half)
 
 
 REDUCE_OPS = {"sum": 0, "mean": 1, "amax": 2, "amin": 3}
@@ -1070,24 +1069,17 @@ def reduce_desc(x_shape, op, axes, in_ld=None, out_ld=None):
 def reduce(x, op, axes, in_ld=None, in_c_off=0, in_fill=0.0, out_ld=None, out_c_off=0, out_fill=0.0, full=False):
     """si_hip_reduce_f32 / _f16 (by the array's dtype) on an NHWC array: torch.sum / mean / amax / amin (`op`) over the NHWC axes of the
     bit mask `axes` (1 n, 2 h, 4 w, 8 c), keepdim=True.  The view hooks are the common ones."""
-    H = _native.hip()
     x = _float_storage(x)
-    half = x.dtype == np.float16
     assert x.ndim == 4, "NHWC (a rank-2 [N, F] array is [N, 1, 1, F])"
     d = reduce_desc(x.shape, op, axes, in_ld, out_ld)
     oshape = reduce_out_shape(x.shape, axes if 1 <= int(axes) <= 15 else 0)
-    oc = oshape[3]
-    (dx, px), (dy, py) = _view_in(x, in_ld, in_c_off, in_fill), _view_out(oshape[:-1], oc, out_ld, out_c_off, out_fill, x.dtype)
-    LAST_KERNEL_NAME["si_hip_reduce"] = H.si_hip_reduce_kernel_name(C.byref(d), C.c_void_p(px), C.c_void_p(py), 1 if half else 0).decode()
-    fn, name = (H.si_hip_reduce_f16, "si_hip_reduce_f16") if half else (H.si_hip_reduce_f32, "si_hip_reduce_f32")
-    _chk(fn(C.byref(d), px, py, None), name)
-    return _ret(dy.to_numpy(oshape[:-1] + (out_ld or oc,), x.dtype), oc, out_c_off, full)
+    return _run_desc_op("reduce", d, x, oshape[:-1], oshape[3], in_ld, in_c_off, in_fill, out_ld, out_c_off, out_fill, full)
 
 
 def reduce_kernel_name(x_shape, op, axes, half=False, in_ld=None, out_ld=None) -> str:
     """the instantiation for 16-byte aligned buffers of these shapes ("none": a descriptor the launch refuses)"""
     d = reduce_desc(x_shape, op, axes, in_ld, out_ld)
-    return _native.hip().si_hip_reduce_kernel_name(C.byref(d), C.c_void_p(256), C.c_void_p(256), 1 if half else 0).decode()
+    return _desc_kernel_name("reduce", d, half)
 
 
 PARAM_ACT_OPS = {"clamp": 0, "softplus": 1, "mish": 2}
@@ -1103,23 +1095,16 @@ def param_act_desc(x_shape, op, p0=0.0, p1=0.0, in_ld=None, out_ld=None):
 def param_act(x, op, p0=0.0, p1=0.0, half=False, in_ld=None, in_c_off=0, in_fill=0.0, out_ld=None, out_c_off=0, out_fill=0.0, full=False):
     """si_hip_param_act_f32 / _f16 (half=True, or a float16 array) on an array whose last axis is the channels: clamp (p0 lo, p1 hi),
     softplus (p0 beta, p1 threshold) or mish.  The view hooks are the common ones."""
-    H = _native.hip()
     x = np.asarray(x)
     x = np.ascontiguousarray(x, dtype=np.float16) if (half or x.dtype == np.float16) else _f32(x)
-    half = x.dtype == np.float16
-    c = x.shape[-1]
     d = param_act_desc(x.shape, op, p0, p1, in_ld, out_ld)
-    (dx, px), (dy, py) = _view_in(x, in_ld, in_c_off, in_fill), _view_out(x.shape[:-1], c, out_ld, out_c_off, out_fill, x.dtype)
-    LAST_KERNEL_NAME["si_hip_param_act"] = H.si_hip_param_act_kernel_name(C.byref(d), C.c_void_p(px), C.c_void_p(py), 1 if half else 0).decode()
-    fn, name = (H.si_hip_param_act_f16, "si_hip_param_act_f16") if half else (H.si_hip_param_act_f32, "si_hip_param_act_f32")
-    _chk(fn(C.byref(d), px, py, None), name)
-    return _ret(dy.to_numpy(x.shape[:-1] + (out_ld or c,), x.dtype), c, out_c_off, full)
+    return _run_desc_op("param_act", d, x, x.shape[:-1], x.shape[-1], in_ld, in_c_off, in_fill, out_ld, out_c_off, out_fill, full)
 
 
 def param_act_kernel_name(x_shape, op, p0=0.0, p1=0.0, half=False, in_ld=None, out_ld=None) -> str:
     """the instantiation for 16-byte aligned buffers of these shapes ("none": a descriptor the launch refuses)"""
     d = param_act_desc(x_shape, op, p0, p1, in_ld, out_ld)
-    return _native.hip().si_hip_param_act_kernel_name(C.byref(d), C.c_void_p(256), C.c_void_p(256), 1 if half else 0).decode()
+    return _desc_kernel_name("param_act", d, half)
 
 
 def pixel_shuffle_desc(x_shape, r, inverse=False, in_ld=None, out_ld=None):
@@ -1135,23 +1120,17 @@ def pixel_shuffle_desc(x_shape, r, inverse=False, in_ld=None, out_ld=None):
 def pixel_shuffle(x_nhwc, r, inverse=False, in_ld=None, in_c_off=0, in_fill=0.0, out_ld=None, out_c_off=0, out_fill=0.0, full=False):
     """si_hip_pixel_shuffle_f32 / _f16 (by the array's dtype) on an NHWC array: torch.nn.functional.pixel_shuffle(x, r) of the NCHW
     tensor, or pixel_unshuffle with inverse=True.  The array's bits travel as they are.  The view hooks are the common ones."""
-    H = _native.hip()
     x = _float_storage(x_nhwc)
-    half = x.dtype == np.float16
     d = pixel_shuffle_desc(x.shape, r, inverse, in_ld, out_ld)
     if d.oh < 1 or d.ow < 1 or d.oc < 1:
         raise HipError("si_hip_pixel_shuffle: factor %d leaves no output for a %r input" % (r, tuple(x.shape)))
-    (dx, px), (dy, py) = _view_in(x, in_ld, in_c_off, in_fill), _view_out((d.n, d.oh, d.ow), d.oc, out_ld, out_c_off, out_fill, x.dtype)
-    LAST_KERNEL_NAME["si_hip_pixel_shuffle"] = H.si_hip_pixel_shuffle_kernel_name(C.byref(d), C.c_void_p(px), C.c_void_p(py), 1 if half else 0).decode()
-    fn, name = (H.si_hip_pixel_shuffle_f16, "si_hip_pixel_shuffle_f16") if half else (H.si_hip_pixel_shuffle_f32, "si_hip_pixel_shuffle_f32")
-    _chk(fn(C.byref(d), px, py, None), name)
-    return _ret(dy.to_numpy((d.n, d.oh, d.ow, out_ld or d.oc), x.dtype), d.oc, out_c_off, full)
+    return _run_desc_op("pixel_shuffle", d, x, (d.n, d.oh, d.ow), d.oc, in_ld, in_c_off, in_fill, out_ld, out_c_off, out_fill, full)
 
 
 def pixel_shuffle_kernel_name(x_shape, r, inverse=False, half=False, in_ld=None, out_ld=None) -> str:
     """the form for 16-byte aligned buffers of these shapes ("none": a descriptor the launch refuses)"""
     d = pixel_shuffle_desc(x_shape, r, inverse, in_ld, out_ld)
-    return _native.hip().si_hip_pixel_shuffle_kernel_name(C.byref(d), C.c_void_p(256), C.c_void_p(256), 1 if half else 0).decode()
+    return _desc_kernel_name("pixel_shuffle", d, half)
 
 
 def prelu(x, slope, in_ld=None, in_c_off=0, in_fill=0.0, out_ld=None, out_c_off=0, out_fill=0.0, full=False):
@@ -1203,24 +1182,18 @@ def slice_desc(x_shape, index, in_ld=None, out_ld=None):
 def slice(x, index, in_ld=None, in_c_off=0, in_fill=0.0, out_ld=None, out_c_off=0, out_fill=0.0, full=False):
     """si_hip_slice_f32 / _f16 (by the array's dtype): x[index] of an NHWC (or [N, F]) array, index as in slice_desc.  The array's bits
     travel as they are.  The view hooks are the common ones."""
-    H = _native.hip()
     x = _float_storage(x)
-    half = x.dtype == np.float16
     d = slice_desc(x.shape, index, in_ld, out_ld)
     if min(d.on, d.oh, d.ow, d.oc) < 1:
         raise HipError("si_hip_slice: %r of a %r input is empty" % (index, tuple(x.shape)))
     oshape = (d.on, d.oh, d.ow) if x.ndim == 4 else (d.on,)
-    (dx, px), (dy, py) = _view_in(x, in_ld, in_c_off, in_fill), _view_out(oshape, d.oc, out_ld, out_c_off, out_fill, x.dtype)
-    LAST_KERNEL_NAME["si_hip_slice"] = H.si_hip_slice_kernel_name(C.byref(d), C.c_void_p(px), C.c_void_p(py), 1 if half else 0).decode()
-    fn, name = (H.si_hip_slice_f16, "si_hip_slice_f16") if half else (H.si_hip_slice_f32, "si_hip_slice_f32")
-    _chk(fn(C.byref(d), px, py, None), name)
-    return _ret(dy.to_numpy(oshape + (out_ld or d.oc,), x.dtype), d.oc, out_c_off, full)
+    return _run_desc_op("slice", d, x, oshape, d.oc, in_ld, in_c_off, in_fill, out_ld, out_c_off, out_fill, full)
 
 
 def slice_kernel_name(x_shape, index, half=False, in_ld=None, out_ld=None) -> str:
     """the form for 16-byte aligned buffers of these shapes ("none": a descriptor the launch refuses)"""
     d = slice_desc(x_shape, index, in_ld, out_ld)
-    return _native.hip().si_hip_slice_kernel_name(C.byref(d), C.c_void_p(256), C.c_void_p(256), 1 if half else 0).decode()
+    return _desc_kernel_name("slice", d, half)
 
 
 def _split_args(widths, offsets, out_lds, ptrs):
