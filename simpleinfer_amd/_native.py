@@ -118,6 +118,12 @@ class SiPermuteDesc(C.Structure):
     _fields_ = [("rank", C.c_int), ("dims", C.c_int * 4), ("in_stride", C.c_longlong * 4), ("out_ld", C.c_int), ("form", C.c_int)]
 
 
+class SiAttentionDesc(C.Structure):
+    """include/si_attention.h; sb / ss: element strides of the batch index and of the sequence index"""
+    _fields_ = [(k, C.c_int) for k in ("batch", "heads", "lq", "lk", "d")] + [
+        (k, C.c_longlong) for k in ("q_sb", "q_ss", "k_sb", "k_ss", "v_sb", "v_ss", "o_sb", "o_ss")] + [("scale", C.c_float)]
+
+
 class SiLayoutNest(C.Structure):
     """include/si_layout.h; what si_layout_plan returns: view != 0, or the loop nest of the copy"""
     _fields_ = [("view", C.c_int), ("rank", C.c_int), ("dims", C.c_int * 8), ("in_stride", C.c_longlong * 8)]
@@ -349,8 +355,15 @@ def hip():
         "si_hip_permute_f16": (i, [C.POINTER(SiPermuteDesc), vp, vp, vp]),
         "si_hip_permute_kernel_name": (C.c_char_p, [C.POINTER(SiPermuteDesc), vp, vp, i]),
     }
+    # include/si_attention.h: fused scaled dot-product attention, the kernel of nn.MultiheadAttention
+    attention_ = {
+        "si_hip_attention_f32": (i, [C.POINTER(SiAttentionDesc), vp, vp, vp, vp, vp]),
+        "si_hip_attention_f16": (i, [C.POINTER(SiAttentionDesc), vp, vp, vp, vp, vp]),
+        "si_hip_attention_kernel_name": (C.c_char_p, [C.POINTER(SiAttentionDesc), vp, vp, vp, vp, i]),
+    }
     for name, (res, args) in (list(sig.items()) + list(norm.items()) + list(pad.items()) + list(pool.items()) + list(softmax.items()) +
-                              list(superres.items()) + list(slice_.items()) + list(reduce_.items()) + list(act.items()) + list(permute_.items())):
+                              list(superres.items()) + list(slice_.items()) + list(reduce_.items()) + list(act.items()) + list(permute_.items()) +
+                              list(attention_.items())):
         fn = getattr(L, name)  # AttributeError here = header/library mismatch, which tests check
         fn.restype = res
         fn.argtypes = args
@@ -364,6 +377,7 @@ def hip():
     L._si_reduce_signatures = reduce_
     L._si_act_signatures = act
     L._si_permute_signatures = permute_
+    L._si_attention_signatures = attention_
     _hip = L
     return L
 

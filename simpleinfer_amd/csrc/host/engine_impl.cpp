@@ -192,6 +192,37 @@ Status EngineImpl::DestroyGraph() {
     return Status::kSuccess;
 }
 
+// The dimension of `out` that carries the batch when dimension `axis` of the operator's input `in` does (file-order shapes; -1: not known).
+// permute / transpose move it by their arguments; for everything else -- reshapes, flatten, and every operator that keeps the leading
+// dimensions -- it is the dimension of `out` that holds the traced batch behind the same number of leading elements.
+static int FollowBatchAxis(const pnnx::Operator* op, const std::vector<int>& in, int axis, const std::vector<int>& out, int file_batch) {
+    const int ir = (int)in.size(), orank = (int)out.size();
+    if (axis < 0 || axis >= ir || in[axis] != file_batch) return -1;
+    auto at = [&](int j) { return j >= 0 && j < orank && out[j] == file_batch ? j : -1; };
+    auto norm = [&](int d) { return d < 0 ? d + ir : d; };
+    if (op->type == "Tensor.permute" || op->type == "torch.permute") {
+        std::vector<int> dims;
+        if (!Get(op, "dims", dims)) return -1;
+        for (int j = 0; j < (int)dims.size(); ++j)
+            if (norm(dims[j]) == axis) return at(j);
+        return -1;
+    }
+    if (op->type == "torch.transpose") {
+        int d0 = 0, d1 = 0;
+        if (!Get(op, "dim0", d0) || !Get(op, "dim1", d1)) return -1;
+        d0 = norm(d0); d1 = norm(d1);
+        return at(axis == d0 ? d1 : axis == d1 ? d0 : axis);
+    }
+    long long lead = 1, seen = 1;
+    for (int k = 0; k < axis; ++k) lead *= in[k];
+    for (int j = 0; j < orank; ++j) {
+        if (seen == lead && out[j] == file_batch) return j;
+        seen *= out[j];
+        if (seen > lead) break;
+    }
+    return -1;
+}
+
 Status EngineImpl::CreateTensorNodes() {
     // Re-batch (SetOption("batch", N)): a pnnx file carries the batch it was traced with in every operand shape
     // (#0=(N,3,640,640)f32).  Every operator here is per-image, so serving another batch is a rewrite of
@@ -211,6 +242,39 @@ Status EngineImpl::CreateTensorNodes() {
             return Status::kUnsupport;
         }
     }
+    // ... wherever it equals the traced batch -- except where the graph itself has moved the batch to another dimension: seq-first token
+    // tensors [L, N, E] (conv -> flatten(2) -> permute(2, 0, 1) in front of nn.MultiheadAttention) carry it in dimension 1.  The batch
+    // dimension of every operand is followed from the graph inputs (dimension 0) through the operators; an operand whose batch sits in a
+    // dimension >= 1 has THAT dimension rewritten and dimension 0 left alone, every other operand keeps the rule above.
+    std::map<const pnnx::Operand*, int> batch_axis;
+    if (file_batch > 0) {
+        for (const pnnx::Operator* op : graph_->ops) {
+            const pnnx::Operand* src = nullptr;
+            int axis = -1;
+            for (const pnnx::Operand* in : op->inputs) {
+                auto it = batch_axis.find(in);
+                if (it != batch_axis.end() && it->second >= 0) { src = in; axis = it->second; break; }
+            }
+            for (const pnnx::Operand* out : op->outputs) {
+                if (op->inputs.empty()) batch_axis[out] = (!out->shape.empty() && out->shape[0] == file_batch) ? 0 : -1;
+                else batch_axis[out] = src ? FollowBatchAxis(op, src->shape, axis, out->shape, file_batch) : -1;
+            }
+            if (op->type == "nn.MultiheadAttention") {
+                // the layer reads the batch from dimension 0 (batch_first) or 1 of its operands: the rewrite has to have reached that one
+                bool batch_first = false;
+                Get(op, "batch_first", batch_first);
+                for (const pnnx::Operand* in : op->inputs) {
+                    auto it = batch_axis.find(in);
+                    if (it == batch_axis.end() || it->second != (batch_first ? 0 : 1)) {
+                        LOG(ERROR) << "re-batch: [" << op->name << "] nn.MultiheadAttention with batch_first=" << (batch_first ? "True" : "False")
+                                   << " reads the batch from dimension " << (batch_first ? 0 : 1) << " of operand [" << in->name
+                                   << "], which the graph does not carry there from a batch-major graph input: served at the file's batch only";
+                        return Status::kUnsupport;
+                    }
+                }
+            }
+        }
+    }
     for (pnnx::Operand* opd : graph_->operands) {
         if (tensor_nodes_.count(opd->name) > 0) {
             LOG(ERROR) << "tensor node [" << opd->name << "] already exists";
@@ -220,13 +284,16 @@ Status EngineImpl::CreateTensorNodes() {
         node->operand = opd;
 
         // file shapes are NCHW; tensors are NHWC: the last three dims C,H,W -> H,W,C for rank >= 4
-        std::vector<int> shape = opd->shape;
-        if (file_batch > 0 && !shape.empty() && shape[0] == file_batch) shape[0] = opt_batch_;
+        std::vector<int> file = opd->shape;
+        auto moved = batch_axis.find(opd);
+        if (moved != batch_axis.end() && moved->second >= 1) file[moved->second] = opt_batch_;
+        else if (file_batch > 0 && !file.empty() && file[0] == file_batch) file[0] = opt_batch_;
+        std::vector<int> shape = file;
         const int rank = (int)shape.size();
         if (rank > 3) {
-            shape[rank - 3] = opd->shape[rank - 2];
-            shape[rank - 2] = opd->shape[rank - 1];
-            shape[rank - 1] = opd->shape[rank - 3];
+            shape[rank - 3] = file[rank - 2];
+            shape[rank - 2] = file[rank - 1];
+            shape[rank - 1] = file[rank - 3];
         }
         DataType dt = PnnxToDataType(opd->type);
         // graph inputs: produced by an operator with no inputs (pnnx.Input)

@@ -50,4 +50,17 @@ Status Flatten::Forward(const Tensor& input, Tensor& output) {
     });
 }
 
+bool Flatten::HalfStorageOk(std::string& why) const {
+    if (!Layer::HalfStorageOk(why)) return false;
+    if (input_tensor_nodes_.empty() || !IsHalf(input_tensor_nodes_[0]->tensor)) return true;
+    const Tensor& in = input_tensor_nodes_[0]->tensor;
+    Dims4 d;
+    if (GetDims4(in, d) && d.h * d.w != 1) { why = "Flatten re-orders a map with H * W > 1 in fp32 only"; return false; }
+    if (in.Shape().empty() || in.Shape().back() % 2 != 0 || in.PixelStride() % 2 != 0) {
+        why = "Flatten copies halves in pairs: an even channel count and pixel stride";
+        return false;
+    }
+    return true;
+}
+
 }  // namespace SimpleInfer

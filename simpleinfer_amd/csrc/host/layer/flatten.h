@@ -14,6 +14,8 @@ public:
     virtual Status Validate() override;
     virtual Status Forward(const Tensor& input, Tensor& output) override;
     virtual const char* KernelName() const override { return "nhwc_to_nchw"; }
+    // fp16 storage: only the permutation-free case has a half path; a map with H * W > 1 runs in fp32 between casts
+    virtual bool HalfStorageOk(std::string& why) const override;
 
 public:
     int start_dim_ = 0;

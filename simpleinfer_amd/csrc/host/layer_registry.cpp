@@ -24,6 +24,7 @@ SI_DECLARE_LAYER(Layout)
 SI_DECLARE_LAYER(LeakyReLU)
 SI_DECLARE_LAYER(Linear)
 SI_DECLARE_LAYER(MaxPool2d)
+SI_DECLARE_LAYER(MultiheadAttention)
 SI_DECLARE_LAYER(Pad2d)
 SI_DECLARE_LAYER(ParamActivation)
 SI_DECLARE_LAYER(PixelShuffle)
@@ -54,7 +55,8 @@ static std::map<std::string, LayerRegistryEntry>& Table() {
     // torch.clamp / nn.Softplus / nn.Mish and their F.* spellings (one class, layer/param_activation.h: never folded into an epilogue); the
     // functional spellings of the activations above, on the classes of their nn.* twins (they fuse as those do; F.tanh, like nn.Tanh, does not);
     // Tensor.permute / torch.permute / Tensor.reshape / Tensor.view / torch.transpose / torch.squeeze / torch.unsqueeze / Tensor.contiguous (one
-    // class, layer/layout.h: the layout algebra of layout_plan.h decides between a view and one permute launch)
+    // class, layer/layout.h: the layout algebra of layout_plan.h decides between a view and one permute launch); nn.MultiheadAttention
+    // (layer/multihead_attention.h: two projections around the fused attention kernel of include/si_attention.h)
     static std::map<std::string, LayerRegistryEntry> table = {
         SI_ENTRY("nn.AdaptiveAvgPool2d", AdaptiveAvgPool2d),
         SI_ENTRY("nn.AvgPool2d", AvgPool2d),
@@ -74,6 +76,7 @@ static std::map<std::string, LayerRegistryEntry>& Table() {
         SI_ENTRY("nn.LogSoftmax", Softmax),
         SI_ENTRY("nn.Linear", Linear),
         SI_ENTRY("nn.MaxPool2d", MaxPool2d),
+        SI_ENTRY("nn.MultiheadAttention", MultiheadAttention),
         SI_ENTRY("nn.PixelShuffle", PixelShuffle),
         SI_ENTRY("nn.PixelUnshuffle", PixelShuffle),
         SI_ENTRY("nn.PReLU", PReLU),

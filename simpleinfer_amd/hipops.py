@@ -1051,6 +1051,67 @@ def softmax_kernel_name(x_shape, axis, half=False, in_ld=None, out_ld=None) -> s
     return _desc_kernel_name("softmax", d, half)
 
 
+def attention_desc(batch, heads, lq, lk, d, scale=None, batch_first=False, q_ld=None, k_ld=None, v_ld=None, out_ld=None):
+    """SiAttentionDesc (include/si_attention.h) of token tensors [L, N, E] (seq-first) or [N, L, E] (batch_first) with E = heads * d, whose
+    token rows are q_ld / k_ld / v_ld / out_ld elements apart (default E: dense).  scale defaults to 1 / sqrt(d) in float32."""
+    e = int(heads) * int(d)
+
+    def strides(length, ld):
+        ld = int(ld or e)
+        return (int(length) * ld, ld) if batch_first else (ld, int(batch) * ld)
+
+    dsc = _native.SiAttentionDesc()
+    dsc.batch, dsc.heads, dsc.lq, dsc.lk, dsc.d = int(batch), int(heads), int(lq), int(lk), int(d)
+    (dsc.q_sb, dsc.q_ss), (dsc.k_sb, dsc.k_ss) = strides(lq, q_ld), strides(lk, k_ld)
+    (dsc.v_sb, dsc.v_ss), (dsc.o_sb, dsc.o_ss) = strides(lk, v_ld), strides(lq, out_ld)
+    dsc.scale = float(np.float32(1.0) / np.sqrt(np.float32(d))) if scale is None else float(scale)
+    return dsc
+
+
+def attention(q, k, v, heads, scale=None, batch_first=False, packed=False, in_ld=None, in_c_off=0, in_fill=0.0, out_ld=None, out_c_off=0,
+              out_fill=0.0, full=False):
+    """si_hip_attention_f32 / _f16 (by q's dtype): softmax(scale * q k^T) v per (batch item, head) on token arrays [L, N, E] (seq-first) or
+    [N, L, E] (batch_first), E = heads * d; k and v share their length, which may differ from q's.  The view hooks are the common ones: every
+    input is the column slice [in_c_off, in_c_off + E) of rows of in_ld elements, the rest holding in_fill; packed=True (lq == lk) makes the
+    three inputs the neighbouring slices q | k | v, from in_c_off on, of ONE buffer of rows of in_ld (default 3 E) elements, as the layer's
+    projection workspace is.  The destination is the slice [out_c_off, out_c_off + E) of rows of out_ld elements pre-filled with out_fill;
+    full=True returns the whole rows."""
+    H = _native.hip()
+    q, k, v = _float_storage(q), _float_storage(np.asarray(k)), _float_storage(np.asarray(v))
+    assert q.ndim == k.ndim == v.ndim == 3 and q.dtype == k.dtype == v.dtype and k.shape == v.shape and q.shape[2] == k.shape[2], (q.shape, k.shape, v.shape)
+    half = q.dtype == np.float16
+    e = q.shape[2]
+    assert e % heads == 0, (e, heads)
+    batch, lq, lk = (q.shape[0], q.shape[1], k.shape[1]) if batch_first else (q.shape[1], q.shape[0], k.shape[0])
+    assert (k.shape[0] if batch_first else k.shape[1]) == batch
+    if packed:
+        assert q.shape == k.shape, "one [rows, 3E] buffer: lq == lk"
+        ld = in_ld or 3 * e
+        assert in_c_off >= 0 and in_c_off + 3 * e <= ld, (in_c_off, e, ld)
+        w = _full(q.shape[:-1] + (ld,), q.dtype, in_fill)
+        for j, t in enumerate((q, k, v)):
+            w[..., in_c_off + j * e:in_c_off + (j + 1) * e] = t
+        dw = DeviceBuffer.from_numpy(w)
+        pq, pk, pv = (dw.ptr + q.itemsize * (in_c_off + j * e) for j in range(3))
+    else:
+        ld = in_ld or e
+        (dq, pq), (dk, pk), (dv, pv) = (_view_in(t, in_ld, in_c_off, in_fill) for t in (q, k, v))
+    d = attention_desc(batch, heads, lq, lk, e // heads, scale, batch_first, ld, ld, ld, out_ld or e)
+    dy, py = _view_out(q.shape[:-1], e, out_ld, out_c_off, out_fill, q.dtype)
+    LAST_KERNEL_NAME["si_hip_attention"] = H.si_hip_attention_kernel_name(C.byref(d), C.c_void_p(pq), C.c_void_p(pk), C.c_void_p(pv), C.c_void_p(py),
+                                                                         1 if half else 0).decode()
+    name = "si_hip_attention_f16" if half else "si_hip_attention_f32"
+    _chk(getattr(H, name)(C.byref(d), pq, pk, pv, py, None), name)
+    return _ret(dy.to_numpy(q.shape[:-1] + (out_ld or e,), q.dtype), e, out_c_off, full)
+
+
+def attention_kernel_name(d, half=False, heads=1, align=256) -> str:
+    """the instantiation for dense seq-first tensors of head dim d at 16-byte aligned (align=256) addresses; "none": a refused descriptor"""
+    dsc = attention_desc(1, heads, 1, 1, d)
+    p = [C.c_void_p(int(align) + 65536 * j) for j in range(4)]
+    return _native.hip().si_hip_attention_kernel_name(C.byref(dsc), p[0], p[1], p[2], p[3], 1 if half else 0).decode()
+
+
 REDUCE_OPS = {"sum": 0, "mean": 1, "amax": 2, "amin": 3}
 
 

@@ -556,22 +556,50 @@ class PnnxBuilder:
                    self._norm_affine(name, c) if affine else {})
         return out
 
-    def flatten(self, x: str) -> str:
+    def flatten(self, x: str, start_dim: int = 1) -> str:
         shp = self.shapes[x]
-        out = self._new_operand((shp[0], int(np.prod(shp[1:]))))
-        self._emit("torch.flatten", self._opname("flatten"), [x], [out], dict(end_dim=-1, start_dim=1))
+        out = self._new_operand(tuple(shp[:start_dim]) + (int(np.prod(shp[start_dim:])),))
+        self._emit("torch.flatten", self._opname("flatten"), [x], [out], dict(end_dim=-1, start_dim=int(start_dim)))
         return out
 
     def linear(self, x: str, out_f: int, bias: bool = True) -> str:
-        n, in_f = self.shapes[x]
+        """nn.Linear over the last dimension of an operand of any rank >= 2 ([N, F]; token tensors [L, N, E] / [N, L, E])"""
+        *lead, in_f = self.shapes[x]
         name = self._opname("linear")
         a = math.sqrt(3.0 / in_f)
         attrs = {"weight": seeded_uniform(name + ".weight", (out_f, in_f), -a, a, self.seed),
                  # the reference requires the attribute even for bias=False (SURVEY Q3)
                  "bias": seeded_uniform(name + ".bias", (out_f,), -0.1, 0.1, self.seed)}
-        out = self._new_operand((n, out_f))
+        out = self._new_operand(tuple(lead) + (out_f,))
         self._emit("nn.Linear", name, [x], [out], dict(bias=bool(bias), in_features=in_f, out_features=out_f), attrs)
         return out
+
+    def multihead_attention(self, q: str, k: str = None, v: str = None, num_heads: int = 1, bias: bool = True, batch_first: bool = False,
+                            add_bias_kv: bool = False, add_zero_attn: bool = False, kdim: int = None, vdim: int = None,
+                            need_weights: bool = False) -> str:
+        """pnnx's nn.MultiheadAttention line: 1 input (self-attention), 2 (query; key = value) or 3 (query, key, value), rank-3 operands
+        [L, N, E], or [N, L, E] with batch_first; params embed_dim, num_heads, bias, batch_first, add_bias_kv, add_zero_attn, kdim, vdim;
+        attributes in_proj_weight (3E, E), out_proj.weight (E, E) and, with bias, in_proj_bias (3E) / out_proj.bias (E).  need_weights adds
+        the second output operand [N, Lq, Lk] (the engine refuses it)."""
+        ins = [q] + ([k] if k is not None else []) + ([v] if v is not None else [])
+        assert v is None or k is not None
+        e = self.shapes[q][-1]
+        name = self._opname("attention")
+        a = math.sqrt(3.0 / e)
+        attrs = {"in_proj_weight": seeded_uniform(name + ".in_proj_weight", (3 * e, e), -a, a, self.seed),
+                 "out_proj.weight": seeded_uniform(name + ".out_proj.weight", (e, e), -a, a, self.seed)}
+        if bias:
+            attrs["in_proj_bias"] = seeded_uniform(name + ".in_proj_bias", (3 * e,), -0.1, 0.1, self.seed)
+            attrs["out_proj.bias"] = seeded_uniform(name + ".out_proj.bias", (e,), -0.1, 0.1, self.seed)
+        outs = [self._new_operand(self.shapes[q])]
+        if need_weights:
+            kshape = self.shapes[ins[1] if len(ins) > 1 else q]
+            bi, li = (0, 1) if batch_first else (1, 0)
+            outs.append(self._new_operand((self.shapes[q][bi], self.shapes[q][li], kshape[li])))
+        self._emit("nn.MultiheadAttention", name, ins, outs,
+                   dict(add_bias_kv=bool(add_bias_kv), add_zero_attn=bool(add_zero_attn), batch_first=bool(batch_first), bias=bool(bias),
+                        embed_dim=e, kdim=e if kdim is None else int(kdim), num_heads=int(num_heads), vdim=e if vdim is None else int(vdim)), attrs)
+        return outs[0]
 
     def detect(self, xs: Sequence[str], strides=(8.0, 16.0, 32.0), anchors=None, nc: int = 80) -> str:
         """models.yolo.Detect -- attribute names per reference src/layer/yolo_detect.cpp:19-145."""
@@ -1040,6 +1068,40 @@ def build_toy_view_classifier(batch: int = 2, size: int = 32, pool: int = 1, ncl
     x = b.adaptive_avgpool(x, (pool, pool))
     x = b.flatten(x) if flatten else b.view(x, (batch, -1))
     b.output(b.linear(x, ncls))
+    return b
+
+
+def build_toy_c3tr(batch: int = 2, size: int = 32, c: int = 32, heads: int = 4, layers: int = 2, seed: int = 0) -> PnnxBuilder:
+    """YOLOv5's C3TR / TransformerBlock as its export writes it: conv -> torch.flatten(start_dim=2) -> Tensor.permute(2, 0, 1) ->
+    p + linear(p); per layer three bias-free Linears -> nn.MultiheadAttention with 3 inputs -> + x -> fc2(fc1(x)) + x (no LayerNorm, no
+    activation); then permute(1, 2, 0) -> reshape(b, c, w, h) -> conv.  Tokens are seq-first [L, N, E]."""
+    b = PnnxBuilder(seed)
+    x = b.silu(b.conv(b.input((batch, 3, size, size)), c, 3, 2, 1))
+    x = b.silu(b.conv(x, c, 3, 2, 1))
+    _, _, h, w = b.shapes[x]
+    p = b.permute(b.flatten(x, 2), (2, 0, 1))
+    x = b.add(p, b.linear(p, c))
+    for _ in range(layers):
+        q, k, v = (b.linear(x, c, bias=False) for _ in range(3))
+        x = b.add(b.multihead_attention(q, k, v, num_heads=heads), x)
+        x = b.add(b.linear(b.linear(x, c, bias=False), c, bias=False), x)
+    x = b.reshape(b.permute(x, (1, 2, 0)), (batch, c, w, h))
+    b.output(b.silu(b.conv(x, c, 1)))
+    return b
+
+
+def build_toy_mhsa_head(batch: int = 2, size: int = 16, c: int = 24, heads: int = 3, seed: int = 0) -> PnnxBuilder:
+    """A self-attention pooling head on batch-first tokens: convs -> permute(0, 2, 3, 1) -> view(N, -1, C) (a view, not a launch) ->
+    nn.MultiheadAttention(batch_first=True) with one input -> the mean over the tokens -> nn.Linear.  The mean is written on the feature map
+    the tokens came from, permute(0, 2, 1) -> view(N, C, H, W) (again a view) -> mean((2, 3)): reductions over a rank-3 operand are not served."""
+    b = PnnxBuilder(seed)
+    x = b.relu(b.conv(b.input((batch, 3, size, size)), 16, 3, 2, 1))
+    x = b.relu(b.conv(x, c, 3, 1, 1))
+    _, _, h, w = b.shapes[x]
+    t = b.view(b.permute(x, (0, 2, 3, 1)), (batch, -1, c))
+    t = b.multihead_attention(t, num_heads=heads, batch_first=True)
+    m = b.mean(b.view(b.permute(t, (0, 2, 1)), (batch, c, h, w)), (2, 3))
+    b.output(b.linear(m, 10))
     return b
 
 
