@@ -93,17 +93,22 @@ public:
     //   "batch"           N>0  serve batch N whatever batch the .param file was traced with (default 0: as in the file)
     //   "host_slices"     G    host tensors in (Input) and out (Extract) -- the reference's calling convention: one synchronous
     //                          Forward() pipelines G batch slices over an upload, a compute and a download stream; 1 = off,
-    //                          0 (default) = slices of 8 images from batch 32 on, of 4 for batches 8 .. 31 (graphs of built-in
-    //                          layers only: the model is loaded a second time re-batched to N / G, which assumes per-image
-    //                          operators; a graph holding a RegisterLayer type is sliced only on an explicit G > 1).  If the
-    //                          pipeline cannot be set up the engine logs it and serves unsliced.
+    //                          0 (default) = slices of 8 images from batch 32 on, of 4 for batches 8 .. 31.  The model is loaded a
+    //                          second time re-batched to N / G, which is the same computation only when every operator of the graph
+    //                          is per-image.  The engine checks that (BatchMixingLayers() below): a graph with a softmax or a
+    //                          reduction over the batch, a slice / chunk / cat along it, a view that folds it, a broadcast over it, an
+    //                          output whose batch is not dimension 0, or a RegisterLayer type is served unsliced -- said once at
+    //                          INFO under 0, as an ERROR naming the layer under an explicit G > 1.  If the pipeline cannot be set up
+    //                          the engine logs it and serves unsliced.
     //   "pin_inputs"      1/0  host_slices only: a borrowed input buffer handed over for a second Forward() in a row is pinned IN
     //                          PLACE (hipHostRegister) so its uploads run at link rate.  Default 0, opt-in: the registration
     //                          outlives Forward(), so the caller must keep the buffer mapped -- not free or reallocate it --
     //                          until the next Input() for that name or Release(), which unregister it; and must not hand the
     //                          same buffer to a second engine meanwhile.  Without it the uploads are staged copies.
     //   "streams"         1/2  2: the batch runs as two half-batch lanes on two streams (default 1: no gain measured since the
-    //                          tile policy follows the launch size); with 2 the lanes, not host_slices, serve host tensors
+    //                          tile policy follows the launch size); with 2 the lanes, not host_slices, serve host tensors.  A lane
+    //                          is the model re-batched to N / 2: LoadModel returns kUnsupport, with the layer named in the log, for
+    //                          an odd batch and for a graph that holds an operator which is not per-image (BatchMixingLayers())
     //   "detect_stream"   0/1/2  YOLOv5 Detect's finer levels on a second stream: 0 never, 1 (default) for levels with enough work,
     //                          2 always
     //   "detect_priority" -1/0/1  priority of that second stream: 0 (default) the device's default; -1 the lowest (the neck on the main
@@ -130,6 +135,11 @@ public:
 
     // timing of the most recent Forward() measured with HIP events on the engine stream
     float LastForwardMs();
+
+    // The operators of the loaded graph that combine images of the batch, one "[layer] (type): reason" each; empty for a graph of
+    // per-image operators.  With any, the engine never cuts the batch into slabs ("host_slices", "streams"), and ShardedEngine
+    // refuses the engine for more than one rank.  "batch" alone is not affected: such a graph re-batched to N is a model of N images.
+    std::vector<std::string> BatchMixingLayers();
 
 private:
     EngineImpl* impl_ = nullptr;

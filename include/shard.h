@@ -36,7 +36,8 @@ public:
 
     // Collective over the node's ranks.  `group_name`: POSIX shm name ("/...") unique to the job, the same on every
     // rank.  `engine` must have a model loaded with device-resident outputs (SetOption("outputs_to_host", 0)); its
-    // output operand `output_name` is re-bound into this object's gathered buffers (Engine::Output).
+    // output operand `output_name` is re-bound into this object's gathered buffers (Engine::Output).  With world > 1 a graph
+    // that holds an operator which combines images (Engine::BatchMixingLayers()) is refused: kUnsupport, before any rank waits.
     Status Init(const std::string& group_name, int rank, int world, Engine* engine, const std::string& output_name,
                 int slots = 4, double timeout_s = 60.0, GatherMode gather = GatherMode::kAuto);
     GatherMode Mode() const;   // kDirect or kRccl: what Init ended up with

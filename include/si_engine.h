@@ -55,7 +55,10 @@ int si_engine_profile(SiEngine* engine);
 int si_engine_profile_entry(SiEngine* engine, int index, const char** op_name, const char** op_type,
                             const char** kernel, float* ms, double* flops, double* bytes);
 /* text description of the launch schedule: "run <op>", "fused <op>", "alias <operand>" lines, then "arena_bytes <n>" (HBM held
- * for intermediate operands, shared by lifetime) and "per_operand_bytes <n>" (what one allocation per operand would take) */
+ * for intermediate operands, shared by lifetime) and "per_operand_bytes <n>" (what one allocation per operand would take),
+ * "lanes <n>" (option "streams"), "host_slices <G>" (the pipelined batch slices the last Forward ran as; 1: unsliced),
+ * "split_reruns <n>" / "split_demoted <conv>" (the f32_split range guard) and one "batch_mixing <layer> <reason>" line per
+ * operator that combines images of the batch: with any, the batch is never cut (host_slices, streams, ShardedEngine) */
 int si_engine_schedule(SiEngine* engine, char* buf, size_t cap);
 
 /* Loader check: parse a .pnnx.param/.bin with THIS library's pnnx loader (optionally lowering

@@ -30,6 +30,12 @@ Status Engine::Profile(std::vector<LayerProfile>& layers) { return impl_->Profil
 void* Engine::Stream() { return impl_->Stream(); }
 float Engine::LastForwardMs() { return impl_->LastForwardMs(); }
 
+std::vector<std::string> Engine::BatchMixingLayers() {
+    std::vector<std::string> out;
+    for (const BatchMixingEntry& m : impl_->BatchMixing()) out.push_back("[" + m.layer + "] (" + m.type + "): " + m.reason);
+    return out;
+}
+
 void InitializeContext() { InitializeLogger(); }
 
 }  // namespace SimpleInfer

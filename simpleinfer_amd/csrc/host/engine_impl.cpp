@@ -4,6 +4,7 @@
 
 #include <algorithm>
 
+#include "batch_rule.h"
 #include "layer/conv_2d.h"
 #include "layer/yolo_detect.h"
 #include "engine_internal.h"
@@ -97,6 +98,7 @@ Status EngineImpl::LoadModel(const std::string& parampath, const std::string& bi
     }
     param_path_ = parampath;
     bin_path_ = binpath;
+    if (!is_lane_) FindBatchMixingLayers();   // (a lane or the slicer's engine is a re-batched copy of a graph that has passed)
     {
         Status ret = CreateTensorNodes();
         if (Status::kSuccess != ret) {
@@ -189,44 +191,29 @@ Status EngineImpl::CreateGraph(const std::string& parampath, const std::string& 
 Status EngineImpl::DestroyGraph() {
     delete graph_;
     graph_ = nullptr;
+    batch_mixing_.clear();
+    mixing_logged_ = false;
     return Status::kSuccess;
 }
 
-// The dimension of `out` that carries the batch when dimension `axis` of the operator's input `in` does (file-order shapes; -1: not known).
-// permute / transpose move it by their arguments; for everything else -- reshapes, flatten, and every operator that keeps the leading
-// dimensions -- it is the dimension of `out` that holds the traced batch behind the same number of leading elements.
-static int FollowBatchAxis(const pnnx::Operator* op, const std::vector<int>& in, int axis, const std::vector<int>& out, int file_batch) {
-    const int ir = (int)in.size(), orank = (int)out.size();
-    if (axis < 0 || axis >= ir || in[axis] != file_batch) return -1;
-    auto at = [&](int j) { return j >= 0 && j < orank && out[j] == file_batch ? j : -1; };
-    auto norm = [&](int d) { return d < 0 ? d + ir : d; };
-    if (op->type == "Tensor.permute" || op->type == "torch.permute") {
-        std::vector<int> dims;
-        if (!Get(op, "dims", dims)) return -1;
-        for (int j = 0; j < (int)dims.size(); ++j)
-            if (norm(dims[j]) == axis) return at(j);
-        return -1;
+// The operators of the graph that combine images (batch_rule.h), in file order: what keeps "host_slices", "streams" and ShardedEngine from
+// cutting the batch.  A layer type registered at run time (RegisterLayer, also one that replaced a built-in) is one of them: the engine knows
+// nothing about such a layer beyond the Layer interface.
+void EngineImpl::FindBatchMixingLayers() {
+    batch_mixing_ = FindBatchMixing(graph_->ops);
+    for (const pnnx::Operator* op : graph_->ops) {
+        if (!IsUserRegisteredLayer(op->type)) continue;
+        bool listed = false;
+        for (const BatchMixingEntry& m : batch_mixing_) listed = listed || m.layer == op->name;
+        if (!listed) batch_mixing_.push_back({op->name, op->type, "the layer type was registered at run time, so nothing is known about how it treats the batch"});
     }
-    if (op->type == "torch.transpose") {
-        int d0 = 0, d1 = 0;
-        if (!Get(op, "dim0", d0) || !Get(op, "dim1", d1)) return -1;
-        d0 = norm(d0); d1 = norm(d1);
-        return at(axis == d0 ? d1 : axis == d1 ? d0 : axis);
-    }
-    long long lead = 1, seen = 1;
-    for (int k = 0; k < axis; ++k) lead *= in[k];
-    for (int j = 0; j < orank; ++j) {
-        if (seen == lead && out[j] == file_batch) return j;
-        seen *= out[j];
-        if (seen > lead) break;
-    }
-    return -1;
 }
 
 Status EngineImpl::CreateTensorNodes() {
     // Re-batch (SetOption("batch", N)): a pnnx file carries the batch it was traced with in every operand shape
-    // (#0=(N,3,640,640)f32).  Every operator here is per-image, so serving another batch is a rewrite of
-    // dim 0 wherever it equals the traced batch of the graph input.
+    // (#0=(N,3,640,640)f32).  Serving another batch is a rewrite of dim 0 wherever it equals the traced batch of
+    // the graph input.  (An operator that combines images -- a softmax over dimension 0 -- is then that operator over N images,
+    // which is what the model means at batch N; it is cutting ONE batch into pieces that such an operator forbids, batch_rule.h.)
     int file_batch = 0;
     if (opt_batch_ > 0) {
         for (pnnx::Operand* opd : graph_->operands)
@@ -248,17 +235,8 @@ Status EngineImpl::CreateTensorNodes() {
     // dimension >= 1 has THAT dimension rewritten and dimension 0 left alone, every other operand keeps the rule above.
     std::map<const pnnx::Operand*, int> batch_axis;
     if (file_batch > 0) {
+        batch_axis = FollowBatchAxes(graph_->ops, file_batch);   // (batch_rule.h: the rule for the split modes follows the same axes)
         for (const pnnx::Operator* op : graph_->ops) {
-            const pnnx::Operand* src = nullptr;
-            int axis = -1;
-            for (const pnnx::Operand* in : op->inputs) {
-                auto it = batch_axis.find(in);
-                if (it != batch_axis.end() && it->second >= 0) { src = in; axis = it->second; break; }
-            }
-            for (const pnnx::Operand* out : op->outputs) {
-                if (op->inputs.empty()) batch_axis[out] = (!out->shape.empty() && out->shape[0] == file_batch) ? 0 : -1;
-                else batch_axis[out] = src ? FollowBatchAxis(op, src->shape, axis, out->shape, file_batch) : -1;
-            }
             if (op->type == "nn.MultiheadAttention") {
                 // the layer reads the batch from dimension 0 (batch_first) or 1 of its operands: the rewrite has to have reached that one
                 bool batch_first = false;
@@ -324,10 +302,8 @@ Status EngineImpl::DestroyTensorNodes() {
 }
 
 Status EngineImpl::CreateLayers() {
-    has_user_layers_ = false;
     for (pnnx::Operator* op : graph_->ops) {
         if ("pnnx.Input" == op->type || "pnnx.Output" == op->type) continue;
-        if (IsUserRegisteredLayer(op->type)) has_user_layers_ = true;
         if (layers_.count(op->name) > 0) {
             LOG(ERROR) << "layer [" << op->name << "] already exists";
             return Status::kFail;
@@ -437,6 +413,7 @@ Status EngineImpl::DestroyGraphCache() {
 Status EngineImpl::DestroyPipeline() {
     CHECK_STATUS(DestroyGraphCache());
     forward_count_ = 0;
+    last_slices_ = 1;
     plan_warm_ = false;
     plan_.clear();
     fused_ops_.clear();
@@ -537,13 +514,14 @@ Status EngineImpl::DeallocateTensorMemory() {
 // ---- lanes (option "streams") ---------------------------------------------------------------------
 // Two half-batch engines on two streams instead of one full-batch engine on one: while one lane is in a layer's tail (the last,
 // partial round of workgroups, the epilogue stores) the other lane's workgroups fill the idle CUs.  Measured on MI355X,
-// YOLOv5s batch 32, same box, hipGraph replay: +4.9 % (tools/two_stream_exp.py).  Every operator of the
-// path is per-image, so a lane is simply this model re-batched to N / 2 (the "batch" option's rule) that reads
-// and writes slab views of this engine's input and output buffers; results are bit-identical to the one-stream schedule because
-// no kernel's per-element arithmetic depends on the batch (tests/test_gpu_tiles.py, tests/test_gpu_engine.py).
-// Can the batch be cut into contiguous slabs?  Every graph input and output must be batch-major (dimension 0 = the batch, rank >= 2);
-// every operator of the path is per-image, so nothing else is needed.
-bool EngineImpl::BatchSplittable(int& batch) const {
+// YOLOv5s batch 32, same box, hipGraph replay: +4.9 % (tools/two_stream_exp.py).  A lane is this model
+// re-batched to N / 2 (the "batch" option's rule) that reads and writes slab views of this engine's input and output buffers.
+// That is the same computation only for a graph whose every operator is per-image (batch_rule.h; the reference's operators all
+// are, SURVEY.md 8e, a softmax or a mean over the batch, a slice along it or a view that folds it is not): then the results are
+// bit-identical to the one-stream schedule because no kernel's per-element arithmetic depends on the batch
+// (tests/test_gpu_tiles.py, tests/test_gpu_engine.py, tests/test_gpu_batch_split.py).  Any other graph is refused.
+// Can the batch be cut into contiguous slabs?  Every graph input and output must be batch-major (dimension 0 = the batch, rank >= 2) ...
+bool EngineImpl::BatchMajorIO(int& batch) const {
     batch = 0;
     bool ok = !input_tensor_nodes_.empty() && !output_tensor_nodes_.empty();
     for (auto& kv : input_tensor_nodes_) {
@@ -558,12 +536,25 @@ bool EngineImpl::BatchSplittable(int& batch) const {
     return ok && batch >= 2;
 }
 
+// ... and every operator of the graph must be per-image by the rule of batch_rule.h
+bool EngineImpl::BatchSplittable(int& batch) const { return BatchMajorIO(batch) && batch_mixing_.empty(); }
+
+std::string EngineImpl::BatchMixingText() const {
+    std::string s;
+    for (const BatchMixingEntry& m : batch_mixing_) s += (s.empty() ? "[" : "; [") + m.layer + "] (" + m.type + "): " + m.reason;
+    return s;
+}
+
 Status EngineImpl::PlanLanes(int& lanes) {
     lanes = 1;
     if (is_lane_ || opt_streams_ < 2) return Status::kSuccess;
     int batch = 0;
     const bool ok = BatchSplittable(batch) && batch % 2 == 0;
     if (opt_streams_ >= 2) {
+        if (!batch_mixing_.empty()) {
+            LOG(ERROR) << "streams=2 runs two half-batch copies of the model, which needs per-image operators; not per-image: " << BatchMixingText();
+            return Status::kUnsupport;
+        }
         if (!ok) {
             LOG(ERROR) << "streams=2 needs an even batch that is dimension 0 of every graph input and output";
             return Status::kUnsupport;
@@ -667,21 +658,37 @@ Status EngineImpl::LaunchLanes() {
 // slice g-2's output rows come down on a download stream into the pinned mirror Extract() returns.  What is left outside the
 // overlap is the first slice's upload and the last slice's download.  A borrowed input buffer that is handed over for a second
 // Forward is pinned in place (hipHostRegister) so its uploads run asynchronously at the link rate.  Bit-identical to the
-// unsliced schedule (per-image arithmetic; tests/test_gpu_engine.py::test_host_tensor_pipeline_*).
+// unsliced schedule for a graph of per-image operators (tests/test_gpu_engine.py::test_host_tensor_pipeline_*,
+// tests/test_gpu_batch_split.py).  A graph that holds an operator which combines images (batch_rule.h; a layer type registered at
+// run time counts as one) is served unsliced: slices of it would compute something else.  Under auto that is said once at INFO,
+// under an explicit host_slices > 1 once as an ERROR, each with the layer and the reason.
 int EngineImpl::PlanSlices() const {
     if (is_lane_ || opt_host_slices_ == 1 || !opt_outputs_to_host_ || slicer_failed_) return 1;
     if (!lanes_.empty()) return 1;   // "streams" = 2 was asked for: the lanes serve the engine
     int batch = 0;
-    if (!BatchSplittable(batch)) return 1;
+    if (!BatchMajorIO(batch)) return 1;
     for (auto& kv : input_tensor_nodes_) {
         auto u = user_inputs_.find(kv.first);
         if (u == user_inputs_.end() || u->second.RawData() == nullptr || u->second.GetMemoryType() == MemoryType::kDevice) return 1;
     }
     if (!user_outputs_.empty()) return 1;   // caller-owned device outputs: not the host contract
+    const int slices = SlicesFor(batch);
+    if (slices > 1 && !batch_mixing_.empty()) {
+        if (!mixing_logged_) {
+            if (opt_host_slices_ > 1)
+                LOG(ERROR) << "host_slices=" << opt_host_slices_ << " needs per-image operators; serving this engine unsliced.  Not per-image: " << BatchMixingText();
+            else
+                LOG(INFO) << "host_slices: serving this engine unsliced.  Not per-image: " << BatchMixingText();
+            mixing_logged_ = true;
+        }
+        return 1;
+    }
+    return slices;
+}
+
+// the number of slices a batch-major graph of per-image operators is served with
+int EngineImpl::SlicesFor(int batch) const {
     if (opt_host_slices_ > 1) return batch % opt_host_slices_ == 0 ? opt_host_slices_ : 1;
-    // auto re-batches the model to N / G: every built-in operator is per-image, a layer registered at run time
-    // (RegisterLayer) may not be -- such a graph is sliced only on an explicit host_slices > 1
-    if (has_user_layers_) return 1;
     // auto (MI355X, YOLOv5s 640x640, profiles/r03_host_slices.txt): slices of 8 images from batch 32 on (a batch-8 forward is still
     // at 0.6 of the MFMA ceiling, and 8 images are 39 MB up / 69 MB down -- 0.7 / 1.3 ms of PCIe outside the overlap), slices of 4
     // for batches 8 .. 31 (batch 8: 3.49 -> 2.95 ms per Forward with 2 slices; batch 16: 6.61 -> 4.95 with 4); at most 8 slices
@@ -765,6 +772,7 @@ Status EngineImpl::SetupSlicer(int slices) {
 Status EngineImpl::ForwardSliced(int slices) {
     si_stream_t stream = context_->stream();
     CHECK_BOOL(slicer_ != nullptr && slices_ == slices);
+    last_slices_ = slices;
     // the engine's device-side input staging and its own output buffers, whole batch; the slices are views
     for (auto& kv : input_tensor_nodes_) kv.second->tensor.SetView(input_buffers_[kv.first], MemoryType::kDevice, 0);
     CHECK_STATUS(BindOutputs());
@@ -1030,6 +1038,7 @@ Status EngineImpl::ForwardAsync() {
         DestroySlicer();
         slicer_failed_ = true;
     }
+    last_slices_ = 1;
     CHECK_STATUS(EnsureArena());
     CHECK_STATUS(UploadInputs());
     CHECK_STATUS(BindOutputs());

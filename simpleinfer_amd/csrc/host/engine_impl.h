@@ -17,6 +17,7 @@
 #include <string>
 #include <vector>
 
+#include "batch_rule.h"
 #include "context.h"
 #include "engine.h"
 #include "layer.h"
@@ -87,6 +88,9 @@ public:
         for (const EngineImpl* lane : lanes_) arena_bytes += lane->arena_bytes_, per_operand_bytes += lane->unshared_bytes_;
     }
     int Lanes() const { return lanes_.empty() ? 1 : (int)lanes_.size(); }
+    int LastSlices() const { return last_slices_; }   // the host_slices pipeline: slices the last Forward ran as (1: unsliced)
+    // the operators of the loaded graph that are not per-image (batch_rule.h): with any, the batch is never cut into slabs
+    const std::vector<BatchMixingEntry>& BatchMixing() const { return batch_mixing_; }
 
 private:
     struct Step {
@@ -127,8 +131,12 @@ private:
     Status DestroyGraphCache();
 
     // host-tensor contract at speed (option "host_slices"): see ForwardSliced
+    void FindBatchMixingLayers();
+    std::string BatchMixingText() const;
+    bool BatchMajorIO(int& batch) const;
     bool BatchSplittable(int& batch) const;
     int PlanSlices() const;
+    int SlicesFor(int batch) const;
     Status ForwardSliced(int slices);
     Status SetupSlicer(int slices);
     Status DestroySlicer();
@@ -192,7 +200,9 @@ private:
     int slices_ = 0;                         // set only once every resource of the pipeline exists
     bool debug_fail_slicer_ = false;         // option "_fail_slicer" (tests)
     bool slicer_failed_ = false;             // setting the pipeline up failed once: serve unsliced from then on
-    bool has_user_layers_ = false;           // a layer type registered at run time (RegisterLayer): nothing is known about its batch semantics
+    std::vector<BatchMixingEntry> batch_mixing_;   // operators that combine images, with the reason (a lane / the slicer's engine: not looked for)
+    mutable bool mixing_logged_ = false;     // ... and that they keep host_slices off has been said
+    int last_slices_ = 1;                    // slices of the last Forward (1: unsliced)
     size_t max_graphs_ = 8;                  // captured hipGraphs kept (one per distinct set of I/O pointers)
     // the activation arena is planned at LoadModel but allocated at the first forward that runs THIS engine's plan (an engine
     // served by the sliced host pipeline never needs it)

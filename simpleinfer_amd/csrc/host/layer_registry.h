@@ -26,8 +26,9 @@ bool RegisterLayer(const std::string& type, LayerCreatorFunc creator, LayerDestr
 std::vector<std::string> RegisteredLayerTypes();
 
 // true for a type whose entry came from RegisterLayer (also one that replaced a built-in): the engine knows nothing about such
-// a layer beyond the Layer interface -- in particular not whether it is per-image -- and does not re-batch graphs that hold one
-// unless asked to (Engine option "host_slices" > 1, "batch")
+// a layer beyond the Layer interface -- in particular not whether it is per-image -- so a graph that holds one counts as
+// batch-mixing (batch_rule.h): its batch is never cut into slabs (Engine options "host_slices" and "streams", ShardedEngine).
+// "batch" re-batches it when asked to.
 bool IsUserRegisteredLayer(const std::string& type);
 
 }  // namespace SimpleInfer

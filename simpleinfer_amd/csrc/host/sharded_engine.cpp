@@ -34,6 +34,16 @@ Status ShardedEngine::Init(const std::string& group_name, int rank, int world, E
         LOG(ERROR) << "ShardedEngine: the engine must keep its outputs on the device (SetOption(\"outputs_to_host\", 0))";
         return Status::kUnsupport;
     }
+    // every rank computes a slab of the global batch, which is the global batch's result only for a graph of per-image operators
+    if (world > 1) {
+        const std::vector<std::string> mixing = engine->BatchMixingLayers();
+        if (!mixing.empty()) {
+            std::string all;
+            for (const std::string& m : mixing) all += (all.empty() ? "" : "; ") + m;
+            LOG(ERROR) << "ShardedEngine: a batch sharded over " << world << " ranks needs per-image operators; not per-image: " << all;
+            return Status::kUnsupport;
+        }
+    }
     SI_TRY_SHARD(si_hip_get_device(&device_), "hipGetDevice");
     SI_TRY_SHARD(si_group_create(group_name.c_str(), rank, world, timeout_s, &group_), "si_group_create");
     const int rc = si_gather_create_mode(group_, device_, out.ByteSize(), slots, (int)gather, &gather_);

@@ -160,11 +160,13 @@ class Engine:
         n = self._L.si_engine_schedule(self._h, None, 0)
         buf = C.create_string_buffer(n + 1)
         self._L.si_engine_schedule(self._h, buf, n + 1)
-        out: Dict[str, List[str]] = {"run": [], "fused": [], "alias": [], "split_demoted": []}
+        out: Dict[str, List[str]] = {"run": [], "fused": [], "alias": [], "split_demoted": [], "batch_mixing": []}
         for ln in buf.value.decode().splitlines():
             k, v = ln.split(" ", 1)
-            if k in ("arena_bytes", "per_operand_bytes", "lanes", "split_reruns"):
-                out[k] = int(v)      # HBM held for intermediates: shared by lifetime / one allocation per operand
+            if k in ("arena_bytes", "per_operand_bytes", "lanes", "host_slices", "split_reruns"):
+                # HBM held for intermediates: shared by lifetime / one allocation per operand; lanes (option "streams"); the pipelined
+                # batch slices the last forward ran as (option "host_slices", 1: unsliced)
+                out[k] = int(v)
             else:
                 out[k].append(v)
         return out

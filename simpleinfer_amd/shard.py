@@ -149,6 +149,11 @@ class ShardedForward:
 
     def __init__(self, engine, output_name: str, group: NodeGroup, device: int, slots: int = 4, mode: str = "direct"):
         self.e, self.oname = engine, output_name
+        # every rank computes a slab of the global batch: the global batch's result only for a graph of per-image operators
+        mixing = engine.schedule()["batch_mixing"]
+        if group.world > 1 and mixing:
+            from .engine import Status, StatusError
+            raise StatusError("ShardedForward over %d ranks: not per-image: %s" % (group.world, "; ".join(mixing)), Status.kUnsupport)
         shape = engine.operand_shape(output_name)
         self.local_shape = tuple(shape)
         self.gather = DirectGather(group, device, int(np.prod(shape)) * 4, slots, mode)

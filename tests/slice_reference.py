@@ -139,8 +139,7 @@ def eval_graph(builder, x_nhwc, rnd=None):
         elif typ == "nn.ReLU":
             y = np.maximum(x, 0.0)
         elif typ == "torch.cat":
-            assert int(prm["dim"]) == 1
-            y = np.concatenate([vals[i] for i in ins], axis=x.ndim - 1)
+            y = np.concatenate([vals[i] for i in ins], axis=nhwc_axis(int(prm["dim"]), x.ndim))
         elif typ == "pnnx.Expression":
             assert prm["expr"] == "add(@0,@1)"
             y = vals[ins[0]] + vals[ins[1]]
