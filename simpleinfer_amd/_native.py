@@ -124,6 +124,13 @@ class SiAttentionDesc(C.Structure):
         (k, C.c_longlong) for k in ("q_sb", "q_ss", "k_sb", "k_ss", "v_sb", "v_ss", "o_sb", "o_ss")] + [("scale", C.c_float)]
 
 
+class SiDeformConv2dDesc(C.Structure):
+    """include/si_deform.h; in_ld / off_ld / mask_ld / out_ld: the pixel strides of x, offset, mask and out"""
+    _fields_ = [(k, C.c_int) for k in
+                ("n", "ih", "iw", "ic", "in_ld", "oh", "ow", "oc", "out_ld", "off_ld", "mask_ld", "kh", "kw", "sh", "sw", "ph", "pw", "dh", "dw",
+                 "groups", "offset_groups", "has_mask", "has_bias", "act")] + [("act_param", C.c_float)]
+
+
 class SiLayoutNest(C.Structure):
     """include/si_layout.h; what si_layout_plan returns: view != 0, or the loop nest of the copy"""
     _fields_ = [("view", C.c_int), ("rank", C.c_int), ("dims", C.c_int * 8), ("in_stride", C.c_longlong * 8)]
@@ -361,9 +368,16 @@ def hip():
         "si_hip_attention_f16": (i, [C.POINTER(SiAttentionDesc), vp, vp, vp, vp, vp]),
         "si_hip_attention_kernel_name": (C.c_char_p, [C.POINTER(SiAttentionDesc), vp, vp, vp, vp, i]),
     }
+    # include/si_deform.h: deformable convolution, the kernel of torchvision.ops.DeformConv2d
+    deform_ = {
+        "si_hip_deform_conv2d_weight_elems": (sz, [C.POINTER(SiDeformConv2dDesc)]),
+        "si_hip_deform_conv2d_pack_weight_host": (i, [C.POINTER(SiDeformConv2dDesc), vp, vp]),
+        "si_hip_deform_conv2d_f32": (i, [C.POINTER(SiDeformConv2dDesc), vp, vp, vp, vp, vp, vp, vp]),
+        "si_hip_deform_conv2d_kernel_name": (C.c_char_p, [C.POINTER(SiDeformConv2dDesc), vp, vp, vp, vp]),
+    }
     for name, (res, args) in (list(sig.items()) + list(norm.items()) + list(pad.items()) + list(pool.items()) + list(softmax.items()) +
                               list(superres.items()) + list(slice_.items()) + list(reduce_.items()) + list(act.items()) + list(permute_.items()) +
-                              list(attention_.items())):
+                              list(attention_.items()) + list(deform_.items())):
         fn = getattr(L, name)  # AttributeError here = header/library mismatch, which tests check
         fn.restype = res
         fn.argtypes = args
@@ -378,6 +392,7 @@ def hip():
     L._si_act_signatures = act
     L._si_permute_signatures = permute_
     L._si_attention_signatures = attention_
+    L._si_deform_signatures = deform_
     _hip = L
     return L
 

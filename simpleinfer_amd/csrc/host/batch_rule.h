@@ -105,6 +105,7 @@ inline BatchFamily BatchFamilyOf(const std::string& type) {
         {"pnnx.Output", BatchFamily::kOutput},
         {"nn.Conv2d", BatchFamily::kSpatial},
         {"nn.ConvTranspose2d", BatchFamily::kSpatial},
+        {"torchvision.ops.DeformConv2d", BatchFamily::kSpatial},   // (offset and mask are per-pixel operands of the same image)
         {"nn.BatchNorm2d", BatchFamily::kSpatial},       // (inference: running statistics, nothing of the batch)
         {"nn.GroupNorm", BatchFamily::kSpatial},
         {"nn.InstanceNorm2d", BatchFamily::kSpatial},

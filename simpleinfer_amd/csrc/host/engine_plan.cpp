@@ -10,6 +10,7 @@
 #include "layer/cat.h"
 #include "layer/conv_2d.h"
 #include "layer/conv_transpose_2d.h"
+#include "layer/deform_conv_2d.h"
 #include "layer/group_norm.h"
 #include "layer/layout.h"
 #include "layer/linear.h"
@@ -33,7 +34,7 @@ bool HonoursPixelStride(const std::string& type) {
         "F.softmax", "F.log_softmax", "nn.PixelShuffle", "nn.PixelUnshuffle", "F.pixel_shuffle", "F.pixel_unshuffle", "nn.PReLU", "torch.flatten",
         "torch.chunk", "torch.split", "Tensor.slice", "torch.mean", "torch.sum", "torch.amax", "torch.amin", "nn.ReLU6", "F.relu6",
         "nn.Hardtanh", "F.hardtanh", "torch.clamp", "nn.Softplus", "F.softplus", "nn.Mish", "F.mish", "F.relu", "F.silu", "F.sigmoid", "F.hardsigmoid",
-        "F.hardswish", "F.leaky_relu", "F.tanh", "models.yolo.Detect", "pnnx.Output"};
+        "F.hardswish", "F.leaky_relu", "F.tanh", "models.yolo.Detect", "torchvision.ops.DeformConv2d", "pnnx.Output"};
     return ok.count(type) > 0;
 }
 
@@ -223,6 +224,11 @@ Status EngineImpl::FuseEpilogues(std::vector<Step>& order) {
         // transposed conv -> act  ==>  one launch (its epilogue has the activation only: a residual add stays a launch of its own)
         if (ConvTranspose2d* ct = p.At<ConvTranspose2d>(i, "nn.ConvTranspose2d")) {
             p.FuseActivationInto(i, ct);
+            continue;
+        }
+        // deformable conv -> act  ==>  one launch, as for the transposed conv
+        if (DeformConv2d* dc = p.At<DeformConv2d>(i, "torchvision.ops.DeformConv2d")) {
+            p.FuseActivationInto(i, dc);
             continue;
         }
         // group / instance norm -> act  ==>  one launch (or the same two): the activation runs in the normalise pass's epilogue
@@ -675,6 +681,12 @@ Status EngineImpl::AliasConcats() {
             for (const pnnx::Operator* c2 : r->consumers) ok = ok && c2 && HonoursPixelStride(c2->type);
             // flatten writes dense NCHW and Detect writes rank-3 rows: they never feed a rank-4 cat
             if (ok && (r->producer->type == "torch.flatten" || r->producer->type == "models.yolo.Detect")) ok = false;
+            // the deformable conv refuses an output whose extent intersects an input's (include/si_deform.h), which a slice of a concat row
+            // that also holds one of its inputs would: its output (also behind a fused activation) keeps a buffer of its own
+            if (ok)
+                for (const Step& w : plan_)
+                    if (dynamic_cast<DeformConv2d*>(w.layer))
+                        for (TensorNode* n : w.layer->OutputNodes()) ok = ok && n != tensor_nodes_[r->name];
             seen.insert(r);
             if (ok) {
                 Alias a;

@@ -16,6 +16,7 @@ SI_DECLARE_LAYER(BinaryOp)
 SI_DECLARE_LAYER(Cat)
 SI_DECLARE_LAYER(Conv2d)
 SI_DECLARE_LAYER(ConvTranspose2d)
+SI_DECLARE_LAYER(DeformConv2d)
 SI_DECLARE_LAYER(Flatten)
 SI_DECLARE_LAYER(GroupNorm)
 SI_DECLARE_LAYER(HardSigmoid)
@@ -56,7 +57,8 @@ static std::map<std::string, LayerRegistryEntry>& Table() {
     // functional spellings of the activations above, on the classes of their nn.* twins (they fuse as those do; F.tanh, like nn.Tanh, does not);
     // Tensor.permute / torch.permute / Tensor.reshape / Tensor.view / torch.transpose / torch.squeeze / torch.unsqueeze / Tensor.contiguous (one
     // class, layer/layout.h: the layout algebra of layout_plan.h decides between a view and one permute launch); nn.MultiheadAttention
-    // (layer/multihead_attention.h: two projections around the fused attention kernel of include/si_attention.h)
+    // (layer/multihead_attention.h: two projections around the fused attention kernel of include/si_attention.h); torchvision.ops.DeformConv2d
+    // (layer/deform_conv_2d.h: DCNv1 / DCNv2 in one launch of include/si_deform.h; the type string is the one pnnx writes for the module)
     static std::map<std::string, LayerRegistryEntry> table = {
         SI_ENTRY("nn.AdaptiveAvgPool2d", AdaptiveAvgPool2d),
         SI_ENTRY("nn.AvgPool2d", AvgPool2d),
@@ -132,6 +134,7 @@ static std::map<std::string, LayerRegistryEntry>& Table() {
         SI_ENTRY("torch.unsqueeze", Layout),
         SI_ENTRY("Tensor.contiguous", Layout),
         SI_ENTRY("models.yolo.Detect", YoloDetect),
+        SI_ENTRY("torchvision.ops.DeformConv2d", DeformConv2d),
     };
     return table;
 }

@@ -418,6 +418,65 @@ def conv_transpose2d_kernel_name(x_shape, w_shape, stride=(1, 1), padding=(0, 0)
     return _native.hip().si_hip_conv_transpose2d_kernel_name(C.byref(d)).decode()
 
 
+def deform_conv2d_desc(x_shape, off_shape, w_shape, mask=False, bias=True, stride=(1, 1), padding=(0, 0), dilation=(1, 1), groups=1, act1="none",
+                       act_param=0.0, in_ld=None, off_ld=None, mask_ld=None, out_ld=None):
+    """SiDeformConv2dDesc (include/si_deform.h) for an NHWC input of x_shape, an NHWC offset of off_shape [n, oh, ow, 2 og kh kw] and a torch
+    weight of w_shape [Cout][Cin/groups][kh][kw]; the offset-group count is read off the offset's channels"""
+    n, ih, iw, ic = x_shape
+    oc, _, kh, kw = w_shape
+    oh, ow = conv_out_hw(ih, iw, (kh, kw), stride, padding, dilation)
+    off_c = int(off_shape[-1])
+    og = off_c // (2 * kh * kw)
+    return _native.SiDeformConv2dDesc(n, ih, iw, ic, in_ld or ic, oh, ow, oc, out_ld or oc, off_ld or off_c, (mask_ld or og * kh * kw) if mask else 0,
+                                      kh, kw, stride[0], stride[1], padding[0], padding[1], dilation[0], dilation[1], groups, og,
+                                      1 if mask else 0, 1 if bias else 0, ACT[act1], float(act_param))
+
+
+def deform_conv2d_pack(d, w_oihw) -> np.ndarray:
+    """the kernel's weight image of a torch [Cout][Cin/groups][kh][kw] weight (host only)"""
+    H = _native.hip()
+    w_oihw = _f32(w_oihw)
+    packed = np.zeros(H.si_hip_deform_conv2d_weight_elems(C.byref(d)), np.float32)
+    _chk(H.si_hip_deform_conv2d_pack_weight_host(C.byref(d), w_oihw.ctypes.data_as(C.c_void_p), packed.ctypes.data_as(C.c_void_p)),
+         "pack deformable-conv weight")
+    return packed
+
+
+def deform_conv2d(x_nhwc, offset_nhwc, w_oihw, bias=None, mask_nhwc=None, stride=(1, 1), padding=(0, 0), dilation=(1, 1), groups=1, act1="none",
+                  act_param=0.0, in_ld: Optional[int] = None, in_c_off: int = 0, in_fill=0.0, off_ld: Optional[int] = None, off_c_off: int = 0,
+                  off_fill=0.0, mask_ld: Optional[int] = None, mask_c_off: int = 0, mask_fill=0.0, out_ld: Optional[int] = None, out_c_off: int = 0,
+                  out_fill=0.0, full: bool = False):
+    """si_hip_deform_conv2d_f32 (torchvision.ops.deform_conv2d; NHWC operands, w_oihw in torch's [Cout][Cin/groups][kh][kw] layout; without
+    mask_nhwc DCNv1).  The view hooks are conv_transpose2d's, for all four views: x, offset and mask are each the channel slice
+    [*_c_off, *_c_off + c) of rows of *_ld elements whose other channels hold *_fill; the destination is the slice [out_c_off, out_c_off + Cout)
+    of rows of out_ld elements pre-filled with out_fill.  full=True returns the whole rows."""
+    H = _native.hip()
+    x, off, w_oihw = _f32(x_nhwc), _f32(offset_nhwc), _f32(w_oihw)
+    mask = _f32(mask_nhwc) if mask_nhwc is not None else None
+    oc = w_oihw.shape[0]
+    d = deform_conv2d_desc(x.shape, off.shape, w_oihw.shape, mask is not None, bias is not None, stride, padding, dilation, groups, act1,
+                           act_param, in_ld, off_ld, mask_ld, out_ld)
+    assert off.shape[:3] == (d.n, d.oh, d.ow) and (mask is None or mask.shape[:3] == (d.n, d.oh, d.ow)), (x.shape, off.shape, (d.oh, d.ow))
+    packed = deform_conv2d_pack(d, w_oihw)
+    (dx, px), (do, po) = _view_in(x, in_ld, in_c_off, in_fill), _view_in(off, off_ld, off_c_off, off_fill)
+    dm, pm = _view_in(mask, mask_ld, mask_c_off, mask_fill) if mask is not None else (None, None)
+    dw = DeviceBuffer.from_numpy(packed)
+    db = DeviceBuffer.from_numpy(_f32(bias)) if bias is not None else None
+    dy, py = _view_out((d.n, d.oh, d.ow), oc, out_ld, out_c_off, out_fill)
+    LAST_KERNEL_NAME["si_hip_deform_conv2d"] = H.si_hip_deform_conv2d_kernel_name(C.byref(d), C.c_void_p(px), C.c_void_p(po), C.c_void_p(pm) if pm else None,
+                                                                                 C.c_void_p(py)).decode()
+    _chk(H.si_hip_deform_conv2d_f32(C.byref(d), px, po, pm, dw.ptr, db.ptr if db else None, py, None), "si_hip_deform_conv2d_f32")
+    return _ret(dy.to_numpy((d.n, d.oh, d.ow, out_ld or oc)), oc, out_c_off, full)
+
+
+def deform_conv2d_kernel_name(x_shape, off_shape, w_shape, mask=False, stride=(1, 1), padding=(0, 0), dilation=(1, 1), groups=1, in_ld=None,
+                              align=256) -> str:
+    """the instantiation for dense operands (x rows of in_ld elements) whose x sits at address `align`; "none": a refused descriptor"""
+    d = deform_conv2d_desc(x_shape, off_shape, w_shape, mask, True, stride, padding, dilation, groups, in_ld=in_ld)
+    p = [C.c_void_p(int(align) + (1 << 32) * j) for j in range(4)]
+    return _native.hip().si_hip_deform_conv2d_kernel_name(C.byref(d), p[0], p[1], p[2] if mask else None, p[3]).decode()
+
+
 def _range_flag(d, want):
     """a zeroed device word handed to an f32_split launch as SiConv2dDesc::range_flag (the kernel writes 1 when an operand left fp16's range)"""
     if not want:

@@ -170,6 +170,27 @@ class PnnxBuilder:
                         stride=(sh, sw)), attrs)
         return out
 
+    def deform_conv(self, x: str, offset: str, mask: str = None, cout: int = None, k=3, s=1, p=None, d=1, groups: int = 1, bias: bool = True,
+                    name: str = None) -> str:
+        """torchvision.ops.DeformConv2d as pnnx writes the module: inputs (x, offset) or (x, offset, mask), Conv2d's keys without
+        padding_mode, weight [Cout][Cin/groups][kh][kw].  offset is [N, 2 og kh kw, Ho, Wo], mask [N, og kh kw, Ho, Wo]."""
+        n, cin, h, w = self.shapes[x]
+        pair = lambda v: (v, v) if isinstance(v, int) else tuple(v)
+        (kh, kw), (sh, sw), (dh, dw) = pair(k), pair(s), pair(d)
+        ph, pw = (kh // 2, kw // 2) if p is None else pair(p)
+        oh = (h + 2 * ph - ((kh - 1) * dh + 1)) // sh + 1
+        ow = (w + 2 * pw - ((kw - 1) * dw + 1)) // sw + 1
+        name = name or self._opname("deformconv")
+        a = math.sqrt(3.0 / ((cin // groups) * kh * kw))
+        attrs = {"weight": seeded_uniform(name + ".weight", (cout, cin // groups, kh, kw), -a, a, self.seed)}
+        if bias:
+            attrs["bias"] = seeded_uniform(name + ".bias", (cout,), -0.1, 0.1, self.seed)
+        out = self._new_operand((n, cout, oh, ow))
+        self._emit("torchvision.ops.DeformConv2d", name, [x, offset] + ([mask] if mask is not None else []), [out],
+                   dict(bias=bool(bias), dilation=(dh, dw), groups=groups, in_channels=cin, kernel_size=(kh, kw), out_channels=cout,
+                        padding=(ph, pw), stride=(sh, sw)), attrs)
+        return out
+
     def _unary(self, typ: str, prefix: str, x: str, params=None) -> str:
         out = self._new_operand(self.shapes[x])
         self._emit(typ, self._opname(prefix), [x], [out], params or {})
@@ -1102,6 +1123,21 @@ def build_toy_mhsa_head(batch: int = 2, size: int = 16, c: int = 24, heads: int 
     t = b.multihead_attention(t, num_heads=heads, batch_first=True)
     m = b.mean(b.view(b.permute(t, (0, 2, 1)), (batch, c, h, w)), (2, 3))
     b.output(b.linear(m, 10))
+    return b
+
+
+def build_toy_dcn_head(batch: int = 2, size: int = 32, mask: bool = True, seed: int = 0) -> PnnxBuilder:
+    """The usual DCNv2 block at toy width: stem conv 3 -> 16 stride 2 + SiLU; an offset conv 3x3 16 -> 27 whose output torch.split([18, 9]) cuts
+    into the offsets (a channel view) and the mask logits -> nn.Sigmoid; torchvision.ops.DeformConv2d 16 -> 24 3x3 pad 1 on (x, offset, mask)
+    + ReLU; a 1x1 conv to 8 channels.  mask=False: DCNv1 -- an 18-channel offset conv and two inputs."""
+    b = PnnxBuilder(seed)
+    x = b.silu(b.conv(b.input((batch, 3, size, size)), 16, 3, 2, 1))
+    if mask:
+        off, m = b.split(b.conv(x, 27, 3, 1, 1), [18, 9], 1)
+        y = b.deform_conv(x, off, b.sigmoid(m), cout=24, k=3, s=1, p=1)
+    else:
+        y = b.deform_conv(x, b.conv(x, 18, 3, 1, 1), cout=24, k=3, s=1, p=1)
+    b.output(b.conv(b.relu(y), 8, 1))
     return b
 
 
