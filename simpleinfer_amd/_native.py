@@ -131,6 +131,18 @@ class SiDeformConv2dDesc(C.Structure):
                  "groups", "offset_groups", "has_mask", "has_bias", "act")] + [("act_param", C.c_float)]
 
 
+class SiGridSampleDesc(C.Structure):
+    """include/si_grid.h; in_ld / out_ld: pixel strides of x and out (0: dense); gs_*: the element strides of the grid (grid_source 0), which
+    are not looked at when the pointer is theta (grid_source 1)"""
+    _fields_ = [(k, C.c_int) for k in ("n", "c", "h", "w", "ho", "wo", "in_ld", "out_ld", "mode", "padding_mode", "align_corners", "grid_source",
+                                       "spatial_dims")] + [(k, C.c_longlong) for k in ("gs_n", "gs_h", "gs_w", "gs_k")]
+
+
+class SiAffineGridDesc(C.Structure):
+    """include/si_grid.h; out_ld: row stride of the stored [n][w][2][h] image (0: dense)"""
+    _fields_ = [(k, C.c_int) for k in ("n", "h", "w", "out_ld", "align_corners")]
+
+
 class SiLayoutNest(C.Structure):
     """include/si_layout.h; what si_layout_plan returns: view != 0, or the loop nest of the copy"""
     _fields_ = [("view", C.c_int), ("rank", C.c_int), ("dims", C.c_int * 8), ("in_stride", C.c_longlong * 8)]
@@ -375,9 +387,18 @@ def hip():
         "si_hip_deform_conv2d_f32": (i, [C.POINTER(SiDeformConv2dDesc), vp, vp, vp, vp, vp, vp, vp]),
         "si_hip_deform_conv2d_kernel_name": (C.c_char_p, [C.POINTER(SiDeformConv2dDesc), vp, vp, vp, vp]),
     }
+    # include/si_grid.h: F.grid_sample and F.affine_grid
+    grid_ = {
+        "si_hip_grid_sample_f32": (i, [C.POINTER(SiGridSampleDesc), vp, vp, vp, vp]),
+        "si_hip_grid_sample_f16": (i, [C.POINTER(SiGridSampleDesc), vp, vp, vp, vp]),
+        "si_hip_grid_sample_kernel_name": (C.c_char_p, [C.POINTER(SiGridSampleDesc), vp, vp, vp, i]),
+        "si_hip_affine_grid_f32": (i, [C.POINTER(SiAffineGridDesc), vp, vp, vp]),
+        "si_hip_affine_grid_f16": (i, [C.POINTER(SiAffineGridDesc), vp, vp, vp]),
+        "si_hip_affine_grid_kernel_name": (C.c_char_p, [C.POINTER(SiAffineGridDesc), vp, vp, i]),
+    }
     for name, (res, args) in (list(sig.items()) + list(norm.items()) + list(pad.items()) + list(pool.items()) + list(softmax.items()) +
                               list(superres.items()) + list(slice_.items()) + list(reduce_.items()) + list(act.items()) + list(permute_.items()) +
-                              list(attention_.items()) + list(deform_.items())):
+                              list(attention_.items()) + list(deform_.items()) + list(grid_.items())):
         fn = getattr(L, name)  # AttributeError here = header/library mismatch, which tests check
         fn.restype = res
         fn.argtypes = args
@@ -393,6 +414,7 @@ def hip():
     L._si_permute_signatures = permute_
     L._si_attention_signatures = attention_
     L._si_deform_signatures = deform_
+    L._si_grid_signatures = grid_
     _hip = L
     return L
 

@@ -106,6 +106,8 @@ inline BatchFamily BatchFamilyOf(const std::string& type) {
         {"nn.Conv2d", BatchFamily::kSpatial},
         {"nn.ConvTranspose2d", BatchFamily::kSpatial},
         {"torchvision.ops.DeformConv2d", BatchFamily::kSpatial},   // (offset and mask are per-pixel operands of the same image)
+        {"F.grid_sample", BatchFamily::kSpatial},        // (x [N,C,H,W] and the grid [N,Ho,Wo,2] are operands of the same image)
+        {"F.affine_grid", BatchFamily::kSpatial},        // (theta [N,2,3] -> grid [N,H,W,2]: the batch is dimension 0 on both sides)
         {"nn.BatchNorm2d", BatchFamily::kSpatial},       // (inference: running statistics, nothing of the batch)
         {"nn.GroupNorm", BatchFamily::kSpatial},
         {"nn.InstanceNorm2d", BatchFamily::kSpatial},

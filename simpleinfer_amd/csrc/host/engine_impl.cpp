@@ -23,6 +23,7 @@ Status EngineImpl::SetOption(const std::string& key, int value) {
     else if (key == "alias_cat") opt_alias_cat_ = value != 0;
     else if (key == "alias_split") opt_alias_split_ = value != 0;   // chunk / split / slice outputs on the channel axis as views of the input (default 1)
     else if (key == "fuse_layout") opt_fuse_layout_ = value != 0;   // runs of layout operators as one step (default 1)
+    else if (key == "fuse_grid") opt_fuse_grid_ = value != 0;       // F.grid_sample reads its grid in place / from theta (default 1; 0: A/B runs)
     else if (key == "alias_view") opt_alias_view_ = value != 0;     // layout steps that move no byte as views of their input (default 1)
     else if (key == "graph") opt_graph_ = value != 0;
     else if (key == "outputs_to_host") opt_outputs_to_host_ = value != 0;
@@ -575,6 +576,7 @@ Status EngineImpl::LoadLanes(int lanes) {
         lane->opt_alias_cat_ = opt_alias_cat_;
         lane->opt_alias_split_ = opt_alias_split_;
         lane->opt_fuse_layout_ = opt_fuse_layout_;
+        lane->opt_fuse_grid_ = opt_fuse_grid_;
         lane->opt_alias_view_ = opt_alias_view_;
         lane->opt_fuse_upsample_ = opt_fuse_upsample_;
         lane->opt_fuse_stem_ = opt_fuse_stem_;
@@ -734,6 +736,7 @@ Status EngineImpl::SetupSlicer(int slices) {
     slicer_->opt_alias_cat_ = opt_alias_cat_;
     slicer_->opt_alias_split_ = opt_alias_split_;
     slicer_->opt_fuse_layout_ = opt_fuse_layout_;
+    slicer_->opt_fuse_grid_ = opt_fuse_grid_;
     slicer_->opt_alias_view_ = opt_alias_view_;
     slicer_->opt_fuse_upsample_ = opt_fuse_upsample_;
     slicer_->opt_fuse_stem_ = opt_fuse_stem_;

@@ -107,6 +107,8 @@ private:
     Status FuseSiblingConvs(std::vector<Step>& order);
     Status FusePoolChains(std::vector<Step>& order);
     Status FuseLayoutChains(std::vector<Step>& order);
+    Status FuseGridInPlace(std::vector<Step>& order);
+    Status FuseAffineGrids(std::vector<Step>& order);
     Status FuseUpsampleIntoConvs(std::vector<Step>& order);
     Status FuseStemPairs(std::vector<Step>& order);
     Status FuseStemTriples(std::vector<Step>& order);
@@ -149,7 +151,8 @@ private:
     bool opt_fuse_ = true;
     bool opt_alias_cat_ = true;
     bool opt_alias_split_ = true;   // torch.chunk / torch.split / Tensor.slice outputs that are channel ranges become views of the input (0: always copied)
-    bool opt_fuse_layout_ = true;   // a run of permute / reshape / view / transpose / squeeze / unsqueeze operators is planned as ONE layout step (0: one step each)
+    bool opt_fuse_grid_ = true;     // F.grid_sample reads a permuted grid in place and an affine grid from theta (0: the grid is written first; A/B runs)
+    bool opt_fuse_layout_ = true;  // a run of permute / reshape / view / transpose / squeeze / unsqueeze operators is planned as ONE layout step (0: one step each)
     bool opt_alias_view_ = true;    // a layout step that moves no byte makes its output a view of its input's buffer (0: one permute_rows copy)
     bool opt_fuse_upsample_ = true;
     int opt_fuse_stem_ = 2;

@@ -6,11 +6,13 @@
 #include "engine_impl.h"
 #include "engine_internal.h"
 #include "layer/activation.h"
+#include "layer/affine_grid.h"
 #include "layer/binary_op.h"
 #include "layer/cat.h"
 #include "layer/conv_2d.h"
 #include "layer/conv_transpose_2d.h"
 #include "layer/deform_conv_2d.h"
+#include "layer/grid_sample.h"
 #include "layer/group_norm.h"
 #include "layer/layout.h"
 #include "layer/linear.h"
@@ -34,7 +36,7 @@ bool HonoursPixelStride(const std::string& type) {
         "F.softmax", "F.log_softmax", "nn.PixelShuffle", "nn.PixelUnshuffle", "F.pixel_shuffle", "F.pixel_unshuffle", "nn.PReLU", "torch.flatten",
         "torch.chunk", "torch.split", "Tensor.slice", "torch.mean", "torch.sum", "torch.amax", "torch.amin", "nn.ReLU6", "F.relu6",
         "nn.Hardtanh", "F.hardtanh", "torch.clamp", "nn.Softplus", "F.softplus", "nn.Mish", "F.mish", "F.relu", "F.silu", "F.sigmoid", "F.hardsigmoid",
-        "F.hardswish", "F.leaky_relu", "F.tanh", "models.yolo.Detect", "torchvision.ops.DeformConv2d", "pnnx.Output"};
+        "F.hardswish", "F.leaky_relu", "F.tanh", "models.yolo.Detect", "torchvision.ops.DeformConv2d", "F.grid_sample", "F.affine_grid", "pnnx.Output"};
     return ok.count(type) > 0;
 }
 
@@ -79,6 +81,8 @@ Status EngineImpl::CreatePipeline() {
         CHECK_STATUS(FuseSiblingConvs(order));
         CHECK_STATUS(FusePoolChains(order));
         if (opt_fuse_layout_) CHECK_STATUS(FuseLayoutChains(order));
+        if (opt_fuse_layout_ && opt_fuse_grid_) CHECK_STATUS(FuseGridInPlace(order));   // (after the chains are composed: the run in front of a sampler is one step)
+        if (opt_fuse_grid_) CHECK_STATUS(FuseAffineGrids(order));
         if (opt_fuse_upsample_ && opt_alias_cat_) CHECK_STATUS(FuseUpsampleIntoConvs(order));   // (fp16 storage too since round 4)
         if (opt_fp16_ && opt_fuse_stem_) CHECK_STATUS(FuseStemPairs(order));
         if (opt_fp16_ && opt_fuse_stem_ > 1) CHECK_STATUS(FuseStemTriples(order));
@@ -384,6 +388,77 @@ Status EngineImpl::FuseLayoutChains(std::vector<Step>& order) {
     return Status::kSuccess;
 }
 
+// x.permute(0, 2, 3, 1) -> F.grid_sample(., grid)  ==>  the sampler reads the grid IN PLACE.  A rank-4 tensor is stored as dimensions
+// (0, 2, 3, 1), so the logical grid [N, Ho, Wo, 2] behind the permute would be moved into [N][Wo][2][Ho] order by a transpose launch, the two
+// coordinates of a pixel Ho elements apart -- while the tensor in front of it, [N, 2, Ho, Wo] stored NHWC, already has torch's dense grid
+// bytes.  When the grid operand is written by a layout step (a run composed by FuseLayoutChains, or a single operator) that only the sampler
+// reads, that is no graph output, and whose chain from its rank-4 root composes to exactly the permutation (0, 2, 3, 1) (permutes,
+// transposes and Tensor.contiguous; anything else leaves the plan alone), the layout step is retired and the sampler is pointed at the root.
+Status EngineImpl::FuseGridInPlace(std::vector<Step>& order) {
+    Pass p(*this, order);
+    for (size_t i = 0; i < order.size(); ++i) {
+        GridSample* gs = p.At<GridSample>(i, "F.grid_sample");
+        if (!gs || gs->Form() != GridSample::GridForm::kStored || order[i].op->inputs.size() != 2 || gs->InputNodes().size() != 2) continue;
+        const pnnx::Operand* grid = order[i].op->inputs[1];
+        if (!grid || !grid->producer || tensor_nodes_[grid->name] != gs->InputNodes()[1] || p.SoleConsumer(grid) != order[i].op) continue;
+        auto at = p.index.find(grid->producer);
+        if (at == p.index.end()) continue;
+        Layout* lay = p.At<Layout>(at->second);
+        if (!lay || lay->InputNodes().size() != 1 || lay->OutputNodes().size() != 1 || lay->OutputNodes()[0] != gs->InputNodes()[1]) continue;
+        TensorNode* root = lay->InputNodes()[0];
+        if (root->tensor.Shape().size() != 4) continue;
+        int perm[4] = {0, 1, 2, 3};   // perm[j]: the root dimension that result dimension j is
+        bool ok = true;
+        for (const LayoutOp& op : lay->Chain()) {
+            auto norm = [](int d) { return d < 0 ? d + 4 : d; };
+            if (op.kind == LayoutOp::kIdentity) continue;
+            if (op.kind == LayoutOp::kPermute && op.args.size() == 4) {
+                int next[4];
+                for (int j = 0; j < 4 && ok; ++j) {
+                    const int d = norm(op.args[(size_t)j]);
+                    ok = d >= 0 && d < 4;
+                    if (ok) next[j] = perm[d];
+                }
+                for (int j = 0; j < 4 && ok; ++j) perm[j] = next[j];
+            } else if (op.kind == LayoutOp::kTranspose && op.args.size() == 2) {
+                const int a = norm(op.args[0]), b = norm(op.args[1]);
+                ok = a >= 0 && a < 4 && b >= 0 && b < 4;
+                if (ok) std::swap(perm[a], perm[b]);
+            } else {
+                ok = false;
+            }
+            if (!ok) break;
+        }
+        if (!ok || perm[0] != 0 || perm[1] != 2 || perm[2] != 3 || perm[3] != 1) continue;
+        if (!gs->SetGridInPlace(root)) continue;
+        p.Retire(at->second, grid);
+    }
+    p.Compact();
+    return Status::kSuccess;
+}
+
+// F.affine_grid(theta) -> F.grid_sample(x, .)  ==>  ONE launch: the sampler computes the coordinates from theta (include/si_grid.h, the theta
+// source) and the grid is never written.  Conditions: the grid has the sampler as its only reader and is no graph output, and both operators
+// have the same align_corners (the kernel's theta source has one flag; torch warns about the other combination).  Spatial transformer
+// networks: Linear -> view(N, 2, 3) -> affine_grid -> grid_sample.
+Status EngineImpl::FuseAffineGrids(std::vector<Step>& order) {
+    Pass p(*this, order);
+    for (size_t i = 0; i < order.size(); ++i) {
+        AffineGrid* ag = p.At<AffineGrid>(i, "F.affine_grid");
+        if (!ag || ag->InputNodes().size() != 1 || order[i].op->outputs.size() != 1) continue;
+        const pnnx::Operand* grid = order[i].op->outputs[0];
+        const pnnx::Operator* c = p.SoleConsumer(grid);
+        if (!c || c->type != "F.grid_sample" || c->inputs.size() != 2 || c->inputs[1] != grid || c->inputs[0] == grid) continue;
+        GridSample* gs = dynamic_cast<GridSample*>(p.LayerOf(c));
+        if (!gs || gs->Form() != GridSample::GridForm::kStored || gs->align_corners_ != ag->align_corners_) continue;
+        if (gs->InputNodes().size() != 2 || gs->InputNodes()[1] != tensor_nodes_[grid->name]) continue;
+        if (!gs->SetTheta(ag->InputNodes()[0])) continue;
+        p.Retire(i, grid);
+    }
+    p.Compact();
+    return Status::kSuccess;
+}
+
 // nn.Upsample(nearest) -> torch.cat(dim = channels) -> 1x1 convs only  ==>  the upsample launch disappears: every consumer conv
 // reads the upsampled channel range from the LOW-RESOLUTION tensor at the nearest-neighbour source pixel (dual-source A rows,
 // si_hip_conv2d_upcat_f32), with the reference's index rule (src/layer/upsample.cpp:85-92), so the results are bit-identical to
@@ -682,10 +757,11 @@ Status EngineImpl::AliasConcats() {
             // flatten writes dense NCHW and Detect writes rank-3 rows: they never feed a rank-4 cat
             if (ok && (r->producer->type == "torch.flatten" || r->producer->type == "models.yolo.Detect")) ok = false;
             // the deformable conv refuses an output whose extent intersects an input's (include/si_deform.h), which a slice of a concat row
-            // that also holds one of its inputs would: its output (also behind a fused activation) keeps a buffer of its own
+            // that also holds one of its inputs would: its output (also behind a fused activation) keeps a buffer of its own.  The sampler
+            // of F.grid_sample has the same rule (include/si_grid.h)
             if (ok)
                 for (const Step& w : plan_)
-                    if (dynamic_cast<DeformConv2d*>(w.layer))
+                    if (dynamic_cast<DeformConv2d*>(w.layer) || dynamic_cast<GridSample*>(w.layer))
                         for (TensorNode* n : w.layer->OutputNodes()) ok = ok && n != tensor_nodes_[r->name];
             seen.insert(r);
             if (ok) {

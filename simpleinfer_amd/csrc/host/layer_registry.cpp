@@ -10,6 +10,7 @@ namespace SimpleInfer {
     void type##_LayerDestroyer(Layer*);
 
 SI_DECLARE_LAYER(AdaptiveAvgPool2d)
+SI_DECLARE_LAYER(AffineGrid)
 SI_DECLARE_LAYER(AvgPool2d)
 SI_DECLARE_LAYER(BatchNorm2d)
 SI_DECLARE_LAYER(BinaryOp)
@@ -18,6 +19,7 @@ SI_DECLARE_LAYER(Conv2d)
 SI_DECLARE_LAYER(ConvTranspose2d)
 SI_DECLARE_LAYER(DeformConv2d)
 SI_DECLARE_LAYER(Flatten)
+SI_DECLARE_LAYER(GridSample)
 SI_DECLARE_LAYER(GroupNorm)
 SI_DECLARE_LAYER(HardSigmoid)
 SI_DECLARE_LAYER(HardSwish)
@@ -58,7 +60,8 @@ static std::map<std::string, LayerRegistryEntry>& Table() {
     // Tensor.permute / torch.permute / Tensor.reshape / Tensor.view / torch.transpose / torch.squeeze / torch.unsqueeze / Tensor.contiguous (one
     // class, layer/layout.h: the layout algebra of layout_plan.h decides between a view and one permute launch); nn.MultiheadAttention
     // (layer/multihead_attention.h: two projections around the fused attention kernel of include/si_attention.h); torchvision.ops.DeformConv2d
-    // (layer/deform_conv_2d.h: DCNv1 / DCNv2 in one launch of include/si_deform.h; the type string is the one pnnx writes for the module)
+    // (layer/deform_conv_2d.h: DCNv1 / DCNv2 in one launch of include/si_deform.h; the type string is the one pnnx writes for the module);
+    // F.grid_sample and F.affine_grid (layer/grid_sample.h, layer/affine_grid.h: the sampler and the tiny grid kernel of include/si_grid.h)
     static std::map<std::string, LayerRegistryEntry> table = {
         SI_ENTRY("nn.AdaptiveAvgPool2d", AdaptiveAvgPool2d),
         SI_ENTRY("nn.AvgPool2d", AvgPool2d),
@@ -135,6 +138,8 @@ static std::map<std::string, LayerRegistryEntry>& Table() {
         SI_ENTRY("Tensor.contiguous", Layout),
         SI_ENTRY("models.yolo.Detect", YoloDetect),
         SI_ENTRY("torchvision.ops.DeformConv2d", DeformConv2d),
+        SI_ENTRY("F.grid_sample", GridSample),
+        SI_ENTRY("F.affine_grid", AffineGrid),
     };
     return table;
 }

@@ -477,6 +477,83 @@ def deform_conv2d_kernel_name(x_shape, off_shape, w_shape, mask=False, stride=(1
     return _native.hip().si_hip_deform_conv2d_kernel_name(C.byref(d), p[0], p[1], p[2] if mask else None, p[3]).decode()
 
 
+GRID_MODE = {"bilinear": 0, "nearest": 1, "bicubic": 2}
+GRID_PADDING = {"zeros": 0, "border": 1, "reflection": 2}
+
+
+def grid_sample_desc(x_shape, out_hw, mode="bilinear", padding_mode="zeros", align_corners=False, grid_strides=None, theta=False, in_ld=None,
+                     out_ld=None, spatial_dims=2):
+    """SiGridSampleDesc (include/si_grid.h) for an NHWC input of x_shape and an output of out_hw; grid_strides: the element strides
+    (gs_n, gs_h, gs_w, gs_k) of the grid, torch's dense [n, ho, wo, 2] when None; theta: the coordinates come from a [n, 2, 3] theta"""
+    n, h, w, c = x_shape
+    ho, wo = out_hw
+    gs = (0, 0, 0, 0) if theta else (tuple(grid_strides) if grid_strides is not None else (ho * wo * 2, wo * 2, 2, 1))
+    return _native.SiGridSampleDesc(n, c, h, w, ho, wo, in_ld or 0, out_ld or 0, GRID_MODE[mode], GRID_PADDING[padding_mode], 1 if align_corners else 0,
+                                    1 if theta else 0, spatial_dims, *[int(s) for s in gs])
+
+
+def grid_sample(x, grid=None, mode="bilinear", padding_mode="zeros", align_corners=False, theta=None, out_hw=None, grid_strides=None,
+                grid_off: int = 0, in_ld: Optional[int] = None, in_c_off: int = 0, in_fill=0.0, out_ld: Optional[int] = None, out_c_off: int = 0,
+                out_fill=0.0, full: bool = False):
+    """si_hip_grid_sample_f32 / _f16 (by x's dtype) on an NHWC x.  The coordinates come from `grid` -- an array of any shape that is uploaded as
+    it lies in memory and addressed with the element strides grid_strides = (gs_n, gs_h, gs_w, gs_k) from element grid_off on; a [n, ho, wo, 2]
+    array without strides is torch's dense grid -- or from theta= [n, 2, 3] with out_hw=(ho, wo) (F.affine_grid computed in the kernel).  The
+    grid (or theta) is converted to x's storage type.  The view hooks of x and the destination are conv_transpose2d's."""
+    H = _native.hip()
+    x = _float_storage(x)
+    half = x.dtype == np.float16
+    n, h, w, c = x.shape
+    assert (grid is None) != (theta is None), "give grid or theta"
+    if theta is not None:
+        src = np.ascontiguousarray(np.asarray(theta), dtype=x.dtype)
+        assert src.shape == (n, 2, 3) and out_hw is not None, (src.shape, out_hw)
+        ho, wo = out_hw
+    else:
+        src = np.ascontiguousarray(np.asarray(grid), dtype=x.dtype)
+        if grid_strides is None:
+            assert src.ndim == 4 and src.shape[0] == n and src.shape[3] == 2 and grid_off == 0, src.shape
+            out_hw = src.shape[1:3]
+        assert out_hw is not None, "a grid with explicit strides needs out_hw"
+        ho, wo = out_hw
+    d = grid_sample_desc(x.shape, (ho, wo), mode, padding_mode, align_corners, grid_strides, theta is not None, in_ld, out_ld)
+    dx, px = _view_in(x, in_ld, in_c_off, in_fill)
+    dg = DeviceBuffer.from_numpy(src)
+    pg = dg.ptr + src.itemsize * int(grid_off)
+    dy, py = _view_out((n, ho, wo), c, out_ld, out_c_off, out_fill, x.dtype)
+    name = "si_hip_grid_sample_f16" if half else "si_hip_grid_sample_f32"
+    LAST_KERNEL_NAME["si_hip_grid_sample"] = H.si_hip_grid_sample_kernel_name(C.byref(d), C.c_void_p(px), C.c_void_p(pg), C.c_void_p(py),
+                                                                             1 if half else 0).decode()
+    _chk(getattr(H, name)(C.byref(d), px, pg, py, None), name)
+    return _ret(dy.to_numpy((n, ho, wo, out_ld or c), x.dtype), c, out_c_off, full)
+
+
+def grid_sample_kernel_name(x_shape, out_hw, half=False, grid_strides=None, theta=False, in_ld=None, out_ld=None, align=256, grid_align=256) -> str:
+    """the instantiation for operands far apart whose x and out sit at an address that is `align` modulo 256 and whose grid sits at `grid_align`;
+    "none": a refused descriptor"""
+    d = grid_sample_desc(x_shape, out_hw, grid_strides=grid_strides, theta=theta, in_ld=in_ld, out_ld=out_ld)
+    p = [C.c_void_p(int(a) + (1 << 40) * (j + 1)) for j, a in enumerate((align, grid_align, align))]
+    return _native.hip().si_hip_grid_sample_kernel_name(C.byref(d), p[0], p[1], p[2], 1 if half else 0).decode()
+
+
+def affine_grid(theta, out_hw, align_corners=False, half=False, out_ld: Optional[int] = None, out_fill=0.0, full: bool = False):
+    """si_hip_affine_grid_f32 / _f16: theta [n, 2, 3] -> the grid [n, H, W, 2] of F.affine_grid(theta, (n, C, H, W)).  The kernel writes this
+    project's storage order of that rank-4 tensor, [n][W][2][H] with rows out_ld apart; the return value is the logical [n, H, W, 2] array
+    (full=True: the stored rows, [n, W, 2, out_ld])"""
+    H = _native.hip()
+    dt = np.float16 if half else np.float32
+    theta = np.ascontiguousarray(np.asarray(theta), dtype=dt)
+    n = theta.shape[0]
+    assert theta.shape == (n, 2, 3), theta.shape
+    h, w = out_hw
+    d = _native.SiAffineGridDesc(n, h, w, out_ld or 0, 1 if align_corners else 0)
+    dt_, dy = DeviceBuffer.from_numpy(theta), DeviceBuffer.from_numpy(_full((n, w, 2, out_ld or h), dt, out_fill), out=True)
+    name = "si_hip_affine_grid_f16" if half else "si_hip_affine_grid_f32"
+    LAST_KERNEL_NAME["si_hip_affine_grid"] = H.si_hip_affine_grid_kernel_name(C.byref(d), C.c_void_p(dt_.ptr), C.c_void_p(dy.ptr), 1 if half else 0).decode()
+    _chk(getattr(H, name)(C.byref(d), dt_.ptr, dy.ptr, None), name)
+    y = dy.to_numpy((n, w, 2, out_ld or h), dt)
+    return y if full else np.ascontiguousarray(y[..., :h].transpose(0, 3, 1, 2))
+
+
 def _range_flag(d, want):
     """a zeroed device word handed to an f32_split launch as SiConv2dDesc::range_flag (the kernel writes 1 when an operand left fp16's range)"""
     if not want:

@@ -191,6 +191,24 @@ class PnnxBuilder:
                         padding=(ph, pw), stride=(sh, sw)), attrs)
         return out
 
+    def grid_sample(self, x: str, grid: str, mode: str = "bilinear", padding_mode: str = "zeros", align_corners=False) -> str:
+        """F.grid_sample as pnnx writes the function: inputs (x [N, C, H, W], grid [N, Ho, Wo, 2]), keys align_corners= (a bool, or None for
+        torch's default), mode= and padding_mode= (bare strings)"""
+        n, c = self.shapes[x][:2]
+        gs = self.shapes[grid]
+        out = self._new_operand((n, c) + tuple(gs[1:-1]))
+        self._emit("F.grid_sample", self._opname("F_grid_sample"), [x, grid], [out],
+                   dict(align_corners="None" if align_corners is None else bool(align_corners), mode=str(mode), padding_mode=str(padding_mode)))
+        return out
+
+    def affine_grid(self, theta: str, size: Sequence[int], align_corners=False) -> str:
+        """F.affine_grid: theta [N, 2, 3] -> [N, H, W, 2] for size=(N, C, H, W); keys align_corners= and size="""
+        size = tuple(int(s) for s in size)
+        out = self._new_operand((size[0],) + size[2:] + (len(size) - 2,))
+        self._emit("F.affine_grid", self._opname("F_affine_grid"), [theta], [out],
+                   dict(align_corners="None" if align_corners is None else bool(align_corners), size=size))
+        return out
+
     def _unary(self, typ: str, prefix: str, x: str, params=None) -> str:
         out = self._new_operand(self.shapes[x])
         self._emit(typ, self._opname(prefix), [x], [out], params or {})
@@ -1139,6 +1157,50 @@ def build_toy_dcn_head(batch: int = 2, size: int = 32, mask: bool = True, seed: 
         y = b.deform_conv(x, b.conv(x, 18, 3, 1, 1), cout=24, k=3, s=1, p=1)
     b.output(b.conv(b.relu(y), 8, 1))
     return b
+
+
+def build_toy_stn(batch: int = 2, size: int = 32, seed: int = 0) -> PnnxBuilder:
+    """A spatial transformer at toy width: the localisation net conv 3 -> 8 stride 2 + ReLU -> maxpool 2 -> conv 8 -> 16 -> AdaptiveAvgPool2d(1) ->
+    flatten -> Linear(6) whose bias is the identity transform (1, 0, 0, 0, 1, 0) and whose weight is small, so theta stays near the identity ->
+    view(N, 2, 3) -> F.affine_grid(size of the image) -> F.grid_sample(image, grid; bilinear, zeros, align_corners=False) -> conv 3 -> 8."""
+    b = PnnxBuilder(seed)
+    img = b.input((batch, 3, size, size))
+    x = b.relu(b.conv(img, 8, 3, 2, 1))
+    x = b.conv(b.maxpool(x, 2, 2, 0), 16, 3, 1, 1)
+    x = b.flatten(b.adaptive_avgpool(x, (1, 1)))
+    theta = b.linear(x, 6)
+    name = "linear_%d" % (b._counts["linear"] - 1)
+    b.attrs[name + ".weight"] *= np.float32(0.25)
+    b.attrs[name + ".bias"][:] = np.asarray([1, 0, 0, 0, 1, 0], np.float32)
+    grid = b.affine_grid(b.view(theta, (batch, 2, 3)), (batch, 3, size, size), align_corners=False)
+    b.output(b.conv(b.grid_sample(img, grid, "bilinear", "zeros", False), 8, 3, 1, 1))
+    return b
+
+
+def build_toy_flow_warp(batch: int = 2, height: int = 24, width: int = 20, c: int = 8, seed: int = 0) -> PnnxBuilder:
+    """Warping features by a predicted flow (EDVR / BasicVSR++ / RIFE style).  Two graph inputs: the image [N, 3, H, W] and a channels-first
+    base grid [N, 2, H, W] (channel 0 x, channel 1 y, normalised for align_corners=True: flow_base_grid; graph constants are not served, so
+    the caller supplies it).  A feature conv 3 -> c; a 3x3 flow conv c -> 2 + nn.Tanh; base + flow -> permute(0, 2, 3, 1) ->
+    F.grid_sample(features, grid; bilinear, border, align_corners=True) -> 1x1 conv c -> c."""
+    b = PnnxBuilder(seed)
+    img = b.input((batch, 3, height, width))
+    base = b.input((batch, 2, height, width))
+    feat = b.conv(img, c, 3, 1, 1)
+    flow = b.tanh(b.conv(feat, 2, 3, 1, 1))
+    grid = b.permute(b.add(base, flow), (0, 2, 3, 1))
+    b.output(b.conv(b.grid_sample(feat, grid, "bilinear", "border", True), c, 1))
+    return b
+
+
+def flow_base_grid(batch: int, height: int, width: int) -> np.ndarray:
+    """the base grid input of build_toy_flow_warp as an NHWC array [N, H, W, 2] (the storage of the channels-first [N, 2, H, W] operand):
+    torch.linspace(-1, 1, size) per axis, x in channel 0 and y in channel 1 -- the identity warp under align_corners=True"""
+    xs = np.linspace(-1.0, 1.0, width, dtype=np.float64) if width > 1 else np.zeros(1)
+    ys = np.linspace(-1.0, 1.0, height, dtype=np.float64) if height > 1 else np.zeros(1)
+    g = np.empty((batch, height, width, 2), np.float32)
+    g[..., 0] = xs[None, None, :]
+    g[..., 1] = ys[None, :, None]
+    return g
 
 
 def build_toy_channel_shuffle(batch: int = 2, size: int = 16, c: int = 24, groups: int = 3, seed: int = 0) -> PnnxBuilder:
