@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from containment import checked_dest
+from f16_reference import assert_f16_elementwise
 from util import assert_detect_parity, assert_exact, assert_parity, rng_uniform
 
 SENTINEL = 0x7B   # the strided cases pre-fill the wider output row with this byte (61280 as fp16) and hold everything outside the slice to it
@@ -13,6 +14,9 @@ SENTINEL = 0x7B   # the strided cases pre-fill the wider output row with this by
 pytestmark = pytest.mark.gpu
 
 F16_TOL = 1e-3
+# beside every single-conv F16_TOL assertion: the ELEMENT-WISE bound f16_bound (tests/f16_reference.py) -- the bar the fp32 store of the same
+# accumulators carries (relative to max|ref|: PLAIN for a bare conv, FUSED where an activation is fused) plus ONE nearest-even store of the element
+PLAIN, FUSED = 2e-5, 1e-4
 
 
 @pytest.fixture(scope="module")
@@ -48,6 +52,7 @@ def test_conv_f16_vs_oracle_on_rounded_operands(hops, orc, n, ih, iw, ic, oc, k,
     got = hops.conv2d_f16(x, w, b, (s, s), (p, p), (d, d), g)
     assert got.dtype == np.float16
     assert_parity(got.astype(np.float32), ref, F16_TOL, what="fp16 conv")
+    assert_f16_elementwise(got, ref, PLAIN, "fp16 conv")
     # fp32 store of the same accumulators: only the accumulation order is left
     assert_parity(hops.conv2d_f16(x, w, b, (s, s), (p, p), (d, d), g, out_f32=True), ref, 2e-5, what="fp16 conv, fp32 out")
 
@@ -60,10 +65,13 @@ def test_conv_f16_fused_epilogue_strides_and_batch_invariance(hops, orc):
     y = orc.conv2d(x, w, b, (1, 1), (1, 1), path="naive")
     got = hops.conv2d_f16(x, w, b, (1, 1), (1, 1), act1="silu", residual=r).astype(np.float32)
     assert_parity(got, orc.activation("silu", y) + r, F16_TOL, what="silu + residual")
+    assert_f16_elementwise(got, orc.activation("silu", y) + r, FUSED, "silu + residual")
     got = hops.conv2d_f16(x, w, b, (1, 1), (1, 1), residual=r, act2="relu").astype(np.float32)
     assert_parity(got, orc.activation("relu", y + r), F16_TOL, what="residual + relu")
+    assert_f16_elementwise(got, orc.activation("relu", y + r), FUSED, "residual + relu")
     wide = hops.conv2d_f16(x, w, b, (1, 1), (1, 1), in_ld=96, out_ld=160, out_c_off=32, out_fill=hops.ByteFill(SENTINEL), full=True)
     assert_parity(checked_dest(wide, 32, 64, SENTINEL, "strided tensors").astype(np.float32), y, F16_TOL, what="strided tensors")
+    assert_f16_elementwise(checked_dest(wide, 32, 64, SENTINEL, "strided tensors"), y, PLAIN, "strided tensors")
     full = hops.conv2d_f16(x, w, b, (1, 1), (1, 1), act1="silu")
     assert_exact(hops.conv2d_f16(x[1:2], w, b, (1, 1), (1, 1), act1="silu")[0], full[1], "an image's result does not depend on the batch")
     with pytest.raises(hops.HipError):
@@ -80,10 +88,13 @@ def test_conv_f16_pointwise_padded_k(hops, orc, ic, oc):
     b = rng_uniform(ic + 2, (oc,), -0.5, 0.5)
     ref = orc.conv2d(x, w, b, path="naive")
     assert_parity(hops.conv2d_f16(x, w, b).astype(np.float32), ref, F16_TOL, what="dense")
+    assert_f16_elementwise(hops.conv2d_f16(x, w, b), ref, PLAIN, "dense")
     assert_parity(hops.conv2d_f16(x, w, b, out_f32=True), ref, 2e-5, what="fp32 out")
     assert_parity(hops.conv2d_f16(x, w, b, act1="hardswish").astype(np.float32), orc.activation("hardswish", ref), F16_TOL, what="hardswish")
+    assert_f16_elementwise(hops.conv2d_f16(x, w, b, act1="hardswish"), orc.activation("hardswish", ref), FUSED, "hardswish")
     got = hops.conv2d_f16(x, w, b, in_ld=ic + 24, in_fill=np.nan)
     assert_parity(got.astype(np.float32), ref, F16_TOL, what="strided input, NaN beyond the channels")
+    assert_f16_elementwise(got, ref, PLAIN, "strided input, NaN beyond the channels")
 
 
 @pytest.mark.parametrize("ic,oc,k,s", [(8, 16, 3, 2), (24, 32, 3, 1), (40, 72, 5, 1), (16, 8, 3, 1), (72, 130, 3, 2)])
@@ -99,8 +110,10 @@ def test_conv_f16_spatial_padded_k(hops, orc, ic, oc, k, s):
     ref = orc.conv2d(x, w, b, (s, s), (p, p), path="naive")
     got = hops.conv2d_f16(x, w, b, (s, s), (p, p))
     assert_parity(got.astype(np.float32), ref, F16_TOL, what="dense")
+    assert_f16_elementwise(got, ref, PLAIN, "dense")
     assert_parity(hops.conv2d_f16(x, w, b, (s, s), (p, p), out_f32=True), ref, 2e-5, what="fp32 out")
     assert_parity(hops.conv2d_f16(x, w, b, (s, s), (p, p), act1="silu").astype(np.float32), orc.activation("silu", ref), F16_TOL, what="silu")
+    assert_f16_elementwise(hops.conv2d_f16(x, w, b, (s, s), (p, p), act1="silu"), orc.activation("silu", ref), FUSED, "silu")
     wide = hops.conv2d_f16(x, w, b, (s, s), (p, p), in_ld=ic + 24, in_fill=np.nan)
     assert_exact(wide, got, "strided input, NaN beyond the channels")
     assert_exact(hops.conv2d_f16(x[2:], w, b, (s, s), (p, p)), got[2:], "batch position")
@@ -117,13 +130,17 @@ def test_conv_f16_depthwise(hops, orc, n, hw, c, k, s, p):
     got = hops.conv2d_f16(x, w, b, (s, s), (p, p), (1, 1), c)
     assert got.dtype == np.float16
     assert_parity(got.astype(np.float32), ref, F16_TOL, what="depthwise fp16")
+    assert_f16_elementwise(got, ref, PLAIN, "depthwise fp16")
     assert_parity(hops.conv2d_f16(x, w, b, (s, s), (p, p), (1, 1), c, act1="hardswish").astype(np.float32), orc.activation("hardswish", ref), F16_TOL,
                   what="hardswish")
+    assert_f16_elementwise(hops.conv2d_f16(x, w, b, (s, s), (p, p), (1, 1), c, act1="hardswish"), orc.activation("hardswish", ref), FUSED, "depthwise hardswish")
     r = h(rng_uniform(c + 3, ref.shape, -1, 1))
     assert_parity(hops.conv2d_f16(x, w, b, (s, s), (p, p), (1, 1), c, residual=r, act2="relu").astype(np.float32), orc.activation("relu", ref + r), F16_TOL,
                   what="residual + relu")
+    assert_f16_elementwise(hops.conv2d_f16(x, w, b, (s, s), (p, p), (1, 1), c, residual=r, act2="relu"), orc.activation("relu", ref + r), FUSED, "depthwise residual + relu")
     wide = hops.conv2d_f16(x, w, b, (s, s), (p, p), (1, 1), c, in_ld=c + 8, out_ld=c + 16, out_c_off=8, out_fill=hops.ByteFill(SENTINEL), full=True)
     assert_parity(checked_dest(wide, 8, c, SENTINEL, "depthwise strided").astype(np.float32), ref, F16_TOL, what="strided tensors")
+    assert_f16_elementwise(checked_dest(wide, 8, c, SENTINEL, "depthwise strided"), ref, PLAIN, "depthwise strided tensors")
     if n > 1:
         assert_exact(hops.conv2d_f16(x[1:2], w, b, (s, s), (p, p), (1, 1), c)[0], got[1], "batch invariance")
 
@@ -178,6 +195,7 @@ def test_stem_f16_output(hops, orc, k, s, p, oc, n, ih, iw, act):
     got = hops.conv2d_f16(x, w, b, (s, s), (p, p), act1=act)
     assert got.dtype == np.float16 and got.shape == ref.shape
     assert_parity(got.astype(np.float32), ref, F16_TOL, what="stem %dx%d" % (k, k))
+    assert_f16_elementwise(got, ref, PLAIN if act == "none" else FUSED, "stem %dx%d" % (k, k))
     # against the unrounded operands the error is the fp16 rounding of the image and the weights
     full = fact(orc.conv2d(x, w, b, (s, s), (p, p), path="naive"))
     assert_parity(got.astype(np.float32), full, 4 * F16_TOL, what="stem vs fp32 operands")
@@ -196,6 +214,7 @@ def test_stem_f16_strided_output_and_two_channel_image(hops, orc):
     ref = orc.conv2d(h(x), h(w), None, (2, 2), (2, 2), path="naive")
     wide = hops.conv2d_f16(x, w, None, (2, 2), (2, 2), in_ld=4, out_ld=96, out_c_off=32, out_fill=hops.ByteFill(SENTINEL), full=True)   # strided image: element-wise loads
     assert_parity(checked_dest(wide, 32, 32, SENTINEL, "strided stem").astype(np.float32), ref, F16_TOL, what="strided stem")
+    assert_f16_elementwise(checked_dest(wide, 32, 32, SENTINEL, "strided stem"), ref, PLAIN, "strided stem")
 
 
 def test_maxpool5_chain3_f16_exact(hops, orc):
@@ -214,6 +233,8 @@ def test_conv_split_f16(hops, orc):
     ya, yb = hops.conv2d_split_f16(x, wa, ba, wb, bb, act1="silu")
     assert_parity(ya.astype(np.float32), orc.activation("silu", orc.conv2d(x, wa, ba, path="naive")), F16_TOL, what="first sibling")
     assert_parity(yb.astype(np.float32), orc.activation("silu", orc.conv2d(x, wb, bb, path="naive")), F16_TOL, what="second sibling")
+    assert_f16_elementwise(ya, orc.activation("silu", orc.conv2d(x, wa, ba, path="naive")), FUSED, "first sibling")
+    assert_f16_elementwise(yb, orc.activation("silu", orc.conv2d(x, wb, bb, path="naive")), FUSED, "second sibling")
 
 
 @pytest.mark.parametrize("n,levels", [(2, ((8, 32), (4, 64), (2, 128))), (5, ((4, 32), (2, 64), (1, 96)))])
@@ -380,6 +401,7 @@ def test_s2c32_kernel_same_bits_as_generic_tiles(hops, orc, gpu, n, ih, iw, oc, 
     if act == "res+relu":
         ref = orc.activation("relu", ref)
     assert_parity(got.astype(np.float32), ref, F16_TOL, what="c32 patch kernel")
+    assert_f16_elementwise(got, ref, PLAIN if act == "none" else FUSED, "c32 patch kernel")
 
 
 @pytest.mark.parametrize("n,hh,ww,ic,oc,act,res", [
@@ -427,6 +449,7 @@ def test_slab_kernel_same_bits_as_generic_tiles(hops, orc, gpu, n, hh, ww, ic, o
     if act == "res+relu":
         ref = orc.activation("relu", ref)
     assert_parity(got.astype(np.float32), ref, F16_TOL, what="slab kernel")
+    assert_f16_elementwise(got, ref, PLAIN if act == "none" else FUSED, "slab kernel")
 
 
 @pytest.mark.parametrize("n,hh,ww,c,res", [
@@ -649,6 +672,7 @@ def test_conv_f16_reads_upsampled_source(hops, orc, n, lh, lw, cl, cs, oc, scale
     assert got.dtype == np.float16
     assert_exact(got, hops.conv2d_f16(cat, w, b, act1="silu"), "dual-source fp16 conv == conv over the materialised concat")
     assert_parity(got.astype(np.float32), orc.activation("silu", orc.conv2d(cat, w, b)), F16_TOL, what="vs the oracle's upsample + cat + conv")
+    assert_f16_elementwise(got, orc.activation("silu", orc.conv2d(cat, w, b, path="naive")), FUSED, "vs the float64 conv over the oracle's upsample + cat")
     if oc >= 64:
         ya, yb = hops.conv2d_upcat_f16(low, skip, w, b, scale, up_first, act1="silu", split_oc=32)
         assert_exact(np.concatenate([ya, yb], -1), got, "sibling-split form")
