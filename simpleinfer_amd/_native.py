@@ -143,6 +143,12 @@ class SiAffineGridDesc(C.Structure):
     _fields_ = [(k, C.c_int) for k in ("n", "h", "w", "out_ld", "align_corners")]
 
 
+class SiRoiAlignDesc(C.Structure):
+    """include/si_roi.h; in_ld / out_ld: pixel strides of x and out, rois_ld: row stride of the fp32 boxes (0: dense)"""
+    _fields_ = [(k, C.c_int) for k in ("n", "c", "h", "w", "k", "ph", "pw", "in_ld", "out_ld", "rois_ld", "sampling_ratio", "aligned")] + [
+        ("spatial_scale", C.c_float)]
+
+
 class SiLayoutNest(C.Structure):
     """include/si_layout.h; what si_layout_plan returns: view != 0, or the loop nest of the copy"""
     _fields_ = [("view", C.c_int), ("rank", C.c_int), ("dims", C.c_int * 8), ("in_stride", C.c_longlong * 8)]
@@ -396,9 +402,15 @@ def hip():
         "si_hip_affine_grid_f16": (i, [C.POINTER(SiAffineGridDesc), vp, vp, vp]),
         "si_hip_affine_grid_kernel_name": (C.c_char_p, [C.POINTER(SiAffineGridDesc), vp, vp, i]),
     }
+    # include/si_roi.h: torchvision.ops.RoIAlign / roi_align (the boxes are fp32 for both entries)
+    roi_ = {
+        "si_hip_roi_align_f32": (i, [C.POINTER(SiRoiAlignDesc), vp, vp, vp, vp]),
+        "si_hip_roi_align_f16": (i, [C.POINTER(SiRoiAlignDesc), vp, vp, vp, vp]),
+        "si_hip_roi_align_kernel_name": (C.c_char_p, [C.POINTER(SiRoiAlignDesc), vp, vp, vp, i]),
+    }
     for name, (res, args) in (list(sig.items()) + list(norm.items()) + list(pad.items()) + list(pool.items()) + list(softmax.items()) +
                               list(superres.items()) + list(slice_.items()) + list(reduce_.items()) + list(act.items()) + list(permute_.items()) +
-                              list(attention_.items()) + list(deform_.items()) + list(grid_.items())):
+                              list(attention_.items()) + list(deform_.items()) + list(grid_.items()) + list(roi_.items())):
         fn = getattr(L, name)  # AttributeError here = header/library mismatch, which tests check
         fn.restype = res
         fn.argtypes = args
@@ -415,6 +427,7 @@ def hip():
     L._si_attention_signatures = attention_
     L._si_deform_signatures = deform_
     L._si_grid_signatures = grid_
+    L._si_roi_signatures = roi_
     _hip = L
     return L
 

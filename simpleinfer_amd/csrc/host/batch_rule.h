@@ -97,7 +97,13 @@ enum class BatchFamily {
     kMove,          // permute / transpose: moves the batch dimension, combines nothing
     kReshape,       // reshape / view / flatten / squeeze / unsqueeze / contiguous: per-image while the batch stays a dimension of its own
     kAttention,     // nn.MultiheadAttention: reads the batch from dimension 0 (batch_first) or 1
+    kRoi,           // torchvision.ops.RoIAlign / roi_align: boxes [K, 5] that name their image by an index in the data -- never per-image
 };
+
+// why an operator of the family kRoi is never per-image (also the engine's reason for refusing to re-batch a graph that holds one)
+inline const char* RoiBatchReason() {
+    return "the boxes name their image by an index in the data: dimension 0 of the output counts boxes, not images";
+}
 
 inline BatchFamily BatchFamilyOf(const std::string& type) {
     static const std::map<std::string, BatchFamily> table = {
@@ -180,6 +186,8 @@ inline BatchFamily BatchFamilyOf(const std::string& type) {
         {"torch.unsqueeze", BatchFamily::kReshape},
         {"Tensor.contiguous", BatchFamily::kReshape},
         {"nn.MultiheadAttention", BatchFamily::kAttention},
+        {"torchvision.ops.RoIAlign", BatchFamily::kRoi},
+        {"torchvision.ops.roi_align", BatchFamily::kRoi},
     };
     auto it = table.find(type);
     return it == table.end() ? BatchFamily::kUnknown : it->second;
@@ -204,6 +212,11 @@ inline bool PerImageOperator(const pnnx::Operator* op, const std::vector<BatchOp
         return false;
     }
     if (family == BatchFamily::kInput) return true;
+    if (family == BatchFamily::kRoi) {
+        // whatever the shapes say: K == N is a coincidence, and a slab of the boxes still indexes every image
+        why = RoiBatchReason();
+        return false;
+    }
     if (family == BatchFamily::kOutput) {
         for (const BatchOperand& o : in)
             if (o.axis != 0) {
@@ -346,7 +359,13 @@ struct BatchMixingEntry {
 inline std::vector<BatchMixingEntry> FindBatchMixing(const std::vector<pnnx::Operator*>& ops) {
     std::vector<BatchMixingEntry> found;
     const int file_batch = FileBatch(ops);
-    if (file_batch <= 0) return found;   // no static batch: such a graph is never split
+    if (file_batch <= 0) {
+        // no static batch: such a graph is never split.  The graph inputs of a box head, [N, ...] and [K, 5], disagree whenever K != N: its
+        // kRoi operators are listed all the same, so that what the engine logs and refuses does not depend on whether K happens to equal N
+        for (const pnnx::Operator* op : ops)
+            if (BatchFamilyOf(op->type) == BatchFamily::kRoi) found.push_back({op->name, op->type, RoiBatchReason()});
+        return found;
+    }
     const std::map<const pnnx::Operand*, int> axes = FollowBatchAxes(ops, file_batch);
     auto describe = [&](const std::vector<pnnx::Operand*>& operands) {
         std::vector<BatchOperand> v;

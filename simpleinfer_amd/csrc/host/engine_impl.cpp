@@ -217,6 +217,13 @@ Status EngineImpl::CreateTensorNodes() {
     // which is what the model means at batch N; it is cutting ONE batch into pieces that such an operator forbids, batch_rule.h.)
     int file_batch = 0;
     if (opt_batch_ > 0) {
+        // a box head: the graph inputs [N, ...] and [K, 5] disagree in dimension 0, and where K == N by coincidence the rewrite below would
+        // change the number of boxes with the number of images.  Neither is re-batched
+        for (const pnnx::Operator* op : graph_->ops)
+            if (BatchFamilyOf(op->type) == BatchFamily::kRoi) {
+                LOG(ERROR) << "re-batch: [" << op->name << "] (" << op->type << "): " << RoiBatchReason() << ": served at the file's batch only";
+                return Status::kUnsupport;
+            }
         for (pnnx::Operand* opd : graph_->operands)
             if (opd->producer && opd->producer->inputs.empty() && !opd->shape.empty()) {
                 if (file_batch != 0 && file_batch != opd->shape[0]) {

@@ -34,6 +34,7 @@ SI_DECLARE_LAYER(PixelShuffle)
 SI_DECLARE_LAYER(PReLU)
 SI_DECLARE_LAYER(Reduce)
 SI_DECLARE_LAYER(ReLU)
+SI_DECLARE_LAYER(RoiAlign)
 SI_DECLARE_LAYER(Sigmoid)
 SI_DECLARE_LAYER(SiLU)
 SI_DECLARE_LAYER(Slice)
@@ -61,7 +62,8 @@ static std::map<std::string, LayerRegistryEntry>& Table() {
     // class, layer/layout.h: the layout algebra of layout_plan.h decides between a view and one permute launch); nn.MultiheadAttention
     // (layer/multihead_attention.h: two projections around the fused attention kernel of include/si_attention.h); torchvision.ops.DeformConv2d
     // (layer/deform_conv_2d.h: DCNv1 / DCNv2 in one launch of include/si_deform.h; the type string is the one pnnx writes for the module);
-    // F.grid_sample and F.affine_grid (layer/grid_sample.h, layer/affine_grid.h: the sampler and the tiny grid kernel of include/si_grid.h)
+    // F.grid_sample and F.affine_grid (layer/grid_sample.h, layer/affine_grid.h: the sampler and the tiny grid kernel of include/si_grid.h);
+    // torchvision.ops.RoIAlign / torchvision.ops.roi_align (one class, layer/roi_align.h: the box-pooling kernel of include/si_roi.h)
     static std::map<std::string, LayerRegistryEntry> table = {
         SI_ENTRY("nn.AdaptiveAvgPool2d", AdaptiveAvgPool2d),
         SI_ENTRY("nn.AvgPool2d", AvgPool2d),
@@ -140,6 +142,8 @@ static std::map<std::string, LayerRegistryEntry>& Table() {
         SI_ENTRY("torchvision.ops.DeformConv2d", DeformConv2d),
         SI_ENTRY("F.grid_sample", GridSample),
         SI_ENTRY("F.affine_grid", AffineGrid),
+        SI_ENTRY("torchvision.ops.RoIAlign", RoiAlign),
+        SI_ENTRY("torchvision.ops.roi_align", RoiAlign),
     };
     return table;
 }

@@ -310,17 +310,19 @@ def _ret(y, c, c_off, full):
     return y[..., c_off:c_off + c].copy()
 
 
-def _run_desc_op(stem, d, x, out_pixel_shape, oc, in_ld, in_c_off, in_fill, out_ld, out_c_off, out_fill, full):
+def _run_desc_op(stem, d, x, out_pixel_shape, oc, in_ld, in_c_off, in_fill, out_ld, out_c_off, out_fill, full, operands=()):
     """what the descriptor wrappers share: si_hip_<stem>_f32 / _f16 (by x's dtype) with descriptor `d`, from the channel view of x to a fresh
-    view of `out_pixel_shape` pixels of `oc` channels; records LAST_KERNEL_NAME["si_hip_<stem>"] for the two pointers"""
+    view of `out_pixel_shape` pixels of `oc` channels; records LAST_KERNEL_NAME["si_hip_<stem>"] for the two pointers.  operands: device
+    pointers of further read-only operands, which the entry takes between x and the destination (the boxes of roi_align)"""
     H = _native.hip()
     half = x.dtype == np.float16
     name = "si_hip_%s_%s" % (stem, "f16" if half else "f32")
     out_pixel_shape = tuple(out_pixel_shape)
     (dx, px), (dy, py) = _view_in(x, in_ld, in_c_off, in_fill), _view_out(out_pixel_shape, oc, out_ld, out_c_off, out_fill, x.dtype)
     kernel_name = getattr(H, "si_hip_%s_kernel_name" % stem)
-    LAST_KERNEL_NAME["si_hip_" + stem] = kernel_name(C.byref(d), C.c_void_p(px), C.c_void_p(py), 1 if half else 0).decode()
-    _chk(getattr(H, name)(C.byref(d), px, py, None), name)
+    mid = [C.c_void_p(int(p)) for p in operands]
+    LAST_KERNEL_NAME["si_hip_" + stem] = kernel_name(C.byref(d), C.c_void_p(px), *mid, C.c_void_p(py), 1 if half else 0).decode()
+    _chk(getattr(H, name)(C.byref(d), px, *mid, py, None), name)
     return _ret(dy.to_numpy(out_pixel_shape + (out_ld or oc,), x.dtype), oc, out_c_off, full)
 
 
@@ -552,6 +554,41 @@ def affine_grid(theta, out_hw, align_corners=False, half=False, out_ld: Optional
     _chk(getattr(H, name)(C.byref(d), dt_.ptr, dy.ptr, None), name)
     y = dy.to_numpy((n, w, 2, out_ld or h), dt)
     return y if full else np.ascontiguousarray(y[..., :h].transpose(0, 3, 1, 2))
+
+
+def roi_align_desc(x_shape, k, output_size, spatial_scale=1.0, sampling_ratio=-1, aligned=False, in_ld=None, out_ld=None, rois_ld=None):
+    """SiRoiAlignDesc (include/si_roi.h) for an NHWC input of x_shape, k boxes and output_size = ph or (ph, pw)"""
+    n, h, w, c = x_shape
+    ph, pw = _pair(output_size)
+    return _native.SiRoiAlignDesc(n, c, h, w, int(k), ph, pw, in_ld or 0, out_ld or 0, rois_ld or 0, int(sampling_ratio), 1 if aligned else 0,
+                                  float(spatial_scale))
+
+
+def roi_align(x, rois, output_size, spatial_scale=1.0, sampling_ratio=-1, aligned=False, rois_ld: Optional[int] = None, rois_fill=0.0,
+              in_ld: Optional[int] = None, in_c_off: int = 0, in_fill=0.0, out_ld: Optional[int] = None, out_c_off: int = 0, out_fill=0.0,
+              full: bool = False):
+    """si_hip_roi_align_f32 / _f16 (by x's dtype) on an NHWC x [n, h, w, c] and boxes [k, 5] of (image index, x1, y1, x2, y2), which are
+    uploaded as fp32 whatever x is, in rows of rois_ld floats whose other columns hold rois_fill.  Returns [k, ph, pw, c].  The view hooks of
+    x and the destination are conv_transpose2d's."""
+    x = _float_storage(x)
+    rois = np.ascontiguousarray(np.asarray(rois), dtype=np.float32)
+    assert rois.ndim == 2 and rois.shape[1] == 5, rois.shape
+    k = rois.shape[0]
+    if rois_ld and rois_ld != 5:
+        rows = _full((k, rois_ld), np.float32, rois_fill)
+        rows[:, :5] = rois
+        rois = rows
+    ph, pw = _pair(output_size)
+    d = roi_align_desc(x.shape, k, (ph, pw), spatial_scale, sampling_ratio, aligned, in_ld, out_ld, rois_ld)
+    dr = DeviceBuffer.from_numpy(rois)
+    return _run_desc_op("roi_align", d, x, (k, ph, pw), x.shape[-1], in_ld, in_c_off, in_fill, out_ld, out_c_off, out_fill, full, operands=(dr.ptr,))
+
+
+def roi_align_kernel_name(x_shape, k, output_size, half=False, sampling_ratio=-1, in_ld=None, out_ld=None, rois_ld=None, align=256) -> str:
+    """the instantiation for operands far apart whose x and out sit at an address that is `align` modulo 256; "none": a refused descriptor"""
+    d = roi_align_desc(x_shape, k, output_size, sampling_ratio=sampling_ratio, in_ld=in_ld, out_ld=out_ld, rois_ld=rois_ld)
+    p = [C.c_void_p(int(a) + (1 << 40) * (j + 1)) for j, a in enumerate((align, 256, align))]
+    return _native.hip().si_hip_roi_align_kernel_name(C.byref(d), p[0], p[1], p[2], 1 if half else 0).decode()
 
 
 def _range_flag(d, want):

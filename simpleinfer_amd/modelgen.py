@@ -209,6 +209,18 @@ class PnnxBuilder:
                    dict(align_corners="None" if align_corners is None else bool(align_corners), size=size))
         return out
 
+    def roi_align(self, x: str, rois: str, output_size, spatial_scale: float = 1.0, sampling_ratio: int = -1, aligned: bool = False,
+                  functional: bool = False) -> str:
+        """torchvision.ops.RoIAlign as pnnx writes the module (functional: torchvision.ops.roi_align, the same keys): inputs (x [N, C, H, W],
+        rois [K, 5] with rows (image index, x1, y1, x2, y2)), keys aligned=, output_size= (a pair), sampling_ratio=, spatial_scale="""
+        c = self.shapes[x][1]
+        ph, pw = (output_size, output_size) if isinstance(output_size, int) else tuple(output_size)
+        out = self._new_operand((self.shapes[rois][0], c, ph, pw))
+        typ, prefix = ("torchvision.ops.roi_align", "torchvision_ops_roi_align") if functional else ("torchvision.ops.RoIAlign", "roialign")
+        self._emit(typ, self._opname(prefix), [x, rois], [out],
+                   dict(aligned=bool(aligned), output_size=(ph, pw), sampling_ratio=int(sampling_ratio), spatial_scale=float(spatial_scale)))
+        return out
+
     def _unary(self, typ: str, prefix: str, x: str, params=None) -> str:
         out = self._new_operand(self.shapes[x])
         self._emit(typ, self._opname(prefix), [x], [out], params or {})
@@ -1201,6 +1213,52 @@ def flow_base_grid(batch: int, height: int, width: int) -> np.ndarray:
     g[..., 0] = xs[None, None, :]
     g[..., 1] = ys[None, :, None]
     return g
+
+
+def build_toy_box_head(batch: int = 2, boxes: int = 6, c: int = 8, height: int = 20, width: int = 24, classes: int = 5, seed: int = 0,
+                       spatial_scale: float = 0.25, sampling_ratio: int = 2, aligned: bool = False) -> PnnxBuilder:
+    """The box head of Faster R-CNN at toy width.  Two graph inputs: the features [N, c, H, W] and the boxes [K, 5], rows (image index, x1,
+    y1, x2, y2) in image pixels.  RoIAlign 7x7 -> 3x3 conv c -> 2c + ReLU -> flatten -> Linear(32) + ReLU -> two Linear heads: the class
+    scores [K, classes] and the box deltas [K, 4 classes]."""
+    b = PnnxBuilder(seed)
+    feat = b.input((batch, c, height, width))
+    rois = b.input((boxes, 5))
+    x = b.roi_align(feat, rois, 7, spatial_scale, sampling_ratio, aligned)
+    x = b.relu(b.conv(x, 2 * c, 3, 1, 1))
+    x = b.relu(b.linear(b.flatten(x), 32))
+    scores, deltas = b.linear(x, classes), b.linear(x, 4 * classes)
+    b.output(scores)
+    b.output(deltas)
+    return b
+
+
+def build_toy_mask_head(batch: int = 2, boxes: int = 5, c: int = 8, height: int = 20, width: int = 24, classes: int = 3, seed: int = 0,
+                        spatial_scale: float = 0.25, sampling_ratio: int = 2, aligned: bool = True) -> PnnxBuilder:
+    """The mask head of Mask R-CNN at toy width.  Graph inputs as build_toy_box_head's.  The functional torchvision.ops.roi_align 14x14 -> two
+    3x3 convs c -> c + ReLU -> ConvTranspose2d 2x2 stride 2 + ReLU -> 1x1 conv to `classes` -> Sigmoid: masks [K, classes, 28, 28]."""
+    b = PnnxBuilder(seed)
+    feat = b.input((batch, c, height, width))
+    rois = b.input((boxes, 5))
+    x = b.roi_align(feat, rois, 14, spatial_scale, sampling_ratio, aligned, functional=True)
+    x = b.relu(b.conv(x, c, 3, 1, 1))
+    x = b.relu(b.conv(x, c, 3, 1, 1))
+    x = b.relu(b.conv_transpose(x, c, 2, 2))
+    b.output(b.sigmoid(b.conv(x, classes, 1)))
+    return b
+
+
+def toy_rois(boxes: int, batch: int, height: int, width: int, spatial_scale: float = 0.25, seed: int = 0) -> np.ndarray:
+    """boxes [K, 5] for the two toys: image indices round the batch, corners in image pixels (the map's extent over spatial_scale), a few of
+    them crossing the border"""
+    u = seeded_uniform("toy_rois", (boxes, 4), 0.0, 1.0, seed)
+    ih, iw = height / spatial_scale, width / spatial_scale
+    r = np.empty((boxes, 5), np.float32)
+    r[:, 0] = np.arange(boxes) % batch
+    r[:, 1] = (u[:, 0] * 0.8 - 0.1) * iw
+    r[:, 2] = (u[:, 1] * 0.8 - 0.1) * ih
+    r[:, 3] = r[:, 1] + (0.1 + 0.5 * u[:, 2]) * iw
+    r[:, 4] = r[:, 2] + (0.1 + 0.5 * u[:, 3]) * ih
+    return r
 
 
 def build_toy_channel_shuffle(batch: int = 2, size: int = 16, c: int = 24, groups: int = 3, seed: int = 0) -> PnnxBuilder:
