@@ -62,10 +62,20 @@ public:
     //   "device"          HIP device ordinal (default: current device)
     //   "fuse"            1/0  fold activation / residual add into the conv epilogue (default 1)
     //   "alias_cat"       1/0  producers write straight into torch.cat outputs (default 1)
+    //   "alias_split"     1/0  torch.chunk / torch.split / Tensor.slice outputs that are channel ranges are views of the input (default 1; 0: always copied)
+    //   "fuse_layout"     1/0  a run of permute / reshape / view / transpose / squeeze / unsqueeze operators is planned as ONE layout step
+    //                          (default 1; 0: one step each)
+    //   "alias_view"      1/0  a layout step that moves no byte makes its output a view of its input's buffer (default 1; 0: one copy)
+    //   "fuse_grid"       1/0  F.grid_sample reads a permuted grid in place and an affine grid from theta (default 1; 0: the grid is written
+    //                          first -- A/B runs)
     //   "arena"           1/0  intermediate operands share one HBM arena by lifetime (default 1); 0 = one allocation per operand,
     //                          as the reference does (src/engine_impl.cpp:465-482)
     //   "fuse_upsample"   1/0  a 1x1 conv that consumes cat(upsample(x), skip) reads x at the source pixel; the upsample launch
     //                          and its output disappear (default 1; needs "fuse" and "alias_cat")
+    //   "fuse_stem"       0/1/2  fp16: 1 the RGB stem conv and the 3x3 stride-2 conv behind it in one launch; 2 (default) ... and the 1x1
+    //                          conv(s) reading that; 0 off
+    //   "fuse_pw"         0/1/2  fp16: 1 (default) a C3 bottleneck's 1x1 conv computed inside the kernel of its 3x3 conv; 2 ... and the C3's
+    //                          closing conv behind its last 64-channel pair (bit-identical, measured slower: opt-in); 0 off
     //   "winograd"        0/1/2  3x3 stride-1 convs: 1 (default) fused Winograd F(2,3) where it is the faster kernel, as
     //                          the reference does on the CPU; 0 = implicit GEMM everywhere; 2 = fused Winograd F(4,3)
     //   "fp16"            1/0  fp16 storage for internal activations and weights, fp16 MFMA with fp32 accumulation;
@@ -87,7 +97,9 @@ public:
     //                          overflowed step, and gets what the default engine computes for that layer.  (ForwardAsync() steps queued
     //                          without a Sync() between them: the guard acts at the Sync(), on the last one.)  Tensors whose every
     //                          value is tiny (scale ~1e-6) keep 1e-5-class, not fp32-class, relative accuracy (fp16 subnormals).
-    //   "f32_tile", "wino23_form", "wino23_ocg", "f16_tile", "f16_detect_tile", "f16_s2c32", "f16_slab", "f16_slab_w2", "f16_pw_patch"
+    //   "f32_split_policy" 1..4  which layers "f32_split" takes: 1 round 5's set, 2 + sibling-fused and wide 1x1 layers from K = 256,
+    //                          3 + the layers that read upsample + concat at the source, 4 (default) + the RGB stem
+    //   "f32_tile", "wino23_form", "wino23_ocg", "f16_tile", "f16_detect_tile", "f16_s2c32", "f16_slab", "f16_slab_w2", "f16_pw_patch", "split3_bm"
     //                          kernel-form choices handed to every conv launch (SiConvPlan, include/si_hip.h): A/B runs and tests.  Every
     //                          form of a kernel family produces the same bits; the default leaves the choice to the launch-size policy.
     //   "batch"           N>0  serve batch N whatever batch the .param file was traced with (default 0: as in the file)

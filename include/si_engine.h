@@ -19,8 +19,7 @@ typedef struct SiEngine SiEngine;
 /* Engine::Engine / ~Engine */
 int si_engine_create(SiEngine** engine);
 int si_engine_destroy(SiEngine* engine);
-/* Engine::SetOption -- before load_model.  Keys: device, fuse, alias_cat, fuse_upsample, arena, winograd, fp16, batch, graph, outputs_to_host, streams, host_slices, detect_stream
- * (include/engine.h documents the values) */
+/* Engine::SetOption -- before load_model.  The keys and their values: the list at Engine::SetOption in include/engine.h */
 int si_engine_set_option(SiEngine* engine, const char* key, int value);
 /* Engine::LoadModel / Release (reference src/engine_impl.cpp:16-75, :77-127) */
 int si_engine_load_model(SiEngine* engine, const char* param_path, const char* bin_path);

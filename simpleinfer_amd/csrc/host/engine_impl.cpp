@@ -18,43 +18,7 @@ EngineImpl::EngineImpl() {}
 EngineImpl::~EngineImpl() { Release(); }
 
 Status EngineImpl::SetOption(const std::string& key, int value) {
-    if (key == "device") opt_device_ = value;
-    else if (key == "fuse") opt_fuse_ = value != 0;
-    else if (key == "alias_cat") opt_alias_cat_ = value != 0;
-    else if (key == "alias_split") opt_alias_split_ = value != 0;   // chunk / split / slice outputs on the channel axis as views of the input (default 1)
-    else if (key == "fuse_layout") opt_fuse_layout_ = value != 0;   // runs of layout operators as one step (default 1)
-    else if (key == "fuse_grid") opt_fuse_grid_ = value != 0;       // F.grid_sample reads its grid in place / from theta (default 1; 0: A/B runs)
-    else if (key == "alias_view") opt_alias_view_ = value != 0;     // layout steps that move no byte as views of their input (default 1)
-    else if (key == "graph") opt_graph_ = value != 0;
-    else if (key == "outputs_to_host") opt_outputs_to_host_ = value != 0;
-    else if (key == "fp16") opt_fp16_ = value != 0;
-    else if (key == "batch") opt_batch_ = value;  // > 0: re-batch the graph at load (the file bakes its batch into every shape)
-    else if (key == "arena") opt_arena_ = value != 0;  // 1 (default): intermediates share one arena by lifetime; 0: one hipMalloc each
-    else if (key == "fuse_pw") opt_fuse_pw_ = value;           // fp16: 1 (default) a C3 bottleneck's 1x1 conv computed inside the kernel of its 3x3 conv; 2 ... and the C3's closing conv behind its last 64-channel pair (measured slower: opt-in); 0 off
-    else if (key == "fuse_stem") opt_fuse_stem_ = value;       // fp16: 1 RGB stem conv + the 3x3 s2 conv behind it in one launch; 2 (default) ... and the 1x1 conv(s) reading that; 0 off
-    else if (key == "fuse_upsample") opt_fuse_upsample_ = value != 0;  // upsample -> cat -> 1x1 conv read at the source (default 1)
-    else if (key == "detect_priority") opt_detect_priority_ = value < 0 ? -1 : (value > 0 ? 1 : 0);   // priority of Detect's side stream: -1 low, 0 default, +1 high
-    else if (key == "detect_stream") opt_detect_stream_ = value;  // Detect's early levels on a second stream: 0 never, 1 (default) where they have enough work, 2 always
-    else if (key == "f32_split") opt_f32_split_ = value != 0;   // fp32 tensors, conv contraction from three fp16 MFMA products (default 0: true fp32)
-    // kernel-form choices (SiConvPlan, include/si_hip.h; every form of a family produces the same bits): A/B runs and tests.  Until round 6
-    // these were process-global setters / environment switches of the kernel library.
-    else if (key == "f32_tile") { opt_plan_.f32_tile = value; opt_plan_set_ = true; }
-    else if (key == "wino23_form") { opt_plan_.wino23_form = value; opt_plan_set_ = true; }
-    else if (key == "wino23_ocg") { opt_plan_.wino23_ocg = value; opt_plan_set_ = true; }
-    else if (key == "f16_tile") { opt_plan_.f16_tile = value; opt_plan_set_ = true; }
-    else if (key == "f16_detect_tile") { opt_plan_.f16_detect_tile = value; opt_plan_set_ = true; }
-    else if (key == "f16_s2c32") { opt_plan_.f16_s2c32 = value; opt_plan_set_ = true; }
-    else if (key == "f16_slab") { opt_plan_.f16_slab = value; opt_plan_set_ = true; }
-    else if (key == "f16_slab_w2") { opt_plan_.f16_slab_w2 = value; opt_plan_set_ = true; }
-    else if (key == "f16_pw_patch") { opt_plan_.f16_pw_patch = value; opt_plan_set_ = true; }
-    else if (key == "split3_bm") { opt_plan_.split3_bm = value; opt_plan_set_ = true; }
-    else if (key == "f32_split_policy") opt_f32_split_policy_ = value;   // which layers f32_split takes: 1 round 5's, 2 + sibling-fused / wide 1x1 from K = 256, 3 + dual-source (upsampled) layers, 4 (default) + the RGB stem
-    else if (key == "winograd") opt_winograd_ = value;  // 0 off, 1 F(2,3) where faster (default), 2 F(4,3) on those layers
-    else if (key == "streams") opt_streams_ = value;  // 2: two half-batch lanes on two streams, 1 (default): one stream
-    else if (key == "_fail_slicer") debug_fail_slicer_ = value != 0;  // tests: the sliced pipeline's setup fails half way
-    else if (key == "pin_inputs") opt_pin_inputs_ = value != 0;  // host_slices: pin a borrowed input buffer in place (default 0, see engine.h)
-    else if (key == "host_slices") opt_host_slices_ = value;  // host tensors in and out: G pipelined batch slices per Forward(), 1 off, 0 (default) auto
-    else {
+    if (!opt_.Set(key, value)) {   // (the keys and their rules: engine_options.h)
         LOG(ERROR) << "unknown engine option [" << key << "]";
         return Status::kUnsupport;
     }
@@ -160,7 +124,7 @@ Status EngineImpl::Release() {
 
 Status EngineImpl::CreateContext() {
     context_ = new Context;
-    CHECK_STATUS(context_->Init(opt_device_));
+    CHECK_STATUS(context_->Init(opt_.device));
     SI_TRY_HIP(si_hip_event_create(&ev_start_), "event create");
     SI_TRY_HIP(si_hip_event_create(&ev_stop_), "event create");
     return Status::kSuccess;
@@ -216,7 +180,7 @@ Status EngineImpl::CreateTensorNodes() {
     // the graph input.  (An operator that combines images -- a softmax over dimension 0 -- is then that operator over N images,
     // which is what the model means at batch N; it is cutting ONE batch into pieces that such an operator forbids, batch_rule.h.)
     int file_batch = 0;
-    if (opt_batch_ > 0) {
+    if (opt_.batch > 0) {
         // a box head: the graph inputs [N, ...] and [K, 5] disagree in dimension 0, and where K == N by coincidence the rewrite below would
         // change the number of boxes with the number of images.  Neither is re-batched
         for (const pnnx::Operator* op : graph_->ops)
@@ -272,8 +236,8 @@ Status EngineImpl::CreateTensorNodes() {
         // file shapes are NCHW; tensors are NHWC: the last three dims C,H,W -> H,W,C for rank >= 4
         std::vector<int> file = opd->shape;
         auto moved = batch_axis.find(opd);
-        if (moved != batch_axis.end() && moved->second >= 1) file[moved->second] = opt_batch_;
-        else if (file_batch > 0 && !file.empty() && file[0] == file_batch) file[0] = opt_batch_;
+        if (moved != batch_axis.end() && moved->second >= 1) file[moved->second] = opt_.batch;
+        else if (file_batch > 0 && !file.empty() && file[0] == file_batch) file[0] = opt_.batch;
         std::vector<int> shape = file;
         const int rank = (int)shape.size();
         if (rank > 3) {
@@ -290,7 +254,7 @@ Status EngineImpl::CreateTensorNodes() {
             if (c && c->outputs.empty()) is_output = true;
         // fp16 storage: every internal fp32 activation becomes fp16; the tensors the caller hands over / reads back
         // (Input / Extract) keep the file's type
-        if (opt_fp16_ && dt == DataType::kFloat32 && !is_input && !is_output) dt = DataType::kFloat16;
+        if (opt_.fp16 && dt == DataType::kFloat32 && !is_input && !is_output) dt = DataType::kFloat16;
         node->tensor = Tensor(dt, shape, MemoryType::kDevice, false);
         tensor_nodes_[opd->name] = node;
         if (is_input) input_tensor_nodes_[opd->name] = node;
@@ -338,8 +302,8 @@ Status EngineImpl::CreateLayers() {
         // kernels can write; 1024 words: more convs than that simply run unguarded-by-flag on the fp32 kernels)
         auto arm_split = [&](Conv2d& cv, bool on) {
             cv.f32_split_ = on;
-            cv.f32_split_level_ = opt_f32_split_policy_;
-            if (opt_plan_set_) cv.SetPlan(opt_plan_);
+            cv.f32_split_level_ = opt_.f32_split_policy;
+            if (opt_.plan_set) cv.SetPlan(opt_.plan);
             if (!on) return;
             if (!split_flags_) {
                 void* p = nullptr;
@@ -352,13 +316,13 @@ Status EngineImpl::CreateLayers() {
             split_convs_.push_back(&cv);
         };
         if (YoloDetect* yd = dynamic_cast<YoloDetect*>(layer)) {
-            yd->fuse_decode_ = opt_fuse_;
-            for (Conv2d& cv : yd->conv_2d_layer_) arm_split(cv, opt_f32_split_ && !opt_fp16_ && opt_fuse_);
+            yd->fuse_decode_ = opt_.fuse;
+            for (Conv2d& cv : yd->conv_2d_layer_) arm_split(cv, opt_.f32_split && !opt_.fp16 && opt_.fuse);
         }
         if (Conv2d* cv = dynamic_cast<Conv2d*>(layer)) {
-            if (!opt_winograd_) cv->algo_ = Conv2d::Algo::kImplicitGemm;
-            cv->prefer_wino43_ = opt_winograd_ == 2;
-            arm_split(*cv, opt_f32_split_ && !opt_fp16_);
+            if (!opt_.winograd) cv->algo_ = Conv2d::Algo::kImplicitGemm;
+            cv->prefer_wino43_ = opt_.winograd == 2;
+            arm_split(*cv, opt_.f32_split && !opt_.fp16);
         }
 
         std::vector<TensorNode*> ins, outs;
@@ -449,7 +413,7 @@ Status EngineImpl::AllocateTensorMemory() {
             return Status::kErrorShape;
         }
         const bool io = input_tensor_nodes_.count(name) || output_tensor_nodes_.count(name);
-        if (io || !opt_arena_) {
+        if (io || !opt_.arena) {
             void* p = nullptr;
             SI_TRY_HIP(si_hip_malloc(&p, bytes), "hipMalloc operand");
             device_allocs_.push_back(p);
@@ -466,10 +430,10 @@ Status EngineImpl::AllocateTensorMemory() {
     // An engine whose forwards may all be served by the sliced host pipeline (host outputs, slicing not switched off, not a lane)
     // leaves the arena to the first forward that runs its OWN plan: the slicer has an arena of its own, and this one would be a
     // second, never-touched allocation.  Everyone else allocates now, so LoadModel reports an arena that does not fit.
-    const bool defer = arena_pending_ && !is_lane_ && opt_outputs_to_host_ && opt_host_slices_ != 1 && lanes_.empty();
+    const bool defer = arena_pending_ && !is_lane_ && opt_.outputs_to_host && opt_.host_slices != 1 && lanes_.empty();
     if (!defer) CHECK_STATUS(EnsureArena());
     // 3. pinned host mirrors for outputs
-    if (opt_outputs_to_host_) {
+    if (opt_.outputs_to_host) {
         for (auto& kv : output_tensor_nodes_) {
             void* h = nullptr;
             SI_TRY_HIP(si_hip_host_alloc(&h, kv.second->tensor.ByteSize()), "hipHostMalloc output");
@@ -515,327 +479,6 @@ Status EngineImpl::DeallocateTensorMemory() {
     for (auto& kv : host_outputs_) si_hip_host_free(kv.second);
     host_outputs_.clear();
     for (auto& kv : tensor_nodes_) kv.second->tensor.SetView(nullptr, MemoryType::kDevice, 0);
-    return Status::kSuccess;
-}
-
-
-// ---- lanes (option "streams") ---------------------------------------------------------------------
-// Two half-batch engines on two streams instead of one full-batch engine on one: while one lane is in a layer's tail (the last,
-// partial round of workgroups, the epilogue stores) the other lane's workgroups fill the idle CUs.  Measured on MI355X,
-// YOLOv5s batch 32, same box, hipGraph replay: +4.9 % (tools/two_stream_exp.py).  A lane is this model
-// re-batched to N / 2 (the "batch" option's rule) that reads and writes slab views of this engine's input and output buffers.
-// That is the same computation only for a graph whose every operator is per-image (batch_rule.h; the reference's operators all
-// are, SURVEY.md 8e, a softmax or a mean over the batch, a slice along it or a view that folds it is not): then the results are
-// bit-identical to the one-stream schedule because no kernel's per-element arithmetic depends on the batch
-// (tests/test_gpu_tiles.py, tests/test_gpu_engine.py, tests/test_gpu_batch_split.py).  Any other graph is refused.
-// Can the batch be cut into contiguous slabs?  Every graph input and output must be batch-major (dimension 0 = the batch, rank >= 2) ...
-bool EngineImpl::BatchMajorIO(int& batch) const {
-    batch = 0;
-    bool ok = !input_tensor_nodes_.empty() && !output_tensor_nodes_.empty();
-    for (auto& kv : input_tensor_nodes_) {
-        const std::vector<int>& sh = kv.second->tensor.Shape();
-        if (sh.size() < 2 || (batch != 0 && sh[0] != batch)) ok = false;
-        else batch = sh[0];
-    }
-    for (auto& kv : output_tensor_nodes_) {
-        const std::vector<int>& sh = kv.second->tensor.Shape();
-        if (sh.size() < 2 || sh[0] != batch) ok = false;
-    }
-    return ok && batch >= 2;
-}
-
-// ... and every operator of the graph must be per-image by the rule of batch_rule.h
-bool EngineImpl::BatchSplittable(int& batch) const { return BatchMajorIO(batch) && batch_mixing_.empty(); }
-
-std::string EngineImpl::BatchMixingText() const {
-    std::string s;
-    for (const BatchMixingEntry& m : batch_mixing_) s += (s.empty() ? "[" : "; [") + m.layer + "] (" + m.type + "): " + m.reason;
-    return s;
-}
-
-Status EngineImpl::PlanLanes(int& lanes) {
-    lanes = 1;
-    if (is_lane_ || opt_streams_ < 2) return Status::kSuccess;
-    int batch = 0;
-    const bool ok = BatchSplittable(batch) && batch % 2 == 0;
-    if (opt_streams_ >= 2) {
-        if (!batch_mixing_.empty()) {
-            LOG(ERROR) << "streams=2 runs two half-batch copies of the model, which needs per-image operators; not per-image: " << BatchMixingText();
-            return Status::kUnsupport;
-        }
-        if (!ok) {
-            LOG(ERROR) << "streams=2 needs an even batch that is dimension 0 of every graph input and output";
-            return Status::kUnsupport;
-        }
-        lanes = 2;
-    }
-    return Status::kSuccess;
-}
-
-Status EngineImpl::LoadLanes(int lanes) {
-    int batch = input_tensor_nodes_.begin()->second->tensor.Shape()[0];
-    for (int l = 0; l < lanes; ++l) {
-        EngineImpl* lane = new EngineImpl;
-        lanes_.push_back(lane);
-        lane->is_lane_ = true;
-        lane->opt_device_ = context_->device();
-        lane->opt_fuse_ = opt_fuse_;
-        lane->opt_alias_cat_ = opt_alias_cat_;
-        lane->opt_alias_split_ = opt_alias_split_;
-        lane->opt_fuse_layout_ = opt_fuse_layout_;
-        lane->opt_fuse_grid_ = opt_fuse_grid_;
-        lane->opt_alias_view_ = opt_alias_view_;
-        lane->opt_fuse_upsample_ = opt_fuse_upsample_;
-        lane->opt_fuse_stem_ = opt_fuse_stem_;
-        lane->opt_fuse_pw_ = opt_fuse_pw_;
-        lane->opt_arena_ = opt_arena_;
-        lane->opt_winograd_ = opt_winograd_;
-        lane->opt_f32_split_ = opt_f32_split_;
-        lane->opt_f32_split_policy_ = opt_f32_split_policy_;
-        lane->opt_plan_ = opt_plan_;
-        lane->opt_plan_set_ = opt_plan_set_;
-        lane->opt_detect_stream_ = opt_detect_stream_;
-        lane->opt_detect_priority_ = opt_detect_priority_;
-        lane->opt_fp16_ = opt_fp16_;
-        lane->opt_graph_ = opt_graph_;        // every lane replays its OWN captured graph on its own stream; this engine only forks / joins
-                                              // (one graph holding both branches measured 10 % SLOWER than one stream: profiles/r03_ab_streams.txt)
-        lane->opt_outputs_to_host_ = false;   // ... and owns the host mirrors
-        lane->opt_streams_ = 1;
-        lane->opt_batch_ = batch / lanes;
-        CHECK_STATUS(lane->LoadModel(param_path_, bin_path_));
-        si_event_t ev = nullptr;
-        SI_TRY_HIP(si_hip_event_create(&ev), "event create");
-        lane_done_.push_back(ev);
-    }
-    if (!ev_fork_) SI_TRY_HIP(si_hip_event_create(&ev_fork_), "event create");
-    LOG(INFO) << "streams: " << lanes << " lanes of batch " << batch / lanes;
-    return Status::kSuccess;
-}
-
-Status EngineImpl::DestroyLanes() {
-    for (EngineImpl* lane : lanes_) delete lane;
-    lanes_.clear();
-    for (si_event_t ev : lane_done_) si_hip_event_destroy(ev);
-    lane_done_.clear();
-    return Status::kSuccess;
-}
-
-namespace {
-// lane `l` of `n`: the contiguous slab of images [l * N / n, (l + 1) * N / n) of a batch-major tensor, as a non-owning view
-Tensor SlabView(const Tensor& t, int l, int n) {
-    std::vector<int> shape = t.Shape();
-    const size_t rows = t.NumElements() / (size_t)shape.back();   // pixels (rank 4) / rows of the last dimension
-    const size_t slab_bytes = rows / (size_t)n * (size_t)t.PixelStride() * ElementSize(t.GetDataType());
-    shape[0] /= n;
-    Tensor v(t.GetDataType(), shape, MemoryType::kDevice, false);
-    v.SetView(static_cast<char*>(t.RawData()) + (size_t)l * slab_bytes, MemoryType::kDevice, t.PixelStride() == t.Shape().back() ? 0 : t.PixelStride());
-    return v;
-}
-}  // namespace
-
-// hand every lane its slab of the (already resolved) input and output tensors of this engine
-Status EngineImpl::BindLanes() {
-    const int n = (int)lanes_.size();
-    for (int l = 0; l < n; ++l) {
-        for (auto& kv : input_tensor_nodes_) CHECK_STATUS(lanes_[l]->Input(kv.first, SlabView(kv.second->tensor, l, n)));
-        for (auto& kv : output_tensor_nodes_) CHECK_STATUS(lanes_[l]->Output(kv.first, SlabView(kv.second->tensor, l, n)));
-    }
-    return Status::kSuccess;
-}
-
-// fork: every lane's stream waits for this engine's stream (the input upload); join: this stream waits for every lane.  With
-// option "graph" every lane replays its own captured graph between the two.
-Status EngineImpl::LaunchLanes() {
-    si_stream_t stream = context_->stream();
-    SI_TRY_HIP(si_hip_event_record(ev_fork_, stream), "event record");
-    for (size_t l = 0; l < lanes_.size(); ++l) {
-        SI_TRY_HIP(si_hip_stream_wait_event(lanes_[l]->context_->stream(), ev_fork_), "stream wait");
-        CHECK_STATUS(lanes_[l]->ForwardAsync());
-        lanes_[l]->forward_pending_ = false;   // (the lane's own start / stop events may sit inside a capture: never read)
-        SI_TRY_HIP(si_hip_event_record(lane_done_[l], lanes_[l]->context_->stream()), "event record");
-    }
-    for (size_t l = 0; l < lanes_.size(); ++l) SI_TRY_HIP(si_hip_stream_wait_event(stream, lane_done_[l]), "stream wait");
-    return Status::kSuccess;
-}
-
-// ---- the reference's host-tensor contract at speed (option "host_slices") -------------------------------------------------
-// Engine::Input borrows a HOST tensor that is read at Forward() time and Extract hands back host-visible memory (reference
-// src/engine_impl.cpp:522-555, bench/bench_yolo.cpp:20-28).  Done naively that is upload -> compute -> download in series:
-// YOLOv5s batch 32 moves 157 MB up and 274 MB down around 4.3 ms of kernels, 12.8 ms per Forward.  Here one synchronous
-// Forward() is a three-stage pipeline over G contiguous batch slices: slice g's images go up on an upload stream while slice
-// g-1 computes (ONE child engine of batch N / G runs the slices back to back on its own stream: same weights, same arena) and
-// slice g-2's output rows come down on a download stream into the pinned mirror Extract() returns.  What is left outside the
-// overlap is the first slice's upload and the last slice's download.  A borrowed input buffer that is handed over for a second
-// Forward is pinned in place (hipHostRegister) so its uploads run asynchronously at the link rate.  Bit-identical to the
-// unsliced schedule for a graph of per-image operators (tests/test_gpu_engine.py::test_host_tensor_pipeline_*,
-// tests/test_gpu_batch_split.py).  A graph that holds an operator which combines images (batch_rule.h; a layer type registered at
-// run time counts as one) is served unsliced: slices of it would compute something else.  Under auto that is said once at INFO,
-// under an explicit host_slices > 1 once as an ERROR, each with the layer and the reason.
-int EngineImpl::PlanSlices() const {
-    if (is_lane_ || opt_host_slices_ == 1 || !opt_outputs_to_host_ || slicer_failed_) return 1;
-    if (!lanes_.empty()) return 1;   // "streams" = 2 was asked for: the lanes serve the engine
-    int batch = 0;
-    if (!BatchMajorIO(batch)) return 1;
-    for (auto& kv : input_tensor_nodes_) {
-        auto u = user_inputs_.find(kv.first);
-        if (u == user_inputs_.end() || u->second.RawData() == nullptr || u->second.GetMemoryType() == MemoryType::kDevice) return 1;
-    }
-    if (!user_outputs_.empty()) return 1;   // caller-owned device outputs: not the host contract
-    const int slices = SlicesFor(batch);
-    if (slices > 1 && !batch_mixing_.empty()) {
-        if (!mixing_logged_) {
-            if (opt_host_slices_ > 1)
-                LOG(ERROR) << "host_slices=" << opt_host_slices_ << " needs per-image operators; serving this engine unsliced.  Not per-image: " << BatchMixingText();
-            else
-                LOG(INFO) << "host_slices: serving this engine unsliced.  Not per-image: " << BatchMixingText();
-            mixing_logged_ = true;
-        }
-        return 1;
-    }
-    return slices;
-}
-
-// the number of slices a batch-major graph of per-image operators is served with
-int EngineImpl::SlicesFor(int batch) const {
-    if (opt_host_slices_ > 1) return batch % opt_host_slices_ == 0 ? opt_host_slices_ : 1;
-    // auto (MI355X, YOLOv5s 640x640, profiles/r03_host_slices.txt): slices of 8 images from batch 32 on (a batch-8 forward is still
-    // at 0.6 of the MFMA ceiling, and 8 images are 39 MB up / 69 MB down -- 0.7 / 1.3 ms of PCIe outside the overlap), slices of 4
-    // for batches 8 .. 31 (batch 8: 3.49 -> 2.95 ms per Forward with 2 slices; batch 16: 6.61 -> 4.95 with 4); at most 8 slices
-    // (one captured graph per slice under "graph")
-    const int per = batch >= 32 ? 8 : 4;
-    if (batch < 8 || batch % per != 0) return 1;
-    int g = batch / per;
-    while (g > 8 && g % 2 == 0) g /= 2;
-    return g <= 8 ? g : 1;
-}
-
-Status EngineImpl::DestroySlicer() {
-    delete slicer_;
-    slicer_ = nullptr;
-    slices_ = 0;
-    for (si_event_t e : ev_up_) si_hip_event_destroy(e);
-    for (si_event_t e : ev_done_) si_hip_event_destroy(e);
-    ev_up_.clear();
-    ev_done_.clear();
-    if (ev_down_all_) si_hip_event_destroy(ev_down_all_);
-    ev_down_all_ = nullptr;
-    delete up_context_;
-    delete down_context_;
-    up_context_ = down_context_ = nullptr;
-    return Status::kSuccess;
-}
-
-void EngineImpl::UnpinInputs() {
-    for (auto& kv : pinned_inputs_)
-        if (kv.second.registered) si_hip_host_unregister(const_cast<void*>(kv.second.ptr));
-    pinned_inputs_.clear();
-}
-
-// everything the sliced pipeline needs; slices_ is set LAST, so a failure half way leaves nothing that looks usable
-Status EngineImpl::SetupSlicer(int slices) {
-    CHECK_STATUS(DestroySlicer());
-    int batch = 0;
-    CHECK_BOOL(BatchSplittable(batch) && batch % slices == 0);
-    slicer_ = new EngineImpl;
-    slicer_->is_lane_ = true;
-    slicer_->opt_device_ = context_->device();
-    slicer_->opt_fuse_ = opt_fuse_;
-    slicer_->opt_alias_cat_ = opt_alias_cat_;
-    slicer_->opt_alias_split_ = opt_alias_split_;
-    slicer_->opt_fuse_layout_ = opt_fuse_layout_;
-    slicer_->opt_fuse_grid_ = opt_fuse_grid_;
-    slicer_->opt_alias_view_ = opt_alias_view_;
-    slicer_->opt_fuse_upsample_ = opt_fuse_upsample_;
-    slicer_->opt_fuse_stem_ = opt_fuse_stem_;
-    slicer_->opt_fuse_pw_ = opt_fuse_pw_;
-    slicer_->opt_arena_ = opt_arena_;
-    slicer_->opt_winograd_ = opt_winograd_;
-    slicer_->opt_f32_split_ = opt_f32_split_;
-    slicer_->opt_f32_split_policy_ = opt_f32_split_policy_;
-    slicer_->opt_plan_ = opt_plan_;
-    slicer_->opt_plan_set_ = opt_plan_set_;
-    slicer_->opt_detect_stream_ = opt_detect_stream_;
-    slicer_->opt_detect_priority_ = opt_detect_priority_;
-    slicer_->opt_fp16_ = opt_fp16_;
-    slicer_->opt_graph_ = opt_graph_;          // one captured graph per slice (its I/O pointers key the cache) ...
-    slicer_->max_graphs_ = std::max<size_t>(max_graphs_, (size_t)slices);   // ... so the cache holds at least one per slice
-    slicer_->opt_outputs_to_host_ = false;
-    slicer_->opt_streams_ = 1;
-    slicer_->opt_batch_ = batch / slices;
-    CHECK_STATUS(slicer_->LoadModel(param_path_, bin_path_));
-    up_context_ = new Context;
-    CHECK_STATUS(up_context_->Init(context_->device()));
-    if (debug_fail_slicer_) return Status::kFail;
-    down_context_ = new Context;
-    CHECK_STATUS(down_context_->Init(context_->device()));
-    ev_up_.assign((size_t)slices, nullptr);
-    ev_done_.assign((size_t)slices, nullptr);
-    for (auto& e : ev_up_) SI_TRY_HIP(si_hip_event_create(&e), "event create");
-    for (auto& e : ev_done_) SI_TRY_HIP(si_hip_event_create(&e), "event create");
-    SI_TRY_HIP(si_hip_event_create(&ev_down_all_), "event create");
-    if (!ev_fork_) SI_TRY_HIP(si_hip_event_create(&ev_fork_), "event create");
-    slices_ = slices;
-    LOG(INFO) << "host_slices: " << slices << " pipelined slices of batch " << batch / slices;
-    return Status::kSuccess;
-}
-
-Status EngineImpl::ForwardSliced(int slices) {
-    si_stream_t stream = context_->stream();
-    CHECK_BOOL(slicer_ != nullptr && slices_ == slices);
-    last_slices_ = slices;
-    // the engine's device-side input staging and its own output buffers, whole batch; the slices are views
-    for (auto& kv : input_tensor_nodes_) kv.second->tensor.SetView(input_buffers_[kv.first], MemoryType::kDevice, 0);
-    CHECK_STATUS(BindOutputs());
-    // a borrowed input seen for the second Forward in a row is pinned in place; a different pointer drops the old pin
-    for (auto& kv : input_tensor_nodes_) {
-        const Tensor& host = user_inputs_[kv.first];
-        Pinned& p = pinned_inputs_[kv.first];
-        if (p.ptr != host.RawData() || p.bytes != host.ByteSize()) {
-            if (p.registered) si_hip_host_unregister(const_cast<void*>(p.ptr));
-            p = Pinned();
-            p.ptr = host.RawData();
-            p.bytes = host.ByteSize();
-        }
-        // (opt-in, "pin_inputs": a registration outlives this call, so the caller has to keep the buffer mapped until the next
-        // Input() / Release -- freeing it after Forward(), which the reference's borrow allows, would leave a stale registration)
-        if (opt_pin_inputs_ && ++p.seen == 2 && !p.registered) {
-            p.registered = si_hip_host_register(const_cast<void*>(p.ptr), p.bytes) == 0;   // (failure: the uploads stay staged copies)
-            if (!p.registered) LOG(INFO) << "host_slices: could not pin the input buffer of [" << kv.first << "]; uploads stay staged";
-        }
-    }
-    SI_TRY_HIP(si_hip_event_record(ev_start_, stream), "event record");
-    // the upload stream starts behind whatever this engine's stream still holds (a previous ForwardAsync)
-    SI_TRY_HIP(si_hip_event_record(ev_fork_, stream), "event record");
-    SI_TRY_HIP(si_hip_stream_wait_event(up_context_->stream(), ev_fork_), "stream wait");
-    SI_TRY_HIP(si_hip_stream_wait_event(slicer_->context_->stream(), ev_fork_), "stream wait");
-    SI_TRY_HIP(si_hip_stream_wait_event(down_context_->stream(), ev_fork_), "stream wait");
-    for (int g = 0; g < slices; ++g) {
-        for (auto& kv : input_tensor_nodes_) {
-            const Tensor dst = SlabView(kv.second->tensor, g, slices);
-            const size_t bytes = dst.ByteSize();
-            const char* src = static_cast<const char*>(user_inputs_[kv.first].RawData()) + (size_t)g * bytes;
-            SI_TRY_HIP(si_hip_memcpy_h2d(dst.RawData(), src, bytes, up_context_->stream()), "input slice h2d");
-            CHECK_STATUS(slicer_->Input(kv.first, dst));
-        }
-        SI_TRY_HIP(si_hip_event_record(ev_up_[(size_t)g], up_context_->stream()), "event record");
-        SI_TRY_HIP(si_hip_stream_wait_event(slicer_->context_->stream(), ev_up_[(size_t)g]), "stream wait");
-        for (auto& kv : output_tensor_nodes_) CHECK_STATUS(slicer_->Output(kv.first, SlabView(kv.second->tensor, g, slices)));
-        CHECK_STATUS(slicer_->ForwardAsync());
-        slicer_->forward_pending_ = false;
-        SI_TRY_HIP(si_hip_event_record(ev_done_[(size_t)g], slicer_->context_->stream()), "event record");
-        SI_TRY_HIP(si_hip_stream_wait_event(down_context_->stream(), ev_done_[(size_t)g]), "stream wait");
-        for (auto& kv : output_tensor_nodes_) {
-            const Tensor src = SlabView(kv.second->tensor, g, slices);
-            const size_t bytes = src.ByteSize();
-            SI_TRY_HIP(si_hip_memcpy_d2h(static_cast<char*>(host_outputs_[kv.first]) + (size_t)g * bytes, src.RawData(), bytes,
-                                         down_context_->stream()), "output slice d2h");
-        }
-    }
-    SI_TRY_HIP(si_hip_event_record(ev_down_all_, down_context_->stream()), "event record");
-    SI_TRY_HIP(si_hip_stream_wait_event(stream, ev_down_all_), "stream wait");   // Sync() on this engine's stream covers the pipeline
-    SI_TRY_HIP(si_hip_event_record(ev_stop_, stream), "event record");
-    forward_pending_ = true;
-    ++forward_count_;
     return Status::kSuccess;
 }
 
@@ -1055,7 +698,7 @@ Status EngineImpl::ForwardAsync() {
     if (!lanes_.empty()) CHECK_STATUS(BindLanes());
 
     SI_TRY_HIP(si_hip_event_record(ev_start_, stream), "event record");
-    if (opt_graph_ && plan_warm_ && lanes_.empty()) {
+    if (opt_.graph && plan_warm_ && lanes_.empty()) {
         // a captured graph bakes pointers in: key the cache on where the device-resident inputs and the outputs are now
         std::vector<void*> key;
         for (auto& kv : input_tensor_nodes_) key.push_back(kv.second->tensor.RawData());
@@ -1078,16 +721,7 @@ Status EngineImpl::ForwardAsync() {
                 if (exec) si_hip_graph_destroy(exec);
                 LOG(WARNING) << "graph: the capture of this step failed; running it eagerly";
                 CHECK_STATUS(LaunchAll());
-                SI_TRY_HIP(si_hip_event_record(ev_stop_, stream), "event record");
-                if (opt_outputs_to_host_) {
-                    for (auto& kv : output_tensor_nodes_) {
-                        const Tensor& t = kv.second->tensor;
-                        SI_TRY_HIP(si_hip_memcpy_d2h(host_outputs_[kv.first], t.RawData(), t.ByteSize(), stream), "output d2h");
-                    }
-                }
-                forward_pending_ = true;
-                ++forward_count_;
-                return Status::kSuccess;
+                return EndForward();
             }
             if (graph_cache_.size() >= max_graphs_) {
                 // the evicted exec may be the one a not-yet-synchronised ForwardAsync() launched: let the stream drain first
@@ -1104,9 +738,14 @@ Status EngineImpl::ForwardAsync() {
         CHECK_STATUS(LaunchAll());
         plan_warm_ = true;
     }
-    SI_TRY_HIP(si_hip_event_record(ev_stop_, stream), "event record");
+    return EndForward();
+}
 
-    if (opt_outputs_to_host_) {
+// the end of every ForwardAsync that ran this engine's own plan: the stop event, the outputs on their way to the host mirrors, the step counted
+Status EngineImpl::EndForward() {
+    si_stream_t stream = context_->stream();
+    SI_TRY_HIP(si_hip_event_record(ev_stop_, stream), "event record");
+    if (opt_.outputs_to_host) {
         for (auto& kv : output_tensor_nodes_) {
             const Tensor& t = kv.second->tensor;
             SI_TRY_HIP(si_hip_memcpy_d2h(host_outputs_[kv.first], t.RawData(), t.ByteSize(), stream), "output d2h");
@@ -1124,7 +763,7 @@ Status EngineImpl::Extract(const std::string& name, Tensor& output) {
         return Status::kFail;
     }
     const Tensor& t = it->second->tensor;
-    if (opt_outputs_to_host_) {
+    if (opt_.outputs_to_host) {
         output = Tensor(t.GetDataType(), t.Shape(), MemoryType::kHost, false);
         output.SetData(host_outputs_[name], MemoryType::kHost);
     } else {

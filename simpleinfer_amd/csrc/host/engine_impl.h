@@ -20,6 +20,7 @@
 #include "batch_rule.h"
 #include "context.h"
 #include "engine.h"
+#include "engine_options.h"
 #include "layer.h"
 #include "pnnx/pnnx_helper.h"
 #include "tensor.h"
@@ -123,10 +124,12 @@ private:
     Status UploadInputs();
     Status BindOutputs();
     Status LaunchAll();
+    Status EndForward();   // ForwardAsync's tail: stop event, outputs to host, the step counted
 
     // option "streams" = 2: the batch runs as two half-batch LANES on two streams (see LoadLanes)
     Status PlanLanes(int& lanes);
     Status LoadLanes(int lanes);
+    Status NewChild(int batch, size_t min_graphs, EngineImpl*& child);   // a lane / the slicer's engine: this model under opt_.ForChild
     Status BindLanes();
     Status LaunchLanes();
     Status DestroyLanes();
@@ -146,36 +149,7 @@ private:
     void UnpinInputs();
 
 private:
-    // options
-    int opt_device_ = -1;
-    bool opt_fuse_ = true;
-    bool opt_alias_cat_ = true;
-    bool opt_alias_split_ = true;   // torch.chunk / torch.split / Tensor.slice outputs that are channel ranges become views of the input (0: always copied)
-    bool opt_fuse_grid_ = true;     // F.grid_sample reads a permuted grid in place and an affine grid from theta (0: the grid is written first; A/B runs)
-    bool opt_fuse_layout_ = true;  // a run of permute / reshape / view / transpose / squeeze / unsqueeze operators is planned as ONE layout step (0: one step each)
-    bool opt_alias_view_ = true;    // a layout step that moves no byte makes its output a view of its input's buffer (0: one permute_rows copy)
-    bool opt_fuse_upsample_ = true;
-    int opt_fuse_stem_ = 2;
-    int opt_fuse_pw_ = 1;   // (2: ... and the C3's closing conv behind its last 64-channel pair -- built in round 6, bit-identical, 0.74-0.84x of the launches
-                            // it replaces: the fused workgroup is bound by its three SiLU epilogues on two waves per SIMD; opt-in, LAB_NOTEBOOK R6.4)
-    bool opt_f32_split_ = false;
-    int opt_f32_split_policy_ = 4;
-    SiConvPlan opt_plan_ = SI_CONV_PLAN_DEFAULT;   // kernel-form choices handed to every conv launch (options f32_tile, f16_slab, ...; all default: the policy)
-    bool opt_plan_set_ = false;
-    bool opt_arena_ = true;      // intermediate operands share one HBM arena by lifetime (0: one allocation per operand, as the reference)
-    bool opt_graph_ = false;
-    bool opt_outputs_to_host_ = true;
-    int opt_winograd_ = 1;
-    int opt_batch_ = 0;          // > 0: serve this batch whatever batch the file was traced with
-    int opt_detect_stream_ = 1;        // Detect's early levels on a second stream beside the layers that follow their inputs: 0 never, 1 for levels with enough work, 2 always
-    int opt_detect_priority_ = 0;   // si_hip_stream_create_priority level of that stream (engine option detect_priority): the device default.  -1 (lowest: the
-                                    // neck on the main stream is the critical path, Detect fills what it leaves) measured +0.7 % fp16 / flat fp32 on ONE engine
-                                    // (r05_ab_detect_priority.txt) -- inside the box-to-box spread, and with several engines on a device a lowest-priority
-                                    // stream can be starved by the others' default-priority work: opt-in since round 6
-    bool opt_fp16_ = false;      // fp16 storage for internal activations and weights (BASELINE.json configs[3])
-    int opt_streams_ = 1;        // 2: two half-batch lanes on two streams; 1 (default): one stream
-    int opt_host_slices_ = 0;    // host inputs + host outputs: G batch slices pipelined over PCIe inside one Forward(); 1: off; 0 (default): auto
-    bool opt_pin_inputs_ = false; // the sliced pipeline may hipHostRegister a borrowed input buffer in place (opt-in: the caller keeps it mapped until the next Input() / Release)
+    EngineOptions opt_;   // every option of SetOption (engine_options.h)
 
     Context* context_ = nullptr;
     Context* side_context_ = nullptr;        // second stream (option "detect_stream"); created with the first plan that uses it
@@ -201,7 +175,6 @@ private:
     // download stream beside it
     EngineImpl* slicer_ = nullptr;
     int slices_ = 0;                         // set only once every resource of the pipeline exists
-    bool debug_fail_slicer_ = false;         // option "_fail_slicer" (tests)
     bool slicer_failed_ = false;             // setting the pipeline up failed once: serve unsliced from then on
     std::vector<BatchMixingEntry> batch_mixing_;   // operators that combine images, with the reason (a lane / the slicer's engine: not looked for)
     mutable bool mixing_logged_ = false;     // ... and that they keep host_slices off has been said

@@ -1,4 +1,4 @@
-// engine_internal.h -- shared by the translation units of EngineImpl (engine_impl.cpp, engine_plan.cpp) and by nothing else.
+// engine_internal.h -- shared by the translation units of EngineImpl (engine_impl.cpp, engine_plan.cpp, engine_split.cpp) and by nothing else.
 #ifndef SIMPLE_INFER_SRC_ENGINE_INTERNAL_H_
 #define SIMPLE_INFER_SRC_ENGINE_INTERNAL_H_
 

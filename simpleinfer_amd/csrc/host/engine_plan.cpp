@@ -76,23 +76,23 @@ Status EngineImpl::CreatePipeline() {
         }
     }
 
-    if (opt_fuse_) {
+    if (opt_.fuse) {
         CHECK_STATUS(FuseEpilogues(order));
         CHECK_STATUS(FuseSiblingConvs(order));
         CHECK_STATUS(FusePoolChains(order));
-        if (opt_fuse_layout_) CHECK_STATUS(FuseLayoutChains(order));
-        if (opt_fuse_layout_ && opt_fuse_grid_) CHECK_STATUS(FuseGridInPlace(order));   // (after the chains are composed: the run in front of a sampler is one step)
-        if (opt_fuse_grid_) CHECK_STATUS(FuseAffineGrids(order));
-        if (opt_fuse_upsample_ && opt_alias_cat_) CHECK_STATUS(FuseUpsampleIntoConvs(order));   // (fp16 storage too since round 4)
-        if (opt_fp16_ && opt_fuse_stem_) CHECK_STATUS(FuseStemPairs(order));
-        if (opt_fp16_ && opt_fuse_stem_ > 1) CHECK_STATUS(FuseStemTriples(order));
-        if (opt_fp16_ && opt_fuse_pw_) CHECK_STATUS(FuseBottleneckPairs(order));
-        if (opt_fp16_ && opt_fuse_pw_ > 1 && opt_alias_cat_) CHECK_STATUS(FuseCv3IntoPairs(order));
+        if (opt_.fuse_layout) CHECK_STATUS(FuseLayoutChains(order));
+        if (opt_.fuse_layout && opt_.fuse_grid) CHECK_STATUS(FuseGridInPlace(order));   // (after the chains are composed: the run in front of a sampler is one step)
+        if (opt_.fuse_grid) CHECK_STATUS(FuseAffineGrids(order));
+        if (opt_.fuse_upsample && opt_.alias_cat) CHECK_STATUS(FuseUpsampleIntoConvs(order));   // (fp16 storage too since round 4)
+        if (opt_.fp16 && opt_.fuse_stem) CHECK_STATUS(FuseStemPairs(order));
+        if (opt_.fp16 && opt_.fuse_stem > 1) CHECK_STATUS(FuseStemTriples(order));
+        if (opt_.fp16 && opt_.fuse_pw) CHECK_STATUS(FuseBottleneckPairs(order));
+        if (opt_.fp16 && opt_.fuse_pw > 1 && opt_.alias_cat) CHECK_STATUS(FuseCv3IntoPairs(order));
     }
     // what a layout operator could not decide on its own (a tensor of rank > 4 that exists only inside a fused chain) is decided now
     for (const Step& st : order)
         if (Layout* lay = dynamic_cast<Layout*>(st.layer)) CHECK_STATUS(lay->Final());
-    if (opt_fp16_) {
+    if (opt_.fp16) {
         CHECK_STATUS(InsertOutputCasts(order));
         // every layer is asked NOW whether it has a kernel for the storage types it ended up with.  One that has none (a 3x3 conv
         // whose channel count is not a multiple of 32, UnaryOp ...) runs its fp32 kernel between two casts (round 4); only what
@@ -100,11 +100,11 @@ Status EngineImpl::CreatePipeline() {
         CHECK_STATUS(InsertFp32Fallbacks(order));
     }
     plan_ = order;
-    if (opt_alias_split_) CHECK_STATUS(AliasSplits());   // (first: a chunk that is a view stays one when its halves also feed a concat)
-    if (opt_alias_view_) CHECK_STATUS(AliasViews());
-    if (opt_alias_cat_) CHECK_STATUS(AliasConcats());
+    if (opt_.alias_split) CHECK_STATUS(AliasSplits());   // (first: a chunk that is a view stays one when its halves also feed a concat)
+    if (opt_.alias_view) CHECK_STATUS(AliasViews());
+    if (opt_.alias_cat) CHECK_STATUS(AliasConcats());
     ResolveAliases();
-    if (opt_detect_stream_) CHECK_STATUS(PlanDetectStream());
+    if (opt_.detect_stream) CHECK_STATUS(PlanDetectStream());
     return Status::kSuccess;
 }
 
@@ -135,12 +135,12 @@ Status EngineImpl::PlanDetectStream() {
             // Worth a fork / join only for a level with real work (MI355X, YOLOv5s same-box A/B: batch 32 +1.3 %, batch 8 +-0,
             // batch 1 -3 %: two more graph edges against launches of a few microseconds)
             const double level_flops = 2.0 * (double)n->tensor.NumElements() * det->num_elements_;
-            if (producer[k] >= 0 && producer[k] + 1 < (int)di && (level_flops >= 4e9 || opt_detect_stream_ >= 2)) mask |= 1u << k;   // something runs in between
+            if (producer[k] >= 0 && producer[k] + 1 < (int)di && (level_flops >= 4e9 || opt_.detect_stream >= 2)) mask |= 1u << k;   // something runs in between
         }
         if (!mask) continue;
         if (!side_context_) {
             side_context_ = new Context;
-            CHECK_STATUS(side_context_->Init(context_->device(), opt_detect_priority_));
+            CHECK_STATUS(side_context_->Init(context_->device(), opt_.detect_priority));
             SI_TRY_HIP(si_hip_event_create(&ev_fork_), "event create");
             SI_TRY_HIP(si_hip_event_create(&ev_join_), "event create");
         }

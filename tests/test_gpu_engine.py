@@ -467,6 +467,63 @@ def test_host_tensor_pipeline_is_bit_identical(si, tmp_path, slices, graph, pin)
     dx.free()
 
 
+@pytest.fixture(scope="module")
+def yolo_b4(si, tmp_path_factory):
+    """YOLOv5s 160x160 traced at batch 4 (the size tests/plan_snapshot.py plans streams=2 at), one input, and what the default options compute
+    for it: shared, read-only, by the tests of what a child engine inherits."""
+    pp, bp = _save(tmp_path_factory.mktemp("yolo_b4"), si.modelgen.build_yolov5s(4, 160), "b4")
+    x = si.modelgen.synth_input((4, 160, 160, 3))
+    _, _, default_out = _run(si, pp, bp, x, host_slices=1)
+    default_out.setflags(write=False)
+    return pp, bp, x, default_out
+
+
+def _load(si, pp, bp, **opts):
+    e = si.Engine(**opts)
+    e.load_model(pp, bp)
+    return e
+
+
+@pytest.mark.parametrize("o", [dict(fuse=0, alias_cat=0), dict(fp16=1, fuse_stem=0, fuse_pw=0), dict(fuse_upsample=0, detect_stream=0), dict(arena=0)],
+                         ids=lambda o: "-".join("%s%d" % kv for kv in o.items()))
+def test_lanes_plan_with_the_parents_options(si, yolo_b4, o):
+    """streams=2 under non-default options: each of the two lanes is planned exactly as an engine of half the batch is under the SAME options --
+    the same launch list, the same fused-away operators, the same aliases, the same arena, twice.  (A lane that missed an option would plan with
+    that option's default.)  LoadModel only: nothing is launched."""
+    pp, bp, _, _ = yolo_b4
+    s2, s1 = _load(si, pp, bp, streams=2, **o).schedule(), _load(si, pp, bp, batch=2, **o).schedule()
+    sd = _load(si, pp, bp, batch=2).schedule()
+    assert any(s1[k] != sd[k] for k in ("run", "fused", "alias", "arena_bytes")), "the options %s do not change the plan: the case proves nothing" % o
+    assert s2["lanes"] == 2 and s1["lanes"] == 1
+    assert s2["run"] == s1["run"] and s2["fused"] == s1["fused"] and s2["alias"] == s1["alias"]
+    assert s2["arena_bytes"] == 2 * s1["arena_bytes"] and s2["per_operand_bytes"] == 2 * s1["per_operand_bytes"]
+
+
+@pytest.mark.parametrize("o", [dict(winograd=0), dict(winograd=2), dict(f32_split=1)], ids=lambda o: "-".join("%s%d" % kv for kv in o.items()))
+def test_lanes_build_their_layers_with_the_parents_options(si, yolo_b4, o):
+    """... and its layers are set up as that engine's are: after one forward, the kernels of the two-lane engine are the kernels of the half-batch
+    engine under the same options, lane 0 then lane 1."""
+    pp, bp, x, _ = yolo_b4
+    e2, _, _ = _run(si, pp, bp, x, streams=2, **o)
+    e1, _, _ = _run(si, pp, bp, x[:2], batch=2, **o)
+    ed, _, _ = _run(si, pp, bp, x[:2], batch=2)
+    k2, k1, kd = ([L["kernel"] for L in e.profile()] for e in (e2, e1, ed))
+    assert k1 != kd, "the options %s do not change a kernel: the case proves nothing" % o
+    assert k2 == k1 * 2
+
+
+@pytest.mark.parametrize("o", [dict(fp16=1), dict(winograd=0), dict(f32_split=1)], ids=lambda o: "-".join("%s%d" % kv for kv in o.items()))
+def test_host_tensor_pipeline_computes_with_the_parents_options(si, yolo_b4, o):
+    """host_slices=2 under non-default options: the sliced pipeline's engine computes what the unsliced engine computes under the SAME options,
+    bit for bit -- and that is not what the default options compute, so a slicer that missed the option would show."""
+    pp, bp, x, default_out = yolo_b4
+    _, _, ref = _run(si, pp, bp, x, host_slices=1, **o)
+    e, _, got = _run(si, pp, bp, x, host_slices=2, **o)
+    assert e.schedule()["host_slices"] == 2
+    assert_exact(got, ref, "two host slices vs unsliced under %s" % o)
+    assert ref.shape == default_out.shape and (ref != default_out).any(), "the options %s do not change a bit of the output: the case proves nothing" % o
+
+
 def test_borrowed_input_may_be_freed_after_forward_and_a_failed_pipeline_falls_back(si, tmp_path):
     """(1) by default nothing of the caller's stays registered with the driver across calls, so a borrowed buffer
     may be freed after Forward() and a new one -- at the same address or not -- handed over (the reference's borrow rule,
