@@ -1,5 +1,6 @@
 #include "conv_2d.h"
 
+#include <cstdio>
 #include <cstring>
 
 #include "layer_util.h"
@@ -168,9 +169,9 @@ Status Conv2d::LaunchStemTriple(const Tensor& image, Tensor& out0, Tensor* out1)
     Conv2d* const stem = c1 ? c1->stem_producer_ : nullptr;
     if (!stem || !c1->stem_mid_ || !stem_pair_mid_ || IsHalf(image) || !IsHalf(out0) || (out1 && !IsHalf(*out1)) || (sibling_ != nullptr) != (out1 != nullptr))
         return Status::kUnsupport;
-    CHECK_STATUS(PrepareDevice(1));
-    CHECK_STATUS(c1->PrepareDevice(1));
-    CHECK_STATUS(stem->PrepareDevice(2));
+    CHECK_STATUS(Prepare(WeightImage::kIgemmF16));
+    CHECK_STATUS(c1->Prepare(WeightImage::kIgemmF16));
+    CHECK_STATUS(stem->Prepare(WeightImage::kStemF16));
     SiConv2dDesc d0 = stem->MakeDesc(image, c1->stem_mid_->tensor), d1 = c1->MakeDesc(c1->stem_mid_->tensor, stem_pair_mid_->tensor);
     SiConv2dDesc d2 = MakeDesc(stem_pair_mid_->tensor, out0);
     d0.out_ld = d0.oc; d1.in_ld = d1.ic; d1.out_ld = d1.oc; d2.in_ld = d2.ic;
@@ -179,10 +180,9 @@ Status Conv2d::LaunchStemTriple(const Tensor& image, Tensor& out0, Tensor* out1)
         split = out_channels_;
         d2.oc = out_channels_ + sibling_->out_channels_;
     }
-    return CheckHip(si_hip_conv2d_stem_s2c32_pw_f16(&d0, &d1, &d2, image.Data<float>(), stem->weight_dev_.As<void>(),
-                                                    stem->use_bias_ ? stem->bias_dev_.As<float>() : nullptr, c1->weight_dev_.As<void>(),
-                                                    c1->use_bias_ ? c1->bias_dev_.As<float>() : nullptr, weight_dev_.As<void>(),
-                                                    use_bias_ ? bias_dev_.As<float>() : nullptr, out0.RawData(), split,
+    CHECK_BOOL(stem->Holds(WeightImage::kStemF16) && c1->Holds(WeightImage::kIgemmF16) && Holds(WeightImage::kIgemmF16));
+    return CheckHip(si_hip_conv2d_stem_s2c32_pw_f16(&d0, &d1, &d2, image.Data<float>(), stem->weight_dev_.As<void>(), stem->Bias(),
+                                                    c1->weight_dev_.As<void>(), c1->Bias(), weight_dev_.As<void>(), Bias(), out0.RawData(), split,
                                                     out1 ? out1->RawData() : nullptr, out1 ? out1->PixelStride() : 0, Stream()),
                     "conv2d stem + 3x3 s2 + 1x1 (fp16, one launch)");
 }
@@ -220,9 +220,9 @@ Status Conv2d::LaunchCv3(const Tensor& x, Tensor& output) {
     Conv2d* const pair = cv3_pair_;
     Conv2d* const pw = pair ? pair->pw_producer_ : nullptr;
     if (!pw || !pair->pw_mid_ || !cv3_z_ || !cv3_cat_ || pair->output_tensor_nodes_.empty() || !IsHalf(x) || !IsHalf(output)) return Status::kUnsupport;
-    CHECK_STATUS(PrepareDevice(1));
-    CHECK_STATUS(pair->PrepareDevice(1));
-    CHECK_STATUS(pw->PrepareDevice(1));
+    CHECK_STATUS(Prepare(WeightImage::kIgemmF16));
+    CHECK_STATUS(pair->Prepare(WeightImage::kIgemmF16));
+    CHECK_STATUS(pw->Prepare(WeightImage::kIgemmF16));
     const Tensor& y = pair->output_tensor_nodes_[0]->tensor;   // (shape only: never allocated)
     SiConv2dDesc d0 = pw->MakeDesc(x, pair->pw_mid_->tensor), d1 = pair->MakeDesc(pair->pw_mid_->tensor, y), d2 = MakeDesc(cv3_cat_->tensor, output);
     d0.out_ld = d0.oc; d1.in_ld = d1.ic; d1.out_ld = d1.oc; d2.in_ld = d2.ic;
@@ -232,10 +232,10 @@ Status Conv2d::LaunchCv3(const Tensor& x, Tensor& output) {
         d1.res_ld = res->PixelStride();
     }
     const Tensor& z = cv3_z_->tensor;
-    return CheckHip(si_hip_conv2d_pw_cv3_f16(&d0, &d1, &d2, x.RawData(), pw->weight_dev_.As<void>(), pw->use_bias_ ? pw->bias_dev_.As<float>() : nullptr,
-                                             pair->weight_dev_.As<void>(), pair->use_bias_ ? pair->bias_dev_.As<float>() : nullptr,
-                                             res ? res->RawData() : nullptr, z.RawData(), z.PixelStride(), weight_dev_.As<void>(),
-                                             use_bias_ ? bias_dev_.As<float>() : nullptr, output.RawData(), Stream()),
+    CHECK_BOOL(pw->Holds(WeightImage::kIgemmF16) && pair->Holds(WeightImage::kIgemmF16) && Holds(WeightImage::kIgemmF16));
+    return CheckHip(si_hip_conv2d_pw_cv3_f16(&d0, &d1, &d2, x.RawData(), pw->weight_dev_.As<void>(), pw->Bias(), pair->weight_dev_.As<void>(),
+                                             pair->Bias(), res ? res->RawData() : nullptr, z.RawData(), z.PixelStride(), weight_dev_.As<void>(),
+                                             Bias(), output.RawData(), Stream()),
                     "conv2d 1x1 + 3x3 + cat + 1x1 (fp16, one launch)");
 }
 
@@ -301,11 +301,92 @@ SiConv2dDesc Conv2d::MakeDesc(const Tensor& input, const Tensor& output) const {
     return d;
 }
 
-// mode 0: fp32 kernels; 1: fp16 implicit GEMM (fp16 weights); 2: fp16 stem kernel, fp32 image in / fp16 out (fp16 B fragments)
-Status Conv2d::PrepareDevice(int mode) {
-    if (device_ready_ && mode == prepared_mode_) return Status::kSuccess;
+// The layer's static shape (channels, kernel, stride, dilation, padding, groups): weight layouts and kernel eligibility are chosen from it, so
+// the descriptor used for packing carries all of those, exactly as the launch descriptor will.  `extra_oc`: a fused sibling's output channels.
+SiConv2dDesc Conv2d::StaticDesc(int extra_oc) const {
+    SiConv2dDesc d;
+    memset(&d, 0, sizeof(d));
+    d.ic = in_channels_; d.oc = out_channels_ + extra_oc; d.kh = kernel_h_; d.kw = kernel_w_; d.groups = groups_;
+    d.sh = stride_h_; d.sw = stride_w_; d.dh = dilation_h_; d.dw = dilation_w_; d.pt = padding_t_; d.pl = padding_l_;
+    return d;
+}
+
+// How a fused sibling's filters (SetSibling) enter an image.  kConcatOihw: ONE conv over the concatenated filters (OIHW: the sibling's rows
+// follow this layer's), packed as a whole -- such a buffer is not rows alone (the fp16 image is rows, then MFMA lane order: include/si_hip.h),
+// so two packed buffers cannot be appended.  kAppendPacked: [oc][K] layouts with the same K, the two packed images one after the other.
+enum class SiblingRule { kNone, kConcatOihw, kAppendPacked };
+
+// One row per weight image: how many elements of which size, who packs them, and what a fused sibling does to them.
+struct Conv2d::ImageRow {
+    size_t (*elems)(const SiConv2dDesc*);
+    int (*pack)(const SiConv2dDesc*, const float* w_oihw, void* packed);
+    size_t elem_size;
+    SiblingRule sibling;
+    // f32_split images: SI_E_UNSUPPORTED from the pack is a weight outside fp16's range (or not finite) -- this layer cannot be split and goes
+    // to the true-fp32 kernels, decided here, at load.  The log line, for (in_channels_, out_channels_); nullptr: that answer is an error
+    const char* demote;
+    const char* pack_label;
+};
+
+const Conv2d::ImageRow& Conv2d::RowOf(WeightImage image) {
+    static const ImageRow rows[] = {
+        /* kNone        */ {nullptr, nullptr, 0, SiblingRule::kNone, nullptr, ""},
+        /* kIgemmF32    */ {si_hip_conv2d_weight_elems,
+                            [](const SiConv2dDesc* d, const float* w, void* p) { return si_hip_conv2d_pack_weight_host(d, w, static_cast<float*>(p)); },
+                            sizeof(float), SiblingRule::kAppendPacked, nullptr, "pack weight"},
+        /* kWino23F32   */ {si_hip_conv2d_wino23_weight_elems,
+                            [](const SiConv2dDesc* d, const float* w, void* p) { return si_hip_conv2d_wino23_pack_weight_host(d, w, static_cast<float*>(p)); },
+                            sizeof(float), SiblingRule::kNone, nullptr, "winograd filter transform"},
+        /* kWino43F32   */ {si_hip_conv2d_wino43_weight_elems,
+                            [](const SiConv2dDesc* d, const float* w, void* p) { return si_hip_conv2d_wino43_pack_weight_host(d, w, static_cast<float*>(p)); },
+                            sizeof(float), SiblingRule::kNone, nullptr, "winograd filter transform"},
+        /* kIgemmF16    */ {si_hip_conv2d_f16_weight_elems, si_hip_conv2d_f16_pack_weight_host, sizeof(uint16_t), SiblingRule::kConcatOihw, nullptr,
+                            "pack fp16 weight"},
+        /* kStemF16     */ {si_hip_conv2d_stem_f16_weight_elems, si_hip_conv2d_stem_f16_pack_weight_host, sizeof(uint16_t), SiblingRule::kNone, nullptr,
+                            "pack stem weight"},
+        /* kSplit3      */ {si_hip_conv2d_split3_weight_elems, si_hip_conv2d_split3_pack_weight_host, sizeof(uint16_t), SiblingRule::kConcatOihw,
+                            "f32_split: conv %d -> %d has a weight outside fp16's range; the layer stays on the fp32 kernels",
+                            "split weights (hi / lo halves)"},
+        /* kWino23Split */ {si_hip_conv2d_wino23_split_weight_elems, si_hip_conv2d_wino23_split_pack_weight_host, sizeof(uint16_t), SiblingRule::kNone,
+                            "f32_split: conv %d -> %d has a transformed filter value outside fp16's range; the layer stays on the fp32 kernels",
+                            "winograd filter transform (hi / lo halves)"},
+        /* kStemSplit3  */ {si_hip_conv2d_stem_split3_weight_elems, si_hip_conv2d_stem_split3_pack_weight_host, sizeof(uint16_t), SiblingRule::kNone,
+                            "f32_split: stem conv %d -> %d has a weight outside fp16's range; the layer stays on the fp32 kernels",
+                            "split stem weights (hi / lo halves)"},
+    };
+    static_assert(sizeof(rows) / sizeof(rows[0]) == (size_t)WeightImage::kStemSplit3 + 1, "one row per weight image, in the enum's order");
+    return rows[(int)image];
+}
+
+Conv2d::WeightImage Conv2d::ImageFor(Route route) {
+    switch (route) {
+        case Route::kIgemmF32: return WeightImage::kIgemmF32;
+        case Route::kWino23F32: return WeightImage::kWino23F32;
+        case Route::kWino43F32: return WeightImage::kWino43F32;
+        case Route::kIgemmF16: return WeightImage::kIgemmF16;
+        case Route::kStemF16: return WeightImage::kStemF16;
+        case Route::kDepthwiseF16: return WeightImage::kIgemmF32;   // fp32 weights in the fp32 depthwise layout, as the fp32 kernel reads them
+        case Route::kSplit3: return WeightImage::kSplit3;
+        case Route::kWinoSplit: return WeightImage::kWino23Split;
+        case Route::kStemSplit: return WeightImage::kStemSplit3;
+    }
+    return WeightImage::kNone;
+}
+
+// said before every launch: the kernel about to run reads `need`.  A mismatch is a returned kFail and this line, not a read past a buffer
+bool Conv2d::Holds(WeightImage need) const {
+    if (device_ready_ && image_ == need) return true;
+    LOG(ERROR) << "Conv2d " << in_channels_ << " -> " << out_channels_ << ": the launch reads weight image " << (int)need << ", the device buffer holds "
+               << (device_ready_ ? (int)image_ : 0);
+    return false;
+}
+
+// packs and uploads `image` (and the bias) unless the device buffer holds it already
+Status Conv2d::Prepare(WeightImage image) {
+    if (device_ready_ && image == image_) return Status::kSuccess;
     device_ready_ = false;
-    prepared_mode_ = mode;
+    image_ = image;
+    CHECK_BOOL(image != WeightImage::kNone);
     CHECK_BOOL(groups_ > 0 && in_channels_ > 0 && out_channels_ > 0 && kernel_h_ > 0 && kernel_w_ > 0);
     CHECK_BOOL(in_channels_ % groups_ == 0 && out_channels_ % groups_ == 0);
     const size_t expect = (size_t)out_channels_ * (in_channels_ / groups_) * kernel_h_ * kernel_w_;
@@ -315,152 +396,65 @@ Status Conv2d::PrepareDevice(int mode) {
     }
     if (use_bias_ && bias_.size() != (size_t)out_channels_) return Status::kErrorShape;
 
-    // the weight layout is chosen from the layer's static shape (channels, kernel, stride, dilation, groups), so the
-    // descriptor used for packing must carry all of those, exactly as the launch descriptor will
-    SiConv2dDesc d;
-    memset(&d, 0, sizeof(d));
-    d.ic = in_channels_; d.oc = out_channels_; d.kh = kernel_h_; d.kw = kernel_w_; d.groups = groups_;
-    d.sh = stride_h_; d.sw = stride_w_; d.dh = dilation_h_; d.dw = dilation_w_; d.pt = padding_t_; d.pl = padding_l_;
-    if (mode == 1) return PrepareDeviceHalf(d);
-    if (mode == 3 && si_hip_conv2d_f16_supported(&d) != 3) {
-        LOG(ERROR) << "Conv2d: no fp16 depthwise kernel for " << in_channels_ << " channels (needs a multiple of 8)";
-        return Status::kUnsupport;
-    }   // (mode 3 then packs the fp32 depthwise image below, exactly as mode 0 does)
-    if (mode == 4) {
-        wino_tile_ = 0;
-        use_winograd_ = false;
-        // (sibling fusion: ONE conv over the concatenated filters -- OIHW: the sibling's rows follow this layer's -- as PrepareDeviceHalf)
-        std::vector<float> w_all = weight_, bias_all = bias_;
-        if (sibling_) {
-            CHECK_BOOL(sibling_->weight_.size() == (size_t)sibling_->out_channels_ * in_channels_);
-            d.oc = out_channels_ + sibling_->out_channels_;
-            w_all.insert(w_all.end(), sibling_->weight_.begin(), sibling_->weight_.end());
-            if (use_bias_) bias_all.insert(bias_all.end(), sibling_->bias_.begin(), sibling_->bias_.end());
-        }
-        std::vector<uint16_t> packed(si_hip_conv2d_split3_weight_elems(&d));
-        CHECK_BOOL(!packed.empty());
-        if (si_hip_conv2d_split3_pack_weight_host(&d, w_all.data(), packed.data()) == SI_E_UNSUPPORTED) {
-            // a weight outside fp16's range (or not finite): this layer cannot be split -- the true-fp32 kernels, decided here, at load
-            LOG(WARNING) << "f32_split: conv " << in_channels_ << " -> " << out_channels_ << " has a weight outside fp16's range; the layer stays on the fp32 kernels";
-            DemoteSplit();
-            return Status::kUnsupport;
-        }
-        CHECK_STATUS(CheckHip(si_hip_conv2d_split3_pack_weight_host(&d, w_all.data(), packed.data()), "split weights (hi / lo halves)"));
-        CHECK_STATUS(CheckHip(weight_dev_.Upload(packed.data(), packed.size() * sizeof(uint16_t)), "upload weight"));
-        if (use_bias_) CHECK_STATUS(CheckHip(bias_dev_.Upload(bias_all.data(), bias_all.size() * sizeof(float)), "upload bias"));
-        device_ready_ = true;
-        return Status::kSuccess;
-    }
-    if (mode == 5) {
-        wino_tile_ = 0;
-        use_winograd_ = false;
-        std::vector<uint16_t> packed(si_hip_conv2d_wino23_split_weight_elems(&d));
-        CHECK_BOOL(!packed.empty());
-        if (si_hip_conv2d_wino23_split_pack_weight_host(&d, weight_.data(), packed.data()) == SI_E_UNSUPPORTED) {
-            LOG(WARNING) << "f32_split: conv " << in_channels_ << " -> " << out_channels_ << " has a transformed filter value outside fp16's range; the layer stays on the fp32 kernels";
-            DemoteSplit();
-            return Status::kUnsupport;
-        }
-        CHECK_STATUS(CheckHip(si_hip_conv2d_wino23_split_pack_weight_host(&d, weight_.data(), packed.data()), "winograd filter transform (hi / lo halves)"));
-        CHECK_STATUS(CheckHip(weight_dev_.Upload(packed.data(), packed.size() * sizeof(uint16_t)), "upload weight"));
-        if (use_bias_) CHECK_STATUS(CheckHip(bias_dev_.Upload(bias_.data(), bias_.size() * sizeof(float)), "upload bias"));
-        device_ready_ = true;
-        return Status::kSuccess;
-    }
-    if (mode == 6) {
-        wino_tile_ = 0;
-        use_winograd_ = false;
-        std::vector<uint16_t> packed(si_hip_conv2d_stem_split3_weight_elems(&d));
-        CHECK_BOOL(!packed.empty());
-        if (si_hip_conv2d_stem_split3_pack_weight_host(&d, weight_.data(), packed.data()) == SI_E_UNSUPPORTED) {
-            LOG(WARNING) << "f32_split: stem conv " << in_channels_ << " -> " << out_channels_ << " has a weight outside fp16's range; the layer stays on the fp32 kernels";
-            DemoteSplit();
-            return Status::kUnsupport;
-        }
-        CHECK_STATUS(CheckHip(si_hip_conv2d_stem_split3_pack_weight_host(&d, weight_.data(), packed.data()), "split stem weights (hi / lo halves)"));
-        CHECK_STATUS(CheckHip(weight_dev_.Upload(packed.data(), packed.size() * sizeof(uint16_t)), "upload weight"));
-        if (use_bias_) CHECK_STATUS(CheckHip(bias_dev_.Upload(bias_.data(), bias_.size() * sizeof(float)), "upload bias"));
-        device_ready_ = true;
-        return Status::kSuccess;
-    }
-    if (mode == 2) {
-        wino_tile_ = 0;
-        use_winograd_ = false;
-        std::vector<uint16_t> packed(si_hip_conv2d_stem_f16_weight_elems(&d));
-        CHECK_BOOL(!packed.empty());
-        CHECK_STATUS(CheckHip(si_hip_conv2d_stem_f16_pack_weight_host(&d, weight_.data(), packed.data()), "pack stem weight"));
-        CHECK_STATUS(CheckHip(weight_dev_.Upload(packed.data(), packed.size() * sizeof(uint16_t)), "upload weight"));
-        if (use_bias_) CHECK_STATUS(CheckHip(bias_dev_.Upload(bias_.data(), bias_.size() * sizeof(float)), "upload bias"));
-        device_ready_ = true;
-        return Status::kSuccess;
-    }
-    wino_tile_ = WinogradTile(d);
+    wino_tile_ = TileOf(image);
     use_winograd_ = wino_tile_ != 0;
-    if ((algo_ == Algo::kWinograd23 || algo_ == Algo::kWinograd43) && !use_winograd_) {
-        LOG(ERROR) << "Conv2d: Winograd requested for a shape it does not support";
-        return Status::kUnsupport;
-    }
-    std::vector<float> packed(wino_tile_ == 4   ? si_hip_conv2d_wino43_weight_elems(&d)
-                              : wino_tile_ == 2 ? si_hip_conv2d_wino23_weight_elems(&d)
-                                                : si_hip_conv2d_weight_elems(&d));
-    if (wino_tile_ == 4) {
-        CHECK_STATUS(CheckHip(si_hip_conv2d_wino43_pack_weight_host(&d, weight_.data(), packed.data()), "winograd filter transform"));
-    } else if (wino_tile_ == 2) {
-        CHECK_STATUS(CheckHip(si_hip_conv2d_wino23_pack_weight_host(&d, weight_.data(), packed.data()), "winograd filter transform"));
-    } else {
-        CHECK_STATUS(CheckHip(si_hip_conv2d_pack_weight_host(&d, weight_.data(), packed.data()), "pack weight"));
-    }
-    std::vector<float> bias_all = bias_;
-    if (sibling_) {
-        // [oc][K] layouts with the same K: the fused weight is the two images one after the other
-        SiConv2dDesc ds = d;
-        ds.oc = sibling_->out_channels_;
-        CHECK_BOOL(sibling_->weight_.size() == (size_t)ds.oc * in_channels_);
-        std::vector<float> packed2(si_hip_conv2d_weight_elems(&ds));
-        CHECK_STATUS(CheckHip(si_hip_conv2d_pack_weight_host(&ds, sibling_->weight_.data(), packed2.data()), "pack sibling weight"));
-        packed.insert(packed.end(), packed2.begin(), packed2.end());
-        if (use_bias_) bias_all.insert(bias_all.end(), sibling_->bias_.begin(), sibling_->bias_.end());
-    }
-    CHECK_STATUS(CheckHip(weight_dev_.Upload(packed.data(), packed.size() * sizeof(float)), "upload weight"));
-    if (use_bias_) CHECK_STATUS(CheckHip(bias_dev_.Upload(bias_all.data(), bias_all.size() * sizeof(float)), "upload bias"));
-    device_ready_ = true;
-    return Status::kSuccess;
-}
-
-Status Conv2d::PrepareDeviceHalf(const SiConv2dDesc& d) {
-    wino_tile_ = 0;
-    use_winograd_ = false;
-    if (si_hip_conv2d_f16_supported(&d) != 1) {
+    const ImageRow& row = RowOf(image);
+    SiConv2dDesc d = StaticDesc();
+    if (image == WeightImage::kIgemmF16 && si_hip_conv2d_f16_supported(&d) != 1) {
         LOG(ERROR) << "Conv2d: no fp16 kernel for " << in_channels_ << " -> " << out_channels_ << " channels, groups " << groups_
                    << " (needs ic/groups % 32 == 0)";
         return Status::kUnsupport;
     }
-    // sibling fusion: ONE conv over the concatenated filters (OIHW: the sibling's rows follow this layer's), packed as a whole --
-    // the packed buffer holds two images (rows, then MFMA lane order, include/si_hip.h), so two packed buffers cannot be appended
-    SiConv2dDesc df = d;
-    std::vector<float> w_all = weight_;
-    std::vector<float> bias_all = bias_;
-    if (sibling_) {
-        CHECK_BOOL(sibling_->weight_.size() == (size_t)sibling_->out_channels_ * in_channels_);
-        df.oc = d.oc + sibling_->out_channels_;
-        w_all.insert(w_all.end(), sibling_->weight_.begin(), sibling_->weight_.end());
-        if (use_bias_) bias_all.insert(bias_all.end(), sibling_->bias_.begin(), sibling_->bias_.end());
+    if (image == WeightImage::kIgemmF32 && (algo_ == Algo::kWinograd23 || algo_ == Algo::kWinograd43)) {   // (RouteFor found no tile for it)
+        LOG(ERROR) << "Conv2d: Winograd requested for a shape it does not support";
+        return Status::kUnsupport;
     }
-    std::vector<uint16_t> packed(si_hip_conv2d_f16_weight_elems(&df));
+    std::vector<float> w_all, bias_all = bias_;
+    const float* w = weight_.data();
+    if (sibling_) {
+        // today's routes never bring a fused pair to an image that has no rule for it (RouteFor, WinogradTile); were one to, packing this
+        // conv alone would leave the sibling's output unwritten
+        if (row.sibling == SiblingRule::kNone) {
+            LOG(ERROR) << "Conv2d: weight image " << (int)image << " has no form for a fused sibling";
+            return Status::kUnsupport;
+        }
+        CHECK_BOOL(sibling_->weight_.size() == (size_t)sibling_->out_channels_ * in_channels_);
+        if (use_bias_) bias_all.insert(bias_all.end(), sibling_->bias_.begin(), sibling_->bias_.end());
+        if (row.sibling == SiblingRule::kConcatOihw) {
+            d.oc += sibling_->out_channels_;
+            w_all = weight_;
+            w_all.insert(w_all.end(), sibling_->weight_.begin(), sibling_->weight_.end());
+            w = w_all.data();
+        }
+    }
+    std::vector<unsigned char> packed(row.elems(&d) * row.elem_size);
     CHECK_BOOL(!packed.empty());
-    CHECK_STATUS(CheckHip(si_hip_conv2d_f16_pack_weight_host(&df, w_all.data(), packed.data()), "pack fp16 weight"));
-    CHECK_STATUS(CheckHip(weight_dev_.Upload(packed.data(), packed.size() * sizeof(uint16_t)), "upload weight"));
+    const int rc = row.pack(&d, w, packed.data());
+    if (rc == SI_E_UNSUPPORTED && row.demote) {
+        char line[192];
+        snprintf(line, sizeof(line), row.demote, in_channels_, out_channels_);
+        LOG(WARNING) << line;
+        DemoteSplit();
+        return Status::kUnsupport;
+    }
+    CHECK_STATUS(CheckHip(rc, row.pack_label));
+    if (sibling_ && row.sibling == SiblingRule::kAppendPacked) {
+        SiConv2dDesc ds = d;
+        ds.oc = sibling_->out_channels_;
+        std::vector<unsigned char> packed2(row.elems(&ds) * row.elem_size);
+        CHECK_STATUS(CheckHip(row.pack(&ds, sibling_->weight_.data(), packed2.data()), "pack sibling weight"));
+        packed.insert(packed.end(), packed2.begin(), packed2.end());
+    }
+    CHECK_STATUS(CheckHip(weight_dev_.Upload(packed.data(), packed.size()), "upload weight"));
     if (use_bias_) CHECK_STATUS(CheckHip(bias_dev_.Upload(bias_all.data(), bias_all.size() * sizeof(float)), "upload bias"));
     device_ready_ = true;
     return Status::kSuccess;
 }
 
-// which kernel family serves this (input, output) storage pair; a non-stem conv fed an fp32 tensor inside an fp16 graph
-// converts its input first (in_half_)
-// (4: fp32 tensors, the contraction on the fp16 matrix cores by operand splitting -- engine option f32_split, opt-in)
 // Detect levels under f32_split: from this channel count on (tools/split3_check.py --detect; profiles/r05_f32_split_detect.txt)
 static const int kSplit3DetectMinChannels = 128;
 
+// (kSplit3: fp32 tensors, the contraction on the fp16 matrix cores by operand splitting -- engine option f32_split, opt-in)
 bool Conv2d::UseSplit3() const {
     if (!f32_split_ || stem_producer_ || groups_ != 1 || dilation_h_ != 1 || dilation_w_ != 1) return false;
     // (round 6: the dual-source form -- upsample + concat read at the source -- exists on the split kernel too, for 64-channel granularity)
@@ -472,10 +466,7 @@ bool Conv2d::UseSplit3() const {
     // (round 6: a sibling-fused conv -- C3's cv1 | cv2 -- is ONE conv over the concatenated filters here too: si_hip_conv2d_split3_split_f32)
     if (sibling_ && (f32_split_level_ < 2 || residual_node_ || out_channels_ % 32 != 0)) return false;
     const int oc_all = out_channels_ + (sibling_ ? sibling_->out_channels_ : 0);
-    SiConv2dDesc d;
-    memset(&d, 0, sizeof(d));
-    d.ic = in_channels_; d.oc = oc_all; d.kh = kernel_h_; d.kw = kernel_w_; d.groups = groups_;
-    d.sh = stride_h_; d.sw = stride_w_; d.dh = dilation_h_; d.dw = dilation_w_; d.pt = padding_t_; d.pl = padding_l_;
+    SiConv2dDesc d = StaticDesc(oc_all - out_channels_);
     d.in_ld = in_channels_;
     if (!si_hip_conv2d_split3_supported(&d)) return false;
     // Where it pays (YOLOv5s batch 32, per layer, profiles/r05_f32_split.txt): K >= 512 and >= 128 output channels -- the 3x3 stride-2
@@ -495,38 +486,67 @@ bool Conv2d::UseSplit3() const {
     return !(wino_shape && in_channels_ < 256 && algo_ != Algo::kImplicitGemm);
 }
 
-// (5: f32_split on a layer the fused Winograd F(2,3) kernel serves -- the same kernel around a channel loop on the fp16 matrix cores,
-// conv_wino23_split.hip)
+// (kWinoSplit: f32_split on a layer the fused Winograd F(2,3) kernel serves -- the same kernel around a channel loop on the fp16 matrix
+// cores, conv_wino23_split.hip)
 bool Conv2d::UseWinoSplit() const {
     if (!f32_split_ || sibling_ || up_node_ || stem_producer_ || groups_ != 1) return false;
-    SiConv2dDesc d;
-    memset(&d, 0, sizeof(d));
-    d.ic = in_channels_; d.oc = out_channels_; d.kh = kernel_h_; d.kw = kernel_w_; d.groups = groups_;
-    d.sh = stride_h_; d.sw = stride_w_; d.dh = dilation_h_; d.dw = dilation_w_; d.pt = padding_t_; d.pl = padding_l_;
+    const SiConv2dDesc d = StaticDesc();
     return WinogradTile(d) == 2 && si_hip_conv2d_wino23_split_supported(&d) != 0;
 }
 
-// (6: f32_split on the RGB stem -- the fp16 stem kernel's staging and MFMA loop on operands split hi + 2^-11 lo, fp32 out: conv_stem_f16.hip)
+// (kStemSplit: f32_split on the RGB stem -- the fp16 stem kernel's staging and MFMA loop on operands split hi + 2^-11 lo, fp32 out:
+// conv_stem_f16.hip)
 bool Conv2d::UseStemSplit() const {
     if (!f32_split_ || f32_split_level_ < 4 || sibling_ || up_node_ || stem_producer_ || residual_node_) return false;
-    SiConv2dDesc d;
-    memset(&d, 0, sizeof(d));
-    d.ic = in_channels_; d.oc = out_channels_; d.kh = kernel_h_; d.kw = kernel_w_; d.groups = groups_;
-    d.sh = stride_h_; d.sw = stride_w_; d.dh = dilation_h_; d.dw = dilation_w_; d.pt = padding_t_; d.pl = padding_l_;
+    const SiConv2dDesc d = StaticDesc();
     return si_hip_conv2d_f16_supported(&d) == 2;
 }
 
-int Conv2d::PrecisionMode(const Tensor& input, const Tensor& output) const {
-    if (!IsHalf(input) && !IsHalf(output)) return UseSplit3() ? 4 : (UseWinoSplit() ? 5 : (UseStemSplit() ? 6 : 0));
-    if (groups_ > 1 && groups_ == in_channels_ && in_channels_ == out_channels_ && IsHalf(input) && IsHalf(output)) return 3;   // depthwise, fp16 storage
-    if (!IsHalf(input)) {
-        SiConv2dDesc d;
-        memset(&d, 0, sizeof(d));
-        d.ic = in_channels_; d.oc = out_channels_; d.kh = kernel_h_; d.kw = kernel_w_; d.groups = groups_;
-        d.sh = stride_h_; d.sw = stride_w_; d.dh = dilation_h_; d.dw = dilation_w_; d.pt = padding_t_; d.pl = padding_l_;
-        if (si_hip_conv2d_f16_supported(&d) == 2 && !residual_node_ && !sibling_) return 2;
+// which kernel family serves this (input, output) storage pair; a non-stem conv fed an fp32 tensor inside an fp16 graph
+// converts its input first (in_half_)
+Conv2d::Route Conv2d::RouteFor(bool in_half, bool out_half) const {
+    if (!in_half && !out_half) {
+        if (UseSplit3()) return Route::kSplit3;
+        if (UseWinoSplit()) return Route::kWinoSplit;
+        if (UseStemSplit()) return Route::kStemSplit;
+        const SiConv2dDesc d = StaticDesc();
+        const int tile = WinogradTile(d);
+        return tile == 4 ? Route::kWino43F32 : (tile == 2 ? Route::kWino23F32 : Route::kIgemmF32);
     }
-    return 1;
+    if (groups_ > 1 && groups_ == in_channels_ && in_channels_ == out_channels_ && in_half && out_half) return Route::kDepthwiseF16;
+    if (!in_half) {
+        const SiConv2dDesc d = StaticDesc();
+        if (si_hip_conv2d_f16_supported(&d) == 2 && !residual_node_ && !sibling_) return Route::kStemF16;
+    }
+    return Route::kIgemmF16;
+}
+
+// the Detect-head entry point's own choice (ForwardYolo): the input's storage type, and under f32_split the level's channel counts
+// (YOLOv5s batch 32: 147 -> 118, 64 -> 43, 33 -> 26 us per level, +3 % on the network; profiles/r05_f32_split_detect.txt)
+Conv2d::Route Conv2d::YoloRoute(bool in_half) const {
+    if (in_half) return Route::kIgemmF16;
+    return (f32_split_ && in_channels_ % 64 == 0 && in_channels_ >= kSplit3DetectMinChannels && out_channels_ > 64) ? Route::kSplit3 : Route::kIgemmF32;
+}
+
+// Prepare for the route that serves the pair.  A weight out of fp16's range demotes an f32_split layer while its image is packed (Prepare):
+// the route is then asked for once more, without the option
+Status Conv2d::PrepareRoute(bool in_half, bool out_half, Route& route, bool yolo) {
+    const auto pick = [&] { return yolo ? YoloRoute(in_half) : RouteFor(in_half, out_half); };
+    route = pick();
+    if (route == Route::kDepthwiseF16) {   // (the image is the fp32 kernel's, which serves any channel count)
+        const SiConv2dDesc d = StaticDesc();
+        if (si_hip_conv2d_f16_supported(&d) != 3) {
+            LOG(ERROR) << "Conv2d: no fp16 depthwise kernel for " << in_channels_ << " channels (needs a multiple of 8)";
+            return Status::kUnsupport;
+        }
+    }
+    const bool split_on = f32_split_;
+    Status st = Prepare(ImageFor(route));
+    if (Status::kUnsupport == st && split_on && !f32_split_) {
+        route = pick();
+        st = Prepare(ImageFor(route));
+    }
+    return st;
 }
 
 Status Conv2d::HalfInput(const Tensor& input, Tensor& half) {
@@ -550,67 +570,65 @@ Status Conv2d::Forward(const Tensor& input, std::vector<Tensor>& outputs) {
     if (!sibling_ || outputs.size() != 2) return Status::kUnsupport;
     return RunOnDevice({&input}, {&outputs[0], &outputs[1]}, [this](const std::vector<Tensor>& in, std::vector<Tensor>& out) {
         if (stem_pair_) return LaunchStemTriple(in[0], out[0], &out[1]);
-        int mode = PrecisionMode(in[0], out[0]);
         if (IsHalf(out[0]) != IsHalf(out[1])) return Status::kUnsupport;
-        {
-            Status st = PrepareDevice(mode);
-            if (Status::kUnsupport == st && mode == 4 && !f32_split_) {   // (a weight out of fp16's range: see PrepareDevice)
-                mode = PrecisionMode(in[0], out[0]);
-                st = PrepareDevice(mode);
-            }
-            CHECK_STATUS(st);
-        }
+        Route route;
+        CHECK_STATUS(PrepareRoute(IsHalf(in[0]), IsHalf(out[0]), route));
         Dims4 di, d0, d1;
         if (!GetDims4(in[0], di) || !GetDims4(out[0], d0) || !GetDims4(out[1], d1)) return Status::kErrorShape;
         if (di.c != in_channels_ || d0.c != out_channels_ || d1.c != sibling_->out_channels_ || d0.pixels() != d1.pixels()) return Status::kErrorShape;
         SiConv2dDesc d = MakeDesc(in[0], out[0]);
         d.oc = out_channels_ + sibling_->out_channels_;
-        if (mode == 4) {
-            d.range_flag = range_flag_;
-            int rc;
-            if (up_node_) {
-                SiConv2dUpsampledSource up;
-                CHECK_STATUS(MakeUpsampledSource(up));
-                rc = si_hip_conv2d_split3_upcat_f32(&d, in[0].Data<float>(), &up, weight_dev_.As<void>(), use_bias_ ? bias_dev_.As<float>() : nullptr,
-                                                    out[0].Data<float>(), out_channels_, out[1].Data<float>(), out[1].PixelStride(), Stream());
-            } else
-            rc = si_hip_conv2d_split3_split_f32(&d, in[0].Data<float>(), weight_dev_.As<void>(), use_bias_ ? bias_dev_.As<float>() : nullptr,
-                                                          out[0].Data<float>(), out_channels_, out[1].Data<float>(), out[1].PixelStride(), Stream());
-            if (rc != SI_E_UNSUPPORTED) return CheckHip(rc, "conv2d (fused siblings, fp32 by three fp16 products)");
-            DemoteSplit();   // an unaligned / oversized view: the true-fp32 kernels from here on
-            d.range_flag = nullptr;
-            mode = 0;
-            CHECK_STATUS(PrepareDevice(0));
+        switch (route) {
+            case Route::kSplit3: {
+                d.range_flag = range_flag_;
+                int rc;
+                CHECK_BOOL(Holds(WeightImage::kSplit3));
+                if (up_node_) {
+                    SiConv2dUpsampledSource up;
+                    CHECK_STATUS(MakeUpsampledSource(up));
+                    rc = si_hip_conv2d_split3_upcat_f32(&d, in[0].Data<float>(), &up, weight_dev_.As<void>(), Bias(), out[0].Data<float>(), out_channels_,
+                                                        out[1].Data<float>(), out[1].PixelStride(), Stream());
+                } else {
+                    rc = si_hip_conv2d_split3_split_f32(&d, in[0].Data<float>(), weight_dev_.As<void>(), Bias(), out[0].Data<float>(), out_channels_,
+                                                        out[1].Data<float>(), out[1].PixelStride(), Stream());
+                }
+                if (rc != SI_E_UNSUPPORTED) return CheckHip(rc, "conv2d (fused siblings, fp32 by three fp16 products)");
+                DemoteSplit();   // an unaligned / oversized view: the true-fp32 kernels from here on
+                d.range_flag = nullptr;
+                CHECK_STATUS(Prepare(WeightImage::kIgemmF32));
+            }
+                [[fallthrough]];
+            case Route::kIgemmF32:
+                CHECK_BOOL(Holds(WeightImage::kIgemmF32));
+                if (up_node_) {
+                    SiConv2dUpsampledSource up;
+                    CHECK_STATUS(MakeUpsampledSource(up));
+                    return CheckHip(si_hip_conv2d_upcat_f32(&d, in[0].Data<float>(), &up, weight_dev_.As<float>(), Bias(), out[0].Data<float>(),
+                                                            out_channels_, out[1].Data<float>(), out[1].PixelStride(), Stream()),
+                                    "conv2d (fused siblings, upsampled source)");
+                }
+                return CheckHip(si_hip_conv2d_split_f32(&d, in[0].Data<float>(), weight_dev_.As<float>(), Bias(), out[0].Data<float>(), out_channels_,
+                                                        out[1].Data<float>(), out[1].PixelStride(), Stream()),
+                                "conv2d (fused siblings)");
+            case Route::kIgemmF16: {
+                CHECK_BOOL(Holds(WeightImage::kIgemmF16));
+                if (up_node_) {
+                    if (!IsHalf(in[0])) return Status::kUnsupport;
+                    SiConv2dUpsampledSource up;
+                    CHECK_STATUS(MakeUpsampledSource(up));
+                    return CheckHip(si_hip_conv2d_upcat_f16(&d, in[0].RawData(), &up, weight_dev_.As<void>(), Bias(), out[0].RawData(), out_channels_,
+                                                            out[1].RawData(), out[1].PixelStride(), Stream()),
+                                    "conv2d fp16 (fused siblings, upsampled source)");
+                }
+                Tensor xin;
+                CHECK_STATUS(HalfInput(in[0], xin));
+                d.in_ld = xin.PixelStride();
+                return CheckHip(si_hip_conv2d_split_f16(&d, xin.RawData(), weight_dev_.As<void>(), Bias(), out[0].RawData(), out_channels_,
+                                                        out[1].RawData(), out[1].PixelStride(), Stream()),
+                                "conv2d fp16 (fused siblings)");
+            }
+            default: return Status::kUnsupport;   // (no other family computes two outputs; RouteFor gives a fused pair none of them)
         }
-        if (mode == 1 && up_node_) {
-            if (!IsHalf(in[0])) return Status::kUnsupport;
-            SiConv2dUpsampledSource up;
-            CHECK_STATUS(MakeUpsampledSource(up));
-            return CheckHip(si_hip_conv2d_upcat_f16(&d, in[0].RawData(), &up, weight_dev_.As<void>(), use_bias_ ? bias_dev_.As<float>() : nullptr,
-                                                    out[0].RawData(), out_channels_, out[1].RawData(), out[1].PixelStride(), Stream()),
-                            "conv2d fp16 (fused siblings, upsampled source)");
-        }
-        if (mode == 1) {
-            Tensor xin;
-            CHECK_STATUS(HalfInput(in[0], xin));
-            d.in_ld = xin.PixelStride();
-            return CheckHip(si_hip_conv2d_split_f16(&d, xin.RawData(), weight_dev_.As<void>(),
-                                                    use_bias_ ? bias_dev_.As<float>() : nullptr, out[0].RawData(), out_channels_,
-                                                    out[1].RawData(), out[1].PixelStride(), Stream()),
-                            "conv2d fp16 (fused siblings)");
-        }
-        if (up_node_) {
-            if (mode != 0) return Status::kUnsupport;
-            SiConv2dUpsampledSource up;
-            CHECK_STATUS(MakeUpsampledSource(up));
-            return CheckHip(si_hip_conv2d_upcat_f32(&d, in[0].Data<float>(), &up, weight_dev_.As<float>(), use_bias_ ? bias_dev_.As<float>() : nullptr,
-                                                    out[0].Data<float>(), out_channels_, out[1].Data<float>(), out[1].PixelStride(), Stream()),
-                            "conv2d (fused siblings, upsampled source)");
-        }
-        return CheckHip(si_hip_conv2d_split_f32(&d, in[0].Data<float>(), weight_dev_.As<float>(),
-                                                use_bias_ ? bias_dev_.As<float>() : nullptr, out[0].Data<float>(), out_channels_,
-                                                out[1].Data<float>(), out[1].PixelStride(), Stream()),
-                        "conv2d (fused siblings)");
     });
 }
 
@@ -620,31 +638,29 @@ Status Conv2d::Launch(const Tensor& input, const Tensor* residual, Tensor& outpu
     if (stem_producer_) {
         // the stem conv and this one in one launch: `input` is the fp32 image
         if (residual || !stem_mid_ || IsHalf(input) || !IsHalf(output)) return Status::kUnsupport;
-        CHECK_STATUS(PrepareDevice(1));
-        CHECK_STATUS(stem_producer_->PrepareDevice(2));
+        CHECK_STATUS(Prepare(WeightImage::kIgemmF16));
+        CHECK_STATUS(stem_producer_->Prepare(WeightImage::kStemF16));
         SiConv2dDesc d0 = stem_producer_->MakeDesc(input, stem_mid_->tensor), d1 = MakeDesc(stem_mid_->tensor, output);
         d0.out_ld = d0.oc; d1.in_ld = d1.ic;
-        return CheckHip(si_hip_conv2d_stem_s2c32_f16(&d0, &d1, input.Data<float>(), stem_producer_->weight_dev_.As<void>(),
-                                                     stem_producer_->use_bias_ ? stem_producer_->bias_dev_.As<float>() : nullptr,
-                                                     weight_dev_.As<void>(), use_bias_ ? bias_dev_.As<float>() : nullptr, output.RawData(),
-                                                     Stream()),
+        CHECK_BOOL(stem_producer_->Holds(WeightImage::kStemF16) && Holds(WeightImage::kIgemmF16));
+        return CheckHip(si_hip_conv2d_stem_s2c32_f16(&d0, &d1, input.Data<float>(), stem_producer_->weight_dev_.As<void>(), stem_producer_->Bias(),
+                                                     weight_dev_.As<void>(), Bias(), output.RawData(), Stream()),
                         "conv2d stem + 3x3 s2 (fp16, one launch)");
     }
     if (pw_producer_) {
         // the bottleneck's 1x1 conv and this 3x3 one in one launch: `input` is the 1x1 conv's input
         if (!pw_mid_ || !IsHalf(input) || !IsHalf(output) || (residual && !IsHalf(*residual))) return Status::kUnsupport;
-        CHECK_STATUS(PrepareDevice(1));
-        CHECK_STATUS(pw_producer_->PrepareDevice(1));
+        CHECK_STATUS(Prepare(WeightImage::kIgemmF16));
+        CHECK_STATUS(pw_producer_->Prepare(WeightImage::kIgemmF16));
         SiConv2dDesc d0 = pw_producer_->MakeDesc(input, pw_mid_->tensor), d1 = MakeDesc(pw_mid_->tensor, output);
         d0.out_ld = d0.oc; d1.in_ld = d1.ic;
         if (residual) {
             d1.has_residual = 1;
             d1.res_ld = residual->PixelStride();
         }
-        const int rc = si_hip_conv2d_pw_slab_f16(&d0, &d1, input.RawData(), pw_producer_->weight_dev_.As<void>(),
-                                                 pw_producer_->use_bias_ ? pw_producer_->bias_dev_.As<float>() : nullptr, weight_dev_.As<void>(),
-                                                 use_bias_ ? bias_dev_.As<float>() : nullptr, residual ? residual->RawData() : nullptr,
-                                                 output.RawData(), Stream());
+        CHECK_BOOL(pw_producer_->Holds(WeightImage::kIgemmF16) && Holds(WeightImage::kIgemmF16));
+        const int rc = si_hip_conv2d_pw_slab_f16(&d0, &d1, input.RawData(), pw_producer_->weight_dev_.As<void>(), pw_producer_->Bias(),
+                                                 weight_dev_.As<void>(), Bias(), residual ? residual->RawData() : nullptr, output.RawData(), Stream());
         if (rc != SI_E_UNSUPPORTED) return CheckHip(rc, "conv2d 1x1 + 3x3 (fp16, one launch)");
         // The pair was fused on dense strides, before the concat aliasing gave the tensors their real views (CanFusePointwiseProducer); the
         // launch re-checks the views it gets (16-byte aligned rows, strides in whole 16-byte vectors) and may refuse a channel slice at an odd
@@ -658,15 +674,8 @@ Status Conv2d::Launch(const Tensor& input, const Tensor* residual, Tensor& outpu
         pw_producer_ = pw;
         return st;
     }
-    int mode = PrecisionMode(input, output);
-    {
-        Status st = PrepareDevice(mode);
-        if (Status::kUnsupport == st && (mode == 4 || mode == 5 || mode == 6) && !f32_split_) {   // (a weight out of fp16's range: see PrepareDevice)
-            mode = PrecisionMode(input, output);
-            st = PrepareDevice(mode);
-        }
-        CHECK_STATUS(st);
-    }
+    Route route;
+    CHECK_STATUS(PrepareRoute(IsHalf(input), IsHalf(output), route));
     Dims4 in, out;
     if (!GetDims4(input, in) || !GetDims4(output, out)) return Status::kErrorShape;
     if (in.c != in_channels_ || out.c != out_channels_ || in.n != out.n) {
@@ -678,91 +687,95 @@ Status Conv2d::Launch(const Tensor& input, const Tensor* residual, Tensor& outpu
         d.has_residual = 1;
         d.res_ld = residual->PixelStride();
     }
-    if (mode == 4) {
-        d.range_flag = range_flag_;
-        int rc;
-        if (up_node_) {
-            if (residual) return Status::kUnsupport;
-            SiConv2dUpsampledSource up;
-            CHECK_STATUS(MakeUpsampledSource(up));
-            rc = si_hip_conv2d_split3_upcat_f32(&d, input.Data<float>(), &up, weight_dev_.As<void>(), use_bias_ ? bias_dev_.As<float>() : nullptr,
-                                                output.Data<float>(), 0, nullptr, 0, Stream());
-        } else
-        rc = si_hip_conv2d_split3_f32(&d, input.Data<float>(), weight_dev_.As<void>(), use_bias_ ? bias_dev_.As<float>() : nullptr,
-                                                residual ? residual->Data<float>() : nullptr, output.Data<float>(), Stream());
-        if (rc != SI_E_UNSUPPORTED) return CheckHip(rc, "conv2d (fp32 by three fp16 products)");
-        // an unaligned / oversized view: the true-fp32 kernels from here on.  (The re-pack uploads weights: inside a hipGraph capture that
-        // fails, and EngineImpl::ForwardAsync then discards the capture and runs the step eagerly.)
+    // An f32_split kernel that refuses the view it is handed (unaligned, strided, oversized) sends the layer to the true-fp32 kernels from here on.
+    // (The re-pack uploads weights: inside a hipGraph capture that fails, and EngineImpl::ForwardAsync then discards the capture and runs the
+    // step eagerly.)
+    const auto or_demote = [&](int rc, const char* what) {
+        if (rc != SI_E_UNSUPPORTED) return CheckHip(rc, what);
         DemoteSplit();
-        d.range_flag = nullptr;
         return Launch(input, residual, output);
+    };
+    switch (route) {
+        case Route::kSplit3:
+            d.range_flag = range_flag_;
+            CHECK_BOOL(Holds(WeightImage::kSplit3));
+            if (up_node_) {
+                if (residual) return Status::kUnsupport;
+                SiConv2dUpsampledSource up;
+                CHECK_STATUS(MakeUpsampledSource(up));
+                return or_demote(si_hip_conv2d_split3_upcat_f32(&d, input.Data<float>(), &up, weight_dev_.As<void>(), Bias(), output.Data<float>(), 0,
+                                                                nullptr, 0, Stream()),
+                                 "conv2d (fp32 by three fp16 products)");
+            }
+            return or_demote(si_hip_conv2d_split3_f32(&d, input.Data<float>(), weight_dev_.As<void>(), Bias(), residual ? residual->Data<float>() : nullptr,
+                                                      output.Data<float>(), Stream()),
+                             "conv2d (fp32 by three fp16 products)");
+        case Route::kWinoSplit:
+            d.range_flag = range_flag_;
+            CHECK_BOOL(Holds(WeightImage::kWino23Split));
+            return or_demote(si_hip_conv2d_wino23_split_f32(&d, input.Data<float>(), weight_dev_.As<void>(), Bias(),
+                                                            residual ? residual->Data<float>() : nullptr, output.Data<float>(), Stream()),
+                             "conv2d (winograd, fp32 by three fp16 products)");
+        case Route::kStemSplit:
+            d.range_flag = range_flag_;
+            CHECK_BOOL(Holds(WeightImage::kStemSplit3));
+            return or_demote(si_hip_conv2d_stem_split3_f32(&d, input.Data<float>(), weight_dev_.As<void>(), Bias(), output.Data<float>(), Stream()),
+                             "conv2d stem (fp32 by three fp16 products)");
+        case Route::kStemF16:
+            CHECK_BOOL(Holds(WeightImage::kStemF16));
+            return CheckHip(si_hip_conv2d_stem_f16(&d, input.Data<float>(), weight_dev_.As<void>(), Bias(), output.RawData(), Stream()),
+                            "conv2d stem (fp16 out)");
+        case Route::kDepthwiseF16:
+            if (residual && !IsHalf(*residual)) return Status::kUnsupport;
+            CHECK_BOOL(Holds(WeightImage::kIgemmF32));
+            return CheckHip(si_hip_conv2d_depthwise_f16(&d, input.RawData(), weight_dev_.As<float>(), Bias(), residual ? residual->RawData() : nullptr,
+                                                        output.RawData(), Stream()),
+                            "conv2d depthwise fp16");
+        case Route::kIgemmF16: {
+            CHECK_BOOL(Holds(WeightImage::kIgemmF16));
+            if (up_node_) {
+                if (residual || !IsHalf(input) || !IsHalf(output)) return Status::kUnsupport;
+                SiConv2dUpsampledSource up;
+                CHECK_STATUS(MakeUpsampledSource(up));
+                return CheckHip(si_hip_conv2d_upcat_f16(&d, input.RawData(), &up, weight_dev_.As<void>(), Bias(), output.RawData(), 0, nullptr, 0, Stream()),
+                                "conv2d fp16 (upsampled source)");
+            }
+            if (residual && !IsHalf(*residual)) return Status::kUnsupport;
+            Tensor xin;
+            CHECK_STATUS(HalfInput(input, xin));
+            d.in_ld = xin.PixelStride();
+            return CheckHip(si_hip_conv2d_f16(&d, xin.RawData(), weight_dev_.As<void>(), Bias(), residual ? residual->RawData() : nullptr,
+                                              output.RawData(), IsHalf(output) ? 0 : 1, Stream()),
+                            "conv2d fp16");
+        }
+        case Route::kWino23F32:
+        case Route::kWino43F32: {
+            const auto fn = route == Route::kWino43F32 ? si_hip_conv2d_wino43_f32 : si_hip_conv2d_wino23_f32;
+            CHECK_BOOL(Holds(ImageFor(route)));   // kWino23F32 / kWino43F32
+            const int rc = fn(&d, input.Data<float>(), weight_dev_.As<float>(), Bias(), residual ? residual->Data<float>() : nullptr,
+                              output.Data<float>(), Stream());
+            if (rc != SI_E_UNSUPPORTED) return CheckHip(rc, "conv2d (winograd)");
+            // an unaligned / oversized tensor view: re-pack for the implicit-GEMM kernel once and stay there
+            algo_ = Algo::kImplicitGemm;
+            device_ready_ = false;
+            CHECK_STATUS(Prepare(WeightImage::kIgemmF32));
+        }
+            [[fallthrough]];
+        case Route::kIgemmF32:
+            CHECK_BOOL(Holds(WeightImage::kIgemmF32));
+            if (up_node_) {
+                if (residual) return Status::kUnsupport;
+                SiConv2dUpsampledSource up;
+                CHECK_STATUS(MakeUpsampledSource(up));
+                return CheckHip(si_hip_conv2d_upcat_f32(&d, input.Data<float>(), &up, weight_dev_.As<float>(), Bias(), output.Data<float>(), 0, nullptr, 0,
+                                                        Stream()),
+                                "conv2d (upsampled source)");
+            }
+            return CheckHip(si_hip_conv2d_f32(&d, input.Data<float>(), weight_dev_.As<float>(), Bias(), residual ? residual->Data<float>() : nullptr,
+                                              output.Data<float>(), Stream()),
+                            "conv2d");
     }
-    if (mode == 5) {
-        d.range_flag = range_flag_;
-        const int rc = si_hip_conv2d_wino23_split_f32(&d, input.Data<float>(), weight_dev_.As<void>(), use_bias_ ? bias_dev_.As<float>() : nullptr,
-                                                      residual ? residual->Data<float>() : nullptr, output.Data<float>(), Stream());
-        if (rc != SI_E_UNSUPPORTED) return CheckHip(rc, "conv2d (winograd, fp32 by three fp16 products)");
-        DemoteSplit();   // an unaligned / oversized view: the true-fp32 kernels from here on
-        return Launch(input, residual, output);
-    }
-    if (mode == 6) {
-        d.range_flag = range_flag_;
-        const int rc = si_hip_conv2d_stem_split3_f32(&d, input.Data<float>(), weight_dev_.As<void>(), use_bias_ ? bias_dev_.As<float>() : nullptr,
-                                                     output.Data<float>(), Stream());
-        if (rc != SI_E_UNSUPPORTED) return CheckHip(rc, "conv2d stem (fp32 by three fp16 products)");
-        DemoteSplit();   // a strided / unaligned image view: the true-fp32 stem kernel from here on
-        return Launch(input, residual, output);
-    }
-    if (mode == 2)
-        return CheckHip(si_hip_conv2d_stem_f16(&d, input.Data<float>(), weight_dev_.As<void>(),
-                                               use_bias_ ? bias_dev_.As<float>() : nullptr, output.RawData(), Stream()),
-                        "conv2d stem (fp16 out)");
-    if (mode == 3) {
-        if (residual && !IsHalf(*residual)) return Status::kUnsupport;
-        return CheckHip(si_hip_conv2d_depthwise_f16(&d, input.RawData(), weight_dev_.As<float>(), use_bias_ ? bias_dev_.As<float>() : nullptr,
-                                                    residual ? residual->RawData() : nullptr, output.RawData(), Stream()),
-                        "conv2d depthwise fp16");
-    }
-    if (mode == 1 && up_node_) {
-        if (residual || !IsHalf(input) || !IsHalf(output)) return Status::kUnsupport;
-        SiConv2dUpsampledSource up;
-        CHECK_STATUS(MakeUpsampledSource(up));
-        return CheckHip(si_hip_conv2d_upcat_f16(&d, input.RawData(), &up, weight_dev_.As<void>(), use_bias_ ? bias_dev_.As<float>() : nullptr,
-                                                output.RawData(), 0, nullptr, 0, Stream()),
-                        "conv2d fp16 (upsampled source)");
-    }
-    if (mode == 1) {
-        if (residual && !IsHalf(*residual)) return Status::kUnsupport;
-        Tensor xin;
-        CHECK_STATUS(HalfInput(input, xin));
-        d.in_ld = xin.PixelStride();
-        return CheckHip(si_hip_conv2d_f16(&d, xin.RawData(), weight_dev_.As<void>(), use_bias_ ? bias_dev_.As<float>() : nullptr,
-                                          residual ? residual->RawData() : nullptr, output.RawData(), IsHalf(output) ? 0 : 1,
-                                          Stream()),
-                        "conv2d fp16");
-    }
-    if (use_winograd_) {
-        const auto fn = wino_tile_ == 4 ? si_hip_conv2d_wino43_f32 : si_hip_conv2d_wino23_f32;
-        const int rc = fn(&d, input.Data<float>(), weight_dev_.As<float>(), use_bias_ ? bias_dev_.As<float>() : nullptr,
-                          residual ? residual->Data<float>() : nullptr, output.Data<float>(), Stream());
-        if (rc != SI_E_UNSUPPORTED) return CheckHip(rc, "conv2d (winograd)");
-        // an unaligned / oversized tensor view: re-pack for the implicit-GEMM kernel once and stay there
-        algo_ = Algo::kImplicitGemm;
-        device_ready_ = false;
-        CHECK_STATUS(PrepareDevice(0));
-    }
-    if (up_node_) {
-        if (residual) return Status::kUnsupport;
-        SiConv2dUpsampledSource up;
-        CHECK_STATUS(MakeUpsampledSource(up));
-        return CheckHip(si_hip_conv2d_upcat_f32(&d, input.Data<float>(), &up, weight_dev_.As<float>(), use_bias_ ? bias_dev_.As<float>() : nullptr,
-                                                output.Data<float>(), 0, nullptr, 0, Stream()),
-                        "conv2d (upsampled source)");
-    }
-    return CheckHip(si_hip_conv2d_f32(&d, input.Data<float>(), weight_dev_.As<float>(),
-                                      use_bias_ ? bias_dev_.As<float>() : nullptr,
-                                      residual ? residual->Data<float>() : nullptr, output.Data<float>(), Stream()),
-                    "conv2d");
+    return Status::kFail;
 }
 
 bool Conv2d::CanReadUpsampled(int c0, int c) const {
@@ -817,41 +830,39 @@ Status Conv2d::MakeUpsampledSource(SiConv2dUpsampledSource& up) const {
 // Detect-head variant: device tensors only (called by YoloDetect inside its own RunOnDevice scope)
 Status Conv2d::ForwardYolo(const Tensor& input, const SiYoloLevel& level, const float* grid_dev, const float* anchor_dev,
                            Tensor& detect_out) {
-    // (f32_split: the Detect levels take the three-fp16-products kernel too -- YOLOv5s batch 32: 147 -> 118, 64 -> 43, 33 -> 26 us per
-    // level, +3 % on the network; profiles/r05_f32_split_detect.txt)
-    int mode = IsHalf(input) ? 1 : ((f32_split_ && in_channels_ % 64 == 0 && in_channels_ >= kSplit3DetectMinChannels && out_channels_ > 64) ? 4 : 0);
-    {
-        Status st = PrepareDevice(mode);
-        if (Status::kUnsupport == st && mode == 4 && !f32_split_) {   // (a weight out of fp16's range)
-            mode = 0;
-            st = PrepareDevice(mode);
-        }
-        CHECK_STATUS(st);
-    }
+    Route route;
+    CHECK_STATUS(PrepareRoute(IsHalf(input), false, route, true));   // (its own choice: YoloRoute)
     Dims4 in;
     if (!GetDims4(input, in) || in.c != in_channels_) return Status::kErrorShape;
     if (input.GetMemoryType() != MemoryType::kDevice || detect_out.GetMemoryType() != MemoryType::kDevice) return Status::kUnsupport;
     Tensor conv_out(DataType::kFloat32, {in.n, in.h, in.w, out_channels_}, MemoryType::kDevice, false);  // shape only
     SiConv2dDesc d = MakeDesc(input, conv_out);
     d.act1 = d.act2 = SI_ACT_NONE;
-    if (mode == 4) {
-        d.range_flag = range_flag_;
-        const int rc = si_hip_conv2d_split3_yolo_f32(&d, input.Data<float>(), weight_dev_.As<void>(), use_bias_ ? bias_dev_.As<float>() : nullptr,
-                                                     &level, grid_dev, anchor_dev, detect_out.Data<float>(), Stream());
-        if (rc != SI_E_UNSUPPORTED) return CheckHip(rc, "conv2d+yolo (fp32 by three fp16 products)");
-        DemoteSplit();   // an unaligned view: the true-fp32 kernel from here on
-        return ForwardYolo(input, level, grid_dev, anchor_dev, detect_out);
+    switch (route) {
+        case Route::kSplit3: {
+            d.range_flag = range_flag_;
+            CHECK_BOOL(Holds(WeightImage::kSplit3));
+            const int rc = si_hip_conv2d_split3_yolo_f32(&d, input.Data<float>(), weight_dev_.As<void>(), Bias(), &level, grid_dev, anchor_dev,
+                                                         detect_out.Data<float>(), Stream());
+            if (rc != SI_E_UNSUPPORTED) return CheckHip(rc, "conv2d+yolo (fp32 by three fp16 products)");
+            DemoteSplit();   // an unaligned view: the true-fp32 kernel from here on
+            return ForwardYolo(input, level, grid_dev, anchor_dev, detect_out);
+        }
+        case Route::kIgemmF16: {
+            CHECK_BOOL(Holds(WeightImage::kIgemmF16));
+            const int rc = si_hip_conv2d_yolo_f16(&d, input.RawData(), weight_dev_.As<void>(), Bias(), &level, grid_dev, anchor_dev,
+                                                  detect_out.Data<float>(), Stream());
+            if (rc == SI_E_UNSUPPORTED) return Status::kUnsupport;
+            return CheckHip(rc, "conv2d+yolo fp16");
+        }
+        default: {
+            CHECK_BOOL(Holds(WeightImage::kIgemmF32));
+            const int rc = si_hip_conv2d_yolo_f32(&d, input.Data<float>(), weight_dev_.As<float>(), Bias(), &level, grid_dev, anchor_dev,
+                                                  detect_out.Data<float>(), Stream());
+            if (rc == SI_E_UNSUPPORTED) return Status::kUnsupport;
+            return CheckHip(rc, "conv2d+yolo");
+        }
     }
-    if (mode == 1) {
-        const int rc = si_hip_conv2d_yolo_f16(&d, input.RawData(), weight_dev_.As<void>(), use_bias_ ? bias_dev_.As<float>() : nullptr,
-                                              &level, grid_dev, anchor_dev, detect_out.Data<float>(), Stream());
-        if (rc == SI_E_UNSUPPORTED) return Status::kUnsupport;
-        return CheckHip(rc, "conv2d+yolo fp16");
-    }
-    const int rc = si_hip_conv2d_yolo_f32(&d, input.Data<float>(), weight_dev_.As<float>(), use_bias_ ? bias_dev_.As<float>() : nullptr,
-                                          &level, grid_dev, anchor_dev, detect_out.Data<float>(), Stream());
-    if (rc == SI_E_UNSUPPORTED) return Status::kUnsupport;
-    return CheckHip(rc, "conv2d+yolo");
 }
 
 Status Conv2d::Forward(const Tensor& input, Tensor& output) {
@@ -873,19 +884,21 @@ const char* Conv2d::KernelName() const {
     if (pw_producer_) return in_channels_ <= 64 ? "conv_pw_patch_f16_kernel<pw + 3x3>" : "conv3x3s1_slab_f16_kernel<pw + 3x3>";
     SiConv2dDesc d = MakeDesc(in, out);
     if (sibling_) d.oc += sibling_->out_channels_;
-    const int mode = PrecisionMode(in, out);
-    if (mode == 1) {
-        const char* name = si_hip_conv2d_f16_kernel_name(&d, up_node_ ? 1 : 0);   // the tile follows the launch size (round 4)
-        return name && name[0] ? name : "conv_igemm_f16_kernel";
+    switch (RouteFor(IsHalf(in), IsHalf(out))) {   // the route Launch will take
+        case Route::kIgemmF16: {
+            const char* name = si_hip_conv2d_f16_kernel_name(&d, up_node_ ? 1 : 0);   // the tile follows the launch size (round 4)
+            return name && name[0] ? name : "conv_igemm_f16_kernel";
+        }
+        case Route::kStemF16: return "conv_stem_f16_kernel";
+        case Route::kDepthwiseF16: return "conv_depthwise_f16_kernel<2>";
+        case Route::kSplit3: return "conv_split3_f32_kernel";
+        case Route::kWinoSplit: return "conv_wino23s_kernel";
+        case Route::kStemSplit: return "conv_stem_split_f32_kernel";
+        case Route::kWino43F32: return "conv_wino43_kernel";
+        case Route::kWino23F32: return "conv_wino23_kernel";
+        case Route::kIgemmF32: return si_hip_conv2d_kernel_name_form(&d, in.Data<float>(), up_node_ ? 1 : 0);
     }
-    if (mode == 2) return "conv_stem_f16_kernel";
-    if (mode == 3) return "conv_depthwise_f16_kernel<2>";
-    if (mode == 4) return "conv_split3_f32_kernel";
-    if (mode == 5) return "conv_wino23s_kernel";
-    if (mode == 6) return "conv_stem_split_f32_kernel";
-    const int tile = WinogradTile(d);
-    if (tile) return tile == 4 ? "conv_wino43_kernel" : "conv_wino23_kernel";
-    return si_hip_conv2d_kernel_name_form(&d, in.Data<float>(), up_node_ ? 1 : 0);
+    return "conv_igemm_f32";
 }
 
 // 0 = implicit GEMM, 2 = fused Winograd F(2,3), 4 = fused Winograd F(4,3) for this layer's static shape
@@ -945,11 +958,8 @@ bool Conv2d::HalfStorageOk(std::string& why) const {
     const Tensor& out = output_tensor_nodes_[0]->tensor;
     if (!IsHalf(in) && !IsHalf(out)) return true;
     if (stem_producer_ || pw_producer_ || stem_pair_ || cv3_pair_) return true;   // (asked of the kernel when the pair was fused: CanFuseStemProducer / CanFusePointwiseProducer)
-    SiConv2dDesc d;
-    memset(&d, 0, sizeof(d));
-    d.ic = in_channels_; d.oc = out_channels_; d.kh = kernel_h_; d.kw = kernel_w_; d.groups = groups_;
-    d.sh = stride_h_; d.sw = stride_w_; d.dh = dilation_h_; d.dw = dilation_w_; d.pt = padding_t_; d.pl = padding_l_;
-    // (2 is the stem kernel, which reads an fp32 image: PrecisionMode takes it under exactly these conditions, and a stem shape has no other fp16 kernel --
+    const SiConv2dDesc d = StaticDesc();
+    // (2 is the stem kernel, which reads an fp32 image: RouteFor takes it under exactly these conditions, and a stem shape has no other fp16 kernel --
     // behind a half producer, an explicit pad in front of a generator's 7x7 stem for one, the layer runs in fp32 between casts)
     const int kind = si_hip_conv2d_f16_supported(&d);
     if (2 == kind ? (!IsHalf(in) && !residual_node_ && !sibling_) : 0 != kind) return true;

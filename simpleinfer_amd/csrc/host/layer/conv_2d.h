@@ -1,7 +1,23 @@
 // layer/conv_2d.h -- nn.Conv2d on the MI355X.  Public configuration fields keep the reference's
-// names (src/layer/conv_2d.h:39-57) so layer tests that poke them still read the same; the three
-// CPU paths (Winograd23 / im2col / grouped im2col, src/layer/conv_2d.cpp:108-118) collapse into one
-// implicit-GEMM MFMA kernel (si_hip_conv2d_f32) with bias / activation / residual in its epilogue.
+// names (src/layer/conv_2d.h:39-57) so layer tests that poke them still read the same.
+//
+// The host side is two decisions.  The ROUTE is the kernel family that serves an (input, output) storage pair (RouteFor); the WEIGHT IMAGE
+// is the packed form of the filters that family reads (ImageFor, packed by Prepare from one table row per image).  weight_dev_ holds
+// image_, and every launch states the image it needs before it hands weight_dev_ to a kernel.
+//
+//   route           storage       kernel family                                        weight image
+//   kIgemmF32       fp32 -> fp32  implicit GEMM on the fp32 matrix cores               kIgemmF32 (the sibling's image appended)
+//   kWino23F32      fp32 -> fp32  fused Winograd F(2,3)                                kWino23F32
+//   kWino43F32      fp32 -> fp32  fused Winograd F(4,3)                                kWino43F32
+//   kIgemmF16       any half      fp16 implicit GEMM (an fp32 input is converted)      kIgemmF16 (one conv over this | sibling)
+//   kStemF16        fp32 -> half  the RGB stem, fp32 image in                          kStemF16
+//   kDepthwiseF16   half -> half  depthwise                                            kIgemmF32 (fp32 weights, the fp32 depthwise layout)
+//   kSplit3         fp32 -> fp32  f32_split: implicit GEMM by three fp16 products      kSplit3 (one conv over this | sibling)
+//   kWinoSplit      fp32 -> fp32  f32_split: the fused Winograd F(2,3) kernel's form   kWino23Split
+//   kStemSplit      fp32 -> fp32  f32_split: the RGB stem's form                       kStemSplit3
+//
+// The producer fusions (SetStemProducer, SetPointwiseProducer, SetStemPairProducer, SetCv3Pair) are fp16 launches of their own over the
+// kIgemmF16 / kStemF16 images of the layers they join.  Bias, activation and residual are in every kernel's epilogue.
 #ifndef SIMPLE_INFER_SRC_LAYER_CONV_2D_H_
 #define SIMPLE_INFER_SRC_LAYER_CONV_2D_H_
 
@@ -98,10 +114,13 @@ public:
     void SetCv3Pair(Conv2d* pair, TensorNode* z);
     Conv2d* Cv3Pair() const { return cv3_pair_; }
 
-    Status PrepareDevice(int mode = 0);
-    Status PrepareDeviceHalf(const SiConv2dDesc& d);
-    int PrecisionMode(const Tensor& input, const Tensor& output) const;
-    Status HalfInput(const Tensor& input, Tensor& half);
+    // the kernel family of a launch.  use_winograd_ / wino_tile_ follow from it (Prepare)
+    enum class Route { kIgemmF32 = 0, kWino23F32, kWino43F32, kIgemmF16, kStemF16, kDepthwiseF16, kSplit3, kWinoSplit, kStemSplit };
+    // what the layer would do, as plain numbers and without a device (tests/cpp/test_conv_route.cpp): the route serving a storage pair /
+    // ForwardYolo's own choice, the weight image it reads and its Winograd tile
+    struct RouteInfo { int route, image, wino_tile; };
+    RouteInfo DescribeRoute(bool in_half, bool out_half) const { return Describe(RouteFor(in_half, out_half)); }
+    RouteInfo DescribeYoloRoute(bool in_half) const { return Describe(YoloRoute(in_half)); }
 
     // conv + YOLOv5 decode epilogue, writing into the Detect output (kUnsupport: shape not eligible)
     Status ForwardYolo(const Tensor& input, const SiYoloLevel& level, const float* grid_dev, const float* anchor_dev,
@@ -142,11 +161,8 @@ public:
     void DemoteSplit() { f32_split_ = false; split_demoted_ = true; device_ready_ = false; }
     // kernel-form choices handed to every launch of this layer (engine options f32_tile, f16_slab, ...; SiConvPlan in include/si_hip.h)
     void SetPlan(const SiConvPlan& plan) { plan_ = plan; has_plan_ = true; }
-    bool UseSplit3() const;
-    bool UseStemSplit() const;   // ... the RGB stem on the split form of the fp16 stem kernel (si_hip_conv2d_stem_split3_f32; level 4)
-    bool UseWinoSplit() const;   // ... and the Winograd layers on the split form of the fused Winograd kernel (si_hip_conv2d_wino23_split_f32)
     bool prefer_wino43_ = false;  // kAuto: take F(4,3) instead of F(2,3) wherever F(2,3) would have been chosen
-    bool use_winograd_ = false;  // resolved at PrepareDevice (same name as the reference's flag, conv_2d.h:60)
+    bool use_winograd_ = false;  // resolved at Prepare (same name as the reference's flag, conv_2d.h:60)
     int wino_tile_ = 0;          // 2 = F(2,3), 4 = F(4,3) when use_winograd_
 
     // fused epilogue
@@ -169,6 +185,26 @@ public:
     float up_scale_h_ = 1.0f, up_scale_w_ = 1.0f;
 
 private:
+    // which packed form of the filters weight_dev_ holds
+    enum class WeightImage { kNone = 0, kIgemmF32, kWino23F32, kWino43F32, kIgemmF16, kStemF16, kSplit3, kWino23Split, kStemSplit3 };
+    struct ImageRow;
+    static const ImageRow& RowOf(WeightImage image);
+    static WeightImage ImageFor(Route route);
+    static int TileOf(WeightImage image) { return image == WeightImage::kWino43F32 ? 4 : (image == WeightImage::kWino23F32 ? 2 : 0); }
+    static RouteInfo Describe(Route r) { return {(int)r, (int)ImageFor(r), TileOf(ImageFor(r))}; }
+    Route RouteFor(bool in_half, bool out_half) const;
+    Route YoloRoute(bool in_half) const;
+    // f32_split, per layer: the dense layers where the split implicit GEMM is faster; the RGB stem on the split form of the fp16 stem kernel
+    // (si_hip_conv2d_stem_split3_f32; level 4); the Winograd layers on the split form of the fused Winograd kernel (si_hip_conv2d_wino23_split_f32)
+    bool UseSplit3() const;
+    bool UseStemSplit() const;
+    bool UseWinoSplit() const;
+    Status Prepare(WeightImage image);
+    Status PrepareRoute(bool in_half, bool out_half, Route& route, bool yolo = false);
+    bool Holds(WeightImage need) const;
+    Status HalfInput(const Tensor& input, Tensor& half);
+    SiConv2dDesc StaticDesc(int extra_oc = 0) const;
+    const float* Bias() const { return use_bias_ ? bias_dev_.As<float>() : nullptr; }
     Status Launch(const Tensor& input, const Tensor* residual, Tensor& output);
     Status LaunchStemTriple(const Tensor& image, Tensor& out0, Tensor* out1);
     Status LaunchCv3(const Tensor& x, Tensor& output);
@@ -180,7 +216,7 @@ private:
     DeviceBuffer weight_dev_;
     DeviceBuffer bias_dev_;
     bool device_ready_ = false;
-    int prepared_mode_ = 0;      // which weight image weight_dev_ holds (see PrepareDevice)
+    WeightImage image_ = WeightImage::kNone;   // what weight_dev_ holds once device_ready_ (see Prepare)
     Tensor in_half_;             // fp16 copy of an fp32 input consumed by the fp16 kernel
     Tensor pw_scratch_;          // the fused-away 1x1 conv's output, when the fused launch refuses the views it is handed (Launch)
 };

@@ -195,6 +195,42 @@ def test_f32_split_weights_out_of_range_keep_the_layer_in_fp32(si, tmp_path):
     assert sch["split_reruns"] == 0 and sch["split_demoted"] == ["conv_0"], sch
 
 
+def test_winograd_layers_fall_back_when_the_kernel_refuses_their_input_view(si, tmp_path):
+    """The fused Winograd kernels (fp32 and its f32_split form) read 16-byte vectors: they refuse an input whose pixel stride is no multiple of
+    four floats.  Here conv_0's output is written in place into cat(conv_0, conv_1, conv_2) -- 32 + 3 + 32 channels, a pixel stride of 67
+    floats -- and conv_2, a 32 -> 32 3x3 stride-1 conv that the Winograd kernel would otherwise serve, reads it there.  The layer re-packs for
+    the implicit-GEMM kernel once and stays there: the bits of an engine that never used Winograd.  With f32_split the split form refuses the
+    view first, the layer is demoted, and the result is the default engine's."""
+    mg = si.modelgen
+    b = mg.PnnxBuilder(seed=5)
+    x = b.input((2, 32, 13, 11))
+    p = b.silu(b.conv(x, 32, 1, 1))
+    y = b.conv(x, 3, 1, 1)          # 3: the concat's rows are 67 floats, not a whole number of 16-byte vectors
+    a = b.silu(b.conv(p, 32, 3, 1))
+    b.output(b.cat([p, y, a]))
+    pp, bp = _save(tmp_path, b, "winoview")
+    xin = mg.synth_input((2, 13, 11, 32))
+
+    def conv2_kernel(e):
+        (k,) = [L["kernel"] for L in e.profile() if L["name"] == "conv_2"]
+        return k
+
+    e0, oname, want = _run(si, pp, bp, xin, winograd=0)
+    assert e0.schedule()["alias"], e0.schedule()     # conv_0 really writes into the concat output
+    e1, _, got = _run(si, pp, bp, xin)
+    print("conv_2: winograd=0 [%s], default [%s]" % (conv2_kernel(e0), conv2_kernel(e1)))
+    assert_exact(got, want, "a Winograd layer on a view the kernel refuses vs winograd=0")
+    assert "wino" not in conv2_kernel(e1) and conv2_kernel(e1) == conv2_kernel(e0)
+    e1.forward()
+    assert_exact(e1.extract(oname), want, "the second step, on the re-packed weights")
+    e2, _, got2 = _run(si, pp, bp, xin, f32_split=1)
+    sch = e2.schedule()
+    print("f32_split: conv_2 [%s], schedule %s" % (conv2_kernel(e2), {k: sch[k] for k in ("split_reruns", "split_demoted")}))
+    assert_exact(got2, got, "f32_split on the same view vs the default engine")
+    assert sch["split_reruns"] == 0 and sch["split_demoted"] == ["conv_2"], sch
+    assert "wino" not in conv2_kernel(e2) and "split" not in conv2_kernel(e2)
+
+
 def test_f32_split_range_guard_in_a_whole_network(si, tmp_path):
     """YOLOv5s with one input pixel at 1e6: the stem's output overflows fp16 in front of the first split layer; every split layer downstream of
     it sees non-finite operands in that pass, all of them go back to true fp32 in ONE re-run, and the caller's result is the default engine's.
