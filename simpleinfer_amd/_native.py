@@ -149,6 +149,12 @@ class SiRoiAlignDesc(C.Structure):
         ("spatial_scale", C.c_float)]
 
 
+class SiRnnDesc(C.Structure):
+    """include/si_rnn.h; st / sb: element strides of the time index and of the batch index of x, the gate workspace and y"""
+    _fields_ = [(k, C.c_int) for k in ("cell", "t", "batch", "input", "hidden", "dirs")] + [
+        (k, C.c_longlong) for k in ("x_st", "x_sb", "g_st", "g_sb", "y_st", "y_sb")] + [("step0", C.c_int)]
+
+
 class SiLayoutNest(C.Structure):
     """include/si_layout.h; what si_layout_plan returns: view != 0, or the loop nest of the copy"""
     _fields_ = [("view", C.c_int), ("rank", C.c_int), ("dims", C.c_int * 8), ("in_stride", C.c_longlong * 8)]
@@ -408,9 +414,18 @@ def hip():
         "si_hip_roi_align_f16": (i, [C.POINTER(SiRoiAlignDesc), vp, vp, vp, vp]),
         "si_hip_roi_align_kernel_name": (C.c_char_p, [C.POINTER(SiRoiAlignDesc), vp, vp, vp, i]),
     }
+    # include/si_rnn.h: the recurrent step kernel of nn.LSTM / nn.GRU
+    rnn_ = {
+        "si_hip_rnn_layer_f32": (i, [C.POINTER(SiRnnDesc), vp, vp, vp, vp, vp, vp, vp, vp]),
+        "si_hip_rnn_layer_f16": (i, [C.POINTER(SiRnnDesc), vp, vp, vp, vp, vp, vp, vp, vp]),
+        "si_hip_rnn_workspace_bytes": (sz, [C.POINTER(SiRnnDesc), i, i]),
+        "si_hip_rnn_pack_whh_f32": (i, [C.POINTER(SiRnnDesc), vp, vp]),
+        "si_hip_rnn_pack_whh_f16": (i, [C.POINTER(SiRnnDesc), vp, vp]),
+        "si_hip_rnn_kernel_name": (C.c_char_p, [C.POINTER(SiRnnDesc), vp, vp, i]),
+    }
     for name, (res, args) in (list(sig.items()) + list(norm.items()) + list(pad.items()) + list(pool.items()) + list(softmax.items()) +
                               list(superres.items()) + list(slice_.items()) + list(reduce_.items()) + list(act.items()) + list(permute_.items()) +
-                              list(attention_.items()) + list(deform_.items()) + list(grid_.items()) + list(roi_.items())):
+                              list(attention_.items()) + list(deform_.items()) + list(grid_.items()) + list(roi_.items()) + list(rnn_.items())):
         fn = getattr(L, name)  # AttributeError here = header/library mismatch, which tests check
         fn.restype = res
         fn.argtypes = args
@@ -428,6 +443,7 @@ def hip():
     L._si_deform_signatures = deform_
     L._si_grid_signatures = grid_
     L._si_roi_signatures = roi_
+    L._si_rnn_signatures = rnn_
     _hip = L
     return L
 

@@ -59,9 +59,14 @@ inline std::map<const pnnx::Operand*, int> FollowBatchAxes(const std::vector<pnn
             auto it = batch_axis.find(in);
             if (it != batch_axis.end() && it->second >= 0) { src = in; axis = it->second; break; }
         }
+        const bool recurrent = op->type == "nn.LSTM" || op->type == "nn.GRU";
         for (const pnnx::Operand* out : op->outputs) {
             if (op->inputs.empty()) batch_axis[out] = (!out->shape.empty() && out->shape[0] == file_batch) ? 0 : -1;
-            else batch_axis[out] = src ? FollowBatchAxis(op, src->shape, axis, out->shape, file_batch) : -1;
+            else if (recurrent && src) {
+                // y keeps the input's batch dimension; the state outputs [layers * dirs, N, H] carry it in dimension 1 whatever batch_first says
+                const int to = out == op->outputs[0] ? axis : 1;
+                batch_axis[out] = (out->shape.size() == 3 && to < 3 && out->shape[to] == file_batch) ? to : -1;
+            } else batch_axis[out] = src ? FollowBatchAxis(op, src->shape, axis, out->shape, file_batch) : -1;
         }
     }
     return batch_axis;
@@ -98,6 +103,7 @@ enum class BatchFamily {
     kReshape,       // reshape / view / flatten / squeeze / unsqueeze / contiguous: per-image while the batch stays a dimension of its own
     kAttention,     // nn.MultiheadAttention: reads the batch from dimension 0 (batch_first) or 1
     kRoi,           // torchvision.ops.RoIAlign / roi_align: boxes [K, 5] that name their image by an index in the data -- never per-image
+    kRecurrent,     // nn.LSTM / nn.GRU: reads the batch from dimension 0 (batch_first) or 1; y keeps it there, the state outputs carry it in 1
 };
 
 // why an operator of the family kRoi is never per-image (also the engine's reason for refusing to re-batch a graph that holds one)
@@ -188,6 +194,8 @@ inline BatchFamily BatchFamilyOf(const std::string& type) {
         {"nn.MultiheadAttention", BatchFamily::kAttention},
         {"torchvision.ops.RoIAlign", BatchFamily::kRoi},
         {"torchvision.ops.roi_align", BatchFamily::kRoi},
+        {"nn.LSTM", BatchFamily::kRecurrent},
+        {"nn.GRU", BatchFamily::kRecurrent},
     };
     auto it = table.find(type);
     return it == table.end() ? BatchFamily::kUnknown : it->second;
@@ -332,6 +340,17 @@ inline bool PerImageOperator(const pnnx::Operator* op, const std::vector<BatchOp
             }
             break;
         }
+        case BatchFamily::kRecurrent: {
+            bool batch_first = false;
+            Get(op, "batch_first", batch_first);
+            const int want = batch_first ? 0 : 1;
+            if (axis != want) {
+                why = op->type + " with batch_first=" + (batch_first ? "True" : "False") + " reads the batch from " + dim_text(want) +
+                      ", but its input carries it in " + dim_text(axis);
+                return false;
+            }
+            break;
+        }
         default:   // kElementwise, kBinary, kMove, kReshape: what is left is where the batch ends up, below
             break;
     }
@@ -343,8 +362,12 @@ inline bool PerImageOperator(const pnnx::Operator* op, const std::vector<BatchOp
             return false;
         }
         const bool moves = family == BatchFamily::kMove || family == BatchFamily::kReshape || family == BatchFamily::kReduce;
-        if (!moves && out[i].axis != axis) {
-            why = "output " + std::to_string(i) + " carries the batch in " + dim_text(out[i].axis) + ", the input in " + dim_text(axis);
+        // (a recurrent operator's state outputs [layers * dirs, N, H] carry the batch in dimension 1 whatever its input does)
+        const bool state = family == BatchFamily::kRecurrent && i > 0;
+        const int expect = state ? 1 : axis;
+        if (!moves && out[i].axis != expect) {
+            why = "output " + std::to_string(i) + " carries the batch in " + dim_text(out[i].axis) +
+                  (state ? ", a state output in " + dim_text(expect) : ", the input in " + dim_text(axis));
             return false;
         }
     }

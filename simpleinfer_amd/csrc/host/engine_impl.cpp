@@ -209,16 +209,29 @@ Status EngineImpl::CreateTensorNodes() {
     if (file_batch > 0) {
         batch_axis = FollowBatchAxes(graph_->ops, file_batch);   // (batch_rule.h: the rule for the split modes follows the same axes)
         for (const pnnx::Operator* op : graph_->ops) {
-            if (op->type == "nn.MultiheadAttention") {
+            const bool recurrent = BatchFamilyOf(op->type) == BatchFamily::kRecurrent;
+            bool batch_first = false;
+            Get(op, "batch_first", batch_first);
+            if (op->type == "nn.MultiheadAttention" || recurrent) {
                 // the layer reads the batch from dimension 0 (batch_first) or 1 of its operands: the rewrite has to have reached that one
-                bool batch_first = false;
-                Get(op, "batch_first", batch_first);
                 for (const pnnx::Operand* in : op->inputs) {
                     auto it = batch_axis.find(in);
                     if (it == batch_axis.end() || it->second != (batch_first ? 0 : 1)) {
-                        LOG(ERROR) << "re-batch: [" << op->name << "] nn.MultiheadAttention with batch_first=" << (batch_first ? "True" : "False")
+                        LOG(ERROR) << "re-batch: [" << op->name << "] " << op->type << " with batch_first=" << (batch_first ? "True" : "False")
                                    << " reads the batch from dimension " << (batch_first ? 0 : 1) << " of operand [" << in->name
                                    << "], which the graph does not carry there from a batch-major graph input: served at the file's batch only";
+                        return Status::kUnsupport;
+                    }
+                }
+            }
+            if (recurrent) {
+                // ... and every output has to be followed: y in the input's batch dimension, the state outputs [layers * dirs, N, H] in 1.  One
+                // that is not would keep the file's batch in its shape while the layer writes the new one
+                for (size_t i = 0; i < op->outputs.size(); ++i) {
+                    auto it = batch_axis.find(op->outputs[i]);
+                    if (it == batch_axis.end() || it->second != (i == 0 && batch_first ? 0 : 1)) {
+                        LOG(ERROR) << "re-batch: [" << op->name << "] " << op->type << ": the batch dimension of output " << i << " [" << op->outputs[i]->name
+                                   << "] cannot be followed, so its shape would keep the file's batch: served at the file's batch only";
                         return Status::kUnsupport;
                     }
                 }

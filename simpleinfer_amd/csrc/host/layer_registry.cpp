@@ -34,6 +34,7 @@ SI_DECLARE_LAYER(PixelShuffle)
 SI_DECLARE_LAYER(PReLU)
 SI_DECLARE_LAYER(Reduce)
 SI_DECLARE_LAYER(ReLU)
+SI_DECLARE_LAYER(Rnn)
 SI_DECLARE_LAYER(RoiAlign)
 SI_DECLARE_LAYER(Sigmoid)
 SI_DECLARE_LAYER(SiLU)
@@ -63,7 +64,8 @@ static std::map<std::string, LayerRegistryEntry>& Table() {
     // (layer/multihead_attention.h: two projections around the fused attention kernel of include/si_attention.h); torchvision.ops.DeformConv2d
     // (layer/deform_conv_2d.h: DCNv1 / DCNv2 in one launch of include/si_deform.h; the type string is the one pnnx writes for the module);
     // F.grid_sample and F.affine_grid (layer/grid_sample.h, layer/affine_grid.h: the sampler and the tiny grid kernel of include/si_grid.h);
-    // torchvision.ops.RoIAlign / torchvision.ops.roi_align (one class, layer/roi_align.h: the box-pooling kernel of include/si_roi.h)
+    // torchvision.ops.RoIAlign / torchvision.ops.roi_align (one class, layer/roi_align.h: the box-pooling kernel of include/si_roi.h);
+    // nn.LSTM / nn.GRU (one class with a cell kind, layer/rnn.h: the input projection and the recurrent step kernel of include/si_rnn.h)
     static std::map<std::string, LayerRegistryEntry> table = {
         SI_ENTRY("nn.AdaptiveAvgPool2d", AdaptiveAvgPool2d),
         SI_ENTRY("nn.AvgPool2d", AvgPool2d),
@@ -144,6 +146,8 @@ static std::map<std::string, LayerRegistryEntry>& Table() {
         SI_ENTRY("F.affine_grid", AffineGrid),
         SI_ENTRY("torchvision.ops.RoIAlign", RoiAlign),
         SI_ENTRY("torchvision.ops.roi_align", RoiAlign),
+        SI_ENTRY("nn.LSTM", Rnn),
+        SI_ENTRY("nn.GRU", Rnn),
     };
     return table;
 }

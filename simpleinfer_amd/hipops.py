@@ -1285,6 +1285,145 @@ def attention_kernel_name(d, half=False, heads=1, align=256) -> str:
     return _native.hip().si_hip_attention_kernel_name(C.byref(dsc), p[0], p[1], p[2], p[3], 1 if half else 0).decode()
 
 
+RNN_CELLS = {"lstm": 0, "gru": 1}
+RNN_GATES = {"lstm": 4, "gru": 3}
+
+
+def rnn_desc(cell, t, batch, input_size, hidden, dirs, batch_first=False, x_ld=None, g_ld=None, y_ld=None, step0=0):
+    """SiRnnDesc (include/si_rnn.h) of x [T, N, I] (seq-first) or [N, T, I] (batch_first), the gate workspace [.., dirs * G * H] and y
+    [.., dirs * H], whose rows are x_ld / g_ld / y_ld elements apart (default: dense).  cell: "lstm" / "gru" or the code"""
+    code = RNN_CELLS[cell] if isinstance(cell, str) else int(cell)
+    gates = 3 if code == 1 else 4
+
+    def strides(ld):
+        ld = int(ld)
+        return (ld, int(t) * ld) if batch_first else (int(batch) * ld, ld)
+
+    d = _native.SiRnnDesc()
+    d.cell, d.t, d.batch, d.input, d.hidden, d.dirs, d.step0 = code, int(t), int(batch), int(input_size), int(hidden), int(dirs), int(step0)
+    (d.x_st, d.x_sb), (d.g_st, d.g_sb) = strides(x_ld or input_size), strides(g_ld or dirs * gates * hidden)
+    d.y_st, d.y_sb = strides(y_ld or dirs * hidden)
+    return d
+
+
+def rnn_pack_whh(d, w_hh, half=False) -> np.ndarray:
+    """si_hip_rnn_pack_whh_f32 / _f16: w_hh fp32 [dirs, G * H, H] -> the step kernel's image (floats, or halves)"""
+    H = _native.hip()
+    w_hh = _f32(w_hh)
+    nbytes = H.si_hip_rnn_workspace_bytes(C.byref(d), 2, 1 if half else 0)
+    if nbytes == 0:
+        raise HipError("no %s step kernel for this descriptor" % ("fp16" if half else "fp32"))
+    image = np.zeros(nbytes // (2 if half else 4), np.float16 if half else np.float32)
+    name = "si_hip_rnn_pack_whh_f16" if half else "si_hip_rnn_pack_whh_f32"
+    _chk(getattr(H, name)(C.byref(d), w_hh.ctypes.data_as(C.c_void_p), image.ctypes.data_as(C.c_void_p)), name)
+    return image
+
+
+def rnn_layer(cell, gates, w_hh, b_hn=None, batch_first=False, want_state=False, input_size=8, g_ld=None, g_c_off=0, g_fill=0.0, out_ld=None,
+              out_c_off=0, out_fill=0.0, full=False, c_fill=ByteFill(0xFF), step0=0, resume=None, return_c=False):
+    """si_hip_rnn_layer_f32 / _f16 (by the gates' dtype): stages 2 and 3 of one layer on the projected gates [T, N, dirs * G * H] (seq-first) or
+    [N, T, ..] (batch_first); w_hh fp32 [dirs, G * H, H]; b_hn fp32 [dirs, H] (GRU) or None.  The view hooks are the common ones, on the gates
+    (g_*) and on y (out_*).  The c buffer starts as c_fill -- NaN bytes by default: the first step must not read it.  resume = (y, c): the
+    dense y and the c buffer a call with step0 = 0 .. s - 1 left, to continue from step0 = s.  Returns y, with want_state (y, h_n, c_n) /
+    (y, h_n); return_c appends the fp32 c buffer."""
+    H = _native.hip()
+    gates = _float_storage(gates)
+    half = gates.dtype == np.float16
+    w_hh = _f32(w_hh)
+    dirs, gh, hidden = w_hh.shape
+    ng = RNN_GATES[cell]
+    assert gates.ndim == 3 and gh == ng * hidden and gates.shape[2] == dirs * gh, (gates.shape, w_hh.shape)
+    batch, t = (gates.shape[0], gates.shape[1]) if batch_first else (gates.shape[1], gates.shape[0])
+    yw = dirs * hidden
+    d = rnn_desc(cell, t, batch, input_size, hidden, dirs, batch_first, None, g_ld or dirs * gh, out_ld or yw, step0)
+    dimg = DeviceBuffer.from_numpy(rnn_pack_whh(d, w_hh, half))
+    dg, pg = _view_in(gates, g_ld, g_c_off, g_fill)
+    db = DeviceBuffer.from_numpy(_f32(b_hn)) if b_hn is not None else None
+    if resume is not None:
+        y0 = _full(gates.shape[:2] + (out_ld or yw,), gates.dtype, out_fill)
+        y0[..., out_c_off:out_c_off + yw] = resume[0]
+        dy = DeviceBuffer.from_numpy(y0, out=True)
+        py = dy.ptr + gates.itemsize * out_c_off
+    else:
+        dy, py = _view_out(gates.shape[:2], yw, out_ld, out_c_off, out_fill, gates.dtype)
+    lstm = cell == "lstm"
+    dc = None
+    if lstm:
+        c0 = _f32(resume[1]) if resume is not None else _full((dirs, batch, hidden), np.float32, c_fill)
+        dc = DeviceBuffer.from_numpy(c0, out=True)
+    state_shape = (dirs, batch, hidden)
+    dhn = DeviceBuffer.from_numpy(_full(state_shape, gates.dtype, out_fill), out=True) if want_state else None
+    dcn = DeviceBuffer.from_numpy(_full(state_shape, gates.dtype, out_fill), out=True) if want_state and lstm else None
+    LAST_KERNEL_NAME["si_hip_rnn"] = H.si_hip_rnn_kernel_name(C.byref(d), C.c_void_p(pg), C.c_void_p(py), 1 if half else 0).decode()
+    name = "si_hip_rnn_layer_f16" if half else "si_hip_rnn_layer_f32"
+    _chk(getattr(H, name)(C.byref(d), pg, dimg.ptr, db.ptr if db else None, py, dc.ptr if dc else None, dhn.ptr if dhn else None,
+                          dcn.ptr if dcn else None, None), name)
+    out = [_ret(dy.to_numpy(gates.shape[:2] + (out_ld or yw,), gates.dtype), yw, out_c_off, full)]
+    if want_state:
+        out.append(dhn.to_numpy(state_shape, gates.dtype))
+        if lstm:
+            out.append(dcn.to_numpy(state_shape, gates.dtype))
+    if return_c:
+        out.append(dc.to_numpy(state_shape, np.float32) if dc else None)
+    return out[0] if len(out) == 1 else tuple(out)
+
+
+def rnn_layer_f32(cell, gates, w_hh, b_hn=None, **kw):
+    return rnn_layer(cell, np.asarray(gates, np.float32), w_hh, b_hn, **kw)
+
+
+def rnn_layer_f16(cell, gates, w_hh, b_hn=None, **kw):
+    return rnn_layer(cell, np.asarray(gates, np.float16), w_hh, b_hn, **kw)
+
+
+def rnn_projection_bias(cell, b_ih, b_hh):
+    """the bias of the input projection and b_hn, as include/si_rnn.h pins them: one fp32 sum on the host -- LSTM b_ih + b_hh; GRU b_ih + b_hh for r
+    and z, b_ih alone for n, b_hn = b_hh's n rows"""
+    b_ih, b_hh = _f32(b_ih), _f32(b_hh)
+    if cell == "lstm":
+        return b_ih + b_hh, None
+    h = b_ih.size // 3
+    return np.concatenate([b_ih[:2 * h] + b_hh[:2 * h], b_ih[2 * h:]]), b_hh[2 * h:].copy()
+
+
+def _rnn(cell, x, weights, batch_first, want_state, views):
+    x = _float_storage(x)
+    half = x.dtype == np.float16
+    states = []
+    cur = x
+    for l, per_dir in enumerate(weights):
+        w_ih = np.concatenate([_f32(w[0]) for w in per_dir])
+        w_hh = np.stack([_f32(w[1]) for w in per_dir])
+        bias = b_hn = None
+        if per_dir[0][2] is not None:
+            parts = [rnn_projection_bias(cell, w[2], w[3]) for w in per_dir]
+            bias = np.concatenate([p[0] for p in parts])
+            b_hn = np.stack([p[1] for p in parts]) if cell == "gru" else None
+        rows = cur.reshape(-1, 1, 1, cur.shape[2])
+        conv = conv2d_f16 if half else conv2d
+        gates = conv(rows, w_ih.reshape(w_ih.shape + (1, 1)), bias).reshape(cur.shape[:2] + (w_ih.shape[0],))
+        last = l == len(weights) - 1
+        res = rnn_layer(cell, gates, w_hh, b_hn, batch_first=batch_first, want_state=want_state, input_size=cur.shape[2], **(views if last else {}))
+        cur = res[0] if want_state else res
+        if want_state:
+            states.append(res[1:])
+    if not want_state:
+        return cur
+    return (cur,) + tuple(np.concatenate([s[j] for s in states]) for j in range(len(states[0])))
+
+
+def lstm(x, weights, batch_first=False, want_state=False, **views):
+    """torch.nn.LSTM in eval mode on a numpy array [T, N, I] (or [N, T, I]): per layer the input projection through si_hip_conv2d_f32 / _f16 and
+    si_hip_rnn_layer_f32 / _f16 (by x's dtype).  weights[layer][direction] = (w_ih, w_hh, b_ih, b_hh), the biases None without bias.  The view
+    hooks (out_ld, out_c_off, out_fill, full) apply to y of the last layer.  want_state: (y, h_n, c_n) with the states [layers * dirs, N, H]"""
+    return _rnn("lstm", x, weights, batch_first, want_state, views)
+
+
+def gru(x, weights, batch_first=False, want_state=False, **views):
+    """torch.nn.GRU in eval mode, as lstm() above; want_state: (y, h_n)"""
+    return _rnn("gru", x, weights, batch_first, want_state, views)
+
+
 REDUCE_OPS = {"sum": 0, "mean": 1, "amax": 2, "amin": 3}
 
 

@@ -652,6 +652,46 @@ class PnnxBuilder:
                         embed_dim=e, kdim=e if kdim is None else int(kdim), num_heads=int(num_heads), vdim=e if vdim is None else int(vdim)), attrs)
         return outs[0]
 
+    def _recurrent(self, cell: str, x: str, hidden: int, num_layers: int, bias: bool, batch_first: bool, bidirectional: bool, states: bool,
+                   proj_size: int, initial: Sequence[str]):
+        n_gates, typ = (4, "nn.LSTM") if cell == "lstm" else (3, "nn.GRU")
+        shp = self.shapes[x]
+        assert len(shp) == 3, shp
+        in_f, dirs = shp[2], 2 if bidirectional else 1
+        name = self._opname(cell)
+        a = 1.0 / math.sqrt(hidden)   # torch's reset_parameters
+        attrs = {}
+        for l in range(num_layers):
+            for sfx in ["_l%d" % l] + (["_l%d_reverse" % l] if bidirectional else []):
+                shapes = [("weight_ih", (n_gates * hidden, in_f if l == 0 else dirs * hidden)), ("weight_hh", (n_gates * hidden, hidden))]
+                if bias:
+                    shapes += [("bias_ih", (n_gates * hidden,)), ("bias_hh", (n_gates * hidden,))]
+                for key, shape in shapes:
+                    attrs[key + sfx] = seeded_uniform("%s.%s%s" % (name, key, sfx), shape, -a, a, self.seed)
+        outs = [self._new_operand(tuple(shp[:2]) + (dirs * hidden,))]
+        if states:
+            batch = shp[0] if batch_first else shp[1]
+            outs += [self._new_operand((num_layers * dirs, batch, hidden)) for _ in range(2 if cell == "lstm" else 1)]
+        params = dict(batch_first=bool(batch_first), bias=bool(bias), bidirectional=bool(bidirectional), dropout=0.0, hidden_size=int(hidden),
+                      input_size=int(in_f), num_layers=int(num_layers))
+        if cell == "lstm":
+            params["proj_size"] = int(proj_size)
+        self._emit(typ, name, [x] + list(initial), outs, params, attrs)
+        return tuple(outs) if states else outs[0]
+
+    def lstm(self, x: str, hidden: int, num_layers: int = 1, bias: bool = True, batch_first: bool = False, bidirectional: bool = False,
+             states: bool = False, proj_size: int = 0, initial: Sequence[str] = ()):
+        """pnnx's nn.LSTM line on a rank-3 operand [T, N, I], or [N, T, I] with batch_first: params input_size, hidden_size, num_layers, bias,
+        batch_first, bidirectional, proj_size, dropout; attributes weight_ih_l{k} (4H, I_k), weight_hh_l{k} (4H, H) and, with bias,
+        bias_ih_l{k} / bias_hh_l{k} (4H), with their _reverse twins.  Returns y [.., D H]; states=True: (y, h_n, c_n), the states
+        [layers * D, N, H].  proj_size != 0 and initial (h0, c0 as further inputs) write lines the engine refuses."""
+        return self._recurrent("lstm", x, hidden, num_layers, bias, batch_first, bidirectional, states, proj_size, initial)
+
+    def gru(self, x: str, hidden: int, num_layers: int = 1, bias: bool = True, batch_first: bool = False, bidirectional: bool = False,
+            states: bool = False, initial: Sequence[str] = ()):
+        """pnnx's nn.GRU line, as lstm() above with three gates (r, z, n) and no proj_size; states=True: (y, h_n)"""
+        return self._recurrent("gru", x, hidden, num_layers, bias, batch_first, bidirectional, states, 0, initial)
+
     def detect(self, xs: Sequence[str], strides=(8.0, 16.0, 32.0), anchors=None, nc: int = 80) -> str:
         """models.yolo.Detect -- attribute names per reference src/layer/yolo_detect.cpp:19-145."""
         anchors = anchors or [[(10, 13), (16, 30), (33, 23)], [(30, 61), (62, 45), (59, 119)],
@@ -1153,6 +1193,29 @@ def build_toy_mhsa_head(batch: int = 2, size: int = 16, c: int = 24, heads: int 
     t = b.multihead_attention(t, num_heads=heads, batch_first=True)
     m = b.mean(b.view(b.permute(t, (0, 2, 1)), (batch, c, h, w)), (2, 3))
     b.output(b.linear(m, 10))
+    return b
+
+
+def build_toy_crnn(batch: int = 2, height: int = 16, width: int = 40, hidden: int = 32, layers: int = 2, cell: str = "lstm",
+                   bidirectional: bool = True, batch_first: bool = False, states: bool = False, channels: int = 32, ncls: int = 11,
+                   seed: int = 0) -> PnnxBuilder:
+    """A CRNN text recogniser at toy width: three conv + ReLU + max pool stages that take the height to 1 and the width to width / 4 ->
+    torch.flatten(start_dim=2) [N, C, T] -> Tensor.permute(2, 0, 1) [T, N, C] (batch_first: (0, 2, 1), [N, T, C]) -> nn.LSTM / nn.GRU ->
+    nn.Linear to the classes, per time step.  No softmax: the argmax over the classes is the host's.  states=True: the operator's state outputs
+    are operands too, and h_n feeds a second nn.Linear whose result is a second graph output."""
+    assert height % 4 == 0 and width % 4 == 0 and cell in ("lstm", "gru")
+    b = PnnxBuilder(seed)
+    x = b.maxpool(b.relu(b.conv(b.input((batch, 3, height, width)), 16, 3, 1, 1)), 2, 2, 0)
+    x = b.maxpool(b.relu(b.conv(x, channels, 3, 1, 1)), 2, 2, 0)
+    x = b.maxpool(b.relu(b.conv(x, channels, 3, 1, 1)), (height // 4, 1), (height // 4, 1), 0)
+    t = b.permute(b.flatten(x, 2), (0, 2, 1) if batch_first else (2, 0, 1))
+    rec = b.lstm if cell == "lstm" else b.gru
+    y = rec(t, hidden, num_layers=layers, batch_first=batch_first, bidirectional=bidirectional, states=states)
+    if states:
+        b.output(b.linear(y[0], ncls))
+        b.output(b.linear(y[1], ncls))
+    else:
+        b.output(b.linear(y, ncls))
     return b
 
 
