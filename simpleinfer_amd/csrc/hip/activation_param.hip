@@ -16,9 +16,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int PA_THREADS = 256;
 
 // log1p(e) for 0 <= e <= 1 (a NaN comes out).  u = 1 + e rounds; d = (u - 1) - e is that rounding error, exactly (u - 1 is exact for

@@ -42,10 +42,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int AT_THREADS = 256;
 constexpr int AT_BQ = SI_ATTENTION_BLOCK_Q;
 constexpr int AT_TK = SI_ATTENTION_TILE_K;

@@ -24,9 +24,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int AP_THREADS = 256;
 
 struct AvgArgs {

@@ -12,8 +12,6 @@
 #include "si_hip.h"
 #include "si_hip_internal.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
 
 struct DwArgs {
@@ -28,18 +26,6 @@ struct DwArgs {
     int act1, act2;
     float act_param;
 };
-
-__device__ __forceinline__ float dw_act(int act, float v, float p) {
-    switch (act) {
-        case SI_ACT_RELU: return fmaxf(v, 0.0f);
-        case SI_ACT_SILU: return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v));
-        case SI_ACT_SIGMOID: return __builtin_amdgcn_rcpf(1.0f + __expf(-v));
-        case SI_ACT_HARDSIGMOID: return fminf(fmaxf(v * (1.0f / 6.0f) + 0.5f, 0.0f), 1.0f);
-        case SI_ACT_HARDSWISH: return v * fminf(fmaxf(v * (1.0f / 6.0f) + 0.5f, 0.0f), 1.0f);
-        case SI_ACT_LEAKYRELU: return v > 0.0f ? v : v * p;
-        default: return v;
-    }
-}
 
 // Specialisation for dilation 1 and compile-time kernel width / column stride (3x3 and 5x5, stride 1 and 2: every
 // MobileNet depthwise layer): the (TW-1)*SW + KW distinct input columns of a kernel row are loaded ONCE into registers
@@ -98,9 +84,9 @@ __global__ __launch_bounds__(256) void conv_depthwise_cols_kernel(const DwArgs a
             const f32x4 r = a.res ? *reinterpret_cast<const f32x4*>(a.res + pix * a.res_ld + ch) : (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                float e = dw_act(a.act1, v[k], a.act_param);
+                float e = si_act(a.act1, v[k], a.act_param);
                 if (a.res) e += r[k];
-                v[k] = dw_act(a.act2, e, a.act_param);
+                v[k] = si_act(a.act2, e, a.act_param);
             }
             *reinterpret_cast<f32x4*>(a.out + pix * a.out_ld + ch) = v;
         }
@@ -175,9 +161,9 @@ __global__ __launch_bounds__(256) void conv_depthwise_kernel(const DwArgs a) {
             }
 #pragma unroll
             for (int k = 0; k < CV; ++k) {
-                float e = dw_act(a.act1, v[k], a.act_param);
+                float e = si_act(a.act1, v[k], a.act_param);
                 if (a.res) e += r[k];
-                v[k] = dw_act(a.act2, e, a.act_param);
+                v[k] = si_act(a.act2, e, a.act_param);
             }
             float* o = a.out + pix * a.out_ld + ch;
             if (VEC) *reinterpret_cast<f32x4*>(o) = v;
@@ -232,8 +218,8 @@ int si_conv_depthwise_launch(const SiConv2dDesc* d, const float* in, const float
     a.oh = d->oh; a.ow = d->ow; a.out_ld = d->out_ld; a.res_ld = d->res_ld;
     a.kh = d->kh; a.kw = d->kw; a.sh = d->sh; a.sw = d->sw; a.dh = d->dh; a.dw = d->dw; a.pt = d->pt; a.pl = d->pl;
     a.act1 = d->act1; a.act2 = d->act2; a.act_param = d->act_param;
-    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    const bool vec = dw_vec_strides(d) && al16(in) && al16(out) && al16(w_packed) && (!a.bias || al16(a.bias)) && (!a.res || al16(a.res));
+    const bool vec = dw_vec_strides(d) && si_aligned_to(in, 16) && si_aligned_to(out, 16) && si_aligned_to(w_packed, 16) &&
+                     (!a.bias || si_aligned_to(a.bias, 16)) && (!a.res || si_aligned_to(a.res, 16));
     constexpr int TW = 4;
     const size_t items = (size_t)d->n * d->oh * ((d->ow + TW - 1) / TW) * (vec ? d->ic / 4 : d->ic);
     if (items == 0) return 0;

@@ -7,14 +7,10 @@
 // Algorithmic bytes: 2 * (N*H*W*C + N*OH*OW*C).
 #include <hip/hip_runtime.h>
 
-#include "si_hip.h"
-#include "si_hip_internal.h"
-
 #pragma clang fp contract(off)
 
-typedef _Float16 half_t;
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "si_hip.h"
+#include "si_hip_internal.h"
 
 namespace {
 
@@ -30,18 +26,6 @@ struct DwArgsH {
     int act1, act2;
     float act_param;
 };
-
-__device__ __forceinline__ float dwh_act(int act, float v, float p) {
-    switch (act) {
-        case SI_ACT_RELU: return fmaxf(v, 0.0f);
-        case SI_ACT_SILU: return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v));
-        case SI_ACT_SIGMOID: return __builtin_amdgcn_rcpf(1.0f + __expf(-v));
-        case SI_ACT_HARDSIGMOID: return fminf(fmaxf(v * (1.0f / 6.0f) + 0.5f, 0.0f), 1.0f);
-        case SI_ACT_HARDSWISH: return v * fminf(fmaxf(v * (1.0f / 6.0f) + 0.5f, 0.0f), 1.0f);
-        case SI_ACT_LEAKYRELU: return v > 0.0f ? v : v * p;
-        default: return v;
-    }
-}
 
 template <int TW>
 __global__ __launch_bounds__(256) void conv_depthwise_f16_kernel(const DwArgsH a) {
@@ -101,9 +85,9 @@ __global__ __launch_bounds__(256) void conv_depthwise_f16_kernel(const DwArgsH a
             f16x8 o;
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
-                float e = dwh_act(a.act1, acc[j][k] + bv[k], a.act_param);
+                float e = si_act(a.act1, acc[j][k] + bv[k], a.act_param);
                 if (a.res) e += (float)r[k];
-                o[k] = si_store_cast<half_t>(dwh_act(a.act2, e, a.act_param));
+                o[k] = si_store_cast<half_t>(si_act(a.act2, e, a.act_param));
             }
             *reinterpret_cast<f16x8*>(a.out + pix * a.out_ld + ch) = o;
         }
@@ -123,9 +107,8 @@ extern "C" int si_hip_conv2d_depthwise_f16(const SiConv2dDesc* d, const void* in
     if (d->n <= 0 || d->oh <= 0 || d->ow <= 0) return SI_E_BADARG;
     if (d->has_bias && !bias) return SI_E_BADARG;
     if (d->has_residual && !residual) return SI_E_BADARG;
-    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    if (d->in_ld % 8 != 0 || d->out_ld % 8 != 0 || !al16(in) || !al16(out) || !al16(w_packed) || (d->has_bias && !al16(bias)) ||
-        (d->has_residual && (d->res_ld % 8 != 0 || !al16(residual))))
+    if (d->in_ld % 8 != 0 || d->out_ld % 8 != 0 || !si_aligned_to(in, 16) || !si_aligned_to(out, 16) || !si_aligned_to(w_packed, 16) || (d->has_bias && !si_aligned_to(bias, 16)) ||
+        (d->has_residual && (d->res_ld % 8 != 0 || !si_aligned_to(residual, 16))))
         return SI_E_UNSUPPORTED;
     DwArgsH a;
     a.in = static_cast<const half_t*>(in); a.w = w_packed; a.bias = d->has_bias ? bias : nullptr;

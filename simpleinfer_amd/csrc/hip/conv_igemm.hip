@@ -35,16 +35,13 @@
 #include <cstdio>
 #include <cstdlib>
 
-#include "si_hip.h"
-#include "si_hip_internal.h"
-
 // No floating-point contraction in this file: the epilogue exists in several template instantiations (interior / edge
 // tile, with / without residual, activation known or not) and an image's result must not depend on which one a pixel
 // happens to go through (bit-exact batch sharding).  The MFMA builtins are unaffected.
 #pragma clang fp contract(off)
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "si_hip.h"
+#include "si_hip_internal.h"
 
 // conv_smallc.hip: stem kernel for 1..3 input channels
 bool si_conv_smallc_ok(const SiConv2dDesc* d);
@@ -77,7 +74,7 @@ struct ConvArgs {
     int Kp;                     // kh*kw*icg_pad
     int M;                      // n*oh*ow
     int ohow;
-    unsigned mg_ohow, mg_ow;    // floor(2^32 / d) for the two per-row divisions of the fast kernel's prologue (see fast_div)
+    unsigned mg_ohow, mg_ow;    // floor(2^32 / d) for the two per-row divisions of the fast kernel's prologue (si_magic.h)
     unsigned mg_chunk;          // ... and for the block decode's division by 8 * n_tiles
     int m_tiles, n_tiles;
     int act1, act2;
@@ -103,53 +100,9 @@ struct ConvArgs {
     unsigned up_bytes;
 };
 
-__device__ __forceinline__ float apply_act(int act, float v, float p) {
-    switch (act) {
-        case SI_ACT_RELU: return fmaxf(v, 0.0f);
-        case SI_ACT_SILU: return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v));
-        case SI_ACT_SIGMOID: return __builtin_amdgcn_rcpf(1.0f + __expf(-v));
-        case SI_ACT_HARDSIGMOID: return fminf(fmaxf(v * (1.0f / 6.0f) + 0.5f, 0.0f), 1.0f);
-        case SI_ACT_HARDSWISH: return v * fminf(fmaxf(v * (1.0f / 6.0f) + 0.5f, 0.0f), 1.0f);
-        case SI_ACT_LEAKYRELU: return v > 0.0f ? v : v * p;
-        default: return v;
-    }
-}
-
-// The two fp32 MFMA tiles the kernels use.  Both round like ONE sequential fma chain over k (tools/mfma_chain_test.hip, measured:
-// v_mfma_f32_32x32x2_f32, v_mfma_f32_16x16x4_f32 and a scalar fmaf loop agree bit for bit), so a kernel on 16x16 tiles that feeds
-// k in the same order as one on 32x32 tiles produces the same bits per output element -- the tile policy may follow the batch
-// size without breaking the engine's batch-invariance contract.
-//   32x32x2: A/B operand of lane l = row (l & 31), k = l >> 5;   C/D: col = l & 31, row = (e&3) + 8*(e>>2) + 4*(l>>5), 16 registers
-//   16x16x4: A/B operand of lane l = row (l & 15), k = l >> 4;   C/D: col = l & 15, row = e + 4*(l>>4),             4 registers
-template <int MT> struct Mma;
-template <> struct Mma<32> {
-    typedef f32x16 acc_t;
-    static constexpr int NE = 16;
-    __device__ static __forceinline__ constexpr int row(int e) { return (e & 3) + 8 * (e >> 2); }
-};
-template <> struct Mma<16> {
-    typedef f32x4 acc_t;
-    static constexpr int NE = 4;
-    __device__ static __forceinline__ constexpr int row(int e) { return e; }
-};
-
-// ---- epilogue shared by the kernels.  32x32 C/D map: col = lane&31, row = (e&3) + 8*(e>>2) + 4*(lane>>5).
+// ---- epilogue shared by the kernels.  32x32 C/D map (Mma<32>, si_hip_internal.h): col = lane&31, row = (e&3) + 8*(e>>2) + 4*(lane>>5).
 // Each store instruction writes two 128-byte row segments (lanes 0-31 / 32-63).  The activation switch
 // is resolved once per workgroup, not per element.
-// v_rcp_f32 / v_exp_f32 are accurate to 1 ulp: SiLU and sigmoid are within ~2e-7 relative of the exact value, three orders
-// inside the parity bar, at 5 instructions instead of the 15 of an IEEE division.
-__device__ __forceinline__ float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
-
-template <int ACT>
-__device__ __forceinline__ float act_fn(float v, float p) {
-    if (ACT == SI_ACT_RELU) return fmaxf(v, 0.0f);
-    if (ACT == SI_ACT_SILU) return v * fast_rcp(1.0f + __expf(-v));
-    if (ACT == SI_ACT_SIGMOID) return fast_rcp(1.0f + __expf(-v));
-    if (ACT == SI_ACT_HARDSIGMOID) return fminf(fmaxf(v * (1.0f / 6.0f) + 0.5f, 0.0f), 1.0f);
-    if (ACT == SI_ACT_HARDSWISH) return v * fminf(fmaxf(v * (1.0f / 6.0f) + 0.5f, 0.0f), 1.0f);
-    if (ACT == SI_ACT_LEAKYRELU) return v > 0.0f ? v : v * p;
-    return v;
-}
 
 // The straight-line epilogue: one activation known at compile time, residual yes / no and "every row of the tile is inside
 // M" (all tiles but the last) resolved once per workgroup, row offsets c*ld computed once -- per element this leaves
@@ -196,8 +149,8 @@ __device__ __forceinline__ void epilogue_lean(const ConvArgs& a, typename Mma<MT
                 }
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const float vl = act_fn<ACT1>(acc[t][u][e] + bv_l, a.act_param);
-                    const float vr = act_fn<ACT1>(acc[t][u + 1][e] + bv_r, a.act_param);
+                    const float vl = si_act<ACT1>(acc[t][u][e] + bv_l, a.act_param);
+                    const float vr = si_act<ACT1>(acc[t][u + 1][e] + bv_r, a.act_param);
                     // (inline assembly: with __builtin_amdgcn_permlane16_swap hipcc 7.2 used the FIRST result for both halves in this
                     // function -- the second result's register was reused as an address before its store; the s_nop covers the
                     // VALU-write -> permlane-read hazard the compiler otherwise pads)
@@ -205,11 +158,11 @@ __device__ __forceinline__ void epilogue_lean(const ConvArgs& a, typename Mma<MT
                     asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1\n\ts_nop 1" : "+v"(x), "+v"(y));
                     if (live && (INTERIOR || mb + e < a.M)) {
                         if (HAS_RES) x += rx[e];
-                        op[e * old] = act_fn<ACT2>(x, a.act_param);
+                        op[e * old] = si_act<ACT2>(x, a.act_param);
                     }
                     if (live && (INTERIOR || mb + 4 + e < a.M)) {
                         if (HAS_RES) y += ry[e];
-                        op[(4 + e) * old] = act_fn<ACT2>(y, a.act_param);
+                        op[(4 + e) * old] = si_act<ACT2>(y, a.act_param);
                     }
                 }
             }
@@ -234,7 +187,6 @@ __device__ __forceinline__ void epilogue_lean(const ConvArgs& a, typename Mma<MT
                 // SiLU on PAIRS of rows with the packed fp32 instructions (v_pk_add / v_pk_mul: two values per issue slot, each
                 // component rounded exactly like the scalar form, so the bits are the scalar path's): bias add, the -log2(e)
                 // scale, the + 1 and the final product take 4 vector issues per pair instead of 8; v_exp / v_rcp stay scalar.
-                typedef float f32x2 __attribute__((ext_vector_type(2)));
 #pragma unroll
                 for (int e = 0; e < NE; e += 2) {
                     const int c0 = Mma<MT>::row(e);   // rows c0 and c0 + 1 (e and e + 1 never straddle a group of 4)
@@ -258,9 +210,9 @@ __device__ __forceinline__ void epilogue_lean(const ConvArgs& a, typename Mma<MT
             for (int e = 0; e < NE; ++e) {
                 const int c = Mma<MT>::row(e);  // row of the C/D map (plus 4 * (lane >> 5) or 4 * (lane >> 4), already in mrow0)
                 if (INTERIOR || mb + c < a.M) {
-                    float v = act_fn<ACT1>(acc[t][u][e] + bv, a.act_param);
+                    float v = si_act<ACT1>(acc[t][u][e] + bv, a.act_param);
                     if (HAS_RES) v += rv[e];
-                    op[c * old] = act_fn<ACT2>(v, a.act_param);
+                    op[c * old] = si_act<ACT2>(v, a.act_param);
                 }
             }
             }
@@ -303,9 +255,9 @@ __device__ __forceinline__ void epilogue_generic(const ConvArgs& a, typename Mma
                 const int m = mb + Mma<MT>::row(e);
                 if (m < a.M) {
                     float v = acc[t][u][e] + bv;
-                    v = apply_act(a.act1, v, a.act_param);
+                    v = si_act(a.act1, v, a.act_param);
                     if (has_res) v += a.res[(size_t)m * a.res_ld + oc_abs];
-                    v = apply_act(a.act2, v, a.act_param);
+                    v = si_act(a.act2, v, a.act_param);
                     obase[(size_t)m * old] = v;
                 }
             }
@@ -341,7 +293,7 @@ __device__ __forceinline__ void epilogue_yolo(const ConvArgs& a, typename Mma<MT
                         pix -= adv * a.ohow;
                         img += adv;
                     }
-                    const float sg = __builtin_amdgcn_rcpf(1.0f + __expf(-(acc[t][u][e] + bv)));
+                    const float sg = si_sigmoid_fast(acc[t][u][e] + bv);
                     const size_t row = (size_t)pix * a.yna + anc;
                     float v = sg;
                     if (e_ < 2) {
@@ -556,16 +508,6 @@ __global__ __launch_bounds__(256) void conv_igemm_f32_kernel(const ConvArgs a) {
 //   fixed byte offset and looks its tap up in a 64-bit validity mask computed once.
 // * loads are raw buffer loads: an out-of-image tap (or a row past M / past OC) is an out-of-range offset
 //   and the hardware returns zeros -- no branches around the loads.
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-// n / d for 0 <= n < 2^32 with mg = floor(2^32 / d) (0xFFFFFFFF for d = 1): mulhi gives the quotient or one less, one
-// correction step makes it exact -- 5 instructions instead of the ~40 of an emulated integer division, twice per staged row
-__device__ __forceinline__ int fast_div(int n, int d, unsigned mg) {
-    unsigned q = __umulhi((unsigned)n, mg);
-    if ((unsigned)n - q * (unsigned)d >= (unsigned)d) ++q;
-    return (int)q;
-}
-constexpr unsigned OOB_A = 0xFFFFFF00u;  // >= any legal num_records
-constexpr unsigned OOB_B = 0x80000000u;  // weights are < 2 GB; + kt*128 cannot wrap
 
 // PADK: the K axis of a 1x1 conv is zero-padded to whole 32-channel blocks (conv_icg_pad); a separate instantiation so the
 // channel check costs the ordinary layers nothing (it was worth 0.5 % of the YOLOv5s step inside the shared loop)
@@ -608,7 +550,7 @@ __global__ __launch_bounds__(256) void conv_igemm_f32_fast_kernel(const ConvArgs
 
     const int g = blockIdx.y;
     const int per_chunk = 8 * a.n_tiles;
-    const int chunk = fast_div((int)blockIdx.x, per_chunk, a.mg_chunk);
+    const int chunk = si_fast_div((int)blockIdx.x, per_chunk, a.mg_chunk);
     const int r = blockIdx.x - chunk * per_chunk;
     const int m_tile = chunk * 8 + (r & 7);
     const int n_tile = r >> 3;
@@ -620,12 +562,10 @@ __global__ __launch_bounds__(256) void conv_igemm_f32_fast_kernel(const ConvArgs
     const int kv = tid & 7;
     const int r0 = tid >> 3;
 
-    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(a.in + (size_t)g * a.icg), 0, a.in_bytes - (unsigned)g * a.icg * 4u, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(a.w + (size_t)g * a.ocg * a.Kp), 0, (unsigned)a.ocg * a.Kp * 4u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_in = si_buffer(a.in + (size_t)g * a.icg, a.in_bytes - (unsigned)g * a.icg * 4u);
+    const __amdgpu_buffer_rsrc_t rs_w = si_buffer(a.w + (size_t)g * a.ocg * a.Kp, (unsigned)a.ocg * a.Kp * 4u);
 
-    const __amdgpu_buffer_rsrc_t rs_up = UPS ? __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.up), 0, a.up_bytes, 0x00020000) : rs_in;
+    const __amdgpu_buffer_rsrc_t rs_up = UPS ? si_buffer(a.up, a.up_bytes) : rs_in;
 
     // per-thread A rows: byte offset of (tap 0, channel kv*4) and the tap validity mask
     unsigned a_off[A_IT];
@@ -637,11 +577,11 @@ __global__ __launch_bounds__(256) void conv_igemm_f32_fast_kernel(const ConvArgs
         a_off[i] = 0;
         a_mask[i] = 0ull;
         if (UPS) {
-            u_off[i] = OOB_A;
+            u_off[i] = SI_OOB;
             if (m < a.M) {
-                const int img = fast_div(m, a.ohow, a.mg_ohow);
+                const int img = si_fast_div(m, a.ohow, a.mg_ohow);
                 const int rem = m - img * a.ohow;
-                const int oy = fast_div(rem, a.ow, a.mg_ow);
+                const int oy = si_fast_div(rem, a.ow, a.mg_ow);
                 const int ox = rem - oy * a.ow;
                 // upsample.cpp:85-92: src = clamp(int(float(dst) * (1 / scale)), 0, in - 1)
                 int sy = (int)((float)oy * a.up_inv_h), sx = (int)((float)ox * a.up_inv_w);
@@ -651,15 +591,15 @@ __global__ __launch_bounds__(256) void conv_igemm_f32_fast_kernel(const ConvArgs
             }
         }
         if (PW || UPS || YOLO) {   // (the dual-source and Detect forms are pointwise by construction)
-            a_off[i] = m < a.M ? (unsigned)m * (unsigned)(a.in_ld * 4) + (unsigned)(kv * 16) : OOB_A;
+            a_off[i] = m < a.M ? (unsigned)m * (unsigned)(a.in_ld * 4) + (unsigned)(kv * 16) : SI_OOB;
         } else if (m < a.M && a.pointwise) {
             // 1x1, stride 1, no padding: output pixel m IS input pixel m -- no index decomposition, one always-valid tap
             a_off[i] = (unsigned)m * (unsigned)(a.in_ld * 4) + (unsigned)(kv * 16);
             a_mask[i] = 1ull;
         } else if (m < a.M) {
-            const int img = fast_div(m, a.ohow, a.mg_ohow);
+            const int img = si_fast_div(m, a.ohow, a.mg_ohow);
             const int rem = m - img * a.ohow;
-            const int oy = fast_div(rem, a.ow, a.mg_ow);
+            const int oy = si_fast_div(rem, a.ow, a.mg_ow);
             const int ox = rem - oy * a.ow;
             const int y0 = oy * a.sh - a.pt, x0 = ox * a.sw - a.pl;
             // modulo-2^32 arithmetic: (tap-0 pixel may lie before the tensor start; adding the tap delta brings
@@ -693,7 +633,7 @@ __global__ __launch_bounds__(256) void conv_igemm_f32_fast_kernel(const ConvArgs
 #pragma unroll
     for (int i = 0; i < B_IT; ++i) {
         const int o = n0 + r0 + 32 * i;
-        b_off[i] = o < a.ocg ? (unsigned)(o * a.Kp * 4 + kv * 16) : OOB_B;
+        b_off[i] = o < a.ocg ? (unsigned)(o * a.Kp * 4 + kv * 16) : SI_OOB_HALF;
     }
 
     u32x4 pa_[KU][A_IT], pb_[KU][B_IT];
@@ -724,12 +664,12 @@ __global__ __launch_bounds__(256) void conv_igemm_f32_fast_kernel(const ConvArgs
         if (from_up) {
             const unsigned du = (unsigned)(cb - a.up_cb0) * 128u;
 #pragma unroll
-            for (int i = 0; i < A_IT; ++i) pa[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_up, u_off[i] == OOB_A ? OOB_A : u_off[i] + du, 0, 0);
+            for (int i = 0; i < A_IT; ++i) pa[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_up, u_off[i] == SI_OOB ? SI_OOB : u_off[i] + du, 0, 0);
         } else {
 #pragma unroll
             for (int i = 0; i < A_IT; ++i) {
                 const bool ok = ((a_mask[i] >> tapbit) & 1ull) && cok;
-                const unsigned off = ok ? a_off[i] + delta : OOB_A;
+                const unsigned off = ok ? a_off[i] + delta : SI_OOB;
                 pa[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_in, off, 0, 0);
             }
         }
@@ -906,7 +846,7 @@ int launch_fast(const ConvArgs& a, int groups, hipStream_t s) {
     ConvArgs b = a;
     b.m_tiles = (a.M + BM - 1) / BM;
     b.n_tiles = (a.ocg + BN - 1) / BN;
-    b.mg_chunk = (unsigned)(0x100000000ull / (unsigned)(8 * b.n_tiles));
+    b.mg_chunk = si_magic(8 * b.n_tiles);
     const int chunks = (b.m_tiles + 7) / 8;
     dim3 grid(chunks * 8 * b.n_tiles, groups, 1);
     // the tiles that carry every instantiation (pointwise / dual-source / zero-padded K): the two defaults and the 16x16-MFMA ones
@@ -1225,8 +1165,8 @@ static int conv2d_dispatch(const SiConv2dDesc* d, const float* in, const float* 
     a.Kp = d->kh * d->kw * a.icg_pad;
     a.M = d->n * d->oh * d->ow;
     a.ohow = d->oh * d->ow;
-    a.mg_ohow = a.ohow > 1 ? (unsigned)(0x100000000ull / (unsigned)a.ohow) : 0xFFFFFFFFu;
-    a.mg_ow = d->ow > 1 ? (unsigned)(0x100000000ull / (unsigned)d->ow) : 0xFFFFFFFFu;
+    a.mg_ohow = si_magic(a.ohow);
+    a.mg_ow = si_magic(d->ow);
     a.m_tiles = a.n_tiles = 0;
     a.act1 = d->act1; a.act2 = d->act2; a.act_param = d->act_param;
     a.cb_major = conv_cb_major(d) ? 1 : 0;

@@ -19,20 +19,14 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "si_hip.h"
-#include "si_hip_internal.h"
-
 // No floating-point contraction in this file: the epilogue exists in several template instantiations (interior / edge
 // tile, with / without residual, ...) and an image's result must not depend on which one a pixel happens to go through
 // (bit-exact batch sharding); with contraction the compiler fuses a*b+c differently per instantiation.  The MFMA
 // builtins are unaffected.
 #pragma clang fp contract(off)
 
-typedef _Float16 half_t;
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "si_hip.h"
+#include "si_hip_internal.h"
 
 // conv_stem_f16.hip: stem kernel of this path (fp32 image in, fp16 out)
 bool si_conv_stem_f16_ok(const SiConv2dDesc* d);
@@ -60,7 +54,7 @@ struct ConvArgsH {
     int icg, ocg, oc;
     int Kp;                     // kh*kw*icg
     int M, ohow;
-    unsigned mg_ohow, mg_ow;    // floor(2^32 / d) of the two per-row divisions of the prologue (fast_div_h)
+    unsigned mg_ohow, mg_ow;    // floor(2^32 / d) of the two per-row divisions of the prologue (si_magic.h)
     int m_tiles, n_tiles;
     int act1, act2;
     float act_param;
@@ -82,25 +76,6 @@ struct ConvArgsH {
     unsigned up_bytes;
 };
 
-// n / d for 0 <= n < 2^32 with mg = floor(2^32 / d) (0xFFFFFFFF for d = 1): the high product is the quotient or one less
-__device__ __forceinline__ int fast_div_h(int n, int d, unsigned mg) {
-    unsigned q = __umulhi((unsigned)n, mg);
-    if ((unsigned)n - q * (unsigned)d >= (unsigned)d) ++q;
-    return (int)q;
-}
-
-__device__ __forceinline__ float act_h(int act, float v, float p) {
-    switch (act) {
-        case SI_ACT_RELU: return fmaxf(v, 0.0f);
-        case SI_ACT_SILU: return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v));
-        case SI_ACT_SIGMOID: return __builtin_amdgcn_rcpf(1.0f + __expf(-v));
-        case SI_ACT_HARDSIGMOID: return fminf(fmaxf(v * (1.0f / 6.0f) + 0.5f, 0.0f), 1.0f);
-        case SI_ACT_HARDSWISH: return v * fminf(fmaxf(v * (1.0f / 6.0f) + 0.5f, 0.0f), 1.0f);
-        case SI_ACT_LEAKYRELU: return v > 0.0f ? v : v * p;
-        default: return v;
-    }
-}
-
 // 32x32 C/D map: col = lane&31, row = (e&3) + 8*(e>>2) + 4*(lane>>5)
 template <int TM, int TN, typename OutT>
 __device__ __forceinline__ void epilogue_plain(const ConvArgsH& a, f32x16 (&acc)[TM][TN], int g, int mrow0, int ocol0) {
@@ -119,24 +94,17 @@ __device__ __forceinline__ void epilogue_plain(const ConvArgsH& a, f32x16 (&acc)
             const int mb = mrow0 + t * 32;
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int m = mb + (e & 3) + 8 * (e >> 2);
+                const int m = mb + Mma<32>::row(e);
                 if (m < a.M) {
                     float v = acc[t][u][e] + bv;
-                    v = act_h(a.act1, v, a.act_param);
+                    v = si_act(a.act1, v, a.act_param);
                     if (has_res) v += (float)a.res[(size_t)m * a.res_ld + oc_abs];
-                    v = act_h(a.act2, v, a.act_param);
+                    v = si_act(a.act2, v, a.act_param);
                     obase[(size_t)m * old] = si_store_cast<OutT>(v);
                 }
             }
         }
     }
-}
-
-template <int ACT>
-__device__ __forceinline__ float act_c(float v, float p) {
-    if (ACT == SI_ACT_RELU) return fmaxf(v, 0.0f);
-    if (ACT == SI_ACT_SILU) return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v));
-    return v;
 }
 
 // straight-line fp16 epilogue for the combinations the graphs produce (see conv_igemm.hip epilogue_lean)
@@ -165,17 +133,17 @@ __device__ __forceinline__ void epilogue_lean_h(const ConvArgsH& a, f32x16 (&acc
             if (HAS_RES) {
 #pragma unroll
                 for (int e = 0; e < 16; ++e) {
-                    const int c = (e & 3) + 8 * (e >> 2);
+                    const int c = Mma<32>::row(e);
                     rv[e] = rp[((INTERIOR || mb + c < a.M) ? c : a.M - 1 - mb) * a.res_ld];
                 }
             }
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int c = (e & 3) + 8 * (e >> 2);
+                const int c = Mma<32>::row(e);
                 if (INTERIOR || mb + c < a.M) {
-                    float v = act_c<ACT1>(acc[t][u][e] + bv, a.act_param);
+                    float v = si_act<ACT1>(acc[t][u][e] + bv, a.act_param);
                     if (HAS_RES) v += (float)rv[e];
-                    op[c * old] = si_store_cast<half_t>(act_c<ACT2>(v, a.act_param));
+                    op[c * old] = si_store_cast<half_t>(si_act<ACT2>(v, a.act_param));
                 }
             }
         }
@@ -213,7 +181,7 @@ __device__ __forceinline__ void epilogue_yolo_h(const ConvArgsH& a, f32x16 (&acc
             const int pix0 = mb - img0 * a.ohow;
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int dm = (e & 3) + 8 * (e >> 2);
+                const int dm = Mma<32>::row(e);
                 if (mb + dm < a.M) {
                     int pix = pix0 + dm, img = img0;
                     if (pix >= a.ohow) {
@@ -221,7 +189,7 @@ __device__ __forceinline__ void epilogue_yolo_h(const ConvArgsH& a, f32x16 (&acc
                         pix -= adv * a.ohow;
                         img += adv;
                     }
-                    const float sg = __builtin_amdgcn_rcpf(1.0f + __expf(-(acc[t][u][e] + bv)));
+                    const float sg = si_sigmoid_fast(acc[t][u][e] + bv);
                     const size_t row = (size_t)pix * a.yna + anc;
                     float v = sg;
                     if (e_ < 2) {
@@ -236,9 +204,6 @@ __device__ __forceinline__ void epilogue_yolo_h(const ConvArgsH& a, f32x16 (&acc
         }
     }
 }
-
-constexpr unsigned OOB_A = 0xFFFFFF00u;
-constexpr unsigned OOB_B = 0x80000000u;
 
 // BKH: channels per K-tile = one tap of one BKH-channel block.  64 whenever the channel count allows: a row of the
 // tile is then a whole 128-byte line per load instruction (32: half lines) and a 1x1 conv over 64 channels needs a
@@ -273,12 +238,10 @@ __global__ __launch_bounds__(256) void conv_igemm_f16_kernel(const ConvArgsH a) 
     const int kv = tid % VPR;
     const int r0 = tid / VPR;
 
-    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<half_t*>(a.in + (size_t)g * a.icg), 0, a.in_bytes - (unsigned)g * a.icg * 2u, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<half_t*>(a.w + (size_t)g * a.ocg * a.Kp), 0, (unsigned)a.ocg * a.Kp * 2u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_in = si_buffer(a.in + (size_t)g * a.icg, a.in_bytes - (unsigned)g * a.icg * 2u);
+    const __amdgpu_buffer_rsrc_t rs_w = si_buffer(a.w + (size_t)g * a.ocg * a.Kp, (unsigned)a.ocg * a.Kp * 2u);
 
-    const __amdgpu_buffer_rsrc_t rs_up = UPS ? __builtin_amdgcn_make_buffer_rsrc(const_cast<half_t*>(a.up), 0, a.up_bytes, 0x00020000) : rs_in;
+    const __amdgpu_buffer_rsrc_t rs_up = UPS ? si_buffer(a.up, a.up_bytes) : rs_in;
     unsigned a_off[A_IT];
     unsigned u_off[UPS ? A_IT : 1];   // UPS: byte offset of the row's source pixel in the low-resolution tensor
     unsigned long long a_mask[A_IT];
@@ -288,11 +251,11 @@ __global__ __launch_bounds__(256) void conv_igemm_f16_kernel(const ConvArgsH a) 
         a_off[i] = 0;
         a_mask[i] = 0ull;
         if (UPS) {
-            u_off[i] = OOB_A;
+            u_off[i] = SI_OOB;
             if (m < a.M) {
-                const int img = fast_div_h(m, a.ohow, a.mg_ohow);
+                const int img = si_fast_div(m, a.ohow, a.mg_ohow);
                 const int rem = m - img * a.ohow;
-                const int oy = fast_div_h(rem, a.ow, a.mg_ow);
+                const int oy = si_fast_div(rem, a.ow, a.mg_ow);
                 const int ox = rem - oy * a.ow;
                 // src/layer/upsample.cpp:85-92: src = clamp(int(float(dst) * (1 / scale)), 0, in - 1)
                 int sy = (int)((float)oy * a.up_inv_h), sx = (int)((float)ox * a.up_inv_w);
@@ -305,9 +268,9 @@ __global__ __launch_bounds__(256) void conv_igemm_f16_kernel(const ConvArgsH a) 
             a_off[i] = (unsigned)m * (unsigned)(a.in_ld * 2) + (unsigned)(kv * 16);
             a_mask[i] = 1ull;
         } else if (m < a.M) {
-            const int img = fast_div_h(m, a.ohow, a.mg_ohow);
+            const int img = si_fast_div(m, a.ohow, a.mg_ohow);
             const int rem = m - img * a.ohow;
-            const int oy = fast_div_h(rem, a.ow, a.mg_ow);
+            const int oy = si_fast_div(rem, a.ow, a.mg_ow);
             const int ox = rem - oy * a.ow;
             const int y0 = oy * a.sh - a.pt, x0 = ox * a.sw - a.pl;
             a_off[i] = (unsigned)((img * a.ih + y0) * a.iw + x0) * (unsigned)(a.in_ld * 2) + (unsigned)(kv * 16);
@@ -324,7 +287,7 @@ __global__ __launch_bounds__(256) void conv_igemm_f16_kernel(const ConvArgsH a) 
 #pragma unroll
     for (int i = 0; i < B_IT; ++i) {
         const int o = n0 + r0 + RPP * i;
-        b_off[i] = o < a.ocg ? (unsigned)(o * a.Kp * 2 + kv * 16) : OOB_B;
+        b_off[i] = o < a.ocg ? (unsigned)(o * a.Kp * 2 + kv * 16) : SI_OOB_HALF;
     }
 
     // Register prefetch ring, DEPTH K-tiles deep.  Measured on YOLOv5s batch 32 (MI355X): depth 1 12.2 k img/s, depth 2
@@ -344,12 +307,12 @@ __global__ __launch_bounds__(256) void conv_igemm_f16_kernel(const ConvArgsH a) 
             const unsigned du = (unsigned)(cb - a.up_cb0) * (unsigned)(BKH * 2);
 #pragma unroll
             for (int i = 0; i < A_IT; ++i)
-                qa[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_up, u_off[i] == OOB_A ? OOB_A : u_off[i] + du, 0, 0);
+                qa[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_up, u_off[i] == SI_OOB ? SI_OOB : u_off[i] + du, 0, 0);
         } else {
 #pragma unroll
             for (int i = 0; i < A_IT; ++i) {
                 const bool ok = ((a_mask[i] >> tapbit) & 1ull) && cok;
-                qa[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_in, ok ? a_off[i] + delta : OOB_A, 0, 0);
+                qa[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_in, ok ? a_off[i] + delta : SI_OOB, 0, 0);
             }
         }
         const unsigned kb = (unsigned)kt * (BKH * 2);
@@ -494,11 +457,9 @@ __global__ __launch_bounds__(256, MINW) void conv_igemm_f16_bd_kernel(const Conv
     const int wm = wave / WN, wn = wave - wm * WN;
     const int l31 = lane & 31, lh = lane >> 5;
 
-    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<half_t*>(a.in + (size_t)g * a.icg), 0, a.in_bytes - (unsigned)g * a.icg * 2u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_in = si_buffer(a.in + (size_t)g * a.icg, a.in_bytes - (unsigned)g * a.icg * 2u);
     const unsigned wl_group_bytes = (unsigned)a.wl_nb * (unsigned)a.wl_ks * 1024u;
-    const __amdgpu_buffer_rsrc_t rs_wl = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<half_t*>(a.wl) + (size_t)g * (wl_group_bytes / 2u), 0, wl_group_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_wl = si_buffer(a.wl + (size_t)g * (wl_group_bytes / 2u), wl_group_bytes);
 
     unsigned a_off[A_IT];
     unsigned long long a_mask[A_IT];
@@ -513,9 +474,9 @@ __global__ __launch_bounds__(256, MINW) void conv_igemm_f16_bd_kernel(const Conv
             a_off[i] = (unsigned)m * (unsigned)(a.in_ld * 2) + (unsigned)(kv * 16);
             a_mask[i] = 1ull;
         } else if (m < a.M) {
-            const int img = fast_div_h(m, a.ohow, a.mg_ohow);
+            const int img = si_fast_div(m, a.ohow, a.mg_ohow);
             const int rem = m - img * a.ohow;
-            const int oy = fast_div_h(rem, a.ow, a.mg_ow);
+            const int oy = si_fast_div(rem, a.ow, a.mg_ow);
             const int ox = rem - oy * a.ow;
             const int y0 = oy * a.sh - a.pt, x0 = ox * a.sw - a.pl;
             a_off[i] = (unsigned)((img * a.ih + y0) * a.iw + x0) * (unsigned)(a.in_ld * 2) + (unsigned)(kv * 16);
@@ -533,7 +494,7 @@ __global__ __launch_bounds__(256, MINW) void conv_igemm_f16_bd_kernel(const Conv
 #pragma unroll
     for (int u = 0; u < TN; ++u) {
         const int nb = (n0 >> 5) + wn * TN + u;
-        b_off[u] = nb < a.wl_nb ? (unsigned)nb * (unsigned)a.wl_ks * 1024u + (unsigned)lane * 16u : OOB_B;
+        b_off[u] = nb < a.wl_nb ? (unsigned)nb * (unsigned)a.wl_ks * 1024u + (unsigned)lane * 16u : SI_OOB_HALF;
     }
 
     // The K loop is ONE basic block: every load is issued unconditionally and a K-tile behind the last one is an out-of-range
@@ -551,7 +512,7 @@ __global__ __launch_bounds__(256, MINW) void conv_igemm_f16_bd_kernel(const Conv
 #pragma unroll
         for (int i = 0; i < A_IT; ++i) {
             const bool ok = ((a_mask[i] >> tapbit) & 1ull) && cok;
-            ra[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_in, ok ? a_off[i] + delta : OOB_A, 0, 0);
+            ra[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_in, ok ? a_off[i] + delta : SI_OOB, 0, 0);
         }
         // branch-free walk: kx, then ky, then the channel block
         ++kx;
@@ -575,7 +536,7 @@ __global__ __launch_bounds__(256, MINW) void conv_igemm_f16_bd_kernel(const Conv
         const unsigned kb = (unsigned)(live ? kt : 0) * (unsigned)(QS * 1024);
 #pragma unroll
         for (int u = 0; u < TN; ++u) {
-            const unsigned vo = live ? b_off[u] : OOB_B;
+            const unsigned vo = live ? b_off[u] : SI_OOB_HALF;
 #pragma unroll
             for (int s = 0; s < QS; ++s)
                 q[u][s] = __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(rs_wl, vo + (unsigned)(s * 1024), kb, 0));
@@ -751,9 +712,8 @@ __global__ __launch_bounds__(256, NCH <= 2 ? SI_DET_MINW : 2) void detect_f16_ti
     const int valid = min(64, a.ohow - pix0);
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l31 = lane & 31, lh = lane >> 5;
 
-    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<half_t*>(a.in), 0, a.in_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_wl = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<half_t*>(a.wl), 0, (unsigned)a.wl_nb * (unsigned)a.wl_ks * 1024u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_in = si_buffer(a.in, a.in_bytes);
+    const __amdgpu_buffer_rsrc_t rs_wl = si_buffer(a.wl, (unsigned)a.wl_nb * (unsigned)a.wl_ks * 1024u);
 
     u32x4 ra[A_IT];
 #pragma unroll
@@ -761,13 +721,13 @@ __global__ __launch_bounds__(256, NCH <= 2 ? SI_DET_MINW : 2) void detect_f16_ti
         const int idx = tid + 256 * i;
         const int row = idx / VPR, kv = idx - row * VPR;
         const unsigned off = (unsigned)(img * a.ohow + pix0 + row) * (unsigned)(a.in_ld * 2) + (unsigned)(kv * 16);
-        ra[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_in, (row < valid && !(SI_DET_ABL & 4)) ? off : OOB_A, 0, 0);
+        ra[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_in, (row < valid && !(SI_DET_ABL & 4)) ? off : SI_OOB, 0, 0);
     }
     unsigned b_off[2];
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
         const int nb = wave * 2 + u;
-        b_off[u] = nb < a.wl_nb ? (unsigned)nb * (unsigned)a.wl_ks * 1024u + (unsigned)lane * 16u : OOB_B;
+        b_off[u] = nb < a.wl_nb ? (unsigned)nb * (unsigned)a.wl_ks * 1024u + (unsigned)lane * 16u : SI_OOB_HALF;
     }
     f16x8 rb[RING][2];
 #pragma unroll
@@ -840,7 +800,7 @@ __global__ __launch_bounds__(256, NCH <= 2 ? SI_DET_MINW : 2) void detect_f16_ti
                 const int blk = wave * 2 + u;   // wave-uniform
                 float v[16];
 #pragma unroll
-                for (int e = 0; e < 16; ++e) v[e] = __builtin_amdgcn_rcpf(1.0f + __expf(-(acc[t][u][e] + bv[u])));
+                for (int e = 0; e < 16; ++e) v[e] = si_sigmoid_fast(acc[t][u][e] + bv[u]);
                 if (blk == 0 || blk == 2 || blk == 5) {
                     const int oo = col[u] < 255 ? col[u] : 0;
                     const int anc = oo / 85;
@@ -852,7 +812,7 @@ __global__ __launch_bounds__(256, NCH <= 2 ? SI_DET_MINW : 2) void detect_f16_ti
                     for (int e = 0; e < 16; ++e) auxv[e] = 0.0f;
                     if (is_box) {
 #pragma unroll
-                        for (int e = 0; e < 16; ++e) auxv[e] = ap[((e & 3) + 8 * (e >> 2)) * 6];
+                        for (int e = 0; e < 16; ++e) auxv[e] = ap[Mma<32>::row(e) * 6];
                     }
                     const unsigned mxy = is_xy ? ~0u : 0u, mwh = (is_box && !is_xy) ? ~0u : 0u, msg = is_box ? 0u : ~0u;
 #pragma unroll
@@ -867,7 +827,7 @@ __global__ __launch_bounds__(256, NCH <= 2 ? SI_DET_MINW : 2) void detect_f16_ti
                 if (col[u] < 255) {
                     float* const sp = stage + 4 * lh * 255 + col[u];
 #pragma unroll
-                    for (int e = 0; e < 16; ++e) sp[((e & 3) + 8 * (e >> 2)) * 255] = v[e];
+                    for (int e = 0; e < 16; ++e) sp[Mma<32>::row(e) * 255] = v[e];
                 }
             }
         } else if (rows > 0) {
@@ -885,14 +845,14 @@ __global__ __launch_bounds__(256, NCH <= 2 ? SI_DET_MINW : 2) void detect_f16_ti
                 if (is_box) {
 #pragma unroll
                     for (int e = 0; e < 16; ++e) {
-                        const int dm = (e & 3) + 8 * (e >> 2) + 4 * lh;
+                        const int dm = Mma<32>::row(e) + 4 * lh;
                         auxv[e] = ap[(dm < rows ? dm : 0) * a.yna * 2];
                     }
                 }
 #pragma unroll
                 for (int e = 0; e < 16; ++e) {
-                    const int dm = (e & 3) + 8 * (e >> 2) + 4 * lh;
-                    const float sg = (SI_DET_ABL & 1) ? acc[t][u][e] + bv[u] : __builtin_amdgcn_rcpf(1.0f + __expf(-(acc[t][u][e] + bv[u])));
+                    const int dm = Mma<32>::row(e) + 4 * lh;
+                    const float sg = (SI_DET_ABL & 1) ? acc[t][u][e] + bv[u] : si_sigmoid_fast(acc[t][u][e] + bv[u]);
                     const float aux = auxv[e];
                     const float t2 = sg * 2.0f;
                     const float xy = (t2 + aux) * a.ystride;
@@ -969,9 +929,8 @@ __global__ __launch_bounds__(256, CB == 64 ? 2 : 3) void conv_c32_patch_f16_kern
 
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l31 = lane & 31, lh = lane >> 5;
     const int wm = wave / NBW, wn = wave - wm * NBW;
-    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<half_t*>(a.in), 0, a.in_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_wl = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<half_t*>(a.wl), 0, (unsigned)a.wl_nb * (unsigned)a.wl_ks * 1024u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_in = si_buffer(a.in, a.in_bytes);
+    const __amdgpu_buffer_rsrc_t rs_wl = si_buffer(a.wl, (unsigned)a.wl_nb * (unsigned)a.wl_ks * 1024u);
 
     // staging chunks of this thread: chunk c -> (patch row, patch column, 16-byte channel chunk); LDS offsets are item-invariant
     int l_off[N_IT], c_pr[N_IT], c_px[N_IT], c_ch[N_IT];
@@ -993,7 +952,7 @@ __global__ __launch_bounds__(256, CB == 64 ? 2 : 3) void conv_c32_patch_f16_kern
             const int gy = y0 + c_pr[i], gx = x0 + c_px[i];
             const bool ok = l_off[i] >= 0 && (unsigned)gy < (unsigned)a.ih && (unsigned)gx < (unsigned)a.iw;
             const unsigned off = (unsigned)((img * a.ih + gy) * a.iw + gx) * (unsigned)(a.in_ld * 2) + (unsigned)(c_ch[i] * 16);
-            rp[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_in, ok ? off : OOB_A, 0, 0);
+            rp[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_in, ok ? off : SI_OOB, 0, 0);
         }
     };
     auto commit = [&](int buf) {
@@ -1008,7 +967,7 @@ __global__ __launch_bounds__(256, CB == 64 ? 2 : 3) void conv_c32_patch_f16_kern
     // this wave's column block of the weights: 18 k-steps (tap-major, two 16-channel halves per tap), resident in registers
     f16x8 wf[KS];
     {
-        const unsigned vo = wn < a.wl_nb ? (unsigned)wn * (unsigned)a.wl_ks * 1024u + (unsigned)lane * 16u : OOB_B;
+        const unsigned vo = wn < a.wl_nb ? (unsigned)wn * (unsigned)a.wl_ks * 1024u + (unsigned)lane * 16u : SI_OOB_HALF;
 #pragma unroll
         for (int s = 0; s < KS; ++s) wf[s] = __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(rs_wl, vo, (unsigned)(s * 1024), 0));
     }
@@ -1036,7 +995,7 @@ __global__ __launch_bounds__(256, CB == 64 ? 2 : 3) void conv_c32_patch_f16_kern
         if (HAS_RES) {
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int r = (e & 3) + 8 * (e >> 2) + 4 * lh;
+                const int r = Mma<32>::row(e) + 4 * lh;
                 const int oy = oy0 + (r >> 4), ox = ox0 + (r & 15);
                 const bool in = oy < a.oh && ox < a.ow && o < a.ocg;
                 rv[e] = a.res[in ? (size_t)((img * a.oh + oy) * a.ow + ox) * a.res_ld + o : (size_t)0];
@@ -1072,20 +1031,20 @@ __global__ __launch_bounds__(256, CB == 64 ? 2 : 3) void conv_c32_patch_f16_kern
             // buffer stores, everything that keeps a value from being written (its pixel outside the tensor, its channel past the last one) as an
             // out-of-range OFFSET: no branch around a store, so the wait in front of the next patch's commit() counts the stores instead of
             // draining them (conv_stem_s2c32_f16.hip BST; LAB_NOTEBOOK R6.10)
-            const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(a.out, 0, a.out_bytes, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rs_out = si_buffer(a.out, a.out_bytes);
             const int ow_live = o < a.ocg ? a.ow : 0;
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int r = (e & 3) + 8 * (e >> 2) + 4 * lh;
+                const int r = Mma<32>::row(e) + 4 * lh;
                 const int oy = oy0 + (r >> 4), ox = ox0 + (r & 15);
                 // ACT1 == SiLU: SiLU then nothing (the YOLOv5 forms); otherwise whatever act1 / act2 the layer carries (ResNet's
                 // ReLU before or behind the shortcut), as epilogue_plain evaluates them
-                float v = ACT1 == SI_ACT_SILU ? act_c<SI_ACT_SILU>(acc[e] + bv, a.act_param) : act_h(a.act1, acc[e] + bv, a.act_param);
+                float v = ACT1 == SI_ACT_SILU ? si_act<SI_ACT_SILU>(acc[e] + bv, a.act_param) : si_act(a.act1, acc[e] + bv, a.act_param);
                 if (HAS_RES) v += (float)rv[e];
-                if (ACT1 != SI_ACT_SILU) v = act_h(a.act2, v, a.act_param);
+                if (ACT1 != SI_ACT_SILU) v = si_act(a.act2, v, a.act_param);
                 const unsigned off = ((unsigned)((img * a.oh + oy) * a.ow + ox) * (unsigned)a.out_ld + (unsigned)o) * 2u;
                 __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, si_store_cast<half_t>(v)), rs_out,
-                                                      (oy < a.oh && ox < ow_live) ? off : OOB_A, 0, 0);
+                                                      (oy < a.oh && ox < ow_live) ? off : SI_OOB, 0, 0);
             }
         }
         if (next < items) {
@@ -1265,8 +1224,8 @@ int dispatch_h(const SiConv2dDesc* d, const void* in, const void* w_packed, cons
     a.Kp = d->kh * d->kw * f16_icg_pad(d);
     a.M = d->n * d->oh * d->ow;
     a.ohow = d->oh * d->ow;
-    a.mg_ohow = a.ohow > 1 ? (unsigned)(0x100000000ull / (unsigned)a.ohow) : 0xFFFFFFFFu;
-    a.mg_ow = d->ow > 1 ? (unsigned)(0x100000000ull / (unsigned)d->ow) : 0xFFFFFFFFu;
+    a.mg_ohow = si_magic(a.ohow);
+    a.mg_ow = si_magic(d->ow);
     a.m_tiles = a.n_tiles = 0;
     a.act1 = d->act1; a.act2 = d->act2; a.act_param = d->act_param;
     a.in_bytes = (unsigned)in_bytes;

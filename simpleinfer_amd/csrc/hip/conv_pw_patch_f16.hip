@@ -21,16 +21,7 @@
 
 #pragma clang fp contract(off)
 
-typedef _Float16 half_t;
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
-
-constexpr unsigned OOB = 0xFFFFFF00u;   // beyond any resource below: the load returns zeros
 
 struct PwPatchArgs {
     const half_t* x;            // the pair's input [n][ih][iw][x_ld]
@@ -53,8 +44,6 @@ struct PwPatchArgs {
     half_t* out3;
     int out3_ld;
 };
-
-__device__ __forceinline__ float silu(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
 
 // CB = 64: the geometry of conv_c32_patch_f16_kernel<1, 2, .., 64> -- 4 x 16-pixel tiles, waves 2 (row pairs) x 2 (column blocks), 144-byte
 // pixels, 2816-byte patch rows; CB = 32: of <1, 1, .., 32> -- 8 x 16-pixel tiles, four row-pair waves, 80-byte pixels, 1536-byte rows.
@@ -81,9 +70,9 @@ __global__ __launch_bounds__(256, CB == 64 ? 2 : 3) void conv_pw_patch_f16_kerne
 
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l31 = lane & 31, lh = lane >> 5;
     const int wm = wave / NBW, wn = wave - wm * NBW;
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<half_t*>(a.x), 0, a.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_wl = __builtin_amdgcn_make_buffer_rsrc(const_cast<half_t*>(a.wl), 0, (unsigned)NBW * KS * 1024u, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_wa = __builtin_amdgcn_make_buffer_rsrc(const_cast<half_t*>(a.wlA), 0, (unsigned)NBW * QS * 1024u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_x = si_buffer(a.x, a.x_bytes);
+    const __amdgpu_buffer_rsrc_t rs_wl = si_buffer(a.wl, (unsigned)NBW * KS * 1024u);
+    const __amdgpu_buffer_rsrc_t rs_wa = si_buffer(a.wlA, (unsigned)NBW * QS * 1024u);
 
     // staging chunks of this thread: chunk c -> (patch pixel, 16-byte channel chunk); item-invariant
     int l_off[N_IT], c_pos[N_IT];   // (c_pos: patch row << 8 | patch column)
@@ -104,7 +93,7 @@ __global__ __launch_bounds__(256, CB == 64 ? 2 : 3) void conv_pw_patch_f16_kerne
             const int gy = y0 + (c_pos[i] >> 8), gx = x0 + (c_pos[i] & 255);
             const bool ok = l_off[i] >= 0 && (unsigned)gy < (unsigned)a.ih && (unsigned)gx < (unsigned)a.iw;
             const unsigned off = (unsigned)((img * a.ih + gy) * a.iw + gx) * (unsigned)(a.x_ld * 2) + (unsigned)((tid % CH8) * 16);
-            rp[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_x, ok ? off : OOB, 0, 0);
+            rp[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_x, ok ? off : SI_OOB, 0, 0);
         }
     };
     auto commit = [&]() {
@@ -129,12 +118,12 @@ __global__ __launch_bounds__(256, CB == 64 ? 2 : 3) void conv_pw_patch_f16_kerne
                 *reinterpret_cast<u32x4*>(wa_s + (tid + 256 * i) * 16) = __builtin_amdgcn_raw_buffer_load_b128(rs_wa, (unsigned)(tid + 256 * i) * 16u, 0, 0);
     }
     if (CV3) {
-        const __amdgpu_buffer_rsrc_t rs_w3 = __builtin_amdgcn_make_buffer_rsrc(const_cast<half_t*>(a.w3), 0, 4u * 8u * 1024u, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs_w3 = si_buffer(a.w3, 4u * 8u * 1024u);
 #pragma unroll
         for (int i = 0; i < 8; ++i)
             *reinterpret_cast<u32x4*>(w3_s + (tid + 256 * i) * 16) = __builtin_amdgcn_raw_buffer_load_b128(rs_w3, (unsigned)(tid + 256 * i) * 16u, 0, 0);
     }
-    const __amdgpu_buffer_rsrc_t rs_z = __builtin_amdgcn_make_buffer_rsrc(const_cast<half_t*>(CV3 ? a.z : a.x), 0, CV3 ? a.z_bytes : 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_z = si_buffer(CV3 ? a.z : a.x, CV3 ? a.z_bytes : 0u);
     const unsigned char* const WA = wa_s + wn * QS * 1024 + lane * 16;
     const int o = wn * 32 + l31;
     const float bv = a.bias ? a.bias[o] : 0.0f;
@@ -177,7 +166,7 @@ __global__ __launch_bounds__(256, CB == 64 ? 2 : 3) void conv_pw_patch_f16_kerne
                         const f32x4 bj = *reinterpret_cast<const f32x4*>(ba + 8 * j);
                         f16x4 hv;
 #pragma unroll
-                        for (int i = 0; i < 4; ++i) hv[i] = si_store_cast<half_t>(silu(acc0[4 * j + i] + bj[i]));
+                        for (int i = 0; i < 4; ++i) hv[i] = si_store_cast<half_t>(si_silu_fast(acc0[4 * j + i] + bj[i]));
                         if (!inside) hv = f16x4{(half_t)0.0f, (half_t)0.0f, (half_t)0.0f, (half_t)0.0f};
                         *reinterpret_cast<f16x4*>(patch + p_off[t] + j * 16) = hv;
                     }
@@ -234,7 +223,7 @@ __global__ __launch_bounds__(256, CB == 64 ? 2 : 3) void conv_pw_patch_f16_kerne
             for (int i = 0; i < 2; ++i) {
                 const int c = tid + 256 * i, px = c >> 3, oy = ty * TR + (px >> 4), ox = tx * 16 + (px & 15);
                 const unsigned off = (unsigned)((img * a.ih + oy) * a.iw + ox) * (unsigned)(a.z_ld * 2) + (unsigned)((c & 7) * 16);
-                zr[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_z, (oy < a.ih && ox < a.iw) ? off : OOB, 0, 0);
+                zr[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_z, (oy < a.ih && ox < a.iw) ? off : SI_OOB, 0, 0);
             }
         }
         // ---- the 3x3 conv from the patch: conv_c32_patch_f16_kernel's loop and epilogue
@@ -242,7 +231,7 @@ __global__ __launch_bounds__(256, CB == 64 ? 2 : 3) void conv_pw_patch_f16_kerne
         auto load_res = [&]() {
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int r = (e & 3) + 8 * (e >> 2) + 4 * lh;
+                const int r = Mma<32>::row(e) + 4 * lh;
                 const int oy = oy0 + (r >> 4), ox = ox0 + (r & 15);
                 const bool in = oy < a.ih && ox < a.iw;
                 rv[e] = a.res[in ? (size_t)((img * a.ih + oy) * a.iw + ox) * a.res_ld + o : (size_t)0];
@@ -277,8 +266,8 @@ __global__ __launch_bounds__(256, CB == 64 ? 2 : 3) void conv_pw_patch_f16_kerne
             unsigned char* const T = xbuf;
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int r = (e & 3) + 8 * (e >> 2) + 4 * lh;
-                float v = silu(acc[e] + bv);
+                const int r = Mma<32>::row(e) + 4 * lh;
+                float v = si_silu_fast(acc[e] + bv);
                 if (HAS_RES) v += (float)rv[e];
                 *reinterpret_cast<half_t*>(T + (32 * wm + r) * TP3 + o * 2) = si_store_cast<half_t>(v);
             }
@@ -315,25 +304,25 @@ __global__ __launch_bounds__(256, CB == 64 ? 2 : 3) void conv_pw_patch_f16_kerne
                 half_t* const ob = a.out3 + o3;
 #pragma unroll
                 for (int e = 0; e < 16; ++e) {
-                    const int r = (e & 3) + 8 * (e >> 2) + 4 * lh;
+                    const int r = Mma<32>::row(e) + 4 * lh;
                     const int oy = oy0 + (r >> 4), ox = ox0 + (r & 15);
-                    if (oy < a.ih && ox < a.iw) ob[(size_t)((img * a.ih + oy) * a.iw + ox) * a.out3_ld] = si_store_cast<half_t>(silu(acc3[e] + b3));
+                    if (oy < a.ih && ox < a.iw) ob[(size_t)((img * a.ih + oy) * a.iw + ox) * a.out3_ld] = si_store_cast<half_t>(si_silu_fast(acc3[e] + b3));
                 }
             }
             if (next < a.items) __syncthreads();   // every wave is done with the tile image: the next item's x goes over it
         } else {
             // buffer stores, the out-of-range pixel as an out-of-range offset: no branch around a store, so the wait in front of the next item's
             // commit() counts them instead of draining them (conv_stem_s2c32_f16.hip BST; LAB_NOTEBOOK R6.10)
-            const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(a.out, 0, a.out_bytes, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rs_out = si_buffer(a.out, a.out_bytes);
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int r = (e & 3) + 8 * (e >> 2) + 4 * lh;
+                const int r = Mma<32>::row(e) + 4 * lh;
                 const int oy = oy0 + (r >> 4), ox = ox0 + (r & 15);
-                float v = silu(acc[e] + bv);
+                float v = si_silu_fast(acc[e] + bv);
                 if (HAS_RES) v += (float)rv[e];
                 const unsigned off = ((unsigned)((img * a.ih + oy) * a.iw + ox) * (unsigned)a.out_ld + (unsigned)o) * 2u;
                 __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, si_store_cast<half_t>(v)), rs_out,
-                                                      (oy < a.ih && ox < a.iw) ? off : OOB, 0, 0);
+                                                      (oy < a.ih && ox < a.iw) ? off : SI_OOB, 0, 0);
             }
         }
         if (next < a.items) {

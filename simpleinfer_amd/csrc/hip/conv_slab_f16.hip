@@ -35,14 +35,6 @@
 
 #pragma clang fp contract(off)
 
-typedef _Float16 half_t;
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-
 namespace {
 
 struct SlabArgs {
@@ -67,22 +59,6 @@ struct SlabArgs {
     const float* biasA;
     int wlA_nb, wlA_ks, pr, n_xpix, x_blk;
 };
-
-constexpr unsigned OOB = 0xFFFFFF00u;
-constexpr unsigned OOB_W = 0x80000000u;
-
-__device__ __forceinline__ int fdiv(int n, int d, unsigned mg) {
-    unsigned q = __umulhi((unsigned)n, mg);
-    if ((unsigned)n - q * (unsigned)d >= (unsigned)d) ++q;
-    return (int)q;
-}
-
-template <int ACT>
-__device__ __forceinline__ float act_ct(float v) {
-    if (ACT == SI_ACT_RELU) return fmaxf(v, 0.0f);
-    if (ACT == SI_ACT_SILU) return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v));
-    return v;
-}
 
 #ifndef SI_SLAB_NB
 #define SI_SLAB_NB 6
@@ -131,23 +107,21 @@ __global__ __launch_bounds__(W2 ? 512 : 256, W2 ? 2 : 1) void conv3x3s1_slab_f16
     // only): an XCD takes WHOLE images -- image 8 k + (b & 7) -- so that the halo rows two neighbouring slabs both fetch, and the patch
     // the output-channel groups of a slab share, meet in one L2
     const int b8 = blockIdx.x & 7, bq = blockIdx.x >> 3;
-    const int bqq = fdiv(bq, a.n_ocg, a.mg_nocg);
+    const int bqq = si_fast_div(bq, a.n_ocg, a.mg_nocg);
     const int ocg = bq - bqq * a.n_ocg;
-    const int imgq = fdiv(bqq, a.slabs_per_img, a.mg_spi);
+    const int imgq = si_fast_div(bqq, a.slabs_per_img, a.mg_spi);
     const int img = imgq * 8 + b8, y0 = (bqq - imgq * a.slabs_per_img) * a.th;
     if (img >= a.n_img) return;
     const int rows_here = min(a.th, a.oh - y0);
     const int npix = rows_here * a.ow;
 
-    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<half_t*>(a.in), 0, a.in_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_wl = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<half_t*>(a.wl), 0, (unsigned)a.wl_nb * (unsigned)a.wl_ks * 1024u, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_bias = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(a.bias ? a.bias : reinterpret_cast<const float*>(a.in)), 0, a.bias ? (unsigned)a.oc * 4u : 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_in = si_buffer(a.in, a.in_bytes);
+    const __amdgpu_buffer_rsrc_t rs_wl = si_buffer(a.wl, (unsigned)a.wl_nb * (unsigned)a.wl_ks * 1024u);
+    const __amdgpu_buffer_rsrc_t rs_bias = si_buffer(a.bias ? a.bias : reinterpret_cast<const float*>(a.in), a.bias ? (unsigned)a.oc * 4u : 0u);
 
     // this wave's 32 output channels: the weight ring
     const int nb = ocg * 4 + wave;
-    const unsigned w_voff = nb < a.wl_nb ? (unsigned)nb * (unsigned)a.wl_ks * 1024u + (unsigned)lane * 16u : OOB_W;
+    const unsigned w_voff = nb < a.wl_nb ? (unsigned)nb * (unsigned)a.wl_ks * 1024u + (unsigned)lane * 16u : SI_OOB_HALF;
     f16x8 rb[NB];
     u32x4 rp[N_IT];
     int l_off[N_IT];
@@ -170,14 +144,14 @@ __global__ __launch_bounds__(W2 ? 512 : 256, W2 ? 2 : 1) void conv3x3s1_slab_f16
 #pragma unroll
         for (int i = 0; i < N_IT; ++i) {
             const int q = (tid >> 3) + (NT / 8) * i;
-            const int pr = fdiv(q, a.pc, a.mg_pc), px = q - pr * a.pc;
+            const int pr = si_fast_div(q, a.pc, a.mg_pc), px = q - pr * a.pc;
             const int gy = y0 - 1 + pr, gx = px - 1;
             const bool live = q < a.n_ppix;
             const bool ok = live && (unsigned)gy < (unsigned)a.ih && (unsigned)gx < (unsigned)a.iw && !(SI_SLAB_ABL & 1);
             unsigned go = (unsigned)(gbase + pr * a.iw + px) * pitch + (unsigned)(ch * 16);
             int lo = pr * a.rowp + px * 144 + ch * 16;
             asm volatile("" : "+v"(go), "+v"(lo));   // (computed for every lane, then selected: no exec-mask branches around the arithmetic)
-            g_off[i] = ok ? go : OOB;
+            g_off[i] = ok ? go : SI_OOB;
             l_off[i] = live ? lo : a.rowp - 16;   // (a dead chunk lands in the unused tail of patch row 0)
             rp[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_in, g_off[i], 0, 0);
         }
@@ -221,12 +195,10 @@ __global__ __launch_bounds__(W2 ? 512 : 256, W2 ? 2 : 1) void conv3x3s1_slab_f16
             const int c = tid + NT * i;
             const int q = c >> LOG_C8, ch = c & (C8 - 1);
             const bool ok = q >= qlo && q < qhi && !(SI_SLAB_ABL & 1);
-            rx[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_in, ok ? (unsigned)(gpix0 + q) * pitch + (unsigned)(ch * 16) : OOB, 0, 0);
+            rx[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_in, ok ? (unsigned)(gpix0 + q) * pitch + (unsigned)(ch * 16) : SI_OOB, 0, 0);
         }
-        const __amdgpu_buffer_rsrc_t rs_wlA = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<half_t*>(a.wlA), 0, (unsigned)a.wlA_nb * (unsigned)a.wlA_ks * 1024u, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rs_biasA = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<float*>(a.biasA ? a.biasA : reinterpret_cast<const float*>(a.in)), 0, a.biasA ? (unsigned)(NBLK * 64) * 4u : 0u, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs_wlA = si_buffer(a.wlA, (unsigned)a.wlA_nb * (unsigned)a.wlA_ks * 1024u);
+        const __amdgpu_buffer_rsrc_t rs_biasA = si_buffer(a.biasA ? a.biasA : reinterpret_cast<const float*>(a.in), a.biasA ? (unsigned)(NBLK * 64) * 4u : 0u);
         unsigned wA_voff[TNA];
         f16x8 rbA[NBA][TNA];
 #pragma unroll
@@ -305,14 +277,14 @@ __global__ __launch_bounds__(W2 ? 512 : 256, W2 ? 2 : 1) void conv3x3s1_slab_f16
 #pragma unroll
             for (int t = X0; t < X1; ++t) {
                 const int q = t * 32 + l31;
-                const int r = fdiv(q < a.n_xpix ? q : 0, a.ow, a.mg_ow), cx = q - r * a.ow;
+                const int r = si_fast_div(q < a.n_xpix ? q : 0, a.ow, a.mg_ow), cx = q - r * a.ow;
                 const bool row_ok = (unsigned)(y0 - 1 + r) < (unsigned)a.ih;
                 unsigned char* const yp = slab_smem + ((chan0 >> 6) * a.blk_bytes + r * a.rowp + (cx + 1) * 144 + (chan0 & 63) * 2);
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     f16x4 hv;
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) hv[j] = row_ok ? si_store_cast<half_t>(act_ct<SI_ACT_SILU>(acc0[t][u][4 * g + j] + bA[g][j])) : (half_t)0.0f;
+                    for (int j = 0; j < 4; ++j) hv[j] = row_ok ? si_store_cast<half_t>(si_act<SI_ACT_SILU>(acc0[t][u][4 * g + j] + bA[g][j], a.act_param)) : (half_t)0.0f;
                     if (q < a.n_xpix) *reinterpret_cast<f16x4*>(yp + g * 16) = hv;
                 }
             }
@@ -339,7 +311,7 @@ __global__ __launch_bounds__(W2 ? 512 : 256, W2 ? 2 : 1) void conv3x3s1_slab_f16
     for (int t = 0; t < TM; ++t) {
         int p = t * 32 + l31;
         p = p < npix ? p : 0;
-        const int r = fdiv(p, a.ow, a.mg_ow), c = p - r * a.ow;
+        const int r = si_fast_div(p, a.ow, a.mg_ow), c = p - r * a.ow;
         abase[t] = (unsigned)(r * a.rowp + c * 144 + lh * 16);
     }
     __builtin_amdgcn_sched_barrier(0);   // (otherwise this arithmetic sinks between the first MFMAs)
@@ -373,7 +345,7 @@ __global__ __launch_bounds__(W2 ? 512 : 256, W2 ? 2 : 1) void conv3x3s1_slab_f16
     const unsigned pix0 = (unsigned)((img * a.oh + y0) * a.ow);
     u32x2 rres[HAS_RES ? TM : 1][4];
     f32x4 bq4[4];
-    const __amdgpu_buffer_rsrc_t rs_res = __builtin_amdgcn_make_buffer_rsrc(const_cast<half_t*>(HAS_RES ? a.res : a.in), 0, HAS_RES ? a.res_bytes : 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_res = si_buffer(HAS_RES ? a.res : a.in, HAS_RES ? a.res_bytes : 0u);
 
     // one register quad of the epilogue: bias, activation, shortcut, activation, rounding (epilogue_lean_h's expressions per element),
     // four channels of one pixel as one 8-byte write into the staging image
@@ -384,9 +356,9 @@ __global__ __launch_bounds__(W2 ? 512 : 256, W2 ? 2 : 1) void conv3x3s1_slab_f16
         if (HAS_RES) rv4 = __builtin_bit_cast(f16x4, rres[t][g]);
 #pragma unroll
         for (int j = j0; j < j1; ++j) {
-            float v = act_ct<A1>(acc[t][4 * g + j] + bq4[g][j]);
+            float v = si_act<A1>(acc[t][4 * g + j] + bq4[g][j], a.act_param);
             if (HAS_RES) v += (float)rv4[j];
-            hv[j] = si_store_cast<half_t>(act_ct<A2>(v));
+            hv[j] = si_store_cast<half_t>(si_act<A2>(v, a.act_param));
         }
     };
     auto quad_store = [&](f16x4 hv, int t, int g) {
@@ -428,7 +400,7 @@ __global__ __launch_bounds__(W2 ? 512 : 256, W2 ? 2 : 1) void conv3x3s1_slab_f16
                 const unsigned ro = (pix0 + (unsigned)p) * (unsigned)(a.res_ld * 2) + (unsigned)((nb * 32 + 4 * lh) * 2);
 #pragma unroll
                 for (int g = 0; g < 4; ++g)
-                    rres[t][g] = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(rs_res, p < npix ? ro + (unsigned)(g * 16) : OOB, 0, 0));
+                    rres[t][g] = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(rs_res, p < npix ? ro + (unsigned)(g * 16) : SI_OOB, 0, 0));
                 extra = 4;
             }
             if (!PW && MODE == 0 && b + 1 < NBLK && s == 28) commit(b + 1);
@@ -533,7 +505,7 @@ __global__ __launch_bounds__(W2 ? 512 : 256, W2 ? 2 : 1) void conv3x3s1_slab_f16
     SI_STAMP(4);
 #endif
     {
-        const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(a.out, 0, a.out_bytes, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs_out = si_buffer(a.out, a.out_bytes);
         const unsigned obase = pix0 * (unsigned)(a.out_ld * 2) + (unsigned)(ocg * 256);
 #pragma unroll
         for (int k = 0; k < 2 * TM * 256 / NT; ++k) {
@@ -541,7 +513,7 @@ __global__ __launch_bounds__(W2 ? 512 : 256, W2 ? 2 : 1) void conv3x3s1_slab_f16
             const int pixel = c >> 4, c16 = c & 15;
             const u32x4 val = *reinterpret_cast<const u32x4*>(stage + pixel * STAGE_SP + c16 * 16);
             const unsigned off = obase + (unsigned)pixel * (unsigned)(a.out_ld * 2) + (unsigned)(c16 * 16);
-            if (!(SI_SLAB_ABL & 4)) __builtin_amdgcn_raw_buffer_store_b128(val, rs_out, pixel < npix ? off : OOB, 0, 0);
+            if (!(SI_SLAB_ABL & 4)) __builtin_amdgcn_raw_buffer_store_b128(val, rs_out, pixel < npix ? off : SI_OOB, 0, 0);
             else asm volatile("" ::"v"(val));
         }
     }
@@ -712,10 +684,10 @@ int slab_launch(const SiConv2dDesc* d, const void* in, unsigned long long in_byt
     a.n_ocg = (d->oc + 127) / 128;
     a.rowp = p.rowp; a.blk_bytes = p.blk_bytes;
     a.pc = d->ow + 2;
-    a.mg_pc = (unsigned)(0x100000000ull / (unsigned)a.pc);
-    a.mg_ow = d->ow > 1 ? (unsigned)(0x100000000ull / (unsigned)d->ow) : 0xFFFFFFFFu;
-    a.mg_nocg = a.n_ocg > 1 ? (unsigned)(0x100000000ull / (unsigned)a.n_ocg) : 0xFFFFFFFFu;
-    a.mg_spi = a.slabs_per_img > 1 ? (unsigned)(0x100000000ull / (unsigned)a.slabs_per_img) : 0xFFFFFFFFu;
+    a.mg_pc = si_magic(a.pc);
+    a.mg_ow = si_magic(d->ow);
+    a.mg_nocg = si_magic(a.n_ocg);
+    a.mg_spi = si_magic(a.slabs_per_img);
     a.n_ppix = (p.th + 2) * a.pc;
     a.act1 = d->act1; a.act2 = d->act2; a.act_param = d->act_param;
     const unsigned long long out_bytes = (unsigned long long)d->n * d->oh * d->ow * d->out_ld * 2ull;

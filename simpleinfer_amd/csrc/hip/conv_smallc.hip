@@ -23,9 +23,6 @@
 #include "si_hip.h"
 #include "si_hip_internal.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 // conv_stem_roll.hip: the rolling-window kernel that serves the RGB stride-2 stems (6x6, 7x7, 3x3; <= 64 output channels);
 // this file's kernel remains for every other 1..3-channel shape (other strides / kernel sizes, wider outputs)
 bool si_conv_stemroll_ok(const SiConv2dDesc* d);
@@ -62,18 +59,6 @@ struct SmallCArgs {
     float act_param;
 };
 
-__device__ __forceinline__ float act_any(int act, float v, float p) {
-    switch (act) {
-        case SI_ACT_RELU: return fmaxf(v, 0.0f);
-        case SI_ACT_SILU: return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v));
-        case SI_ACT_SIGMOID: return __builtin_amdgcn_rcpf(1.0f + __expf(-v));
-        case SI_ACT_HARDSIGMOID: return fminf(fmaxf(v * (1.0f / 6.0f) + 0.5f, 0.0f), 1.0f);
-        case SI_ACT_HARDSWISH: return v * fminf(fmaxf(v * (1.0f / 6.0f) + 0.5f, 0.0f), 1.0f);
-        case SI_ACT_LEAKYRELU: return v > 0.0f ? v : v * p;
-        default: return v;
-    }
-}
-
 // NW waves per workgroup (32*NW output pixels along W), NT 32-wide output-channel tiles per wave, RB output rows per
 // item, HP = (kw*c rounded up to even)/2 MFMA steps per kernel row (compile time: 9 for 6x6x3, 11 for 7x7x3),
 // PF = prefetch registers per thread (>= n_in_rows*row_len / (64*NW)).
@@ -105,7 +90,7 @@ __global__ __launch_bounds__(NW * 64) void conv_smallc_rows_kernel(const SmallCA
     // entirely outside, and then an offset outside the buffer makes the hardware return zeros.  Otherwise element-wise
     // loads with per-element bounds.  The values are not touched until they are committed to LDS after the MFMAs.
     constexpr int MAX_ROWS = PF / 4;
-    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.in), 0, a.in_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_in = si_buffer(a.in, a.in_bytes);
     const int row_floats = a.iw * a.c;
     const bool mine = 4 * tid < a.row_len;
     auto prefetch = [&](int item) {
@@ -119,7 +104,7 @@ __global__ __launch_bounds__(NW * 64) void conv_smallc_rows_kernel(const SmallCA
             const bool yok = mine && r < a.n_in_rows && (unsigned)y < (unsigned)a.ih;
             if (VEC) {
                 unsigned off = ((unsigned)((img * a.ih + y) * row_floats + e)) * 4u;  // modulo 2^32
-                if (!(yok && e >= 0 && e + 3 < row_floats)) off = 0xFFFFFF00u;
+                if (!(yok && e >= 0 && e + 3 < row_floats)) off = SI_OOB;
                 pre[r] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_in, off, 0, 0));
             } else {
 #pragma unroll
@@ -127,7 +112,7 @@ __global__ __launch_bounds__(NW * 64) void conv_smallc_rows_kernel(const SmallCA
                     const int ee = e + t;
                     const int px = ee / a.c, ch = ee - px * a.c;
                     unsigned off = ((unsigned)(((img * a.ih + y) * a.iw + px) * a.in_ld + ch)) * 4u;
-                    if (!(yok && ee >= 0 && ee < row_floats)) off = 0xFFFFFF00u;
+                    if (!(yok && ee >= 0 && ee < row_floats)) off = SI_OOB;
                     pre[r][t] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_in, off, 0, 0));
                 }
             }
@@ -216,25 +201,25 @@ __global__ __launch_bounds__(NW * 64) void conv_smallc_rows_kernel(const SmallCA
                 if (simple && a.act1 == SI_ACT_SILU) {
 #pragma unroll
                     for (int e = 0; e < 16; ++e) {
-                        const int ox = oxb + (e & 3) + 8 * (e >> 2);
+                        const int ox = oxb + Mma<32>::row(e);
                         const float v = acc[u][e] + bvu;
-                        if (ox < a.ow) orow[(size_t)ox * a.out_ld] = si_store_cast<OutT>(v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)));
+                        if (ox < a.ow) orow[(size_t)ox * a.out_ld] = si_store_cast<OutT>(si_silu_fast(v));
                     }
                 } else if (simple && a.act1 == SI_ACT_RELU) {
 #pragma unroll
                     for (int e = 0; e < 16; ++e) {
-                        const int ox = oxb + (e & 3) + 8 * (e >> 2);
+                        const int ox = oxb + Mma<32>::row(e);
                         if (ox < a.ow) orow[(size_t)ox * a.out_ld] = si_store_cast<OutT>(fmaxf(acc[u][e] + bvu, 0.0f));
                     }
                 } else {
 #pragma unroll
                     for (int e = 0; e < 16; ++e) {
-                        const int ox = oxb + (e & 3) + 8 * (e >> 2);
+                        const int ox = oxb + Mma<32>::row(e);
                         if (ox < a.ow) {
                             float v = acc[u][e] + bvu;
-                            v = act_any(a.act1, v, a.act_param);
+                            v = si_act(a.act1, v, a.act_param);
                             if (a.res) v += a.res[(mrow + ox) * a.res_ld + o];
-                            v = act_any(a.act2, v, a.act_param);
+                            v = si_act(a.act2, v, a.act_param);
                             orow[(size_t)ox * a.out_ld] = si_store_cast<OutT>(v);
                         }
                     }

@@ -20,17 +20,10 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "si_hip.h"
-#include "si_hip_internal.h"
-
 #pragma clang fp contract(off)
 
-typedef _Float16 half_t;
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+#include "si_hip.h"
+#include "si_hip_internal.h"
 
 namespace {
 
@@ -75,26 +68,6 @@ __device__ __forceinline__ void split_range_report(bool bad, unsigned* flag) {
     if (flag && __builtin_amdgcn_ballot_w64(bad) != 0ull && (threadIdx.x & 63) == 0) *reinterpret_cast<volatile unsigned*>(flag) = 1u;
 }
 
-__device__ __forceinline__ int fdiv(int n, int d, unsigned mg) {
-    unsigned q = __umulhi((unsigned)n, mg);
-    if ((unsigned)n - q * (unsigned)d >= (unsigned)d) ++q;
-    return (int)q;
-}
-
-__device__ __forceinline__ float act_rt(int act, float v, float p) {
-    switch (act) {
-        case SI_ACT_RELU: return fmaxf(v, 0.0f);
-        case SI_ACT_SILU: return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v));
-        case SI_ACT_SIGMOID: return __builtin_amdgcn_rcpf(1.0f + __expf(-v));
-        case SI_ACT_HARDSIGMOID: return fminf(fmaxf(v * (1.0f / 6.0f) + 0.5f, 0.0f), 1.0f);
-        case SI_ACT_HARDSWISH: return v * fminf(fmaxf(v * (1.0f / 6.0f) + 0.5f, 0.0f), 1.0f);
-        case SI_ACT_LEAKYRELU: return v > 0.0f ? v : v * p;
-        default: return v;
-    }
-}
-
-constexpr unsigned OOB_A = 0xFFFFFF00u;
-constexpr unsigned OOB_B = 0x80000000u;
 constexpr float kLoScale = 2048.0f;   // 2^11
 
 // BM x (32 WN) workgroup tile, WM x WN waves (a wave: BM / WM rows x 32 columns of its own -- 1 x 4 for >= 128 output channels: every
@@ -127,12 +100,12 @@ __global__ __launch_bounds__(256, 2) void conv_split3_f32_kernel(const Split3Arg
     const int wave = tid >> 6, lane = tid & 63, l31 = lane & 31, lh = lane >> 5;
     const int wm = wave / WN, wn = wave - wm * WN;
 
-    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.in), 0, a.in_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_in = si_buffer(a.in, a.in_bytes);
     const unsigned wl_bytes = (unsigned)a.wl_nb * (unsigned)a.wl_ks * 1024u;
-    const __amdgpu_buffer_rsrc_t rs_hi = __builtin_amdgcn_make_buffer_rsrc(const_cast<half_t*>(a.wl_hi), 0, wl_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_lo = __builtin_amdgcn_make_buffer_rsrc(const_cast<half_t*>(a.wl_lo), 0, wl_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_hi = si_buffer(a.wl_hi, wl_bytes);
+    const __amdgpu_buffer_rsrc_t rs_lo = si_buffer(a.wl_lo, wl_bytes);
 
-    const __amdgpu_buffer_rsrc_t rs_up = UPS ? __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.up), 0, a.up_bytes, 0x00020000) : rs_in;
+    const __amdgpu_buffer_rsrc_t rs_up = UPS ? si_buffer(a.up, a.up_bytes) : rs_in;
     unsigned a_off[A_IT];
     unsigned u_off[UPS ? A_IT : 1];   // UPS: byte offset of the row's source pixel in the low-resolution tensor
     unsigned a_mask[A_IT];   // tap validity bits (at most 32 taps)
@@ -141,11 +114,11 @@ __global__ __launch_bounds__(256, 2) void conv_split3_f32_kernel(const Split3Arg
         const int m = m0 + r0 + RPP * i;
         a_off[i] = 0;
         a_mask[i] = 0u;
-        if (UPS) u_off[i] = OOB_A;
+        if (UPS) u_off[i] = SI_OOB;
         if (m < a.M) {
-            const int img = fdiv(m, a.ohow, a.mg_ohow);
+            const int img = si_fast_div(m, a.ohow, a.mg_ohow);
             const int rem = m - img * a.ohow;
-            const int oy = fdiv(rem, a.ow, a.mg_ow);
+            const int oy = si_fast_div(rem, a.ow, a.mg_ow);
             const int ox = rem - oy * a.ow;
             if (UPS) {
                 // upsample.cpp:85-92: src = clamp(int(float(dst) * (1 / scale)), 0, in - 1)
@@ -166,7 +139,7 @@ __global__ __launch_bounds__(256, 2) void conv_split3_f32_kernel(const Split3Arg
         }
     }
     const int nb = (n0 >> 5) + wn;
-    const unsigned b_off = nb < a.wl_nb ? (unsigned)nb * (unsigned)a.wl_ks * 1024u + (unsigned)lane * 16u : OOB_B;
+    const unsigned b_off = nb < a.wl_nb ? (unsigned)nb * (unsigned)a.wl_ks * 1024u + (unsigned)lane * 16u : SI_OOB_HALF;
 
     const int nk = a.Kp / BKH;
     int cb = 0, ky = 0, kx = 0;
@@ -180,7 +153,7 @@ __global__ __launch_bounds__(256, 2) void conv_split3_f32_kernel(const Split3Arg
     auto load_b = [&](int slot, int ks) {
         const bool live = ks < ks_tot;
         const unsigned kb = (unsigned)(live ? ks : 0) * 1024u;
-        const unsigned vo = live ? b_off : OOB_B;
+        const unsigned vo = live ? b_off : SI_OOB_HALF;
         rbh[slot] = __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(rs_hi, vo, kb, 0));
         rbl[slot] = __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(rs_lo, vo, kb, 0));
     };
@@ -193,12 +166,12 @@ __global__ __launch_bounds__(256, 2) void conv_split3_f32_kernel(const Split3Arg
             const unsigned du = (unsigned)(cb - a.up_cb0) * (unsigned)(BKH * 4);
 #pragma unroll
             for (int i = 0; i < A_IT; ++i)
-                ra[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_up, (live && u_off[i] != OOB_A) ? u_off[i] + du : OOB_A, 0, 0);
+                ra[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_up, (live && u_off[i] != SI_OOB) ? u_off[i] + du : SI_OOB, 0, 0);
         } else {
 #pragma unroll
             for (int i = 0; i < A_IT; ++i) {
                 const bool ok = ((a_mask[i] >> tapbit) & 1u) && live;
-                ra[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_in, ok ? a_off[i] + delta : OOB_A, 0, 0);
+                ra[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_in, ok ? a_off[i] + delta : SI_OOB, 0, 0);
             }
         }
         ++kx;
@@ -285,7 +258,7 @@ __global__ __launch_bounds__(256, 2) void conv_split3_f32_kernel(const Split3Arg
             }
         split_range_report(bad, a.range_flag);
         const int mrow0 = m0 + wm * TM * 32 + 4 * lh;
-        const int img0 = fdiv(m0, a.ohow, a.mg_ohow);
+        const int img0 = si_fast_div(m0, a.ohow, a.mg_ohow);
         if (m0 + BM <= a.M && m0 - img0 * a.ohow + BM <= a.ohow) {   // (workgroup-uniform: the tile lies inside one image)
             si_yolo_tile_one_image<TM, 1>(a, a.out, accc, mrow0, o, img0);
         } else if (o < a.oc) {
@@ -296,10 +269,10 @@ __global__ __launch_bounds__(256, 2) void conv_split3_f32_kernel(const Split3Arg
             for (int t = 0; t < TM; ++t)
 #pragma unroll
                 for (int e = 0; e < 16; ++e) {
-                    const int m = mrow0 + t * 32 + (e & 3) + 8 * (e >> 2);
+                    const int m = mrow0 + t * 32 + Mma<32>::row(e);
                     if (m < a.M) {
-                        const int img = fdiv(m, a.ohow, a.mg_ohow), pix = m - img * a.ohow;
-                        const float sg = __builtin_amdgcn_rcpf(1.0f + __expf(-(accc[t][0][e] + bv)));
+                        const int img = si_fast_div(m, a.ohow, a.mg_ohow), pix = m - img * a.ohow;
+                        const float sg = si_sigmoid_fast(accc[t][0][e] + bv);
                         const size_t row = (size_t)pix * a.yna + anc;
                         float v = sg;
                         if (e_ < 2) {
@@ -337,12 +310,12 @@ __global__ __launch_bounds__(256, 2) void conv_split3_f32_kernel(const Split3Arg
             const int mb = m0 + (wm * TM + t) * 32 + 4 * lh;
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int m = mb + (e & 3) + 8 * (e >> 2);
+                const int m = mb + Mma<32>::row(e);
                 if (m < a.M) {
                     float v = acc_h[t][e];
-                    v = act_rt(a.act1, v + bv, a.act_param);
+                    v = si_act(a.act1, v + bv, a.act_param);
                     if (a.res) v += a.res[(size_t)m * a.res_ld + o];
-                    ob[(size_t)m * old] = act_rt(a.act2, v, a.act_param);
+                    ob[(size_t)m * old] = si_act(a.act2, v, a.act_param);
                 }
             }
         }
@@ -380,10 +353,10 @@ __global__ __launch_bounds__(256, 2) void detect_split_tile_kernel(const Split3A
     const int valid = min(64, a.ohow - pix0);
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l31 = lane & 31, lh = lane >> 5;
 
-    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.in), 0, a.in_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_in = si_buffer(a.in, a.in_bytes);
     const unsigned wl_bytes = (unsigned)a.wl_nb * (unsigned)a.wl_ks * 1024u;
-    const __amdgpu_buffer_rsrc_t rs_hi = __builtin_amdgcn_make_buffer_rsrc(const_cast<half_t*>(a.wl_hi), 0, wl_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_lo = __builtin_amdgcn_make_buffer_rsrc(const_cast<half_t*>(a.wl_lo), 0, wl_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_hi = si_buffer(a.wl_hi, wl_bytes);
+    const __amdgpu_buffer_rsrc_t rs_lo = si_buffer(a.wl_lo, wl_bytes);
 
     // the A tile: fp32 -> (hi, lo) on the way into LDS, eight vectors per thread at a time
     static_assert(A_IT % 8 == 0, "A tile in batches of eight vectors per thread");
@@ -395,7 +368,7 @@ __global__ __launch_bounds__(256, 2) void detect_split_tile_kernel(const Split3A
             const int idx = tid + 256 * (c + i);
             const int row = idx / VPR, kv = idx - row * VPR;
             const unsigned off = (unsigned)(img * a.ohow + pix0 + row) * (unsigned)(a.in_ld * 4) + (unsigned)(kv * 16);
-            ra[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_in, row < valid ? off : OOB_A, 0, 0);
+            ra[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_in, row < valid ? off : SI_OOB, 0, 0);
         }
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
@@ -418,7 +391,7 @@ __global__ __launch_bounds__(256, 2) void detect_split_tile_kernel(const Split3A
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
         const int nb = wave * 2 + u;
-        b_off[u] = nb < a.wl_nb ? (unsigned)nb * (unsigned)a.wl_ks * 1024u + (unsigned)lane * 16u : OOB_B;
+        b_off[u] = nb < a.wl_nb ? (unsigned)nb * (unsigned)a.wl_ks * 1024u + (unsigned)lane * 16u : SI_OOB_HALF;
         col[u] = wave * 64 + u * 32 + l31;
         bv[u] = (a.bias && col[u] < a.ocg) ? a.bias[col[u]] : 0.0f;
     }
@@ -492,7 +465,7 @@ __global__ __launch_bounds__(256, 2) void detect_split_tile_kernel(const Split3A
                 const int blk = wave * 2 + u;   // wave-uniform
                 float v[16];
 #pragma unroll
-                for (int e = 0; e < 16; ++e) v[e] = __builtin_amdgcn_rcpf(1.0f + __expf(-(accc[t][u][e] + bv[u])));
+                for (int e = 0; e < 16; ++e) v[e] = si_sigmoid_fast(accc[t][u][e] + bv[u]);
                 if (blk == 0 || blk == 2 || blk == 5) {   // (the 32-column blocks that hold x, y, w, h of an anchor: columns 0-3, 85-88, 170-173)
                     const int oo = col[u] < 255 ? col[u] : 0;
                     const int anc = oo / 85;
@@ -504,7 +477,7 @@ __global__ __launch_bounds__(256, 2) void detect_split_tile_kernel(const Split3A
                     for (int e = 0; e < 16; ++e) auxv[e] = 0.0f;
                     if (is_box) {
 #pragma unroll
-                        for (int e = 0; e < 16; ++e) auxv[e] = ap[((e & 3) + 8 * (e >> 2)) * 6];
+                        for (int e = 0; e < 16; ++e) auxv[e] = ap[Mma<32>::row(e) * 6];
                     }
                     const unsigned mxy = is_xy ? ~0u : 0u, mwh = (is_box && !is_xy) ? ~0u : 0u, msg = is_box ? 0u : ~0u;
 #pragma unroll
@@ -519,7 +492,7 @@ __global__ __launch_bounds__(256, 2) void detect_split_tile_kernel(const Split3A
                 if (col[u] < 255) {
                     float* const sp = stage + 4 * lh * 255 + col[u];
 #pragma unroll
-                    for (int e = 0; e < 16; ++e) sp[((e & 3) + 8 * (e >> 2)) * 255] = v[e];
+                    for (int e = 0; e < 16; ++e) sp[Mma<32>::row(e) * 255] = v[e];
                 }
             }
         } else if (rows > 0) {
@@ -538,14 +511,14 @@ __global__ __launch_bounds__(256, 2) void detect_split_tile_kernel(const Split3A
                 if (is_box) {
 #pragma unroll
                     for (int e = 0; e < 16; ++e) {
-                        const int dm = (e & 3) + 8 * (e >> 2) + 4 * lh;
+                        const int dm = Mma<32>::row(e) + 4 * lh;
                         auxv[e] = ap[(dm < rows ? dm : 0) * a.yna * 2];
                     }
                 }
 #pragma unroll
                 for (int e = 0; e < 16; ++e) {
-                    const int dm = (e & 3) + 8 * (e >> 2) + 4 * lh;
-                    const float sg = __builtin_amdgcn_rcpf(1.0f + __expf(-(accc[t][u][e] + bv[u])));
+                    const int dm = Mma<32>::row(e) + 4 * lh;
+                    const float sg = si_sigmoid_fast(accc[t][u][e] + bv[u]);
                     const float aux = auxv[e];
                     const float t2 = sg * 2.0f;
                     const float xy = (t2 + aux) * a.ystride;
@@ -646,8 +619,8 @@ static int split3_launch(const SiConv2dDesc* d, const float* in, const void* w_p
     a.ic = d->ic; a.oc = d->oc; a.Kp = d->kh * d->kw * d->ic;
     a.M = d->n * d->oh * d->ow;
     a.ohow = d->oh * d->ow;
-    a.mg_ohow = a.ohow > 1 ? (unsigned)(0x100000000ull / (unsigned)a.ohow) : 0xFFFFFFFFu;
-    a.mg_ow = d->ow > 1 ? (unsigned)(0x100000000ull / (unsigned)d->ow) : 0xFFFFFFFFu;
+    a.mg_ohow = si_magic(a.ohow);
+    a.mg_ow = si_magic(d->ow);
     a.act1 = d->act1; a.act2 = d->act2; a.act_param = d->act_param;
     a.in_bytes = (unsigned)in_bytes;
     a.ocg = d->oc;

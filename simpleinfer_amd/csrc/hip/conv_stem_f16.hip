@@ -24,13 +24,6 @@
 #include "si_hip.h"
 #include "si_hip_internal.h"
 
-typedef _Float16 half_t;
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
 
 struct StemArgs {
@@ -65,18 +58,6 @@ struct StemArgs {
 #define STEM_EXP(a, bit) 0
 #endif
 
-__device__ __forceinline__ float act_any(int act, float v, float p) {
-    switch (act) {
-        case SI_ACT_RELU: return fmaxf(v, 0.0f);
-        case SI_ACT_SILU: return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v));
-        case SI_ACT_SIGMOID: return __builtin_amdgcn_rcpf(1.0f + __expf(-v));
-        case SI_ACT_HARDSIGMOID: return fminf(fmaxf(v * (1.0f / 6.0f) + 0.5f, 0.0f), 1.0f);
-        case SI_ACT_HARDSWISH: return v * fminf(fmaxf(v * (1.0f / 6.0f) + 0.5f, 0.0f), 1.0f);
-        case SI_ACT_LEAKYRELU: return v > 0.0f ? v : v * p;
-        default: return v;
-    }
-}
-
 // NPW pixel waves x NOT output-channel waves per workgroup (32*NPW output pixels along W, 32*NOT channels), KH kernel
 // rows of GPR 8-value groups, RB output rows per item.  EVEN: every fragment starts on an even half index (stride*C and
 // pad*C even), so it is four aligned dwords; otherwise five dwords are read and funnel-shifted per lane.  VEC: the
@@ -108,7 +89,7 @@ __global__ __launch_bounds__(NPW * NOT * 64, STEM_MINW) void conv_stem_f16_kerne
         img = t; oy0 = rbk * RB; ox0 = wt * TOW;
     };
 
-    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.in), 0, a.in_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_in = si_buffer(a.in, a.in_bytes);
     const int row_floats = a.iw * a.c;
     auto prefetch = [&](int item) {
         int img, oy0, ox0;
@@ -123,7 +104,7 @@ __global__ __launch_bounds__(NPW * NOT * 64, STEM_MINW) void conv_stem_f16_kerne
             if (VEC) {
                 // byte offset modulo 2^32; a vector outside its row gets an offset outside the buffer -> zeros
                 unsigned off = ((unsigned)((img * a.ih + y) * row_floats + e)) * 4u;
-                if (!(yok && e >= 0 && e + 3 < row_floats)) off = 0xFFFFFF00u;
+                if (!(yok && e >= 0 && e + 3 < row_floats)) off = SI_OOB;
                 pre[r] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_in, off, 0, 0));
             } else {
 #pragma unroll
@@ -131,7 +112,7 @@ __global__ __launch_bounds__(NPW * NOT * 64, STEM_MINW) void conv_stem_f16_kerne
                     const int ee = e + t;
                     const int px = ee / a.c, ch = ee - px * a.c;
                     unsigned off = ((unsigned)(((img * a.ih + y) * a.iw + px) * a.in_ld + ch)) * 4u;
-                    if (!(yok && ee >= 0 && ee < row_floats)) off = 0xFFFFFF00u;
+                    if (!(yok && ee >= 0 && ee < row_floats)) off = SI_OOB;
                     pre[r][t] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_in, off, 0, 0));
                 }
             }
@@ -226,23 +207,23 @@ __global__ __launch_bounds__(NPW * NOT * 64, STEM_MINW) void conv_stem_f16_kerne
 #pragma unroll
                     for (int e = 0; e < 16; e += 2) {
                         const unsigned pk = si_pair_halves(act(acc[e] + bvv), act(acc[e + 1] + bvv), odd);
-                        const int dx = (e & 3) + 8 * (e >> 2) + (odd ? 1 : 0);
+                        const int dx = Mma<32>::row(e) + (odd ? 1 : 0);
                         if (o < a.oc && oxb + dx < a.ow) *reinterpret_cast<unsigned*>(pcol + dx * a.out_ld) = pk;
                     }
                 } else if (o < a.oc) {
 #pragma unroll
                     for (int e = 0; e < 16; ++e) {
-                        const int dx = (e & 3) + 8 * (e >> 2);
+                        const int dx = Mma<32>::row(e);
                         if (oxb + dx < a.ow) prow[dx * a.out_ld + o] = si_store_cast<half_t>(act(acc[e] + bvv));
                     }
                 }
             };
             if (a.act1 == SI_ACT_SILU && a.act2 == SI_ACT_NONE)
-                store_tile([](float t) { return t * __builtin_amdgcn_rcpf(1.0f + __expf(-t)); });
+                store_tile([](float t) { return si_silu_fast(t); });
             else if (a.act1 == SI_ACT_RELU && a.act2 == SI_ACT_NONE)
                 store_tile([](float t) { return fmaxf(t, 0.0f); });
             else
-                store_tile([&](float t) { return act_any(a.act2, act_any(a.act1, t, a.act_param), a.act_param); });
+                store_tile([&](float t) { return si_act(a.act2, si_act(a.act1, t, a.act_param), a.act_param); });
         }
 
         if (next < a.items) {
@@ -302,8 +283,8 @@ __global__ __launch_bounds__(W * 64, 4) void conv_stem_split_f32_kernel(const St
 
     half_t* const ring_h = rows_h + wave * 2 * ring_elems;
     half_t* const ring_l = ring_h + ring_elems;
-    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.in), 0, a.in_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(a.out_f32, 0, a.out_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_in = si_buffer(a.in, a.in_bytes);
+    const __amdgpu_buffer_rsrc_t rs_out = si_buffer(a.out_f32, a.out_bytes);
     const int row_floats = a.iw * a.c;
     const int x0 = (ox0 * a.sw - a.pl) * a.c;
     const int e0 = (x0 & ~3) + 4 * lane;   // float index of this lane's vector within an image row
@@ -317,7 +298,7 @@ __global__ __launch_bounds__(W * 64, 4) void conv_stem_split_f32_kernel(const St
         for (int i = 0; i < MAXNR; ++i) {
             const int y = y0 + i;
             unsigned off = ((unsigned)((img * a.ih + y) * row_floats + e0)) * 4u;
-            if (!(mine && i < cnt && (unsigned)y < (unsigned)a.ih)) off = 0xFFFFFF00u;
+            if (!(mine && i < cnt && (unsigned)y < (unsigned)a.ih)) off = SI_OOB;
             pre[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_in, off, 0, 0));
         }
     };
@@ -418,9 +399,9 @@ __global__ __launch_bounds__(W * 64, 4) void conv_stem_split_f32_kernel(const St
                     const int ow_live = (o < a.oc && oy < a.oh && !STEM_EXP(a, 1)) ? a.ow : 0;   // (one compare per store: dead lanes / rows see an empty row)
 #pragma unroll
                     for (int e = 0; e < 16; ++e) {
-                        const int dx = (e & 3) + 8 * (e >> 2);
+                        const int dx = Mma<32>::row(e);
                         // the pixel's distance from the tile's first one travels in the scalar offset (not part of the range check: a dropped store stays dropped)
-                        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, act(acc[e] + bvv)), rs_out, oxb + dx < ow_live ? obase : 0xFFFFFF00u,
+                        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, act(acc[e] + bvv)), rs_out, oxb + dx < ow_live ? obase : SI_OOB,
                                                               dx * a.out_ld * 4, 0);
                     }
                 }
@@ -431,13 +412,13 @@ __global__ __launch_bounds__(W * 64, 4) void conv_stem_split_f32_kernel(const St
         }
     };
     if (a.act1 == SI_ACT_SILU && a.act2 == SI_ACT_NONE)
-        run([](float t) { return t * __builtin_amdgcn_rcpf(1.0f + __expf(-t)); });
+        run([](float t) { return si_silu_fast(t); });
     else if (a.act1 == SI_ACT_RELU && a.act2 == SI_ACT_NONE)
         run([](float t) { return fmaxf(t, 0.0f); });
     else if (a.act1 == SI_ACT_NONE && a.act2 == SI_ACT_NONE)
         run([](float t) { return t; });
     else
-        run([&](float t) { return act_any(a.act2, act_any(a.act1, t, a.act_param), a.act_param); });
+        run([&](float t) { return si_act(a.act2, si_act(a.act1, t, a.act_param), a.act_param); });
     if (a.range_flag && __builtin_amdgcn_ballot_w64(bad) != 0ull && lane == 0) *reinterpret_cast<volatile unsigned*>(a.range_flag) = 1u;
 }
 

@@ -24,14 +24,11 @@
 #include <cstdint>
 #include <cstdlib>
 
-#include "si_hip.h"
-#include "si_hip_internal.h"
-
 // one rounding per operation, whatever instantiation a pixel goes through (bit-exact batch sharding)
 #pragma clang fp contract(off)
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4s __attribute__((ext_vector_type(4)));
+#include "si_hip.h"
+#include "si_hip_internal.h"
 
 // development ablations (tools/build_exp.sh): 1 no output stores, 2 no activation, 4 no row fetch in the loop
 #ifndef SI_STEM_ABLATE
@@ -68,18 +65,6 @@ struct StemArgs {
     float act_param;
 };
 
-__device__ __forceinline__ float stem_act(int act, float v, float p) {
-    switch (act) {
-        case SI_ACT_RELU: return fmaxf(v, 0.0f);
-        case SI_ACT_SILU: return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v));
-        case SI_ACT_SIGMOID: return __builtin_amdgcn_rcpf(1.0f + __expf(-v));
-        case SI_ACT_HARDSIGMOID: return fminf(fmaxf(v * (1.0f / 6.0f) + 0.5f, 0.0f), 1.0f);
-        case SI_ACT_HARDSWISH: return v * fminf(fmaxf(v * (1.0f / 6.0f) + 0.5f, 0.0f), 1.0f);
-        case SI_ACT_LEAKYRELU: return v > 0.0f ? v : v * p;
-        default: return v;
-    }
-}
-
 // NW waves, each PB blocks of 16 output pixels along W; NT 32-wide output-channel tiles per wave; KH x KW kernel, 3 channels,
 // stride 2.
 // EP: the epilogue known at compile time -- 1: bias + SiLU, 2: bias + ReLU (no residual, no second activation: the YOLOv5 / ResNet
@@ -105,7 +90,7 @@ __global__ __launch_bounds__(NW * 64) SI_STEM_WAVES_ATTR void conv_stem_roll_ker
 
     const int tid = threadIdx.x;
     const int wave = tid >> 6, lane = tid & 63, l15 = lane & 15, kq = lane >> 4;
-    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.in), 0, a.in_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_in = si_buffer(a.in, a.in_bytes);
     const int row_floats = a.iw * C;
 
     // ---- once per persistent workgroup: weight image and bias
@@ -134,7 +119,7 @@ __global__ __launch_bounds__(NW * 64) SI_STEM_WAVES_ATTR void conv_stem_roll_ker
             // the lane's part of the address is its float index in the row (or the out-of-range offset: the hardware returns 0),
             // the row's part a scalar offset (the range check does not see it; valid rows keep it inside the tensor)
             const bool ok = yok && e >= 0 && e + 3 < row_floats;
-            const unsigned off = ok ? (unsigned)e * 4u : 0xFFFFFF00u;
+            const unsigned off = ok ? (unsigned)e * 4u : SI_OOB;
             const unsigned row = (unsigned)y < (unsigned)a.ih ? (unsigned)((img * a.ih + y) * row_floats) * 4u : 0u;   // wave-uniform
             return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_in, off, row, 0));
         }
@@ -144,7 +129,7 @@ __global__ __launch_bounds__(NW * 64) SI_STEM_WAVES_ATTR void conv_stem_roll_ker
             const int ee = e + t;
             const int px = ee / C, ch = ee - px * C;
             unsigned off = ((unsigned)(((img * a.ih + y) * a.iw + px) * a.in_ld + ch)) * 4u;
-            if (!(yok && ee >= 0 && ee < row_floats)) off = 0xFFFFFF00u;
+            if (!(yok && ee >= 0 && ee < row_floats)) off = SI_OOB;
             v[t] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_in, off, 0, 0));
         }
         return v;
@@ -192,7 +177,7 @@ __global__ __launch_bounds__(NW * 64) SI_STEM_WAVES_ATTR void conv_stem_roll_ker
         // offset -- the 64-bit pixel index and pointer arithmetic cost ~15 vector instructions per tile, a third of what a row
         // issues beside its MFMAs.  A pixel block past the row's end, or a channel group past oc, stores to the out-of-range offset.
         constexpr bool bst = EP != 0 && (SI_STEM_EXP & 8) && sizeof(OutT) == 4;   // (the launcher picks EP != 0 only with out_bytes != 0)
-        const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(a.out, 0, a.out_bytes, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs_out = si_buffer(a.out, a.out_bytes);
         const unsigned st_lane = (unsigned)(((wave * PB * 16 + l15) * a.out_ld + 4 * kq) * 4);
         unsigned st_mask = 0;                         // bit h * NOC + u: this lane's (pixel block h, channel tile u) lies inside the tensor
 #pragma unroll
@@ -205,7 +190,7 @@ __global__ __launch_bounds__(NW * 64) SI_STEM_WAVES_ATTR void conv_stem_roll_ker
                 f32x4 v = accv + bv[u];
                 if (EP == 1) {
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) v[q] = v[q] * __builtin_amdgcn_rcpf(1.0f + __expf(-v[q]));
+                    for (int q = 0; q < 4; ++q) v[q] = si_silu_fast(v[q]);
                 } else {
 #pragma unroll
                     for (int q = 0; q < 4; ++q) v[q] = fmaxf(v[q], 0.0f);
@@ -215,8 +200,8 @@ __global__ __launch_bounds__(NW * 64) SI_STEM_WAVES_ATTR void conv_stem_roll_ker
                 // (the tile's offset is ADDED to the lane's, not passed as the instruction's scalar offset: a 16-byte store with an SGPR
                 // offset reads its data registers one cycle late, and with the next tile's arithmetic right behind it the last
                 // four lanes of every 16 stored the next tile's first value -- 1216 wrong elements in 3.3 M on image 31 of 32)
-                const unsigned voff = ((st_mask >> (h * NOC + u)) & 1u) ? st_lane + soff : 0xFFFFFF00u;
-                if (!(SI_STEM_ABLATE & 1)) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4s, v), rs_out, voff, 0, 0);
+                const unsigned voff = ((st_mask >> (h * NOC + u)) & 1u) ? st_lane + soff : SI_OOB;
+                if (!(SI_STEM_ABLATE & 1)) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs_out, voff, 0, 0);
             } else {
             const int ox = ox0 + (wave * PB + h) * 16 + l15;
             const int o = u * 16 + 4 * kq;
@@ -227,22 +212,22 @@ __global__ __launch_bounds__(NW * 64) SI_STEM_WAVES_ATTR void conv_stem_roll_ker
             if (SI_STEM_ABLATE & 2) {
             } else if (EP == 1 && (SI_STEM_EXP & 1)) {
 #pragma unroll
-                for (int q = 0; q < 4; ++q) v[q] = v[q] * __builtin_amdgcn_rcpf(1.0f + __expf(-v[q]));
+                for (int q = 0; q < 4; ++q) v[q] = si_silu_fast(v[q]);
             } else if (EP == 2 && (SI_STEM_EXP & 1)) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) v[q] = fmaxf(v[q], 0.0f);
             } else if (simple && a.act1 == SI_ACT_SILU) {
 #pragma unroll
-                for (int q = 0; q < 4; ++q) v[q] = v[q] * __builtin_amdgcn_rcpf(1.0f + __expf(-v[q]));
+                for (int q = 0; q < 4; ++q) v[q] = si_silu_fast(v[q]);
             } else if (simple && a.act1 == SI_ACT_RELU) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) v[q] = fmaxf(v[q], 0.0f);
             } else {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
-                    float t2 = stem_act(a.act1, v[q], a.act_param);
+                    float t2 = si_act(a.act1, v[q], a.act_param);
                     if (a.res && o + q < a.oc) t2 += a.res[pix * a.res_ld + o + q];
-                    v[q] = stem_act(a.act2, t2, a.act_param);
+                    v[q] = si_act(a.act2, t2, a.act_param);
                 }
             }
             if (SI_STEM_ABLATE & 1) {

@@ -24,13 +24,6 @@
 
 #pragma clang fp contract(off)
 
-typedef _Float16 half_t;
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
 
 struct FusedArgs {
@@ -58,10 +51,8 @@ struct FusedArgs {
 #ifndef SI_FUSED_ABL
 #define SI_FUSED_ABL 0
 #endif
-__device__ __forceinline__ float silu_f(float t) { return t * __builtin_amdgcn_rcpf(1.0f + __expf(-t)); }
 // SiLU of (x0 + b, x1 + b) on the packed fp32 instructions (conv_igemm.hip epilogue_lean: each component is rounded exactly like the
-// scalar form -- __expf(-t) is v_exp_f32(t * -log2(e)) -- so the bits are silu_f's), then fp16 bit patterns
-typedef float f32x2 __attribute__((ext_vector_type(2)));
+// scalar form -- __expf(-t) is v_exp_f32(t * -log2(e)) -- so the bits are si_silu_fast's), then fp16 bit patterns
 __device__ __forceinline__ void silu2_bits(float x0, float x1, float b, unsigned& h0, unsigned& h1) {
     const f32x2 v = f32x2{x0, x1} + f32x2{b, b};
     const f32x2 x = v * f32x2{-1.44269504088896340736f, -1.44269504088896340736f};
@@ -71,7 +62,6 @@ __device__ __forceinline__ void silu2_bits(float x0, float x1, float b, unsigned
     h1 = __builtin_bit_cast(unsigned short, si_store_cast<half_t>(o[1]));
 }
 
-constexpr unsigned OOB = 0xFFFFFF00u;
 constexpr int PITCH = 80, ROWP = 2688, EOFF = 17 * PITCH;     // patch image, bytes (conv_s2c32_f16_kernel)
 constexpr int PR = 9;
 constexpr int RL = 216;                                       // halves per staged image row: 70 pixels x 3 + the last group's over-read
@@ -100,7 +90,7 @@ __global__ __launch_bounds__(256, SI_FUSED_MINW) void conv_stem_s2c32_f16_kernel
     __shared__ __attribute__((aligned(16))) half_t tile[PW ? 64 * TP : 8];
 
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, l31 = lane & 31, lh = lane >> 5;
-    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.in), 0, a.in_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_in = si_buffer(a.in, a.in_bytes);
     const int row_floats = a.iw * 3;
 
     // staging vectors of this thread: vector v of staged row r is image floats [192 tx - 12 + 4 v, + 4) of image row 16 ty - 4 + r
@@ -121,7 +111,7 @@ __global__ __launch_bounds__(256, SI_FUSED_MINW) void conv_stem_s2c32_f16_kernel
             const int y = iy0 + v_r[i], e = e0 + 4 * v_v[i];
             const bool ok = v_r[i] >= 0 && (unsigned)y < (unsigned)a.ih && e >= 0 && e + 3 < row_floats;
             const unsigned off = ((unsigned)((img * a.ih + y) * row_floats + e)) * 4u;
-            pre[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_in, ok ? off : OOB, 0, 0));
+            pre[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_in, ok ? off : SI_OOB, 0, 0));
         }
     };
     auto commit = [&]() {
@@ -141,10 +131,10 @@ __global__ __launch_bounds__(256, SI_FUSED_MINW) void conv_stem_s2c32_f16_kernel
     for (int i = tid; i < 9 * 2 * 32; i += 256) *reinterpret_cast<f16x8*>(wsl + i * 8) = *reinterpret_cast<const f16x8*>(a.ws + (size_t)i * 8);
     // conv_1: this wave's column block of the weights, 18 k-steps (tap-major, two 16-channel halves per tap), resident in registers
     const int wm = wave >> 1, wn = wave & 1;
-    const __amdgpu_buffer_rsrc_t rs_wl = __builtin_amdgcn_make_buffer_rsrc(const_cast<half_t*>(a.wl), 0, (unsigned)a.nb * 18u * 1024u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_wl = si_buffer(a.wl, (unsigned)a.nb * 18u * 1024u);
     f16x8 wf[18];
     {
-        const unsigned vo = wn < a.nb ? (unsigned)wn * 18u * 1024u + (unsigned)lane * 16u : 0x80000000u;
+        const unsigned vo = wn < a.nb ? (unsigned)wn * 18u * 1024u + (unsigned)lane * 16u : SI_OOB_HALF;
 #pragma unroll
         for (int s = 0; s < 18; ++s) wf[s] = __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(rs_wl, vo, (unsigned)(s * 1024), 0));
     }
@@ -155,7 +145,7 @@ __global__ __launch_bounds__(256, SI_FUSED_MINW) void conv_stem_s2c32_f16_kernel
     f16x8 wpf[PW ? 4 : 1];
     float bpv = 0.0f;
     if (PW) {
-        const __amdgpu_buffer_rsrc_t rs_wp = __builtin_amdgcn_make_buffer_rsrc(const_cast<half_t*>(a.wp), 0, 2u * 4u * 1024u, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs_wp = si_buffer(a.wp, 2u * 4u * 1024u);
 #pragma unroll
         for (int s = 0; s < 4; ++s)
             wpf[s] = __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(rs_wp, (unsigned)wn * 4096u + (unsigned)lane * 16u, (unsigned)(s * 1024), 0));
@@ -172,8 +162,8 @@ __global__ __launch_bounds__(256, SI_FUSED_MINW) void conv_stem_s2c32_f16_kernel
 #pragma unroll
         for (int s = 0; s < 9; ++s) wsf[s] = *reinterpret_cast<const f16x8*>(wfrag + s * (2 * 32 * 8));
     }
-    const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(a.out, 0, a.out_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_out_b = __builtin_amdgcn_make_buffer_rsrc(PW ? a.out_b : a.out, 0, PW ? a.out_b_bytes : a.out_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_out = si_buffer(a.out, a.out_bytes);
+    const __amdgpu_buffer_rsrc_t rs_out_b = si_buffer(PW ? a.out_b : a.out, PW ? a.out_b_bytes : a.out_bytes);
     const uint32_t* const stage_w = reinterpret_cast<const uint32_t*>(stage);
     const int a_base = (2 * (2 * wm + (l31 >> 4))) * ROWP + (l31 & 15) * PITCH + lh * 16;
     // conv_1's weights and the biases have LANDED before the loop: otherwise every MFMA of phase B carries a vmcnt(N) wait for "its"
@@ -223,7 +213,7 @@ __global__ __launch_bounds__(256, SI_FUSED_MINW) void conv_stem_s2c32_f16_kernel
                 unsigned char* const pr = prow_l + b * ROWP;
 #pragma unroll
                 for (int e = 0; e < 16; e += 2) {
-                    const int c = (e & 3) + 8 * (e >> 2);                        // compile-time part of the column (c, c + 1)
+                    const int c = Mma<32>::row(e);                        // compile-time part of the column (c, c + 1)
                     unsigned h0, h1;
                     silu2_bits(acc[e], acc[e + 1], bsv, h0, h1);
                     // (masks, not branches: a pixel outside the stem's output is conv_1's zero padding)
@@ -236,7 +226,7 @@ __global__ __launch_bounds__(256, SI_FUSED_MINW) void conv_stem_s2c32_f16_kernel
                 const bool col_ok = (unsigned)(32 * tx + 31) < (unsigned)a.sow;  // uniform
 #pragma unroll
                 for (int e = 0; e < 16; e += 2) {
-                    const int r = (e & 3) + 8 * (e >> 2) + 4 * lh;
+                    const int r = SI_MMA32_ROW(e) + 4 * lh;   // (the expression form: see SI_MMA32_ROW)
                     unsigned h0, h1;
                     silu2_bits(acc[e], acc[e + 1], bsv, h0, h1);
                     h0 &= (col_ok && (unsigned)(8 * ty - 1 + r) < (unsigned)a.soh) ? 0xFFFFu : 0u;
@@ -278,7 +268,7 @@ __global__ __launch_bounds__(256, SI_FUSED_MINW) void conv_stem_s2c32_f16_kernel
                 // the tile into LDS as [pixel 32 wm + r][channel o] (conv_1's own epilogue expressions and rounding: silu2_bits)
 #pragma unroll
                 for (int e = 0; e < 16; e += 2) {
-                    const int r = (e & 3) + 8 * (e >> 2) + 4 * lh;
+                    const int r = Mma<32>::row(e) + 4 * lh;
                     unsigned h0, h1;
                     silu2_bits(acc[e], acc[e + 1], bcv, h0, h1);
                     *reinterpret_cast<unsigned short*>(tile + (32 * wm + r) * TP + o) = (unsigned short)h0;
@@ -298,7 +288,7 @@ __global__ __launch_bounds__(256, SI_FUSED_MINW) void conv_stem_s2c32_f16_kernel
                 const int old = wn == 0 ? a.out_ld : a.out_b_ld;
 #pragma unroll
                 for (int e = 0; e < 16; e += 2) {
-                    const int r = (e & 3) + 8 * (e >> 2) + 4 * lh;
+                    const int r = Mma<32>::row(e) + 4 * lh;
                     const int oy = oy0 + (r >> 4), ox = ox0 + (r & 15);
                     unsigned h0, h1;
                     silu2_bits(acc2[e], acc2[e + 1], bpv, h0, h1);
@@ -306,8 +296,8 @@ __global__ __launch_bounds__(256, SI_FUSED_MINW) void conv_stem_s2c32_f16_kernel
                         const int ow_live = oy < a.oh ? a.ow : 0;   // (uniform: r >> 4 is a compile-time 0 / 1)
                         const unsigned off = ((unsigned)((img * a.oh + oy) * a.ow + ox) * (unsigned)old + (unsigned)l31) * 2u;
                         const __amdgpu_buffer_rsrc_t rs = wn == 0 ? rs_out : rs_out_b;
-                        __builtin_amdgcn_raw_buffer_store_b16((unsigned short)h0, rs, ox < ow_live ? off : OOB, 0, 0);
-                        __builtin_amdgcn_raw_buffer_store_b16((unsigned short)h1, rs, ox + 1 < ow_live ? off : OOB, old * 2, 0);
+                        __builtin_amdgcn_raw_buffer_store_b16((unsigned short)h0, rs, ox < ow_live ? off : SI_OOB, 0, 0);
+                        __builtin_amdgcn_raw_buffer_store_b16((unsigned short)h1, rs, ox + 1 < ow_live ? off : SI_OOB, old * 2, 0);
                     } else {
                     unsigned short* const op = reinterpret_cast<unsigned short*>(ob + (size_t)((img * a.oh + oy) * a.ow + ox) * old);
                     if (oy < a.oh && ox < a.ow) op[0] = (unsigned short)h0;
@@ -320,19 +310,19 @@ __global__ __launch_bounds__(256, SI_FUSED_MINW) void conv_stem_s2c32_f16_kernel
             if constexpr (BST) {
 #pragma unroll
                 for (int e = 0; e < 16; e += 2) {
-                    const int r = (e & 3) + 8 * (e >> 2) + 4 * lh;   // rows r, r + 1: the same output row (r & 15 is even)
+                    const int r = Mma<32>::row(e) + 4 * lh;   // rows r, r + 1: the same output row (r & 15 is even)
                     const int oy = oy0 + (r >> 4), ox = ox0 + (r & 15);
                     unsigned h0, h1;
                     silu2_bits(acc[e], acc[e + 1], bcv, h0, h1);
                     const int ow_live = (oy < a.oh && o < a.oc && !(SI_FUSED_ABL & 8)) ? a.ow : 0;
                     const unsigned off = ((unsigned)((img * a.oh + oy) * a.ow + ox) * (unsigned)a.out_ld + (unsigned)o) * 2u;
-                    __builtin_amdgcn_raw_buffer_store_b16((unsigned short)h0, rs_out, ox < ow_live ? off : OOB, 0, 0);
-                    __builtin_amdgcn_raw_buffer_store_b16((unsigned short)h1, rs_out, ox + 1 < ow_live ? off : OOB, a.out_ld * 2, 0);
+                    __builtin_amdgcn_raw_buffer_store_b16((unsigned short)h0, rs_out, ox < ow_live ? off : SI_OOB, 0, 0);
+                    __builtin_amdgcn_raw_buffer_store_b16((unsigned short)h1, rs_out, ox + 1 < ow_live ? off : SI_OOB, a.out_ld * 2, 0);
                 }
             } else if (o < a.oc) {
 #pragma unroll
                 for (int e = 0; e < 16; e += 2) {
-                    const int r = (e & 3) + 8 * (e >> 2) + 4 * lh;   // rows r, r + 1: the same output row (r & 15 is even)
+                    const int r = Mma<32>::row(e) + 4 * lh;   // rows r, r + 1: the same output row (r & 15 is even)
                     const int oy = oy0 + (r >> 4), ox = ox0 + (r & 15);
                     unsigned h0, h1;
                     silu2_bits(acc[e], acc[e + 1], bcv, h0, h1);

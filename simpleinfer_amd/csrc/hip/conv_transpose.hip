@@ -28,16 +28,13 @@
 
 #include <cstdint>
 
-#include "si_hip.h"
-#include "si_hip_internal.h"
-
 // No contraction: bias add and activation round as written in every instantiation.
 #pragma clang fp contract(off)
 
-namespace {
+#include "si_hip.h"
+#include "si_hip_internal.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+namespace {
 
 constexpr int CT_BM = 64, CT_BN = 64, CT_BK = 32, CT_LDL = CT_BK + 4;
 
@@ -56,18 +53,7 @@ struct CtArgs {
     float act_param;
 };
 
-template <int ACT>
-__device__ __forceinline__ float ct_act(float v, float p) {
-    if (ACT == SI_ACT_RELU) return fmaxf(v, 0.0f);
-    if (ACT == SI_ACT_SILU) return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v));
-    if (ACT == SI_ACT_SIGMOID) return __builtin_amdgcn_rcpf(1.0f + __expf(-v));
-    if (ACT == SI_ACT_HARDSIGMOID) return fminf(fmaxf(v * (1.0f / 6.0f) + 0.5f, 0.0f), 1.0f);
-    if (ACT == SI_ACT_HARDSWISH) return v * fminf(fmaxf(v * (1.0f / 6.0f) + 0.5f, 0.0f), 1.0f);
-    if (ACT == SI_ACT_LEAKYRELU) return v > 0.0f ? v : v * p;
-    return v;
-}
-
-// C/D map of the 32x32 tile: col = lane & 31 (GEMM column), row = (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5).
+// C/D map of the 32x32 tile: col = lane & 31 (GEMM column), row = Mma<32>::row(e) + 4 * (lane >> 5).
 // rows[]: the output pixel of each of the workgroup's 64 rows (-1 past M); col_pix: the pixel offset of this lane's
 // column (the one-tap path's ky * ow + kx, else 0); o: its output channel.
 template <int ACT>
@@ -77,8 +63,8 @@ __device__ __forceinline__ void ct_store(const CtArgs& a, const f32x16& acc, con
     float* const ob = a.out + o;
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
-        const int pix = rows[row0 + (e & 3) + 8 * (e >> 2)];
-        if (pix >= 0) ob[(size_t)(pix + col_pix) * a.out_ld] = ct_act<ACT>(acc[e] + bv, a.act_param);
+        const int pix = rows[row0 + Mma<32>::row(e)];
+        if (pix >= 0) ob[(size_t)(pix + col_pix) * a.out_ld] = si_act<ACT>(acc[e] + bv, a.act_param);
     }
 }
 

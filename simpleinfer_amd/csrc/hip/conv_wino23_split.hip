@@ -21,12 +21,6 @@
 #include "si_hip.h"
 #include "si_hip_internal.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 half_t;
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
 
 struct WinoArgs {
@@ -41,7 +35,7 @@ struct WinoArgs {
     int th, tw;          // tiles per image column / row
     int rows_total;      // n * th
     int col_blocks, oc_blocks, spatial_blocks;
-    unsigned mg_chunk, mg_cols, mg_th;   // floor(2^32 / d) of the block decode's three divisors (wino_div)
+    unsigned mg_chunk, mg_cols, mg_th;   // floor(2^32 / d) of the block decode's three divisors (si_magic.h)
     unsigned in_bytes, u_bytes;
     int act1, act2;
     float act_param;
@@ -49,31 +43,12 @@ struct WinoArgs {
     unsigned* range_flag; // SiConv2dDesc::range_flag: set to 1 when an accumulator left the matrix cores non-finite (a V value overflowed fp16)
 };
 
-__device__ __forceinline__ float wino_act(int act, float v, float p) {
-    switch (act) {
-        case SI_ACT_RELU: return fmaxf(v, 0.0f);
-        case SI_ACT_SILU: return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v));
-        case SI_ACT_SIGMOID: return __builtin_amdgcn_rcpf(1.0f + __expf(-v));
-        case SI_ACT_HARDSIGMOID: return fminf(fmaxf(v * (1.0f / 6.0f) + 0.5f, 0.0f), 1.0f);
-        case SI_ACT_HARDSWISH: return v * fminf(fmaxf(v * (1.0f / 6.0f) + 0.5f, 0.0f), 1.0f);
-        case SI_ACT_LEAKYRELU: return v > 0.0f ? v : v * p;
-        default: return v;
-    }
-}
-
 constexpr int CB = 16;  // input channels per staged block
 // SI_WS_ABL (diagnostic builds only, tools/hip_variant.sh): bit 0 no MFMAs, 1 no transform / split (constant operands), 2 no staging stores
 // after block 0, 3 no filter loads after block 0, 4 no patch fetches after block 1, 5 no LDS reads -- wrong results, timing only
 #ifndef SI_WS_ABL
 #define SI_WS_ABL 0
 #endif
-
-// n / d for 0 <= n < 2^32 with mg = floor(2^32 / d) (0xFFFFFFFF for d = 1): the high product is the quotient or one less
-__device__ __forceinline__ int wino_div(int n, int d, unsigned mg) {
-    unsigned q = __umulhi((unsigned)n, mg);
-    if ((unsigned)n - q * (unsigned)d >= (unsigned)d) ++q;
-    return (int)q;
-}
 
 #ifndef SI_WINO_ABLATE   // diagnostic builds only (timing experiments, wrong results): 1 no patch loads after block 0,
 #define SI_WINO_ABLATE 0  // 2 no filter loads after the first, 4 no staging stores after block 0, 8 no output stores
@@ -128,25 +103,25 @@ __global__ __launch_bounds__(256, 2) void conv_wino23s_kernel(const WinoArgs a) 
     // block id -> (spatial block, oc block): the oc blocks of one spatial block share blockIdx % 8, i.e. one XCD and its
     // L2, because they all stage the same input patches (placement is a speed hint only)
     const int per_chunk = 8 * a.oc_blocks;
-    const int chunk = wino_div((int)blockIdx.x, per_chunk, a.mg_chunk);
+    const int chunk = si_fast_div((int)blockIdx.x, per_chunk, a.mg_chunk);
     const int rr = blockIdx.x - chunk * per_chunk;
     const int sb = chunk * 8 + (rr & 7);
     const int ocb = rr >> 3;
     if (sb >= a.spatial_blocks) return;
-    const int by = wino_div(sb, a.col_blocks, a.mg_cols);
+    const int by = si_fast_div(sb, a.col_blocks, a.mg_cols);
     const int bc = sb - by * a.col_blocks;
     const int row0 = by * TBH;               // first flattened tile row of the block
     const int col0 = bc * TBW;               // first tile column
     const int oc0 = ocb * OCW;
 
-    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.in), 0, a.in_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_in = si_buffer(a.in, a.in_bytes);
     const unsigned row_pitch = (unsigned)(a.iw * a.in_ld * 4);
 
     // ---- staging items.  Core: thread -> (tile row, one of the 2*TBW own pixels, 4 channels); halo: the first NHALO threads
     // -> (tile row, one of the two halo pixels, 4 channels).  An item is the byte offset of patch row 0 (it may lie before
     // the tensor when that row is padding; only valid rows use it) and a 4-bit mask of the rows inside the image.
     auto make_item = [&](int tr, int px, int cq, unsigned& base, unsigned& rows) {
-        const int img = wino_div(row0 + tr, a.th, a.mg_th);   // (image, tile row) of the item's flattened tile row, branch free
+        const int img = si_fast_div(row0 + tr, a.th, a.mg_th);   // (image, tile row) of the item's flattened tile row, branch free
         const int ty = row0 + tr - img * a.th;
         const int y0 = 2 * ty - a.pad, x = 2 * col0 - a.pad + px;
         const bool ok = row0 + tr < a.rows_total && (unsigned)x < (unsigned)a.iw;
@@ -175,7 +150,7 @@ __global__ __launch_bounds__(256, 2) void conv_wino23s_kernel(const WinoArgs a) 
         unsigned base, rows;
         make_item(h_tr, h_px, h_cq, base, rows);
         h_live[i] = hv < NHALO;
-        h_off[i] = (h_live[i] && ((rows >> h_j) & 1u)) ? base + (unsigned)h_j * row_pitch : 0xFFFFFF00u;
+        h_off[i] = (h_live[i] && ((rows >> h_j) & 1u)) ? base + (unsigned)h_j * row_pitch : SI_OOB;
         h_dst[i] = (h_cq * 4) * PLANE + (h_j * TBH + h_tr) * PWP + h_px;   // plane row j is the one this lane produces
     }
 
@@ -189,8 +164,8 @@ __global__ __launch_bounds__(256, 2) void conv_wino23s_kernel(const WinoArgs a) 
     // zero records (`live` false), so every staging load is issued unconditionally and costs no vector instruction.
     unsigned c_off[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) c_off[j] = ((c_rows >> j) & 1u) ? (j == 0 ? c_base - row_pitch : c_base) : 0xFFFFFF00u;
-    const __amdgpu_buffer_rsrc_t rs_none = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.in), 0, 0, 0x00020000);
+    for (int j = 0; j < 4; ++j) c_off[j] = ((c_rows >> j) & 1u) ? (j == 0 ? c_base - row_pitch : c_base) : SI_OOB;
+    const __amdgpu_buffer_rsrc_t rs_none = si_buffer(a.in, 0);
     auto fetch = [&](u32x4 (&dst)[4], int cb, bool live) {
         const __amdgpu_buffer_rsrc_t rs = live ? rs_in : rs_none;
 #pragma unroll
@@ -252,8 +227,8 @@ __global__ __launch_bounds__(256, 2) void conv_wino23s_kernel(const WinoArgs a) 
     const int noct = a.oc / 32;
     const int ncb = a.ic / CBX;
     const unsigned img_bytes = (unsigned)(16 * a.ic) * (unsigned)a.oc * 2u;
-    const __amdgpu_buffer_rsrc_t rs_hi = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(a.u), 0, img_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_lo = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(a.u) + (size_t)16 * a.ic * a.oc, 0, img_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_hi = si_buffer(a.u, img_bytes);
+    const __amdgpu_buffer_rsrc_t rs_lo = si_buffer(a.u + (size_t)16 * a.ic * a.oc, img_bytes);
     const unsigned u_lane = (unsigned)lane * 16u;
     const unsigned u_row = (unsigned)(wave * ncb * noct + oc0 / 32) * 4096u;   // (row, cb 0, oc tile, q 0)
     const unsigned u_cb = (unsigned)noct * 4096u;
@@ -366,7 +341,7 @@ __global__ __launch_bounds__(256, 2) void conv_wino23s_kernel(const WinoArgs a) 
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
             // the two scales meet; C/D map: row (tile inside the block) = (e&3) + 8*(e>>2) + 4*lh, column = oc % 32
-            const int m = (e & 3) + 8 * (e >> 2);
+            const int m = Mma<32>::row(e);
             float mq[4];
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
@@ -394,7 +369,7 @@ __global__ __launch_bounds__(256, 2) void conv_wino23s_kernel(const WinoArgs a) 
             const int tr = t >> LOG_TBW, tc = t & (TBW - 1);
             const int txg = col0 + tc;
             if (row0 + tr >= a.rows_total || txg >= a.tw) continue;
-            const int img = wino_div(row0 + tr, a.th, a.mg_th);
+            const int img = si_fast_div(row0 + tr, a.th, a.mg_th);
             const int ty = row0 + tr - img * a.th;
             const int oy = 2 * ty + i_out, ox = 2 * txg + jc;
             if (oy >= a.oh || ox >= a.ow) continue;
@@ -409,11 +384,11 @@ __global__ __launch_bounds__(256, 2) void conv_wino23s_kernel(const WinoArgs a) 
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 float vv = y[k] + bv[k];
-                vv = decltype(act1)::value < 0 ? wino_act(a.act1, vv, a.act_param)
-                                               : (decltype(act1)::value == SI_ACT_SILU ? vv * __builtin_amdgcn_rcpf(1.0f + __expf(-vv))
+                vv = decltype(act1)::value < 0 ? si_act(a.act1, vv, a.act_param)
+                                               : (decltype(act1)::value == SI_ACT_SILU ? si_silu_fast(vv)
                                                   : (decltype(act1)::value == SI_ACT_RELU ? fmaxf(vv, 0.0f) : vv));
                 if (decltype(has_res)::value) vv += rv[k];
-                vv = decltype(act2)::value < 0 ? wino_act(a.act2, vv, a.act_param)
+                vv = decltype(act2)::value < 0 ? si_act(a.act2, vv, a.act_param)
                                                : (decltype(act2)::value == SI_ACT_RELU ? fmaxf(vv, 0.0f) : vv);
                 o4[k] = vv;
             }
@@ -457,10 +432,9 @@ int launch_wino_split(WinoArgs a, hipStream_t s) {
     a.oc_blocks = a.oc / 32;
     const int row_blocks = (a.rows_total + TBH - 1) / TBH;
     a.spatial_blocks = a.col_blocks * row_blocks;
-    auto magic = [](int d) { return d > 1 ? (unsigned)(0x100000000ull / (unsigned)d) : 0xFFFFFFFFu; };
-    a.mg_chunk = magic(8 * a.oc_blocks);
-    a.mg_cols = magic(a.col_blocks);
-    a.mg_th = magic(a.th);
+    a.mg_chunk = si_magic(8 * a.oc_blocks);
+    a.mg_cols = si_magic(a.col_blocks);
+    a.mg_th = si_magic(a.th);
     const long long nblocks = (long long)((a.spatial_blocks + 7) / 8) * 8 * a.oc_blocks;
     if (nblocks > 0x7fffffffLL) return SI_E_UNSUPPORTED;
     hipLaunchKernelGGL((conv_wino23s_kernel<LOG_TBW, 1, 32>), dim3((unsigned)nblocks, 1, 1), dim3(256), 0, s, a);

@@ -31,10 +31,6 @@
 #include "si_hip.h"
 #include "si_hip_internal.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
 namespace {
 
 struct Wino43Args {
@@ -53,18 +49,6 @@ struct Wino43Args {
     int act1, act2;
     float act_param;
 };
-
-__device__ __forceinline__ float w43_act(int act, float v, float p) {
-    switch (act) {
-        case SI_ACT_RELU: return fmaxf(v, 0.0f);
-        case SI_ACT_SILU: return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v));
-        case SI_ACT_SIGMOID: return __builtin_amdgcn_rcpf(1.0f + __expf(-v));
-        case SI_ACT_HARDSIGMOID: return fminf(fmaxf(v * (1.0f / 6.0f) + 0.5f, 0.0f), 1.0f);
-        case SI_ACT_HARDSWISH: return v * fminf(fmaxf(v * (1.0f / 6.0f) + 0.5f, 0.0f), 1.0f);
-        case SI_ACT_LEAKYRELU: return v > 0.0f ? v : v * p;
-        default: return v;
-    }
-}
 
 constexpr int CB = 16;     // input channels per staged block
 constexpr int WG = 384;    // 6 waves
@@ -102,14 +86,14 @@ __global__ __launch_bounds__(WG, 3) void conv_wino43_kernel(const Wino43Args a) 
     const int col0 = bc * TBW;               // first tile column
     const int oc0 = ocb * 32;
 
-    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.in), 0, a.in_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_in = si_buffer(a.in, a.in_bytes);
 
     // ---- per-thread staging slots: byte offset of channel block 0 and LDS destination
     unsigned g_off[PFV];
 #pragma unroll
     for (int q = 0; q < PFV; ++q) {
         const int v = tid + q * WG;
-        g_off[q] = 0xFFFFFF00u;
+        g_off[q] = SI_OOB;
         if (v < NVEC) {
             const int cq = v & 3;
             const int rest = v >> 2;
@@ -133,7 +117,7 @@ __global__ __launch_bounds__(WG, 3) void conv_wino43_kernel(const Wino43Args a) 
     auto prefetch = [&](int cb) {
 #pragma unroll
         for (int q = 0; q < PFV; ++q) {
-            const unsigned off = g_off[q] == 0xFFFFFF00u ? 0xFFFFFF00u : g_off[q] + (unsigned)(cb * CB * 4);
+            const unsigned off = g_off[q] == SI_OOB ? SI_OOB : g_off[q] + (unsigned)(cb * CB * 4);
             pre[q] = __builtin_amdgcn_raw_buffer_load_b128(rs_in, off, 0, 0);
         }
     };
@@ -334,9 +318,9 @@ __global__ __launch_bounds__(WG, 3) void conv_wino43_kernel(const Wino43Args a) 
                 if (ocok && i_out < nrow[e] && jc < ncol[e]) {
                     const size_t pix = (size_t)(pix0[e] + i_out * a.ow + jc);
                     float vv = y + bv;
-                    vv = w43_act(a.act1, vv, a.act_param);
+                    vv = si_act(a.act1, vv, a.act_param);
                     if (a.res) vv += a.res[pix * a.res_ld + o];
-                    vv = w43_act(a.act2, vv, a.act_param);
+                    vv = si_act(a.act2, vv, a.act_param);
                     a.out[pix * a.out_ld + o] = vv;
                 }
             }

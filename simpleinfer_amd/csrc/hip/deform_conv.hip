@@ -16,16 +16,13 @@
 
 #include <cstdint>
 
-#include "si_deform.h"
-#include "si_hip_internal.h"
-
 // No contraction: the coordinate add, the blend, the mask multiply, bias add and activation round as written in every instantiation.
 #pragma clang fp contract(off)
 
-namespace {
+#include "si_deform.h"
+#include "si_hip_internal.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+namespace {
 
 constexpr int DC_BM = 64, DC_BN = 64, DC_BK = 32, DC_LDL = DC_BK + 4;
 
@@ -45,18 +42,7 @@ struct DcArgs {
     float act_param;
 };
 
-template <int ACT>
-__device__ __forceinline__ float dc_act(float v, float p) {
-    if (ACT == SI_ACT_RELU) return fmaxf(v, 0.0f);
-    if (ACT == SI_ACT_SILU) return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v));
-    if (ACT == SI_ACT_SIGMOID) return __builtin_amdgcn_rcpf(1.0f + __expf(-v));
-    if (ACT == SI_ACT_HARDSIGMOID) return fminf(fmaxf(v * (1.0f / 6.0f) + 0.5f, 0.0f), 1.0f);
-    if (ACT == SI_ACT_HARDSWISH) return v * fminf(fmaxf(v * (1.0f / 6.0f) + 0.5f, 0.0f), 1.0f);
-    if (ACT == SI_ACT_LEAKYRELU) return v > 0.0f ? v : v * p;
-    return v;
-}
-
-// C/D map of the 32x32 tile: col = lane & 31 (GEMM column), row = (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5).
+// C/D map of the 32x32 tile: col = lane & 31 (GEMM column), row = Mma<32>::row(e) + 4 * (lane >> 5).
 // rows[]: the output pixel of each of the workgroup's 64 rows (-1 past M); o: this lane's output channel.
 template <int ACT>
 __device__ __forceinline__ void dc_store(const DcArgs& a, const f32x16& acc, const int* rows, int row0, bool live, int o) {
@@ -65,8 +51,8 @@ __device__ __forceinline__ void dc_store(const DcArgs& a, const f32x16& acc, con
     float* const ob = a.out + o;
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
-        const int pix = rows[row0 + (e & 3) + 8 * (e >> 2)];
-        if (pix >= 0) ob[(size_t)pix * a.out_ld] = dc_act<ACT>(acc[e] + bv, a.act_param);
+        const int pix = rows[row0 + Mma<32>::row(e)];
+        if (pix >= 0) ob[(size_t)pix * a.out_ld] = si_act<ACT>(acc[e] + bv, a.act_param);
     }
 }
 

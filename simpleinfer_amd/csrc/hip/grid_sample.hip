@@ -38,12 +38,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-
 template <typename T, int VW> struct VecOf;
 template <> struct VecOf<float, 4> { typedef f32x4 type; };
 template <> struct VecOf<float, 2> { typedef f32x2 type; };

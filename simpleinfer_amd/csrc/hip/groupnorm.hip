@@ -30,16 +30,13 @@
 
 #include <cstdint>
 
-#include "si_hip_internal.h"
-#include "si_norm.h"
-
 // (x - mean) * scale + beta and the activations round as written in every instantiation
 #pragma clang fp contract(off)
 
-namespace {
+#include "si_hip_internal.h"
+#include "si_norm.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+namespace {
 
 constexpr int GN_THREADS = 256;
 constexpr int GN_MAX_PL = 64;          // pixel lanes per channel vector: bounds the serial sums of step 2
@@ -116,19 +113,6 @@ __device__ __forceinline__ void gn_store(T* p, const float (&v)[VW]) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) r[i] = si_store_cast<_Float16>(v[i]);
         *reinterpret_cast<f16x8*>(p) = r;
-    }
-}
-
-// the SI_ACT_* set with conv_transpose.hip's formulas
-__device__ __forceinline__ float gn_act(int act, float v, float p) {
-    switch (act) {
-        case SI_ACT_RELU: return fmaxf(v, 0.0f);
-        case SI_ACT_SILU: return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v));
-        case SI_ACT_SIGMOID: return __builtin_amdgcn_rcpf(1.0f + __expf(-v));
-        case SI_ACT_HARDSIGMOID: return fminf(fmaxf(v * (1.0f / 6.0f) + 0.5f, 0.0f), 1.0f);
-        case SI_ACT_HARDSWISH: return v * fminf(fmaxf(v * (1.0f / 6.0f) + 0.5f, 0.0f), 1.0f);
-        case SI_ACT_LEAKYRELU: return v > 0.0f ? v : v * p;
-        default: return v;
     }
 }
 
@@ -296,7 +280,7 @@ __device__ __forceinline__ void gn_tile_apply(const GnArgs<T>& a, const GnTile& 
             if constexpr (CACHE) gn_load<T, VW>(cache + (size_t)(p * t.cvc + v) * VW, x);
             else gn_load<T, VW>(src, x);
 #pragma unroll
-            for (int i = 0; i < VW; ++i) y[i] = gn_act(a.act, (x[i] - mu[i]) * sc[i] + be[i], a.act_param);
+            for (int i = 0; i < VW; ++i) y[i] = si_act(a.act, (x[i] - mu[i]) * sc[i] + be[i], a.act_param);
             gn_store<T, VW>(dst, y);
         }
     }

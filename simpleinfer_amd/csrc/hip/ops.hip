@@ -13,25 +13,7 @@
 #include "si_hip.h"
 #include "si_hip_internal.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
-
-// The standalone activation operator passes a NaN on, as torch does: fmaxf / fminf alone (v_max_f32 / v_min_f32) return the OTHER operand for
-// a NaN, which turned relu(NaN) and hardsigmoid(NaN) into 0.  Every other input keeps the bits fmaxf / fminf gave it.
-__device__ __forceinline__ float act_relu(float v) { return v != v ? v : fmaxf(v, 0.0f); }
-__device__ __forceinline__ float act_clamp01(float t) { return t != t ? t : fminf(fmaxf(t, 0.0f), 1.0f); }
-__device__ __forceinline__ float act_apply(int act, float v, float p) {
-    switch (act) {
-        case SI_ACT_RELU: return act_relu(v);
-        case SI_ACT_SILU: return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v));
-        case SI_ACT_SIGMOID: return __builtin_amdgcn_rcpf(1.0f + __expf(-v));
-        case SI_ACT_HARDSIGMOID: return act_clamp01(v * (1.0f / 6.0f) + 0.5f);
-        case SI_ACT_HARDSWISH: return v * act_clamp01(v * (1.0f / 6.0f) + 0.5f);
-        case SI_ACT_LEAKYRELU: return v > 0.0f ? v : v * p;
-        default: return v;
-    }
-}
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
@@ -46,13 +28,13 @@ __global__ void activation_kernel(int act, float ap, const float* __restrict__ i
         const int ch = (int)(i - p * cv);
         if (VEC) {
             f32x4 v = *reinterpret_cast<const f32x4*>(in + p * in_ld + ch * 4);
-            v.x = act_apply(act, v.x, ap);
-            v.y = act_apply(act, v.y, ap);
-            v.z = act_apply(act, v.z, ap);
-            v.w = act_apply(act, v.w, ap);
+            v.x = si_act_exact<float>(act, v.x, ap);
+            v.y = si_act_exact<float>(act, v.y, ap);
+            v.z = si_act_exact<float>(act, v.z, ap);
+            v.w = si_act_exact<float>(act, v.w, ap);
             *reinterpret_cast<f32x4*>(out + p * out_ld + ch * 4) = v;
         } else {
-            out[p * out_ld + ch] = act_apply(act, in[p * in_ld + ch], ap);
+            out[p * out_ld + ch] = si_act_exact<float>(act, in[p * in_ld + ch], ap);
         }
     }
 }
@@ -388,7 +370,7 @@ __global__ void yolo_decode_kernel(const float* __restrict__ conv, int n, size_t
         const size_t t = i / ne;
         const size_t r = t % rows;
         const size_t b = t / rows;
-        const float s = __builtin_amdgcn_rcpf(1.0f + __expf(-conv[i]));
+        const float s = si_sigmoid_fast(conv[i]);
         float v = s;
         if (e < 2) {
             v = (s * 2.0f + grid[r * 2 + e]) * stride;

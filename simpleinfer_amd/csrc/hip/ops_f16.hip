@@ -11,40 +11,7 @@
 #include "si_hip.h"
 #include "si_hip_internal.h"
 
-typedef _Float16 half_t;
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
-
-// v * p rounded to odd.  The slope is an fp32 value, so the product of a widened half and the slope has up to 35 significant bits: rounded to
-// fp32's 24 and then to fp16's 11 it can differ from the product rounded once (it lands on an fp16 tie that the exact product only came
-// near: 103 of the 65536 inputs at slope 0.1).  Rounding the fp32 product to odd keeps a sticky last bit, and the store's round-to-nearest-even
-// then gives the exact product rounded once.  fmaf returns the rounding error of `hi` exactly.
-__device__ __forceinline__ float mul_round_odd(float v, float p) {
-    const float hi = v * p;
-    const float lo = fmaf(v, p, -hi);
-    unsigned u = __builtin_bit_cast(unsigned, hi);
-    if (lo != 0.0f && !(u & 1u) && fabsf(hi) < __builtin_inff()) u += ((lo < 0.0f) == (hi < 0.0f)) ? 1u : ~0u;
-    return __builtin_bit_cast(float, u);
-}
-
-// (a NaN goes through relu and the clamp: see act_apply in ops.hip)
-__device__ __forceinline__ float act_relu(float v) { return v != v ? v : fmaxf(v, 0.0f); }
-__device__ __forceinline__ float act_clamp01(float t) { return t != t ? t : fminf(fmaxf(t, 0.0f), 1.0f); }
-__device__ __forceinline__ float act_f(int act, float v, float p) {
-    switch (act) {
-        case SI_ACT_RELU: return act_relu(v);
-        case SI_ACT_SILU: return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v));
-        case SI_ACT_SIGMOID: return __builtin_amdgcn_rcpf(1.0f + __expf(-v));
-        case SI_ACT_HARDSIGMOID: return act_clamp01(v * (1.0f / 6.0f) + 0.5f);
-        case SI_ACT_HARDSWISH: return v * act_clamp01(v * (1.0f / 6.0f) + 0.5f);
-        case SI_ACT_LEAKYRELU: return v > 0.0f ? v : mul_round_odd(v, p);
-        default: return v;
-    }
-}
-
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 template <bool VEC>
 __global__ void activation_h_kernel(int act, float ap, const half_t* __restrict__ in, size_t pixels, int c, int in_ld,
@@ -57,10 +24,10 @@ __global__ void activation_h_kernel(int act, float ap, const half_t* __restrict_
         if (VEC) {
             f16x8 v = *reinterpret_cast<const f16x8*>(in + p * in_ld + ch * 8);
 #pragma unroll
-            for (int k = 0; k < 8; ++k) v[k] = si_store_cast<half_t>(act_f(act, (float)v[k], ap));
+            for (int k = 0; k < 8; ++k) v[k] = si_store_cast<half_t>(si_act_exact<half_t>(act, (float)v[k], ap));
             *reinterpret_cast<f16x8*>(out + p * out_ld + ch * 8) = v;
         } else {
-            out[p * out_ld + ch] = si_store_cast<half_t>(act_f(act, (float)in[p * in_ld + ch], ap));
+            out[p * out_ld + ch] = si_store_cast<half_t>(si_act_exact<half_t>(act, (float)in[p * in_ld + ch], ap));
         }
     }
 }
@@ -231,7 +198,7 @@ int si_hip_activation_f16(int act, float act_param, const void* in, size_t pixel
     hipStream_t s = (hipStream_t)stream;
     const half_t* i = static_cast<const half_t*>(in);
     half_t* o = static_cast<half_t*>(out);
-    const bool vec = (c % 8 == 0) && (in_ld % 8 == 0) && (out_ld % 8 == 0) && al16(in) && al16(out);
+    const bool vec = (c % 8 == 0) && (in_ld % 8 == 0) && (out_ld % 8 == 0) && si_aligned_to(in, 16) && si_aligned_to(out, 16);
     if (vec)
         hipLaunchKernelGGL(activation_h_kernel<true>, dim3(si_grid_for(pixels * (size_t)(c / 8))), dim3(256), 0, s, act,
                            act_param, i, pixels, c, in_ld, o, out_ld);
@@ -248,7 +215,7 @@ int si_hip_unary_f16(int op, const void* in, size_t pixels, int c, int in_ld, vo
     hipStream_t s = (hipStream_t)stream;
     const half_t* i = static_cast<const half_t*>(in);
     half_t* o = static_cast<half_t*>(out);
-    const bool vec = (c % 8 == 0) && (in_ld % 8 == 0) && (out_ld % 8 == 0) && al16(in) && al16(out);
+    const bool vec = (c % 8 == 0) && (in_ld % 8 == 0) && (out_ld % 8 == 0) && si_aligned_to(in, 16) && si_aligned_to(out, 16);
     if (vec)
         hipLaunchKernelGGL(unary_h_kernel<true>, dim3(si_grid_for(pixels * (size_t)(c / 8))), dim3(256), 0, s, op, i, pixels, c, in_ld, o, out_ld);
     else
@@ -262,7 +229,7 @@ int si_hip_binary_same_f16(int op, const void* a, int a_ld, const void* b, int b
     if (op != 0 && op != 2) return SI_E_UNSUPPORTED;
     if (pixels == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
-    const bool vec = (c % 8 == 0) && (a_ld % 8 == 0) && (b_ld % 8 == 0) && (out_ld % 8 == 0) && al16(a) && al16(b) && al16(out);
+    const bool vec = (c % 8 == 0) && (a_ld % 8 == 0) && (b_ld % 8 == 0) && (out_ld % 8 == 0) && si_aligned_to(a, 16) && si_aligned_to(b, 16) && si_aligned_to(out, 16);
     if (vec)
         hipLaunchKernelGGL(binary_same_h_kernel<true>, dim3(si_grid_for(pixels * (size_t)(c / 8))), dim3(256), 0, s, op,
                            static_cast<const half_t*>(a), a_ld, static_cast<const half_t*>(b), b_ld, static_cast<half_t*>(out),
@@ -281,7 +248,7 @@ int si_hip_binary_bcast_f16(int op, const void* a, int a_ld, const void* s, int 
     if (!a || !s || !out || c <= 0 || n < 0 || a_ld < c || s_ld < c || out_ld < c) return SI_E_BADARG;
     if (op != 0 && op != 2) return SI_E_UNSUPPORTED;
     if (n == 0 || pixels_per_image == 0) return 0;
-    if (c % 8 != 0 || a_ld % 8 != 0 || s_ld % 8 != 0 || out_ld % 8 != 0 || !al16(a) || !al16(s) || !al16(out)) return SI_E_UNSUPPORTED;
+    if (c % 8 != 0 || a_ld % 8 != 0 || s_ld % 8 != 0 || out_ld % 8 != 0 || !si_aligned_to(a, 16) || !si_aligned_to(s, 16) || !si_aligned_to(out, 16)) return SI_E_UNSUPPORTED;
     hipLaunchKernelGGL(binary_bcast_h_kernel, dim3(si_grid_for((size_t)n * pixels_per_image * (size_t)(c / 8))), dim3(256), 0, (hipStream_t)stream, op,
                        static_cast<const half_t*>(a), a_ld, static_cast<const half_t*>(s), s_ld, static_cast<half_t*>(out), out_ld, n,
                        pixels_per_image, c);
@@ -294,7 +261,7 @@ int si_hip_maxpool2d_f16(const SiPool2dDesc* d, const void* in, void* out, si_st
     const size_t total = (size_t)d->n * d->oh * d->ow;
     if (total == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
-    const bool vec = (d->c % 8 == 0) && (d->in_ld % 8 == 0) && (d->out_ld % 8 == 0) && al16(in) && al16(out);
+    const bool vec = (d->c % 8 == 0) && (d->in_ld % 8 == 0) && (d->out_ld % 8 == 0) && si_aligned_to(in, 16) && si_aligned_to(out, 16);
     if (vec)
         hipLaunchKernelGGL(maxpool_h_kernel<true>, dim3(si_grid_for(total * (size_t)(d->c / 8))), dim3(256), 0, s, *d,
                            static_cast<const half_t*>(in), static_cast<half_t*>(out));

@@ -19,8 +19,6 @@
 
 namespace {
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int PAD_THREADS = 256;
 constexpr int PAD_ROWS = 4;
 

@@ -28,8 +28,6 @@
 
 namespace {
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int PS_THREADS = 256;
 constexpr int PS_LDS_BYTES = 16 * 1024;   // per workgroup: a budget (8 workgroups of 256 lanes fit a CU beside it), not a measured optimum
 #ifndef SI_PS_UNROLL

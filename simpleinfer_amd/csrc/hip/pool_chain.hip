@@ -13,9 +13,6 @@
 #include "si_hip.h"
 #include "si_hip_internal.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
 namespace {
 
 struct ChainArgs {
@@ -93,10 +90,9 @@ __global__ __launch_bounds__(256) void maxpool5_chain3_kernel(const ChainArgs a)
 template <typename VecT, typename ElemT, int NE>
 int launch_chain(const void* in, int n, int h, int w, int c, int in_ld, void* const out[3], const int out_ld[3], hipStream_t s) {
     if (!in || n <= 0 || h <= 0 || w <= 0 || c <= 0) return SI_E_BADARG;
-    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    if (c % NE != 0 || in_ld % NE != 0 || in_ld < c || !al16(in)) return SI_E_UNSUPPORTED;
+    if (c % NE != 0 || in_ld % NE != 0 || in_ld < c || !si_aligned_to(in, 16)) return SI_E_UNSUPPORTED;
     for (int k = 0; k < 3; ++k)
-        if (!out[k] || out_ld[k] % NE != 0 || out_ld[k] < c || !al16(out[k])) return SI_E_UNSUPPORTED;
+        if (!out[k] || out_ld[k] % NE != 0 || out_ld[k] < c || !si_aligned_to(out[k], 16)) return SI_E_UNSUPPORTED;
     // as many channel vectors per workgroup as two map planes of them fit in 64 KB of LDS (at most 4)
     int cgv = 4;
     while (cgv > 1 && (size_t)2 * h * w * cgv * 16 > 64 * 1024) cgv /= 2;

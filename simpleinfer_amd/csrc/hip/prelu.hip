@@ -19,7 +19,7 @@ constexpr int PRELU_THREADS = 256;
 template <typename T, int VW>
 __global__ __launch_bounds__(PRELU_THREADS) void prelu_kernel(const T* in, unsigned items, int cv, int in_ld, const float* __restrict__ slope,
                                                               int per_channel, T* out, int out_ld) {
-    typedef T Vec __attribute__((ext_vector_type(VW)));
+    typedef si_vec<T, VW> Vec;
     const float shared = slope[0];
     for (unsigned item = blockIdx.x * PRELU_THREADS + threadIdx.x; item < items; item += gridDim.x * PRELU_THREADS) {   // (items < 2^31)
         const int pix = (int)(item / (unsigned)cv), v = (int)item - pix * cv;

@@ -35,9 +35,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int RD_THREADS = 256;
 constexpr int RD_WAVES = RD_THREADS / 64;
 constexpr int RD_GROUP_ITEMS = 4;   // items per lane that size a group

@@ -29,10 +29,6 @@ namespace {
 
 namespace plan = si_rnn_plan;
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int RNN_THREADS = 256;
 static_assert(plan::kBlockUnits == plan::kWaveUnits * (RNN_THREADS / 64), "a wave owns 16 units");
 static_assert(SI_RNN_TILE_ROWS == plan::kTileRows && SI_RNN_BLOCK_UNITS == plan::kBlockUnits && SI_RNN_MAX_HIDDEN == plan::kMaxHidden, "header and plan agree");
@@ -49,7 +45,6 @@ struct RnnArgs {
 };
 
 // the forms of nn.Sigmoid (ops.hip) and nn.Tanh (UnaryOp 16)
-__device__ __forceinline__ float rnn_sigmoid(float v) { return __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
 __device__ __forceinline__ float rnn_tanh(float v) { return tanhf(v); }
 
 // four neighbouring elements from `u` on, as floats: halves by one 8-byte load (H % 8 == 0: in or out together), floats one by one
@@ -200,7 +195,7 @@ __global__ __launch_bounds__(RNN_THREADS) void rnn_step_kernel(RnnArgs a) {
     if constexpr (LSTM) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const float ig = rnn_sigmoid(pre[0][r]), fg = rnn_sigmoid(pre[1][r]), gg = rnn_tanh(pre[2][r]), og = rnn_sigmoid(pre[3][r]);
+            const float ig = si_sigmoid_fast(pre[0][r]), fg = si_sigmoid_fast(pre[1][r]), gg = rnn_tanh(pre[2][r]), og = si_sigmoid_fast(pre[3][r]);
             cv[r] = fg * cv[r] + ig * gg;
             hv[r] = og * rnn_tanh(cv[r]);
         }
@@ -208,7 +203,7 @@ __global__ __launch_bounds__(RNN_THREADS) void rnn_step_kernel(RnnArgs a) {
     } else {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const float rg = rnn_sigmoid(pre[0][r]), zg = rnn_sigmoid(pre[1][r]);
+            const float rg = si_sigmoid_fast(pre[0][r]), zg = si_sigmoid_fast(pre[1][r]);
             const float ng = rnn_tanh(pre[2][r] + rg * (acc[2][r] + bn[r]));
             hv[r] = (1.0f - zg) * ng + zg * hprev[r];
         }

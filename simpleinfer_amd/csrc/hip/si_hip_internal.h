@@ -8,6 +8,24 @@
 #include <mutex>
 #include <utility>
 
+#include "si_hip.h"
+#include "si_magic.h"
+
+// ---- device commons: what every kernel file shares.  A kernel file defines no activation formula, no division helper (si_magic.h), no
+// vector typedef and no buffer flag of its own ("Device commons").
+
+// Vector types, under the names the kernels use
+typedef _Float16 half_t;
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+template <typename T, int N> using si_vec = T __attribute__((ext_vector_type(N)));   // for a width that is a template parameter
+
 // Environment switches (ablations, sweeps) exist in the EXPERIMENT build of the library only (-DSI_EXPERIMENT: tools/hip_variant.sh,
 // simpleinfer_amd/build.py build_hip(defines=...)); in the product build the expression is its default and nothing reads the environment
 // (round 6).  Choices a caller may legitimately make per call travel in SiConv2dDesc::plan (include/si_hip.h).
@@ -93,14 +111,115 @@ __device__ __forceinline__ T si_store_cast(float v) {
 // values: half the store instructions for fp16 activations.  v0 / v1: this lane's channel at two pixels; afterwards the
 // even lane owns the first pixel and the odd lane the second.  Returns {channel 2k, channel 2k+1} as packed halves.
 __device__ __forceinline__ unsigned si_pair_halves(float v0, float v1, bool odd) {
-    typedef _Float16 si_h2 __attribute__((ext_vector_type(2)));
     const float send = odd ? v0 : v1;
     const float recv = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, send), 0xB1, 0xF, 0xF, true));
-    si_h2 p;
+    f16x2 p;
     p[0] = si_store_cast<_Float16>(odd ? recv : v0);
     p[1] = si_store_cast<_Float16>(odd ? v1 : recv);
     return __builtin_bit_cast(unsigned, p);
 }
+
+// ---- activations.  Two families with different rules for special values and rounding; neither is a slip of the other.
+//   * Fused epilogues (si_act): the value is a convolution's or a normalisation's accumulator on its way to the store.  ReLU and the two
+//     clamps are plain fmaxf / fminf (v_max_f32 / v_min_f32 return the OTHER operand for a NaN), so ReLU and the hard sigmoid turn a NaN into 0;
+//     it passes through the others (hard swish multiplies that 0 by the NaN again).  Leaky ReLU is the fp32 product v * p; under fp16 storage the store rounds it a second
+//     time.
+//   * Stand-alone operators (si_act_exact<T>, T the storage type): a NaN passes through every activation, as in torch, and under fp16
+//     storage the leaky product is rounded to odd so that the store's rounding is the only one (mul_round_odd).
+// Both use the fast sigmoid.  v_rcp_f32 / v_exp_f32 are accurate to 1 ulp: SiLU and sigmoid are within ~2e-7 relative of the exact
+// value, three orders inside the parity bar, at 5 instructions instead of the 15 of an IEEE division.
+// The formulas take the floating-point contraction of the file that includes them: a kernel file whose `#pragma clang fp contract(off)`
+// stands above this header's include computes the hard sigmoid's v * (1/6) + 0.5 as a multiply and an add, every other file as one fma.
+__device__ __forceinline__ float si_sigmoid_fast(float v) { return __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
+__device__ __forceinline__ float si_silu_fast(float v) { return v * si_sigmoid_fast(v); }
+
+// compile-time form: the activation of a template instance
+template <int ACT>
+__device__ __forceinline__ float si_act(float v, float p) {
+    if (ACT == SI_ACT_RELU) return fmaxf(v, 0.0f);
+    if (ACT == SI_ACT_SILU) return si_silu_fast(v);
+    if (ACT == SI_ACT_SIGMOID) return si_sigmoid_fast(v);
+    if (ACT == SI_ACT_HARDSIGMOID) return fminf(fmaxf(v * (1.0f / 6.0f) + 0.5f, 0.0f), 1.0f);
+    if (ACT == SI_ACT_HARDSWISH) return v * fminf(fmaxf(v * (1.0f / 6.0f) + 0.5f, 0.0f), 1.0f);
+    if (ACT == SI_ACT_LEAKYRELU) return v > 0.0f ? v : v * p;
+    return v;
+}
+// run-time form: the same formulas behind a switch that a kernel resolves once per workgroup, not per element
+__device__ __forceinline__ float si_act(int act, float v, float p) {
+    switch (act) {
+        case SI_ACT_RELU: return si_act<SI_ACT_RELU>(v, p);
+        case SI_ACT_SILU: return si_act<SI_ACT_SILU>(v, p);
+        case SI_ACT_SIGMOID: return si_act<SI_ACT_SIGMOID>(v, p);
+        case SI_ACT_HARDSIGMOID: return si_act<SI_ACT_HARDSIGMOID>(v, p);
+        case SI_ACT_HARDSWISH: return si_act<SI_ACT_HARDSWISH>(v, p);
+        case SI_ACT_LEAKYRELU: return si_act<SI_ACT_LEAKYRELU>(v, p);
+        default: return v;
+    }
+}
+
+// The stand-alone activation operator passes a NaN on, as torch does: fmaxf / fminf alone (v_max_f32 / v_min_f32) return the OTHER operand for
+// a NaN, which turned relu(NaN) and hardsigmoid(NaN) into 0.  Every other input keeps the bits fmaxf / fminf gave it.
+__device__ __forceinline__ float act_relu(float v) { return v != v ? v : fmaxf(v, 0.0f); }
+__device__ __forceinline__ float act_clamp01(float t) { return t != t ? t : fminf(fmaxf(t, 0.0f), 1.0f); }
+// v * p rounded to odd.  The slope is an fp32 value, so the product of a widened half and the slope has up to 35 significant bits: rounded to
+// fp32's 24 and then to fp16's 11 it can differ from the product rounded once (it lands on an fp16 tie that the exact product only came
+// near: 103 of the 65536 inputs at slope 0.1).  Rounding the fp32 product to odd keeps a sticky last bit, and the store's round-to-nearest-even
+// then gives the exact product rounded once.  fmaf returns the rounding error of `hi` exactly.
+__device__ __forceinline__ float mul_round_odd(float v, float p) {
+    const float hi = v * p;
+    const float lo = fmaf(v, p, -hi);
+    unsigned u = __builtin_bit_cast(unsigned, hi);
+    if (lo != 0.0f && !(u & 1u) && fabsf(hi) < __builtin_inff()) u += ((lo < 0.0f) == (hi < 0.0f)) ? 1u : ~0u;
+    return __builtin_bit_cast(float, u);
+}
+// T: the storage type the result is rounded to (as for si_store_cast)
+template <typename T>
+__device__ __forceinline__ float si_act_exact(int act, float v, float p) {
+    switch (act) {
+        case SI_ACT_RELU: return act_relu(v);
+        case SI_ACT_SILU: return si_silu_fast(v);
+        case SI_ACT_SIGMOID: return si_sigmoid_fast(v);
+        case SI_ACT_HARDSIGMOID: return act_clamp01(v * (1.0f / 6.0f) + 0.5f);
+        case SI_ACT_HARDSWISH: return v * act_clamp01(v * (1.0f / 6.0f) + 0.5f);
+        case SI_ACT_LEAKYRELU:
+            if constexpr (sizeof(T) == 2) return v > 0.0f ? v : mul_round_odd(v, p);
+            else return v > 0.0f ? v : v * p;
+        default: return v;
+    }
+}
+
+// ---- buffer views: raw buffer loads and stores check the byte offset against `bytes` in hardware; a load beyond it returns zeros and a
+// store beyond it is dropped, so an out-of-image tap or a row past M needs no branch, only one of the two offsets below.
+// The flag word is dword 3 of the gfx9 buffer descriptor: DATA_FORMAT = BUF_DATA_FORMAT_32 (value 4 in bits 15..18) and every other
+// field zero -- no index stride, no swizzle, no add-tid; the raw instructions carry their own width and ignore the destination selects.
+template <typename T>
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t si_buffer(const T* p, unsigned bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(p), 0, bytes, 0x00020000);
+}
+constexpr unsigned SI_OOB = 0xFFFFFF00u;       // >= any legal num_records
+constexpr unsigned SI_OOB_HALF = 0x80000000u;  // for a view below 2 GB (weights): + kt*128 cannot wrap
+
+// The two fp32 MFMA tiles the kernels use.  Both round like ONE sequential fma chain over k (tools/mfma_chain_test.hip, measured:
+// v_mfma_f32_32x32x2_f32, v_mfma_f32_16x16x4_f32 and a scalar fmaf loop agree bit for bit), so a kernel on 16x16 tiles that feeds
+// k in the same order as one on 32x32 tiles produces the same bits per output element -- the tile policy may follow the batch
+// size without breaking the engine's batch-invariance contract.
+//   32x32x2: A/B operand of lane l = row (l & 31), k = l >> 5;   C/D: col = l & 31, row = (e&3) + 8*(e>>2) + 4*(l>>5), 16 registers
+//   16x16x4: A/B operand of lane l = row (l & 15), k = l >> 4;   C/D: col = l & 15, row = e + 4*(l>>4),             4 registers
+// The fp16 instructions with a 32x32 fp32 result (v_mfma_f32_32x32x16_f16) have the same C/D map.
+// SI_MMA32_ROW: the 32x32 row map as an expression, for a site where the compiler treats the inlined call unlike the written-out sum
+// (conv_stem_s2c32_f16.hip, phase A's patch rows: two LDS stores split base and offset another way).  Same value; use Mma<32>::row.
+#define SI_MMA32_ROW(e) ((e & 3) + 8 * (e >> 2))
+template <int MT> struct Mma;
+template <> struct Mma<32> {
+    typedef f32x16 acc_t;
+    static constexpr int NE = 16;
+    __device__ static __forceinline__ constexpr int row(int e) { return SI_MMA32_ROW(e); }
+};
+template <> struct Mma<16> {
+    typedef f32x4 acc_t;
+    static constexpr int NE = 4;
+    __device__ static __forceinline__ constexpr int row(int e) { return e; }
+};
 
 // UnaryOp codes of expand_expression.cpp:146-165 (ncnn's numbering): 0 abs 1 neg 2 floor 3 ceil 4 square 5 sqrt 6 rsqrt 7 exp
 // 8 log 9 sin 10 cos 11 tan 12 asin 13 acos 14 atan 15 reciprocal 16 tanh 17 log10.  Library-accurate functions, IEEE sqrt and
@@ -138,8 +257,7 @@ __device__ __forceinline__ float si_unary_apply(int op, float x) {
 // row = (e&3) + 8*(e>>2) + 4*(lane>>5) (pixel).
 // MT: the MFMA tile the accumulators come from -- 32 (16 registers, rows (e&3) + 8*(e>>2)) or 16 (v_mfma_f32_16x16x4_f32: 4
 // registers, rows e; col = lane&15, + 4*(lane>>4) already in mrow0)
-typedef float si_f32x16 __attribute__((ext_vector_type(16)));
-template <int TM, int TN, typename Args, int MT = 32, typename AccT = si_f32x16>
+template <int TM, int TN, typename Args, int MT = 32, typename AccT = f32x16>
 __device__ __forceinline__ void si_yolo_tile_one_image(const Args& a, float* out, AccT (&acc)[TM][TN], int mrow0, int ocol0, int img) {
 #pragma clang fp contract(off)
     const int per_pix = a.yna * a.yne;
@@ -166,7 +284,7 @@ __device__ __forceinline__ void si_yolo_tile_one_image(const Args& a, float* out
             // it into two exec-masked branches per element plus one around every store: ~25 instructions per element)
             float v[NE];
 #pragma unroll
-            for (int e = 0; e < NE; ++e) v[e] = __builtin_amdgcn_rcpf(1.0f + __expf(-(acc[t][u][e] + bv)));
+            for (int e = 0; e < NE; ++e) v[e] = si_sigmoid_fast(acc[t][u][e] + bv);
             if (any_box) {
                 const float* const ap = auxp + (size_t)pix0 * a.yna * 2;
                 // the box lanes' grid / anchor values, ALL requested before the first one is used: with the load inside the element
@@ -176,7 +294,7 @@ __device__ __forceinline__ void si_yolo_tile_one_image(const Args& a, float* out
                 for (int e = 0; e < NE; ++e) auxv[e] = 0.0f;
                 if (is_box) {
 #pragma unroll
-                    for (int e = 0; e < NE; ++e) auxv[e] = ap[(MT == 32 ? (e & 3) + 8 * (e >> 2) : e) * a.yna * 2];
+                    for (int e = 0; e < NE; ++e) auxv[e] = ap[Mma<MT>::row(e) * a.yna * 2];
                 }
 #pragma unroll
                 for (int e = 0; e < NE; ++e) {
@@ -190,7 +308,7 @@ __device__ __forceinline__ void si_yolo_tile_one_image(const Args& a, float* out
             }
             if (live) {
 #pragma unroll
-                for (int e = 0; e < NE; ++e) op[(MT == 32 ? (e & 3) + 8 * (e >> 2) : e) * per_pix] = v[e];
+                for (int e = 0; e < NE; ++e) op[Mma<MT>::row(e) * per_pix] = v[e];
             }
         }
     }

@@ -25,8 +25,6 @@
 
 namespace {
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int SL_THREADS = 256;
 
 // the integer word a <T, V> item travels as

@@ -32,9 +32,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int SM_THREADS = 256;
 constexpr int SM_WAVES = SM_THREADS / 64;
 constexpr int SM_LANE_ELEMS = 16;   // floats of a row that a lane of the group / block forms keeps

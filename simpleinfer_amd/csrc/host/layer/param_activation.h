@@ -8,7 +8,7 @@
 // A numeric parameter may be written as a float or an int; a mistyped one is kFail.
 //
 // NOT an ActivationLayer, on purpose: FuseEpilogues folds every ActivationLayer into the convolution, transposed convolution or GroupNorm
-// in front of it by its ActCode(), and every kernel's apply_act ends in `default: return v` -- a folded code the kernels do not know would
+// in front of it by its ActCode(), and the kernels' si_act (si_hip_internal.h) ends in `default: return v` -- a folded code the kernels do not know would
 // drop the activation without a word.  This layer is always a launch of its own; folding ReLU6 / clamp / Mish into the epilogues is the
 // named follow-up.
 #ifndef SIMPLE_INFER_SRC_LAYER_PARAM_ACTIVATION_H_

@@ -208,7 +208,7 @@ def test_fp32_activation_meets_the_fp16_bar(kind):
     if kind == "leakyrelu":
         # x * 0.1f is no fp32 operation on fp16 operands: the slope has 24 bits, the product 35, and the plain fp32 product rounded again to
         # fp16 differs from the product rounded once on 103 inputs (by 1 ulp).  The bar is equality all the same, and it is reachable in fp32
-        # arithmetic: the product rounded to odd (what the kernel computes, mul_round_odd in ops_f16.hip), then the one rounding of the store
+        # arithmetic: the product rounded to odd (what the kernel computes, mul_round_odd in si_hip_internal.h), then the one rounding of the store
         assert er.assert_half(got, ref, 1, kind, er.H_MISMATCH_SHARE) == (103, 1)
         x = h.astype(np.float32)
         with np.errstate(all="ignore"):
