@@ -155,6 +155,12 @@ class SiRnnDesc(C.Structure):
         (k, C.c_longlong) for k in ("x_st", "x_sb", "g_st", "g_sb", "y_st", "y_sb")] + [("step0", C.c_int)]
 
 
+class SiBinaryDesc(C.Structure):
+    """include/si_binary.h; d: extents of x / out in storage order, c0_stride / c1_stride: element strides of the constants (0: broadcast)"""
+    _fields_ = [("d", C.c_int * 4), ("x_ld", C.c_int), ("out_ld", C.c_int), ("stages", C.c_int), ("op", C.c_int * 2), ("c0_stride", C.c_int * 4),
+                ("c1_stride", C.c_int * 4), ("grid_cap", C.c_int)]
+
+
 class SiLayoutNest(C.Structure):
     """include/si_layout.h; what si_layout_plan returns: view != 0, or the loop nest of the copy"""
     _fields_ = [("view", C.c_int), ("rank", C.c_int), ("dims", C.c_int * 8), ("in_stride", C.c_longlong * 8)]
@@ -423,9 +429,16 @@ def hip():
         "si_hip_rnn_pack_whh_f16": (i, [C.POINTER(SiRnnDesc), vp, vp]),
         "si_hip_rnn_kernel_name": (C.c_char_p, [C.POINTER(SiRnnDesc), vp, vp, i]),
     }
+    # include/si_binary.h: arithmetic of an activation against one or two graph constants (pnnx.Attribute operands)
+    binary_ = {
+        "si_hip_binary_const_f32": (i, [C.POINTER(SiBinaryDesc), vp, vp, vp, vp, vp]),
+        "si_hip_binary_const_f16": (i, [C.POINTER(SiBinaryDesc), vp, vp, vp, vp, vp]),
+        "si_hip_binary_const_kernel_name": (C.c_char_p, [C.POINTER(SiBinaryDesc), vp, vp, vp, vp, i]),
+    }
     for name, (res, args) in (list(sig.items()) + list(norm.items()) + list(pad.items()) + list(pool.items()) + list(softmax.items()) +
                               list(superres.items()) + list(slice_.items()) + list(reduce_.items()) + list(act.items()) + list(permute_.items()) +
-                              list(attention_.items()) + list(deform_.items()) + list(grid_.items()) + list(roi_.items()) + list(rnn_.items())):
+                              list(attention_.items()) + list(deform_.items()) + list(grid_.items()) + list(roi_.items()) + list(rnn_.items()) +
+                              list(binary_.items())):
         fn = getattr(L, name)  # AttributeError here = header/library mismatch, which tests check
         fn.restype = res
         fn.argtypes = args
@@ -444,6 +457,7 @@ def hip():
     L._si_grid_signatures = grid_
     L._si_roi_signatures = roi_
     L._si_rnn_signatures = rnn_
+    L._si_binary_signatures = binary_
     _hip = L
     return L
 

@@ -10,6 +10,7 @@
 
 #include <cfloat>
 
+#include "binary_plan.h"
 #include "si_hip.h"
 #include "si_hip_internal.h"
 
@@ -72,16 +73,9 @@ __device__ __forceinline__ f32x4 binary_apply4(int op, f32x4 x, f32x4 y) {
     for (int i = 0; i < 4; ++i) r[i] = binary_apply(op, x[i], y[i]);
     return r;
 }
-__host__ __device__ inline bool binary_op_known(int op) { return (op >= 0 && op <= 3) || (op >= 6 && op <= 11); }
-__host__ __device__ inline int binary_op_reversed(int op) {
-    switch (op) {
-        case 1: return 7; case 7: return 1;
-        case 3: return 8; case 8: return 3;
-        case 6: return 9; case 9: return 6;
-        case 10: return 11; case 11: return 10;
-        default: return op;  // add, mul commute exactly
-    }
-}
+// (the code tables: binary_plan.h, shared with binary_const.hip)
+inline bool binary_op_known(int op) { return si_binary_op_known(op); }
+inline int binary_op_reversed(int op) { return si_binary_op_reversed(op); }
 
 template <bool VEC>
 __global__ void binary_same_kernel(int op, const float* __restrict__ a, int a_ld, const float* __restrict__ b,

@@ -24,4 +24,11 @@ __attribute__((always_inline)) constexpr int si_fast_div(int n, int d, unsigned 
     return (int)q;
 }
 
+// quotient and remainder at once, same contract: what an index decomposition (item -> row, column) asks for at every level
+__attribute__((always_inline)) constexpr int si_fast_divmod(int n, int d, unsigned mg, int& rem) {
+    const int q = si_fast_div(n, d, mg);
+    rem = n - q * d;
+    return q;
+}
+
 #endif  // SI_MAGIC_H_

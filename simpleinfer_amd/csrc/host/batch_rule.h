@@ -10,6 +10,7 @@
 #define SIMPLE_INFER_SRC_BATCH_RULE_H_
 
 #include <map>
+#include <set>
 #include <string>
 #include <vector>
 
@@ -48,8 +49,27 @@ inline int FollowBatchAxis(const pnnx::Operator* op, const std::vector<int>& in,
     return -1;
 }
 
+// Graph constants: the output of a pnnx.Attribute operator (a tensor stored in the file), and every output of an operator whose inputs are all
+// constants.  A constant is no image of the batch whatever its dimension 0 says: it is never re-batched and never cut into slabs.
+inline bool IsAttributeOp(const pnnx::Operator* op) { return op->type == "pnnx.Attribute"; }
+
+inline std::set<const pnnx::Operand*> ConstantOperands(const std::vector<pnnx::Operator*>& ops) {
+    std::set<const pnnx::Operand*> constants;
+    for (const pnnx::Operator* op : ops) {
+        bool all = IsAttributeOp(op);
+        if (!all && !op->inputs.empty()) {
+            all = true;
+            for (const pnnx::Operand* in : op->inputs) all = all && constants.count(in) > 0;
+        }
+        if (all)
+            for (const pnnx::Operand* out : op->outputs) constants.insert(out);
+    }
+    return constants;
+}
+
 // The batch dimension of every operand, followed from the graph inputs (dimension 0 where it holds `file_batch`) through the operators in
-// file order; -1: the operand does not carry the batch, or where it does is not known.
+// file order; -1: the operand does not carry the batch, or where it does is not known.  A constant (ConstantOperands) has
+// -1 even when its dimension 0 equals the traced batch.
 inline std::map<const pnnx::Operand*, int> FollowBatchAxes(const std::vector<pnnx::Operator*>& ops, int file_batch) {
     std::map<const pnnx::Operand*, int> batch_axis;
     for (const pnnx::Operator* op : ops) {
@@ -61,7 +81,8 @@ inline std::map<const pnnx::Operand*, int> FollowBatchAxes(const std::vector<pnn
         }
         const bool recurrent = op->type == "nn.LSTM" || op->type == "nn.GRU";
         for (const pnnx::Operand* out : op->outputs) {
-            if (op->inputs.empty()) batch_axis[out] = (!out->shape.empty() && out->shape[0] == file_batch) ? 0 : -1;
+            if (IsAttributeOp(op)) batch_axis[out] = -1;
+            else if (op->inputs.empty()) batch_axis[out] = (!out->shape.empty() && out->shape[0] == file_batch) ? 0 : -1;
             else if (recurrent && src) {
                 // y keeps the input's batch dimension; the state outputs [layers * dirs, N, H] carry it in dimension 1 whatever batch_first says
                 const int to = out == op->outputs[0] ? axis : 1;
@@ -72,11 +93,11 @@ inline std::map<const pnnx::Operand*, int> FollowBatchAxes(const std::vector<pnn
     return batch_axis;
 }
 
-// the batch the file was traced with: dimension 0 of the graph inputs (0: none, or they disagree)
+// the batch the file was traced with: dimension 0 of the graph inputs (0: none, or they disagree); a pnnx.Attribute is no graph input
 inline int FileBatch(const std::vector<pnnx::Operator*>& ops) {
     int file_batch = 0;
     for (const pnnx::Operator* op : ops) {
-        if (!op->inputs.empty()) continue;
+        if (!op->inputs.empty() || IsAttributeOp(op)) continue;
         for (const pnnx::Operand* out : op->outputs) {
             if (out->shape.empty() || out->shape[0] <= 0 || (file_batch != 0 && file_batch != out->shape[0])) return 0;
             file_batch = out->shape[0];
@@ -103,6 +124,7 @@ enum class BatchFamily {
     kReshape,       // reshape / view / flatten / squeeze / unsqueeze / contiguous: per-image while the batch stays a dimension of its own
     kAttention,     // nn.MultiheadAttention: reads the batch from dimension 0 (batch_first) or 1
     kRoi,           // torchvision.ops.RoIAlign / roi_align: boxes [K, 5] that name their image by an index in the data -- never per-image
+    kConstant,      // pnnx.Attribute: a tensor of the file, the same for every image -- always per-image
     kRecurrent,     // nn.LSTM / nn.GRU: reads the batch from dimension 0 (batch_first) or 1; y keeps it there, the state outputs carry it in 1
 };
 
@@ -115,6 +137,7 @@ inline BatchFamily BatchFamilyOf(const std::string& type) {
     static const std::map<std::string, BatchFamily> table = {
         {"pnnx.Input", BatchFamily::kInput},
         {"pnnx.Output", BatchFamily::kOutput},
+        {"pnnx.Attribute", BatchFamily::kConstant},
         {"nn.Conv2d", BatchFamily::kSpatial},
         {"nn.ConvTranspose2d", BatchFamily::kSpatial},
         {"torchvision.ops.DeformConv2d", BatchFamily::kSpatial},   // (offset and mask are per-pixel operands of the same image)
@@ -205,6 +228,7 @@ inline BatchFamily BatchFamilyOf(const std::string& type) {
 struct BatchOperand {
     std::vector<int> shape;
     int axis = -1;
+    bool constant = false;   // a graph constant (ConstantOperands): broadcast over the images by design, its axis is -1
 };
 
 // Is `op` per-image: does image i of every output depend on image i of the inputs alone, so that the operator re-batched to a slab of the
@@ -219,7 +243,7 @@ inline bool PerImageOperator(const pnnx::Operator* op, const std::vector<BatchOp
         why = "the batch rule has no row for the operator type " + op->type + ", so nothing is known about how it treats the batch";
         return false;
     }
-    if (family == BatchFamily::kInput) return true;
+    if (family == BatchFamily::kInput || family == BatchFamily::kConstant) return true;
     if (family == BatchFamily::kRoi) {
         // whatever the shapes say: K == N is a coincidence, and a slab of the boxes still indexes every image
         why = RoiBatchReason();
@@ -246,6 +270,17 @@ inline bool PerImageOperator(const pnnx::Operator* op, const std::vector<BatchOp
     // that carries the batch elsewhere pairs image i with something that is not image i
     if (batch > 1) {
         for (size_t i = 0; i < in.size(); ++i) {
+            if (in[i].constant) {
+                // a constant is exempt from both checks below: the same tensor meets every image.  What it must not do is hold one value PER
+                // image: an extent above 1 where the other operand (shapes are right-aligned, as torch broadcasts) carries the batch
+                const int at = axis - (rank - (int)in[i].shape.size());
+                if (at >= 0 && at < (int)in[i].shape.size() && in[i].shape[at] != 1) {
+                    why = "the constant input " + std::to_string(i) + " has extent " + std::to_string(in[i].shape[at]) + " along the batch " +
+                          dim_text(axis) + " of input " + std::to_string(first) + ": it pairs one slice of itself with each image";
+                    return false;
+                }
+                continue;
+            }
             if (in[i].axis < 0) {
                 why = "input " + std::to_string(i) + " has no batch dimension while input " + std::to_string(first) + " carries " +
                       std::to_string(batch) + " images: one value is combined with every image";
@@ -390,6 +425,7 @@ inline std::vector<BatchMixingEntry> FindBatchMixing(const std::vector<pnnx::Ope
         return found;
     }
     const std::map<const pnnx::Operand*, int> axes = FollowBatchAxes(ops, file_batch);
+    const std::set<const pnnx::Operand*> constants = ConstantOperands(ops);
     auto describe = [&](const std::vector<pnnx::Operand*>& operands) {
         std::vector<BatchOperand> v;
         for (const pnnx::Operand* r : operands) {
@@ -397,6 +433,7 @@ inline std::vector<BatchMixingEntry> FindBatchMixing(const std::vector<pnnx::Ope
             b.shape = r->shape;
             auto it = axes.find(r);
             b.axis = it == axes.end() ? -1 : it->second;
+            b.constant = constants.count(r) > 0;
             v.push_back(b);
         }
         return v;

@@ -185,13 +185,15 @@ int si_pnnx_save(const char* param_path, const char* bin_path, int expand, int b
         if (batch > 0) {
             int traced = 0;
             for (const pnnx::Operand* r : g.operands)
-                if (r->producer && r->producer->inputs.empty() && !r->shape.empty()) {
+                if (r->producer && r->producer->inputs.empty() && !SimpleInfer::IsAttributeOp(r->producer) && !r->shape.empty()) {
                     if (traced != 0 && traced != r->shape[0]) return 5;
                     traced = r->shape[0];
                 }
             if (traced <= 0) return 5;
+            // (a graph constant keeps its shape and its bytes: it is no image of the batch, batch_rule.h)
+            const std::set<const pnnx::Operand*> constants = SimpleInfer::ConstantOperands(g.ops);
             for (pnnx::Operand* r : g.operands)
-                if (!r->shape.empty() && r->shape[0] == traced) r->shape[0] = batch;
+                if (!r->shape.empty() && r->shape[0] == traced && !constants.count(r)) r->shape[0] = batch;
         }
         return g.save(out_param_path, out_bin_path) == 0 ? 0 : 2;
     } catch (const std::exception&) {

@@ -189,7 +189,7 @@ Status EngineImpl::CreateTensorNodes() {
                 return Status::kUnsupport;
             }
         for (pnnx::Operand* opd : graph_->operands)
-            if (opd->producer && opd->producer->inputs.empty() && !opd->shape.empty()) {
+            if (opd->producer && opd->producer->inputs.empty() && !IsAttributeOp(opd->producer) && !opd->shape.empty()) {
                 if (file_batch != 0 && file_batch != opd->shape[0]) {
                     LOG(ERROR) << "re-batch: graph inputs disagree on the batch dimension";
                     return Status::kUnsupport;
@@ -238,6 +238,32 @@ Status EngineImpl::CreateTensorNodes() {
             }
         }
     }
+    // graph constants (pnnx.Attribute outputs, and what is computed from constants alone): no image of the batch, never re-batched
+    const std::set<const pnnx::Operand*> constants = ConstantOperands(graph_->ops);
+    for (const pnnx::Operator* op : graph_->ops) {
+        if (!IsAttributeOp(op)) continue;
+        auto data = op->attrs.find("data");
+        if (op->outputs.size() != 1 || data == op->attrs.end()) {
+            LOG(ERROR) << "pnnx.Attribute [" << op->name << "]: no data attribute (or not exactly one output)";
+            return Status::kFail;
+        }
+        if (data->second.type != 1 || op->outputs[0]->type != 1) {
+            LOG(ERROR) << "pnnx.Attribute [" << op->name << "]: constants of a type other than f32 are not served";
+            return Status::kUnsupport;
+        }
+        size_t elems = 1;
+        for (int d : op->outputs[0]->shape) elems *= d > 0 ? (size_t)d : 0;
+        if (op->outputs[0]->shape.empty() || elems == 0 || data->second.shape != op->outputs[0]->shape || data->second.data.size() != elems * sizeof(float)) {
+            LOG(ERROR) << "pnnx.Attribute [" << op->name << "]: the data holds " << data->second.data.size() << " bytes, the operand's shape asks for "
+                       << elems * sizeof(float);
+            return Status::kFail;
+        }
+        for (const pnnx::Operator* c : op->outputs[0]->consumers)
+            if (c && c->outputs.empty()) {
+                LOG(ERROR) << "pnnx.Attribute [" << op->name << "]: a constant that is a graph output directly is not served";
+                return Status::kUnsupport;
+            }
+    }
     for (pnnx::Operand* opd : graph_->operands) {
         if (tensor_nodes_.count(opd->name) > 0) {
             LOG(ERROR) << "tensor node [" << opd->name << "] already exists";
@@ -250,7 +276,7 @@ Status EngineImpl::CreateTensorNodes() {
         std::vector<int> file = opd->shape;
         auto moved = batch_axis.find(opd);
         if (moved != batch_axis.end() && moved->second >= 1) file[moved->second] = opt_.batch;
-        else if (file_batch > 0 && !file.empty() && file[0] == file_batch) file[0] = opt_.batch;
+        else if (file_batch > 0 && !file.empty() && file[0] == file_batch && !constants.count(opd)) file[0] = opt_.batch;
         std::vector<int> shape = file;
         const int rank = (int)shape.size();
         if (rank > 3) {
@@ -260,7 +286,8 @@ Status EngineImpl::CreateTensorNodes() {
         }
         DataType dt = PnnxToDataType(opd->type);
         // graph inputs: produced by an operator with no inputs (pnnx.Input)
-        const bool is_input = opd->producer && opd->producer->inputs.empty();
+        const bool is_constant = opd->producer && IsAttributeOp(opd->producer);
+        const bool is_input = opd->producer && opd->producer->inputs.empty() && !is_constant;
         // graph outputs: consumed by an operator with no outputs (pnnx.Output)
         bool is_output = false;
         for (pnnx::Operator* c : opd->consumers)
@@ -269,6 +296,7 @@ Status EngineImpl::CreateTensorNodes() {
         // (Input / Extract) keep the file's type
         if (opt_.fp16 && dt == DataType::kFloat32 && !is_input && !is_output) dt = DataType::kFloat16;
         node->tensor = Tensor(dt, shape, MemoryType::kDevice, false);
+        node->constant = is_constant;
         tensor_nodes_[opd->name] = node;
         if (is_input) input_tensor_nodes_[opd->name] = node;
         if (is_output) output_tensor_nodes_[opd->name] = node;
@@ -288,7 +316,7 @@ Status EngineImpl::DestroyTensorNodes() {
 
 Status EngineImpl::CreateLayers() {
     for (pnnx::Operator* op : graph_->ops) {
-        if ("pnnx.Input" == op->type || "pnnx.Output" == op->type) continue;
+        if ("pnnx.Input" == op->type || "pnnx.Output" == op->type || IsAttributeOp(op)) continue;   // (a constant has no layer and no step)
         if (layers_.count(op->name) > 0) {
             LOG(ERROR) << "layer [" << op->name << "] already exists";
             return Status::kFail;
@@ -418,6 +446,11 @@ Status EngineImpl::AllocateTensorMemory() {
     for (auto& kv : tensor_nodes_) {
         const std::string& name = kv.first;
         Tensor& t = kv.second->tensor;
+        if (kv.second->constant) {
+            // outside the arena, filled once, never written; an engine that runs as lanes leaves it to them (each loads its own copy)
+            if (lanes_.empty()) CHECK_STATUS(UploadConstant(kv.second));
+            continue;
+        }
         if (dead_operands_.count(name) || aliases_.count(name)) continue;
         if (!lanes_.empty() && !input_tensor_nodes_.count(name) && !output_tensor_nodes_.count(name)) continue;   // the lanes own the intermediates
         const size_t bytes = t.ByteSize();
@@ -456,6 +489,56 @@ Status EngineImpl::AllocateTensorMemory() {
     return Status::kSuccess;
 }
 
+// The stored image of a constant: the file's fp32 data of shape `file` under the storage rule of its rank -- rank >= 4 has its last three dims
+// C,H,W stored H,W,C; the transpose happens here, on the host, once.
+static std::vector<float> StoredImage(const float* src, const std::vector<int>& file) {
+    size_t total = 1;
+    for (int d : file) total *= (size_t)d;
+    std::vector<float> dst(total);
+    const size_t r = file.size();
+    if (r < 4) {
+        std::copy(src, src + total, dst.begin());
+        return dst;
+    }
+    const size_t C = file[r - 3], H = file[r - 2], W = file[r - 1], lead = total / (C * H * W);
+    for (size_t l = 0; l < lead; ++l)
+        for (size_t c = 0; c < C; ++c)
+            for (size_t h = 0; h < H; ++h)
+                for (size_t w = 0; w < W; ++w) dst[((l * H + h) * W + w) * C + c] = src[((l * C + c) * H + h) * W + w];
+    return dst;
+}
+
+// a constant's own buffer and those of its promoted images: allocated, filled from the Attribute's data (under fp16 storage converted to half
+// once, round-to-nearest-even), bound
+Status EngineImpl::UploadConstant(TensorNode* node) {
+    const pnnx::Operator* op = node->operand->producer;
+    const pnnx::Attribute& data = op->attrs.at("data");
+    const float* src = reinterpret_cast<const float*>(data.data.data());
+    const std::vector<int>& file = node->operand->shape;
+    auto upload = [&](Tensor& t, int rank) -> Status {
+        std::vector<int> padded((size_t)rank - file.size(), 1);
+        padded.insert(padded.end(), file.begin(), file.end());
+        const std::vector<float> image = StoredImage(src, padded);
+        if (image.size() != t.NumElements()) return Status::kErrorShape;
+        void* p = nullptr;
+        SI_TRY_HIP(si_hip_malloc(&p, t.ByteSize()), "hipMalloc constant");
+        device_allocs_.push_back(p);
+        if (t.GetDataType() == DataType::kFloat16) {
+            std::vector<unsigned short> half(image.size());
+            SI_TRY_HIP(si_hip_f32_to_f16_host(image.data(), half.data(), image.size()), "constant to half");
+            SI_TRY_HIP(si_hip_memcpy_h2d(p, half.data(), t.ByteSize(), nullptr), "constant h2d");
+        } else {
+            SI_TRY_HIP(si_hip_memcpy_h2d(p, image.data(), t.ByteSize(), nullptr), "constant h2d");
+        }
+        SI_TRY_HIP(si_hip_stream_sync(nullptr), "constant h2d sync");
+        t.SetView(p, MemoryType::kDevice, 0);
+        return Status::kSuccess;
+    };
+    CHECK_STATUS(upload(node->tensor, (int)file.size()));
+    for (auto& kv : node->promoted) CHECK_STATUS(upload(kv.second, kv.first));
+    return Status::kSuccess;
+}
+
 // allocate the planned arena (once) and point the operands -- and the aliases (concat inputs, split outputs), which hang off them -- into it
 Status EngineImpl::EnsureArena() {
     if (arena_pending_) {
@@ -491,7 +574,10 @@ Status EngineImpl::DeallocateTensorMemory() {
     own_output_ptrs_.clear();
     for (auto& kv : host_outputs_) si_hip_host_free(kv.second);
     host_outputs_.clear();
-    for (auto& kv : tensor_nodes_) kv.second->tensor.SetView(nullptr, MemoryType::kDevice, 0);
+    for (auto& kv : tensor_nodes_) {
+        kv.second->tensor.SetView(nullptr, MemoryType::kDevice, 0);
+        for (auto& image : kv.second->promoted) image.second.SetView(nullptr, MemoryType::kDevice, 0);
+    }
     return Status::kSuccess;
 }
 

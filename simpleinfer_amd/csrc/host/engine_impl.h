@@ -115,6 +115,7 @@ private:
     Status FuseStemTriples(std::vector<Step>& order);
     Status FuseCv3IntoPairs(std::vector<Step>& order);
     Status FuseBottleneckPairs(std::vector<Step>& order);
+    Status FuseConstStages(std::vector<Step>& order);
     Status InsertOutputCasts(std::vector<Step>& order);
     Status InsertFp32Fallbacks(std::vector<Step>& order);
     Status AliasConcats();
@@ -122,6 +123,7 @@ private:
     Status AliasViews();
     void ResolveAliases();
     Status UploadInputs();
+    Status UploadConstant(TensorNode* node);   // a pnnx.Attribute's buffers: allocated outside the arena and filled once
     Status BindOutputs();
     Status LaunchAll();
     Status EndForward();   // ForwardAsync's tail: stop event, outputs to host, the step counted

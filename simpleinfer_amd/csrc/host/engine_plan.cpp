@@ -49,6 +49,8 @@ Status EngineImpl::CreatePipeline() {
     std::vector<Step> order;
     std::set<const pnnx::Operand*> ready;
     for (auto& kv : input_tensor_nodes_) ready.insert(kv.second->operand);
+    for (auto& kv : tensor_nodes_)
+        if (kv.second->constant) ready.insert(kv.second->operand);   // (a graph constant is there before the first step)
     std::vector<const pnnx::Operator*> pending;
     for (pnnx::Operator* op : graph_->ops)
         if (layers_.count(op->name)) pending.push_back(op);
@@ -83,6 +85,7 @@ Status EngineImpl::CreatePipeline() {
         if (opt_.fuse_layout) CHECK_STATUS(FuseLayoutChains(order));
         if (opt_.fuse_layout && opt_.fuse_grid) CHECK_STATUS(FuseGridInPlace(order));   // (after the chains are composed: the run in front of a sampler is one step)
         if (opt_.fuse_grid) CHECK_STATUS(FuseAffineGrids(order));
+        if (opt_.fuse_const) CHECK_STATUS(FuseConstStages(order));
         if (opt_.fuse_upsample && opt_.alias_cat) CHECK_STATUS(FuseUpsampleIntoConvs(order));   // (fp16 storage too since round 4)
         if (opt_.fp16 && opt_.fuse_stem) CHECK_STATUS(FuseStemPairs(order));
         if (opt_.fp16 && opt_.fuse_stem > 1) CHECK_STATUS(FuseStemTriples(order));
@@ -296,6 +299,27 @@ Status EngineImpl::FuseEpilogues(std::vector<Step>& order) {
             p.removed[last] = false;
             p.removed[i] = true;
         }
+    }
+    p.Compact();
+    return Status::kSuccess;
+}
+
+// BinaryOp(x, c0) -> BinaryOp(., c1), c0 and c1 graph constants (FrozenBatchNorm2d's x * scale + shift): one two-stage launch of the
+// constant-operand kernel (include/si_binary.h) at the first operator's slot.  x is read once and the result written once; the kernel rounds
+// after each stage exactly as the two launches do, so the bits are those of fuse_const = 0.  The second step is retired and the operand between
+// the two is dead.  (Folding the constants into a preceding conv's weights and bias would save the launch altogether but changes rounding: not done.)
+Status EngineImpl::FuseConstStages(std::vector<Step>& order) {
+    Pass p(*this, order);
+    for (size_t i = 0; i < order.size(); ++i) {
+        BinaryOp* a = p.At<BinaryOp>(i, "BinaryOp");
+        if (!a || !a->ConstForm() || a->Stages() != 1 || order[i].op->outputs.size() != 1) continue;
+        const pnnx::Operand* mid = order[i].op->outputs[0];
+        const pnnx::Operator* c = p.SoleConsumer(mid);
+        BinaryOp* b = c ? dynamic_cast<BinaryOp*>(p.LayerOf(c)) : nullptr;
+        if (!b || c->type != "BinaryOp" || c->outputs.size() != 1 || !a->CanAbsorb(*b, tensor_nodes_[mid->name])) continue;
+        a->Absorb(*b);
+        a->SetOutputNodes({tensor_nodes_[c->outputs[0]->name]});
+        p.Retire(p.index[c], mid);
     }
     p.Compact();
     return Status::kSuccess;
@@ -786,7 +810,7 @@ Status EngineImpl::AliasSplits() {
         const pnnx::Operand* x = s.op->inputs[0];
         TensorNode* in = sl->InputNodes()[0];
         // (an fp32 fallback rebinds the layer to shadow tensors: those are not the file's operands and nothing aliases them)
-        if (!x || tensor_nodes_[x->name] != in || input_tensor_nodes_.count(x->name) || output_tensor_nodes_.count(x->name)) continue;
+        if (!x || tensor_nodes_[x->name] != in || input_tensor_nodes_.count(x->name) || output_tensor_nodes_.count(x->name) || in->constant) continue;
         const std::vector<int>& xs = in->tensor.Shape();
         const std::vector<Slice::Piece>& pieces = sl->Pieces();
         if (xs.size() != 4 || pieces.size() != s.op->outputs.size() || sl->OutputNodes().size() != pieces.size()) continue;
@@ -824,7 +848,7 @@ Status EngineImpl::AliasViews() {
         const pnnx::Operand* r = s.op->outputs[0];
         // (fp32 fallbacks and output casts rebind a layer to shadow / staging tensors: those are not the file's operands and nothing aliases them)
         if (!x || !r || tensor_nodes_[x->name] != in || tensor_nodes_[r->name] != out) continue;
-        if (input_tensor_nodes_.count(x->name) || output_tensor_nodes_.count(x->name) || output_tensor_nodes_.count(r->name)) continue;
+        if (input_tensor_nodes_.count(x->name) || output_tensor_nodes_.count(x->name) || output_tensor_nodes_.count(r->name) || in->constant) continue;
         if (aliases_.count(r->name) || dead_operands_.count(r->name) || dead_operands_.count(x->name)) continue;
         if (in->tensor.GetDataType() != out->tensor.GetDataType() || in->tensor.NumElements() != out->tensor.NumElements()) continue;
         // the parent is dense: it is no channel slice of another buffer (a view of a view is fine: that alias is whole and dense itself) and

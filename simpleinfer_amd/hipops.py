@@ -1016,6 +1016,45 @@ def binary_op(op, a, b, out_shape=None, in_ld=None, in_c_off=0, in_fill=0.0, b_l
     return _ret(y, o4[3], out_c_off, False).reshape(out_shape if out_shape is not None else o4)
 
 
+def binary_const_desc(x_shape, ops, const_shapes, in_ld=None, out_ld=None, grid_cap=0):
+    """SiBinaryDesc (include/si_binary.h) of a rank-4 x in storage order and one or two dense constants of rank-4 shapes that broadcast to it
+    (a dimension is x's or 1): the strides of a dense array, 0 where the constant is broadcast"""
+    d4 = [int(v) for v in x_shape]
+    assert len(d4) == 4 and 1 <= len(ops) <= 2 and len(ops) == len(const_shapes)
+    strides = []
+    for cs in const_shapes:
+        cs = [int(v) for v in cs]
+        assert len(cs) == 4 and all(c == x or c == 1 for c, x in zip(cs, d4)), (cs, d4)
+        dense = [cs[1] * cs[2] * cs[3], cs[2] * cs[3], cs[3], 1]
+        strides.append([0 if c == 1 else s for c, s in zip(cs, dense)])
+    strides.append([0, 0, 0, 0])
+    ops = [int(o) for o in ops] + [0]
+    I4, I2 = C.c_int * 4, C.c_int * 2
+    return _native.SiBinaryDesc(I4(*d4), in_ld or d4[3], out_ld or d4[3], len(const_shapes), I2(*ops[:2]), I4(*strides[0]), I4(*strides[1]),
+                                int(grid_cap))
+
+
+def binary_const(x, ops, consts, c_off=0, grid_cap=0, in_ld=None, in_c_off=0, in_fill=0.0, out_ld=None, out_c_off=0, out_fill=0.0, full=False):
+    """si_hip_binary_const_f32 / _f16 (by x's dtype): out = ops[1](ops[0](x, consts[0]), consts[1]) with the BinaryOp codes (7 / 8 / 9 / 11 put
+    the constant first).  consts: arrays that broadcast to the rank-4 x, uploaded dense behind c_off spare elements (c_off = 1: a pointer that
+    is not 16-byte aligned).  The view hooks are the common ones."""
+    x = _float_storage(x)
+    assert x.ndim == 4
+    consts = [np.ascontiguousarray(c, dtype=x.dtype) for c in consts]
+    d = binary_const_desc(x.shape, ops, [c.shape for c in consts], in_ld, out_ld, grid_cap)
+    bufs = [DeviceBuffer.from_numpy(np.concatenate([np.zeros(c_off, x.dtype), c.reshape(-1)])) for c in consts]
+    ptrs = [b.ptr + c_off * x.dtype.itemsize for b in bufs] + [0]
+    return _run_desc_op("binary_const", d, x, x.shape[:3], x.shape[3], in_ld, in_c_off, in_fill, out_ld, out_c_off, out_fill, full,
+                        operands=ptrs[:2])
+
+
+def binary_const_kernel_name(x_shape, ops, const_shapes, half=False, in_ld=None, out_ld=None, grid_cap=0) -> str:
+    """the instantiation for 16-byte aligned buffers of these shapes ("none": a descriptor the launch refuses)"""
+    d = binary_const_desc(x_shape, ops, const_shapes, in_ld, out_ld, grid_cap)
+    p = C.c_void_p(256)
+    return _native.hip().si_hip_binary_const_kernel_name(C.byref(d), p, p, p, p, 1 if half else 0).decode()
+
+
 def binary_scalar(op, x, scalar, in_ld=None, in_c_off=0, in_fill=0.0, out_ld=None, out_c_off=0, out_fill=0.0, full=False):
     """out = x (op) scalar -- BinaryOp's with_scalar form (op codes of include/si_hip.h; 7 / 8 / 9 / 11 put the scalar first)."""
     H = _native.hip()

@@ -126,6 +126,15 @@ class PnnxBuilder:
     def output(self, x: str):
         self._emit("pnnx.Output", self._opname("pnnx_output"), [x], [])
 
+    def attribute(self, array, name: str = None) -> str:
+        """A graph constant as pnnx writes every tensor that is neither a module weight nor an input: `pnnx.Attribute name 0 1 out
+        @data=(shape)f32`, the values (file order) in the .bin under name.data"""
+        arr = np.ascontiguousarray(array, dtype=np.float32)
+        assert arr.ndim >= 1
+        out = self._new_operand(arr.shape)
+        self._emit("pnnx.Attribute", name or self._opname("pnnx_attr"), [], [out], attrs={"data": arr})
+        return out
+
     def conv(self, x: str, cout: int, k, s=1, p=None, d=1, groups: int = 1, bias: bool = True,
              name: str = None) -> str:
         n, cin, h, w = self.shapes[x]
@@ -1254,8 +1263,8 @@ def build_toy_stn(batch: int = 2, size: int = 32, seed: int = 0) -> PnnxBuilder:
 
 def build_toy_flow_warp(batch: int = 2, height: int = 24, width: int = 20, c: int = 8, seed: int = 0) -> PnnxBuilder:
     """Warping features by a predicted flow (EDVR / BasicVSR++ / RIFE style).  Two graph inputs: the image [N, 3, H, W] and a channels-first
-    base grid [N, 2, H, W] (channel 0 x, channel 1 y, normalised for align_corners=True: flow_base_grid; graph constants are not served, so
-    the caller supplies it).  A feature conv 3 -> c; a 3x3 flow conv c -> 2 + nn.Tanh; base + flow -> permute(0, 2, 3, 1) ->
+    base grid [N, 2, H, W] (channel 0 x, channel 1 y, normalised for align_corners=True: flow_base_grid; build_toy_flow_warp_const holds it
+    as a graph constant instead).  A feature conv 3 -> c; a 3x3 flow conv c -> 2 + nn.Tanh; base + flow -> permute(0, 2, 3, 1) ->
     F.grid_sample(features, grid; bilinear, border, align_corners=True) -> 1x1 conv c -> c."""
     b = PnnxBuilder(seed)
     img = b.input((batch, 3, height, width))
@@ -1264,6 +1273,75 @@ def build_toy_flow_warp(batch: int = 2, height: int = 24, width: int = 20, c: in
     flow = b.tanh(b.conv(feat, 2, 3, 1, 1))
     grid = b.permute(b.add(base, flow), (0, 2, 3, 1))
     b.output(b.conv(b.grid_sample(feat, grid, "bilinear", "border", True), c, 1))
+    return b
+
+
+def build_toy_flow_warp_const(batch: int = 2, height: int = 24, width: int = 20, c: int = 8, seed: int = 0) -> PnnxBuilder:
+    """build_toy_flow_warp as an export writes it: the base grid is a graph constant [1, 2, H, W] (flow_base_grid in file order), broadcast
+    over the batch by the add, and the image is the only graph input.  Same weights, same operators otherwise."""
+    b = PnnxBuilder(seed)
+    img = b.input((batch, 3, height, width))
+    base = b.attribute(flow_base_grid(1, height, width).transpose(0, 3, 1, 2))
+    feat = b.conv(img, c, 3, 1, 1)
+    flow = b.tanh(b.conv(feat, 2, 3, 1, 1))
+    grid = b.permute(b.expression("add(@0,@1)", [base, flow], b.shapes[flow]), (0, 2, 3, 1))
+    b.output(b.conv(b.grid_sample(feat, grid, "bilinear", "border", True), c, 1))
+    return b
+
+
+def build_toy_frozenbn_block(batch: int = 2, size: int = 16, c: int = 16, seed: int = 0) -> PnnxBuilder:
+    """A torchvision detection backbone's residual block: FrozenBatchNorm2d is no module to pnnx but `x * scale + shift`, one
+    pnnx.Expression over two [1, C, 1, 1] constants.  stem conv 3 -> c stride 2 + ReLU; conv 3x3 -> frozen bn -> ReLU -> conv 3x3 ->
+    frozen bn -> + skip -> ReLU."""
+    b = PnnxBuilder(seed)
+    x = b.relu(b.conv(b.input((batch, 3, size, size)), c, 3, 2, 1))
+
+    def frozen_bn(y, tag):
+        scale = b.attribute(seeded_uniform(tag + ".scale", (1, c, 1, 1), 0.5, 1.5, seed))
+        shift = b.attribute(seeded_uniform(tag + ".shift", (1, c, 1, 1), -0.5, 0.5, seed))
+        return b.expression("add(mul(@0,@1),@2)", [y, scale, shift])
+
+    y = b.relu(frozen_bn(b.conv(x, c, 3, 1, 1, bias=False), "fbn0"))
+    y = frozen_bn(b.conv(y, c, 3, 1, 1, bias=False), "fbn1")
+    b.output(b.relu(b.add(y, x)))
+    return b
+
+
+def build_toy_layer_scale(batch: int = 2, size: int = 16, c: int = 24, seed: int = 0) -> PnnxBuilder:
+    """A ConvNeXt-style block at toy width: stem conv 3 -> c stride 2; depthwise 3x3 -> 1x1 + ReLU -> 1x1 -> gamma * y with the layer scale
+    gamma a constant [C, 1, 1] on the LEFT (rank 3 against rank 4: torch right-aligns it to [1, C, 1, 1]) -> + x."""
+    b = PnnxBuilder(seed)
+    x = b.conv(b.input((batch, 3, size, size)), c, 3, 2, 1)
+    y = b.conv(b.relu(b.conv(b.conv(x, c, 3, 1, 1, groups=c), 2 * c, 1)), c, 1)
+    gamma = b.attribute(seeded_uniform("layer_scale.gamma", (c, 1, 1), 0.05, 0.5, seed))
+    b.output(b.add(b.expression("mul(@0,@1)", [gamma, y], b.shapes[y]), x))
+    return b
+
+
+def build_toy_pos_embed(batch: int = 2, size: int = 16, c: int = 32, heads: int = 4, batch_first: bool = False, seed: int = 0) -> PnnxBuilder:
+    """Learned position embeddings on tokens around nn.MultiheadAttention.  Seq-first (C3TR's order): convs -> flatten(2) -> permute(2, 0, 1),
+    tokens [L, N, E] + a constant [L, 1, E].  batch_first: permute(0, 2, 1), tokens [N, L, E] + a constant [1, L, E].  Then self-attention
+    + x and a Linear."""
+    b = PnnxBuilder(seed)
+    x = b.silu(b.conv(b.input((batch, 3, size, size)), c, 3, 2, 1))
+    x = b.silu(b.conv(x, c, 3, 2, 1))
+    _, _, h, w = b.shapes[x]
+    t = b.permute(b.flatten(x, 2), (0, 2, 1) if batch_first else (2, 0, 1))
+    pos = b.attribute(seeded_uniform("pos_embed", (1, h * w, c) if batch_first else (h * w, 1, c), -0.5, 0.5, seed))
+    t = b.expression("add(@0,@1)", [t, pos])
+    t = b.add(b.multihead_attention(t, num_heads=heads, batch_first=batch_first), t)
+    b.output(b.linear(t, c))
+    return b
+
+
+def build_toy_fcos_scale(batch: int = 2, size: int = 32, seed: int = 0) -> PnnxBuilder:
+    """FCOS's box regression: per pyramid level conv -> exp(x * s) with s a learned scalar, a constant of shape [1] per level; the two
+    levels are two graph outputs."""
+    b = PnnxBuilder(seed)
+    for i, f in enumerate(_toy_pyramid(b, batch, size)):
+        s = b.attribute(np.asarray([0.75 + 0.5 * i], np.float32))
+        y = b.conv(f, 4, 3, 1, 1)
+        b.output(b.expression("exp(mul(@0,@1))", [y, s]))
     return b
 
 
