@@ -155,6 +155,12 @@ class SiRnnDesc(C.Structure):
         (k, C.c_longlong) for k in ("x_st", "x_sb", "g_st", "g_sb", "y_st", "y_sb")] + [("step0", C.c_int)]
 
 
+class SiConv1dDesc(C.Structure):
+    """include/si_conv1d.h; sn / sc: element strides of the batch index and of the channel row of x and y"""
+    _fields_ = [(k, C.c_int) for k in ("n", "c", "l", "oc", "lo", "k", "stride", "dilation", "pad_left", "groups")] + [
+        (k, C.c_longlong) for k in ("x_sn", "x_sc", "y_sn", "y_sc")] + [("act", C.c_int), ("act_param", C.c_float)]
+
+
 class SiBinaryDesc(C.Structure):
     """include/si_binary.h; d: extents of x / out in storage order, c0_stride / c1_stride: element strides of the constants (0: broadcast)"""
     _fields_ = [("d", C.c_int * 4), ("x_ld", C.c_int), ("out_ld", C.c_int), ("stages", C.c_int), ("op", C.c_int * 2), ("c0_stride", C.c_int * 4),
@@ -435,10 +441,19 @@ def hip():
         "si_hip_binary_const_f16": (i, [C.POINTER(SiBinaryDesc), vp, vp, vp, vp, vp]),
         "si_hip_binary_const_kernel_name": (C.c_char_p, [C.POINTER(SiBinaryDesc), vp, vp, vp, vp, i]),
     }
+    # include/si_conv1d.h: the temporal convolution kernels of nn.Conv1d
+    conv1d_ = {
+        "si_hip_conv1d_f32": (i, [C.POINTER(SiConv1dDesc), vp, vp, vp, vp, vp]),
+        "si_hip_conv1d_f16": (i, [C.POINTER(SiConv1dDesc), vp, vp, vp, vp, vp]),
+        "si_hip_conv1d_weight_bytes": (sz, [C.POINTER(SiConv1dDesc), i]),
+        "si_hip_conv1d_pack_weights_f32": (i, [C.POINTER(SiConv1dDesc), vp, vp]),
+        "si_hip_conv1d_pack_weights_f16": (i, [C.POINTER(SiConv1dDesc), vp, vp]),
+        "si_hip_conv1d_kernel_name": (C.c_char_p, [C.POINTER(SiConv1dDesc), vp, vp, i]),
+    }
     for name, (res, args) in (list(sig.items()) + list(norm.items()) + list(pad.items()) + list(pool.items()) + list(softmax.items()) +
                               list(superres.items()) + list(slice_.items()) + list(reduce_.items()) + list(act.items()) + list(permute_.items()) +
                               list(attention_.items()) + list(deform_.items()) + list(grid_.items()) + list(roi_.items()) + list(rnn_.items()) +
-                              list(binary_.items())):
+                              list(binary_.items()) + list(conv1d_.items())):
         fn = getattr(L, name)  # AttributeError here = header/library mismatch, which tests check
         fn.restype = res
         fn.argtypes = args
@@ -458,6 +473,7 @@ def hip():
     L._si_roi_signatures = roi_
     L._si_rnn_signatures = rnn_
     L._si_binary_signatures = binary_
+    L._si_conv1d_signatures = conv1d_
     _hip = L
     return L
 

@@ -112,7 +112,7 @@ enum class BatchFamily {
     kUnknown,       // no row: not per-image
     kInput,         // pnnx.Input
     kOutput,        // pnnx.Output: a slab of the batch is a slab of the buffer only when the batch is dimension 0
-    kSpatial,       // [N, C, H, W] (or [N, F]) in and out, computed image by image: the batch must be dimension 0
+    kSpatial,       // [N, C, H, W] (or [N, C, L], [N, F]) in and out, computed image by image: the batch must be dimension 0
     kElementwise,   // value by value: any batch dimension, the same one in and out
     kRows,          // over the last dimension (nn.Linear): any batch dimension but the last
     kSoftmax,       // along dim
@@ -140,6 +140,7 @@ inline BatchFamily BatchFamilyOf(const std::string& type) {
         {"pnnx.Attribute", BatchFamily::kConstant},
         {"nn.Conv2d", BatchFamily::kSpatial},
         {"nn.ConvTranspose2d", BatchFamily::kSpatial},
+        {"nn.Conv1d", BatchFamily::kSpatial},            // ([N, C, L] in and out, computed item by item: the batch must be dimension 0)
         {"torchvision.ops.DeformConv2d", BatchFamily::kSpatial},   // (offset and mask are per-pixel operands of the same image)
         {"F.grid_sample", BatchFamily::kSpatial},        // (x [N,C,H,W] and the grid [N,Ho,Wo,2] are operands of the same image)
         {"F.affine_grid", BatchFamily::kSpatial},        // (theta [N,2,3] -> grid [N,H,W,2]: the batch is dimension 0 on both sides)

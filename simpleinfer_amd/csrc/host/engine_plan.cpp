@@ -9,6 +9,7 @@
 #include "layer/affine_grid.h"
 #include "layer/binary_op.h"
 #include "layer/cat.h"
+#include "layer/conv_1d.h"
 #include "layer/conv_2d.h"
 #include "layer/conv_transpose_2d.h"
 #include "layer/deform_conv_2d.h"
@@ -236,6 +237,11 @@ Status EngineImpl::FuseEpilogues(std::vector<Step>& order) {
         // deformable conv -> act  ==>  one launch, as for the transposed conv
         if (DeformConv2d* dc = p.At<DeformConv2d>(i, "torchvision.ops.DeformConv2d")) {
             p.FuseActivationInto(i, dc);
+            continue;
+        }
+        // temporal conv -> act  ==>  one launch, as for the transposed conv
+        if (Conv1d* c1 = p.At<Conv1d>(i, "nn.Conv1d")) {
+            p.FuseActivationInto(i, c1);
             continue;
         }
         // group / instance norm -> act  ==>  one launch (or the same two): the activation runs in the normalise pass's epilogue

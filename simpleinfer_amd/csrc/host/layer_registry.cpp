@@ -15,6 +15,7 @@ SI_DECLARE_LAYER(AvgPool2d)
 SI_DECLARE_LAYER(BatchNorm2d)
 SI_DECLARE_LAYER(BinaryOp)
 SI_DECLARE_LAYER(Cat)
+SI_DECLARE_LAYER(Conv1d)
 SI_DECLARE_LAYER(Conv2d)
 SI_DECLARE_LAYER(ConvTranspose2d)
 SI_DECLARE_LAYER(DeformConv2d)
@@ -65,7 +66,8 @@ static std::map<std::string, LayerRegistryEntry>& Table() {
     // (layer/deform_conv_2d.h: DCNv1 / DCNv2 in one launch of include/si_deform.h; the type string is the one pnnx writes for the module);
     // F.grid_sample and F.affine_grid (layer/grid_sample.h, layer/affine_grid.h: the sampler and the tiny grid kernel of include/si_grid.h);
     // torchvision.ops.RoIAlign / torchvision.ops.roi_align (one class, layer/roi_align.h: the box-pooling kernel of include/si_roi.h);
-    // nn.LSTM / nn.GRU (one class with a cell kind, layer/rnn.h: the input projection and the recurrent step kernel of include/si_rnn.h)
+    // nn.LSTM / nn.GRU (one class with a cell kind, layer/rnn.h: the input projection and the recurrent step kernel of include/si_rnn.h);
+    // nn.Conv1d (layer/conv_1d.h: the temporal convolution kernels of include/si_conv1d.h on rank-3 operands in their native layout)
     static std::map<std::string, LayerRegistryEntry> table = {
         SI_ENTRY("nn.AdaptiveAvgPool2d", AdaptiveAvgPool2d),
         SI_ENTRY("nn.AvgPool2d", AvgPool2d),
@@ -148,6 +150,7 @@ static std::map<std::string, LayerRegistryEntry>& Table() {
         SI_ENTRY("torchvision.ops.roi_align", RoiAlign),
         SI_ENTRY("nn.LSTM", Rnn),
         SI_ENTRY("nn.GRU", Rnn),
+        SI_ENTRY("nn.Conv1d", Conv1d),
     };
     return table;
 }

@@ -1463,6 +1463,98 @@ def gru(x, weights, batch_first=False, want_state=False, **views):
     return _rnn("gru", x, weights, batch_first, want_state, views)
 
 
+def conv1d_pads(k, padding, dilation=1, stride=1):
+    """(left, right) zero pads of nn.Conv1d: an int pads both sides; 'valid' none; 'same' (stride 1) d (K - 1) in all, the odd one on the right"""
+    if padding == "valid":
+        return 0, 0
+    if padding == "same":
+        assert int(stride) == 1, "padding='same' needs stride 1"
+        total = int(dilation) * (int(k) - 1)
+        return total // 2, total - total // 2
+    return int(padding), int(padding)
+
+
+def conv1d_out_len(l, k, stride=1, padding=0, dilation=1):
+    pl, pr = conv1d_pads(k, padding, dilation, stride)
+    e = int(l) + pl + pr - int(dilation) * (int(k) - 1) - 1
+    return e // int(stride) + 1 if e >= 0 else 0
+
+
+def conv1d_desc(n, c, l, oc, k, stride=1, padding=0, dilation=1, groups=1, act="none", act_param=0.0, x_sn=None, x_sc=None, y_sn=None, y_sc=None,
+                lo=None):
+    """SiConv1dDesc (include/si_conv1d.h) of x [N, C, L] -> y [N, OC, Lo]; the strides default to dense tensors, lo to torch's formula"""
+    d = _native.SiConv1dDesc()
+    d.n, d.c, d.l, d.oc, d.k, d.stride, d.dilation, d.groups = int(n), int(c), int(l), int(oc), int(k), int(stride), int(dilation), int(groups)
+    d.pad_left = conv1d_pads(k, padding, dilation, stride)[0]
+    d.lo = int(lo) if lo is not None else conv1d_out_len(l, k, stride, padding, dilation)
+    d.x_sc = int(x_sc) if x_sc is not None else d.l
+    d.x_sn = int(x_sn) if x_sn is not None else d.c * d.x_sc
+    d.y_sc = int(y_sc) if y_sc is not None else d.lo
+    d.y_sn = int(y_sn) if y_sn is not None else d.oc * d.y_sc
+    d.act = ACT[act] if isinstance(act, str) else int(act)
+    d.act_param = float(act_param)
+    return d
+
+
+def conv1d_pack_weights(w, groups=1, half=False) -> np.ndarray:
+    """si_hip_conv1d_pack_weights_f32 / _f16: torch's weight fp32 [OC, C / groups, K] -> the kernels' image (floats, or halves)"""
+    H = _native.hip()
+    w = _f32(w)
+    oc, cg, k = w.shape
+    d = conv1d_desc(1, cg * int(groups), 1, oc, k, groups=groups, lo=1)
+    nbytes = H.si_hip_conv1d_weight_bytes(C.byref(d), 1 if half else 0)
+    LAST_ENTRIES.append("si_hip_conv1d_weight_bytes")
+    if nbytes == 0:
+        raise HipError("no %s conv1d kernel for this filter" % ("fp16" if half else "fp32"))
+    image = np.zeros(nbytes // (2 if half else 4), np.float16 if half else np.float32)
+    name = "si_hip_conv1d_pack_weights_f16" if half else "si_hip_conv1d_pack_weights_f32"
+    _chk(getattr(H, name)(C.byref(d), w.ctypes.data_as(C.c_void_p), image.ctypes.data_as(C.c_void_p)), name)
+    return image
+
+
+def conv1d(x, w, b=None, stride=1, padding=0, dilation=1, groups=1, act="none", act_param=0.0, in_c_total=None, in_c_off=0, in_ld=None,
+           in_l_off=0, in_fill=0.0, out_c_total=None, out_c_off=0, out_ld=None, out_l_off=0, out_fill=0.0, full=False):
+    """torch.nn.functional.conv1d (zero padding: an int, 'same' or 'valid') with a fused activation, through si_hip_conv1d_f32 / _f16 (by x's
+    dtype).  x [N, C, L]; w fp32 [OC, C / groups, K]; b fp32 [OC] or None.  The view hooks make x channels [in_c_off, in_c_off + C) and
+    positions [in_l_off, in_l_off + L) of a tensor [N, in_c_total, in_ld] whose other elements hold in_fill, and y the same kind of window of a
+    tensor [N, out_c_total, out_ld] pre-filled with out_fill; full=True returns that whole tensor"""
+    H = _native.hip()
+    x = _float_storage(x)
+    half = x.dtype == np.float16
+    w = _f32(w)
+    n, c, l = x.shape
+    oc, cg, k = w.shape
+    assert cg * int(groups) == c, (x.shape, w.shape, groups)
+    lo = conv1d_out_len(l, k, stride, padding, dilation)
+    ict, ild, oct_, old = int(in_c_total or c), int(in_ld or l), int(out_c_total or oc), int(out_ld or lo)
+    assert 0 <= in_c_off and in_c_off + c <= ict and 0 <= in_l_off and in_l_off + l <= ild
+    assert 0 <= out_c_off and out_c_off + oc <= oct_ and 0 <= out_l_off and out_l_off + lo <= old
+    d = conv1d_desc(n, c, l, oc, k, stride, padding, dilation, groups, act, act_param, x_sn=ict * ild, x_sc=ild, y_sn=oct_ * old, y_sc=old)
+    dimg = DeviceBuffer.from_numpy(conv1d_pack_weights(w, groups, half))
+    xw = x
+    if (ict, ild) != (c, l):
+        xw = _full((n, ict, ild), x.dtype, in_fill)
+        xw[:, in_c_off:in_c_off + c, in_l_off:in_l_off + l] = x
+    dx = DeviceBuffer.from_numpy(xw)
+    px = dx.ptr + x.itemsize * (in_c_off * ild + in_l_off)
+    dy = DeviceBuffer.from_numpy(_full((n, oct_, old), x.dtype, out_fill), out=True)
+    py = dy.ptr + x.itemsize * (out_c_off * old + out_l_off)
+    db = DeviceBuffer.from_numpy(_f32(b)) if b is not None else None
+    LAST_KERNEL_NAME["si_hip_conv1d"] = H.si_hip_conv1d_kernel_name(C.byref(d), C.c_void_p(px), C.c_void_p(py), 1 if half else 0).decode()
+    name = "si_hip_conv1d_f16" if half else "si_hip_conv1d_f32"
+    _chk(getattr(H, name)(C.byref(d), px, dimg.ptr, db.ptr if db else None, py, None), name)
+    y = dy.to_numpy((n, oct_, old), x.dtype)
+    if full:
+        return y
+    return np.ascontiguousarray(y[:, out_c_off:out_c_off + oc, out_l_off:out_l_off + lo])
+
+
+def conv1d_kernel_name(n, c, l, oc, k, stride=1, padding=0, dilation=1, groups=1, half=False) -> str:
+    """the instantiation for dense tensors at aligned addresses; "none": a refused descriptor"""
+    d = conv1d_desc(n, c, l, oc, k, stride, padding, dilation, groups)
+    return _native.hip().si_hip_conv1d_kernel_name(C.byref(d), C.c_void_p(1 << 24), C.c_void_p(1 << 30), 1 if half else 0).decode()
+
+
 REDUCE_OPS = {"sum": 0, "mean": 1, "amax": 2, "amin": 3}
 
 

@@ -159,6 +159,26 @@ class PnnxBuilder:
                         padding_mode="zeros", stride=(sh, sw)), attrs)
         return out
 
+    def conv1d(self, x: str, cout: int, k: int, s: int = 1, p=None, d: int = 1, groups: int = 1, bias: bool = True, padding_mode: str = "zeros",
+               name: str = None) -> str:
+        """pnnx's nn.Conv1d line on a rank-3 operand [N, C, L] (an unbatched [C, L] is written too: the engine refuses it): one-element tuples
+        for kernel_size / stride / dilation; padding an int tuple, or the text `same` / `valid`; weight (Cout, Cin / groups, K).  p=None: K // 2"""
+        *lead, cin, l = self.shapes[x]
+        if p is None:
+            p = (d * (k - 1)) // 2
+        total = d * (k - 1) if p == "same" else 0 if p == "valid" else 2 * int(p)
+        lo = (l + total - d * (k - 1) - 1) // s + 1
+        name = name or self._opname("conv1d")
+        a = math.sqrt(3.0 / ((cin // groups) * k))
+        attrs = {"weight": seeded_uniform(name + ".weight", (cout, cin // groups, k), -a, a, self.seed)}
+        if bias:
+            attrs["bias"] = seeded_uniform(name + ".bias", (cout,), -0.1, 0.1, self.seed)
+        out = self._new_operand(tuple(lead) + (cout, lo))
+        self._emit("nn.Conv1d", name, [x], [out],
+                   dict(bias=bool(bias), dilation=(d,), groups=groups, in_channels=cin, kernel_size=(k,), out_channels=cout,
+                        padding=p if isinstance(p, str) else (int(p),), padding_mode=padding_mode, stride=(s,)), attrs)
+        return out
+
     def conv_transpose(self, x: str, cout: int, k, s=1, p=0, output_padding=0, d=1, bias: bool = True,
                        name: str = None) -> str:
         """pnnx's nn.ConvTranspose2d line; weight [Cin][Cout][kh][kw] (torch's layout), groups 1"""
@@ -1225,6 +1245,31 @@ def build_toy_crnn(batch: int = 2, height: int = 16, width: int = 40, hidden: in
         b.output(b.linear(y[1], ncls))
     else:
         b.output(b.linear(y, ncls))
+    return b
+
+
+def build_toy_quartznet(batch: int = 2, frames: int = 64, feats: int = 16, width: int = 32, ncls: int = 12, seed: int = 0) -> PnnxBuilder:
+    """QuartzNet at toy width on a rank-3 graph input [N, feats, T]: a strided dense stem (K = 11, stride 2) + ReLU; two blocks of depthwise
+    K = 33 -> pointwise -> ReLU with a pointwise residual branch, `+`, ReLU; a dilated K = 3 conv (dilation 2, `same`) + ReLU; a pointwise conv
+    to the classes, per frame [N, ncls, T / 2].  BatchNorm1d is absent as pnnx folds it into the convs at export"""
+    b = PnnxBuilder(seed)
+    x = b.relu(b.conv1d(b.input((batch, feats, frames)), width, 11, 2, 5))
+    for _ in range(2):
+        y = b.relu(b.conv1d(b.conv1d(x, width, 33, 1, 16, groups=width), width, 1, 1, 0))
+        x = b.relu(b.add(y, b.conv1d(x, width, 1, 1, 0)))
+    x = b.relu(b.conv1d(x, width, 3, 1, "same", d=2))
+    b.output(b.conv1d(x, ncls, 1, 1, 0))
+    return b
+
+
+def build_toy_conv_gru(batch: int = 2, frames: int = 50, feats: int = 8, width: int = 16, hidden: int = 16, ncls: int = 9,
+                       seed: int = 0) -> PnnxBuilder:
+    """A DeepSpeech2-style front end at toy width: two strided nn.Conv1d + nn.Hardtanh(0, 20) on [N, feats, T] -> Tensor.permute(2, 0, 1)
+    [T', N, C] -> nn.GRU -> nn.Linear to the classes, per time step"""
+    b = PnnxBuilder(seed)
+    x = b.hardtanh(b.conv1d(b.input((batch, feats, frames)), width, 11, 2, 5), 0.0, 20.0)
+    x = b.hardtanh(b.conv1d(x, width, 5, 2, 2), 0.0, 20.0)
+    b.output(b.linear(b.gru(b.permute(x, (2, 0, 1)), hidden), ncls))
     return b
 
 
