@@ -161,6 +161,15 @@ class SiConv1dDesc(C.Structure):
         (k, C.c_longlong) for k in ("x_sn", "x_sc", "y_sn", "y_sc")] + [("act", C.c_int), ("act_param", C.c_float)]
 
 
+class SiXcorrDesc(C.Structure):
+    """include/si_xcorr.h; NHWC views: sn / sh / sp the element strides of the image (w: the filter; depthwise: the image), the row and the pixel,
+    w_sc that of the filter's channel"""
+    _fields_ = [(k, C.c_int) for k in ("n", "h", "w", "c", "oc", "ho", "wo", "kh", "kw", "stride_h", "stride_w", "dilation_h", "dilation_w",
+                                       "pad_top", "pad_left", "groups")] + [
+        (k, C.c_longlong) for k in ("x_sn", "x_sh", "x_sp", "w_sn", "w_sh", "w_sp", "w_sc", "y_sn", "y_sh", "y_sp")] + [
+        ("per_sample", C.c_int), ("act", C.c_int), ("act_param", C.c_float)]
+
+
 class SiBinaryDesc(C.Structure):
     """include/si_binary.h; d: extents of x / out in storage order, c0_stride / c1_stride: element strides of the constants (0: broadcast)"""
     _fields_ = [("d", C.c_int * 4), ("x_ld", C.c_int), ("out_ld", C.c_int), ("stages", C.c_int), ("op", C.c_int * 2), ("c0_stride", C.c_int * 4),
@@ -450,10 +459,16 @@ def hip():
         "si_hip_conv1d_pack_weights_f16": (i, [C.POINTER(SiConv1dDesc), vp, vp]),
         "si_hip_conv1d_kernel_name": (C.c_char_p, [C.POINTER(SiConv1dDesc), vp, vp, i]),
     }
+    # include/si_xcorr.h: the cross-correlation kernels of F.conv2d with a tensor filter
+    xcorr_ = {
+        "si_hip_xcorr_f32": (i, [C.POINTER(SiXcorrDesc), vp, vp, vp, vp, vp]),
+        "si_hip_xcorr_f16": (i, [C.POINTER(SiXcorrDesc), vp, vp, vp, vp, vp]),
+        "si_hip_xcorr_kernel_name": (C.c_char_p, [C.POINTER(SiXcorrDesc), vp, vp, vp, i]),
+    }
     for name, (res, args) in (list(sig.items()) + list(norm.items()) + list(pad.items()) + list(pool.items()) + list(softmax.items()) +
                               list(superres.items()) + list(slice_.items()) + list(reduce_.items()) + list(act.items()) + list(permute_.items()) +
                               list(attention_.items()) + list(deform_.items()) + list(grid_.items()) + list(roi_.items()) + list(rnn_.items()) +
-                              list(binary_.items()) + list(conv1d_.items())):
+                              list(binary_.items()) + list(conv1d_.items()) + list(xcorr_.items())):
         fn = getattr(L, name)  # AttributeError here = header/library mismatch, which tests check
         fn.restype = res
         fn.argtypes = args
@@ -474,6 +489,7 @@ def hip():
     L._si_rnn_signatures = rnn_
     L._si_binary_signatures = binary_
     L._si_conv1d_signatures = conv1d_
+    L._si_xcorr_signatures = xcorr_
     _hip = L
     return L
 

@@ -126,11 +126,25 @@ enum class BatchFamily {
     kRoi,           // torchvision.ops.RoIAlign / roi_align: boxes [K, 5] that name their image by an index in the data -- never per-image
     kConstant,      // pnnx.Attribute: a tensor of the file, the same for every image -- always per-image
     kRecurrent,     // nn.LSTM / nn.GRU: reads the batch from dimension 0 (batch_first) or 1; y keeps it there, the state outputs carry it in 1
+    kXcorr,         // F.conv2d: kSpatial on x while the filter (and bias) are graph constants; with a filter computed from a graph input never per-image
 };
 
 // why an operator of the family kRoi is never per-image (also the engine's reason for refusing to re-batch a graph that holds one)
 inline const char* RoiBatchReason() {
     return "the boxes name their image by an index in the data: dimension 0 of the output counts boxes, not images";
+}
+
+// why F.conv2d with a filter computed from a graph input is never per-image (also the engine's reason for refusing to re-batch such a graph)
+inline const char* XcorrBatchReason() {
+    return "the filter is computed from a graph input: its dimension 0 counts filters, not images, and every image of x meets every filter";
+}
+
+// F.conv2d (kXcorr) whose filter, or bias, is no graph constant; `constants`: ConstantOperands of the graph
+inline bool HasTensorFilter(const pnnx::Operator* op, const std::set<const pnnx::Operand*>& constants) {
+    if (op->type != "F.conv2d") return false;
+    for (size_t i = 1; i < op->inputs.size(); ++i)
+        if (!constants.count(op->inputs[i])) return true;
+    return op->inputs.size() < 2;
 }
 
 inline BatchFamily BatchFamilyOf(const std::string& type) {
@@ -141,6 +155,7 @@ inline BatchFamily BatchFamilyOf(const std::string& type) {
         {"nn.Conv2d", BatchFamily::kSpatial},
         {"nn.ConvTranspose2d", BatchFamily::kSpatial},
         {"nn.Conv1d", BatchFamily::kSpatial},            // ([N, C, L] in and out, computed item by item: the batch must be dimension 0)
+        {"F.conv2d", BatchFamily::kXcorr},               // (x image by image against a CONSTANT filter; a tensor filter is never per-image)
         {"torchvision.ops.DeformConv2d", BatchFamily::kSpatial},   // (offset and mask are per-pixel operands of the same image)
         {"F.grid_sample", BatchFamily::kSpatial},        // (x [N,C,H,W] and the grid [N,Ho,Wo,2] are operands of the same image)
         {"F.affine_grid", BatchFamily::kSpatial},        // (theta [N,2,3] -> grid [N,H,W,2]: the batch is dimension 0 on both sides)
@@ -249,6 +264,31 @@ inline bool PerImageOperator(const pnnx::Operator* op, const std::vector<BatchOp
         // whatever the shapes say: K == N is a coincidence, and a slab of the boxes still indexes every image
         why = RoiBatchReason();
         return false;
+    }
+    if (family == BatchFamily::kXcorr) {
+        // dimension 0 of the filter [O, C / g, kh, kw] counts filters.  A constant one meets every image (the right-aligned broadcast check
+        // below does not apply to it); one computed from a graph input pairs every image with filters made from every image, whatever the
+        // shapes say -- also the depthwise sandwich, whose views fold the batch into the channels
+        for (size_t i = 1; i < in.size(); ++i)
+            if (!in[i].constant) {
+                why = XcorrBatchReason();
+                return false;
+            }
+        if (in.size() < 2) {
+            why = XcorrBatchReason();
+            return false;
+        }
+        if (in[0].axis < 0) return true;
+        if (in[0].axis != 0) {
+            why = "the operator works image by image over dimension 0, but its input carries the batch in " + dim_text(in[0].axis);
+            return false;
+        }
+        for (size_t i = 0; i < out.size(); ++i)
+            if (out[i].axis != 0) {
+                why = "output " + std::to_string(i) + " does not carry the batch in dimension 0";
+                return false;
+            }
+        return true;
     }
     if (family == BatchFamily::kOutput) {
         for (const BatchOperand& o : in)
@@ -421,8 +461,12 @@ inline std::vector<BatchMixingEntry> FindBatchMixing(const std::vector<pnnx::Ope
     if (file_batch <= 0) {
         // no static batch: such a graph is never split.  The graph inputs of a box head, [N, ...] and [K, 5], disagree whenever K != N: its
         // kRoi operators are listed all the same, so that what the engine logs and refuses does not depend on whether K happens to equal N
-        for (const pnnx::Operator* op : ops)
+        // ... and so are the cross-correlations with a tensor filter: a template of batch 1 beside a search batch of N is such a graph
+        const std::set<const pnnx::Operand*> consts = ConstantOperands(ops);
+        for (const pnnx::Operator* op : ops) {
             if (BatchFamilyOf(op->type) == BatchFamily::kRoi) found.push_back({op->name, op->type, RoiBatchReason()});
+            else if (HasTensorFilter(op, consts)) found.push_back({op->name, op->type, XcorrBatchReason()});
+        }
         return found;
     }
     const std::map<const pnnx::Operand*, int> axes = FollowBatchAxes(ops, file_batch);

@@ -13,6 +13,7 @@
 #include "engine_impl.h"
 #include "layer_registry.h"
 #include "pnnx/expand_expression.h"
+#include "pnnx/lower_functional_conv.h"
 #include "pnnx/ir.h"
 
 using namespace SimpleInfer;
@@ -182,6 +183,7 @@ int si_pnnx_save(const char* param_path, const char* bin_path, int expand, int b
     try {
         if (g.load(param_path, bin_path) != 0) return 1;
         if (expand) pnnx::expand_expression(g);
+        if (expand) pnnx::lower_functional_conv(g);   // (what LoadModel does to the graph: F.conv2d with constant operands is nn.Conv2d)
         if (batch > 0) {
             int traced = 0;
             for (const pnnx::Operand* r : g.operands)

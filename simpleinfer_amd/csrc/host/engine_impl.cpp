@@ -10,6 +10,7 @@
 #include "engine_internal.h"
 #include "layer_registry.h"
 #include "pnnx/expand_expression.h"
+#include "pnnx/lower_functional_conv.h"
 
 namespace SimpleInfer {
 
@@ -150,6 +151,9 @@ Status EngineImpl::CreateGraph(const std::string& parampath, const std::string& 
         return Status::kFail;
     }
     pnnx::expand_expression(*graph_);
+    // F.conv2d whose filter and bias are constants of the file with no other reader is nn.Conv2d written as a function: it becomes that
+    // operator here, before layers exist and before the batch rule looks at the graph
+    pnnx::lower_functional_conv(*graph_);
     return Status::kSuccess;
 }
 
@@ -186,6 +190,14 @@ Status EngineImpl::CreateTensorNodes() {
         for (const pnnx::Operator* op : graph_->ops)
             if (BatchFamilyOf(op->type) == BatchFamily::kRoi) {
                 LOG(ERROR) << "re-batch: [" << op->name << "] (" << op->type << "): " << RoiBatchReason() << ": served at the file's batch only";
+                return Status::kUnsupport;
+            }
+        // a cross-correlation head: the filter of F.conv2d is computed from a graph input, so dimension 0 of it (and, behind the depthwise
+        // sandwich's views, the channels) follows the traced batch in ways the rewrite below does not know.  Not re-batched either
+        const std::set<const pnnx::Operand*> consts = ConstantOperands(graph_->ops);
+        for (const pnnx::Operator* op : graph_->ops)
+            if (HasTensorFilter(op, consts)) {
+                LOG(ERROR) << "re-batch: [" << op->name << "] (" << op->type << "): " << XcorrBatchReason() << ": served at the file's batch only";
                 return Status::kUnsupport;
             }
         for (pnnx::Operand* opd : graph_->operands)

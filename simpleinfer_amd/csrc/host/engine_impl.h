@@ -116,6 +116,7 @@ private:
     Status FuseCv3IntoPairs(std::vector<Step>& order);
     Status FuseBottleneckPairs(std::vector<Step>& order);
     Status FuseConstStages(std::vector<Step>& order);
+    Status FuseCrossCorrelations(std::vector<Step>& order);
     Status InsertOutputCasts(std::vector<Step>& order);
     Status InsertFp32Fallbacks(std::vector<Step>& order);
     Status AliasConcats();

@@ -13,6 +13,7 @@
 #include "layer/conv_2d.h"
 #include "layer/conv_transpose_2d.h"
 #include "layer/deform_conv_2d.h"
+#include "layer/functional_conv_2d.h"
 #include "layer/grid_sample.h"
 #include "layer/group_norm.h"
 #include "layer/layout.h"
@@ -83,6 +84,7 @@ Status EngineImpl::CreatePipeline() {
         CHECK_STATUS(FuseEpilogues(order));
         CHECK_STATUS(FuseSiblingConvs(order));
         CHECK_STATUS(FusePoolChains(order));
+        if (opt_.fuse_xcorr) CHECK_STATUS(FuseCrossCorrelations(order));   // (before the chains are composed: the views around the call are still single steps)
         if (opt_.fuse_layout) CHECK_STATUS(FuseLayoutChains(order));
         if (opt_.fuse_layout && opt_.fuse_grid) CHECK_STATUS(FuseGridInPlace(order));   // (after the chains are composed: the run in front of a sampler is one step)
         if (opt_.fuse_grid) CHECK_STATUS(FuseAffineGrids(order));
@@ -242,6 +244,11 @@ Status EngineImpl::FuseEpilogues(std::vector<Step>& order) {
         // temporal conv -> act  ==>  one launch, as for the transposed conv
         if (Conv1d* c1 = p.At<Conv1d>(i, "nn.Conv1d")) {
             p.FuseActivationInto(i, c1);
+            continue;
+        }
+        // F.conv2d with a tensor filter -> act  ==>  one launch, as for the transposed conv
+        if (FunctionalConv2d* fc = p.At<FunctionalConv2d>(i, "F.conv2d")) {
+            p.FuseActivationInto(i, fc);
             continue;
         }
         // group / instance norm -> act  ==>  one launch (or the same two): the activation runs in the normalise pass's epilogue
@@ -413,6 +420,51 @@ Status EngineImpl::FuseLayoutChains(std::vector<Step>& order) {
         Layout* last = dynamic_cast<Layout*>(order[run.back()].layer);
         if (!last->TryChain(head->InputNodes()[0], ops)) continue;
         for (size_t k = 0; k + 1 < run.size(); ++k) p.Retire(run[k], order[run[k]].op->outputs[0]);
+    }
+    p.Compact();
+    return Status::kSuccess;
+}
+
+// x.view(1, N C, H, W), z.view(N C, 1, kh, kw) -> F.conv2d(groups = N C) -> .view(N, C, Ho, Wo)  ==>  ONE launch of the depthwise kernel in
+// its per-sample addressing (include/si_xcorr.h) on x and z themselves: the depthwise cross-correlation of SiamRPN++, SiamMask, SiamBAN and
+// Ocean.  In NHWC storage each of the three views is a transpose launch for N > 1 (the batch is folded into the contiguous axis); the kernel
+// instead takes the filter of image n from image n of z, [N][kh][kw][C] as it lies, and writes [N][Ho][Wo][C].  The arithmetic per output
+// element is that of the unfused addressing, tap by tap, so the bits are those of fuse_xcorr = 0.  Conditions: each view is a single
+// Tensor.view / Tensor.reshape step, every intermediate has one reader and is no graph output, and the shapes are exactly the pattern's
+// (FunctionalConv2d::SetPerSample checks them).  The three layout steps are retired, the operands between them are dead.
+Status EngineImpl::FuseCrossCorrelations(std::vector<Step>& order) {
+    Pass p(*this, order);
+    auto view_step = [&](const pnnx::Operator* op) -> Layout* {
+        if (!op || (op->type != "Tensor.view" && op->type != "Tensor.reshape") || op->inputs.size() != 1 || op->outputs.size() != 1) return nullptr;
+        auto at = p.index.find(op);
+        return at == p.index.end() ? nullptr : p.At<Layout>(at->second);
+    };
+    for (size_t i = 0; i < order.size(); ++i) {
+        FunctionalConv2d* fc = p.At<FunctionalConv2d>(i, "F.conv2d");
+        const pnnx::Operator* op = order[i].op;
+        if (!fc || fc->PerSample() || op->inputs.size() < 2 || op->outputs.size() != 1 || fc->InputNodes().size() != op->inputs.size()) continue;
+        const pnnx::Operand* xv = op->inputs[0];
+        const pnnx::Operand* zv = op->inputs[1];
+        const pnnx::Operand* yv = op->outputs[0];
+        if (!xv || !zv || xv == zv || p.SoleConsumer(xv) != op || p.SoleConsumer(zv) != op) continue;
+        if (fc->InputNodes()[0] != tensor_nodes_[xv->name] || fc->InputNodes()[1] != tensor_nodes_[zv->name]) continue;
+        if (fc->OutputNodes().size() != 1 || fc->OutputNodes()[0] != tensor_nodes_[yv->name]) continue;   // (an absorbed activation: not the pattern)
+        const pnnx::Operator* back = p.SoleConsumer(yv);
+        Layout* lx = view_step(xv->producer);
+        Layout* lz = view_step(zv->producer);
+        Layout* ly = view_step(back);
+        if (!lx || !lz || !ly) continue;
+        TensorNode* x = lx->InputNodes().size() == 1 ? lx->InputNodes()[0] : nullptr;
+        TensorNode* z = lz->InputNodes().size() == 1 ? lz->InputNodes()[0] : nullptr;
+        TensorNode* out = ly->OutputNodes().size() == 1 ? ly->OutputNodes()[0] : nullptr;
+        if (!x || !z || !out || x == z) continue;
+        if (x->tensor.GetDataType() != z->tensor.GetDataType() || x->tensor.GetDataType() != out->tensor.GetDataType()) continue;
+        if (!fc->SetPerSample(x, z, out)) continue;
+        p.Retire(p.index[xv->producer], xv);
+        p.Retire(p.index[zv->producer], zv);
+        // (the launch keeps the conv's slot: x and z are ready before their views were, and nothing between the conv and the view behind it
+        // reads or writes `out`)
+        p.Retire(p.index[back], yv);
     }
     p.Compact();
     return Status::kSuccess;

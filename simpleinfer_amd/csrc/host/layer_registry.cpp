@@ -20,6 +20,7 @@ SI_DECLARE_LAYER(Conv2d)
 SI_DECLARE_LAYER(ConvTranspose2d)
 SI_DECLARE_LAYER(DeformConv2d)
 SI_DECLARE_LAYER(Flatten)
+SI_DECLARE_LAYER(FunctionalConv2d)
 SI_DECLARE_LAYER(GridSample)
 SI_DECLARE_LAYER(GroupNorm)
 SI_DECLARE_LAYER(HardSigmoid)
@@ -67,7 +68,8 @@ static std::map<std::string, LayerRegistryEntry>& Table() {
     // F.grid_sample and F.affine_grid (layer/grid_sample.h, layer/affine_grid.h: the sampler and the tiny grid kernel of include/si_grid.h);
     // torchvision.ops.RoIAlign / torchvision.ops.roi_align (one class, layer/roi_align.h: the box-pooling kernel of include/si_roi.h);
     // nn.LSTM / nn.GRU (one class with a cell kind, layer/rnn.h: the input projection and the recurrent step kernel of include/si_rnn.h);
-    // nn.Conv1d (layer/conv_1d.h: the temporal convolution kernels of include/si_conv1d.h on rank-3 operands in their native layout)
+    // nn.Conv1d (layer/conv_1d.h: the temporal convolution kernels of include/si_conv1d.h on rank-3 operands in their native layout);
+    // F.conv2d (layer/functional_conv_2d.h: the filter is an operand, read as stored by the cross-correlation kernels of include/si_xcorr.h)
     static std::map<std::string, LayerRegistryEntry> table = {
         SI_ENTRY("nn.AdaptiveAvgPool2d", AdaptiveAvgPool2d),
         SI_ENTRY("nn.AvgPool2d", AvgPool2d),
@@ -151,6 +153,7 @@ static std::map<std::string, LayerRegistryEntry>& Table() {
         SI_ENTRY("nn.LSTM", Rnn),
         SI_ENTRY("nn.GRU", Rnn),
         SI_ENTRY("nn.Conv1d", Conv1d),
+        SI_ENTRY("F.conv2d", FunctionalConv2d),
     };
     return table;
 }

@@ -1555,6 +1555,117 @@ def conv1d_kernel_name(n, c, l, oc, k, stride=1, padding=0, dilation=1, groups=1
     return _native.hip().si_hip_conv1d_kernel_name(C.byref(d), C.c_void_p(1 << 24), C.c_void_p(1 << 30), 1 if half else 0).decode()
 
 
+def xcorr_pads(kh, kw, padding, dilation=1, stride=1):
+    """((top, bottom), (left, right)) zero pads of F.conv2d: an int or a pair pads both sides; 'valid' none; 'same' (stride 1) d (K - 1) per
+    axis, the odd one on the far side"""
+    (dh, dw), (sh, sw) = _pair(dilation), _pair(stride)
+    if isinstance(padding, str):
+        if padding == "valid":
+            return (0, 0), (0, 0)
+        assert padding == "same" and sh == 1 and sw == 1, "padding='same' needs stride 1"
+        th, tw = dh * (int(kh) - 1), dw * (int(kw) - 1)
+        return (th // 2, th - th // 2), (tw // 2, tw - tw // 2)
+    ph, pw = _pair(padding)
+    return (ph, ph), (pw, pw)
+
+
+def xcorr_out_hw(h, w, kh, kw, stride=1, padding=0, dilation=1):
+    (pt, pb), (pl, pr) = xcorr_pads(kh, kw, padding, dilation, stride)
+    (sh, sw), (dh, dw) = _pair(stride), _pair(dilation)
+    eh, ew = int(h) + pt + pb - dh * (int(kh) - 1) - 1, int(w) + pl + pr - dw * (int(kw) - 1) - 1
+    return (eh // sh + 1 if eh >= 0 else 0), (ew // sw + 1 if ew >= 0 else 0)
+
+
+def xcorr_desc(n, h, w, c, oc, kh, kw, stride=1, padding=0, dilation=1, groups=1, act="none", act_param=0.0, per_sample=False, ho=None, wo=None,
+               **strides):
+    """SiXcorrDesc (include/si_xcorr.h) of x [N, H, W, C] * w -> y [N, Ho, Wo, OC].  The strides default to dense NHWC tensors with the filter
+    as stored: dense [OC][kh][kw][C]; depthwise [C][kh][kw][1] (the unfused addressing) or, per_sample, [N][kh][kw][C]"""
+    d = _native.SiXcorrDesc()
+    d.n, d.h, d.w, d.c, d.oc, d.kh, d.kw, d.groups = int(n), int(h), int(w), int(c), int(oc), int(kh), int(kw), int(groups)
+    (d.stride_h, d.stride_w), (d.dilation_h, d.dilation_w) = _pair(stride), _pair(dilation)
+    (d.pad_top, _), (d.pad_left, _) = xcorr_pads(kh, kw, padding, dilation, stride)
+    oh, ow = xcorr_out_hw(h, w, kh, kw, stride, padding, dilation)
+    d.ho, d.wo = int(ho) if ho is not None else oh, int(wo) if wo is not None else ow
+    d.x_sp, d.x_sh, d.x_sn = d.c, d.w * d.c, d.h * d.w * d.c
+    d.y_sp, d.y_sh, d.y_sn = d.oc, d.wo * d.oc, d.ho * d.wo * d.oc
+    if per_sample or (int(groups) == 1 and not d.c == d.oc == 1):
+        d.w_sc, d.w_sp, d.w_sh, d.w_sn = 1, d.c, d.kw * d.c, d.kh * d.kw * d.c
+    else:
+        d.w_sc, d.w_sp, d.w_sh, d.w_sn = d.kh * d.kw, 1, d.kw, 0
+    for k, v in strides.items():
+        assert k in ("x_sn", "x_sh", "x_sp", "w_sn", "w_sh", "w_sp", "w_sc", "y_sn", "y_sh", "y_sp"), k
+        setattr(d, k, int(v))
+    d.per_sample = 1 if per_sample else 0
+    d.act = ACT[act] if isinstance(act, str) else int(act)
+    d.act_param = float(act_param)
+    return d
+
+
+def _window(a, c_total, c_off, w_total, w_off, fill):
+    """`a` [.., W, C] as the window [.., w_off : w_off + W, c_off : c_off + C] of a tensor [.., w_total, c_total] filled with `fill`:
+    (the wide array, the element offset of the window's first element, the pixel stride, the row stride)"""
+    wd, c = a.shape[-2], a.shape[-1]
+    ct, wt = int(c_total or c), int(w_total or wd)
+    assert 0 <= c_off and c_off + c <= ct and 0 <= w_off and w_off + wd <= wt
+    wide = a
+    if (ct, wt) != (c, wd):
+        wide = _full(a.shape[:-2] + (wt, ct), a.dtype, fill)
+        wide[..., w_off:w_off + wd, c_off:c_off + c] = a
+    return wide, w_off * ct + c_off, ct, wt * ct
+
+
+def xcorr(x, w, b=None, stride=1, padding=0, dilation=1, groups=1, act="none", act_param=0.0, per_sample=False,
+          in_c_total=None, in_c_off=0, in_w_total=None, in_w_off=0, in_fill=0.0,
+          w_c_total=None, w_c_off=0, w_w_total=None, w_w_off=0, w_fill=0.0,
+          out_c_total=None, out_c_off=0, out_w_total=None, out_w_off=0, out_fill=0.0, full=False):
+    """F.conv2d with a TENSOR filter and a fused activation through si_hip_xcorr_f32 / _f16 (by x's dtype).  NHWC arrays, the filter as the
+    engine stores it: x [N, H, W, C]; w [OC, kh, kw, C] (groups == 1), [C, kh, kw, 1] (groups == C == OC) or, per_sample, [N, kh, kw, C]
+    (filter n meets image n: the fused depthwise cross-correlation); b fp32 [OC] or None.  The view hooks make x, w and y windows
+    [.., w_off : w_off + W, c_off : c_off + C] of tensors [.., w_total, c_total] whose other elements hold the fill (y: pre-filled with
+    out_fill); full=True returns that whole tensor"""
+    H = _native.hip()
+    x = _float_storage(x)
+    half = x.dtype == np.float16
+    w = np.ascontiguousarray(w, dtype=x.dtype)
+    n, h, wd, c = x.shape
+    depthwise = per_sample or (int(groups) == c and w.shape[0] == c)
+    if per_sample:
+        assert w.shape[0] == n and w.shape[3] == c, (x.shape, w.shape)
+        oc, groups = c, c
+    else:
+        oc = w.shape[0]
+        assert w.shape[3] * int(groups) == c, (x.shape, w.shape, groups)
+    kh, kw = w.shape[1], w.shape[2]
+    ho, wo = xcorr_out_hw(h, wd, kh, kw, stride, padding, dilation)
+    xw, x_off, x_sp, x_sh = _window(x, in_c_total, in_c_off, in_w_total, in_w_off, in_fill)
+    ww, w_off, w_sp, w_sh = _window(w, w_c_total, w_c_off, w_w_total, w_w_off, w_fill)
+    yw, y_off, y_sp, y_sh = _window(np.zeros((n, ho, wo, oc), x.dtype), out_c_total, out_c_off, out_w_total, out_w_off, 0.0)
+    yw = _full(yw.shape, x.dtype, out_fill)
+    if depthwise and not per_sample:
+        wst = dict(w_sn=0, w_sc=kh * w_sh, w_sh=w_sh, w_sp=w_sp)      # a channel's filter is one "image" of the stored [C][kh][kw][1]
+    else:
+        wst = dict(w_sn=kh * w_sh, w_sc=1, w_sh=w_sh, w_sp=w_sp)
+    d = xcorr_desc(n, h, wd, c, oc, kh, kw, stride, padding, dilation, groups, act, act_param, per_sample,
+                   x_sn=h * x_sh, x_sh=x_sh, x_sp=x_sp, y_sn=ho * y_sh, y_sh=y_sh, y_sp=y_sp, **wst)
+    dx, dw = DeviceBuffer.from_numpy(xw), DeviceBuffer.from_numpy(ww)
+    dy = DeviceBuffer.from_numpy(yw, out=True)
+    db = DeviceBuffer.from_numpy(_f32(b)) if b is not None else None
+    px, pw, py = dx.ptr + x.itemsize * x_off, dw.ptr + x.itemsize * w_off, dy.ptr + x.itemsize * y_off
+    LAST_KERNEL_NAME["si_hip_xcorr"] = H.si_hip_xcorr_kernel_name(C.byref(d), C.c_void_p(px), C.c_void_p(pw), C.c_void_p(py), 1 if half else 0).decode()
+    name = "si_hip_xcorr_f16" if half else "si_hip_xcorr_f32"
+    _chk(getattr(H, name)(C.byref(d), px, pw, db.ptr if db else None, py, None), name)
+    y = dy.to_numpy(yw.shape, x.dtype)
+    if full:
+        return y
+    return np.ascontiguousarray(y[:, :, out_w_off:out_w_off + wo, out_c_off:out_c_off + oc])
+
+
+def xcorr_kernel_name(n, h, w, c, oc, kh, kw, stride=1, padding=0, dilation=1, groups=1, half=False, per_sample=False) -> str:
+    """the instantiation for dense tensors at aligned addresses; "none": a refused descriptor"""
+    d = xcorr_desc(n, h, w, c, oc, kh, kw, stride, padding, dilation, groups, per_sample=per_sample)
+    return _native.hip().si_hip_xcorr_kernel_name(C.byref(d), C.c_void_p(1 << 24), C.c_void_p(1 << 28), C.c_void_p(1 << 30), 1 if half else 0).decode()
+
+
 REDUCE_OPS = {"sum": 0, "mean": 1, "amax": 2, "amin": 3}
 
 

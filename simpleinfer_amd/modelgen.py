@@ -179,6 +179,30 @@ class PnnxBuilder:
                         padding=p if isinstance(p, str) else (int(p),), padding_mode=padding_mode, stride=(s,)), attrs)
         return out
 
+    def conv2d_functional(self, x: str, w: str, bias: str = None, stride=1, padding=0, dilation=1, groups: int = 1) -> str:
+        """F.conv2d as pnnx writes the function, the filter an OPERAND: `F.conv2d name 2 1 x w out bias=None stride=(..) padding=(..) dilation=(..)
+        groups=G`, or three inputs x w b and no bias= key; padding an int pair or the bare text `same` / `valid`.  x [N, C, H, W],
+        w [O, C / groups, kh, kw] (an activation or an attribute()), bias [O]"""
+        n, c, h, wd = self.shapes[x]
+        oc, cg, kh, kw = self.shapes[w]
+        assert cg * groups == c and oc % groups == 0, (self.shapes[x], self.shapes[w], groups)
+        sh, sw = (stride, stride) if isinstance(stride, int) else stride
+        dh, dw = (dilation, dilation) if isinstance(dilation, int) else dilation
+        if padding == "same":
+            th, tw = dh * (kh - 1), dw * (kw - 1)
+        elif padding == "valid":
+            th = tw = 0
+        else:
+            ph, pw = (padding, padding) if isinstance(padding, int) else padding
+            th, tw = 2 * ph, 2 * pw
+        oh = (h + th - dh * (kh - 1) - 1) // sh + 1
+        ow = (wd + tw - dw * (kw - 1) - 1) // sw + 1
+        out = self._new_operand((n, oc, oh, ow))
+        params = {} if bias is not None else {"bias": "None"}
+        params.update(stride=(sh, sw), padding=padding if isinstance(padding, str) else (ph, pw), dilation=(dh, dw), groups=int(groups))
+        self._emit("F.conv2d", self._opname("F_conv2d"), [x, w] + ([bias] if bias is not None else []), [out], params)
+        return out
+
     def conv_transpose(self, x: str, cout: int, k, s=1, p=0, output_padding=0, d=1, bias: bool = True,
                        name: str = None) -> str:
         """pnnx's nn.ConvTranspose2d line; weight [Cin][Cout][kh][kw] (torch's layout), groups 1"""
@@ -1270,6 +1294,70 @@ def build_toy_conv_gru(batch: int = 2, frames: int = 50, feats: int = 8, width: 
     x = b.hardtanh(b.conv1d(b.input((batch, feats, frames)), width, 11, 2, 5), 0.0, 20.0)
     x = b.hardtanh(b.conv1d(x, width, 5, 2, 2), 0.0, 20.0)
     b.output(b.linear(b.gru(b.permute(x, (2, 0, 1)), hidden), ncls))
+    return b
+
+
+def build_toy_siamfc(batch: int = 1, seed: int = 0) -> PnnxBuilder:
+    """SiamFC at toy width: two graph inputs, the template z [1, 3, 17, 17] and the search image x [N, 3, 33, 33], each through a stack of two
+    valid 3x3 convs (3 -> 8 + ReLU, 8 -> 16; the two stacks have weights of their own: pnnx writes a shared module once per call all the same);
+    the response map is F.conv2d(search features [N, 16, 29, 29], template features [1, 16, 13, 13]) -> [N, 1, 17, 17]: the dense form, O = 1"""
+    b = PnnxBuilder(seed)
+    z, x = b.input((1, 3, 17, 17)), b.input((batch, 3, 33, 33))
+    fz = b.conv(b.relu(b.conv(z, 8, 3, 1, 0)), 16, 3, 1, 0)
+    fx = b.conv(b.relu(b.conv(x, 8, 3, 1, 0)), 16, 3, 1, 0)
+    b.output(b.conv2d_functional(fx, fz))
+    return b
+
+
+def build_toy_siamrpn(k: int = 5, batch: int = 1, seed: int = 0) -> PnnxBuilder:
+    """SiamRPN's up-channel classification branch at toy width: the template z [1, 3, 12, 12] -> conv 3 -> 8 + ReLU -> conv 8 -> 2k * 8, 7x7
+    valid -> [1, 2k * 8, 4, 4] -> Tensor.view to 2k filters [2k, 8, 4, 4]; the search image x [N, 3, 20, 20] -> two convs -> [N, 8, 16, 16];
+    F.conv2d(x features, filters) -> [N, 2k, 13, 13] -> ReLU (the launch's epilogue)"""
+    b = PnnxBuilder(seed)
+    z, x = b.input((1, 3, 12, 12)), b.input((batch, 3, 20, 20))
+    fz = b.conv(b.relu(b.conv(z, 8, 3, 1, 0)), 2 * k * 8, 7, 1, 0)
+    fx = b.conv(b.relu(b.conv(x, 8, 3, 1, 0)), 8, 3, 1, 0)
+    b.output(b.relu(b.conv2d_functional(fx, b.view(fz, (2 * k, 8, 4, 4)))))
+    return b
+
+
+def build_toy_siamrpnpp(batch: int = 1, c: int = 8, seed: int = 0) -> PnnxBuilder:
+    """SiamRPN++'s depthwise cross-correlation at toy width: z [N, 3, 11, 11] and x [N, 3, 19, 19] through two valid 3x3 convs each ->
+    [N, c, 7, 7] and [N, c, 15, 15]; the sandwich x.view(1, N c, 15, 15), z.view(N c, 1, 7, 7), F.conv2d(groups = N c), .view(N, c, 9, 9);
+    a 1x1 head c -> 4 behind it"""
+    b = PnnxBuilder(seed)
+    z, x = b.input((batch, 3, 11, 11)), b.input((batch, 3, 19, 19))
+    fz = b.conv(b.relu(b.conv(z, c, 3, 1, 0)), c, 3, 1, 0)
+    fx = b.conv(b.relu(b.conv(x, c, 3, 1, 0)), c, 3, 1, 0)
+    y = b.conv2d_functional(b.view(fx, (1, batch * c, 15, 15)), b.view(fz, (batch * c, 1, 7, 7)), groups=batch * c)
+    b.output(b.conv(b.view(y, (batch, c, 9, 9)), 4, 1, 1, 0))
+    return b
+
+
+def build_toy_dynamic_head(batch: int = 1, constant: bool = False, seed: int = 0) -> PnnxBuilder:
+    """SOLOv2 / CondInst at toy width: the mask feature x [N, 3, 16, 16] -> conv 3 -> 8 + ReLU; the kernel branch pools it to [1, 8, 1, 1] and a
+    1x1 conv predicts 4 * 8 values, viewed as four 1x1 kernels [4, 8, 1, 1] (batch 1: a kernel set belongs to one image);
+    F.conv2d(feature, kernels) -> [N, 4, 16, 16] -> Sigmoid.  constant=True: the kernels are a constant of the file behind the same view --
+    filters DERIVED from a constant, which the batch modes may cut"""
+    b = PnnxBuilder(seed)
+    assert constant or batch == 1
+    f = b.relu(b.conv(b.input((batch, 3, 16, 16)), 8, 3, 1, 1))
+    if constant:
+        k = b.attribute(seeded_uniform("dynamic_head.kernels", (1, 32, 1, 1), -0.5, 0.5, seed))
+    else:
+        k = b.conv(b.adaptive_avgpool(f, (1, 1)), 32, 1, 1, 0)
+    b.output(b.sigmoid(b.conv2d_functional(f, b.view(k, (4, 8, 1, 1)))))
+    return b
+
+
+def build_toy_blurpool(batch: int = 2, c: int = 8, seed: int = 0) -> PnnxBuilder:
+    """Anti-aliased downsampling (timm's BlurPool2d): conv 3 -> c + ReLU, then F.conv2d(x, buffer, stride=2, padding=1, groups=c) with the
+    binomial 3x3 filter [c, 1, 3, 3] / 16 kept as a constant of the file, then a 1x1 head.  The engine lowers the function to nn.Conv2d"""
+    b = PnnxBuilder(seed)
+    x = b.relu(b.conv(b.input((batch, 3, 16, 16)), c, 3, 1, 1))
+    a = np.array([1.0, 2.0, 1.0], np.float32)
+    blur = np.broadcast_to((a[:, None] * a[None, :] / 16.0)[None, None], (c, 1, 3, 3))
+    b.output(b.conv(b.conv2d_functional(x, b.attribute(blur), stride=2, padding=1, groups=c), 4, 1, 1, 0))
     return b
 
 
