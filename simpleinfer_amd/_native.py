@@ -170,6 +170,24 @@ class SiXcorrDesc(C.Structure):
         ("per_sample", C.c_int), ("act", C.c_int), ("act_param", C.c_float)]
 
 
+class SiDetectPostDesc(C.Structure):
+    """include/si_detect.h; ne = 4 + objectness + classes + extra, ld / image_ld the element strides of a row (ROWS) or a channel (CHANNELS) and
+    of an image"""
+    _fields_ = [(k, C.c_int) for k in ("n", "rows", "classes", "objectness", "extra", "layout", "ld")] + [("image_ld", C.c_longlong),
+                ("box_format", C.c_int), ("prob_threshold", C.c_float), ("nms_threshold", C.c_float), ("agnostic", C.c_int), ("max_det", C.c_int)]
+
+
+class SiDetectPostOut(C.Structure):
+    """include/si_detect.h; device pointers: dets and counts, and the three optional outputs (NULL: not wanted)"""
+    _fields_ = [(k, C.c_void_p) for k in ("dets", "counts", "src_rows", "net_boxes", "extras")]
+
+
+class SiDetectMaskDesc(C.Structure):
+    """include/si_detect.h; prototypes [n][mh][mw][nm] with pixels proto_ld apart, the coefficients at extras[b][d][coef_off .. coef_off + nm)"""
+    _fields_ = [(k, C.c_int) for k in ("n", "mh", "mw", "nm", "proto_ld", "max_det", "extra", "coef_off")] + [
+        ("ratio_w", C.c_float), ("ratio_h", C.c_float)]
+
+
 class SiBinaryDesc(C.Structure):
     """include/si_binary.h; d: extents of x / out in storage order, c0_stride / c1_stride: element strides of the constants (0: broadcast)"""
     _fields_ = [("d", C.c_int * 4), ("x_ld", C.c_int), ("out_ld", C.c_int), ("stages", C.c_int), ("op", C.c_int * 2), ("c0_stride", C.c_int * 4),
@@ -465,10 +483,18 @@ def hip():
         "si_hip_xcorr_f16": (i, [C.POINTER(SiXcorrDesc), vp, vp, vp, vp, vp]),
         "si_hip_xcorr_kernel_name": (C.c_char_p, [C.POINTER(SiXcorrDesc), vp, vp, vp, i]),
     }
+    # include/si_detect.h: detection post-processing for anchor-free heads, payloads and instance masks
+    detect_ = {
+        "si_hip_detect_postprocess_workspace_bytes": (sz, [C.POINTER(SiDetectPostDesc)]),
+        "si_hip_detect_postprocess_f32": (i, [C.POINTER(SiDetectPostDesc), vp, vp, C.POINTER(SiDetectPostOut), vp, sz, vp]),
+        "si_hip_detect_filter_kernel_name": (C.c_char_p, [C.POINTER(SiDetectPostDesc), vp]),
+        "si_hip_detect_masks_f32": (i, [C.POINTER(SiDetectMaskDesc), vp, vp, vp, vp, vp, vp]),
+        "si_hip_detect_masks_kernel_name": (C.c_char_p, [C.POINTER(SiDetectMaskDesc), vp]),
+    }
     for name, (res, args) in (list(sig.items()) + list(norm.items()) + list(pad.items()) + list(pool.items()) + list(softmax.items()) +
                               list(superres.items()) + list(slice_.items()) + list(reduce_.items()) + list(act.items()) + list(permute_.items()) +
                               list(attention_.items()) + list(deform_.items()) + list(grid_.items()) + list(roi_.items()) + list(rnn_.items()) +
-                              list(binary_.items()) + list(conv1d_.items()) + list(xcorr_.items())):
+                              list(binary_.items()) + list(conv1d_.items()) + list(xcorr_.items()) + list(detect_.items())):
         fn = getattr(L, name)  # AttributeError here = header/library mismatch, which tests check
         fn.restype = res
         fn.argtypes = args
@@ -490,6 +516,7 @@ def hip():
     L._si_binary_signatures = binary_
     L._si_conv1d_signatures = conv1d_
     L._si_xcorr_signatures = xcorr_
+    L._si_detect_signatures = detect_
     _hip = L
     return L
 

@@ -6,7 +6,9 @@
 // Everything here is compare / index work plus a handful of fp32 operations whose results must equal the reference's
 // bit for bit (the picks depend on them), so floating-point contraction is switched off for this file.
 #include "si_hip.h"
+#include "si_detect.h"
 #include "si_hip_internal.h"
+#include "detect_plan.h"
 
 #pragma clang fp contract(off)
 
@@ -123,12 +125,10 @@ __global__ void resize_letterbox_batch_kernel(const unsigned char* __restrict__ 
 }
 
 // ---- post-processing workspace ----------------------------------------------------------------
-// per image, cap = rows candidates, nbins = classes + 1 (bin = label + 1; label -1 = "no class"):
-//   count[n] | bin_count[n][nbins] | keep[n][cap]            (zeroed at the start of every call, one memset)
-//   key[n][cap] u64 | box, label [n][cap]                    candidates in arrival order
-//   sbox, slabel, sprob [n][cap]                             sorted by confidence (the reference's order)
-//   gbox[n][cap] float4, grank[n][cap]                       sorted by (label, confidence): one segment per label
-//   pbox, plabel, parea [n][cap]                             boxes picked so far (network coordinates)
+// The regions, their order and their sizes: detect_plan.h (Layout).  srow / drow exist in the general entry's layout alone and are
+// null for si_hip_yolo_postprocess_f32, whose byte count is what it always was.
+namespace plan = si_detect_plan;
+
 struct PostWs {
     int* count;
     int* bin_count;
@@ -146,36 +146,40 @@ struct PostWs {
     float4* pbox;
     int* plabel;
     float* parea;
+    int* srow;   // prediction row of each candidate in the confidence order
+    int* drow;   // prediction row of each stored detection: what the payload gather reads
 };
 
-__host__ __device__ inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-inline size_t post_ws_layout(int n, int cap, int nbins, char* base, PostWs* ws) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char* p = base ? base + off : nullptr;
-        off += align256(bytes);
-        return p;
-    };
-    const size_t nc = (size_t)n * cap;
-    char* p;
-    p = take(sizeof(int) * n);                     if (ws) ws->count = (int*)p;
-    p = take(sizeof(int) * (size_t)n * nbins);     if (ws) ws->bin_count = (int*)p;
-    p = take(sizeof(int) * nc);                    if (ws) ws->keep = (int*)p;
-    if (ws) { ws->zero_bytes = off; ws->nbins = nbins; }
-    p = take(sizeof(float4) * nc);                 if (ws) ws->gbox = (float4*)p;
-    p = take(sizeof(int) * nc);                    if (ws) ws->grank = (int*)p;
-    p = take(sizeof(unsigned long long) * nc);     if (ws) ws->key = (unsigned long long*)p;
-    p = take(sizeof(float4) * nc);                 if (ws) ws->box = (float4*)p;
-    p = take(sizeof(int) * nc);                    if (ws) ws->label = (int*)p;
-    p = take(sizeof(float4) * nc);                 if (ws) ws->sbox = (float4*)p;
-    p = take(sizeof(int) * nc);                    if (ws) ws->slabel = (int*)p;
-    p = take(sizeof(float) * nc);                  if (ws) ws->sprob = (float*)p;
-    p = take(sizeof(float4) * nc);                 if (ws) ws->pbox = (float4*)p;
-    p = take(sizeof(int) * nc);                    if (ws) ws->plabel = (int*)p;
-    p = take(sizeof(float) * nc);                  if (ws) ws->parea = (float*)p;
-    return off;
+inline size_t post_ws_bind(int n, int cap, int nbins, bool general, char* base, PostWs* ws) {
+    const plan::Workspace w = plan::Layout(n, cap, nbins, general);
+    auto at = [&](int r) { return w.bytes[r] ? base + w.offset[r] : nullptr; };
+    ws->count = (int*)at(plan::kCount);
+    ws->bin_count = (int*)at(plan::kBinCount);
+    ws->keep = (int*)at(plan::kKeep);
+    ws->nbins = nbins;
+    ws->zero_bytes = w.zero_bytes;
+    ws->gbox = (float4*)at(plan::kGbox);
+    ws->grank = (int*)at(plan::kGrank);
+    ws->key = (unsigned long long*)at(plan::kKey);
+    ws->box = (float4*)at(plan::kBox);
+    ws->label = (int*)at(plan::kLabel);
+    ws->sbox = (float4*)at(plan::kSbox);
+    ws->slabel = (int*)at(plan::kSlabel);
+    ws->sprob = (float*)at(plan::kSprob);
+    ws->pbox = (float4*)at(plan::kPbox);
+    ws->plabel = (int*)at(plan::kPlabel);
+    ws->parea = (float*)at(plan::kParea);
+    ws->srow = (int*)at(plan::kSrow);
+    ws->drow = (int*)at(plan::kDrow);
+    return w.total;
 }
+
+// what the general entry adds to the NMS / compaction kernels' outputs: each pointer may be null (all are for si_hip_yolo_postprocess_f32)
+struct PostMore {
+    int* drow;          // [n][rows]: row of each stored detection, for the payload gather
+    int* src_rows;      // [n][max_det]
+    float* net_boxes;   // [n][max_det][4]
+};
 
 // order-preserving map float -> u32 (larger float <=> larger integer), so the sort key is one integer compare
 __device__ __forceinline__ unsigned ordered_bits(float f) {
@@ -184,47 +188,97 @@ __device__ __forceinline__ unsigned ordered_bits(float f) {
 }
 
 // ---- 1. confidence filter (test_yolo.cpp:341-377) ----------------------------------------------
-// RPB prediction rows are staged in LDS with coalesced loads; one thread then scans one row: box score, first-maximum
-// class (strict '>' as :349-353), confidence = box * class, kept when >= prob_threshold.  Survivors are appended to the
-// image's candidate list (order is irrelevant: the sort key carries the element index).
-constexpr int RPB = 128;
+// One lane scans one row: box score (when the head has one), first-maximum class (strict '>' as :349-353), confidence = box * class or the
+// class score alone, kept when >= prob_threshold.  Survivors are appended to the image's candidate list (order is irrelevant: the sort
+// key carries the element index).  The payload behind the class scores is never read here.
+constexpr int RPB = plan::kStageRows;
 
-__global__ __launch_bounds__(RPB) void yolo_filter_kernel(const float* __restrict__ pred, int rows, int ne,
-                                                          float prob_threshold, PostWs ws) {
+struct FilterArgs {
+    const float* pred;
+    long long image_ld;
+    int rows, ld;
+    int classes, objectness, box_format;
+    float prob_threshold;
+};
+
+// a kept row: its box from the four raw elements, its label, its sort key
+__device__ __forceinline__ void post_emit(const PostWs& ws, int b, int rows, int e, float r0, float r1, float r2, float r3, int box_format,
+                                          int class_index, float confidence) {
+    float x0, y0, x1, y1;
+    if (box_format == plan::kCxCyWh) {
+        x0 = r0 - r2 * 0.5f; y0 = r1 - r3 * 0.5f;
+        x1 = r0 + r2 * 0.5f; y1 = r1 + r3 * 0.5f;
+    } else {
+        x0 = r0; y0 = r1; x1 = r2; y1 = r3;
+    }
+    const int slot = atomicAdd(&ws.count[b], 1);
+    atomicAdd(&ws.bin_count[(size_t)b * ws.nbins + class_index + 1], 1);
+    const size_t o = (size_t)b * rows + slot;
+    ws.box[o] = make_float4(x0, y0, x1 - x0, y1 - y0);
+    ws.label[o] = class_index;
+    // descending (prob, then earlier element first): larger key sorts first
+    ws.key[o] = ((unsigned long long)ordered_bits(confidence) << 32) | (unsigned)(0xffffffffu - (unsigned)e);
+}
+
+// SI_DETECT_ROWS: the scanned part (box, box score, class scores) of RPB rows is staged in LDS with coalesced loads
+__global__ __launch_bounds__(RPB) void detect_filter_rows_kernel(FilterArgs a, PostWs ws) {
     extern __shared__ float stage[];
     const int b = blockIdx.y;
     const int r0 = blockIdx.x * RPB;
-    const int nrows = min(RPB, rows - r0);
-    const float* src = pred + ((size_t)b * rows + r0) * ne;
-    const int total = nrows * ne;
-    for (int i = threadIdx.x; i < total; i += RPB) stage[i] = src[i];
+    const int nrows = min(RPB, a.rows - r0);
+    const int first = 4 + a.objectness;
+    const int scan = first + a.classes;
+    const float* src = a.pred + (size_t)b * (size_t)a.image_ld + (size_t)r0 * a.ld;
+    if (a.ld == scan) {
+        const int total = nrows * scan;
+        for (int i = threadIdx.x; i < total; i += RPB) stage[i] = src[i];
+    } else {
+        // a wave per row, its lanes along the row: nothing between the rows (or of the payload) is touched
+        const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+        for (int r = wave; r < nrows; r += RPB / 64)
+            for (int e = lane; e < scan; e += 64) stage[r * scan + e] = src[(size_t)r * a.ld + e];
+    }
     __syncthreads();
     if ((int)threadIdx.x >= nrows) return;
-    const float* r = stage + threadIdx.x * ne;
-    const float box_score = r[4];
+    const float* r = stage + threadIdx.x * scan;
     int class_index = -1;
     float class_score = -3.402823466e+38f;  // -FLT_MAX
-    for (int k = 0; k < ne - 5; ++k) {
-        const float s = r[5 + k];
+    for (int k = 0; k < a.classes; ++k) {
+        const float s = r[first + k];
         if (s > class_score) {
             class_index = k;
             class_score = s;
         }
     }
-    const float confidence = box_score * class_score;
-    if (confidence >= prob_threshold) {
-        const float cx = r[0], cy = r[1], w = r[2], h = r[3];
-        const float x0 = cx - w * 0.5f, y0 = cy - h * 0.5f;
-        const float x1 = cx + w * 0.5f, y1 = cy + h * 0.5f;
-        const int e = r0 + threadIdx.x;
-        const int slot = atomicAdd(&ws.count[b], 1);
-        atomicAdd(&ws.bin_count[(size_t)b * ws.nbins + class_index + 1], 1);
-        const size_t o = (size_t)b * rows + slot;
-        ws.box[o] = make_float4(x0, y0, x1 - x0, y1 - y0);
-        ws.label[o] = class_index;
-        // descending (prob, then earlier element first): larger key sorts first
-        ws.key[o] = ((unsigned long long)ordered_bits(confidence) << 32) | (unsigned)(0xffffffffu - (unsigned)e);
+    const float confidence = a.objectness ? r[4] * class_score : class_score;
+    if (confidence >= a.prob_threshold)
+        post_emit(ws, b, a.rows, r0 + threadIdx.x, r[0], r[1], r[2], r[3], a.box_format, class_index, confidence);
+}
+
+// SI_DETECT_CHANNELS: element e of row r at e * ld + r.  One lane per row walks the elements, so a wave reads 64 neighbouring floats per
+// step; nothing is staged, and the element count has no limit.
+constexpr int CH_T = 256;
+
+__global__ __launch_bounds__(CH_T) void detect_filter_channels_kernel(FilterArgs a, PostWs ws) {
+    const int b = blockIdx.y;
+    const int row = blockIdx.x * CH_T + threadIdx.x;
+    if (row >= a.rows) return;
+    const float* p = a.pred + (size_t)b * (size_t)a.image_ld + row;
+    const size_t ld = (size_t)a.ld;
+    const float* cls = p + (size_t)(4 + a.objectness) * ld;
+    int class_index = -1;
+    float class_score = -3.402823466e+38f;  // -FLT_MAX
+    int k = 0;
+    for (; k < a.classes; ++k) {
+        const float s = cls[(size_t)k * ld];
+        if (s > class_score) {
+            class_index = k;
+            class_score = s;
+        }
     }
+    const float confidence = a.objectness ? p[4 * ld] * class_score : class_score;
+    if (confidence >= a.prob_threshold)
+        post_emit(ws, b, a.rows, row, p[0], p[ld], p[2 * ld], p[3 * ld], a.box_format, class_index, confidence);
 }
 
 // ---- 2. sort by rank counting -------------------------------------------------------------------
@@ -285,6 +339,7 @@ __global__ __launch_bounds__(SORT_T) void yolo_rank_sort_kernel(int rows, PostWs
         const unsigned ob = (unsigned)(mine >> 32);
         const unsigned u = (ob & 0x80000000u) ? (ob & 0x7fffffffu) : ~ob;
         ws.sprob[o] = __uint_as_float(u);
+        if (ws.srow) ws.srow[o] = (int)(0xffffffffu - (unsigned)(mine & 0xffffffffull));
         ws.gbox[base + start + seg] = bx;
         ws.grank[base + start + seg] = rank;
     }
@@ -314,12 +369,25 @@ __device__ __forceinline__ float clipf(float v, float lo, float hi) {
     return lo < m ? m : lo;
 }
 
+// the general entry's outputs for the candidate at confidence rank `idx`, stored as detection `pos` (< max_det) of image b
+__device__ __forceinline__ void post_more(const PostMore& more, const PostWs& ws, int b, int rows, int max_det, int idx, int pos, const float4 box) {
+    if (more.drow || more.src_rows) {
+        const int row = ws.srow[(size_t)b * rows + idx];
+        if (more.drow) more.drow[(size_t)b * rows + pos] = row;
+        if (more.src_rows) more.src_rows[(size_t)b * max_det + pos] = row;
+    }
+    if (more.net_boxes) {
+        float* nb = more.net_boxes + ((size_t)b * max_det + pos) * 4;
+        nb[0] = box.x; nb[1] = box.y; nb[2] = box.z; nb[3] = box.w;
+    }
+}
+
 // One workgroup (4 waves) per image walks the sorted candidates 64 at a time.  Phase 1: every wave tests the 64
 // candidates against its quarter of the boxes picked so far.  Phase 2 (wave 0): the in-chunk dependency chain is
 // resolved with ballots -- candidate i, if still alive, suppresses later same-label candidates it overlaps.
 __global__ __launch_bounds__(256) void yolo_nms_kernel(int rows, float nms_threshold, int agnostic,
                                                        const float* __restrict__ adjust, float* __restrict__ dets,
-                                                       int* __restrict__ counts, int max_det, PostWs ws) {
+                                                       int* __restrict__ counts, int max_det, PostWs ws, PostMore more) {
     __shared__ unsigned long long dead[4];
     __shared__ int picked_n;
     const int b = blockIdx.x;
@@ -398,6 +466,7 @@ __global__ __launch_bounds__(256) void yolo_nms_kernel(int rows, float nms_thres
                     d[3] = adj ? y1 - y0 : box.w;
                     d[4] = ws.sprob[base + idx];
                     d[5] = (float)label;
+                    post_more(more, ws, b, rows, max_det, idx, pos, box);
                 }
             }
             if (lane == 0) picked_n = P + __popcll(alive);
@@ -469,7 +538,7 @@ __global__ __launch_bounds__(256) void yolo_nms_segments_kernel(int rows, float 
 // keep flags (indexed by confidence rank) -> dense output in confidence order + un-letterbox / clip (:386-416)
 __global__ __launch_bounds__(256) void yolo_compact_kernel(int rows, const float* __restrict__ adjust,
                                                            float* __restrict__ dets, int* __restrict__ counts,
-                                                           int max_det, PostWs ws) {
+                                                           int max_det, PostWs ws, PostMore more) {
     __shared__ int wsum[4];
     const int b = blockIdx.x;
     const int count = ws.count[b];
@@ -510,9 +579,74 @@ __global__ __launch_bounds__(256) void yolo_compact_kernel(int rows, const float
             d[3] = adj ? y1 - y0 : box.w;
             d[4] = ws.sprob[base + g];
             d[5] = (float)ws.slabel[base + g];
+            post_more(more, ws, b, rows, max_det, g, pos, box);
         }
     }
     if (threadIdx.x == 0) counts[b] = total;
+}
+
+// ---- 4. payload gather ---------------------------------------------------------------------------
+// extras[b][d][k] = element (first + k) of the prediction row of stored detection d, as 32-bit words (a NaN keeps its bits).  Runs behind
+// the NMS / compaction kernel of the same stream, which wrote counts and drow.
+__global__ __launch_bounds__(256) void detect_gather_kernel(const unsigned* __restrict__ pred, long long image_ld, int rows, int ld, int layout,
+                                                            int first, int extra, const int* __restrict__ counts, int max_det,
+                                                            const int* __restrict__ drow, unsigned* __restrict__ extras) {
+    const int b = blockIdx.y;
+    const size_t items = (size_t)min(counts[b], max_det) * (size_t)extra;
+    const unsigned* src = pred + (size_t)b * (size_t)image_ld;
+    unsigned* dst = extras + (size_t)b * (size_t)max_det * (size_t)extra;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < items; i += (size_t)gridDim.x * 256) {
+        const size_t d = i / (size_t)extra;
+        const size_t e = (size_t)first + (i - d * (size_t)extra);
+        const size_t row = (size_t)drow[(size_t)b * rows + d];
+        dst[i] = layout == plan::kRows ? src[row * (size_t)ld + e] : src[e * (size_t)ld + row];
+    }
+}
+
+// filter, sort, NMS / compaction (+ gather): the launches of both entries
+struct PostLaunch {
+    FilterArgs filter;
+    int n, extra, layout;
+    float nms_threshold;
+    int agnostic, max_det;
+    const float* adjust;
+    float* dets;
+    int* counts;
+    float* extras;
+};
+
+int post_launch(const PostLaunch& L, const PostWs& ws, const PostMore& more, hipStream_t s) {
+    const int n = L.n, rows = L.filter.rows;
+    SI_HIP_TRY(hipMemsetAsync(ws.count, 0, ws.zero_bytes, s));
+    if (L.layout == plan::kRows) {
+        const size_t lds = (size_t)RPB * (size_t)(4 + L.filter.objectness + L.filter.classes) * sizeof(float);
+        hipLaunchKernelGGL(detect_filter_rows_kernel, dim3((rows + RPB - 1) / RPB, n), dim3(RPB), lds, s, L.filter, ws);
+    } else {
+        hipLaunchKernelGGL(detect_filter_channels_kernel, dim3((rows + CH_T - 1) / CH_T, n), dim3(CH_T), 0, s, L.filter, ws);
+    }
+    hipLaunchKernelGGL(yolo_rank_sort_kernel, dim3((rows + SORT_T - 1) / SORT_T, n), dim3(SORT_T), 0, s, rows, ws);
+    if (L.agnostic) {
+        // one chain per image: a workgroup walks the confidence order against everything picked so far
+        hipLaunchKernelGGL(yolo_nms_kernel, dim3(n), dim3(256), 0, s, rows, L.nms_threshold, 1, L.adjust, L.dets, L.counts, L.max_det, ws, more);
+    } else {
+        hipLaunchKernelGGL(yolo_nms_segments_kernel, dim3((ws.nbins + 3) / 4, n), dim3(256), 0, s, rows, L.nms_threshold, ws);
+        hipLaunchKernelGGL(yolo_compact_kernel, dim3(n), dim3(256), 0, s, rows, L.adjust, L.dets, L.counts, L.max_det, ws, more);
+    }
+    if (L.extras && L.extra > 0 && L.max_det > 0) {
+        const size_t items = (size_t)(L.max_det < rows ? L.max_det : rows) * (size_t)L.extra;
+        const size_t gx = (items + 255) / 256;
+        hipLaunchKernelGGL(detect_gather_kernel, dim3((unsigned)(gx > 64 ? 64 : gx), n), dim3(256), 0, s, (const unsigned*)L.filter.pred,
+                           L.filter.image_ld, rows, L.filter.ld, L.layout, 4 + L.filter.objectness + L.filter.classes, L.extra, L.counts, L.max_det,
+                           more.drow, (unsigned*)L.extras);
+    }
+    return (int)hipGetLastError();
+}
+
+plan::Shape detect_shape(const SiDetectPostDesc* d) {
+    plan::Shape v;
+    v.n = d->n; v.rows = d->rows; v.classes = d->classes; v.objectness = d->objectness; v.extra = d->extra; v.layout = d->layout; v.ld = d->ld;
+    v.image_ld = d->image_ld; v.box_format = d->box_format; v.agnostic = d->agnostic; v.max_det = d->max_det;
+    return v;
 }
 
 }  // namespace
@@ -597,7 +731,7 @@ int si_hip_resize_letterbox_batch_u8_f32(const unsigned char* frames_bgr, int n,
 
 size_t si_hip_yolo_postprocess_workspace_bytes(int n, int rows, int ne) {
     if (n <= 0 || rows <= 0 || ne < 5) return 0;
-    return post_ws_layout(n, rows, ne - 5 + 1, nullptr, nullptr);
+    return plan::Layout(n, rows, ne - 5 + 1, false).total;
 }
 
 int si_hip_yolo_postprocess_f32(const float* pred, int n, int rows, int ne, float prob_threshold, float nms_threshold,
@@ -615,22 +749,47 @@ int si_hip_yolo_postprocess_f32(const float* pred, int n, int rows, int ne, floa
     // n is a grid's y extent (65535 at most), RPB rows of ne floats are the filter's LDS stage (64 KB at most: ne <= 128)
     if (n > 65535 || (size_t)RPB * ne * sizeof(float) > 64 * 1024) return SI_E_UNSUPPORTED;
     PostWs ws;
-    const size_t need = post_ws_layout(n, rows, ne - 5 + 1, (char*)workspace, &ws);
+    const size_t need = post_ws_bind(n, rows, ne - 5 + 1, false, (char*)workspace, &ws);
     if (workspace_bytes < need) return SI_E_BADARG;
-    SI_HIP_TRY(hipMemsetAsync(workspace, 0, ws.zero_bytes, s));
-    hipLaunchKernelGGL(yolo_filter_kernel, dim3((rows + RPB - 1) / RPB, n), dim3(RPB), (size_t)RPB * ne * sizeof(float), s,
-                       pred, rows, ne, prob_threshold, ws);
-    hipLaunchKernelGGL(yolo_rank_sort_kernel, dim3((rows + SORT_T - 1) / SORT_T, n), dim3(SORT_T), 0, s, rows, ws);
-    if (agnostic) {
-        // one chain per image: a workgroup walks the confidence order against everything picked so far
-        hipLaunchKernelGGL(yolo_nms_kernel, dim3(n), dim3(256), 0, s, rows, nms_threshold, 1, adjust, dets, counts,
-                           max_det, ws);
-    } else {
-        hipLaunchKernelGGL(yolo_nms_segments_kernel, dim3((ws.nbins + 3) / 4, n), dim3(256), 0, s, rows, nms_threshold,
-                           ws);
-        hipLaunchKernelGGL(yolo_compact_kernel, dim3(n), dim3(256), 0, s, rows, adjust, dets, counts, max_det, ws);
+    PostLaunch L;
+    L.filter = FilterArgs{pred, (long long)rows * ne, rows, ne, ne - 5, 1, plan::kCxCyWh, prob_threshold};
+    L.n = n; L.extra = 0; L.layout = plan::kRows;
+    L.nms_threshold = nms_threshold; L.agnostic = agnostic; L.max_det = max_det;
+    L.adjust = adjust; L.dets = dets; L.counts = counts; L.extras = nullptr;
+    return post_launch(L, ws, PostMore{nullptr, nullptr, nullptr}, s);
+}
+
+size_t si_hip_detect_postprocess_workspace_bytes(const SiDetectPostDesc* d) {
+    return d ? plan::WorkspaceBytes(detect_shape(d)) : 0;
+}
+
+const char* si_hip_detect_filter_kernel_name(const SiDetectPostDesc* d, const void* pred) {
+    if (!d || !pred || (reinterpret_cast<uintptr_t>(pred) & 3) != 0) return "none";
+    switch (plan::FormOf(detect_shape(d))) {
+        case plan::kRowsStaged: return "detect_filter_rows_kernel";
+        case plan::kChannelLanes: return "detect_filter_channels_kernel";
+        default: return "none";
     }
-    return (int)hipGetLastError();
+}
+
+int si_hip_detect_postprocess_f32(const SiDetectPostDesc* d, const float* pred, const float* adjust, const SiDetectPostOut* out,
+                                  void* workspace, size_t workspace_bytes, si_stream_t stream) {
+    if (!d || !pred || !out || !out->counts || !workspace) return SI_E_BADARG;
+    if ((reinterpret_cast<uintptr_t>(pred) & 3) != 0) return SI_E_BADARG;
+    const plan::Shape v = detect_shape(d);
+    const int rc = plan::StatusOf(v);
+    if (rc != plan::kOk) return rc == plan::kBadArg ? SI_E_BADARG : SI_E_UNSUPPORTED;
+    if (d->max_det > 0 && !out->dets) return SI_E_BADARG;
+    PostWs ws;
+    const size_t need = post_ws_bind(d->n, d->rows, (int)plan::Bins(v), true, (char*)workspace, &ws);
+    if (workspace_bytes < need) return SI_E_BADARG;
+    PostLaunch L;
+    L.filter = FilterArgs{pred, d->image_ld, d->rows, d->ld, d->classes, d->objectness, d->box_format, d->prob_threshold};
+    L.n = d->n; L.extra = d->extra; L.layout = d->layout;
+    L.nms_threshold = d->nms_threshold; L.agnostic = d->agnostic; L.max_det = d->max_det;
+    L.adjust = adjust; L.dets = out->dets; L.counts = out->counts; L.extras = out->extras;
+    PostMore more{out->extras && d->extra > 0 ? ws.drow : nullptr, out->src_rows, out->net_boxes};
+    return post_launch(L, ws, more, (hipStream_t)stream);
 }
 
 }  // extern "C"

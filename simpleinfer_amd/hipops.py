@@ -2117,6 +2117,150 @@ def yolo_postprocess(pred, prob_threshold=0.25, nms_threshold=0.45, agnostic=Fal
     return [dets[b, :min(int(cnt[b]), max_det)].copy() for b in range(n)], cnt
 
 
+# ---- include/si_detect.h: post-processing for anchor-free heads, payloads and instance masks -------------------------------------------------
+DETECT_LAYOUTS = {"rows": 0, "channels": 1}
+DETECT_BOX_FORMATS = {"cxcywh": 0, "xyxy": 1}
+
+
+def detect_desc(n, rows, classes, objectness=False, extra=0, layout="rows", box_format="cxcywh", prob_threshold=0.25, nms_threshold=0.45,
+                agnostic=False, max_det=None, ld=None, image_ld=None):
+    """SiDetectPostDesc; ld / image_ld default to the dense strides of the layout, max_det to rows"""
+    ne = 4 + int(bool(objectness)) + int(classes) + int(extra)
+    lay = DETECT_LAYOUTS[layout] if isinstance(layout, str) else int(layout)
+    fmt = DETECT_BOX_FORMATS[box_format] if isinstance(box_format, str) else int(box_format)
+    if ld is None:
+        ld = rows if lay == 1 else ne
+    if image_ld is None:
+        image_ld = ne * ld if lay == 1 else rows * ld
+    return _native.SiDetectPostDesc(int(n), int(rows), int(classes), int(bool(objectness)), int(extra), lay, int(ld), int(image_ld), fmt,
+                                    float(prob_threshold), float(nms_threshold), int(bool(agnostic)), int(rows if max_det is None else max_det))
+
+
+def detect_filter_kernel_name(d, pred_ptr=256) -> str:
+    return _native.hip().si_hip_detect_filter_kernel_name(C.byref(d), C.c_void_p(pred_ptr)).decode()
+
+
+def detect_workspace_bytes(d) -> int:
+    return int(_native.hip().si_hip_detect_postprocess_workspace_bytes(C.byref(d)))
+
+
+def detect_storage(pred, layout="rows", ld=None, image_ld=None, offset=0, fill=np.nan):
+    """the flat fp32 storage of a logical pred ([n][rows][ne] for "rows", [n][ne][rows] for "channels") with row / channel stride ld, image stride
+    image_ld and `offset` leading elements; every gap holds `fill`"""
+    pred = _f32(pred)
+    n, outer, inner = pred.shape
+    ld = inner if ld is None else int(ld)
+    image_ld = outer * ld if image_ld is None else int(image_ld)
+    assert ld >= inner and image_ld >= (outer - 1) * ld + inner
+    flat = _full((offset + (n - 1) * image_ld + (outer - 1) * ld + inner,), np.float32, fill)
+    for b in range(n):
+        for o in range(outer):
+            at = offset + b * image_ld + o * ld
+            flat[at:at + inner] = pred[b, o]
+    return flat
+
+
+class DetectResult:
+    """what detect_postprocess returns: per-image lists cut to min(counts[b], max_det) (dets [k][6], src_rows [k], net_boxes [k][4], extras
+    [k][extra]; None for an output that was not asked for), counts [n], `full`: the whole output arrays as read back, `dev`: their device
+    buffers (for detect_masks), `max_det`, `extra`"""
+
+    def __init__(self, n, max_det, extra, counts, full, dev):
+        self.n, self.max_det, self.extra, self.counts, self.full, self.dev = n, max_det, extra, counts, full, dev
+        k = [min(int(c), max_det) for c in counts]
+        for name in ("dets", "src_rows", "net_boxes", "extras"):
+            a = full.get(name)
+            setattr(self, name, None if a is None else [a[b, :k[b]].copy() for b in range(n)])
+
+
+def detect_postprocess(pred, classes, objectness=False, extra=0, layout="rows", box_format="cxcywh", prob_threshold=0.25, nms_threshold=0.45,
+                       agnostic=False, adjust=None, max_det=None, pred_dev=None, ld=None, image_ld=None, workspace=None, shape=None, pred_off=0,
+                       in_fill=np.nan, want=("src_rows", "net_boxes", "extras"), host=None, out_fill=0.0, stream=None):
+    """si_hip_detect_postprocess_f32 (include/si_detect.h).  pred: the logical array, [n][rows][ne] for layout "rows" and [n][ne][rows] for
+    "channels"; ld / image_ld / pred_off lay it out with gaps (filled with in_fill) and a base pointer pred_off elements into the buffer.
+    pred_dev: a DeviceBuffer (or a view on an Engine.extract pointer with outputs_to_host=0) that already holds the storage, with
+    shape = (n, rows); pred is then not read.  want: which optional outputs to ask for; host: which outputs to copy to the host (None: all that
+    exist; counts always) -- the others stay on the device in the result's `dev`, where detect_masks finds them.  out_fill: what the output buffers hold before the
+    call (a value or a ByteFill), so that a caller sees what was left untouched.  Returns a DetectResult."""
+    H = _native.hip()
+    lay = DETECT_LAYOUTS[layout]
+    if pred_dev is None:
+        pred = _f32(pred)
+        n, rows = (pred.shape[0], pred.shape[2]) if lay == 1 else (pred.shape[0], pred.shape[1])
+        dbuf = DeviceBuffer.from_numpy(detect_storage(pred, layout, ld, image_ld, pred_off, in_fill))
+        pred_ptr = dbuf.ptr + 4 * pred_off
+    else:
+        n, rows = (int(v) for v in shape)
+        pred_ptr = pred_dev.ptr + 4 * pred_off
+    d = detect_desc(n, rows, classes, objectness, extra, layout, box_format, prob_threshold, nms_threshold, agnostic, max_det, ld, image_ld)
+    max_det = d.max_det
+    dadj = DeviceBuffer.from_numpy(_f32(adjust).reshape(n, 5)) if adjust is not None else None
+    wsb = detect_workspace_bytes(d)
+    dws = workspace if workspace is not None else DeviceBuffer(max(wsb, 16))
+    assert wsb == 0 or dws.nbytes >= wsb, "workspace of %d bytes, the call needs %d" % (dws.nbytes, wsb)
+    shapes = {"dets": ((n, max_det, 6), np.float32), "counts": ((n,), np.int32), "src_rows": ((n, max_det), np.int32),
+              "net_boxes": ((n, max_det, 4), np.float32), "extras": ((n, max_det, int(extra)), np.float32)}
+    dev = {}
+    for name, (shp, dt) in shapes.items():
+        if name in ("dets", "counts") or name in want:
+            dev[name] = DeviceBuffer.from_numpy(_full((max(int(np.prod(shp)), 4),), dt, out_fill), out=True)
+    out = _native.SiDetectPostOut(*[dev[k].ptr if k in dev else None for k in ("dets", "counts", "src_rows", "net_boxes", "extras")])
+    _chk(H.si_hip_detect_postprocess_f32(C.byref(d), pred_ptr, dadj.ptr if dadj else None, C.byref(out), dws.ptr, dws.nbytes, stream),
+         "si_hip_detect_postprocess_f32")
+    full = {k: b.to_numpy(shapes[k][0], shapes[k][1], stream) for k, b in dev.items() if host is None or k in host or k == "counts"}
+    return DetectResult(n, max_det, int(extra), full["counts"].copy(), full, dev)
+
+
+def detect_mask_desc(n, mh, mw, nm, max_det, extra, coef_off=0, ratio_w=0.25, ratio_h=0.25, proto_ld=None):
+    return _native.SiDetectMaskDesc(int(n), int(mh), int(mw), int(nm), int(nm if proto_ld is None else proto_ld), int(max_det), int(extra),
+                                    int(coef_off), float(np.float32(ratio_w)), float(np.float32(ratio_h)))
+
+
+def detect_masks_kernel_name(d, protos_ptr=256) -> str:
+    return _native.hip().si_hip_detect_masks_kernel_name(C.byref(d), C.c_void_p(protos_ptr)).decode()
+
+
+def detect_masks(protos, extras, net_boxes, counts, ratio_w=0.25, ratio_h=0.25, coef_off=0, nm=None, proto_ld=None, protos_dev=None, shape=None,
+                 protos_off=0, in_fill=np.nan, out_fill=0, full=False, stream=None):
+    """si_hip_detect_masks_f32.  protos: [n][mh][mw][nm] (NHWC), laid out with pixel stride proto_ld (gaps: in_fill) and protos_off leading
+    elements -- or protos_dev, a DeviceBuffer that holds them (an Engine.extract pointer with outputs_to_host=0), with shape = (n, mh, mw, nm).
+    extras [n][max_det][extra], net_boxes [n][max_det][4] and counts [n] are numpy arrays -- or pass a DetectResult as `extras` (net_boxes and
+    counts are then ignored): its device buffers are read where detect_postprocess left them.  Returns, per image, the planes
+    [min(counts[b], max_det)][mh][mw] uint8, the only bytes copied back -- or with full=True the whole [n][max_det][mh][mw] buffer as read
+    back (pre-filled with the byte out_fill)."""
+    H = _native.hip()
+    if isinstance(extras, DetectResult):
+        res = extras
+        max_det, extra = res.max_det, res.extra
+        dext, dbox, dcnt, cnt = res.dev["extras"], res.dev["net_boxes"], res.dev["counts"], res.counts
+    else:
+        extras, net_boxes, cnt = _f32(extras), _f32(net_boxes), np.ascontiguousarray(counts, np.int32)
+        max_det, extra = int(extras.shape[1]), int(extras.shape[2])
+        dext = DeviceBuffer.from_numpy(extras if extras.size else np.zeros(4, np.float32))
+        dbox = DeviceBuffer.from_numpy(net_boxes if net_boxes.size else np.zeros(4, np.float32))
+        dcnt = DeviceBuffer.from_numpy(cnt)
+    if protos_dev is None:
+        protos = _f32(protos)
+        n, mh, mw, pnm = (int(v) for v in protos.shape)
+        ldp = pnm if proto_ld is None else int(proto_ld)
+        store = _full((protos_off + n * mh * mw * ldp,), np.float32, in_fill)
+        store[protos_off:].reshape(n * mh * mw, ldp)[:, :pnm] = protos.reshape(-1, pnm)
+        dpro = DeviceBuffer.from_numpy(store)
+    else:
+        n, mh, mw, pnm = (int(v) for v in shape)
+        ldp = pnm if proto_ld is None else int(proto_ld)
+        dpro = protos_dev
+    nm = pnm if nm is None else int(nm)
+    d = detect_mask_desc(n, mh, mw, nm, max_det, extra, coef_off, ratio_w, ratio_h, ldp)
+    dmask = DeviceBuffer.from_numpy(np.full(max(n * max_det * mh * mw, 16), out_fill, np.uint8), out=True)
+    _chk(H.si_hip_detect_masks_f32(C.byref(d), dpro.ptr + 4 * protos_off, dext.ptr, dbox.ptr, dcnt.ptr, dmask.ptr, stream), "si_hip_detect_masks_f32")
+    if full:
+        return dmask.to_numpy((n, max_det, mh, mw), np.uint8, stream)
+    # the planes of the kept detections alone leave the device
+    kept = [min(int(cnt[b]), max_det) for b in range(n)]
+    return [DeviceBuffer.view(dmask.ptr + b * max_det * mh * mw, max(kept[b] * mh * mw, 16)).to_numpy((kept[b], mh, mw), np.uint8, stream) for b in range(n)]
+
+
 # ---------------------------------------------------------------------------
 # fp16 storage path (include/si_hip.h "fp16 storage path").  Activations travel as numpy float16 (IEEE binary16, the
 # device's _Float16); results come back as float16 unless noted.

@@ -1190,6 +1190,26 @@ def build_toy_anchorfree_head(batch: int = 2, size: int = 64, no: int = 32, seed
     return b
 
 
+def build_toy_yolov8_seg(batch: int = 2, size: int = 64, nc: int = 5, nm: int = 32, channels_first: bool = True, seed: int = 0) -> PnnxBuilder:
+    """A YOLOv8-seg style export: per level a conv to no = 4 + nc + nm channels (box as cx cy w h, class scores, mask coefficients) -> view(N, no, -1);
+    cat(dim=2) over the levels: [N, no, cells], channel-major as ultralytics exports it -- or [N, cells, no] behind the closing permute(0,2,1)
+    when channels_first is False; and the prototype branch, two convs on the finest level: [N, nm, size / 4, size / 4], a second graph output."""
+    b = PnnxBuilder(seed)
+    feats = _toy_pyramid(b, batch, size)
+    no = 4 + nc + nm
+    rows = []
+    for lv, f in enumerate(feats):
+        name = "seg_head_%d" % lv
+        rows.append(b.view(b.conv(f, no, 1, name=name), (batch, no, -1)))
+        # boxes of a plausible size around the image centre instead of a few pixels around the origin: they overlap, and they cover mask pixels
+        b.attrs[name + ".weight"][:4] *= size / 2.0
+        b.attrs[name + ".bias"][:4] = (size / 2.0, size / 2.0, size / 3.0, size / 3.0)
+    y = b.cat(rows, 2)
+    b.output(y if channels_first else b.permute(y, (0, 2, 1)))
+    b.output(b.conv(b.relu(b.conv(feats[0], nm, 3, 1, 1)), nm, 1))
+    return b
+
+
 def build_toy_yolov5_raw_head(batch: int = 2, size: int = 32, na: int = 3, no: int = 7, seed: int = 0) -> PnnxBuilder:
     """A raw YOLOv5 export's head: per level conv to na * no channels -> view(N, na, no, H, W) -> permute(0,1,3,4,2) -> view(N, -1, no) (the
     rank-5 route), sigmoid, cat(dim=1) over the levels: [N, na * cells, no]."""
