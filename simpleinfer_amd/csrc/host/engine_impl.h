@@ -123,6 +123,7 @@ private:
     Status AliasSplits();
     Status AliasViews();
     void ResolveAliases();
+    bool ViewTaken(const TensorNode* node, int ld, int off, const char* into) const;   // every step that touches `node` takes it as that channel slice
     Status UploadInputs();
     Status UploadConstant(TensorNode* node);   // a pnnx.Attribute's buffers: allocated outside the arena and filled once
     Status BindOutputs();

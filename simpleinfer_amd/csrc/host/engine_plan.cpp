@@ -816,6 +816,27 @@ Status EngineImpl::InsertFp32Fallbacks(std::vector<Step>& order) {
     return Status::kSuccess;
 }
 
+// Fusions and storage decisions are re-asked with the real views, or the view is not made.  Every fusion pass and InsertFp32Fallbacks ran on
+// dense strides; the alias passes below are what gives an operand its real row.  Before one of them makes `node` a channel slice (pixel
+// stride `ld`, `off` channels into the row), every scheduled step is asked whether its launch takes the operand that way (Layer::TakesView:
+// a step that does not touch the node says yes) -- the fused groups answer for their real operand lists (the pair's input, the shortcut, the
+// upsampled source, the cv3 form's z).  Views that already hang off `node` (the pieces of a split it feeds) move with it and are asked too.
+// A "no" leaves the operand its own buffer, and the concat or split launches the copy it has for that case.
+bool EngineImpl::ViewTaken(const TensorNode* node, int ld, int off, const char* into) const {
+    for (const Step& s : plan_) {
+        if (s.layer->TakesView(node, ld, off)) continue;
+        LOG(INFO) << "alias: operand [" << (node->operand ? node->operand->name : std::string("-")) << "] keeps its own buffer: [" << s.op->name
+                  << "] (" << s.op->type << ") does not take it at pixel stride " << ld << ", channel offset " << off << " (" << into << ")";
+        return false;
+    }
+    for (const auto& kv : aliases_) {
+        if (kv.second.parent != node || kv.second.whole) continue;
+        auto it = tensor_nodes_.find(kv.first);
+        if (it != tensor_nodes_.end() && it->second != node && !ViewTaken(it->second, ld, off + kv.second.channel_offset, into)) return false;
+    }
+    return true;
+}
+
 // torch.cat on the channel axis: every eligible input operand becomes a view into the concat output
 // (same pixel grid, pixel stride = total channels), so its producer writes in place and Cat::Forward
 // finds nothing left to copy.
@@ -846,6 +867,8 @@ Status EngineImpl::AliasConcats() {
                     if (dynamic_cast<DeformConv2d*>(w.layer) || dynamic_cast<GridSample*>(w.layer))
                         for (TensorNode* n : w.layer->OutputNodes()) ok = ok && n != tensor_nodes_[r->name];
             seen.insert(r);
+            // ... and its producer and every reader take it at the concat's row (asked last: the refusal it logs is then the only reason)
+            ok = ok && ViewTaken(tensor_nodes_[r->name], out->tensor.Shape().back(), offset, s.op->name.c_str());
             if (ok) {
                 Alias a;
                 a.parent = out;
@@ -873,6 +896,16 @@ Status EngineImpl::AliasSplits() {
         const std::vector<Slice::Piece>& pieces = sl->Pieces();
         if (xs.size() != 4 || pieces.size() != s.op->outputs.size() || sl->OutputNodes().size() != pieces.size()) continue;
         const int in_dims[4] = {xs[0], xs[1], xs[2], xs[3]};
+        // the row the views will have: the input's own, or -- a chunk of a chunk -- that of the buffer the input is already a slice of
+        const TensorNode* root = in;
+        int root_off = 0;
+        for (size_t hops = 0; hops <= aliases_.size() && root->operand; ++hops) {
+            auto up = aliases_.find(root->operand->name);
+            if (up == aliases_.end() || up->second.whole || tensor_nodes_[up->first] != root || !up->second.parent) break;
+            root_off += up->second.channel_offset;
+            root = up->second.parent;
+        }
+        const int root_ld = root->tensor.Shape().empty() ? xs[3] : root->tensor.Shape().back();
         for (size_t i = 0; i < pieces.size(); ++i) {
             const pnnx::Operand* r = s.op->outputs[i];
             TensorNode* out = sl->OutputNodes()[i];
@@ -882,6 +915,8 @@ Status EngineImpl::AliasSplits() {
                       ((size_t)pieces[i].start[3] * ElementSize(in->tensor.GetDataType()) % 16 == 0);
             if (ok)
                 for (const pnnx::Operator* c : r->consumers) ok = ok && c && HonoursPixelStride(c->type);
+            // ... and every reader takes it at that row (a concat that later takes the input asks again, for the views that hang off it too)
+            ok = ok && ViewTaken(out, root_ld, root_off + pieces[i].start[3], s.op->name.c_str());
             if (!ok) continue;
             Alias a;
             a.parent = in;

@@ -68,6 +68,11 @@ public:
     // LoadModel, so that an unsupported combination is a load-time Status with a reason instead of a failing first Forward().
     // Default: fine when no bound tensor is fp16, or when inputs and outputs are all fp16.
     virtual bool HalfStorageOk(std::string& why) const;
+    // Asked by the planner BEFORE it makes `node` (one of this layer's bound or extra operands) a channel slice of a wider buffer: does the
+    // launch this layer will make take the operand at pixel stride `ld` elements, `off` channels into the row, in the storage type the node
+    // has -- itself or through a second launch of its own?  Fusions and HalfStorageOk were decided on dense strides; this is where they meet
+    // the real view, and a "no" leaves the operand its own buffer (view_rule.h).  Default: yes (kernels that step by ld with scalar accesses).
+    virtual bool TakesView(const TensorNode* node, int ld, int off) const { (void)node; (void)ld; (void)off; return true; }
     virtual double Bytes() const;
 
     const std::vector<TensorNode*>& InputNodes() const { return input_tensor_nodes_; }

@@ -277,4 +277,15 @@ bool BinaryOp::HalfStorageOk(std::string& why) const {
     return false;
 }
 
+// The per-image channel vector form under fp16 storage (si_hip_binary_bcast_f16) reads and writes 16-byte vectors only and there is no scalar
+// form behind it: its three operands keep rows of whole vectors.  The same-shape and constant forms step by ld element by element.
+bool BinaryOp::TakesView(const TensorNode* node, int ld, int off) const {
+    if (!node || !IsHalf(node->tensor) || ConstForm() || with_scalar_ || input_tensor_nodes_.size() != 2 || output_tensor_nodes_.size() != 1) return true;
+    const TensorNode* const nodes[3] = {input_tensor_nodes_[0], input_tensor_nodes_[1], output_tensor_nodes_[0]};
+    if (node != nodes[0] && node != nodes[1] && node != nodes[2]) return true;
+    const std::vector<int> o = nodes[2]->tensor.ShapeAs(4);
+    if (nodes[0]->tensor.ShapeAs(4) == o && nodes[1]->tensor.ShapeAs(4) == o) return true;   // the same-shape form
+    return HalfBroadcastTakesView(ld, off);
+}
+
 }  // namespace SimpleInfer

@@ -6,6 +6,7 @@
 #include "layer.h"
 #include "layer_util.h"
 #include "si_binary.h"
+#include "view_rule.h"
 
 namespace SimpleInfer {
 
@@ -18,6 +19,7 @@ public:
     virtual Status Forward(const std::vector<Tensor>& inputs, Tensor& output) override;
     virtual Status Forward(const Tensor& input, Tensor& output) override;  // the `with_scalar` form: one tensor operand
     virtual bool HalfStorageOk(std::string& why) const override;
+    virtual bool TakesView(const TensorNode* node, int ld, int off) const override;
     virtual const char* KernelName() const override;
 
     // ---- the constant form: exactly one operand is a graph constant (a pnnx.Attribute's output) and the other has the output's shape.  It runs

@@ -665,8 +665,12 @@ Status Conv2d::Launch(const Tensor& input, const Tensor* residual, Tensor& outpu
         // The pair was fused on dense strides, before the concat aliasing gave the tensors their real views (CanFusePointwiseProducer); the
         // launch re-checks the views it gets (16-byte aligned rows, strides in whole 16-byte vectors) and may refuse a channel slice at an odd
         // offset.  The fused-away intermediate is never planned, so the two ordinary launches run through a private one (this path
-        // returned kUnsupport until round 6; YOLOv5s never takes it -- all its strides are multiples of 8).
-        if (!pw_scratch_.RawData()) CHECK_STATUS(pw_scratch_.Allocate(DataType::kFloat16, pw_mid_->tensor.Shape()));
+        // returned kUnsupport until round 6; YOLOv5s never takes it -- all its strides are multiples of 8).  The planner only makes views under
+        // which these two launches run (TakesView: the input row in whole vectors); what is left for this path is an output or shortcut row
+        // the fused kernel refuses, e.g. the slab form writing into a concat whose width is no multiple of 8.
+        // (a default-constructed Tensor is a HOST tensor, as in HalfInput: the private intermediate is made a device tensor before it is allocated)
+        if (pw_scratch_.GetMemoryType() != MemoryType::kDevice) pw_scratch_ = Tensor(DataType::kFloat16, pw_mid_->tensor.Shape(), MemoryType::kDevice, false);
+        CHECK_STATUS(pw_scratch_.Allocate(DataType::kFloat16, pw_mid_->tensor.Shape()));
         Conv2d* const pw = pw_producer_;
         CHECK_STATUS(pw->Launch(input, nullptr, pw_scratch_));
         pw_producer_ = nullptr;
@@ -966,6 +970,37 @@ bool Conv2d::HalfStorageOk(std::string& why) const {
     why ="no fp16 conv kernel for " + std::to_string(in_channels_) + " -> " + std::to_string(out_channels_) + " channels, groups " +
           std::to_string(groups_) + " (needs ic / groups % 32 == 0, an ungrouped conv with ic % 8 == 0, a depthwise conv with ic % 8 == 0, or an RGB stem on an fp32 image)";
     return false;
+}
+
+// The fusions above and HalfStorageOk asked the kernels on dense strides; this is the same question with the stride a concat or split view
+// would give `node`.  Half operands, and the upsampled source in fp32: the other fp32 routes have a second launch for a refused view (the
+// Winograd re-pack, DemoteSplit).  The form is the launch Launch() / Forward(input, outputs) will make; the table is view_rule.h's.
+bool Conv2d::TakesView(const TensorNode* node, int ld, int off) const {
+    if (!node || input_tensor_nodes_.empty() || output_tensor_nodes_.empty()) return true;
+    if (!IsHalf(node->tensor)) return node != up_node_ || FloatUpsampledSourceTakesView(ld, off);
+    HalfConvForm form = HalfConvForm::kIgemm;
+    if (cv3_pair_) {
+        form = HalfConvForm::kCv3;
+    } else if (stem_pair_ || stem_producer_) {
+        form = HalfConvForm::kStemFused;
+    } else if (pw_producer_) {
+        form = HalfConvForm::kPair;
+    } else {
+        const Route route = RouteFor(IsHalf(input_tensor_nodes_[0]->tensor), IsHalf(output_tensor_nodes_[0]->tensor));
+        if (route == Route::kDepthwiseF16) form = HalfConvForm::kDepthwise;
+        if (route == Route::kStemF16) form = HalfConvForm::kStemFused;
+    }
+    bool ok = true;
+    const auto ask = [&](const TensorNode* n, ConvOperand operand) {
+        if (n == node) ok = ok && HalfConvTakesView(form, operand, ld, off);
+    };
+    for (const TensorNode* n : input_tensor_nodes_) ask(n, ConvOperand::kInput);
+    for (const TensorNode* n : output_tensor_nodes_) ask(n, ConvOperand::kOutput);
+    ask(residual_node_, ConvOperand::kResidual);
+    ask(up_node_, ConvOperand::kUpsampledSource);
+    ask(cv3_z_, ConvOperand::kCv3Z);
+    if (cv3_pair_) ask(cv3_pair_->residual_node_, ConvOperand::kResidual);
+    return ok;
 }
 
 }  // namespace SimpleInfer

@@ -24,6 +24,7 @@
 #include "layer.h"
 #include "layer_util.h"
 #include "si_hip.h"
+#include "view_rule.h"
 
 namespace SimpleInfer {
 
@@ -49,6 +50,7 @@ public:
 
     virtual const char* KernelName() const override;
     virtual bool HalfStorageOk(std::string& why) const override;
+    virtual bool TakesView(const TensorNode* node, int ld, int off) const override;
     virtual void ExtraReads(std::vector<TensorNode*>& nodes) const override {
         if (residual_node_) nodes.push_back(residual_node_);
         if (up_node_) nodes.push_back(up_node_);

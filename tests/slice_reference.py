@@ -108,6 +108,19 @@ def grouped_conv2d_ref(x, w, bias, stride, padding, dilation, groups):
     return np.concatenate(ys, axis=3)
 
 
+def maxpool2d_ref(x, k, s, p):
+    """nn.MaxPool2d on an NHWC array (dilation 1, floor mode): the padding never wins"""
+    n, h, w, c = x.shape
+    xp = np.full((n, h + 2 * p[0], w + 2 * p[1], c), -np.inf, np.float64)
+    xp[:, p[0]:p[0] + h, p[1]:p[1] + w] = x
+    oh, ow = (h + 2 * p[0] - k[0]) // s[0] + 1, (w + 2 * p[1] - k[1]) // s[1] + 1
+    y = np.full((n, oh, ow, c), -np.inf, np.float64)
+    for dy in range(k[0]):
+        for dx in range(k[1]):
+            y = np.maximum(y, xp[:, dy:dy + (oh - 1) * s[0] + 1:s[0], dx:dx + (ow - 1) * s[1] + 1:s[1]])
+    return y
+
+
 def eval_graph(builder, x_nhwc, rnd=None):
     """fp64 evaluation of a PnnxBuilder graph (NHWC tensors; [N, F] behind a flatten).  rnd: applied to the input, every conv / linear weight
     and bias and every layer's output except the graph outputs (None: exact) -- the fp16-storage emulation.  Returns the graph output, or the
@@ -141,8 +154,17 @@ def eval_graph(builder, x_nhwc, rnd=None):
         elif typ == "torch.cat":
             y = np.concatenate([vals[i] for i in ins], axis=nhwc_axis(int(prm["dim"]), x.ndim))
         elif typ == "pnnx.Expression":
-            assert prm["expr"] == "add(@0,@1)"
-            y = vals[ins[0]] + vals[ins[1]]
+            assert prm["expr"] in ("add(@0,@1)", "mul(@0,@1)"), prm["expr"]
+            y = vals[ins[0]] + vals[ins[1]] if prm["expr"].startswith("add") else vals[ins[0]] * vals[ins[1]]   # (numpy broadcasts [N,1,1,C])
+        elif typ == "nn.Hardsigmoid":
+            y = np.clip(x + 3.0, 0.0, 6.0) / 6.0
+        elif typ == "nn.MaxPool2d":
+            y = maxpool2d_ref(x, _ints(prm["kernel_size"]), _ints(prm["stride"]), _ints(prm["padding"]))
+        elif typ == "nn.Upsample":
+            assert prm["mode"] == "nearest" and prm["size"] == "None", prm
+            sh, sw = (float(v) for v in prm["scale_factor"].strip("()").split(","))
+            assert sh == int(sh) and sw == int(sw), prm    # (whole factors: torch's nearest index rule is then a repeat)
+            y = np.repeat(np.repeat(x, int(sh), axis=1), int(sw), axis=2)
         elif typ == "nn.AdaptiveAvgPool2d":
             assert _ints(prm["output_size"]) == (1, 1)
             y = x.mean(axis=(1, 2), keepdims=True)
