@@ -1,5 +1,5 @@
 // activation_param.hip -- clamp / softplus / mish (include/si_act.h) on fp32 and fp16 [pixels, c] tensors with pixel strides on both sides.
-// Arithmetic, special values, the arms and the refusals: the header.  The model is activation_kernel of ops.hip / ops_f16.hip: one lane per
+// Arithmetic, special values, the arms and the refusals: the header.  The model is activation_kernel of ops.hip: one lane per
 // 16-byte channel vector (or single element), consecutive lanes on consecutive addresses, a grid-stride loop under si_grid_for.  What
 // differs: the operator is a template parameter, so a lane runs straight-line code of one operator, and the two parameters are kernel
 // arguments.  Element offsets are 32-bit: the host refuses tensors whose offsets do not fit 31 bits, and an item index plus one grid
@@ -46,38 +46,6 @@ __device__ __forceinline__ float pa_apply(float x, float p0, float p1) {
     }
 }
 
-template <typename T, int VW>
-__device__ __forceinline__ void pa_load(const T* p, float (&v)[VW]) {
-    if constexpr (VW == 1) {
-        v[0] = (float)*p;
-    } else if constexpr (sizeof(T) == 4) {
-        const f32x4 r = *reinterpret_cast<const f32x4*>(p);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = r[i];
-    } else {
-        const f16x8 r = *reinterpret_cast<const f16x8*>(p);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = (float)r[i];
-    }
-}
-
-template <typename T, int VW>
-__device__ __forceinline__ void pa_store(T* p, const float (&v)[VW]) {
-    if constexpr (VW == 1) {
-        *p = si_store_cast<T>(v[0]);
-    } else if constexpr (sizeof(T) == 4) {
-        f32x4 r;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) r[i] = v[i];
-        *reinterpret_cast<f32x4*>(p) = r;
-    } else {
-        f16x8 r;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) r[i] = si_store_cast<_Float16>(v[i]);
-        *reinterpret_cast<f16x8*>(p) = r;
-    }
-}
-
 // items = pixels * cv, cv = items (vectors of VW elements, or elements) per pixel; in_ld / out_ld in elements
 template <int OP, typename T, int VW>
 __global__ __launch_bounds__(PA_THREADS) void param_act_kernel(float p0, float p1, const T* __restrict__ in, unsigned items, unsigned cv,
@@ -87,16 +55,14 @@ __global__ __launch_bounds__(PA_THREADS) void param_act_kernel(float p0, float p
         const unsigned p = i / cv;
         const unsigned ch = (i - p * cv) * VW;
         float v[VW];
-        pa_load<T, VW>(in + (p * in_ld + ch), v);
+        si_load_vec<T, VW>(in + (p * in_ld + ch), v);
 #pragma unroll
         for (int e = 0; e < VW; ++e) v[e] = pa_apply<OP>(v[e], p0, p1);
-        pa_store<T, VW>(out + (p * out_ld + ch), v);
+        si_store_vec<T, VW>(out + (p * out_ld + ch), v);
     }
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // everything that can be decided without a device or a pointer: SI_E_BADARG / SI_E_UNSUPPORTED / 0
 int check_desc(const SiParamActDesc* d) {
     if (!d) return SI_E_BADARG;
@@ -117,18 +83,10 @@ int check_desc(const SiParamActDesc* d) {
     return 0;
 }
 
-// do the two views share an element?  Two channel windows of one pixel grid (a common stride) that do not meet inside a pixel do not.
+// do the two views share an element?  (the strided-window rule of si_views.h)
 bool views_overlap(const SiParamActDesc* d, const void* in, const void* out, size_t esize) {
-    const uintptr_t ib = reinterpret_cast<uintptr_t>(in), ob = reinterpret_cast<uintptr_t>(out);
-    const uintptr_t ie = ib + (uintptr_t)((((uint64_t)d->pixels - 1) * (uint64_t)d->in_ld + (uint64_t)d->c) * esize);
-    const uintptr_t oe = ob + (uintptr_t)((((uint64_t)d->pixels - 1) * (uint64_t)d->out_ld + (uint64_t)d->c) * esize);
-    if (ie <= ob || oe <= ib) return false;
-    if (d->in_ld == d->out_ld) {
-        const uint64_t pitch = (uint64_t)d->in_ld * esize;
-        const uint64_t m = ob >= ib ? (uint64_t)(ob - ib) % pitch : (pitch - (uint64_t)(ib - ob) % pitch) % pitch;   // out's window inside in's period
-        if (m >= (uint64_t)d->c * esize && m + (uint64_t)d->c * esize <= pitch) return false;
-    }
-    return true;
+    return si_strided_windows_overlap(in, (uint64_t)d->pixels, (uint64_t)d->in_ld, (uint64_t)d->c, out, (uint64_t)d->pixels, (uint64_t)d->out_ld,
+                                      (uint64_t)d->c, esize);
 }
 
 enum Arm { kDense, kVector, kElement };
@@ -136,7 +94,7 @@ enum Arm { kDense, kVector, kElement };
 template <typename T>
 Arm arm_of(const SiParamActDesc* d, const void* in, const void* out) {
     const int full = (int)(16 / sizeof(T));
-    if (!aligned16(in) || !aligned16(out)) return kElement;
+    if (!si_aligned_to(in, 16) || !si_aligned_to(out, 16)) return kElement;
     // a dense tensor is one long row: lets odd channel counts (e.g. 3) still take the 16-byte path
     if (d->in_ld == d->c && d->out_ld == d->c && (d->pixels * (size_t)d->c) % (size_t)full == 0) return kDense;
     return (d->c % full == 0 && d->in_ld % full == 0 && d->out_ld % full == 0) ? kVector : kElement;

@@ -291,13 +291,11 @@ int check_desc(const SiAttentionDesc* d) {
 int check_ptrs(const SiAttentionDesc* d, const void* q, const void* k, const void* v, const void* o, bool half) {
     if (!q || !k || !v || !o) return SI_E_BADARG;
     const size_t es = half ? 2 : 4;
-    const uintptr_t ob = reinterpret_cast<uintptr_t>(o), oe = ob + view_extent(d, d->o_sb, d->o_ss, d->lq) * es;
+    const uint64_t o_bytes = view_extent(d, d->o_sb, d->o_ss, d->lq) * es;
     const void* const in[3] = {q, k, v};
     const long long sb[3] = {d->q_sb, d->k_sb, d->v_sb}, ss[3] = {d->q_ss, d->k_ss, d->v_ss};
-    for (int i = 0; i < 3; ++i) {
-        const uintptr_t ib = reinterpret_cast<uintptr_t>(in[i]), ie = ib + view_extent(d, sb[i], ss[i], i == 0 ? d->lq : d->lk) * es;
-        if (ib < oe && ob < ie) return SI_E_BADARG;
-    }
+    for (int i = 0; i < 3; ++i)
+        if (si_ranges_overlap(in[i], view_extent(d, sb[i], ss[i], i == 0 ? d->lq : d->lk) * es, o, o_bytes)) return SI_E_BADARG;
     if (half) {
         if (d->d % 8 != 0) return SI_E_UNSUPPORTED;
         const long long st[8] = {d->q_sb, d->q_ss, d->k_sb, d->k_ss, d->v_sb, d->v_ss, d->o_sb, d->o_ss};

@@ -53,29 +53,7 @@ __device__ __forceinline__ float bc_round(float v) {
     else return v;
 }
 
-template <typename T, int VW>
-__device__ __forceinline__ void bc_load(const T* p, float (&v)[VW]) {
-    if constexpr (VW == 1) {
-        v[0] = (float)p[0];
-    } else {
-        const si_vec<T, VW> w = *reinterpret_cast<const si_vec<T, VW>*>(p);
-#pragma unroll
-        for (int j = 0; j < VW; ++j) v[j] = (float)w[j];
-    }
-}
-
-// v holds values that are already exactly representable in T
-template <typename T, int VW>
-__device__ __forceinline__ void bc_store(T* p, const float (&v)[VW]) {
-    if constexpr (VW == 1) {
-        p[0] = (T)v[0];
-    } else {
-        si_vec<T, VW> w;
-#pragma unroll
-        for (int j = 0; j < VW; ++j) w[j] = (T)v[j];
-        *reinterpret_cast<si_vec<T, VW>*>(p) = w;
-    }
-}
+// (the stores below are si_store_vec<T, VW, /*exact=*/true>: bc_round already rounded every stage to T, so a plain cast stores it)
 
 // One stage on a lane's piece.  The formulas are those of ops.hip's binary_apply: IEEE division, the library's powf / atan2f.  The code is
 // chosen once per piece, not per element: it is uniform over the launch, and a switch inside the element loop costs a chain of scalar
@@ -119,23 +97,23 @@ __global__ __launch_bounds__(kThreads) void binary_const_kernel(BcArgs a) {
         const int e0 = piece * VW;   // first element of this lane's piece
         float k0[VW], k1[VW];
         if (VW > 1 && a.cvec[0]) {
-            bc_load<T, VW>(c0 + e0, k0);
+            si_load_vec<T, VW>(c0 + e0, k0);
         } else {
 #pragma unroll
             for (int j = 0; j < VW; ++j) k0[j] = (float)c0[(e0 + j) * a.cs[0][3]];
         }
         if (two && VW > 1 && a.cvec[1]) {
-            bc_load<T, VW>(c1 + e0, k1);
+            si_load_vec<T, VW>(c1 + e0, k1);
         } else {
 #pragma unroll
             for (int j = 0; j < VW; ++j) k1[j] = two ? (float)c1[(e0 + j) * a.cs[1][3]] : 0.0f;
         }
         for (unsigned p = (unsigned)p0; p < a.pixels; p += a.pixel_step) {
             float v[VW];
-            bc_load<T, VW>(x + p * (unsigned)a.x_ld + e0, v);
+            si_load_vec<T, VW>(x + p * (unsigned)a.x_ld + e0, v);
             bc_stage<T, VW>(a.op[0], v, k0);
             if (two) bc_stage<T, VW>(a.op[1], v, k1);
-            bc_store<T, VW>(out + p * (unsigned)a.out_ld + e0, v);
+            si_store_vec<T, VW, /*exact=*/true>(out + p * (unsigned)a.out_ld + e0, v);
         }
     } else {
         const unsigned step = gridDim.x * (unsigned)kThreads;
@@ -146,7 +124,7 @@ __global__ __launch_bounds__(kThreads) void binary_const_kernel(BcArgs a) {
             const int t = si_fast_divmod(p, a.d2, a.m_d2, i2);
             const int i0 = si_fast_divmod(t, a.d1, a.m_d1, i1);
             float v[VW];
-            bc_load<T, VW>(x + (unsigned)p * (unsigned)a.x_ld + e0, v);
+            si_load_vec<T, VW>(x + (unsigned)p * (unsigned)a.x_ld + e0, v);
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
                 if (s == 1 && !two) break;
@@ -158,7 +136,7 @@ __global__ __launch_bounds__(kThreads) void binary_const_kernel(BcArgs a) {
                     for (int j = 0; j < VW; ++j) k[j] = ks;
                 } else {
                     if (VW > 1 && a.cvec[s]) {
-                        bc_load<T, VW>(c + e0, k);
+                        si_load_vec<T, VW>(c + e0, k);
                     } else {
 #pragma unroll
                         for (int j = 0; j < VW; ++j) k[j] = (float)c[(e0 + j) * a.cs[s][3]];
@@ -166,7 +144,7 @@ __global__ __launch_bounds__(kThreads) void binary_const_kernel(BcArgs a) {
                 }
                 bc_stage<T, VW>(a.op[s], v, k);
             }
-            bc_store<T, VW>(out + (unsigned)p * (unsigned)a.out_ld + e0, v);
+            si_store_vec<T, VW, /*exact=*/true>(out + (unsigned)p * (unsigned)a.out_ld + e0, v);
         }
     }
 }

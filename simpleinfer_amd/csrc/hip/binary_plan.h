@@ -6,6 +6,7 @@
 #include <cstdint>
 
 #include "si_binary.h"
+#include "si_views.h"
 
 // ---- the BinaryOp codes of pnnx's expression lowering (0 add, 1 sub, 2 mul, 3 div, 6 pow, 10 atan2; 7, 8, 9, 11 their operand-reversed
 // forms).  One table for every kernel file that serves them.
@@ -41,8 +42,6 @@ struct Plan {
     unsigned pixel_step = 0;     // chan form: lanes / cv, the pixels between two passes of a lane
 };
 
-inline bool Aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 inline const int* Strides(const SiBinaryDesc* d, int stage) { return stage == 0 ? d->c0_stride : d->c1_stride; }
 
 // everything that can be decided without a device: SI_E_BADARG / SI_E_UNSUPPORTED / 0.  elem: bytes of an element (4 or 2).
@@ -75,7 +74,7 @@ inline int MakePlan(const SiBinaryDesc* d, const void* x, const void* c0, const 
         if (!si_binary_op_known(d->op[s])) return SI_E_UNSUPPORTED;
 
     const int full = 16 / elem;
-    const bool vec = d->d[3] % full == 0 && d->x_ld % full == 0 && d->out_ld % full == 0 && Aligned16(x) && Aligned16(out);
+    const bool vec = d->d[3] % full == 0 && d->x_ld % full == 0 && d->out_ld % full == 0 && si_aligned_to(x, 16) && si_aligned_to(out, 16);
     p.vw = vec ? full : 1;
     p.cv = d->d[3] / p.vw;
     p.pixels = (unsigned)pixels;
@@ -90,7 +89,7 @@ inline int MakePlan(const SiBinaryDesc* d, const void* x, const void* c0, const 
         chan = chan && cs[0] == 0 && cs[1] == 0 && cs[2] == 0;
         pixel = pixel && cs[3] == 0;
         const void* c = s == 0 ? c0 : c1;
-        p.cvec[s] = p.vw > 1 && cs[3] == 1 && cs[0] % p.vw == 0 && cs[1] % p.vw == 0 && cs[2] % p.vw == 0 && Aligned16(c);
+        p.cvec[s] = p.vw > 1 && cs[3] == 1 && cs[0] % p.vw == 0 && cs[1] % p.vw == 0 && cs[2] % p.vw == 0 && si_aligned_to(c, 16);
     }
     // a lane of the chan form keeps its place in the run: the run has to fit the grid once (it does unless grid_cap is tiny)
     const unsigned threads = p.blocks * (unsigned)kThreads;

@@ -299,19 +299,14 @@ int check_desc(const SiConv1dDesc* d, bool half) {
     return 0;
 }
 
-bool overlap(const void* a, uint64_t a_bytes, const void* b, uint64_t b_bytes) {
-    const uintptr_t ab = reinterpret_cast<uintptr_t>(a), bb = reinterpret_cast<uintptr_t>(b);
-    return ab < bb + b_bytes && bb < ab + a_bytes;
-}
-
 int check_ptrs(const SiConv1dDesc* d, const void* x, const void* w, const float* bias, const void* y, bool half) {
     if (!x || !w || !y) return SI_E_BADARG;
     const uint64_t es = half ? 2 : 4;
     const uint64_t y_bytes = plan::ViewExtent(d->n, d->oc, d->y_sn, d->y_sc, d->lo) * es;
     const uint64_t x_bytes = plan::ViewExtent(d->n, d->c, d->x_sn, d->x_sc, d->l) * es;
-    if (overlap(y, y_bytes, x, x_bytes)) return SI_E_BADARG;
-    if (overlap(y, y_bytes, w, plan::WeightElems(filter_of(d), half) * es)) return SI_E_BADARG;
-    if (bias && overlap(y, y_bytes, bias, (uint64_t)d->oc * 4)) return SI_E_BADARG;
+    if (si_ranges_overlap(y, y_bytes, x, x_bytes)) return SI_E_BADARG;
+    if (si_ranges_overlap(y, y_bytes, w, plan::WeightElems(filter_of(d), half) * es)) return SI_E_BADARG;
+    if (bias && si_ranges_overlap(y, y_bytes, bias, (uint64_t)d->oc * 4)) return SI_E_BADARG;
     if (half && plan::FormOf(shape_of(d)) == plan::kDense && !si_aligned_to(w, 16)) return SI_E_UNSUPPORTED;
     if (!si_aligned_to(x, es) || !si_aligned_to(y, es) || !si_aligned_to(w, es)) return SI_E_UNSUPPORTED;
     return 0;

@@ -204,7 +204,7 @@ static int dw_cols_form(const SiConv2dDesc* d) {
 const char* si_conv_depthwise_name(const SiConv2dDesc* d, const float* in) {
     static const char* cols[4] = {"conv_depthwise_cols_kernel<4, 3, 1>", "conv_depthwise_cols_kernel<4, 3, 2>",
                                   "conv_depthwise_cols_kernel<4, 5, 1>", "conv_depthwise_cols_kernel<4, 5, 2>"};
-    const bool vec = dw_vec_strides(d) && (reinterpret_cast<uintptr_t>(in) & 15) == 0;
+    const bool vec = dw_vec_strides(d) && si_aligned_to(in, 16);
     if (!vec) return "conv_depthwise_kernel<false, 4>";
     const int f = dw_cols_form(d);
     return f >= 0 ? cols[f] : "conv_depthwise_kernel<true, 4>";

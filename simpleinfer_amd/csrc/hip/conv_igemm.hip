@@ -1035,7 +1035,7 @@ static int conv_icg_pad(const SiConv2dDesc* d) {
 
 static bool conv_fast_ok(const SiConv2dDesc* d, const float* in) {
     const int icg = d->ic / d->groups;
-    if (conv_icg_pad(d) % 32 != 0 || d->in_ld % 4 != 0 || (reinterpret_cast<uintptr_t>(in) & 15) != 0) return false;
+    if (conv_icg_pad(d) % 32 != 0 || d->in_ld % 4 != 0 || !si_aligned_to(in, 16)) return false;
     if (d->kh * d->kw > 64) return false;
     const unsigned long long in_bytes = (unsigned long long)d->n * d->ih * d->iw * d->in_ld * 4ull;
     const unsigned long long w_bytes = (unsigned long long)d->oc * d->kh * d->kw * conv_icg_pad(d) * 4ull;
@@ -1044,7 +1044,7 @@ static bool conv_fast_ok(const SiConv2dDesc* d, const float* in) {
 
 static bool conv_vec_a(const SiConv2dDesc* d, const float* in) {
     const int icg = d->ic / d->groups;
-    return (icg % 4 == 0) && (d->in_ld % 4 == 0) && ((reinterpret_cast<uintptr_t>(in) & 15) == 0);
+    return (icg % 4 == 0) && (d->in_ld % 4 == 0) && si_aligned_to(in, 16);
 }
 
 extern "C" size_t si_hip_conv2d_weight_elems(const SiConv2dDesc* d) {
@@ -1178,7 +1178,7 @@ static int conv2d_dispatch(const SiConv2dDesc* d, const float* in, const float* 
     a.up = nullptr; a.up_ih = a.up_iw = a.up_ld = a.up_cb0 = a.up_cb1 = 0; a.up_inv_h = a.up_inv_w = 0.f; a.up_bytes = 0;
     if (up) {
         // channels [c0, c0 + c) of this 1x1 conv's input are nn.Upsample(nearest) of up->src: read them at the source
-        if (!up->src || yolo || !conv_upcat_shape_ok(d, up) || (reinterpret_cast<uintptr_t>(up->src) & 15) != 0 || !conv_fast_ok(d, in))
+        if (!up->src || yolo || !conv_upcat_shape_ok(d, up) || !si_aligned_to(up->src, 16) || !conv_fast_ok(d, in))
             return SI_E_UNSUPPORTED;
         const unsigned long long ub = (unsigned long long)d->n * up->ih * up->iw * up->ld * 4ull;
         a.up = up->src; a.up_ih = up->ih; a.up_iw = up->iw; a.up_ld = up->ld; a.up_cb0 = up->c0 / 32; a.up_cb1 = (up->c0 + up->c) / 32;

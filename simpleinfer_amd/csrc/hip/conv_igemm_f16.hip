@@ -1199,7 +1199,7 @@ int dispatch_h(const SiConv2dDesc* d, const void* in, const void* w_packed, cons
     if (d->has_residual && !residual) return SI_E_BADARG;
     if (!f16_shape_ok(d)) return SI_E_UNSUPPORTED;
     if (d->plan && d->plan->f16_tile >= 0 && !f16_variant_valid(d->plan->f16_tile)) return SI_E_BADARG;   // an unknown or retired tile id
-    if (d->in_ld % 8 != 0 || (reinterpret_cast<uintptr_t>(in) & 15) != 0) return SI_E_UNSUPPORTED;
+    if (d->in_ld % 8 != 0 || !si_aligned_to(in, 16)) return SI_E_UNSUPPORTED;
     if ((long long)d->n * d->oh * d->ow > 0x7fffffffLL) return SI_E_UNSUPPORTED;
     const unsigned long long in_bytes = (unsigned long long)d->n * d->ih * d->iw * d->in_ld * 2ull;
     const unsigned long long w_bytes = (unsigned long long)(f16_row_elems(d) + f16_lane_elems(d)) * 2ull;
@@ -1240,7 +1240,7 @@ int dispatch_h(const SiConv2dDesc* d, const void* in, const void* w_packed, cons
     a.up = nullptr; a.up_ih = a.up_iw = a.up_ld = a.up_cb0 = a.up_cb1 = 0; a.up_inv_h = a.up_inv_w = 0.f; a.up_bytes = 0;
     if (up) {
         // channels [c0, c0 + c) of this 1x1 conv's input are nn.Upsample(nearest) of up->src: read them at the source
-        if (!up->src || yolo || !f16_upcat_shape_ok(d, up) || (reinterpret_cast<uintptr_t>(up->src) & 15) != 0) return SI_E_UNSUPPORTED;
+        if (!up->src || yolo || !f16_upcat_shape_ok(d, up) || !si_aligned_to(up->src, 16)) return SI_E_UNSUPPORTED;
         const int blk = f16_block(d);
         a.up = reinterpret_cast<const half_t*>(up->src);
         a.up_ih = up->ih; a.up_iw = up->iw; a.up_ld = up->ld; a.up_cb0 = up->c0 / blk; a.up_cb1 = (up->c0 + up->c) / blk;
@@ -1268,8 +1268,8 @@ int dispatch_h(const SiConv2dDesc* d, const void* in, const void* w_packed, cons
     if (!up && !yolo && !split && !out_f32 && s2c32_on(d) && f16_forced_variant(d) < 0 && s2c32_shape_ok(d) && a.out_bytes != 0 &&
         (!d->has_residual || (reinterpret_cast<uintptr_t>(residual) & 1) == 0))
         return launch_s2c32(a, d, s);
-    if (!up && !yolo && !split && !out_f32 && f16_forced_variant(d) < 0 && si_conv_slab_f16_ok(d) && (reinterpret_cast<uintptr_t>(out) & 15) == 0 &&
-        (!d->has_bias || (reinterpret_cast<uintptr_t>(bias) & 15) == 0) && (!d->has_residual || (reinterpret_cast<uintptr_t>(residual) & 7) == 0))
+    if (!up && !yolo && !split && !out_f32 && f16_forced_variant(d) < 0 && si_conv_slab_f16_ok(d) && si_aligned_to(out, 16) &&
+        (!d->has_bias || si_aligned_to(bias, 16)) && (!d->has_residual || (reinterpret_cast<uintptr_t>(residual) & 7) == 0))
         return si_conv_slab_f16_launch(d, in, a.wl, a.wl_nb, a.wl_ks, bias, residual, out, s);
 
     const int v = up ? 0 : f16_variant(d);   // (the dual-source form lives in the one-stage 64x64 kernel)

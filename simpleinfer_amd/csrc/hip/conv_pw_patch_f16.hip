@@ -392,7 +392,7 @@ extern "C" int si_hip_conv2d_pw_cv3_f16(const SiConv2dDesc* pw, const SiConv2dDe
                                         const void* cv3_w_packed, const float* cv3_bias, void* out, si_stream_t stream) {
     if (!pw || !conv || !cv3 || !in || !pw_w_packed || !w_packed || !z || !cv3_w_packed || !out) return SI_E_BADARG;
     if ((pw->has_bias && !pw_bias) || (conv->has_bias && !bias) || (cv3->has_bias && !cv3_bias) || (conv->has_residual && !residual)) return SI_E_BADARG;
-    if (!cv3_ok(pw, conv, cv3) || z_ld % 8 != 0 || (reinterpret_cast<uintptr_t>(z) & 15) != 0 || (reinterpret_cast<uintptr_t>(cv3_w_packed) & 15) != 0) return SI_E_UNSUPPORTED;
+    if (!cv3_ok(pw, conv, cv3) || z_ld % 8 != 0 || !si_aligned_to(z, 16) || !si_aligned_to(cv3_w_packed, 16)) return SI_E_UNSUPPORTED;
     // (si_hip_conv2d_f16_pack_weight_host: the row-major image, then the lane-order one)
     const size_t cc = (size_t)conv->ic * conv->ic;
     const half_t* const wA = static_cast<const half_t*>(pw_w_packed) + cc;
@@ -405,7 +405,7 @@ static int pw_patch_launch(const SiConv2dDesc* pw, const SiConv2dDesc* d, const 
                            const float* bias, const void* residual, void* out, hipStream_t s, const SiConv2dDesc* c3, const void* z, int z_ld,
                            const void* w3, const float* bias3) {
     if (!si_conv_pw_patch_f16_ok(pw, d)) return SI_E_UNSUPPORTED;
-    if ((reinterpret_cast<uintptr_t>(in) & 15) != 0 || (d->has_residual && (reinterpret_cast<uintptr_t>(residual) & 1) != 0)) return SI_E_UNSUPPORTED;
+    if (!si_aligned_to(in, 16) || (d->has_residual && (reinterpret_cast<uintptr_t>(residual) & 1) != 0)) return SI_E_UNSUPPORTED;
     PwPatchArgs a;
     a.x = static_cast<const half_t*>(in);
     a.wlA = static_cast<const half_t*>(wlA);

@@ -760,9 +760,9 @@ extern "C" int si_hip_conv2d_pw_slab_f16(const SiConv2dDesc* pw, const SiConv2dD
     }
     SlabPlan p;
     if (!slab_shape_ok(conv) || !slab_plan(conv, &p, pw_tm(conv)) || !pw_pair_ok(pw, conv, p)) return SI_E_UNSUPPORTED;
-    const uintptr_t al = reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out) | (conv->has_bias ? reinterpret_cast<uintptr_t>(bias) : 0) |
-                         (pw->has_bias ? reinterpret_cast<uintptr_t>(pw_bias) : 0);
-    if ((al & 15) != 0 || (conv->has_residual && (reinterpret_cast<uintptr_t>(residual) & 7) != 0)) return SI_E_UNSUPPORTED;
+    const bool al = si_aligned_to(in, 16) && si_aligned_to(out, 16) && (!conv->has_bias || si_aligned_to(bias, 16)) &&
+                    (!pw->has_bias || si_aligned_to(pw_bias, 16));
+    if (!al || (conv->has_residual && (reinterpret_cast<uintptr_t>(residual) & 7) != 0)) return SI_E_UNSUPPORTED;
     const int c = conv->ic;
     // (si_hip_conv2d_f16_pack_weight_host: the row-major image, then the lane-order one)
     const half_t* const wA = static_cast<const half_t*>(pw_w_packed);

@@ -252,7 +252,7 @@ int launch_smallc(SmallCArgs a, hipStream_t s) {
     // one row buffer (padded so the weight image behind it is 16-byte aligned) + the weight image
     const size_t lds = ((size_t)a.n_in_rows * a.row_len + (size_t)a.kh * 2 * HP * a.ocp) * sizeof(float);
     if (lds > 160 * 1024) return SI_E_UNSUPPORTED;
-    const bool vec = a.in_ld == a.c && (a.iw * a.c) % 4 == 0 && (reinterpret_cast<uintptr_t>(a.in) & 15) == 0;
+    const bool vec = a.in_ld == a.c && (a.iw * a.c) % 4 == 0 && si_aligned_to(a.in, 16);
     auto kern = vec ? conv_smallc_rows_kernel<NW, NT, RB, HP, PF, OutT, true> : conv_smallc_rows_kernel<NW, NT, RB, HP, PF, OutT, false>;
     if (hipError_t e = si_allow_dynamic_lds(kern, lds); e != hipSuccess) return (int)e;
     // persistent grid: exactly the workgroups that are resident at once (registers or LDS, whichever binds)

@@ -601,7 +601,7 @@ static int split3_launch(const SiConv2dDesc* d, const float* in, const void* w_p
                          si_stream_t stream, const SiYoloLevel* yolo, const float* ygrid, const float* yanchor, int split_oc = 0, float* out2 = nullptr,
                          int out2_ld = 0, const SiConv2dUpsampledSource* up = nullptr) {
     if (!d || !in || !w_packed || !out) return SI_E_BADARG;
-    if (!split3_ok(d) || (reinterpret_cast<uintptr_t>(in) & 15) != 0) return SI_E_UNSUPPORTED;
+    if (!split3_ok(d) || !si_aligned_to(in, 16)) return SI_E_UNSUPPORTED;
     if ((d->has_bias && !bias) || (d->has_residual && !residual)) return SI_E_BADARG;
     const unsigned long long in_bytes = (unsigned long long)d->n * d->ih * d->iw * d->in_ld * 4ull;
     if (in_bytes >= 0xFFFFFF00ull || (long long)d->n * d->oh * d->ow > 0x7fffffffLL) return SI_E_UNSUPPORTED;
@@ -629,7 +629,7 @@ static int split3_launch(const SiConv2dDesc* d, const float* in, const void* w_p
     a.out2 = nullptr; a.out2_ld = 0; a.split = 0;
     a.up = nullptr; a.up_ih = a.up_iw = a.up_ld = a.up_cb0 = a.up_cb1 = 0; a.up_inv_h = a.up_inv_w = 0.0f; a.up_bytes = 0;
     if (up) {
-        if (yolo || !up->src || !split3_upcat_shape_ok(d, up) || (reinterpret_cast<uintptr_t>(up->src) & 15) != 0) return SI_E_UNSUPPORTED;
+        if (yolo || !up->src || !split3_upcat_shape_ok(d, up) || !si_aligned_to(up->src, 16)) return SI_E_UNSUPPORTED;
         a.up = up->src; a.up_ih = up->ih; a.up_iw = up->iw; a.up_ld = up->ld; a.up_cb0 = up->c0 / 64; a.up_cb1 = (up->c0 + up->c) / 64;
         a.up_inv_h = up->inv_scale_h; a.up_inv_w = up->inv_scale_w;
         a.up_bytes = (unsigned)((unsigned long long)d->n * up->ih * up->iw * up->ld * 4ull);

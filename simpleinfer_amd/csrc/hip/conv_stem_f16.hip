@@ -441,7 +441,7 @@ int launch_stem(StemArgs a, hipStream_t s) {
     a.items = (int)items;
     // rows (+ the dwords the odd-index fragments over-read, keeping the weights 16-byte aligned) + B fragments
     const size_t lds = ((size_t)a.n_in_rows * a.row_len + 8 + (size_t)((KH * GPR + 1) / 2) * 2 * 32 * NOT * 8) * sizeof(half_t);
-    const bool vec = a.in_ld == a.c && (a.iw * a.c) % 4 == 0 && (reinterpret_cast<uintptr_t>(a.in) & 15) == 0;
+    const bool vec = a.in_ld == a.c && (a.iw * a.c) % 4 == 0 && si_aligned_to(a.in, 16);
     // persistent grid: exactly the workgroups that are resident at once (a workgroup that has to wait for a slot would
     // start its share of the items when the others are finishing theirs)
     auto launch = [&](auto kern) {
@@ -467,7 +467,7 @@ int launch_stem_split(StemArgs a, hipStream_t s) {
     a.row_len = (3 + 31 * a.sw * a.c + 8 * GPR + 7) / 8 * 8;   // halves a wave stages per input row
     if (a.row_len > 4 * 64 || a.sh > 2 || a.kh < a.sh) return SI_E_UNSUPPORTED;
     // dense image rows on 16-byte boundaries (what Engine::Input hands over), offsets that fit the buffer descriptors
-    if (!(a.in_ld == a.c && (a.iw * a.c) % 4 == 0 && (reinterpret_cast<uintptr_t>(a.in) & 15) == 0)) return SI_E_UNSUPPORTED;
+    if (!(a.in_ld == a.c && (a.iw * a.c) % 4 == 0 && si_aligned_to(a.in, 16))) return SI_E_UNSUPPORTED;
     const unsigned long long out_bytes = ((unsigned long long)a.n * a.oh * a.ow - 1) * a.out_ld * 4ull + (unsigned long long)a.oc * 4ull;
     if (out_bytes > 0xFFFFFF00ull || (reinterpret_cast<uintptr_t>(a.out_f32) & 3) != 0) return SI_E_UNSUPPORTED;
     a.out_bytes = (unsigned)out_bytes;

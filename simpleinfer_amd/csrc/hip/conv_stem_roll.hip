@@ -469,8 +469,8 @@ static int stemroll_launch_t(const SiConv2dDesc* d, const float* in, const float
     a.in_bytes = (unsigned)in_bytes;
     // extent of the output as the kernel addresses it (the last pixel's row may be a view into a wider concat buffer: out_ld)
     const unsigned long long out_bytes = ((unsigned long long)d->n * d->oh * d->ow - 1ull) * d->out_ld * 4ull + (unsigned long long)d->oc * 4ull;
-    a.out_bytes = (out_bytes < 0xFFFFFF00ull && d->out_ld % 4 == 0 && d->oc % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0) ? (unsigned)out_bytes : 0u;
-    const bool vec = d->in_ld == 3 && (d->iw * 3) % 4 == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0;
+    a.out_bytes = (out_bytes < 0xFFFFFF00ull && d->out_ld % 4 == 0 && d->oc % 4 == 0 && si_aligned_to(out, 16)) ? (unsigned)out_bytes : 0u;
+    const bool vec = d->in_ld == 3 && (d->iw * 3) % 4 == 0 && si_aligned_to(in, 16);
     // the two stems of the path get their epilogue at compile time (YOLOv5: SiLU; ResNet: ReLU)
     const bool plain = !d->has_residual && d->act2 == SI_ACT_NONE && a.out_bytes != 0;
     if (s.kh == 6) {

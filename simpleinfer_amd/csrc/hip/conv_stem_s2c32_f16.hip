@@ -423,8 +423,7 @@ int si_hip_conv2d_stem_s2c32_f16(const SiConv2dDesc* stem, const SiConv2dDesc* c
     if (stem->has_bias && !stem_bias) return SI_E_BADARG;
     if (conv->has_bias && !conv_bias) return SI_E_BADARG;
     if (!si_hip_conv2d_stem_s2c32_f16_supported(stem, conv)) return SI_E_UNSUPPORTED;
-    if ((reinterpret_cast<uintptr_t>(in) & 15) != 0 || (reinterpret_cast<uintptr_t>(conv_w_packed) & 15) != 0 ||
-        (reinterpret_cast<uintptr_t>(stem_w_packed) & 15) != 0)
+    if (!si_aligned_to(in, 16) || !si_aligned_to(conv_w_packed, 16) || !si_aligned_to(stem_w_packed, 16))
         return SI_E_UNSUPPORTED;
     return fused_launch(stem, conv, nullptr, in, stem_w_packed, stem_bias, conv_w_packed, conv_bias, nullptr, nullptr, out, 0, nullptr, 0, stream);
 }
@@ -441,8 +440,7 @@ int si_hip_conv2d_stem_s2c32_pw_f16(const SiConv2dDesc* stem, const SiConv2dDesc
     if (!stem || !conv || !pw || !in || !stem_w_packed || !conv_w_packed || !pw_w_packed || !out || (split_oc && !out2)) return SI_E_BADARG;
     if ((stem->has_bias && !stem_bias) || (conv->has_bias && !conv_bias) || (pw->has_bias && !pw_bias)) return SI_E_BADARG;
     if (!si_hip_conv2d_stem_s2c32_pw_f16_supported(stem, conv, pw, split_oc)) return SI_E_UNSUPPORTED;
-    if (((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(conv_w_packed) | reinterpret_cast<uintptr_t>(stem_w_packed) |
-          reinterpret_cast<uintptr_t>(pw_w_packed)) & 15) != 0)
+    if (!si_aligned_to(in, 16) || !si_aligned_to(conv_w_packed, 16) || !si_aligned_to(stem_w_packed, 16) || !si_aligned_to(pw_w_packed, 16))
         return SI_E_UNSUPPORTED;
     return fused_launch(stem, conv, pw, in, stem_w_packed, stem_bias, conv_w_packed, conv_bias, pw_w_packed, pw_bias, out, split_oc, out2, out2_ld, stream);
 }

@@ -318,7 +318,7 @@ extern "C" int si_hip_conv_transpose2d_f32(const SiConvTranspose2dDesc* d, const
                                            si_stream_t stream) {
     if (const int rc = ct_check(d)) return rc;
     if (!in || !w_packed || !out || (d->has_bias && !bias)) return SI_E_BADARG;
-    if ((reinterpret_cast<uintptr_t>(w_packed) & 15) != 0) return SI_E_BADARG;
+    if (!si_aligned_to(w_packed, 16)) return SI_E_BADARG;
     CtArgs a{};
     a.in = in; a.w = w_packed; a.bias = d->has_bias ? bias : nullptr; a.out = out;
     a.n = d->n; a.ih = d->ih; a.iw = d->iw; a.ic = d->ic; a.icp = ct_icp(d); a.in_ld = d->in_ld;
@@ -344,7 +344,7 @@ extern "C" int si_hip_conv_transpose2d_f32(const SiConvTranspose2dDesc* d, const
     a.n_tiles = (a.ncols + CT_BN - 1) / CT_BN;
     const long long gx_blocks = (long long)((a.m_tiles + 7) / 8) * 8 * a.n_tiles;
     if (gx_blocks >= (1LL << 31) || phases > 65535) return SI_E_UNSUPPORTED;
-    const bool vec = d->ic % 4 == 0 && d->in_ld % 4 == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0;
+    const bool vec = d->ic % 4 == 0 && d->in_ld % 4 == 0 && si_aligned_to(in, 16);
     const dim3 grid((unsigned)gx_blocks, 1, (unsigned)phases);
     hipStream_t s = (hipStream_t)stream;
     if (one) {

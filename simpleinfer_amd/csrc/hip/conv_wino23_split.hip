@@ -521,11 +521,11 @@ extern "C" int si_hip_conv2d_wino23_split_f32(const SiConv2dDesc* d, const float
     if (!wino_split_ok(d)) return SI_E_UNSUPPORTED;
     if (d->has_bias && !bias) return SI_E_BADARG;
     if (d->has_residual && !residual) return SI_E_BADARG;
-    if (d->in_ld % 4 != 0 || (reinterpret_cast<uintptr_t>(in) & 15) != 0) return SI_E_UNSUPPORTED;
+    if (d->in_ld % 4 != 0 || !si_aligned_to(in, 16)) return SI_E_UNSUPPORTED;
     const unsigned long long in_bytes = (unsigned long long)d->n * d->ih * d->iw * d->in_ld * 4ull;
     if (in_bytes >= 0xFFFFFF00ull) return SI_E_UNSUPPORTED;
     if (16ull * d->ic * d->oc * 2ull >= 0x7FFFFF00ull) return SI_E_UNSUPPORTED;
-    if (d->has_bias && (reinterpret_cast<uintptr_t>(bias) & 15) != 0) return SI_E_UNSUPPORTED;
+    if (d->has_bias && !si_aligned_to(bias, 16)) return SI_E_UNSUPPORTED;
     if (d->oh != d->ih + 2 * d->pt - 2 || d->ow != d->iw + 2 * d->pl - 2) return SI_E_BADARG;
 
     WinoArgs a;
@@ -539,8 +539,8 @@ extern "C" int si_hip_conv2d_wino23_split_f32(const SiConv2dDesc* d, const float
     a.col_blocks = a.oc_blocks = a.spatial_blocks = 0;
     a.in_bytes = (unsigned)in_bytes;
     a.u_bytes = 0;
-    a.vec_out = (reinterpret_cast<uintptr_t>(out) & 15) == 0 && d->out_ld % 4 == 0 &&
-                (!d->has_residual || ((reinterpret_cast<uintptr_t>(residual) & 15) == 0 && d->res_ld % 4 == 0));
+    a.vec_out = si_aligned_to(out, 16) && d->out_ld % 4 == 0 &&
+                (!d->has_residual || (si_aligned_to(residual, 16) && d->res_ld % 4 == 0));
     a.act1 = d->act1; a.act2 = d->act2; a.act_param = d->act_param;
     a.range_flag = d->range_flag;
     hipStream_t s = static_cast<hipStream_t>(stream);

@@ -417,7 +417,7 @@ extern "C" int si_hip_conv2d_wino43_f32(const SiConv2dDesc* d, const float* in, 
     if (!si_hip_conv2d_wino43_eligible(d)) return SI_E_UNSUPPORTED;
     if (d->has_bias && !bias) return SI_E_BADARG;
     if (d->has_residual && !residual) return SI_E_BADARG;
-    if (d->in_ld % 4 != 0 || (reinterpret_cast<uintptr_t>(in) & 15) != 0) return SI_E_UNSUPPORTED;
+    if (d->in_ld % 4 != 0 || !si_aligned_to(in, 16)) return SI_E_UNSUPPORTED;
     const unsigned long long in_bytes = (unsigned long long)d->n * d->ih * d->iw * d->in_ld * 4ull;
     if (in_bytes >= 0xFFFFFF00ull) return SI_E_UNSUPPORTED;
     if (d->oh != d->ih + 2 * d->pt - 2 || d->ow != d->iw + 2 * d->pl - 2) return SI_E_BADARG;

@@ -317,21 +317,18 @@ int dc_check_ptrs(const SiDeformConv2dDesc* d, const void* x, const void* offset
     const uint64_t ipix = (uint64_t)d->n * d->ih * d->iw, opix = (uint64_t)d->n * d->oh * d->ow;
     const uint64_t taps = (uint64_t)d->kh * d->kw;
     auto extent = [](uint64_t pixels, uint64_t ld, uint64_t c) { return ((pixels - 1) * ld + c) * sizeof(float); };
-    const uintptr_t ob = reinterpret_cast<uintptr_t>(out), oe = ob + extent(opix, d->out_ld, d->oc);
+    const uint64_t out_bytes = extent(opix, d->out_ld, d->oc);
     const void* const in[3] = {x, offset, d->has_mask ? mask : nullptr};
     const uint64_t bytes[3] = {extent(ipix, d->in_ld, d->ic), extent(opix, d->off_ld, 2 * d->offset_groups * taps),
                                d->has_mask ? extent(opix, d->mask_ld, d->offset_groups * taps) : 0};
-    for (int i = 0; i < 3; ++i) {
-        if (!in[i]) continue;
-        const uintptr_t ib = reinterpret_cast<uintptr_t>(in[i]), ie = ib + bytes[i];
-        if (ib < oe && ob < ie) return SI_E_BADARG;
-    }
+    for (int i = 0; i < 3; ++i)
+        if (in[i] && si_ranges_overlap(in[i], bytes[i], out, out_bytes)) return SI_E_BADARG;
     return 0;
 }
 
 bool dc_vec(const SiDeformConv2dDesc* d, const void* x) {
     return d->ic % 4 == 0 && d->in_ld % 4 == 0 && (d->ic / d->groups) % 4 == 0 && (d->ic / d->offset_groups) % 4 == 0 &&
-           (reinterpret_cast<uintptr_t>(x) & 15) == 0;
+           si_aligned_to(x, 16);
 }
 
 }  // namespace
@@ -364,7 +361,7 @@ extern "C" int si_hip_deform_conv2d_f32(const SiDeformConv2dDesc* d, const float
     if (const int rc = dc_check(d)) return rc;
     if (const int rc = dc_check_ptrs(d, x, offset, mask, out)) return rc;
     if (!w_packed || (d->has_bias && !bias)) return SI_E_BADARG;
-    if ((reinterpret_cast<uintptr_t>(w_packed) & 15) != 0) return SI_E_BADARG;
+    if (!si_aligned_to(w_packed, 16)) return SI_E_BADARG;
     DcArgs a{};
     a.in = x; a.off = offset; a.mask = d->has_mask ? mask : nullptr; a.w = w_packed; a.bias = d->has_bias ? bias : nullptr; a.out = out;
     a.n = d->n; a.ih = d->ih; a.iw = d->iw; a.ic = d->ic; a.in_ld = d->in_ld;

@@ -115,15 +115,13 @@ plan::MaskShape mask_shape(const SiDetectMaskDesc* d) {
     return v;
 }
 
-bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 }  // namespace
 
 extern "C" {
 
 const char* si_hip_detect_masks_kernel_name(const SiDetectMaskDesc* d, const void* protos) {
-    if (!d || !protos || !aligned(protos, 4)) return "none";
-    switch (plan::MaskFormOf(mask_shape(d), aligned(protos, 16))) {
+    if (!d || !protos || !si_aligned_to(protos, 4)) return "none";
+    switch (plan::MaskFormOf(mask_shape(d), si_aligned_to(protos, 16))) {
         case plan::kMaskRegisters: return "detect_masks_kernel<32>";
         case plan::kMaskGeneric: return "detect_masks_kernel<0>";
         default: return "none";
@@ -133,14 +131,14 @@ const char* si_hip_detect_masks_kernel_name(const SiDetectMaskDesc* d, const voi
 int si_hip_detect_masks_f32(const SiDetectMaskDesc* d, const float* protos, const float* extras, const float* net_boxes, const int* counts,
                             unsigned char* masks, si_stream_t stream) {
     if (!d || !protos || !extras || !net_boxes || !counts || !masks) return SI_E_BADARG;
-    if (!aligned(protos, 4) || !aligned(extras, 4) || !aligned(net_boxes, 4) || !aligned(counts, 4)) return SI_E_BADARG;
+    if (!si_aligned_to(protos, 4) || !si_aligned_to(extras, 4) || !si_aligned_to(net_boxes, 4) || !si_aligned_to(counts, 4)) return SI_E_BADARG;
     const plan::MaskShape v = mask_shape(d);
     const int rc = plan::MaskStatusOf(v);
     if (rc != plan::kOk) return rc == plan::kBadArg ? SI_E_BADARG : SI_E_UNSUPPORTED;
     if (d->max_det == 0) return 0;
-    const plan::MaskForm form = plan::MaskFormOf(v, aligned(protos, 16));
+    const plan::MaskForm form = plan::MaskFormOf(v, si_aligned_to(protos, 16));
     MaskArgs a{protos, extras, net_boxes, counts, masks, d->mh, d->mw, d->nm, d->proto_ld, d->max_det, d->extra, d->coef_off,
-               d->ratio_w, d->ratio_h, plan::MaskWordStores(v, aligned(masks, 4)) ? 1 : 0};
+               d->ratio_w, d->ratio_h, plan::MaskWordStores(v, si_aligned_to(masks, 4)) ? 1 : 0};
     const int pixels = d->mh * d->mw;
     hipStream_t s = (hipStream_t)stream;
     if (form == plan::kMaskRegisters) {

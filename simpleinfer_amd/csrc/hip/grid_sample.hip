@@ -229,16 +229,6 @@ SiGridSampleDesc normalised(const SiGridSampleDesc* d) {
     return r;
 }
 
-// elements from the first to the last element of a view of `pixels` pixels of c channels, ld apart; 0: beyond the index limit
-uint64_t view_extent(uint64_t n, uint64_t h, uint64_t w, uint64_t ld, uint64_t c) {
-    const uint64_t rows = n * h;   // < 2^62
-    if (rows > SI_INDEX_LIMIT) return 0;
-    const uint64_t pixels = rows * w;
-    if (pixels > SI_INDEX_LIMIT) return 0;
-    const uint64_t e = (pixels - 1) * ld + c;
-    return e > SI_INDEX_LIMIT ? 0 : e;
-}
-
 uint64_t grid_extent(const SiGridSampleDesc& d) {
     if (d.grid_source == SI_GRID_THETA) return (uint64_t)d.n * 6;
     const uint64_t limit = SI_INDEX_LIMIT;
@@ -258,21 +248,16 @@ int check_desc(const SiGridSampleDesc& d) {
     if (d.grid_source == SI_GRID_TENSOR && (d.gs_n < 0 || d.gs_h < 0 || d.gs_w < 0 || d.gs_k < 0)) return SI_E_BADARG;
     if (d.mode == SI_GRID_BICUBIC || d.spatial_dims == 3) return SI_E_UNSUPPORTED;
     if (d.h > SIZE_LIMIT || d.w > SIZE_LIMIT || d.ho > SIZE_LIMIT || d.wo > SIZE_LIMIT) return SI_E_UNSUPPORTED;
-    if (!view_extent(d.n, d.h, d.w, d.in_ld, d.c) || !view_extent(d.n, d.ho, d.wo, d.out_ld, d.c) || !grid_extent(d)) return SI_E_UNSUPPORTED;
+    if (!si_view_extent(d.n, d.h, d.w, d.in_ld, d.c) || !si_view_extent(d.n, d.ho, d.wo, d.out_ld, d.c) || !grid_extent(d)) return SI_E_UNSUPPORTED;
     return 0;
-}
-
-bool intersects(const void* a, uint64_t a_bytes, const void* b, uint64_t b_bytes) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
 }
 
 int check_call(const SiGridSampleDesc& d, const void* x, const void* grid, const void* out, size_t es) {
     const int rc = check_desc(d);
     if (rc != 0) return rc;
     if (!x || !grid || !out) return SI_E_BADARG;
-    const uint64_t out_bytes = view_extent(d.n, d.ho, d.wo, d.out_ld, d.c) * es;
-    if (intersects(out, out_bytes, x, view_extent(d.n, d.h, d.w, d.in_ld, d.c) * es) || intersects(out, out_bytes, grid, grid_extent(d) * es))
+    const uint64_t out_bytes = si_view_extent(d.n, d.ho, d.wo, d.out_ld, d.c) * es;
+    if (si_ranges_overlap(out, out_bytes, x, si_view_extent(d.n, d.h, d.w, d.in_ld, d.c) * es) || si_ranges_overlap(out, out_bytes, grid, grid_extent(d) * es))
         return SI_E_BADARG;
     return 0;
 }
@@ -347,10 +332,10 @@ int check_affine(const SiAffineGridDesc* d, const void* theta, const void* out, 
     out_ld = d->out_ld == 0 ? d->h : d->out_ld;
     if (out_ld < d->h) return SI_E_BADARG;
     if (d->h > SIZE_LIMIT || d->w > SIZE_LIMIT) return SI_E_UNSUPPORTED;
-    const uint64_t extent = view_extent(d->n, d->w, 2, out_ld, d->h);
+    const uint64_t extent = si_view_extent(d->n, d->w, 2, out_ld, d->h);
     if (!extent || (uint64_t)d->n * 6 > SI_INDEX_LIMIT) return SI_E_UNSUPPORTED;
     if (!theta || !out) return SI_E_BADARG;
-    if (intersects(out, extent * es, theta, (uint64_t)d->n * 6 * es)) return SI_E_BADARG;
+    if (si_ranges_overlap(out, extent * es, theta, (uint64_t)d->n * 6 * es)) return SI_E_BADARG;
     return 0;
 }
 

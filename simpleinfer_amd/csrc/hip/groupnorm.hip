@@ -84,38 +84,6 @@ __device__ __forceinline__ GnTile gn_tile(const GnArgs<T>& a, int slice, int chu
     return t;
 }
 
-template <typename T, int VW>
-__device__ __forceinline__ void gn_load(const T* p, float (&v)[VW]) {
-    if constexpr (VW == 1) {
-        v[0] = (float)*p;
-    } else if constexpr (sizeof(T) == 4) {
-        const f32x4 r = *reinterpret_cast<const f32x4*>(p);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = r[i];
-    } else {
-        const f16x8 r = *reinterpret_cast<const f16x8*>(p);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = (float)r[i];
-    }
-}
-
-template <typename T, int VW>
-__device__ __forceinline__ void gn_store(T* p, const float (&v)[VW]) {
-    if constexpr (VW == 1) {
-        *p = si_store_cast<T>(v[0]);
-    } else if constexpr (sizeof(T) == 4) {
-        f32x4 r;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) r[i] = v[i];
-        *reinterpret_cast<f32x4*>(p) = r;
-    } else {
-        f16x8 r;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) r[i] = si_store_cast<_Float16>(v[i]);
-        *reinterpret_cast<f16x8*>(p) = r;
-    }
-}
-
 // Chan's formula: (na, ma, qa) <- (na, ma, qa) + (nb, mb, qb); an empty b changes nothing
 __device__ __forceinline__ void gn_merge(float& na, float& ma, float& qa, float nb, float mb, float qb) {
     if (nb > 0.0f) {
@@ -192,10 +160,10 @@ __device__ __forceinline__ void gn_tile_stats(const GnArgs<T>& a, const GnTile& 
 #pragma unroll 4
             for (int p = t.pl; p < t.npix; p += t.pl_n, src += step) {
                 float x[VW];
-                gn_load<T, VW>(src, x);
+                si_load_vec<T, VW>(src, x);
                 if constexpr (CACHE) {
                     if constexpr (VW == 1) cache[p * t.cvc + v] = *src;
-                    else gn_store<T, VW>(cache + (size_t)(p * t.cvc + v) * VW, x);   // (exact: x came from T)
+                    else si_store_vec<T, VW>(cache + (size_t)(p * t.cvc + v) * VW, x);   // (exact: x came from T)
                 }
                 k += 1.0f;
                 const float inv = k == 1.0f ? 1.0f : __builtin_amdgcn_rcpf(k);   // (1 ulp: the mean moves by delta * 2^-24 at most)
@@ -277,11 +245,11 @@ __device__ __forceinline__ void gn_tile_apply(const GnArgs<T>& a, const GnTile& 
         const size_t in_step = (size_t)t.pl_n * a.in_ld, out_step = (size_t)t.pl_n * a.out_ld;
         for (int p = t.pl; p < t.npix; p += t.pl_n, src += in_step, dst += out_step) {
             float x[VW], y[VW];
-            if constexpr (CACHE) gn_load<T, VW>(cache + (size_t)(p * t.cvc + v) * VW, x);
-            else gn_load<T, VW>(src, x);
+            if constexpr (CACHE) si_load_vec<T, VW>(cache + (size_t)(p * t.cvc + v) * VW, x);
+            else si_load_vec<T, VW>(src, x);
 #pragma unroll
             for (int i = 0; i < VW; ++i) y[i] = si_act(a.act, (x[i] - mu[i]) * sc[i] + be[i], a.act_param);
-            gn_store<T, VW>(dst, y);
+            si_store_vec<T, VW>(dst, y);
         }
     }
 }

@@ -688,7 +688,7 @@ int si_hip_letterbox_batch_u8_f32(const unsigned char* resized_bgr, int n, size_
     if ((height_resize > 0 && width_resize > 0) && !resized_bgr) return SI_E_BADARG;
     if ((long long)height_new * width_new * 3 > 0x7fffffffLL || n > 65535) return SI_E_UNSUPPORTED;
     if (n == 0) return 0;
-    if (((long long)height_new * width_new * 3) % 4 != 0 || (reinterpret_cast<uintptr_t>(out) & 15) != 0) {
+    if (((long long)height_new * width_new * 3) % 4 != 0 || !si_aligned_to(out, 16)) {
         for (int b = 0; b < n; ++b) {   // odd sizes: one launch per image
             const int rc = si_hip_letterbox_u8_f32(resized_bgr + (size_t)b * image_stride_bytes, height_resize, width_resize,
                                                    out + (size_t)b * height_new * width_new * 3, height_new, width_new, padding_t, padding_l, stream);

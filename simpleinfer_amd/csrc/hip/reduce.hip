@@ -57,38 +57,6 @@ struct RdArgs {
     int chunk, parts;    // col_coop: positions per part, non-empty parts
 };
 
-template <typename T, int VW>
-__device__ __forceinline__ void rd_load(const T* p, float (&v)[VW]) {
-    if constexpr (VW == 1) {
-        v[0] = (float)*p;
-    } else if constexpr (sizeof(T) == 4) {
-        const f32x4 r = *reinterpret_cast<const f32x4*>(p);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = r[i];
-    } else {
-        const f16x8 r = *reinterpret_cast<const f16x8*>(p);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = (float)r[i];
-    }
-}
-
-template <typename T, int VW>
-__device__ __forceinline__ void rd_store(T* p, const float (&v)[VW]) {
-    if constexpr (VW == 1) {
-        *p = si_store_cast<T>(v[0]);
-    } else if constexpr (sizeof(T) == 4) {
-        f32x4 r;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) r[i] = v[i];
-        *reinterpret_cast<f32x4*>(p) = r;
-    } else {
-        f16x8 r;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) r[i] = si_store_cast<_Float16>(v[i]);
-        *reinterpret_cast<f16x8*>(p) = r;
-    }
-}
-
 template <bool MAX>
 __device__ __forceinline__ float rd_identity() { return MAX ? -INFINITY : 0.0f; }
 
@@ -128,7 +96,7 @@ __device__ __forceinline__ void rd_row(const RdArgs& a, float* part) {
     if (live) {
         for (int item = j; item < a.cv; item += L) {
             float v[VW];
-            rd_load<T, VW>(in + item * VW, v);
+            si_load_vec<T, VW>(in + item * VW, v);
 #pragma unroll
             for (int e = 0; e < VW; ++e) acc = rd_combine<MAX>(acc, rd_prep<MAX>(a.op, v[e]));
         }
@@ -187,7 +155,7 @@ __device__ __forceinline__ void rd_walk(const RdArgs& a, const T* in, unsigned o
 #pragma unroll 4
     for (int r = start; r < end; ++r) {
         float v[VW];
-        rd_load<T, VW>(in + off, v);
+        si_load_vec<T, VW>(in + off, v);
 #pragma unroll
         for (int e = 0; e < VW; ++e) acc[e] = rd_combine<MAX>(acc[e], rd_prep<MAX>(a.op, v[e]));
         off += step;
@@ -210,7 +178,7 @@ __device__ __forceinline__ void rd_col_lane(const RdArgs& a) {
     rd_walk<T, VW, MAX>(a, static_cast<const T*>(a.in), in_off, 0, a.R, acc);
 #pragma unroll
     for (int e = 0; e < VW; ++e) acc[e] = rd_finish<MAX>(a, acc[e]);
-    rd_store<T, VW>(static_cast<T*>(a.out) + out_off, acc);
+    si_store_vec<T, VW>(static_cast<T*>(a.out) + out_off, acc);
 }
 
 template <typename T, int VW>
@@ -281,22 +249,13 @@ int check_desc(const SiReduceDesc* d) {
     return 0;
 }
 
-// do the two views share an element?  Two channel windows of one pixel grid (a common stride) that do not meet inside a pixel do not.
+// do the two views share an element?  (the strided-window rule of si_views.h)
 bool views_overlap(const SiReduceDesc* d, const void* in, const void* out, size_t esize) {
     const int oc = (d->axes & SI_REDUCE_AXIS_C) ? 1 : d->c;
     const uint64_t pix = (uint64_t)d->n * d->h * d->w;
     const uint64_t opix = (uint64_t)((d->axes & SI_REDUCE_AXIS_N) ? 1 : d->n) * (uint64_t)((d->axes & SI_REDUCE_AXIS_H) ? 1 : d->h) *
                           (uint64_t)((d->axes & SI_REDUCE_AXIS_W) ? 1 : d->w);
-    const uintptr_t ib = reinterpret_cast<uintptr_t>(in), ob = reinterpret_cast<uintptr_t>(out);
-    const uintptr_t ie = ib + (uintptr_t)(((pix - 1) * (uint64_t)d->in_ld + (uint64_t)d->c) * esize);
-    const uintptr_t oe = ob + (uintptr_t)(((opix - 1) * (uint64_t)d->out_ld + (uint64_t)oc) * esize);
-    if (ie <= ob || oe <= ib) return false;
-    if (d->in_ld == d->out_ld) {
-        const uint64_t pitch = (uint64_t)d->in_ld * esize;
-        const uint64_t m = ob >= ib ? (uint64_t)(ob - ib) % pitch : (pitch - (uint64_t)(ib - ob) % pitch) % pitch;   // out's window inside in's period
-        if (m >= (uint64_t)d->c * esize && m + (uint64_t)oc * esize <= pitch) return false;
-    }
-    return true;
+    return si_strided_windows_overlap(in, pix, (uint64_t)d->in_ld, (uint64_t)d->c, out, opix, (uint64_t)d->out_ld, (uint64_t)oc, esize);
 }
 
 enum Form { kRowGroup, kRowBlock, kColLane, kColCoop };

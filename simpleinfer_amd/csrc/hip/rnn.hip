@@ -257,11 +257,6 @@ int check_desc(const SiRnnDesc* d, bool half) {
     return 0;
 }
 
-bool overlap(const void* a, uint64_t a_bytes, const void* b, uint64_t b_bytes) {
-    const uintptr_t ab = reinterpret_cast<uintptr_t>(a), bb = reinterpret_cast<uintptr_t>(b);
-    return ab < bb + b_bytes && bb < ab + a_bytes;
-}
-
 // the pointers of the layer entries: null, overlap (SI_E_BADARG), the fp16 alignment rule (SI_E_UNSUPPORTED)
 int check_ptrs(const SiRnnDesc* d, const void* gates, const void* whh, const void* y, const float* c, const void* hn, const void* cn, bool half) {
     const bool lstm = d->cell == SI_RNN_LSTM;
@@ -271,11 +266,11 @@ int check_ptrs(const SiRnnDesc* d, const void* gates, const void* whh, const voi
     const uint64_t y_bytes = plan::ViewExtent(d->t, d->batch, d->y_st, d->y_sb, (long long)d->dirs * d->hidden) * es;
     const uint64_t g_bytes = plan::ViewExtent(d->t, d->batch, d->g_st, d->g_sb, (long long)d->dirs * G * d->hidden) * es;
     const uint64_t state = plan::StateElems(d->batch, d->hidden, d->dirs);
-    if (overlap(y, y_bytes, gates, g_bytes)) return SI_E_BADARG;
-    if (overlap(y, y_bytes, whh, plan::WhhImageElems(d->cell, d->hidden, d->dirs, half) * es)) return SI_E_BADARG;
-    if (lstm && overlap(y, y_bytes, c, state * 4)) return SI_E_BADARG;
-    if (hn && overlap(y, y_bytes, hn, state * es)) return SI_E_BADARG;
-    if (cn && overlap(y, y_bytes, cn, state * es)) return SI_E_BADARG;
+    if (si_ranges_overlap(y, y_bytes, gates, g_bytes)) return SI_E_BADARG;
+    if (si_ranges_overlap(y, y_bytes, whh, plan::WhhImageElems(d->cell, d->hidden, d->dirs, half) * es)) return SI_E_BADARG;
+    if (lstm && si_ranges_overlap(y, y_bytes, c, state * 4)) return SI_E_BADARG;
+    if (hn && si_ranges_overlap(y, y_bytes, hn, state * es)) return SI_E_BADARG;
+    if (cn && si_ranges_overlap(y, y_bytes, cn, state * es)) return SI_E_BADARG;
     if (half && (!si_aligned_to(gates, 16) || !si_aligned_to(whh, 16) || !si_aligned_to(y, 16) || (hn && !si_aligned_to(hn, 16)) ||
                  (cn && !si_aligned_to(cn, 16))))
         return SI_E_UNSUPPORTED;

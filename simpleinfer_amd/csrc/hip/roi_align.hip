@@ -179,39 +179,24 @@ SiRoiAlignDesc normalised(const SiRoiAlignDesc* d) {
     return r;
 }
 
-// elements from the first to the last element of a view of n h w pixels of c channels, ld apart; 0: beyond the index limit
-uint64_t view_extent(uint64_t n, uint64_t h, uint64_t w, uint64_t ld, uint64_t c) {
-    const uint64_t rows = n * h;   // < 2^62
-    if (rows > SI_INDEX_LIMIT) return 0;
-    const uint64_t pixels = rows * w;
-    if (pixels > SI_INDEX_LIMIT) return 0;
-    const uint64_t e = (pixels - 1) * ld + c;
-    return e > SI_INDEX_LIMIT ? 0 : e;
-}
-
 // everything that can be decided from the descriptor alone: SI_E_BADARG / SI_E_UNSUPPORTED / 0.  `d` is normalised.
 int check_desc(const SiRoiAlignDesc& d) {
     if (d.n <= 0 || d.c <= 0 || d.h <= 0 || d.w <= 0 || d.k <= 0 || d.ph <= 0 || d.pw <= 0) return SI_E_BADARG;
     if (d.in_ld < d.c || d.out_ld < d.c || d.rois_ld < 5) return SI_E_BADARG;
     if (d.h > SIZE_LIMIT || d.w > SIZE_LIMIT || d.ph > SIZE_LIMIT || d.pw > SIZE_LIMIT) return SI_E_UNSUPPORTED;
     if (d.sampling_ratio > SI_ROI_RATIO_LIMIT) return SI_E_UNSUPPORTED;
-    if (!view_extent(d.n, d.h, d.w, d.in_ld, d.c) || !view_extent(d.k, d.ph, d.pw, d.out_ld, d.c) || !view_extent(1, 1, d.k, d.rois_ld, 5))
+    if (!si_view_extent(d.n, d.h, d.w, d.in_ld, d.c) || !si_view_extent(d.k, d.ph, d.pw, d.out_ld, d.c) || !si_view_extent(1, 1, d.k, d.rois_ld, 5))
         return SI_E_UNSUPPORTED;
     return 0;
-}
-
-bool intersects(const void* a, uint64_t a_bytes, const void* b, uint64_t b_bytes) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
 }
 
 int check_call(const SiRoiAlignDesc& d, const void* x, const void* rois, const void* out, size_t es) {
     const int rc = check_desc(d);
     if (rc != 0) return rc;
     if (!x || !rois || !out) return SI_E_BADARG;
-    const uint64_t out_bytes = view_extent(d.k, d.ph, d.pw, d.out_ld, d.c) * es;
-    if (intersects(out, out_bytes, x, view_extent(d.n, d.h, d.w, d.in_ld, d.c) * es) ||
-        intersects(out, out_bytes, rois, view_extent(1, 1, d.k, d.rois_ld, 5) * sizeof(float)))
+    const uint64_t out_bytes = si_view_extent(d.k, d.ph, d.pw, d.out_ld, d.c) * es;
+    if (si_ranges_overlap(out, out_bytes, x, si_view_extent(d.n, d.h, d.w, d.in_ld, d.c) * es) ||
+        si_ranges_overlap(out, out_bytes, rois, si_view_extent(1, 1, d.k, d.rois_ld, 5) * sizeof(float)))
         return SI_E_BADARG;
     return 0;
 }

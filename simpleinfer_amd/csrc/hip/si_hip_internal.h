@@ -10,9 +10,11 @@
 
 #include "si_hip.h"
 #include "si_magic.h"
+#include "si_views.h"
 
 // ---- device commons: what every kernel file shares.  A kernel file defines no activation formula, no division helper (si_magic.h), no
-// vector typedef and no buffer flag of its own ("Device commons").
+// vector typedef, no buffer flag, no channel-vector load/store, and no alignment, extent or overlap helper (si_views.h) of its own
+// ("Device commons").
 
 // Vector types, under the names the kernels use
 typedef _Float16 half_t;
@@ -83,19 +85,7 @@ static inline hipError_t si_allow_dynamic_lds(Kern kern, size_t lds) {
     return e;
 }
 
-// ---- host-side preamble of the descriptor operators (pad2d, avgpool, softmax, reduce, ...) --------------------------------
-static inline bool si_aligned_to(const void* p, size_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
-
-// kernels index with 32-bit element offsets: a view whose last element lies beyond this is SI_E_UNSUPPORTED
-constexpr uint64_t SI_INDEX_LIMIT = 0x7fffffffull;
-
-// 16-byte channel vectors when c, both strides and both pointers allow it; single elements otherwise
-template <typename T>
-static inline int si_vector_width(int c, int in_ld, int out_ld, const void* in, const void* out) {
-    const int full = (int)(16 / sizeof(T));
-    const bool vec = c % full == 0 && in_ld % full == 0 && out_ld % full == 0 && si_aligned_to(in, 16) && si_aligned_to(out, 16);
-    return vec ? full : 1;
-}
+// (the host-side preamble of the descriptor operators -- alignment, vector width, extents, overlap: si_views.h)
 
 // fp32 -> storage type. For _Float16 the empty asm keeps the value opaque so the compiler cannot fold the multiply / add
 // that produced it into v_fma_mix{lo,hi}_f16 for some unrolled elements and not others: the fused form rounds once, the
@@ -104,6 +94,47 @@ template <typename T>
 __device__ __forceinline__ T si_store_cast(float v) {
     if constexpr (sizeof(T) == 2) asm("" : "+v"(v));
     return (T)v;
+}
+
+// One lane's piece of a pixel's channels as fp32: VW = 1 is a single element, otherwise a full 16-byte vector (f32x4 or f16x8) at a
+// 16-byte aligned address.  The store rounds through si_store_cast; EXACT marks values that are already exactly representable in T and
+// stores them with a plain cast, without the barrier (binary_const.hip: it rounds once per stage, before the store).
+template <typename T, int VW>
+__device__ __forceinline__ void si_load_vec(const T* p, float (&v)[VW]) {
+    static_assert(VW == 1 || VW == (int)(16 / sizeof(T)), "a single element or a full 16-byte vector");
+    if constexpr (VW == 1) {
+        v[0] = (float)*p;
+    } else if constexpr (sizeof(T) == 4) {
+        const f32x4 r = *reinterpret_cast<const f32x4*>(p);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = r[i];
+    } else {
+        const f16x8 r = *reinterpret_cast<const f16x8*>(p);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i] = (float)r[i];
+    }
+}
+
+template <typename T, int VW, bool EXACT = false>
+__device__ __forceinline__ void si_store_vec(T* p, const float (&v)[VW]) {
+    static_assert(VW == 1 || VW == (int)(16 / sizeof(T)), "a single element or a full 16-byte vector");
+    if constexpr (VW == 1) {
+        if constexpr (EXACT) *p = (T)v[0];
+        else *p = si_store_cast<T>(v[0]);
+    } else if constexpr (sizeof(T) == 4) {
+        f32x4 r;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) r[i] = v[i];
+        *reinterpret_cast<f32x4*>(p) = r;
+    } else {
+        f16x8 r;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            if constexpr (EXACT) r[i] = (_Float16)v[i];
+            else r[i] = si_store_cast<_Float16>(v[i]);
+        }
+        *reinterpret_cast<f16x8*>(p) = r;
+    }
 }
 
 // Lanes 2k and 2k+1 of a 32x32 MFMA C/D tile hold neighbouring channels of the same pixels.  The pair trades one value

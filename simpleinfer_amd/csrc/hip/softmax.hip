@@ -51,38 +51,6 @@ struct SmArgs {
     int items;         // strided forms: outer * inner * cv
 };
 
-template <typename T, int VW>
-__device__ __forceinline__ void sm_load(const T* p, float (&v)[VW]) {
-    if constexpr (VW == 1) {
-        v[0] = (float)*p;
-    } else if constexpr (sizeof(T) == 4) {
-        const f32x4 r = *reinterpret_cast<const f32x4*>(p);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = r[i];
-    } else {
-        const f16x8 r = *reinterpret_cast<const f16x8*>(p);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = (float)r[i];
-    }
-}
-
-template <typename T, int VW>
-__device__ __forceinline__ void sm_store(T* p, const float (&v)[VW]) {
-    if constexpr (VW == 1) {
-        *p = si_store_cast<T>(v[0]);
-    } else if constexpr (sizeof(T) == 4) {
-        f32x4 r;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) r[i] = v[i];
-        *reinterpret_cast<f32x4*>(p) = r;
-    } else {
-        f16x8 r;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) r[i] = si_store_cast<_Float16>(v[i]);
-        *reinterpret_cast<f16x8*>(p) = r;
-    }
-}
-
 // the reference point of a recurrence: its maximum, or 0 while that is still -inf
 __device__ __forceinline__ float sm_ref(float m) { return m == -INFINITY ? 0.0f : m; }
 
@@ -138,7 +106,7 @@ __device__ __forceinline__ void sm_row_in_registers(const SmArgs& a) {
     for (int i = 0; i < ITEMS; ++i) {
         const int item = i * L + j;
         if (live && item < a.cv) {
-            sm_load<T, VW>(in + item * VW, v[i]);
+            si_load_vec<T, VW>(in + item * VW, v[i]);
 #pragma unroll
             for (int e = 0; e < VW; ++e) m = fmaxf(m, v[i][e]);
         } else {
@@ -170,7 +138,7 @@ __device__ __forceinline__ void sm_row_in_registers(const SmArgs& a) {
         if (item < a.cv) {
 #pragma unroll
             for (int e = 0; e < VW; ++e) v[i][e] = sm_finish(a.log, v[i][e], k);
-            sm_store<T, VW>(out + item * VW, v[i]);
+            si_store_vec<T, VW>(out + item * VW, v[i]);
         }
     }
 }
@@ -190,7 +158,7 @@ __global__ __launch_bounds__(SM_THREADS) void softmax_block_online_kernel(SmArgs
     float m = -INFINITY, s = 0.0f;
     for (int item = tid; item < a.cv; item += SM_THREADS) {
         float x[VW];
-        sm_load<T, VW>(in + item * VW, x);
+        si_load_vec<T, VW>(in + item * VW, x);
         float mn = m;
 #pragma unroll
         for (int e = 0; e < VW; ++e) mn = fmaxf(mn, x[e]);
@@ -207,13 +175,13 @@ __global__ __launch_bounds__(SM_THREADS) void softmax_block_online_kernel(SmArgs
     T* const out = static_cast<T*>(a.out) + row * a.out_ld;
     for (int item = tid; item < a.cv; item += SM_THREADS) {
         float x[VW];
-        sm_load<T, VW>(in + item * VW, x);
+        si_load_vec<T, VW>(in + item * VW, x);
 #pragma unroll
         for (int e = 0; e < VW; ++e) {
             const float d = x[e] - M;
             x[e] = sm_finish(a.log, a.log ? d : __expf(d), k);
         }
-        sm_store<T, VW>(out + item * VW, x);
+        si_store_vec<T, VW>(out + item * VW, x);
     }
 }
 
@@ -241,7 +209,7 @@ __device__ __forceinline__ void sm_strided(const SmArgs& a) {
 #pragma unroll
         for (int p = 0; p < RA; ++p) {
             if (p < a.A) {
-                sm_load<T, VW>(in + p * in_step, v[p]);
+                si_load_vec<T, VW>(in + p * in_step, v[p]);
 #pragma unroll
                 for (int e = 0; e < VW; ++e) m[e] = fmaxf(m[e], v[p][e]);
             }
@@ -265,13 +233,13 @@ __device__ __forceinline__ void sm_strided(const SmArgs& a) {
             if (p < a.A) {
 #pragma unroll
                 for (int e = 0; e < VW; ++e) v[p][e] = sm_finish(a.log, v[p][e], s[e]);
-                sm_store<T, VW>(out + p * out_step, v[p]);
+                si_store_vec<T, VW>(out + p * out_step, v[p]);
             }
         }
     } else {
         for (int p = 0; p < a.A; ++p) {
             float x[VW];
-            sm_load<T, VW>(in + p * in_step, x);
+            si_load_vec<T, VW>(in + p * in_step, x);
 #pragma unroll
             for (int e = 0; e < VW; ++e) {
                 const float mn = fmaxf(m[e], x[e]);
@@ -284,13 +252,13 @@ __device__ __forceinline__ void sm_strided(const SmArgs& a) {
         for (int e = 0; e < VW; ++e) s[e] = sm_row_const(a.log, s[e]);
         for (int p = 0; p < a.A; ++p) {
             float x[VW];
-            sm_load<T, VW>(in + p * in_step, x);
+            si_load_vec<T, VW>(in + p * in_step, x);
 #pragma unroll
             for (int e = 0; e < VW; ++e) {
                 const float d = x[e] - m[e];
                 x[e] = sm_finish(a.log, a.log ? d : __expf(d), s[e]);
             }
-            sm_store<T, VW>(out + p * out_step, x);
+            si_store_vec<T, VW>(out + p * out_step, x);
         }
     }
 }

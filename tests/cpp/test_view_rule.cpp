@@ -1,7 +1,7 @@
 // The planner's view rule on its own, without a device (csrc/host/view_rule.h): for every fp16 conv form and operand, and for the broadcast
 // BinaryOp, whether a channel slice at pixel stride ld / channel offset off is taken.  The expected answers are spelled out here from the
 // kernels' entry checks (conv_igemm_f16.hip dispatch_h and f16_upcat_shape_ok, conv_depthwise_f16.hip, conv_slab_f16.hip slab_shape_ok and
-// pw_pair_ok, conv_pw_patch_f16.hip, ops_f16.hip si_hip_binary_bcast_f16) and from which refusals Conv2d::Launch has a second launch for.
+// pw_pair_ok, conv_pw_patch_f16.hip, ops.hip si_hip_binary_bcast_f16) and from which refusals Conv2d::Launch has a second launch for.
 // Stand-alone, header only; built by tests/test_view_rule_cpu.py.
 #include <cstdio>
 

@@ -1,4 +1,4 @@
-"""Float64 statements of the elementwise operators (ops.hip / ops_f16.hip), the input sets that reach their edges and the comparators that
+"""Float64 statements of the elementwise operators (ops.hip, fp32 and fp16 storage), the input sets that reach their edges and the comparators that
 hold a kernel to them.  Pure numpy: tests/test_elementwise_reference_cpu.py pins this file against torch and the C oracle without a GPU,
 tests/test_gpu_elementwise_edges.py holds the HIP kernels to it.
 

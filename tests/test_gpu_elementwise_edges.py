@@ -1,4 +1,4 @@
-"""GPU: the elementwise kernels of ops.hip / ops_f16.hip against the float64 reference of tests/elementwise_reference.py (pinned on the CPU by
+"""GPU: the elementwise kernels of ops.hip (fp32 and fp16 storage) against the float64 reference of tests/elementwise_reference.py (pinned on the CPU by
 tests/test_elementwise_reference_cpu.py), where the round-1 tests of test_gpu_ops.py / test_gpu_f16.py never looked:
 
   B1  every fp16 kernel on all 65536 bit patterns, in a shape the 16-byte arm takes and in one it cannot take;
