@@ -69,6 +69,7 @@ public:
     //   "fuse_grid"       1/0  F.grid_sample reads a permuted grid in place and an affine grid from theta (default 1; 0: the grid is written
     //                          first -- A/B runs)
     //   "fuse_xcorr"      1/0  view -> view -> F.conv2d(groups = N C) -> view, the depthwise cross-correlation, is one launch on the operands in front of the views (default 1; 0: four steps, the same bits)
+    //   "fuse_norm"       1/0  torch.norm over one dim -> [torch.unsqueeze] -> x / norm, the written-out F.normalize, is one launch that writes no norm (default 1; 0: the steps as they are, the same bits in fp32)
     //   "fuse_const"      1/0  two BinaryOps against graph constants in a row (x * scale + shift) are one two-stage launch (default 1; 0: two launches, the same bits)
     //   "arena"           1/0  intermediate operands share one HBM arena by lifetime (default 1); 0 = one allocation per operand,
     //                          as the reference does (src/engine_impl.cpp:465-482)

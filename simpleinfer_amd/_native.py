@@ -102,6 +102,11 @@ class SiParamActDesc(C.Structure):
                 ("out_ld", C.c_int)]
 
 
+class SiLpNormDesc(C.Structure):
+    """include/si_lpnorm.h; axes: bit mask of the NHWC axes reduced over (1 n, 2 h, 4 w, 8 c); p: 0 one, 1 two, 2 inf"""
+    _fields_ = [(k, C.c_int) for k in ("n", "h", "w", "c", "in_ld", "out_ld", "axes", "p", "normalize")] + [("eps", C.c_float)]
+
+
 class SiPixelShuffleDesc(C.Structure):
     """include/si_superres.h"""
     _fields_ = [(k, C.c_int) for k in ("n", "ih", "iw", "ic", "in_ld", "oh", "ow", "oc", "out_ld", "r", "inverse")]
@@ -491,10 +496,16 @@ def hip():
         "si_hip_detect_masks_f32": (i, [C.POINTER(SiDetectMaskDesc), vp, vp, vp, vp, vp, vp]),
         "si_hip_detect_masks_kernel_name": (C.c_char_p, [C.POINTER(SiDetectMaskDesc), vp]),
     }
+    # include/si_lpnorm.h: torch.norm / F.normalize
+    lpnorm_ = {
+        "si_hip_lpnorm_f32": (i, [C.POINTER(SiLpNormDesc), vp, vp, vp]),
+        "si_hip_lpnorm_f16": (i, [C.POINTER(SiLpNormDesc), vp, vp, vp]),
+        "si_hip_lpnorm_kernel_name": (C.c_char_p, [C.POINTER(SiLpNormDesc), vp, vp, i]),
+    }
     for name, (res, args) in (list(sig.items()) + list(norm.items()) + list(pad.items()) + list(pool.items()) + list(softmax.items()) +
                               list(superres.items()) + list(slice_.items()) + list(reduce_.items()) + list(act.items()) + list(permute_.items()) +
                               list(attention_.items()) + list(deform_.items()) + list(grid_.items()) + list(roi_.items()) + list(rnn_.items()) +
-                              list(binary_.items()) + list(conv1d_.items()) + list(xcorr_.items()) + list(detect_.items())):
+                              list(binary_.items()) + list(conv1d_.items()) + list(xcorr_.items()) + list(detect_.items()) + list(lpnorm_.items())):
         fn = getattr(L, name)  # AttributeError here = header/library mismatch, which tests check
         fn.restype = res
         fn.argtypes = args
@@ -517,6 +528,7 @@ def hip():
     L._si_conv1d_signatures = conv1d_
     L._si_xcorr_signatures = xcorr_
     L._si_detect_signatures = detect_
+    L._si_lpnorm_signatures = lpnorm_
     _hip = L
     return L
 

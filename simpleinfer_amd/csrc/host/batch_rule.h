@@ -212,10 +212,12 @@ inline BatchFamily BatchFamilyOf(const std::string& type) {
         {"nn.Softmax2d", BatchFamily::kSoftmax},
         {"F.softmax", BatchFamily::kSoftmax},
         {"F.log_softmax", BatchFamily::kSoftmax},
+        {"F.normalize", BatchFamily::kSoftmax},          // (x / max(norm, eps) along dim: per-image unless dim is the batch)
         {"torch.mean", BatchFamily::kReduce},
         {"torch.sum", BatchFamily::kReduce},
         {"torch.amax", BatchFamily::kReduce},
         {"torch.amin", BatchFamily::kReduce},
+        {"torch.norm", BatchFamily::kReduce},            // (the Lp norm over dim: per-image unless a reduced dim is the batch)
         {"torch.chunk", BatchFamily::kSlice},
         {"torch.split", BatchFamily::kSlice},
         {"Tensor.slice", BatchFamily::kSlice},
@@ -354,7 +356,8 @@ inline bool PerImageOperator(const pnnx::Operator* op, const std::vector<BatchOp
                 return false;
             }
             if (norm(dim) == axis) {
-                why = "the softmax runs along " + dim_text(axis) + ", the batch: it normalises over the images";
+                why = std::string(op->type == "F.normalize" ? "the norm is taken along " : "the softmax runs along ") + dim_text(axis) +
+                      ", the batch: it normalises over the images";
                 return false;
             }
             break;

@@ -117,6 +117,7 @@ private:
     Status FuseBottleneckPairs(std::vector<Step>& order);
     Status FuseConstStages(std::vector<Step>& order);
     Status FuseCrossCorrelations(std::vector<Step>& order);
+    Status FuseNormDivisions(std::vector<Step>& order);
     Status InsertOutputCasts(std::vector<Step>& order);
     Status InsertFp32Fallbacks(std::vector<Step>& order);
     Status AliasConcats();

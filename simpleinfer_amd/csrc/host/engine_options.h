@@ -20,6 +20,7 @@ struct EngineOptions {
     bool alias_view = true;    // a layout step that moves no byte makes its output a view of its input's buffer (0: one permute_rows copy)
     bool fuse_const = true;    // BinaryOp(x, c0) whose only reader is BinaryOp(., c1), c0 / c1 graph constants, is ONE two-stage launch (0: two launches, the same bits)
     bool fuse_xcorr = true;    // view -> view -> F.conv2d(groups = N C) -> view is ONE launch of the depthwise kernel in its per-sample addressing (0: the four steps, the same bits)
+    bool fuse_norm = true;     // torch.norm(x, p, dim = d) -> [torch.unsqueeze(d)] -> BinaryOp div(x, .) is ONE lpnorm launch with normalize = 1, eps = 0 (0: the steps as they are; fp32: the same bits)
     bool fuse_upsample = true; // upsample -> cat -> 1x1 conv read at the source
     int fuse_stem = 2;         // fp16: 1 RGB stem conv + the 3x3 s2 conv behind it in one launch; 2 ... and the 1x1 conv(s) reading that; 0 off
     int fuse_pw = 1;   // fp16: 1 a C3 bottleneck's 1x1 conv computed inside the kernel of its 3x3 conv; 0 off
@@ -61,7 +62,7 @@ struct EngineOptions {
         };
         static const Row kRows[] = {
             // value != 0
-            {"fuse", &O::fuse}, {"fuse_upsample", &O::fuse_upsample}, {"fuse_layout", &O::fuse_layout}, {"fuse_grid", &O::fuse_grid}, {"fuse_const", &O::fuse_const}, {"fuse_xcorr", &O::fuse_xcorr},
+            {"fuse", &O::fuse}, {"fuse_upsample", &O::fuse_upsample}, {"fuse_layout", &O::fuse_layout}, {"fuse_grid", &O::fuse_grid}, {"fuse_const", &O::fuse_const}, {"fuse_xcorr", &O::fuse_xcorr}, {"fuse_norm", &O::fuse_norm},
             {"alias_cat", &O::alias_cat}, {"alias_split", &O::alias_split}, {"alias_view", &O::alias_view}, {"arena", &O::arena},
             {"fp16", &O::fp16}, {"f32_split", &O::f32_split}, {"graph", &O::graph}, {"outputs_to_host", &O::outputs_to_host},
             {"pin_inputs", &O::pin_inputs}, {"_fail_slicer", &O::fail_slicer},

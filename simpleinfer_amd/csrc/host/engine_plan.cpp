@@ -18,6 +18,7 @@
 #include "layer/group_norm.h"
 #include "layer/layout.h"
 #include "layer/linear.h"
+#include "layer/lp_norm.h"
 #include "layer/max_pool_2d.h"
 #include "layer/output_cast.h"
 #include "layer/slice.h"
@@ -36,7 +37,7 @@ bool HonoursPixelStride(const std::string& type) {
         "nn.GroupNorm", "nn.InstanceNorm2d", "nn.ReflectionPad2d", "nn.ReplicationPad2d", "nn.ZeroPad2d", "nn.ConstantPad2d", "nn.CircularPad2d",
         "F.pad", "nn.Tanh", "nn.AvgPool2d", "F.avg_pool2d", "F.adaptive_avg_pool2d", "nn.Softmax", "nn.LogSoftmax", "nn.Softmax2d",
         "F.softmax", "F.log_softmax", "nn.PixelShuffle", "nn.PixelUnshuffle", "F.pixel_shuffle", "F.pixel_unshuffle", "nn.PReLU", "torch.flatten",
-        "torch.chunk", "torch.split", "Tensor.slice", "torch.mean", "torch.sum", "torch.amax", "torch.amin", "nn.ReLU6", "F.relu6",
+        "torch.chunk", "torch.split", "Tensor.slice", "torch.mean", "torch.sum", "torch.amax", "torch.amin", "F.normalize", "torch.norm", "nn.ReLU6", "F.relu6",
         "nn.Hardtanh", "F.hardtanh", "torch.clamp", "nn.Softplus", "F.softplus", "nn.Mish", "F.mish", "F.relu", "F.silu", "F.sigmoid", "F.hardsigmoid",
         "F.hardswish", "F.leaky_relu", "F.tanh", "models.yolo.Detect", "torchvision.ops.DeformConv2d", "F.grid_sample", "F.affine_grid", "pnnx.Output"};
     return ok.count(type) > 0;
@@ -85,6 +86,7 @@ Status EngineImpl::CreatePipeline() {
         CHECK_STATUS(FuseSiblingConvs(order));
         CHECK_STATUS(FusePoolChains(order));
         if (opt_.fuse_xcorr) CHECK_STATUS(FuseCrossCorrelations(order));   // (before the chains are composed: the views around the call are still single steps)
+        if (opt_.fuse_norm) CHECK_STATUS(FuseNormDivisions(order));   // (before the chains are composed: the unsqueeze behind the norm is still a single step)
         if (opt_.fuse_layout) CHECK_STATUS(FuseLayoutChains(order));
         if (opt_.fuse_layout && opt_.fuse_grid) CHECK_STATUS(FuseGridInPlace(order));   // (after the chains are composed: the run in front of a sampler is one step)
         if (opt_.fuse_grid) CHECK_STATUS(FuseAffineGrids(order));
@@ -465,6 +467,51 @@ Status EngineImpl::FuseCrossCorrelations(std::vector<Step>& order) {
         // (the launch keeps the conv's slot: x and z are ready before their views were, and nothing between the conv and the view behind it
         // reads or writes `out`)
         p.Retire(p.index[back], yv);
+    }
+    p.Compact();
+    return Status::kSuccess;
+}
+
+// n = torch.norm(x, p, dim = d, keepdim = K) -> [K false: torch.unsqueeze(n, d)] -> BinaryOp div(x, .)  ==>  ONE launch of the Lp-norm kernel
+// with normalize = 1, eps = 0 (include/si_lpnorm.h): F.normalize written out, as SuperPoint's descriptor head does.  The kernel divides every
+// element by the same float32 norm with the same IEEE division BinaryOp uses, so in fp32 the bits are those of fuse_norm = 0; under fp16
+// storage the unfused plan rounds the norm to a half in between and the fused one does not.  Conditions: one reduced dim, the unsqueeze puts
+// it back where it was, the division's first operand is the norm's own input and its second the (unsqueezed) norm, and the norm and the
+// unsqueezed norm have no other reader and are no graph outputs.  The launch keeps the norm's slot (x is ready there and nothing in between
+// touches the quotient); the unsqueeze and the division are retired, the operands between the three are dead and no norm tensor is written.
+Status EngineImpl::FuseNormDivisions(std::vector<Step>& order) {
+    Pass p(*this, order);
+    for (size_t i = 0; i < order.size(); ++i) {
+        LpNorm* ln = p.At<LpNorm>(i, "torch.norm");
+        const pnnx::Operator* op = order[i].op;
+        if (!ln || ln->Normalizes() || ln->dims_.size() != 1 || op->inputs.size() != 1 || op->outputs.size() != 1) continue;
+        const pnnx::Operand* x = op->inputs[0];
+        const pnnx::Operand* norm = op->outputs[0];
+        if (ln->InputNodes().size() != 1 || ln->InputNodes()[0] != tensor_nodes_[x->name]) continue;
+        const int rank = (int)ln->InputNodes()[0]->tensor.Shape().size();
+        const int dim = ln->dims_[0] < 0 ? ln->dims_[0] + rank : ln->dims_[0];
+        const pnnx::Operand* divisor = norm;
+        const pnnx::Operator* unsq = nullptr;
+        const pnnx::Operator* next = p.SoleConsumer(norm);
+        if (!ln->keepdim_) {
+            int at = 0;
+            if (!next || next->type != "torch.unsqueeze" || next->inputs.size() != 1 || next->outputs.size() != 1 || !p.At<Layout>(p.index[next]) ||
+                !Get(next, "dim", at) || (at < 0 ? at + rank : at) != dim)
+                continue;
+            unsq = next;
+            divisor = next->outputs[0];
+            next = p.SoleConsumer(divisor);
+        }
+        BinaryOp* div = next ? dynamic_cast<BinaryOp*>(p.LayerOf(next)) : nullptr;
+        if (!div || next->type != "BinaryOp" || div->binary_op_type_ != BinaryOp::BinaryOpType::kDiv || div->with_scalar_ || div->ConstForm() ||
+            next->inputs.size() != 2 || next->outputs.size() != 1 || next->inputs[0] != x || next->inputs[1] != divisor)
+            continue;
+        TensorNode* out = tensor_nodes_[next->outputs[0]->name];
+        // (whatever storage types x and the quotient have: the planner's later passes treat the launch as they treat F.normalize in that place)
+        if (!out || !ln->SetNormalize(out)) continue;
+        if (unsq) p.Retire(p.index[unsq], norm);
+        p.Retire(p.index[next], divisor);
+        if (!unsq) dead_operands_.insert(norm->name);
     }
     p.Compact();
     return Status::kSuccess;

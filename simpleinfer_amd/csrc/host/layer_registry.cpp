@@ -28,6 +28,7 @@ SI_DECLARE_LAYER(HardSwish)
 SI_DECLARE_LAYER(Layout)
 SI_DECLARE_LAYER(LeakyReLU)
 SI_DECLARE_LAYER(Linear)
+SI_DECLARE_LAYER(LpNorm)
 SI_DECLARE_LAYER(MaxPool2d)
 SI_DECLARE_LAYER(MultiheadAttention)
 SI_DECLARE_LAYER(Pad2d)
@@ -69,7 +70,8 @@ static std::map<std::string, LayerRegistryEntry>& Table() {
     // torchvision.ops.RoIAlign / torchvision.ops.roi_align (one class, layer/roi_align.h: the box-pooling kernel of include/si_roi.h);
     // nn.LSTM / nn.GRU (one class with a cell kind, layer/rnn.h: the input projection and the recurrent step kernel of include/si_rnn.h);
     // nn.Conv1d (layer/conv_1d.h: the temporal convolution kernels of include/si_conv1d.h on rank-3 operands in their native layout);
-    // F.conv2d (layer/functional_conv_2d.h: the filter is an operand, read as stored by the cross-correlation kernels of include/si_xcorr.h)
+    // F.conv2d (layer/functional_conv_2d.h: the filter is an operand, read as stored by the cross-correlation kernels of include/si_xcorr.h);
+    // F.normalize / torch.norm (one class, layer/lp_norm.h: the Lp-norm kernels of include/si_lpnorm.h)
     static std::map<std::string, LayerRegistryEntry> table = {
         SI_ENTRY("nn.AdaptiveAvgPool2d", AdaptiveAvgPool2d),
         SI_ENTRY("nn.AvgPool2d", AvgPool2d),
@@ -154,6 +156,8 @@ static std::map<std::string, LayerRegistryEntry>& Table() {
         SI_ENTRY("nn.GRU", Rnn),
         SI_ENTRY("nn.Conv1d", Conv1d),
         SI_ENTRY("F.conv2d", FunctionalConv2d),
+        SI_ENTRY("F.normalize", LpNorm),
+        SI_ENTRY("torch.norm", LpNorm),
     };
     return table;
 }

@@ -1697,6 +1697,32 @@ def reduce_kernel_name(x_shape, op, axes, half=False, in_ld=None, out_ld=None) -
     return _desc_kernel_name("reduce", d, half)
 
 
+LPNORM_P = {1: 0, 2: 1, float("inf"): 2}
+
+
+def lpnorm_desc(x_shape, p, axes, normalize=False, eps=0.0, in_ld=None, out_ld=None):
+    """SiLpNormDesc (include/si_lpnorm.h) of an NHWC input; p: 1, 2 or inf (or, as an int outside those, the raw code); axes: the bit mask"""
+    n, h, w, c = x_shape
+    oc = c if normalize or not int(axes) & 8 else 1
+    code = LPNORM_P[float(p)] if float(p) in LPNORM_P else int(p)
+    return _native.SiLpNormDesc(n, h, w, c, in_ld or c, out_ld or oc, int(axes), code, int(normalize), float(eps))
+
+
+def lpnorm(x, p, axes, normalize=False, eps=0.0, in_ld=None, in_c_off=0, in_fill=0.0, out_ld=None, out_c_off=0, out_fill=0.0, full=False):
+    """si_hip_lpnorm_f32 / _f16 (by the array's dtype) on an NHWC array: torch.norm(p) over the NHWC axes of the bit mask `axes` (1 n, 2 h,
+    4 w, 8 c), keepdim=True, or -- normalize -- F.normalize(p, eps) along the one axis of the mask.  The view hooks are the common ones."""
+    x = _float_storage(x)
+    assert x.ndim == 4, "NHWC (a rank-2 [N, F] array is [N, 1, 1, F])"
+    d = lpnorm_desc(x.shape, p, axes, normalize, eps, in_ld, out_ld)
+    oshape = tuple(x.shape) if normalize else reduce_out_shape(x.shape, axes if 1 <= int(axes) <= 15 else 0)
+    return _run_desc_op("lpnorm", d, x, oshape[:-1], oshape[3], in_ld, in_c_off, in_fill, out_ld, out_c_off, out_fill, full)
+
+
+def lpnorm_kernel_name(x_shape, p, axes, normalize=False, half=False, in_ld=None, out_ld=None) -> str:
+    """the instantiation for 16-byte aligned buffers of these shapes ("none": a descriptor the launch refuses)"""
+    return _desc_kernel_name("lpnorm", lpnorm_desc(x_shape, p, axes, normalize, 0.0, in_ld, out_ld), half)
+
+
 PARAM_ACT_OPS = {"clamp": 0, "softplus": 1, "mish": 2}
 
 

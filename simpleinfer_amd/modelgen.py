@@ -379,6 +379,25 @@ class PnnxBuilder:
     def amax(self, x: str, dim, keepdim: bool = False) -> str: return self._reduce("amax", x, dim, keepdim)
     def amin(self, x: str, dim, keepdim: bool = False) -> str: return self._reduce("amin", x, dim, keepdim)
 
+    def normalize(self, x: str, dim: int = 1, p=2.0, eps: float = 1e-12) -> str:
+        """pnnx's F.normalize line: dim= an int, eps= and p= floats (float("inf") is written inf, as pnnx writes it)"""
+        return self._unary("F.normalize", "F_normalize", x, dict(dim=int(dim), eps=float(eps), p=p if isinstance(p, str) else float(p)))
+
+    def norm(self, x: str, dim, p=2, keepdim: bool = False) -> str:
+        """pnnx's torch.norm line: dim= an int or a tuple as given, keepdim=, p= as given (an int, a float, or a text such as fro).  dim=None
+        writes dim=None (the reduction to a scalar).  The output shape is torch's rule."""
+        shp = self.shapes[x]
+        dims = list(range(len(shp))) if dim is None else sorted({d % len(shp) for d in ((dim,) if isinstance(dim, int) else dim)})
+        out_shape = [1 if i in dims else s for i, s in enumerate(shp)] if keepdim else [s for i, s in enumerate(shp) if i not in dims]
+        out = self._new_operand(out_shape)
+        params = dict(dim="None" if dim is None else int(dim) if isinstance(dim, int) else tuple(int(d) for d in dim), keepdim=bool(keepdim), p=p)
+        self._emit("torch.norm", self._opname("torch_norm"), [x], [out], params)
+        return out
+
+    def div(self, a: str, b: str) -> str:
+        sa, sb = self.shapes[a], self.shapes[b]
+        return self.expression("div(@0,@1)", [a, b], tuple(max(x, y) for x, y in zip(sa, sb)))
+
     def _head(self, x: str, head) -> str:
         """the optional last layer of the toy builders: None, "softmax" or "log_softmax" over dim 1"""
         assert head in (None, "softmax", "log_softmax"), head
@@ -955,6 +974,42 @@ def build_toy_layernorm2d(batch: int = 2, size: int = 16, seed: int = 0, eps: st
     s = b.mean(b.expression("square(@0)", [d]), (1,), True)
     y = b.expression("div(@0,sqrt(add(@1,%s)))" % eps, [d, s])
     b.output(b.conv(y, 8, 1))
+    return b
+
+
+def build_toy_superpoint(batch: int = 2, size: int = 32, functional: bool = False, seed: int = 0) -> PnnxBuilder:
+    """SuperPoint in small: a shared stack of three 3x3 convs, each behind a 2x2 max pool (cell size 8), then two heads and two graph outputs.
+    Detector: conv -> conv to 65 channels -> softmax(dim=1) -> slice off the dustbin channel -> permute(0,2,3,1) -> reshape(N, Hc, Wc, 8, 8) ->
+    permute(0,1,3,2,4) -> reshape(N, 8 Hc, 8 Wc), the depth-to-space of its export.  Descriptor: conv -> conv to 32 channels, then the norm
+    as the export writes it out -- dn = torch.norm(desc, p=2, dim=1); desc.div(torch.unsqueeze(dn, 1)) -- or, functional=True,
+    F.normalize(desc, p=2, dim=1)."""
+    assert size % 8 == 0, size
+    b = PnnxBuilder(seed)
+    x = b.input((batch, 1, size, size))
+    x = b.maxpool(b.relu(b.conv(x, 8, 3, 1, 1)), 2, 2, 0)
+    x = b.maxpool(b.relu(b.conv(x, 16, 3, 1, 1)), 2, 2, 0)
+    x = b.maxpool(b.relu(b.conv(x, 32, 3, 1, 1)), 2, 2, 0)
+    hc = size // 8
+    s = b.conv(b.relu(b.conv(x, 32, 3, 1, 1)), 65, 1)
+    s = b.slice(b.softmax(s, 1), 1, 0, 64)
+    s = b.reshape(b.permute(s, (0, 2, 3, 1)), (batch, hc, hc, 8, 8))
+    b.output(b.reshape(b.permute(s, (0, 1, 3, 2, 4)), (batch, hc * 8, hc * 8)))
+    d = b.conv(b.relu(b.conv(x, 32, 3, 1, 1)), 32, 1)
+    if functional:
+        b.output(b.normalize(d, 1, 2.0))
+    else:
+        b.output(b.div(d, b.unsqueeze(b.norm(d, 1, 2, False), 1)))
+    return b
+
+
+def build_toy_embedding_head(batch: int = 2, size: int = 32, dim: int = 24, seed: int = 0) -> PnnxBuilder:
+    """A face / re-ID / retrieval embedding head: a conv stack, x.mean((2, 3)), nn.Linear to `dim` features and F.normalize(dim=1) on the
+    rank-2 result: unit rows."""
+    b = PnnxBuilder(seed)
+    x = b.input((batch, 3, size, size))
+    x = b.relu(b.conv(x, 16, 3, 2, 1))
+    x = b.relu(b.conv(x, 32, 3, 2, 1))
+    b.output(b.normalize(b.linear(b.mean(x, (2, 3)), dim), 1))
     return b
 
 
