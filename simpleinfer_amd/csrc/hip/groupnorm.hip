@@ -96,13 +96,6 @@ __device__ __forceinline__ void gn_merge(float& na, float& ma, float& qa, float 
     }
 }
 
-// sum over the tpg (a power of two <= 64) lanes of a team; every lane of the wave takes part and every lane of a team ends
-// with the same bits (a + b is commutative: both partners of an exchange form the same sum)
-__device__ __forceinline__ float gn_team_sum(float v, int tpg) {
-    for (int off = tpg >> 1; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 // k >= 1 partials of the SAME count m, get(i) = (mean_i, M2_i), combined by lane j of a team of tpg lanes: the mean of the
 // means (summed as differences to the first one: no cancellation against a large common offset) and
 // M2 = sum M2_i + m * sum (mean_i - mean)^2.  One partial comes back bit for bit.
@@ -111,7 +104,7 @@ __device__ __forceinline__ float2 gn_combine_equal(Get get, int k, float m, int 
     const float pivot = get(0).x;
     float s = 0.0f;
     for (int i = j; i < k; i += tpg) s += get(i).x - pivot;
-    s = gn_team_sum(s, tpg);
+    s = si_team<SiSum>(s, tpg);
     const float mu = pivot + s / (float)k;
     float q = 0.0f;
     for (int i = j; i < k; i += tpg) {
@@ -119,7 +112,7 @@ __device__ __forceinline__ float2 gn_combine_equal(Get get, int k, float m, int 
         const float d = e.x - mu;
         q += e.y + m * (d * d);
     }
-    q = gn_team_sum(q, tpg);
+    q = si_team<SiSum>(q, tpg);
     return make_float2(mu, q);
 }
 

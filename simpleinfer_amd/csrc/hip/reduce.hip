@@ -1,17 +1,17 @@
 // reduce.hip -- sum / mean / amax / amin over axes of an NHWC tensor (include/si_reduce.h) on fp32 and fp16 tensors with pixel strides on
-// both sides.  Arithmetic, special values, the forms and the refusals: the header.  This is the project's plain reduction; softmax.hip
-// is the model for its fixed order.
+// both sides.  Arithmetic, special values, the forms and the refusals: the header.  This is the project's plain reduction; the fixed
+// order of its combinations, the fold of the mask and the position walk are the reduction commons (si_reduce_dev.h, si_reduce_plan.h).
 //
-// One accumulator per result, float32.  sum / mean add; amax / amin run ONE selection, the NaN-keeping maximum
-//     max(a, b) = (a != a || a > b) ? a : b          (a NaN on either side comes out; fmaxf would drop it)
+// One accumulator per result, float32.  sum / mean add; amax / amin run ONE selection, the NaN-keeping maximum (SiMaxNan of
+// si_reduce_dev.h: a NaN on either side comes out; fmaxf would drop it),
 // amin being -max(-x): negation is exact and keeps a NaN a NaN.  The identity of an empty share is 0 (sum) or -inf (max).
 //
 // Channel axis (axes == 8), a ROW = the c channels of one pixel, seen as cv items (16-byte vectors, or single elements); the elements of
 // an item enter the accumulator in channel order:
 //   row_group  L = 2^k <= 64 lanes per row (the power of two at or above cv / 4, as softmax.hip sizes its groups), 256 / L rows per
 //              workgroup; lane j takes items j, j + L, ...; a butterfly over the xor offsets below L; lane 0 of the group stores.
-//   row_block  one workgroup per row, thread t takes items t, t + 256, ...; butterflies per wave, then thread 0 combines the four wave
-//              values from LDS in index order and stores.
+//   row_block  one workgroup per row, thread t takes items t, t + 256, ...; butterflies per wave, then the four wave values from LDS in
+//              index order (si_block); thread 0 stores.
 // Axes within {n, h, w}: the host folds the three axes into at most two KEPT levels and two REDUCED levels of (count, pixel stride) --
 // neighbouring axes of one kind merge (h and w reduced are one run of h * w pixels), extents of 1 drop out; only {n, w} around a kept h
 // (or kept around a reduced h) needs both levels.  An ITEM = (kept pixel, channel vector); every channel of the vector is a reduction
@@ -52,8 +52,7 @@ struct RdArgs {
     float count;         // mean: (float)positions
     int rows, lg;        // row forms: pixels; group: log2 of the lanes per row
     int items;           // col forms: kept pixels * cv
-    int K1, ks0, ks1;    // kept pixel kp starts at input pixel (kp / K1) * ks0 + (kp % K1) * ks1
-    int R, R1, rs0, rs1; // position r is (r / R1) * rs0 + (r % R1) * rs1 pixels further
+    SiLevelArgs lv;      // col forms: the kept pixels and the positions of the mask
     int chunk, parts;    // col_coop: positions per part, non-empty parts
 };
 
@@ -61,10 +60,7 @@ template <bool MAX>
 __device__ __forceinline__ float rd_identity() { return MAX ? -INFINITY : 0.0f; }
 
 template <bool MAX>
-__device__ __forceinline__ float rd_combine(float a, float b) {
-    if constexpr (MAX) return (a != a || a > b) ? a : b;
-    return a + b;
-}
+__device__ __forceinline__ float rd_combine(float a, float b) { return SiSumOrMaxNan<MAX>::apply(a, b); }
 
 // an element on its way in: amin runs as the maximum of the negated values
 template <bool MAX>
@@ -76,20 +72,12 @@ __device__ __forceinline__ float rd_finish(const RdArgs& a, float acc) {
     return a.op == SI_REDUCE_MEAN ? acc / a.count : acc;
 }
 
-// butterfly over the xor offsets below `lanes` (a power of two <= 64); lane 0 of the team is the one whose value is used
-template <bool MAX>
-__device__ __forceinline__ float rd_team(float v, int lanes) {
-    for (int off = lanes >> 1; off > 0; off >>= 1) v = rd_combine<MAX>(v, __shfl_xor(v, off, 64));
-    return v;
-}
-
 // BLOCK = one workgroup per row, else a group of 1 << a.lg lanes per row
 template <typename T, int VW, bool BLOCK, bool MAX>
 __device__ __forceinline__ void rd_row(const RdArgs& a, float* part) {
-    const int tid = (int)threadIdx.x;
-    const int L = BLOCK ? RD_THREADS : (1 << a.lg);
-    const int j = BLOCK ? tid : (tid & (L - 1));
-    const int row = BLOCK ? (int)blockIdx.x : (int)blockIdx.x * (RD_THREADS >> a.lg) + (tid >> a.lg);
+    const SiRowTile<T, VW, RD_THREADS, BLOCK> tile(a.lg);   // (its geometry alone: the row is streamed, not kept)
+    const int L = tile.L, j = tile.j;
+    const int row = (int)blockIdx.x * tile.rows_per_block + tile.sub;
     const bool live = row < a.rows;   // (a dead row's lanes load and store nothing but take part in every exchange)
     const T* const in = static_cast<const T*>(a.in) + (live ? row : 0) * a.in_ld;
     float acc = rd_identity<MAX>();
@@ -102,15 +90,10 @@ __device__ __forceinline__ void rd_row(const RdArgs& a, float* part) {
         }
     }
     if constexpr (BLOCK) {
-        acc = rd_team<MAX>(acc, 64);
-        if ((tid & 63) == 0) part[tid >> 6] = acc;
-        __syncthreads();
-        if (tid != 0) return;
-        acc = part[0];
-#pragma unroll
-        for (int w = 1; w < RD_WAVES; ++w) acc = rd_combine<MAX>(acc, part[w]);
+        acc = si_block<SiSumOrMaxNan<MAX>, RD_WAVES>(acc, part);
+        if (j != 0) return;
     } else {
-        acc = rd_team<MAX>(acc, L);
+        acc = si_team<SiSumOrMaxNan<MAX>>(acc, L);   // (lane 0 of the team is the one whose value is used)
         if (!live || j != 0) return;
     }
     static_cast<T*>(a.out)[row * a.out_ld] = si_store_cast<T>(rd_finish<MAX>(a, acc));
@@ -138,31 +121,22 @@ template <int VW>
 __device__ __forceinline__ void rd_item(const RdArgs& a, int item, unsigned& in_off, unsigned& out_off) {
     const int kp = item / a.cv;
     const int cvec = item - kp * a.cv;
-    const int k0 = kp / a.K1;
-    const int k1 = kp - k0 * a.K1;
-    in_off = (unsigned)(k0 * a.ks0 + k1 * a.ks1) * (unsigned)a.in_ld + (unsigned)(cvec * VW);
+    const int k0 = kp / a.lv.K1;
+    const int k1 = kp - k0 * a.lv.K1;
+    in_off = (unsigned)(k0 * a.lv.ks0 + k1 * a.lv.ks1) * (unsigned)a.in_ld + (unsigned)(cvec * VW);
     out_off = (unsigned)kp * (unsigned)a.out_ld + (unsigned)(cvec * VW);
 }
 
-// positions [start, end) of one item into acc, in order.  Offsets are unsigned: the step past the last position may wrap, and is unused.
+// positions [start, end) of one item into acc, in order (element offsets: the walk counts in pixel strides)
 template <typename T, int VW, bool MAX>
-__device__ __forceinline__ void rd_walk(const RdArgs& a, const T* in, unsigned off, int start, int end, float (&acc)[VW]) {
-    const int r0 = start / a.R1;
-    int r1 = start - r0 * a.R1;
-    off += (unsigned)(r0 * a.rs0 + r1 * a.rs1) * (unsigned)a.in_ld;
-    const unsigned step = (unsigned)a.rs1 * (unsigned)a.in_ld;
-    const unsigned wrap = (unsigned)(a.rs0 - a.R1 * a.rs1) * (unsigned)a.in_ld;
+__device__ __forceinline__ void rd_walk(const RdArgs& a, const T* in, unsigned off0, int start, int end, float (&acc)[VW]) {
+    SiLevelWalk walk(a.lv, (unsigned)a.in_ld, off0, start);
 #pragma unroll 4
-    for (int r = start; r < end; ++r) {
+    for (int r = start; r < end; ++r, walk.next()) {
         float v[VW];
-        si_load_vec<T, VW>(in + off, v);
+        si_load_vec<T, VW>(in + walk.off, v);
 #pragma unroll
         for (int e = 0; e < VW; ++e) acc[e] = rd_combine<MAX>(acc[e], rd_prep<MAX>(a.op, v[e]));
-        off += step;
-        if (++r1 == a.R1) {
-            r1 = 0;
-            off += wrap;
-        }
     }
 }
 
@@ -175,7 +149,7 @@ __device__ __forceinline__ void rd_col_lane(const RdArgs& a) {
     float acc[VW];
 #pragma unroll
     for (int e = 0; e < VW; ++e) acc[e] = rd_identity<MAX>();
-    rd_walk<T, VW, MAX>(a, static_cast<const T*>(a.in), in_off, 0, a.R, acc);
+    rd_walk<T, VW, MAX>(a, static_cast<const T*>(a.in), in_off, 0, a.lv.R, acc);
 #pragma unroll
     for (int e = 0; e < VW; ++e) acc[e] = rd_finish<MAX>(a, acc[e]);
     si_store_vec<T, VW>(static_cast<T*>(a.out) + out_off, acc);
@@ -202,7 +176,7 @@ __device__ __forceinline__ void rd_col_coop(const RdArgs& a, float* part) {
         unsigned in_off, out_off;
         rd_item<VW>(a, item, in_off, out_off);
         const int start = g * a.chunk;
-        const int end = start + a.chunk < a.R ? start + a.chunk : a.R;
+        const int end = start + a.chunk < a.lv.R ? start + a.chunk : a.lv.R;
         rd_walk<T, VW, MAX>(a, static_cast<const T*>(a.in), in_off, start, end, acc);
     }
 #pragma unroll
@@ -229,91 +203,48 @@ __global__ __launch_bounds__(RD_COOP_THREADS) void reduce_col_coop_kernel(RdArgs
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------
-constexpr int kSpatial = SI_REDUCE_AXIS_N | SI_REDUCE_AXIS_H | SI_REDUCE_AXIS_W;
+static_assert(SI_REDUCE_AXIS_N == SI_AXIS_N && SI_REDUCE_AXIS_H == SI_AXIS_H && SI_REDUCE_AXIS_W == SI_AXIS_W && SI_REDUCE_AXIS_C == SI_AXIS_C,
+              "si_reduce_plan.h folds the header's mask");
+
+int out_channels(const SiReduceDesc* d) { return (d->axes & SI_AXIS_C) ? 1 : d->c; }
 
 // everything that can be decided without a device or a pointer: SI_E_BADARG / SI_E_UNSUPPORTED / 0
 int check_desc(const SiReduceDesc* d) {
     if (!d) return SI_E_BADARG;
-    if (d->n <= 0 || d->h <= 0 || d->w <= 0 || d->c <= 0) return SI_E_BADARG;
     if (d->axes < 1 || d->axes > 15 || d->op < SI_REDUCE_SUM || d->op > SI_REDUCE_AMIN) return SI_E_BADARG;
-    const int oc = (d->axes & SI_REDUCE_AXIS_C) ? 1 : d->c;
-    if (d->in_ld < d->c || d->out_ld < oc) return SI_E_BADARG;
-    if ((d->axes & SI_REDUCE_AXIS_C) && (d->axes & kSpatial)) return SI_E_UNSUPPORTED;
-    const uint64_t rows = (uint64_t)d->n * (uint64_t)d->h;   // < 2^62
-    if (rows > SI_INDEX_LIMIT || rows * (uint64_t)d->w > SI_INDEX_LIMIT) return SI_E_UNSUPPORTED;
-    const uint64_t pix = rows * (uint64_t)d->w;
-    const uint64_t opix = (uint64_t)((d->axes & SI_REDUCE_AXIS_N) ? 1 : d->n) * (uint64_t)((d->axes & SI_REDUCE_AXIS_H) ? 1 : d->h) *
-                          (uint64_t)((d->axes & SI_REDUCE_AXIS_W) ? 1 : d->w);
-    // offsets, and with them the grids: at most one workgroup per pixel, at most one lane per element (c <= ld)
-    if (pix * (uint64_t)d->in_ld > SI_INDEX_LIMIT || opix * (uint64_t)d->out_ld > SI_INDEX_LIMIT) return SI_E_UNSUPPORTED;
+    // (every SI_E_BADARG before the mask refusal, and that one an SI_E_UNSUPPORTED like the limits: each descriptor keeps its code)
+    const int rc = si_check_reduce_views(d->n, d->h, d->w, d->c, d->in_ld, d->out_ld, si_masked_pixels(d->n, d->h, d->w, d->axes), out_channels(d));
+    if (rc != 0) return rc;
+    if ((d->axes & SI_AXIS_C) && (d->axes & SI_AXIS_SPATIAL)) return SI_E_UNSUPPORTED;
     return 0;
 }
 
 // do the two views share an element?  (the strided-window rule of si_views.h)
 bool views_overlap(const SiReduceDesc* d, const void* in, const void* out, size_t esize) {
-    const int oc = (d->axes & SI_REDUCE_AXIS_C) ? 1 : d->c;
     const uint64_t pix = (uint64_t)d->n * d->h * d->w;
-    const uint64_t opix = (uint64_t)((d->axes & SI_REDUCE_AXIS_N) ? 1 : d->n) * (uint64_t)((d->axes & SI_REDUCE_AXIS_H) ? 1 : d->h) *
-                          (uint64_t)((d->axes & SI_REDUCE_AXIS_W) ? 1 : d->w);
-    return si_strided_windows_overlap(in, pix, (uint64_t)d->in_ld, (uint64_t)d->c, out, opix, (uint64_t)d->out_ld, (uint64_t)oc, esize);
+    return si_strided_windows_overlap(in, pix, (uint64_t)d->in_ld, (uint64_t)d->c, out, si_masked_pixels(d->n, d->h, d->w, d->axes),
+                                      (uint64_t)d->out_ld, (uint64_t)out_channels(d), esize);
 }
 
 enum Form { kRowGroup, kRowBlock, kColLane, kColCoop };
 
-// the three spatial axes folded into kept and reduced levels of (count, pixel stride), outer first
-struct Levels {
-    int kept[2][2] = {{1, 0}, {1, 0}};
-    int red[2][2] = {{1, 0}, {1, 0}};
-    uint64_t positions = 1;          // the product of the reduced extents
-    uint64_t outputs_per_image = 1;  // kept h x kept w x c
-};
-
-Levels levels_of(const SiReduceDesc* d) {
-    Levels lv;
-    const int ext[3] = {d->n, d->h, d->w};
-    const int stride[3] = {d->h * d->w, d->w, 1};
-    int nk = 0, nr = 0;
-    int kept[3][2], red[3][2];
-    for (int a = 0; a < 3; ++a) {
-        const bool reduced = (d->axes >> a) & 1;
-        if (reduced) lv.positions *= (uint64_t)ext[a];
-        if (ext[a] == 1) continue;
-        int(*list)[2] = reduced ? red : kept;
-        int& cnt = reduced ? nr : nk;
-        if (cnt > 0 && list[cnt - 1][1] == ext[a] * stride[a]) {   // the level above is a run of this one
-            list[cnt - 1][0] *= ext[a];
-            list[cnt - 1][1] = stride[a];
-        } else {
-            list[cnt][0] = ext[a];
-            list[cnt][1] = stride[a];
-            ++cnt;
-        }
-    }
-    // (three levels of one kind would need the other kind between each pair: there are three axes, so at most two)
-    for (int i = 0; i < nk; ++i) { lv.kept[2 - nk + i][0] = kept[i][0]; lv.kept[2 - nk + i][1] = kept[i][1]; }
-    for (int i = 0; i < nr; ++i) { lv.red[2 - nr + i][0] = red[i][0]; lv.red[2 - nr + i][1] = red[i][1]; }
-    lv.outputs_per_image = (uint64_t)((d->axes & SI_REDUCE_AXIS_H) ? 1 : d->h) * (uint64_t)((d->axes & SI_REDUCE_AXIS_W) ? 1 : d->w) * (uint64_t)d->c;
-    return lv;
-}
-
 // a function of the descriptor; n enters through the positions only, that is only when it is reduced
 Form form_of(const SiReduceDesc* d) {
     if (d->axes == SI_REDUCE_AXIS_C) return d->c <= SI_REDUCE_GROUP_MAX_C ? kRowGroup : kRowBlock;
-    const Levels lv = levels_of(d);
+    const SiLevels lv = si_fold_levels(d->n, d->h, d->w, d->axes);
+    const uint64_t outputs_per_image = si_masked_pixels(1, d->h, d->w, d->axes) * (uint64_t)d->c;   // kept h x kept w x c
     const int force = SI_ENV_INT("SI_REDUCE_FORCE_COL", 0);   // experiment build only: 1 col_lane, 2 col_coop
     if (force == 1) return kColLane;
     if (force == 2) return kColCoop;
-    return (lv.positions >= SI_REDUCE_COOP_MIN_POSITIONS && lv.outputs_per_image <= SI_REDUCE_COOP_MAX_OUTPUTS) ? kColCoop : kColLane;
+    return (lv.positions >= SI_REDUCE_COOP_MIN_POSITIONS && outputs_per_image <= SI_REDUCE_COOP_MAX_OUTPUTS) ? kColCoop : kColLane;
 }
 
 // 16-byte channel vectors when c, the strides and the pointers allow it (the row forms store single elements: their output does not
 // enter); single elements otherwise
 template <typename T>
 int vector_width(const SiReduceDesc* d, const void* in, const void* out) {
-    const int full = (int)(16 / sizeof(T));
-    bool vec = d->c % full == 0 && d->in_ld % full == 0 && si_aligned_to(in, 16);
-    if (d->axes != SI_REDUCE_AXIS_C) vec = vec && d->out_ld % full == 0 && si_aligned_to(out, 16);
-    return vec ? full : 1;
+    if (d->axes == SI_AXIS_C) return si_vector_width<T>(d->c, d->in_ld, d->in_ld, in, in);
+    return si_vector_width<T>(d->c, d->in_ld, d->out_ld, in, out);
 }
 
 template <typename T, int VW>
@@ -325,7 +256,7 @@ int launch(const SiReduceDesc* d, const T* in, T* out, hipStream_t stream) {
     a.out_ld = d->out_ld;
     a.cv = d->c / VW;
     a.op = d->op;
-    a.K1 = a.R1 = a.R = a.chunk = a.parts = 1;
+    a.chunk = a.parts = 1;
     const Form form = form_of(d);
     if (form == kRowGroup || form == kRowBlock) {
         a.rows = d->n * d->h * d->w;
@@ -334,28 +265,22 @@ int launch(const SiReduceDesc* d, const T* in, T* out, hipStream_t stream) {
             hipLaunchKernelGGL((reduce_row_block_kernel<T, VW>), dim3((unsigned)a.rows), dim3(RD_THREADS), 0, stream, a);
         } else {
             // lanes per row: the power of two at or above cv / RD_GROUP_ITEMS, at most 64
-            while ((1 << a.lg) < 64 && (1 << a.lg) * RD_GROUP_ITEMS < a.cv) ++a.lg;
+            a.lg = si_group_lg(a.cv, RD_GROUP_ITEMS);
             const int rows_per_block = RD_THREADS >> a.lg;
             hipLaunchKernelGGL((reduce_row_group_kernel<T, VW>), dim3((unsigned)((a.rows + rows_per_block - 1) / rows_per_block)), dim3(RD_THREADS), 0,
                                stream, a);
         }
         return (int)hipGetLastError();
     }
-    const Levels lv = levels_of(d);
-    a.K1 = lv.kept[1][0];
-    a.ks0 = lv.kept[0][1];
-    a.ks1 = lv.kept[1][1];
-    a.R = (int)lv.positions;
-    a.R1 = lv.red[1][0];
-    a.rs0 = lv.red[0][1];
-    a.rs1 = lv.red[1][1];
+    const SiLevels lv = si_fold_levels(d->n, d->h, d->w, d->axes);
+    a.lv = si_level_args(lv);
     a.count = (float)lv.positions;
     a.items = lv.kept[0][0] * lv.kept[1][0] * a.cv;
     if (form == kColLane) {
         hipLaunchKernelGGL((reduce_col_lane_kernel<T, VW>), dim3(((unsigned)a.items + RD_THREADS - 1) / RD_THREADS), dim3(RD_THREADS), 0, stream, a);
     } else {
-        a.chunk = (a.R + SI_REDUCE_COOP_PARTS - 1) / SI_REDUCE_COOP_PARTS;
-        a.parts = (a.R + a.chunk - 1) / a.chunk;
+        a.chunk = (a.lv.R + SI_REDUCE_COOP_PARTS - 1) / SI_REDUCE_COOP_PARTS;
+        a.parts = (a.lv.R + a.chunk - 1) / a.chunk;
         hipLaunchKernelGGL((reduce_col_coop_kernel<T, VW>), dim3(((unsigned)a.items + SI_REDUCE_COOP_SLOTS - 1) / SI_REDUCE_COOP_SLOTS),
                            dim3(RD_COOP_THREADS), 0, stream, a);
     }
@@ -385,18 +310,10 @@ int si_hip_reduce_f16(const SiReduceDesc* d, const void* in, void* out, si_strea
 
 const char* si_hip_reduce_kernel_name(const SiReduceDesc* d, const void* in, const void* out, int half) {
     if (check_desc(d) != 0) return "none";
-    static const char* const names[4][4] = {
-        {"reduce_row_group_kernel<float, 4>", "reduce_row_group_kernel<float, 1>", "reduce_row_group_kernel<_Float16, 8>",
-         "reduce_row_group_kernel<_Float16, 1>"},
-        {"reduce_row_block_kernel<float, 4>", "reduce_row_block_kernel<float, 1>", "reduce_row_block_kernel<_Float16, 8>",
-         "reduce_row_block_kernel<_Float16, 1>"},
-        {"reduce_col_lane_kernel<float, 4>", "reduce_col_lane_kernel<float, 1>", "reduce_col_lane_kernel<_Float16, 8>",
-         "reduce_col_lane_kernel<_Float16, 1>"},
-        {"reduce_col_coop_kernel<float, 4>", "reduce_col_coop_kernel<float, 1>", "reduce_col_coop_kernel<_Float16, 8>",
-         "reduce_col_coop_kernel<_Float16, 1>"},
-    };
+    static const char* const names[4][4] = {SI_KERNEL_NAMES("reduce_row_group_kernel"), SI_KERNEL_NAMES("reduce_row_block_kernel"),
+                                            SI_KERNEL_NAMES("reduce_col_lane_kernel"), SI_KERNEL_NAMES("reduce_col_coop_kernel")};
     const bool vec = (half ? vector_width<_Float16>(d, in, out) : vector_width<float>(d, in, out)) > 1;
-    return names[form_of(d)][(half ? 2 : 0) + (vec ? 0 : 1)];
+    return names[form_of(d)][si_kernel_name_index(half != 0, vec)];
 }
 
 }  // extern "C"

@@ -345,6 +345,10 @@ __device__ __forceinline__ void si_yolo_tile_one_image(const Args& a, float* out
     }
 }
 
+// ---- reductions: combine operations, lane butterfly, workgroup combine, row tile, position walk (device), and the host plan they go with
+#include "si_reduce_dev.h"
+static_assert(SI_PLAN_BADARG == SI_E_BADARG && SI_PLAN_UNSUPPORTED == SI_E_UNSUPPORTED, "si_reduce_plan.h returns the C-ABI's codes");
+
 // ---- diagnostic build only (-DSI_DIAG_STAMPS; tools/conv_diag.py): per-workgroup s_memtime / s_memrealtime stamps at the phase
 // boundaries of a kernel, written to a __device__ array of their own that nothing else reads.  In the product build no stamp
 // executes and every macro expands to nothing.  Slots: [0] realtime at start, [1..5] cycle stamps, [6] realtime at end, [7] hw id.

@@ -34,7 +34,7 @@ namespace {
 
 constexpr int SM_THREADS = 256;
 constexpr int SM_WAVES = SM_THREADS / 64;
-constexpr int SM_LANE_ELEMS = 16;   // floats of a row that a lane of the group / block forms keeps
+constexpr int SM_LANE_ELEMS = SI_ROW_LANE_ELEMS;   // floats of a row that a lane of the group / block forms keeps
 constexpr int SM_GROUP_ITEMS = 4;   // items per lane that size a group
 
 static_assert(SI_SOFTMAX_GROUP_MAX_C == 64 * SM_LANE_ELEMS && SI_SOFTMAX_BLOCK_MAX_C == SM_THREADS * SM_LANE_ELEMS, "thresholds follow the register tile");
@@ -58,89 +58,36 @@ __device__ __forceinline__ float sm_ref(float m) { return m == -INFINITY ? 0.0f 
 __device__ __forceinline__ float sm_finish(int log, float v, float k) { return log ? v - k : v * k; }
 __device__ __forceinline__ float sm_row_const(int log, float s) { return log ? __logf(s) : __builtin_amdgcn_rcpf(s); }
 
-// butterflies over the xor offsets below `lanes` (a power of two <= 64): every lane of the team ends with the same bits (max and +
-// are commutative: both partners of an exchange form the same value)
-__device__ __forceinline__ float sm_team_max(float v, int lanes) {
-    for (int off = lanes >> 1; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-    return v;
-}
-__device__ __forceinline__ float sm_team_sum(float v, int lanes) {
-    for (int off = lanes >> 1; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-// the whole workgroup: per wave as above, then the wave values in index order (every thread reads all of them)
-__device__ __forceinline__ float sm_block_max(float v, float* part) {
-    v = sm_team_max(v, 64);
-    if (((int)threadIdx.x & 63) == 0) part[(int)threadIdx.x >> 6] = v;
-    __syncthreads();
-    float r = part[0];
-#pragma unroll
-    for (int w = 1; w < SM_WAVES; ++w) r = fmaxf(r, part[w]);
-    return r;
-}
-__device__ __forceinline__ float sm_block_sum(float v, float* part) {
-    v = sm_team_sum(v, 64);
-    if (((int)threadIdx.x & 63) == 0) part[(int)threadIdx.x >> 6] = v;
-    __syncthreads();
-    float r = part[0];
-#pragma unroll
-    for (int w = 1; w < SM_WAVES; ++w) r += part[w];
-    return r;
+// the maximum is SiMaxNum (fmaxf skips a NaN, on purpose: above), the sum SiSum; both are commutative, so every lane of a team and every
+// thread of a workgroup ends with the same bits
+template <bool BLOCK, typename Op>
+__device__ __forceinline__ float sm_combine(float v, int lanes, float* part) {
+    return BLOCK ? si_block<Op, SM_WAVES>(v, part) : si_team<Op>(v, lanes);
 }
 
 // the register-resident row: BLOCK = one workgroup per row, else a group of 1 << a.lg lanes per row
 template <typename T, int VW, bool BLOCK>
 __device__ __forceinline__ void sm_row_in_registers(const SmArgs& a) {
-    constexpr int ITEMS = SM_LANE_ELEMS / VW;
+    using Tile = SiRowTile<T, VW, SM_THREADS, BLOCK>;
     __shared__ float part_m[SM_WAVES], part_s[SM_WAVES];
-    const int tid = (int)threadIdx.x;
-    const int L = BLOCK ? SM_THREADS : (1 << a.lg);
-    const int j = BLOCK ? tid : (tid & (L - 1));
-    const int row = BLOCK ? (int)blockIdx.x : (int)blockIdx.x * (SM_THREADS >> a.lg) + (tid >> a.lg);
-    const bool live = row < a.rows;   // (a dead row's lanes load and store nothing but take part in every exchange)
+    const Tile tile(a.lg);
+    typename Tile::Regs v;
+    const int row = (int)blockIdx.x * tile.rows_per_block + tile.sub;
+    const bool live = row < a.rows;
     const T* const in = static_cast<const T*>(a.in) + (live ? row : 0) * a.in_ld;
-    float v[ITEMS][VW];
-    float m = -INFINITY;
-#pragma unroll
-    for (int i = 0; i < ITEMS; ++i) {
-        const int item = i * L + j;
-        if (live && item < a.cv) {
-            si_load_vec<T, VW>(in + item * VW, v[i]);
-#pragma unroll
-            for (int e = 0; e < VW; ++e) m = fmaxf(m, v[i][e]);
-        } else {
-#pragma unroll
-            for (int e = 0; e < VW; ++e) v[i][e] = 0.0f;
-        }
-    }
-    m = BLOCK ? sm_block_max(m, part_m) : sm_team_max(m, L);
-    float s = 0.0f;
-#pragma unroll
-    for (int i = 0; i < ITEMS; ++i) {
-        if (live && i * L + j < a.cv) {
-#pragma unroll
-            for (int e = 0; e < VW; ++e) {
-                const float d = v[i][e] - m;
-                const float ex = __expf(d);
-                s += ex;
-                v[i][e] = a.log ? d : ex;
-            }
-        }
-    }
-    s = BLOCK ? sm_block_sum(s, part_s) : sm_team_sum(s, L);
+    const int log = a.log;
+    float m = tile.load_row(v, in, live, a.cv, -INFINITY, [](float m, float x) { return SiMaxNum::apply(m, x); });
+    m = sm_combine<BLOCK, SiMaxNum>(m, tile.L, part_m);
+    float s = tile.update_row(v, live, a.cv, 0.0f, [=](float s, float& x) {
+        const float d = x - m;
+        const float ex = __expf(d);
+        x = log ? d : ex;
+        return s + ex;
+    });
+    s = sm_combine<BLOCK, SiSum>(s, tile.L, part_s);
     if (!live) return;
-    const float k = sm_row_const(a.log, s);
-    T* const out = static_cast<T*>(a.out) + row * a.out_ld;
-#pragma unroll
-    for (int i = 0; i < ITEMS; ++i) {
-        const int item = i * L + j;
-        if (item < a.cv) {
-#pragma unroll
-            for (int e = 0; e < VW; ++e) v[i][e] = sm_finish(a.log, v[i][e], k);
-            si_store_vec<T, VW>(out + item * VW, v[i]);
-        }
-    }
+    const float k = sm_row_const(log, s);
+    tile.store_row(v, static_cast<T*>(a.out) + row * a.out_ld, a.cv, [=](float x) { return sm_finish(log, x, k); });
 }
 
 template <typename T, int VW>
@@ -168,9 +115,9 @@ __global__ __launch_bounds__(SM_THREADS) void softmax_block_online_kernel(SmArgs
         for (int e = 0; e < VW; ++e) s += __expf(x[e] - ref);
         m = mn;
     }
-    const float M = sm_block_max(m, part_m);
+    const float M = si_block<SiMaxNum, SM_WAVES>(m, part_m);
     s = s * __expf(m - sm_ref(M));
-    s = sm_block_sum(s, part_s);
+    s = si_block<SiSum, SM_WAVES>(s, part_s);
     const float k = sm_row_const(a.log, s);
     T* const out = static_cast<T*>(a.out) + row * a.out_ld;
     for (int item = tid; item < a.cv; item += SM_THREADS) {
@@ -273,15 +220,8 @@ __global__ __launch_bounds__(SM_THREADS) void softmax_strided_online_kernel(SmAr
 // everything that can be decided without a device: SI_E_BADARG / SI_E_UNSUPPORTED / 0
 int check_desc(const SiSoftmaxDesc* d) {
     if (!d) return SI_E_BADARG;
-    if (d->n <= 0 || d->h <= 0 || d->w <= 0 || d->c <= 0) return SI_E_BADARG;
-    if (d->in_ld < d->c || d->out_ld < d->c) return SI_E_BADARG;
     if (d->axis < 0 || d->axis > 3 || (d->log != 0 && d->log != 1)) return SI_E_BADARG;
-    const uint64_t rows = (uint64_t)d->n * (uint64_t)d->h;   // < 2^62
-    if (rows > SI_INDEX_LIMIT || rows * (uint64_t)d->w > SI_INDEX_LIMIT) return SI_E_UNSUPPORTED;
-    const uint64_t pix = rows * (uint64_t)d->w;
-    // offsets, and with them the grids: at most one workgroup per pixel, at most one lane per element (c <= ld)
-    if (pix * (uint64_t)d->in_ld > SI_INDEX_LIMIT || pix * (uint64_t)d->out_ld > SI_INDEX_LIMIT) return SI_E_UNSUPPORTED;
-    return 0;
+    return si_check_reduce_views(d->n, d->h, d->w, d->c, d->in_ld, d->out_ld, si_masked_pixels(d->n, d->h, d->w, 0), d->c);
 }
 
 enum Form { kGroup, kBlock, kBlockOnline, kStrided, kStridedOnline };
@@ -316,7 +256,7 @@ int launch(const SiSoftmaxDesc* d, const T* in, T* out, hipStream_t stream) {
         case kGroup: {
             // lanes per row: the power of two at or above cv / per, at most 64 (then up to SM_LANE_ELEMS / VW items per lane)
             constexpr int per = SM_LANE_ELEMS / VW < SM_GROUP_ITEMS ? SM_LANE_ELEMS / VW : SM_GROUP_ITEMS;
-            while ((1 << a.lg) < 64 && (1 << a.lg) * per < a.cv) ++a.lg;
+            a.lg = si_group_lg(a.cv, per);
             const int rows_per_block = SM_THREADS >> a.lg;
             hipLaunchKernelGGL((softmax_group_kernel<T, VW>), dim3((unsigned)((a.rows + rows_per_block - 1) / rows_per_block)), block, 0, stream, a);
             break;
@@ -363,18 +303,11 @@ int si_hip_softmax_f16(const SiSoftmaxDesc* d, const void* in, void* out, si_str
 
 const char* si_hip_softmax_kernel_name(const SiSoftmaxDesc* d, const void* in, const void* out, int half) {
     if (check_desc(d) != 0) return "none";
-    static const char* const names[5][4] = {
-        {"softmax_group_kernel<float, 4>", "softmax_group_kernel<float, 1>", "softmax_group_kernel<_Float16, 8>", "softmax_group_kernel<_Float16, 1>"},
-        {"softmax_block_kernel<float, 4>", "softmax_block_kernel<float, 1>", "softmax_block_kernel<_Float16, 8>", "softmax_block_kernel<_Float16, 1>"},
-        {"softmax_block_online_kernel<float, 4>", "softmax_block_online_kernel<float, 1>", "softmax_block_online_kernel<_Float16, 8>",
-         "softmax_block_online_kernel<_Float16, 1>"},
-        {"softmax_strided_kernel<float, 4>", "softmax_strided_kernel<float, 1>", "softmax_strided_kernel<_Float16, 8>",
-         "softmax_strided_kernel<_Float16, 1>"},
-        {"softmax_strided_online_kernel<float, 4>", "softmax_strided_online_kernel<float, 1>", "softmax_strided_online_kernel<_Float16, 8>",
-         "softmax_strided_online_kernel<_Float16, 1>"},
-    };
+    static const char* const names[5][4] = {SI_KERNEL_NAMES("softmax_group_kernel"), SI_KERNEL_NAMES("softmax_block_kernel"),
+                                            SI_KERNEL_NAMES("softmax_block_online_kernel"), SI_KERNEL_NAMES("softmax_strided_kernel"),
+                                            SI_KERNEL_NAMES("softmax_strided_online_kernel")};
     const bool vec = (half ? vector_width<_Float16>(d, in, out) : vector_width<float>(d, in, out)) > 1;
-    return names[form_of(d)][(half ? 2 : 0) + (vec ? 0 : 1)];
+    return names[form_of(d)][si_kernel_name_index(half != 0, vec)];
 }
 
 }  // extern "C"

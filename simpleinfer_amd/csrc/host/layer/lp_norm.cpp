@@ -3,8 +3,6 @@
 #include <cmath>
 #include <cstring>
 
-#include "softmax.h"
-
 namespace SimpleInfer {
 
 DEFINE_LAYER_REGISTRY(LpNorm);
@@ -69,39 +67,7 @@ Status LpNorm::Init(const pnnx::Operator* op) {
         keepdim_ = true;
         return Status::kSuccess;
     }
-    if (IsNone(op, "dim")) {
-        LOG(ERROR) << "LpNorm::Init fail [" << op->type << " without dim: the reduction to a scalar is not served]";
-        return Status::kUnsupport;
-    }
-    int one = 0;
-    if (Get(op, "dim", one)) {
-        dims_.push_back(one);
-    } else {
-        CHECK_BOOL(Get(op, "dim", dims_) && !dims_.empty());
-    }
-    if (FindParam(op, "keepdim")) CHECK_BOOL(Get(op, "keepdim", keepdim_));
-    if (!IsNoneOrText(op, "dtype")) {
-        LOG(ERROR) << "LpNorm::Init fail [" << op->type << " with a dtype: the result has the input's type here]";
-        return Status::kUnsupport;
-    }
-    return Status::kSuccess;
-}
-
-Status LpNorm::Mask(int rank, int& axes) const {
-    axes = 0;
-    for (int dim : dims_) {
-        const int axis = Softmax::NhwcAxis(dim, rank);
-        if (axis < 0) {
-            LOG(ERROR) << "LpNorm: dim " << dim << " of " << TupleString(dims_) << " is out of range for a rank-" << rank << " tensor";
-            return Status::kUnsupport;
-        }
-        if (axes & (1 << axis)) {
-            LOG(ERROR) << "LpNorm: dim " << dim << " appears twice in " << TupleString(dims_);
-            return Status::kFail;
-        }
-        axes |= 1 << axis;
-    }
-    return axes != 0 ? Status::kSuccess : Status::kFail;
+    return ReadDimKeepdimDtype("LpNorm", op, dims_, keepdim_);
 }
 
 Status LpNorm::Validate() {
@@ -117,19 +83,14 @@ Status LpNorm::Validate() {
         LOG(ERROR) << "LpNorm::Validate fail [dim " << TupleString(dims_) << " of a rank-" << rank << " tensor " << ShapeString(is) << ": ranks 2 and 4 only]";
         return Status::kUnsupport;
     }
-    CHECK_STATUS(Mask(rank, axes_));
-    const int kC = 8;   // SI_REDUCE_AXIS_C
-    if ((axes_ & kC) && axes_ != kC) {
-        LOG(ERROR) << "LpNorm::Validate fail [dim " << TupleString(dims_) << " of " << ShapeString(is)
-                   << " (NHWC) reduces the channels together with another axis: the channel dim alone, or any of the others]";
-        return Status::kUnsupport;
-    }
+    CHECK_STATUS(DimsToNhwcMask("LpNorm", dims_, rank, axes_));
+    CHECK_STATUS(RefuseChannelMix("LpNorm", dims_, is, axes_));
     // the shape the rule gives, as the engine holds it (NHWC; [N, F]; [N, H, W] and [N, C] for the two served keepdim=False cases)
     std::vector<int> want;
     if (normalize_) {
         want = is;
     } else if (!keepdim_) {
-        const bool pixel_norm = rank == 4 && axes_ == kC;        // dim=1: [N, H, W], the [N, H, W, 1] memory
+        const bool pixel_norm = rank == 4 && axes_ == 8;         // dim=1: [N, H, W], the [N, H, W, 1] memory
         const bool pool = rank == 4 && axes_ == (2 | 4);         // dims (2, 3): [N, C], the [N, 1, 1, C] memory
         if (!pixel_norm && !pool) {
             LOG(ERROR) << "LpNorm::Validate fail [keepdim=False over dim " << TupleString(dims_) << " of a rank-" << rank
@@ -138,10 +99,8 @@ Status LpNorm::Validate() {
         }
         if (pixel_norm) want = {id[0], id[1], id[2]};
         else want = {id[0], id[3]};
-    } else if (rank == 4) {
-        for (int a = 0; a < 4; ++a) want.push_back(((axes_ >> a) & 1) ? 1 : id[a]);
     } else {
-        want = {(axes_ & 1) ? 1 : id[0], (axes_ & kC) ? 1 : id[3]};
+        want = KeptDimsShape(id, rank, axes_);
     }
     if (!IsSameShape(want, out.Shape())) {
         LOG(ERROR) << "LpNorm::Validate fail [the file's output is " << ShapeString(out.Shape()) << ", the rule gives " << ShapeString(want)
@@ -168,7 +127,7 @@ bool LpNorm::SetNormalize(TensorNode* out) {
 
 bool LpNorm::MakeDesc(const Tensor& input, const Tensor& output, SiLpNormDesc& d) const {
     int id[4], axes = 0;
-    if (!NhwcDims(input, id) || Status::kSuccess != Mask((int)input.Shape().size(), axes)) return false;
+    if (!NhwcDims(input, id) || Status::kSuccess != DimsToNhwcMask("LpNorm", dims_, (int)input.Shape().size(), axes)) return false;
     memset(&d, 0, sizeof(d));
     d.n = id[0]; d.h = id[1]; d.w = id[2]; d.c = id[3];
     d.in_ld = input.PixelStride();

@@ -2,8 +2,6 @@
 
 #include <cstring>
 
-#include "softmax.h"
-
 namespace SimpleInfer {
 
 DEFINE_LAYER_REGISTRY(Reduce);
@@ -14,40 +12,8 @@ Status Reduce::Init(const pnnx::Operator* op) {
     op_code_ = op->type == "torch.sum" ? SI_REDUCE_SUM : op->type == "torch.amax" ? SI_REDUCE_AMAX : op->type == "torch.amin" ? SI_REDUCE_AMIN : SI_REDUCE_MEAN;
     dims_.clear();
     axes_ = 0;
-    if (IsNone(op, "dim")) {
-        LOG(ERROR) << "Reduce::Init fail [" << op->type << " without dim: the reduction to a scalar is not served]";
-        return Status::kUnsupport;
-    }
-    int one = 0;
-    if (Get(op, "dim", one)) {
-        dims_.push_back(one);
-    } else {
-        CHECK_BOOL(Get(op, "dim", dims_) && !dims_.empty());
-    }
     keepdim_ = false;
-    if (FindParam(op, "keepdim")) CHECK_BOOL(Get(op, "keepdim", keepdim_));
-    if (!IsNoneOrText(op, "dtype")) {
-        LOG(ERROR) << "Reduce::Init fail [" << op->type << " with a dtype: the result has the input's type here]";
-        return Status::kUnsupport;
-    }
-    return Status::kSuccess;
-}
-
-Status Reduce::Mask(int rank, int& axes) const {
-    axes = 0;
-    for (int dim : dims_) {
-        const int axis = Softmax::NhwcAxis(dim, rank);
-        if (axis < 0) {
-            LOG(ERROR) << "Reduce: dim " << dim << " of " << TupleString(dims_) << " is out of range for a rank-" << rank << " tensor";
-            return Status::kUnsupport;
-        }
-        if (axes & (1 << axis)) {
-            LOG(ERROR) << "Reduce: dim " << dim << " appears twice in " << TupleString(dims_);
-            return Status::kFail;
-        }
-        axes |= 1 << axis;
-    }
-    return axes != 0 ? Status::kSuccess : Status::kFail;
+    return ReadDimKeepdimDtype("Reduce", op, dims_, keepdim_);
 }
 
 Status Reduce::Validate() {
@@ -63,12 +29,8 @@ Status Reduce::Validate() {
         LOG(ERROR) << "Reduce::Validate fail [dim " << TupleString(dims_) << " of a rank-" << rank << " tensor " << ShapeString(is) << ": ranks 2 and 4 only]";
         return Status::kUnsupport;
     }
-    CHECK_STATUS(Mask(rank, axes_));
-    if ((axes_ & SI_REDUCE_AXIS_C) && axes_ != SI_REDUCE_AXIS_C) {
-        LOG(ERROR) << "Reduce::Validate fail [dim " << TupleString(dims_) << " of " << ShapeString(is)
-                   << " (NHWC) reduces the channels together with another axis: the channel dim alone, or any of the others]";
-        return Status::kUnsupport;
-    }
+    CHECK_STATUS(DimsToNhwcMask("Reduce", dims_, rank, axes_));
+    CHECK_STATUS(RefuseChannelMix("Reduce", dims_, is, axes_));
     const bool pool = rank == 4 && axes_ == (SI_REDUCE_AXIS_H | SI_REDUCE_AXIS_W);
     if (!keepdim_ && !pool) {
         LOG(ERROR) << "Reduce::Validate fail [keepdim=False over dim " << TupleString(dims_) << " of a rank-" << rank
@@ -76,14 +38,7 @@ Status Reduce::Validate() {
         return Status::kUnsupport;
     }
     // the shape the rule gives, as the engine holds it (NHWC; [N, F]; [N, C] for the pool without keepdim)
-    std::vector<int> want;
-    if (!keepdim_) {
-        want = {id[0], id[3]};
-    } else if (rank == 4) {
-        for (int a = 0; a < 4; ++a) want.push_back(((axes_ >> a) & 1) ? 1 : id[a]);
-    } else {
-        want = {(axes_ & SI_REDUCE_AXIS_N) ? 1 : id[0], (axes_ & SI_REDUCE_AXIS_C) ? 1 : id[3]};
-    }
+    const std::vector<int> want = keepdim_ ? KeptDimsShape(id, rank, axes_) : std::vector<int>{id[0], id[3]};
     if (!IsSameShape(want, out.Shape())) {
         LOG(ERROR) << "Reduce::Validate fail [the file's output is " << ShapeString(out.Shape()) << ", the rule gives " << ShapeString(want)
                    << " for dim " << TupleString(dims_) << (keepdim_ ? " keepdim=True" : " keepdim=False") << " of " << ShapeString(is) << " (NHWC)]";
@@ -99,7 +54,7 @@ Status Reduce::Validate() {
 
 bool Reduce::MakeDesc(const Tensor& input, const Tensor& output, SiReduceDesc& d) const {
     int id[4], axes = 0;
-    if (!NhwcDims(input, id) || Status::kSuccess != Mask((int)input.Shape().size(), axes)) return false;
+    if (!NhwcDims(input, id) || Status::kSuccess != DimsToNhwcMask("Reduce", dims_, (int)input.Shape().size(), axes)) return false;
     memset(&d, 0, sizeof(d));
     d.n = id[0]; d.h = id[1]; d.w = id[2]; d.c = id[3];
     d.in_ld = input.PixelStride();

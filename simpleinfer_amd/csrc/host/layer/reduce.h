@@ -34,8 +34,6 @@ public:
     int axes_ = 0;                   // the NHWC mask, set by Validate
 
 private:
-    // the mask of dims_ on a tensor of this rank; kUnsupport / kFail with the reason logged
-    Status Mask(int rank, int& axes) const;
     bool MakeDesc(const Tensor& input, const Tensor& output, SiReduceDesc& d) const;
 };
 

@@ -19,18 +19,7 @@ Status Softmax::Init(const pnnx::Operator* op) {
     return Status::kSuccess;
 }
 
-int Softmax::NhwcAxis(int dim, int rank) {
-    if (dim < 0) dim += rank;
-    if (dim < 0 || dim >= rank) return -1;
-    if (2 == rank) return 1 == dim ? 3 : 0;
-    if (4 != rank) return -1;
-    switch (dim) {   // Cat::NhwcAxis
-        case 1: return 3;
-        case 2: return 1;
-        case 3: return 2;
-        default: return 0;
-    }
-}
+int Softmax::NhwcAxis(int dim, int rank) { return NhwcAxisOfDim(dim, rank); }
 
 Status Softmax::Validate() {
     CHECK_STATUS(Layer::Validate());

@@ -23,46 +23,25 @@ eval_graph: a torch-float64 evaluator of build_toy_superpoint / build_toy_embedd
 for the fp16-storage emulation.
 """
 import os
-import re
 
 import numpy as np
 
 from ct_reference import _ints, _parse, round_f16  # noqa: F401  (round_f16 re-exported)
+from reduction_reference import AXIS_C, AXIS_H, AXIS_N, AXIS_W, header_enum_of, kname_of, mask_axes, nhwc_mask, positions  # noqa: F401  (re-exported)
 
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "si_lpnorm.h")
 LPNORM_TYPES = ("F.normalize", "torch.norm")
-AXIS_N, AXIS_H, AXIS_W, AXIS_C = 1, 2, 4, 8
 MASKS = (8, 1, 2, 3, 4, 5, 6, 7)   # every supported mask: the channel axis alone, and every non-empty subset of {n, h, w}
 PS = (1, 2, float("inf"))
 U = 2.0 ** -24
 
 
-def header_enum(name):
-    return int(re.search(r"\b%s = (\d+)" % name, open(HEADER).read()).group(1))
-
-
-def mask_axes(axes):
-    return tuple(a for a in range(4) if (axes >> a) & 1)
+header_enum = header_enum_of(HEADER)
+kname = kname_of("lpnorm")
 
 
 def out_shape(shape, axes, normalize=False):
     return tuple(shape) if normalize else tuple(1 if (axes >> a) & 1 else s for a, s in enumerate(shape))
-
-
-def positions(shape, axes):
-    return int(np.prod([shape[a] for a in mask_axes(axes)]))
-
-
-def nhwc_mask(dims, rank):
-    """torch's dim (an int or a sequence) on an NCHW (or [N, F]) tensor -> the NHWC bit mask of the descriptor"""
-    mask = 0
-    for dim in ((dims,) if isinstance(dims, int) else dims):
-        dim = dim + rank if dim < 0 else dim
-        assert 0 <= dim < rank and rank in (2, 4), (dim, rank)
-        axis = (0, 3)[dim] if rank == 2 else (0, 3, 1, 2)[dim]
-        assert not mask & (1 << axis), "a repeated dim"
-        mask |= 1 << axis
-    return mask
 
 
 # ---- float64 ---------------------------------------------------------------------------------------------------------------------------------
@@ -113,13 +92,6 @@ def vectorised(shape, axes, dtype, normalize=False, **views):
     if normalize or not axes & AXIS_C:
         ks += [views.get("out_ld") or oc, views.get("out_c_off", 0)]
     return all(int(k) % v == 0 for k in ks)
-
-
-def kname(form, dtype, vec):
-    base = "lpnorm_%s_kernel" % form
-    if np.dtype(dtype) == np.float32:
-        return base + ("<float, 4>" if vec else "<float, 1>")
-    return base + ("<_Float16, 8>" if vec else "<_Float16, 1>")
 
 
 def expected_kernel(shape, axes, dtype, normalize=False, **views):

@@ -13,26 +13,19 @@ eval_graph: a torch-float64 evaluator of a PnnxBuilder graph for the five softma
 build_toy_segnet and build_toy_unet, with the rnd= hook of pool_reference.eval_graph for the fp16-storage emulation.
 """
 import os
-import re
 
 import numpy as np
 
 from ct_reference import _ints, _parse, round_f16  # noqa: F401  (round_f16 re-exported)
+from reduction_reference import header_enum_of, kname_of
 
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "si_softmax.h")
 SOFTMAX_TYPES = ("nn.Softmax", "nn.LogSoftmax", "nn.Softmax2d", "F.softmax", "F.log_softmax")
 FORMS = ("group", "block", "block_online", "strided", "strided_online")
 
 
-def header_enum(name):
-    return int(re.search(r"\b%s = (\d+)" % name, open(HEADER).read()).group(1))
-
-
-def kname(form, dtype, vec):
-    base = "softmax_%s_kernel" % form
-    if np.dtype(dtype) == np.float32:
-        return base + ("<float, 4>" if vec else "<float, 1>")
-    return base + ("<_Float16, 8>" if vec else "<_Float16, 1>")
+header_enum = header_enum_of(HEADER)
+kname = kname_of("softmax")
 
 
 def expected_form(shape, axis):
