@@ -67,8 +67,11 @@ int si_hip_host_free(void* ptr) { if (ptr) SI_HIP_TRY(hipHostFree(ptr)); return 
 // then run asynchronously at the link rate instead of being staged through the runtime's bounce buffers
 int si_hip_host_register(void* ptr, size_t bytes) {
     if (!ptr || bytes == 0) return SI_E_BADARG;
-    SI_HIP_TRY(hipHostRegister(ptr, bytes, hipHostRegisterDefault));
-    return 0;
+    hipError_t e = hipHostRegister(ptr, bytes, hipHostRegisterDefault);
+    // where the driver cannot pin memory in place (a virtual machine) the caller goes on with staged copies: the refusal must not
+    // stay behind as the runtime's last error, where the next kernel launch would report it as its own
+    if (e != hipSuccess) (void)hipGetLastError();
+    return (int)e;
 }
 int si_hip_host_unregister(void* ptr) { if (ptr) SI_HIP_TRY(hipHostUnregister(ptr)); return 0; }
 
