@@ -175,6 +175,12 @@ class SiXcorrDesc(C.Structure):
         ("per_sample", C.c_int), ("act", C.c_int), ("act_param", C.c_float)]
 
 
+class SiBorderConvDesc(C.Structure):
+    """include/si_border.h; pt / pl: the pad of both sides of H / of W, mode: an SI_PAD_* code (reflect 1, replicate 2, circular 3)"""
+    _fields_ = [(k, C.c_int) for k in ("n", "ih", "iw", "ic", "in_ld", "oh", "ow", "oc", "out_ld", "kh", "kw", "sh", "sw", "dh", "dw", "pt", "pl",
+                                       "mode", "groups", "has_bias", "act1", "has_residual", "res_ld", "act2")] + [("act_param", C.c_float)]
+
+
 class SiDetectPostDesc(C.Structure):
     """include/si_detect.h; ne = 4 + objectness + classes + extra, ld / image_ld the element strides of a row (ROWS) or a channel (CHANNELS) and
     of an image"""
@@ -502,7 +508,17 @@ def hip():
         "si_hip_lpnorm_f16": (i, [C.POINTER(SiLpNormDesc), vp, vp, vp]),
         "si_hip_lpnorm_kernel_name": (C.c_char_p, [C.POINTER(SiLpNormDesc), vp, vp, i]),
     }
-    for name, (res, args) in (list(sig.items()) + list(norm.items()) + list(pad.items()) + list(pool.items()) + list(softmax.items()) +
+    # include/si_border.h: nn.Conv2d with padding_mode reflect / replicate / circular
+    border_ = {
+        "si_hip_conv2d_border_supported": (i, [C.POINTER(SiBorderConvDesc), i]),
+        "si_hip_conv2d_border_weight_elems": (sz, [C.POINTER(SiBorderConvDesc), i]),
+        "si_hip_conv2d_border_pack_weight_host": (i, [C.POINTER(SiBorderConvDesc), vp, vp, i]),
+        "si_hip_conv2d_border_f32": (i, [C.POINTER(SiBorderConvDesc), vp, vp, vp, vp, vp, vp]),
+        "si_hip_conv2d_border_f16": (i, [C.POINTER(SiBorderConvDesc), vp, vp, vp, vp, vp, vp]),
+        "si_hip_conv2d_border_kernel_name": (C.c_char_p, [C.POINTER(SiBorderConvDesc), vp, vp, i]),
+        "si_hip_conv2d_border_source_index": (i, [i, i, i]),
+    }
+    for name, (res, args) in (list(border_.items()) + list(sig.items()) + list(norm.items()) + list(pad.items()) + list(pool.items()) + list(softmax.items()) +
                               list(superres.items()) + list(slice_.items()) + list(reduce_.items()) + list(act.items()) + list(permute_.items()) +
                               list(attention_.items()) + list(deform_.items()) + list(grid_.items()) + list(roi_.items()) + list(rnn_.items()) +
                               list(binary_.items()) + list(conv1d_.items()) + list(xcorr_.items()) + list(detect_.items()) + list(lpnorm_.items())):
@@ -529,6 +545,7 @@ def hip():
     L._si_xcorr_signatures = xcorr_
     L._si_detect_signatures = detect_
     L._si_lpnorm_signatures = lpnorm_
+    L._si_border_signatures = border_
     _hip = L
     return L
 

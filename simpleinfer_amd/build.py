@@ -22,6 +22,12 @@ HOST_DIR = os.path.join(PKG, "csrc", "host")
 LIB_HIP = os.path.join(PKG, "libsi_hip.so")
 LIB_HOST = os.path.join(PKG, "libsimpleinfer_amd.so")
 ARCH = "gfx950"
+# Per-file device flags.  conv_border.hip is compiled with the target feature packed-fp32-ops switched off: its fp32 arithmetic is MFMA plus
+# a scalar epilogue, and the bit rules of include/si_border.h (an output element's bits do not depend on its lane's neighbours) must not come
+# to depend on the compiler pairing two lanes' epilogue operations into v_pk_*_f32.  Today neither build of the file contains such an
+# instruction (disassembly), so the results are the same; what the flag does change is the code generator's choices around them: 30 - 58
+# VGPRs and 8 waves / SIMD for seven of the eight instances with it, 55 - 58 VGPRs and 7 waves / SIMD without.
+FILE_FLAGS = {"conv_border.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _newest(paths):
@@ -68,7 +74,7 @@ def build_hip(force=False, verbose_resources=False, defines=(), out=None, objdir
         o = os.path.join(objdir, os.path.basename(s) + ".o")
         objs.append(o)
         if force or not os.path.exists(o) or os.path.getmtime(o) < max(os.path.getmtime(s), hdr_time):
-            cmd = base + ["-c", s, "-o", o]
+            cmd = base + FILE_FLAGS.get(os.path.basename(s), []) + ["-c", s, "-o", o]
             print("+ " + " ".join(cmd), flush=True)
             procs.append(subprocess.Popen(cmd))
             if len(procs) >= 6:

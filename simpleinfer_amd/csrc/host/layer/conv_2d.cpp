@@ -29,6 +29,8 @@ Status Conv2d::Init(const std::map<std::string, pnnx::Parameter>& params,
         padding_mode_ = PaddingMode::kReplicate;
     } else if (mode == "reflect") {
         padding_mode_ = PaddingMode::kReflect;
+    } else if (mode == "circular") {
+        padding_mode_ = PaddingMode::kCircular;
     } else {
         LOG(ERROR) << "Conv2d::Init fail [unsupport padding mode " << mode << "]";
         return Status::kUnsupport;
@@ -79,11 +81,6 @@ Status Conv2d::Init(const std::map<std::string, pnnx::Parameter>& params,
         memcpy(bias_.data(), b.data.data(), b.data.size());
     }
     device_ready_ = false;
-
-    if (padding_mode_ != PaddingMode::kZeros) {
-        // the reference parses replicate/reflect but every path pads with zeros (conv_2d.cpp:260)
-        LOG(WARNING) << "Conv2d: padding_mode " << mode << " computes with zero padding (as the reference does)";
-    }
     return Status::kSuccess;
 }
 
@@ -108,11 +105,12 @@ bool Conv2d::CanFuseSibling(const Conv2d& o) const {
                c.dilation_w_ == 1 && c.padding_t_ == 0 && c.padding_l_ == 0 && c.groups_ == 1 && c.residual_node_ == nullptr &&
                c.act2_ == SI_ACT_NONE && c.sibling_ == nullptr;
     };
-    return this != &o && plain1x1(*this) && plain1x1(o) && in_channels_ == o.in_channels_ && act1_ == o.act1_ &&
+    return this != &o && !Bordered() && !o.Bordered() && plain1x1(*this) && plain1x1(o) && in_channels_ == o.in_channels_ && act1_ == o.act1_ &&
            act_param_ == o.act_param_ && use_bias_ == o.use_bias_ && out_channels_ % 32 == 0 && in_channels_ % 32 == 0;
 }
 
 bool Conv2d::CanFuseStemProducer(const Conv2d& stem) const {
+    if (Bordered() || stem.Bordered()) return false;   // (a bordered layer runs alone: the fused kernels pad with zeros)
     if (residual_node_ || sibling_ || up_node_ || stem_producer_ || stem.residual_node_ || stem.sibling_ || stem.up_node_) return false;
     if (input_tensor_nodes_.size() != 1 || output_tensor_nodes_.size() != 1 || stem.input_tensor_nodes_.size() != 1 ||
         stem.output_tensor_nodes_.size() != 1 || stem.output_tensor_nodes_[0] != input_tensor_nodes_[0])
@@ -135,6 +133,7 @@ void Conv2d::SetStemProducer(Conv2d* stem) {
 }
 
 bool Conv2d::CanFuseStemPairProducer(const Conv2d& c1) const {
+    if (Bordered() || c1.Bordered()) return false;
     if (!c1.stem_producer_ || !c1.stem_mid_ || c1.residual_node_ || c1.sibling_ || c1.up_node_ || c1.pw_producer_ || c1.stem_pair_) return false;
     if (residual_node_ || up_node_ || stem_producer_ || pw_producer_ || stem_pair_ || act2_ != SI_ACT_NONE) return false;
     if (input_tensor_nodes_.size() != 1 || c1.output_tensor_nodes_.size() != 1 || c1.output_tensor_nodes_[0] != input_tensor_nodes_[0]) return false;
@@ -188,6 +187,7 @@ Status Conv2d::LaunchStemTriple(const Tensor& image, Tensor& out0, Tensor* out1)
 }
 
 bool Conv2d::CanFuseCv3Pair(const Conv2d& pair, const TensorNode* z) const {
+    if (Bordered() || pair.Bordered()) return false;
     if (!pair.pw_producer_ || !pair.pw_mid_ || pair.sibling_ || pair.up_node_ || pair.stem_producer_ || pair.stem_pair_ || pair.cv3_pair_) return false;
     if (residual_node_ || sibling_ || up_node_ || stem_producer_ || stem_pair_ || pw_producer_ || cv3_pair_ || act2_ != SI_ACT_NONE) return false;
     if (!z || input_tensor_nodes_.size() != 1 || output_tensor_nodes_.size() != 1 || pair.output_tensor_nodes_.size() != 1 || pair.input_tensor_nodes_.size() != 1) return false;
@@ -240,6 +240,7 @@ Status Conv2d::LaunchCv3(const Tensor& x, Tensor& output) {
 }
 
 bool Conv2d::CanFusePointwiseProducer(const Conv2d& pw) const {
+    if (Bordered() || pw.Bordered()) return false;
     if (sibling_ || up_node_ || stem_producer_ || pw_producer_ || pw.residual_node_ || pw.sibling_ || pw.up_node_ || pw.stem_producer_ || pw.pw_producer_) return false;
     if (input_tensor_nodes_.size() != 1 || output_tensor_nodes_.size() != 1 || pw.input_tensor_nodes_.size() != 1 ||
         pw.output_tensor_nodes_.size() != 1 || pw.output_tensor_nodes_[0] != input_tensor_nodes_[0])
@@ -281,6 +282,17 @@ Status Conv2d::Validate() {
     CHECK_STATUS(Layer::Validate());
     CHECK_STATUS(ValidateShape(1, 1));
     CHECK_STATUS(ValidateFloatLogged("Conv2d"));
+    if (Bordered()) {
+        // where torch raises: a reflect pad must be smaller than the dimension it pads, a circular pad must not exceed it
+        Dims4 in;
+        if (!GetDims4(input_tensor_nodes_[0]->tensor, in)) return Status::kErrorShape;
+        const int limit_h = padding_mode_ == PaddingMode::kReflect ? in.h - 1 : in.h, limit_w = padding_mode_ == PaddingMode::kReflect ? in.w - 1 : in.w;
+        if (padding_mode_ != PaddingMode::kReplicate && (padding_t_ > limit_h || padding_l_ > limit_w)) {
+            LOG(ERROR) << "Conv2d::Validate fail [a " << (padding_mode_ == PaddingMode::kReflect ? "reflect pad must be smaller than" : "circular pad must not exceed")
+                       << " the dimension it pads: input " << in.h << "x" << in.w << ", padding (" << padding_t_ << ", " << padding_l_ << ")]";
+            return Status::kUnsupport;
+        }
+    }
     return Status::kSuccess;
 }
 
@@ -293,7 +305,8 @@ SiConv2dDesc Conv2d::MakeDesc(const Tensor& input, const Tensor& output) const {
     d.n = in.n; d.ih = in.h; d.iw = in.w; d.ic = in.c; d.in_ld = input.PixelStride();
     d.oh = out.h; d.ow = out.w; d.oc = out.c; d.out_ld = output.PixelStride();
     d.kh = kernel_h_; d.kw = kernel_w_; d.sh = stride_h_; d.sw = stride_w_;
-    d.dh = dilation_h_; d.dw = dilation_w_; d.pt = padding_t_; d.pl = padding_l_;
+    d.dh = dilation_h_; d.dw = dilation_w_;
+    d.pt = Bordered() ? 0 : padding_t_; d.pl = Bordered() ? 0 : padding_l_;   // (bordered: the conv of the composition, over the padded tensor)
     d.groups = groups_;
     d.has_bias = use_bias_ ? 1 : 0;
     d.act1 = act1_; d.act2 = act2_; d.act_param = act_param_;
@@ -307,8 +320,43 @@ SiConv2dDesc Conv2d::StaticDesc(int extra_oc) const {
     SiConv2dDesc d;
     memset(&d, 0, sizeof(d));
     d.ic = in_channels_; d.oc = out_channels_ + extra_oc; d.kh = kernel_h_; d.kw = kernel_w_; d.groups = groups_;
-    d.sh = stride_h_; d.sw = stride_w_; d.dh = dilation_h_; d.dw = dilation_w_; d.pt = padding_t_; d.pl = padding_l_;
+    d.sh = stride_h_; d.sw = stride_w_; d.dh = dilation_h_; d.dw = dilation_w_;
+    d.pt = Bordered() ? 0 : padding_t_; d.pl = Bordered() ? 0 : padding_l_;
     return d;
+}
+
+SiBorderConvDesc Conv2d::BorderDesc(int n, int ih, int iw) const {
+    SiBorderConvDesc d;
+    memset(&d, 0, sizeof(d));
+    d.n = n; d.ih = ih; d.iw = iw; d.ic = in_channels_; d.in_ld = in_channels_;
+    d.kh = kernel_h_; d.kw = kernel_w_; d.sh = stride_h_; d.sw = stride_w_; d.dh = dilation_h_; d.dw = dilation_w_;
+    d.pt = padding_t_; d.pl = padding_l_;
+    const auto extent = [](int l, int p, int k, int s, int dil) { return s > 0 ? (l + 2 * p - dil * (k - 1) - 1) / s + 1 : 0; };
+    d.oh = extent(ih, d.pt, d.kh, d.sh, d.dh); d.ow = extent(iw, d.pl, d.kw, d.sw, d.dw); d.oc = out_channels_; d.out_ld = out_channels_;
+    d.mode = padding_mode_ == PaddingMode::kReflect ? SI_PAD_REFLECT : (padding_mode_ == PaddingMode::kCircular ? SI_PAD_CIRCULAR : SI_PAD_REPLICATE);
+    d.groups = groups_;
+    d.has_bias = use_bias_ ? 1 : 0;
+    d.act1 = act1_; d.act2 = act2_; d.act_param = act_param_;
+    d.res_ld = out_channels_;
+    return d;
+}
+
+// Where the one-launch kernel is taken, by measurement (tools/bench_border.py, profiles/border_35f9d12.txt; one launch / composition):
+//   fp32   3 -> 32 7x7: 3.66   16 -> 16: 0.49   32 -> 32: 1.35   64 .. 256 channels: 1.41 - 1.67
+//   fp16                       16 -> 16: 0.55   32 -> 32: 0.84   64 .. 256 channels: 2.23 - 5.05
+// The kernel takes the classes it wins -- from 8 input channels on, below 32 in fp32 and below 64 under fp16 storage --; every other layer takes
+// the composition, whose tuned zero-pad kernels (the small-channel stem, Winograd, the fast implicit GEMM, the fp16 tiles) more than pay for
+// the padded tensor's round trip.
+static const int kBorderMinChannels = 8, kBorderBelowChannelsF32 = 32, kBorderBelowChannelsF16 = 64;
+
+// a property of the layer's static shape (the policy above, groups, channels under fp16, the patch against LDS): asked on the smallest image
+// the pads allow.  What depends on the tensors (extents beyond 31 bits, grid limits, alignment) is asked at the launch, which demotes the
+// layer to the composition for good (LaunchBorder)
+bool Conv2d::BorderKernelServes(bool half) const {
+    if (!Bordered() || border_demoted_ || kernel_h_ <= 0 || kernel_w_ <= 0 || dilation_h_ <= 0 || dilation_w_ <= 0) return false;
+    if (in_channels_ < kBorderMinChannels || in_channels_ >= (half ? kBorderBelowChannelsF16 : kBorderBelowChannelsF32)) return false;
+    const SiBorderConvDesc d = BorderDesc(1, (kernel_h_ - 1) * dilation_h_ + 1 + padding_t_, (kernel_w_ - 1) * dilation_w_ + 1 + padding_l_);
+    return si_hip_conv2d_border_supported(&d, half ? 1 : 0) == 1;
 }
 
 // How a fused sibling's filters (SetSibling) enter an image.  kConcatOihw: ONE conv over the concatenated filters (OIHW: the sibling's rows
@@ -327,6 +375,14 @@ struct Conv2d::ImageRow {
     const char* demote;
     const char* pack_label;
 };
+
+// the fields of a layer's static shape the border kernel's weight image depends on
+static SiBorderConvDesc BorderImageDesc(const SiConv2dDesc* d) {
+    SiBorderConvDesc b;
+    memset(&b, 0, sizeof(b));
+    b.ic = d->ic; b.oc = d->oc; b.kh = d->kh; b.kw = d->kw; b.groups = d->groups;
+    return b;
+}
 
 const Conv2d::ImageRow& Conv2d::RowOf(WeightImage image) {
     static const ImageRow rows[] = {
@@ -353,8 +409,14 @@ const Conv2d::ImageRow& Conv2d::RowOf(WeightImage image) {
         /* kStemSplit3  */ {si_hip_conv2d_stem_split3_weight_elems, si_hip_conv2d_stem_split3_pack_weight_host, sizeof(uint16_t), SiblingRule::kNone,
                             "f32_split: stem conv %d -> %d has a weight outside fp16's range; the layer stays on the fp32 kernels",
                             "split stem weights (hi / lo halves)"},
+        /* kBorderF32   */ {[](const SiConv2dDesc* d) { const SiBorderConvDesc b = BorderImageDesc(d); return si_hip_conv2d_border_weight_elems(&b, 0); },
+                            [](const SiConv2dDesc* d, const float* w, void* p) { const SiBorderConvDesc b = BorderImageDesc(d); return si_hip_conv2d_border_pack_weight_host(&b, w, p, 0); },
+                            sizeof(float), SiblingRule::kNone, nullptr, "pack border weight"},
+        /* kBorderF16   */ {[](const SiConv2dDesc* d) { const SiBorderConvDesc b = BorderImageDesc(d); return si_hip_conv2d_border_weight_elems(&b, 1); },
+                            [](const SiConv2dDesc* d, const float* w, void* p) { const SiBorderConvDesc b = BorderImageDesc(d); return si_hip_conv2d_border_pack_weight_host(&b, w, p, 1); },
+                            sizeof(uint16_t), SiblingRule::kNone, nullptr, "pack border weight (fp16)"},
     };
-    static_assert(sizeof(rows) / sizeof(rows[0]) == (size_t)WeightImage::kStemSplit3 + 1, "one row per weight image, in the enum's order");
+    static_assert(sizeof(rows) / sizeof(rows[0]) == (size_t)WeightImage::kBorderF16 + 1, "one row per weight image, in the enum's order");
     return rows[(int)image];
 }
 
@@ -369,6 +431,8 @@ Conv2d::WeightImage Conv2d::ImageFor(Route route) {
         case Route::kSplit3: return WeightImage::kSplit3;
         case Route::kWinoSplit: return WeightImage::kWino23Split;
         case Route::kStemSplit: return WeightImage::kStemSplit3;
+        case Route::kBorderF32: return WeightImage::kBorderF32;
+        case Route::kBorderF16: return WeightImage::kBorderF16;
     }
     return WeightImage::kNone;
 }
@@ -505,6 +569,10 @@ bool Conv2d::UseStemSplit() const {
 // which kernel family serves this (input, output) storage pair; a non-stem conv fed an fp32 tensor inside an fp16 graph
 // converts its input first (in_half_)
 Conv2d::Route Conv2d::RouteFor(bool in_half, bool out_half) const {
+    // a bordered layer the border kernel serves, before every other choice (fp16: the kernel stores halves; an fp32 graph output behind a half
+    // input is the composition's); what it does not serve falls through to the ordinary route, which then runs over the padded tensor
+    if (Bordered() && in_half == out_half && BorderKernelServes(out_half)) return out_half ? Route::kBorderF16 : Route::kBorderF32;
+    if (Bordered() && !in_half && out_half && BorderKernelServes(true)) return Route::kBorderF16;
     if (!in_half && !out_half) {
         if (UseSplit3()) return Route::kSplit3;
         if (UseWinoSplit()) return Route::kWinoSplit;
@@ -686,6 +754,15 @@ Status Conv2d::Launch(const Tensor& input, const Tensor* residual, Tensor& outpu
         LOG(ERROR) << "Conv2d: tensor channels/batch do not match the layer";
         return Status::kErrorShape;
     }
+    if (IsBorder(route)) return LaunchBorder(route == Route::kBorderF16, input, residual, output);
+    if (Bordered() && !composing_) {
+        // the composition: the mapped pad into a tensor of this layer, then this function once more over it, with pads of 0 (MakeDesc)
+        CHECK_STATUS(PadInput(input));
+        composing_ = true;
+        const Status st = Launch(pad_scratch_, residual, output);
+        composing_ = false;
+        return st;
+    }
     SiConv2dDesc d = MakeDesc(input, output);
     if (residual) {
         d.has_residual = 1;
@@ -778,12 +855,65 @@ Status Conv2d::Launch(const Tensor& input, const Tensor* residual, Tensor& outpu
             return CheckHip(si_hip_conv2d_f32(&d, input.Data<float>(), weight_dev_.As<float>(), Bias(), residual ? residual->Data<float>() : nullptr,
                                               output.Data<float>(), Stream()),
                             "conv2d");
+        case Route::kBorderF32:
+        case Route::kBorderF16: break;   // (taken above)
     }
     return Status::kFail;
 }
 
+Status Conv2d::LaunchBorder(bool half, const Tensor& input, const Tensor* residual, Tensor& output) {
+    Dims4 in;
+    if (!GetDims4(input, in)) return Status::kErrorShape;
+    if (half != IsHalf(output) || (residual && IsHalf(*residual) != half)) return Status::kUnsupport;
+    Tensor xin = input;
+    if (half) {
+        CHECK_STATUS(HalfInput(input, xin));
+    } else if (IsHalf(input)) {
+        return Status::kUnsupport;
+    }
+    SiBorderConvDesc d = BorderDesc(in.n, in.h, in.w);
+    d.in_ld = xin.PixelStride();
+    d.out_ld = output.PixelStride();
+    if (residual) {
+        d.has_residual = 1;
+        d.res_ld = residual->PixelStride();
+    }
+    CHECK_BOOL(Holds(half ? WeightImage::kBorderF16 : WeightImage::kBorderF32));
+    const int rc = half ? si_hip_conv2d_border_f16(&d, xin.RawData(), weight_dev_.As<void>(), Bias(), residual ? residual->RawData() : nullptr,
+                                                   output.RawData(), Stream())
+                        : si_hip_conv2d_border_f32(&d, xin.Data<float>(), weight_dev_.As<float>(), Bias(), residual ? residual->Data<float>() : nullptr,
+                                                   output.Data<float>(), Stream());
+    if (rc != SI_E_UNSUPPORTED) return CheckHip(rc, half ? "conv2d (border-mapped, fp16)" : "conv2d (border-mapped)");
+    // the tensors break a limit the static shape could not show (a view beyond 31 bits, a grid extent, an unaligned pointer): the composition
+    // from here on, as an f32_split layer goes back to the fp32 kernels (the re-pack uploads weights: a capture in progress is discarded)
+    border_demoted_ = true;
+    device_ready_ = false;
+    return Launch(input, residual, output);
+}
+
+// the composition's first launch: F.pad(x, (pl, pl, pt, pt), mode) in the input's storage type into pad_scratch_
+Status Conv2d::PadInput(const Tensor& input) {
+    Dims4 in;
+    if (!GetDims4(input, in)) return Status::kErrorShape;
+    const DataType type = IsHalf(input) ? DataType::kFloat16 : DataType::kFloat32;
+    const std::vector<int> shape{in.n, in.h + 2 * padding_t_, in.w + 2 * padding_l_, in.c};
+    // (a default-constructed Tensor is a HOST tensor, as in HalfInput)
+    if (pad_scratch_.GetMemoryType() != MemoryType::kDevice) pad_scratch_ = Tensor(type, shape, MemoryType::kDevice, false);
+    CHECK_STATUS(pad_scratch_.Allocate(type, shape));
+    const SiBorderConvDesc b = BorderDesc(in.n, in.h, in.w);
+    SiPad2dDesc d;
+    memset(&d, 0, sizeof(d));
+    d.n = in.n; d.ih = in.h; d.iw = in.w; d.c = in.c; d.in_ld = input.PixelStride();
+    d.oh = shape[1]; d.ow = shape[2]; d.out_ld = pad_scratch_.PixelStride();
+    d.pad_l = d.pad_r = padding_l_; d.pad_t = d.pad_b = padding_t_;
+    d.mode = b.mode;
+    const int rc = IsHalf(input) ? si_hip_pad2d_f16(&d, input.RawData(), pad_scratch_.RawData(), Stream())
+                                 : si_hip_pad2d_f32(&d, input.Data<float>(), pad_scratch_.Data<float>(), Stream());
+    return CheckHip(rc, "conv2d (border pad of the composition)");
+}
+
 bool Conv2d::CanReadUpsampled(int c0, int c) const {
-    return kernel_h_ == 1 && kernel_w_ == 1 && stride_h_ == 1 && stride_w_ == 1 && padding_t_ == 0 && padding_b_ == 0 && padding_l_ == 0 &&
+    return !Bordered() && kernel_h_ == 1 && kernel_w_ == 1 && stride_h_ == 1 && stride_w_ == 1 && padding_t_ == 0 && padding_b_ == 0 && padding_l_ == 0 &&
            padding_r_ == 0 && groups_ == 1 && in_channels_ % 32 == 0 && c0 % 32 == 0 && c % 32 == 0 && c0 + c <= in_channels_ &&
            residual_node_ == nullptr && algo_ != Algo::kWinograd23 && algo_ != Algo::kWinograd43;
 }
@@ -888,21 +1018,39 @@ const char* Conv2d::KernelName() const {
     if (pw_producer_) return in_channels_ <= 64 ? "conv_pw_patch_f16_kernel<pw + 3x3>" : "conv3x3s1_slab_f16_kernel<pw + 3x3>";
     SiConv2dDesc d = MakeDesc(in, out);
     if (sibling_) d.oc += sibling_->out_channels_;
-    switch (RouteFor(IsHalf(in), IsHalf(out))) {   // the route Launch will take
-        case Route::kIgemmF16: {
-            const char* name = si_hip_conv2d_f16_kernel_name(&d, up_node_ ? 1 : 0);   // the tile follows the launch size (round 4)
-            return name && name[0] ? name : "conv_igemm_f16_kernel";
-        }
-        case Route::kStemF16: return "conv_stem_f16_kernel";
-        case Route::kDepthwiseF16: return "conv_depthwise_f16_kernel<2>";
-        case Route::kSplit3: return "conv_split3_f32_kernel";
-        case Route::kWinoSplit: return "conv_wino23s_kernel";
-        case Route::kStemSplit: return "conv_stem_split_f32_kernel";
-        case Route::kWino43F32: return "conv_wino43_kernel";
-        case Route::kWino23F32: return "conv_wino23_kernel";
-        case Route::kIgemmF32: return si_hip_conv2d_kernel_name_form(&d, in.Data<float>(), up_node_ ? 1 : 0);
+    const Route route = RouteFor(IsHalf(in), IsHalf(out));
+    if (IsBorder(route)) {
+        SiBorderConvDesc b = BorderDesc(d.n, d.ih, d.iw);
+        b.in_ld = route == Route::kBorderF16 && !IsHalf(in) ? b.ic : d.in_ld;   // (an fp32 input is converted into a dense tensor first)
+        b.out_ld = d.out_ld;
+        return si_hip_conv2d_border_kernel_name(&b, in.RawData() ? in.RawData() : out.RawData(), out.RawData(), route == Route::kBorderF16 ? 1 : 0);
     }
-    return "conv_igemm_f32";
+    // the composition: the pad, then the ordinary route's kernel over the padded tensor
+    const bool composed = Bordered();
+    if (composed) {
+        d.ih += 2 * padding_t_; d.iw += 2 * padding_l_; d.in_ld = d.ic;
+    }
+    const char* name = "conv_igemm_f32";
+    switch (route) {   // the route Launch will take
+        case Route::kIgemmF16: {
+            name = si_hip_conv2d_f16_kernel_name(&d, up_node_ ? 1 : 0);   // the tile follows the launch size (round 4)
+            if (!name || !name[0]) name = "conv_igemm_f16_kernel";
+            break;
+        }
+        case Route::kStemF16: name = "conv_stem_f16_kernel"; break;
+        case Route::kDepthwiseF16: name = "conv_depthwise_f16_kernel<2>"; break;
+        case Route::kSplit3: name = "conv_split3_f32_kernel"; break;
+        case Route::kWinoSplit: name = "conv_wino23s_kernel"; break;
+        case Route::kStemSplit: name = "conv_stem_split_f32_kernel"; break;
+        case Route::kWino43F32: name = "conv_wino43_kernel"; break;
+        case Route::kWino23F32: name = "conv_wino23_kernel"; break;
+        case Route::kIgemmF32: name = si_hip_conv2d_kernel_name_form(&d, composed ? out.Data<float>() : in.Data<float>(), up_node_ ? 1 : 0); break;
+        case Route::kBorderF32:
+        case Route::kBorderF16: break;   // (answered above)
+    }
+    if (!composed) return name;
+    composed_name_ = std::string("pad2d_kernel + ") + name;
+    return composed_name_.c_str();
 }
 
 // 0 = implicit GEMM, 2 = fused Winograd F(2,3), 4 = fused Winograd F(4,3) for this layer's static shape
@@ -953,6 +1101,13 @@ double Conv2d::Bytes() const {
         if (stem_pair_->stem_producer_) b += (double)stem_pair_->stem_producer_->weight_.size() * sizeof(float);
     }
     if (pw_producer_) b += (double)pw_producer_->weight_.size() * sizeof(float);
+    // the composition of a bordered layer writes the padded tensor and reads it back
+    if (Bordered() && !input_tensor_nodes_.empty() && !output_tensor_nodes_.empty()) {
+        const Tensor& in = input_tensor_nodes_[0]->tensor;
+        Dims4 di;
+        if (!IsBorder(RouteFor(IsHalf(in), IsHalf(output_tensor_nodes_[0]->tensor))) && GetDims4(in, di))
+            b += 2.0 * (double)di.n * (di.h + 2 * padding_t_) * (di.w + 2 * padding_l_) * di.c * (IsHalf(in) ? 2 : 4);
+    }
     return b;
 }
 
@@ -962,6 +1117,9 @@ bool Conv2d::HalfStorageOk(std::string& why) const {
     const Tensor& out = output_tensor_nodes_[0]->tensor;
     if (!IsHalf(in) && !IsHalf(out)) return true;
     if (stem_producer_ || pw_producer_ || stem_pair_ || cv3_pair_) return true;   // (asked of the kernel when the pair was fused: CanFuseStemProducer / CanFusePointwiseProducer)
+    // a bordered layer: the border kernel where it stores halves; else the composition, whose pad serves any channel count in either type and
+    // whose conv is judged below as the zero-pad layer it is (StaticDesc)
+    if (IsBorder(RouteFor(IsHalf(in), IsHalf(out)))) return true;
     const SiConv2dDesc d = StaticDesc();
     // (2 is the stem kernel, which reads an fp32 image: RouteFor takes it under exactly these conditions, and a stem shape has no other fp16 kernel --
     // behind a half producer, an explicit pad in front of a generator's 7x7 stem for one, the layer runs in fp32 between casts)
@@ -978,6 +1136,10 @@ bool Conv2d::HalfStorageOk(std::string& why) const {
 bool Conv2d::TakesView(const TensorNode* node, int ld, int off) const {
     if (!node || input_tensor_nodes_.empty() || output_tensor_nodes_.empty()) return true;
     if (!IsHalf(node->tensor)) return node != up_node_ || FloatUpsampledSourceTakesView(ld, off);
+    // a bordered layer: the border kernel takes every view (16-byte accesses where the view allows them, elements otherwise); on the composition
+    // the pad kernel reads the input view and the ordinary conv reads pad_scratch_, so only the output and the residual are its operands
+    const bool bordered = Bordered() && !stem_pair_ && !cv3_pair_ && !stem_producer_ && !pw_producer_;
+    if (bordered && IsBorder(RouteFor(IsHalf(input_tensor_nodes_[0]->tensor), IsHalf(output_tensor_nodes_[0]->tensor)))) return true;
     HalfConvForm form = HalfConvForm::kIgemm;
     if (cv3_pair_) {
         form = HalfConvForm::kCv3;
@@ -994,7 +1156,8 @@ bool Conv2d::TakesView(const TensorNode* node, int ld, int off) const {
     const auto ask = [&](const TensorNode* n, ConvOperand operand) {
         if (n == node) ok = ok && HalfConvTakesView(form, operand, ld, off);
     };
-    for (const TensorNode* n : input_tensor_nodes_) ask(n, ConvOperand::kInput);
+    if (!bordered)
+        for (const TensorNode* n : input_tensor_nodes_) ask(n, ConvOperand::kInput);
     for (const TensorNode* n : output_tensor_nodes_) ask(n, ConvOperand::kOutput);
     ask(residual_node_, ConvOperand::kResidual);
     ask(up_node_, ConvOperand::kUpsampledSource);

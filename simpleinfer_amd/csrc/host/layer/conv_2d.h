@@ -15,6 +15,13 @@
 //   kSplit3         fp32 -> fp32  f32_split: implicit GEMM by three fp16 products      kSplit3 (one conv over this | sibling)
 //   kWinoSplit      fp32 -> fp32  f32_split: the fused Winograd F(2,3) kernel's form   kWino23Split
 //   kStemSplit      fp32 -> fp32  f32_split: the RGB stem's form                       kStemSplit3
+//   kBorderF32      fp32 -> fp32  border-mapped conv (padding_mode not zeros, pad > 0) kBorderF32 ([oc][kh][kw][ic padded], include/si_border.h)
+//   kBorderF16      any -> half   ... its fp16 form (an fp32 input is converted)       kBorderF16
+//
+// padding_mode reflect / replicate / circular with a non-zero pad (Bordered()): the border kernel reads the mapped source pixel in one launch
+// where it serves the layer (groups == 1; ic % 8 == 0 under fp16 storage; a patch that fits LDS).  Everything else is the COMPOSITION, two
+// launches inside the layer: si_hip_pad2d_* into pad_scratch_, then the layer's ordinary route with zero padding over it -- which is why the
+// SiConv2dDesc of a bordered layer always carries pads of 0.  With a pad of 0 the mode means nothing and the layer is a zeros convolution.
 //
 // The producer fusions (SetStemProducer, SetPointwiseProducer, SetStemPairProducer, SetCv3Pair) are fp16 launches of their own over the
 // kIgemmF16 / kStemF16 images of the layers they join.  Bias, activation and residual are in every kernel's epilogue.
@@ -23,6 +30,7 @@
 
 #include "layer.h"
 #include "layer_util.h"
+#include "si_border.h"
 #include "si_hip.h"
 #include "view_rule.h"
 
@@ -117,7 +125,8 @@ public:
     Conv2d* Cv3Pair() const { return cv3_pair_; }
 
     // the kernel family of a launch.  use_winograd_ / wino_tile_ follow from it (Prepare)
-    enum class Route { kIgemmF32 = 0, kWino23F32, kWino43F32, kIgemmF16, kStemF16, kDepthwiseF16, kSplit3, kWinoSplit, kStemSplit };
+    enum class Route { kIgemmF32 = 0, kWino23F32, kWino43F32, kIgemmF16, kStemF16, kDepthwiseF16, kSplit3, kWinoSplit, kStemSplit, kBorderF32, kBorderF16 };
+    static bool IsBorder(Route r) { return r == Route::kBorderF32 || r == Route::kBorderF16; }
     // what the layer would do, as plain numbers and without a device (tests/cpp/test_conv_route.cpp): the route serving a storage pair /
     // ForwardYolo's own choice, the weight image it reads and its Winograd tile
     struct RouteInfo { int route, image, wino_tile; };
@@ -129,7 +138,9 @@ public:
                        Tensor& detect_out);
 
 public:
-    enum class PaddingMode { kZeros = 0, kReplicate, kReflect } padding_mode_ = PaddingMode::kZeros;
+    enum class PaddingMode { kZeros = 0, kReplicate, kReflect, kCircular } padding_mode_ = PaddingMode::kZeros;
+    // out-of-image taps read a mapped source pixel: a mode other than zeros with a non-zero pad
+    bool Bordered() const { return padding_mode_ != PaddingMode::kZeros && (padding_t_ != 0 || padding_l_ != 0); }
     int padding_t_    = 0;
     int padding_b_    = 0;
     int padding_l_    = 0;
@@ -188,7 +199,7 @@ public:
 
 private:
     // which packed form of the filters weight_dev_ holds
-    enum class WeightImage { kNone = 0, kIgemmF32, kWino23F32, kWino43F32, kIgemmF16, kStemF16, kSplit3, kWino23Split, kStemSplit3 };
+    enum class WeightImage { kNone = 0, kIgemmF32, kWino23F32, kWino43F32, kIgemmF16, kStemF16, kSplit3, kWino23Split, kStemSplit3, kBorderF32, kBorderF16 };
     struct ImageRow;
     static const ImageRow& RowOf(WeightImage image);
     static WeightImage ImageFor(Route route);
@@ -211,6 +222,11 @@ private:
     Status LaunchStemTriple(const Tensor& image, Tensor& out0, Tensor* out1);
     Status LaunchCv3(const Tensor& x, Tensor& output);
     SiConv2dDesc MakeDesc(const Tensor& input, const Tensor& output) const;
+    // the border kernel's descriptor for an image of ih x iw (the output extents are torch's), and whether the kernel serves the layer
+    SiBorderConvDesc BorderDesc(int n, int ih, int iw) const;
+    bool BorderKernelServes(bool half) const;
+    Status LaunchBorder(bool half, const Tensor& input, const Tensor* residual, Tensor& output);
+    Status PadInput(const Tensor& input);
     Status MakeUpsampledSource(SiConv2dUpsampledSource& up) const;
 
     SiConvPlan plan_ = SI_CONV_PLAN_DEFAULT;
@@ -220,6 +236,10 @@ private:
     bool device_ready_ = false;
     WeightImage image_ = WeightImage::kNone;   // what weight_dev_ holds once device_ready_ (see Prepare)
     Tensor in_half_;             // fp16 copy of an fp32 input consumed by the fp16 kernel
+    Tensor pad_scratch_;         // the padded input of a bordered layer on the composition path (Launch)
+    bool composing_ = false;     // Launch is running the ordinary route over pad_scratch_
+    bool border_demoted_ = false;   // the border kernel refused the tensors of a launch: the composition from then on (LaunchBorder)
+    mutable std::string composed_name_;   // KernelName() of the composition path
     Tensor pw_scratch_;          // the fused-away 1x1 conv's output, when the fused launch refuses the views it is handed (Launch)
 };
 

@@ -1180,6 +1180,51 @@ def pad2d_kernel_name(x_shape, pads, mode="constant", half=False, in_ld=None, ou
     return _desc_kernel_name("pad2d", d, half)
 
 
+def conv2d_border_desc(x_shape, w_shape, stride=(1, 1), padding=(1, 1), dilation=(1, 1), mode="reflect", bias=True, act1="none", residual=False,
+                       act2="none", act_param=0.0, in_ld=None, out_ld=None, res_ld=None, groups=1):
+    """SiBorderConvDesc (include/si_border.h) for an NHWC input of x_shape and a torch weight of w_shape [Cout][Cin][kh][kw]"""
+    n, ih, iw, ic = x_shape
+    oc, _, kh, kw = w_shape
+    (sh, sw), (pt, pl), (dh, dw) = _pair(stride), _pair(padding), _pair(dilation)
+    oh, ow = conv_out_hw(ih, iw, (kh, kw), (sh, sw), (pt, pl), (dh, dw))
+    return _native.SiBorderConvDesc(n, ih, iw, ic, in_ld or ic, oh, ow, oc, out_ld or oc, kh, kw, sh, sw, dh, dw, pt, pl, PAD_MODE[mode], groups,
+                                    1 if bias else 0, ACT[act1], 1 if residual else 0, res_ld or oc, ACT[act2], float(act_param))
+
+
+def conv2d_border(x, w, b=None, stride=(1, 1), padding=(1, 1), dilation=(1, 1), mode="reflect", act1="none", residual=None, act2="none",
+                  act_param=0.0, half=False, in_ld=None, in_c_off=0, in_fill=0.0, res_ld=None, res_c_off=0, res_fill=0.0, out_ld=None,
+                  out_c_off=0, out_fill=0.0, full=False):
+    """si_hip_conv2d_border_f32 / _f16 (half=True: x and the residual travel as float16, the weights are packed as halves, the bias stays
+    fp32): torch's conv2d(F.pad(x, (pl, pl, pt, pt), mode), w, b, stride, 0, dilation) on an NHWC array with a torch [Cout][Cin][kh][kw]
+    weight, one launch.  The view hooks are conv_transpose2d's, with the residual's beside them."""
+    H = _native.hip()
+    dt = np.float16 if half else np.float32
+    x, w = np.ascontiguousarray(x, dtype=dt), _f32(w)
+    d = conv2d_border_desc(x.shape, w.shape, stride, padding, dilation, mode, b is not None, act1, residual is not None, act2, act_param, in_ld,
+                           out_ld, res_ld)
+    elems = H.si_hip_conv2d_border_weight_elems(C.byref(d), 1 if half else 0)
+    if elems == 0:
+        raise HipError("si_hip_conv2d_border: no weight image for %d -> %d channels (%s)" % (d.ic, d.oc, "fp16" if half else "fp32"))
+    packed = np.zeros(elems, dt)
+    _chk(H.si_hip_conv2d_border_pack_weight_host(C.byref(d), w.ctypes.data_as(C.c_void_p), packed.ctypes.data_as(C.c_void_p), 1 if half else 0),
+         "pack border weight")
+    (dx, px), dw = _view_in(x, in_ld, in_c_off, in_fill), DeviceBuffer.from_numpy(packed)
+    db = DeviceBuffer.from_numpy(_f32(b)) if b is not None else None
+    dr, pr = _view_in(np.ascontiguousarray(residual, dtype=dt), res_ld, res_c_off, res_fill) if residual is not None else (None, None)
+    dy, py = _view_out((d.n, d.oh, d.ow), d.oc, out_ld, out_c_off, out_fill, dt)
+    LAST_KERNEL_NAME["si_hip_conv2d_border"] = H.si_hip_conv2d_border_kernel_name(C.byref(d), C.c_void_p(px), C.c_void_p(py), 1 if half else 0).decode()
+    name = "si_hip_conv2d_border_f16" if half else "si_hip_conv2d_border_f32"
+    _chk(getattr(H, name)(C.byref(d), px, dw.ptr, db.ptr if db else None, pr, py, None), name)
+    return _ret(dy.to_numpy((d.n, d.oh, d.ow, out_ld or d.oc), dt), d.oc, out_c_off, full)
+
+
+def conv2d_border_kernel_name(x_shape, w_shape, stride=(1, 1), padding=(1, 1), dilation=(1, 1), mode="reflect", half=False, in_ld=None,
+                              out_ld=None, groups=1) -> str:
+    """the kernel for 16-byte aligned buffers of these shapes ("none": a descriptor the launch refuses)"""
+    d = conv2d_border_desc(x_shape, w_shape, stride, padding, dilation, mode, in_ld=in_ld, out_ld=out_ld, groups=groups)
+    return _desc_kernel_name("conv2d_border", d, half)
+
+
 def _pair(v):
     return (int(v), int(v)) if isinstance(v, (int, np.integer)) else (int(v[0]), int(v[1]))
 

@@ -136,7 +136,8 @@ class PnnxBuilder:
         return out
 
     def conv(self, x: str, cout: int, k, s=1, p=None, d=1, groups: int = 1, bias: bool = True,
-             name: str = None) -> str:
+             name: str = None, padding_mode: str = "zeros") -> str:
+        """padding_mode: "zeros", "reflect", "replicate" or "circular" (torch's nn.Conv2d; the output size does not depend on it)"""
         n, cin, h, w = self.shapes[x]
         kh, kw = (k, k) if isinstance(k, int) else k
         sh, sw = (s, s) if isinstance(s, int) else s
@@ -156,7 +157,7 @@ class PnnxBuilder:
         self._emit("nn.Conv2d", name, [x], [out],
                    dict(bias=bool(bias), dilation=(dh, dw), groups=groups, in_channels=cin,
                         kernel_size=(kh, kw), out_channels=cout, padding=(ph, pw),
-                        padding_mode="zeros", stride=(sh, sw)), attrs)
+                        padding_mode=str(padding_mode), stride=(sh, sw)), attrs)
         return out
 
     def conv1d(self, x: str, cout: int, k: int, s: int = 1, p=None, d: int = 1, groups: int = 1, bias: bool = True, padding_mode: str = "zeros",
@@ -1094,28 +1095,36 @@ def build_toy_unet(batch: int = 2, size: int = 64, base: int = 16, depth: int = 
     return b
 
 
-def build_toy_cyclegan(batch: int = 2, size: int = 32, base: int = 8, blocks: int = 2, pad: str = "reflect", seed: int = 0) -> PnnxBuilder:
+def build_toy_cyclegan(batch: int = 2, size: int = 32, base: int = 8, blocks: int = 2, pad: str = "reflect", seed: int = 0,
+                       in_conv: bool = False) -> PnnxBuilder:
     """The CycleGAN / Johnson style-transfer ResNet generator at toy width: ReflectionPad2d(3) -> conv7x7 (p = 0) -> InstanceNorm2d
     (no affine) -> ReLU; two stride-2 conv3x3 -> IN -> ReLU; `blocks` residual blocks [pad 1 -> conv3x3 (p = 0) -> IN -> ReLU ->
     pad 1 -> conv3x3 (p = 0) -> IN] + x; two ConvTranspose2d(3, s2, p1, op1) -> IN -> ReLU; ReflectionPad2d(3) -> conv7x7 -> Tanh.
     pad: the mode of every explicit pad ("reflect", "replicate", "circular", "constant").  At size 32 the residual blocks run at
-    8 x 8: every reflect pad is below its input size."""
+    8 x 8: every reflect pad is below its input size.  in_conv: the other spelling of the same network -- no pad layers, the
+    convolutions that had one carry padding = 3 / 1 and padding_mode = pad themselves ("reflect", "replicate" or "circular"); the
+    weights have the same names and values, so both spellings compute the same function."""
     b = PnnxBuilder(seed)
     x = b.input((batch, 3, size, size))
+
+    def padded_conv(x, c, k, p):
+        if in_conv:
+            return b.conv(x, c, k, 1, p, padding_mode=pad)
+        return b.conv(b.pad(x, p, pad), c, k, 1, 0)
 
     def cnr(x, c, k, s, p):
         return b.relu(b.instance_norm(b.conv(x, c, k, s, p)))
 
-    x = cnr(b.pad(x, 3, pad), base, 7, 1, 0)
+    x = b.relu(b.instance_norm(padded_conv(x, base, 7, 3)))
     x = cnr(x, 2 * base, 3, 2, 1)
     x = cnr(x, 4 * base, 3, 2, 1)
     for _ in range(blocks):
-        y = cnr(b.pad(x, 1, pad), 4 * base, 3, 1, 0)
-        y = b.instance_norm(b.conv(b.pad(y, 1, pad), 4 * base, 3, 1, 0))
+        y = b.relu(b.instance_norm(padded_conv(x, 4 * base, 3, 1)))
+        y = b.instance_norm(padded_conv(y, 4 * base, 3, 1))
         x = b.add(x, y)
     for c in (2 * base, base):
         x = b.relu(b.instance_norm(b.conv_transpose(x, c, 3, 2, 1, output_padding=1)))
-    x = b.tanh(b.conv(b.pad(x, 3, pad), 3, 7, 1, 0))
+    x = b.tanh(padded_conv(x, 3, 7, 3))
     b.output(x)
     return b
 
