@@ -1,6 +1,6 @@
 /*
  * si_act.h -- C-ABI of the activations that carry parameters of their own or need an accurate evaluation: clamp (nn.ReLU6, nn.Hardtanh,
- * torch.clamp), softplus (nn.Softplus) and mish (nn.Mish), torch's semantics.  The symbols live in libsi_hip.so beside those of
+ * torch.clamp), softplus (nn.Softplus), mish (nn.Mish) and the two GELUs (F.gelu), torch's semantics.  The symbols live in libsi_hip.so beside those of
  * include/si_hip.h; they have a header of their own as include/si_softmax.h, include/si_slice.h and include/si_reduce.h have.
  *
  * Tensors are [pixels, c] with pixel strides in_ld / out_ld (in elements) on both sides: what lies between two pixels (ld > c) is never
@@ -24,7 +24,19 @@
  *             torch's definition (beta 1, no threshold) with one exponential: tanh(log(1 + e)) = ((1 + e)^2 - 1) / ((1 + e)^2 + 1).
  *             Every operation rounds to fp32 on its own (no contraction), the division is IEEE.  Above the cut the factor is 1 to fp32's
  *             precision (it is from x = 9.1 on; the cut only has to keep e * e finite).
- *   special values: a NaN gives NaN.  softplus(-inf) = 0, softplus(+inf) = +inf, mish(+inf) = +inf; mish(-inf) = -inf * 0 = NaN as
+ *   gelu      out = 0.5 x erfc(-x / sqrt(2))     (approximate="none": x Phi(x); p0, p1 ignored)
+ *             The erfc form keeps the negative tail, where 1 + erf(x / sqrt(2)) cancels (it is 0 in fp32 below x = -5.6, where the true
+ *             value is still -2e-8).  erfcf is the library's accurate function.  t = -x / sqrt(2) is rounded to fp32 and erfc is steep
+ *             where it is small, so the rounding error of t -- known exactly: fmaf(x, k, -t) plus what the fp32 constant k misses of
+ *             -1 / sqrt(2) -- is applied to first order for t > 0: erfc(t) (1 - dt (t + sqrt(t^2 + 2))), Mills' ratio.
+ *             Below x = -13 erfc(t) itself is a subnormal fp32 number (and from x = -14.2 on it is 0): the result there carries
+ *             the absolute error of a subnormal factor, a few units of 2^-149 times |x| / 2, not 4 ulp of its own.
+ *   gelu_tanh out = 0.5 x (1 + tanh(u)),  u = sqrt(2 / pi) (x + 0.044715 x^3)     (approximate="tanh", torch's formula and constants)
+ *             computed as x / (1 + exp(-2u)), the same function without the cancellation of 1 + tanh(u) for u < 0.  For u < 0 the
+ *             rounding error of u (five roundings and the constants' fp32 remainders, collected with fmaf) is applied to first order,
+ *             a relative 2 du; below u = -10 the value is x exp(u) exp(u), which stays normal as long as the result does.
+ *   special values: a NaN gives NaN.  gelu(+inf) = gelu_tanh(+inf) = +inf; gelu(-inf) = gelu_tanh(-inf) = -inf * 0 = NaN as torch's
+ *             formulas give in float64.  softplus(-inf) = 0, softplus(+inf) = +inf, mish(+inf) = +inf; mish(-inf) = -inf * 0 = NaN as
  *             torch's formula gives (silu(-inf) of include/si_hip.h does the same).
  *
  * Arms, chosen from c, both strides, both pointers' alignment and -- the first one -- whether pixels * c fills whole vectors;
@@ -38,9 +50,10 @@
  * workspace, no atomics: two launches give the same bits, an element does not depend on any other, and every launch is safe inside a
  * captured graph.
  *
- * Refused before any device call: a null descriptor or tensor, pixels == 0, c <= 0, in_ld < c, out_ld < c, op outside 0 .. 2, a NaN
+ * Refused before any device call: a null descriptor or tensor, pixels == 0, c <= 0, in_ld < c, out_ld < c, an op that is no SI_PACT_*
+ * code (3 is none: it stays refused), a NaN
  * clamp bound, a softplus beta that is zero or not finite, a NaN softplus threshold, overlapping in / out (SI_E_BADARG); element
- * offsets that do not fit 31 bits (SI_E_UNSUPPORTED).  mish ignores p0 and p1.
+ * offsets that do not fit 31 bits (SI_E_UNSUPPORTED).  mish and the GELUs ignore p0 and p1.
  */
 #ifndef SI_ACT_H_
 #define SI_ACT_H_
@@ -51,14 +64,14 @@
 extern "C" {
 #endif
 
-enum { SI_PACT_CLAMP = 0, SI_PACT_SOFTPLUS = 1, SI_PACT_MISH = 2 };
+enum { SI_PACT_CLAMP = 0, SI_PACT_SOFTPLUS = 1, SI_PACT_MISH = 2, /* 3: unassigned, refused */ SI_PACT_GELU = 4, SI_PACT_GELU_TANH = 5 };
 
 /* mish returns x above this: exp(30)^2 is still finite in fp32, and n / (n + 2) rounds to 1 long before */
 enum { SI_PACT_MISH_CUT = 30 };
 
 typedef struct SiParamActDesc {
     int op;              /* SI_PACT_* */
-    float p0, p1;        /* clamp: lo, hi (either may be -inf / +inf); softplus: beta, threshold; mish: ignored */
+    float p0, p1;        /* clamp: lo, hi (either may be -inf / +inf); softplus: beta, threshold; mish, gelu, gelu_tanh: ignored */
     size_t pixels;
     int c, in_ld, out_ld;
 } SiParamActDesc;
@@ -69,7 +82,7 @@ int si_hip_param_act_f32(const SiParamActDesc* d, const float* in, float* out, s
 int si_hip_param_act_f16(const SiParamActDesc* d, const void* in, void* out, si_stream_t stream);
 
 /* the kernel a launch with these pointers takes: "param_act_kernel<OP, float, 4>", "<OP, float, 1>", "<OP, _Float16, 8>" or
- * "<OP, _Float16, 1>" with OP one of clamp, softplus, mish; "none" for a descriptor the launch would refuse (the pointers are looked at
+ * "<OP, _Float16, 1>" with OP one of clamp, softplus, mish, gelu, gelu_tanh; "none" for a descriptor the launch would refuse (the pointers are looked at
  * for their alignment only) */
 const char* si_hip_param_act_kernel_name(const SiParamActDesc* d, const void* in, const void* out, int half);
 

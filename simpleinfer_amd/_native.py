@@ -107,6 +107,11 @@ class SiLpNormDesc(C.Structure):
     _fields_ = [(k, C.c_int) for k in ("n", "h", "w", "c", "in_ld", "out_ld", "axes", "p", "normalize")] + [("eps", C.c_float)]
 
 
+class SiLayerNormDesc(C.Structure):
+    """include/si_layernorm.h: rows of c contiguous elements, row strides in elements"""
+    _fields_ = [(k, C.c_int) for k in ("rows", "c", "in_ld", "out_ld")] + [("eps", C.c_float)]
+
+
 class SiPixelShuffleDesc(C.Structure):
     """include/si_superres.h"""
     _fields_ = [(k, C.c_int) for k in ("n", "ih", "iw", "ic", "in_ld", "oh", "ow", "oc", "out_ld", "r", "inverse")]
@@ -518,10 +523,17 @@ def hip():
         "si_hip_conv2d_border_kernel_name": (C.c_char_p, [C.POINTER(SiBorderConvDesc), vp, vp, i]),
         "si_hip_conv2d_border_source_index": (i, [i, i, i]),
     }
+    # include/si_layernorm.h: F.layer_norm over the last axis
+    layernorm_ = {
+        "si_hip_layernorm_f32": (i, [C.POINTER(SiLayerNormDesc), vp, vp, vp, vp, vp]),
+        "si_hip_layernorm_f16": (i, [C.POINTER(SiLayerNormDesc), vp, vp, vp, vp, vp]),
+        "si_hip_layernorm_kernel_name": (C.c_char_p, [C.POINTER(SiLayerNormDesc), vp, vp, i]),
+    }
     for name, (res, args) in (list(border_.items()) + list(sig.items()) + list(norm.items()) + list(pad.items()) + list(pool.items()) + list(softmax.items()) +
                               list(superres.items()) + list(slice_.items()) + list(reduce_.items()) + list(act.items()) + list(permute_.items()) +
                               list(attention_.items()) + list(deform_.items()) + list(grid_.items()) + list(roi_.items()) + list(rnn_.items()) +
-                              list(binary_.items()) + list(conv1d_.items()) + list(xcorr_.items()) + list(detect_.items()) + list(lpnorm_.items())):
+                              list(binary_.items()) + list(conv1d_.items()) + list(xcorr_.items()) + list(detect_.items()) + list(lpnorm_.items()) +
+                              list(layernorm_.items())):
         fn = getattr(L, name)  # AttributeError here = header/library mismatch, which tests check
         fn.restype = res
         fn.argtypes = args
@@ -545,6 +557,7 @@ def hip():
     L._si_xcorr_signatures = xcorr_
     L._si_detect_signatures = detect_
     L._si_lpnorm_signatures = lpnorm_
+    L._si_layernorm_signatures = layernorm_
     L._si_border_signatures = border_
     _hip = L
     return L

@@ -27,7 +27,11 @@ ARCH = "gfx950"
 # to depend on the compiler pairing two lanes' epilogue operations into v_pk_*_f32.  Today neither build of the file contains such an
 # instruction (disassembly), so the results are the same; what the flag does change is the code generator's choices around them: 30 - 58
 # VGPRs and 8 waves / SIMD for seven of the eight instances with it, 55 - 58 VGPRs and 7 waves / SIMD without.
-FILE_FLAGS = {"conv_border.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+# layernorm.hip: the same switch for the same reason -- a row's bits must not depend on which of a lane's items the compiler pairs
+# (include/si_layernorm.h).  activation_param.hip: the GELU operators' compensated arithmetic stays scalar (the build without the switch pairs
+# 28 of its operations); the instructions of the clamp / softplus / mish kernels are the same with and without it (disassembly).
+_NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+FILE_FLAGS = {"conv_border.hip": _NO_PACKED_FP32, "layernorm.hip": _NO_PACKED_FP32, "activation_param.hip": _NO_PACKED_FP32}
 
 
 def _newest(paths):

@@ -1,4 +1,4 @@
-// activation_param.hip -- clamp / softplus / mish (include/si_act.h) on fp32 and fp16 [pixels, c] tensors with pixel strides on both sides.
+// activation_param.hip -- clamp / softplus / mish / gelu (include/si_act.h) on fp32 and fp16 [pixels, c] tensors with pixel strides on both sides.
 // Arithmetic, special values, the arms and the refusals: the header.  The model is activation_kernel of ops.hip: one lane per
 // 16-byte channel vector (or single element), consecutive lanes on consecutive addresses, a grid-stride loop under si_grid_for.  What
 // differs: the operator is a template parameter, so a lane runs straight-line code of one operator, and the two parameters are kernel
@@ -28,6 +28,46 @@ __device__ __forceinline__ float pa_log1p_unit(float e) {
     return logf(u) - d * __builtin_amdgcn_rcpf(u);
 }
 
+// x * Phi(x) = 0.5 x erfc(-x / sqrt(2)).  t = -x / sqrt(2) is rounded to fp32, and erfc is steep where it is small: an error dt of t is a
+// relative error 2 exp(-t^2) / (sqrt(pi) erfc(t)) dt of erfc(t), about (t + sqrt(t^2 + 2)) dt for t > 0 (Mills' ratio; up to 20 dt where
+// the result is still a normal number).  dt is known: fmaf gives the product's rounding error exactly, and the second term is what the fp32
+// constant misses of 1 / sqrt(2).  The correction is first order; for t <= 0 erfc is between 1 and 2 and flat, and nothing is corrected.
+__device__ __forceinline__ float pa_gelu_erfc(float x) {
+    constexpr float K_HI = -0.70710677f;       // fp32(-1 / sqrt(2))
+    constexpr float K_LO = -1.2101617e-8f;     // -1 / sqrt(2) - K_HI
+    const float t = x * K_HI;
+    float e = erfcf(t);                         // (a NaN comes out here)
+    if (t > 0.0f && e > 0.0f) {               // (e == 0: t may be huge, and nothing is left to correct)
+        const float dt = fmaf(x, K_HI, -t) + x * K_LO;
+        e = e - e * (dt * (t + sqrtf(t * t + 2.0f)));
+    }
+    return (0.5f * x) * e;
+}
+
+// torch's approximate="tanh": 0.5 x (1 + tanh(u)), u = sqrt(2 / pi) (x + 0.044715 x^3), written as x / (1 + exp(-2u)): 1 + tanh(u) cancels
+// for u < 0.  There the value is about x exp(2u), and an error du of u is a relative error 2 du of it: the five roundings of u (and what
+// the fp32 constants miss) are collected with fmaf and the exact sum's error, and applied to first order.  Below u = -10, 1 + exp(2u) is 1
+// in fp32 and exp(2u) is taken as exp(u)^2, which stays a normal number as long as the result does.
+__device__ __forceinline__ float pa_gelu_tanh(float x) {
+    constexpr float B_HI = 0.79788458f, B_LO = (float)(0.7978845608028654 - (double)0.79788458f);   // sqrt(2 / pi)
+    constexpr float C_HI = 0.044715f, C_LO = (float)(0.044715 - (double)0.044715f);
+    const float x2 = x * x, x3 = x2 * x, p = C_HI * x3, s = x + p, u = B_HI * s;
+    if (!(u < 0.0f)) return x / (1.0f + expf(-2.0f * u));           // (a NaN comes out here)
+    const float e3 = fmaf(x2, x, -x3) + fmaf(x, x, -x2) * x;          // x^3 - x3
+    const float ep = fmaf(C_HI, x3, -p) + (C_HI * e3 + C_LO * x3);   // 0.044715 x^3 - p
+    const float bb = s - x;
+    const float es = (x - (s - bb)) + (p - bb);                      // (x + p) - s, exactly
+    const float du = fmaf(B_HI, s, -u) + (B_HI * (ep + es) + B_LO * s);
+    if (u < -10.0f) {
+        const float h = expf(u);
+        const float y = (x * h) * h;
+        return y == 0.0f ? y : y + y * (2.0f * du);   // (y == 0: x^3 may have overflowed, and du with it)
+    }
+    float e = expf(2.0f * u);
+    e = e + e * (2.0f * du);
+    return x * (e / (1.0f + e));
+}
+
 template <int OP>
 __device__ __forceinline__ float pa_apply(float x, float p0, float p1) {
     if constexpr (OP == SI_PACT_CLAMP) {
@@ -38,6 +78,10 @@ __device__ __forceinline__ float pa_apply(float x, float p0, float p1) {
         if (z > p1) return x;
         // max(z, 0) + log1p(exp(-|z|)): a NaN leaves the first term 0 and comes out of the second
         return ((z > 0.0f ? z : 0.0f) + pa_log1p_unit(expf(-fabsf(z)))) / p0;
+    } else if constexpr (OP == SI_PACT_GELU) {
+        return pa_gelu_erfc(x);
+    } else if constexpr (OP == SI_PACT_GELU_TANH) {
+        return pa_gelu_tanh(x);
     } else {
         if (x > (float)SI_PACT_MISH_CUT) return x;
         const float e = expf(x);            // (a NaN fails the test above and comes out of the product below)
@@ -74,8 +118,10 @@ int check_desc(const SiParamActDesc* d) {
         case SI_PACT_SOFTPLUS:
             if (!std::isfinite(d->p0) || d->p0 == 0.0f || std::isnan(d->p1)) return SI_E_BADARG;
             break;
-        case SI_PACT_MISH: break;
-        default: return SI_E_BADARG;
+        case SI_PACT_MISH:
+        case SI_PACT_GELU:
+        case SI_PACT_GELU_TANH: break;
+        default: return SI_E_BADARG;   // (3 included: no operator has that code)
     }
     // offsets, and with them the item counts (at most one item per element, c <= ld)
     const uint64_t ld = (uint64_t)(d->in_ld > d->out_ld ? d->in_ld : d->out_ld);
@@ -128,6 +174,8 @@ int run(const SiParamActDesc* d, const T* in, T* out, si_stream_t stream) {
     switch (d->op) {
         case SI_PACT_CLAMP: return launch<SI_PACT_CLAMP, T>(d, in, out, s);
         case SI_PACT_SOFTPLUS: return launch<SI_PACT_SOFTPLUS, T>(d, in, out, s);
+        case SI_PACT_GELU: return launch<SI_PACT_GELU, T>(d, in, out, s);
+        case SI_PACT_GELU_TANH: return launch<SI_PACT_GELU_TANH, T>(d, in, out, s);
         default: return launch<SI_PACT_MISH, T>(d, in, out, s);
     }
 }
@@ -144,16 +192,21 @@ int si_hip_param_act_f16(const SiParamActDesc* d, const void* in, void* out, si_
 
 const char* si_hip_param_act_kernel_name(const SiParamActDesc* d, const void* in, const void* out, int half) {
     if (check_desc(d) != 0) return "none";
-    static const char* const names[3][4] = {
+    static const char* const names[5][4] = {
         {"param_act_kernel<clamp, float, 4>", "param_act_kernel<clamp, float, 1>", "param_act_kernel<clamp, _Float16, 8>",
          "param_act_kernel<clamp, _Float16, 1>"},
         {"param_act_kernel<softplus, float, 4>", "param_act_kernel<softplus, float, 1>", "param_act_kernel<softplus, _Float16, 8>",
          "param_act_kernel<softplus, _Float16, 1>"},
         {"param_act_kernel<mish, float, 4>", "param_act_kernel<mish, float, 1>", "param_act_kernel<mish, _Float16, 8>",
          "param_act_kernel<mish, _Float16, 1>"},
+        {"param_act_kernel<gelu, float, 4>", "param_act_kernel<gelu, float, 1>", "param_act_kernel<gelu, _Float16, 8>",
+         "param_act_kernel<gelu, _Float16, 1>"},
+        {"param_act_kernel<gelu_tanh, float, 4>", "param_act_kernel<gelu_tanh, float, 1>", "param_act_kernel<gelu_tanh, _Float16, 8>",
+         "param_act_kernel<gelu_tanh, _Float16, 1>"},
     };
     const bool vec = (half ? arm_of<_Float16>(d, in, out) : arm_of<float>(d, in, out)) != kElement;
-    return names[d->op][(half ? 2 : 0) + (vec ? 0 : 1)];
+    // (the codes skip 3: the rows of the table do not)
+    return names[d->op <= SI_PACT_MISH ? d->op : d->op - 1][(half ? 2 : 0) + (vec ? 0 : 1)];
 }
 
 }  // extern "C"

@@ -205,8 +205,10 @@ inline BatchFamily BatchFamilyOf(const std::string& type) {
         {"F.softplus", BatchFamily::kElementwise},
         {"nn.Mish", BatchFamily::kElementwise},
         {"F.mish", BatchFamily::kElementwise},
+        {"F.gelu", BatchFamily::kElementwise},
         {"UnaryOp", BatchFamily::kElementwise},
         {"nn.Linear", BatchFamily::kRows},
+        {"F.layer_norm", BatchFamily::kRows},            // (over the last dimension; weight and bias are graph constants [E], broadcast over the images)
         {"nn.Softmax", BatchFamily::kSoftmax},
         {"nn.LogSoftmax", BatchFamily::kSoftmax},
         {"nn.Softmax2d", BatchFamily::kSoftmax},

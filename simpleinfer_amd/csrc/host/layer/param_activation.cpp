@@ -49,6 +49,16 @@ Status ParamActivation::Init(const pnnx::Operator* op) {
             LOG(ERROR) << "ParamActivation::Init fail [" << t << " with beta " << p0_ << ", threshold " << p1_ << "]";
             return Status::kFail;
         }
+    } else if (t == "F.gelu" || t == "nn.GELU") {
+        // approximate=none | tanh, as pnnx writes the text (torch's default when the key is missing)
+        std::string approximate = "none";
+        if (FindParam(op, "approximate")) CHECK_BOOL(Get(op, "approximate", approximate));
+        if (approximate != "none" && approximate != "tanh") {
+            LOG(ERROR) << "ParamActivation::Init fail [" << t << " with approximate=" << approximate << ": none and tanh only]";
+            return Status::kUnsupport;
+        }
+        op_code_ = approximate == "tanh" ? SI_PACT_GELU_TANH : SI_PACT_GELU;
+        p0_ = p1_ = 0.0f;
     } else {   // nn.Mish, F.mish
         op_code_ = SI_PACT_MISH;
         p0_ = p1_ = 0.0f;

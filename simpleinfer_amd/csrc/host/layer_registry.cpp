@@ -25,6 +25,7 @@ SI_DECLARE_LAYER(GridSample)
 SI_DECLARE_LAYER(GroupNorm)
 SI_DECLARE_LAYER(HardSigmoid)
 SI_DECLARE_LAYER(HardSwish)
+SI_DECLARE_LAYER(LayerNorm)
 SI_DECLARE_LAYER(Layout)
 SI_DECLARE_LAYER(LeakyReLU)
 SI_DECLARE_LAYER(Linear)
@@ -71,7 +72,10 @@ static std::map<std::string, LayerRegistryEntry>& Table() {
     // nn.LSTM / nn.GRU (one class with a cell kind, layer/rnn.h: the input projection and the recurrent step kernel of include/si_rnn.h);
     // nn.Conv1d (layer/conv_1d.h: the temporal convolution kernels of include/si_conv1d.h on rank-3 operands in their native layout);
     // F.conv2d (layer/functional_conv_2d.h: the filter is an operand, read as stored by the cross-correlation kernels of include/si_xcorr.h);
-    // F.normalize / torch.norm (one class, layer/lp_norm.h: the Lp-norm kernels of include/si_lpnorm.h)
+    // F.normalize / torch.norm (one class, layer/lp_norm.h: the Lp-norm kernels of include/si_lpnorm.h);
+    // F.layer_norm (layer/layer_norm.h: the row kernels of include/si_layernorm.h) and F.gelu (ParamActivation: the two GELU operators of
+    // include/si_act.h).  Their module spellings nn.LayerNorm / nn.GELU are NOT registered yet: the classes read the module form too, so each is
+    // one line here and one row in batch_rule.h once the tests that pin those strings as absent may change.
     static std::map<std::string, LayerRegistryEntry> table = {
         SI_ENTRY("nn.AdaptiveAvgPool2d", AdaptiveAvgPool2d),
         SI_ENTRY("nn.AvgPool2d", AvgPool2d),
@@ -158,6 +162,8 @@ static std::map<std::string, LayerRegistryEntry>& Table() {
         SI_ENTRY("F.conv2d", FunctionalConv2d),
         SI_ENTRY("F.normalize", LpNorm),
         SI_ENTRY("torch.norm", LpNorm),
+        SI_ENTRY("F.layer_norm", LayerNorm),
+        SI_ENTRY("F.gelu", ParamActivation),
     };
     return table;
 }

@@ -1768,7 +1768,7 @@ def lpnorm_kernel_name(x_shape, p, axes, normalize=False, half=False, in_ld=None
     return _desc_kernel_name("lpnorm", lpnorm_desc(x_shape, p, axes, normalize, 0.0, in_ld, out_ld), half)
 
 
-PARAM_ACT_OPS = {"clamp": 0, "softplus": 1, "mish": 2}
+PARAM_ACT_OPS = {"clamp": 0, "softplus": 1, "mish": 2, "gelu": 4, "gelu_tanh": 5}   # (3 is no operator: the entries refuse it)
 
 
 def param_act_desc(x_shape, op, p0=0.0, p1=0.0, in_ld=None, out_ld=None):
@@ -1780,7 +1780,7 @@ def param_act_desc(x_shape, op, p0=0.0, p1=0.0, in_ld=None, out_ld=None):
 
 def param_act(x, op, p0=0.0, p1=0.0, half=False, in_ld=None, in_c_off=0, in_fill=0.0, out_ld=None, out_c_off=0, out_fill=0.0, full=False):
     """si_hip_param_act_f32 / _f16 (half=True, or a float16 array) on an array whose last axis is the channels: clamp (p0 lo, p1 hi),
-    softplus (p0 beta, p1 threshold) or mish.  The view hooks are the common ones."""
+    softplus (p0 beta, p1 threshold), mish, gelu or gelu_tanh.  The view hooks are the common ones."""
     x = np.asarray(x)
     x = np.ascontiguousarray(x, dtype=np.float16) if (half or x.dtype == np.float16) else _f32(x)
     d = param_act_desc(x.shape, op, p0, p1, in_ld, out_ld)
@@ -1791,6 +1791,40 @@ def param_act_kernel_name(x_shape, op, p0=0.0, p1=0.0, half=False, in_ld=None, o
     """the instantiation for 16-byte aligned buffers of these shapes ("none": a descriptor the launch refuses)"""
     d = param_act_desc(x_shape, op, p0, p1, in_ld, out_ld)
     return _desc_kernel_name("param_act", d, half)
+
+
+def gelu(x, approximate="none", **views):
+    """F.gelu through the parametrised-activation entries: approximate = "none" (0.5 x erfc(-x / sqrt 2)) or "tanh" (torch's formula)"""
+    return param_act(x, {"none": "gelu", "tanh": "gelu_tanh"}[approximate], **views)
+
+
+def layernorm_desc(rows, c, eps=1e-5, in_ld=None, out_ld=None):
+    """SiLayerNormDesc (include/si_layernorm.h): `rows` rows of `c` contiguous elements"""
+    return _native.SiLayerNormDesc(int(rows), int(c), int(in_ld or c), int(out_ld or c), float(eps))
+
+
+def layernorm(x, gamma=None, beta=None, eps=1e-5, in_ld=None, in_c_off=0, in_fill=0.0, out_ld=None, out_c_off=0, out_fill=0.0, full=False):
+    """si_hip_layernorm_f32 / _f16 (by the array's dtype): F.layer_norm over the last axis of an array of any rank >= 2; gamma / beta fp32
+    [c] or None.  The view hooks are the common ones."""
+    H = _native.hip()
+    x = _float_storage(x)
+    half = x.dtype == np.float16
+    c = x.shape[-1]
+    rows = int(np.prod(x.shape[:-1], dtype=np.int64))
+    d = layernorm_desc(rows, c, eps, in_ld, out_ld)
+    (dx, px), (dy, py) = _view_in(x, in_ld, in_c_off, in_fill), _view_out(x.shape[:-1], c, out_ld, out_c_off, out_fill, x.dtype)
+    dg = DeviceBuffer.from_numpy(_f32(gamma)) if gamma is not None else None
+    db = DeviceBuffer.from_numpy(_f32(beta)) if beta is not None else None
+    assert (dg is None or dg.nbytes == 4 * c) and (db is None or db.nbytes == 4 * c)
+    LAST_KERNEL_NAME["si_hip_layernorm"] = H.si_hip_layernorm_kernel_name(C.byref(d), C.c_void_p(px), C.c_void_p(py), 1 if half else 0).decode()
+    name = "si_hip_layernorm_f16" if half else "si_hip_layernorm_f32"
+    _chk(getattr(H, name)(C.byref(d), px, dg.ptr if dg else None, db.ptr if db else None, py, None), name)
+    return _ret(dy.to_numpy(tuple(x.shape[:-1]) + (out_ld or c,), x.dtype), c, out_c_off, full)
+
+
+def layernorm_kernel_name(rows, c, half=False, in_ld=None, out_ld=None) -> str:
+    """the instantiation for 16-byte aligned buffers of these shapes ("none": a descriptor the launch refuses)"""
+    return _desc_kernel_name("layernorm", layernorm_desc(rows, c, 1e-5, in_ld, out_ld), half)
 
 
 def pixel_shuffle_desc(x_shape, r, inverse=False, in_ld=None, out_ld=None):

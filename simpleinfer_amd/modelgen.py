@@ -395,6 +395,29 @@ class PnnxBuilder:
         self._emit("torch.norm", self._opname("torch_norm"), [x], [out], params)
         return out
 
+    def layer_norm(self, x: str, weight=True, bias=True, eps: float = 1e-5) -> str:
+        """pnnx's F.layer_norm line over the last dimension: `F.layer_norm name 3 1 x w b out eps= normalized_shape=(E)`, weight and bias graph
+        constants written through attribute(); an absent one is the key weight=None / bias=None and no operand.  weight / bias: True (seeded
+        values), False / None, an array, or the name of an operand (an activation as weight: the engine refuses it)."""
+        e = self.shapes[x][-1]
+        name = self._opname("F_layer_norm")
+        ins, params = [x], {}
+        for key, given, lo, hi in (("weight", weight, 0.5, 1.5), ("bias", bias, -0.5, 0.5)):
+            if given is None or given is False:
+                params[key] = "None"
+            elif isinstance(given, str):
+                ins.append(given)
+            else:
+                ins.append(self.attribute(seeded_uniform("%s.%s" % (name, key), (e,), lo, hi, self.seed) if given is True else given))
+        params.update(eps=float(eps), normalized_shape=(int(e),))
+        out = self._new_operand(self.shapes[x])
+        self._emit("F.layer_norm", name, ins, [out], params)
+        return out
+
+    def gelu(self, x: str, approximate: str = "none") -> str:
+        """pnnx's F.gelu line: approximate=none | tanh, the bare text"""
+        return self._unary("F.gelu", "F_gelu", x, dict(approximate=str(approximate)))
+
     def div(self, a: str, b: str) -> str:
         sa, sb = self.shapes[a], self.shapes[b]
         return self.expression("div(@0,@1)", [a, b], tuple(max(x, y) for x, y in zip(sa, sb)))
@@ -1315,6 +1338,23 @@ def build_toy_c3tr(batch: int = 2, size: int = 32, c: int = 32, heads: int = 4, 
         x = b.add(b.linear(b.linear(x, c, bias=False), c, bias=False), x)
     x = b.reshape(b.permute(x, (1, 2, 0)), (batch, c, w, h))
     b.output(b.silu(b.conv(x, c, 1)))
+    return b
+
+
+def build_toy_vit_block(batch: int = 2, tokens: int = 16, e: int = 32, heads: int = 4, layers: int = 2, seed: int = 0) -> PnnxBuilder:
+    """A pre-norm vision transformer in small, in the functional spellings an export writes for custom norm modules: a 4x4 stride-4 conv patch
+    embedding -> permute(0, 2, 3, 1) -> view(N, L, E) (a view, not a launch); per layer x + MHA(LN(x)) (nn.MultiheadAttention, batch_first,
+    one input) and x + Linear(GELU(Linear(LN(x)))) with a 2E hidden width; a final LN -> Linear closes it.  Every LN is F.layer_norm with
+    constant weight and bias, the GELU is F.gelu(approximate=none).  tokens: a square number (the patch grid)."""
+    side = int(round(math.sqrt(tokens)))
+    assert side * side == tokens, tokens
+    b = PnnxBuilder(seed)
+    x = b.conv(b.input((batch, 3, 4 * side, 4 * side)), e, 4, 4, 0)
+    x = b.view(b.permute(x, (0, 2, 3, 1)), (batch, -1, e))
+    for _ in range(layers):
+        x = b.add(b.multihead_attention(b.layer_norm(x), num_heads=heads, batch_first=True), x)
+        x = b.add(b.linear(b.gelu(b.linear(b.layer_norm(x), 2 * e)), e), x)
+    b.output(b.linear(b.layer_norm(x), 10))
     return b
 
 
