@@ -204,6 +204,17 @@ class SiDetectMaskDesc(C.Structure):
         ("ratio_w", C.c_float), ("ratio_h", C.c_float)]
 
 
+class SiDetectObbDesc(C.Structure):
+    """include/si_obb.h; the fields of SiDetectPostDesc with angle_off (the angle is payload element angle_off) in the place of box_format"""
+    _fields_ = [(k, C.c_int) for k in ("n", "rows", "classes", "objectness", "extra", "layout", "ld")] + [("image_ld", C.c_longlong),
+                ("angle_off", C.c_int), ("prob_threshold", C.c_float), ("nms_threshold", C.c_float), ("agnostic", C.c_int), ("max_det", C.c_int)]
+
+
+class SiDetectObbOut(C.Structure):
+    """include/si_obb.h; device pointers: obbs and counts, and the two optional outputs (NULL: not wanted)"""
+    _fields_ = [(k, C.c_void_p) for k in ("obbs", "counts", "src_rows", "extras")]
+
+
 class SiBinaryDesc(C.Structure):
     """include/si_binary.h; d: extents of x / out in storage order, c0_stride / c1_stride: element strides of the constants (0: broadcast)"""
     _fields_ = [("d", C.c_int * 4), ("x_ld", C.c_int), ("out_ld", C.c_int), ("stages", C.c_int), ("op", C.c_int * 2), ("c0_stride", C.c_int * 4),
@@ -529,7 +540,12 @@ def hip():
         "si_hip_layernorm_f16": (i, [C.POINTER(SiLayerNormDesc), vp, vp, vp, vp, vp]),
         "si_hip_layernorm_kernel_name": (C.c_char_p, [C.POINTER(SiLayerNormDesc), vp, vp, i]),
     }
-    for name, (res, args) in (list(border_.items()) + list(sig.items()) + list(norm.items()) + list(pad.items()) + list(pool.items()) + list(softmax.items()) +
+    # include/si_obb.h: oriented-box post-processing (ProbIoU rotated NMS)
+    obb_ = {
+        "si_hip_detect_obb_postprocess_workspace_bytes": (sz, [C.POINTER(SiDetectObbDesc)]),
+        "si_hip_detect_obb_postprocess_f32": (i, [C.POINTER(SiDetectObbDesc), vp, vp, C.POINTER(SiDetectObbOut), vp, sz, vp]),
+    }
+    for name, (res, args) in (list(obb_.items()) + list(border_.items()) + list(sig.items()) + list(norm.items()) + list(pad.items()) + list(pool.items()) + list(softmax.items()) +
                               list(superres.items()) + list(slice_.items()) + list(reduce_.items()) + list(act.items()) + list(permute_.items()) +
                               list(attention_.items()) + list(deform_.items()) + list(grid_.items()) + list(roi_.items()) + list(rnn_.items()) +
                               list(binary_.items()) + list(conv1d_.items()) + list(xcorr_.items()) + list(detect_.items()) + list(lpnorm_.items()) +
@@ -559,6 +575,7 @@ def hip():
     L._si_lpnorm_signatures = lpnorm_
     L._si_layernorm_signatures = layernorm_
     L._si_border_signatures = border_
+    L._si_obb_signatures = obb_
     _hip = L
     return L
 

@@ -30,8 +30,10 @@ ARCH = "gfx950"
 # layernorm.hip: the same switch for the same reason -- a row's bits must not depend on which of a lane's items the compiler pairs
 # (include/si_layernorm.h).  activation_param.hip: the GELU operators' compensated arithmetic stays scalar (the build without the switch pairs
 # 28 of its operations); the instructions of the clamp / softplus / mish kernels are the same with and without it (disassembly).
+# detect_obb.hip: the pair arithmetic of include/si_obb.h is stated operation by operation and stays scalar.
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-FILE_FLAGS = {"conv_border.hip": _NO_PACKED_FP32, "layernorm.hip": _NO_PACKED_FP32, "activation_param.hip": _NO_PACKED_FP32}
+FILE_FLAGS = {"conv_border.hip": _NO_PACKED_FP32, "layernorm.hip": _NO_PACKED_FP32, "activation_param.hip": _NO_PACKED_FP32,
+              "detect_obb.hip": _NO_PACKED_FP32}
 
 
 def _newest(paths):

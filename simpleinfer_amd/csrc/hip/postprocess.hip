@@ -9,6 +9,7 @@
 #include "si_detect.h"
 #include "si_hip_internal.h"
 #include "detect_plan.h"
+#include "detect_post.h"
 
 #pragma clang fp contract(off)
 
@@ -125,54 +126,11 @@ __global__ void resize_letterbox_batch_kernel(const unsigned char* __restrict__ 
 }
 
 // ---- post-processing workspace ----------------------------------------------------------------
-// The regions, their order and their sizes: detect_plan.h (Layout).  srow / drow exist in the general entry's layout alone and are
-// null for si_hip_yolo_postprocess_f32, whose byte count is what it always was.
+// PostWs, its binding to a workspace and the filter's arguments: detect_post.h, shared with detect_obb.hip.
 namespace plan = si_detect_plan;
-
-struct PostWs {
-    int* count;
-    int* bin_count;
-    int* keep;
-    int nbins;
-    size_t zero_bytes;
-    float4* gbox;
-    int* grank;
-    unsigned long long* key;
-    float4* box;
-    int* label;
-    float4* sbox;
-    int* slabel;
-    float* sprob;
-    float4* pbox;
-    int* plabel;
-    float* parea;
-    int* srow;   // prediction row of each candidate in the confidence order
-    int* drow;   // prediction row of each stored detection: what the payload gather reads
-};
-
-inline size_t post_ws_bind(int n, int cap, int nbins, bool general, char* base, PostWs* ws) {
-    const plan::Workspace w = plan::Layout(n, cap, nbins, general);
-    auto at = [&](int r) { return w.bytes[r] ? base + w.offset[r] : nullptr; };
-    ws->count = (int*)at(plan::kCount);
-    ws->bin_count = (int*)at(plan::kBinCount);
-    ws->keep = (int*)at(plan::kKeep);
-    ws->nbins = nbins;
-    ws->zero_bytes = w.zero_bytes;
-    ws->gbox = (float4*)at(plan::kGbox);
-    ws->grank = (int*)at(plan::kGrank);
-    ws->key = (unsigned long long*)at(plan::kKey);
-    ws->box = (float4*)at(plan::kBox);
-    ws->label = (int*)at(plan::kLabel);
-    ws->sbox = (float4*)at(plan::kSbox);
-    ws->slabel = (int*)at(plan::kSlabel);
-    ws->sprob = (float*)at(plan::kSprob);
-    ws->pbox = (float4*)at(plan::kPbox);
-    ws->plabel = (int*)at(plan::kPlabel);
-    ws->parea = (float*)at(plan::kParea);
-    ws->srow = (int*)at(plan::kSrow);
-    ws->drow = (int*)at(plan::kDrow);
-    return w.total;
-}
+using si_post::FilterArgs;
+using si_post::PostWs;
+using si_post::post_ws_bind;
 
 // what the general entry adds to the NMS / compaction kernels' outputs: each pointer may be null (all are for si_hip_yolo_postprocess_f32)
 struct PostMore {
@@ -192,14 +150,6 @@ __device__ __forceinline__ unsigned ordered_bits(float f) {
 // class score alone, kept when >= prob_threshold.  Survivors are appended to the image's candidate list (order is irrelevant: the sort
 // key carries the element index).  The payload behind the class scores is never read here.
 constexpr int RPB = plan::kStageRows;
-
-struct FilterArgs {
-    const float* pred;
-    long long image_ld;
-    int rows, ld;
-    int classes, objectness, box_format;
-    float prob_threshold;
-};
 
 // a kept row: its box from the four raw elements, its label, its sort key
 __device__ __forceinline__ void post_emit(const PostWs& ws, int b, int rows, int e, float r0, float r1, float r2, float r3, int box_format,
@@ -617,14 +567,8 @@ struct PostLaunch {
 
 int post_launch(const PostLaunch& L, const PostWs& ws, const PostMore& more, hipStream_t s) {
     const int n = L.n, rows = L.filter.rows;
-    SI_HIP_TRY(hipMemsetAsync(ws.count, 0, ws.zero_bytes, s));
-    if (L.layout == plan::kRows) {
-        const size_t lds = (size_t)RPB * (size_t)(4 + L.filter.objectness + L.filter.classes) * sizeof(float);
-        hipLaunchKernelGGL(detect_filter_rows_kernel, dim3((rows + RPB - 1) / RPB, n), dim3(RPB), lds, s, L.filter, ws);
-    } else {
-        hipLaunchKernelGGL(detect_filter_channels_kernel, dim3((rows + CH_T - 1) / CH_T, n), dim3(CH_T), 0, s, L.filter, ws);
-    }
-    hipLaunchKernelGGL(yolo_rank_sort_kernel, dim3((rows + SORT_T - 1) / SORT_T, n), dim3(SORT_T), 0, s, rows, ws);
+    const int rc = si_post::front_launch(L.filter, n, L.layout, ws, s);
+    if (rc != 0) return rc;
     if (L.agnostic) {
         // one chain per image: a workgroup walks the confidence order against everything picked so far
         hipLaunchKernelGGL(yolo_nms_kernel, dim3(n), dim3(256), 0, s, rows, L.nms_threshold, 1, L.adjust, L.dets, L.counts, L.max_det, ws, more);
@@ -632,13 +576,9 @@ int post_launch(const PostLaunch& L, const PostWs& ws, const PostMore& more, hip
         hipLaunchKernelGGL(yolo_nms_segments_kernel, dim3((ws.nbins + 3) / 4, n), dim3(256), 0, s, rows, L.nms_threshold, ws);
         hipLaunchKernelGGL(yolo_compact_kernel, dim3(n), dim3(256), 0, s, rows, L.adjust, L.dets, L.counts, L.max_det, ws, more);
     }
-    if (L.extras && L.extra > 0 && L.max_det > 0) {
-        const size_t items = (size_t)(L.max_det < rows ? L.max_det : rows) * (size_t)L.extra;
-        const size_t gx = (items + 255) / 256;
-        hipLaunchKernelGGL(detect_gather_kernel, dim3((unsigned)(gx > 64 ? 64 : gx), n), dim3(256), 0, s, (const unsigned*)L.filter.pred,
-                           L.filter.image_ld, rows, L.filter.ld, L.layout, 4 + L.filter.objectness + L.filter.classes, L.extra, L.counts, L.max_det,
-                           more.drow, (unsigned*)L.extras);
-    }
+    if (L.extras && L.extra > 0 && L.max_det > 0)
+        return si_post::gather_launch(L.filter, n, L.layout, 4 + L.filter.objectness + L.filter.classes, L.extra, L.counts, L.max_det, more.drow,
+                                      L.extras, s);
     return (int)hipGetLastError();
 }
 
@@ -650,6 +590,28 @@ plan::Shape detect_shape(const SiDetectPostDesc* d) {
 }
 
 }  // namespace
+
+int si_post::front_launch(const FilterArgs& filter, int n, int layout, const PostWs& ws, hipStream_t s) {
+    const int rows = filter.rows;
+    SI_HIP_TRY(hipMemsetAsync(ws.count, 0, ws.zero_bytes, s));
+    if (layout == plan::kRows) {
+        const size_t lds = (size_t)RPB * (size_t)(4 + filter.objectness + filter.classes) * sizeof(float);
+        hipLaunchKernelGGL(detect_filter_rows_kernel, dim3((rows + RPB - 1) / RPB, n), dim3(RPB), lds, s, filter, ws);
+    } else {
+        hipLaunchKernelGGL(detect_filter_channels_kernel, dim3((rows + CH_T - 1) / CH_T, n), dim3(CH_T), 0, s, filter, ws);
+    }
+    hipLaunchKernelGGL(yolo_rank_sort_kernel, dim3((rows + SORT_T - 1) / SORT_T, n), dim3(SORT_T), 0, s, rows, ws);
+    return (int)hipGetLastError();
+}
+
+int si_post::gather_launch(const FilterArgs& filter, int n, int layout, int first, int extra, const int* counts, int max_det, const int* drow,
+                           float* extras, hipStream_t s) {
+    const size_t items = (size_t)(max_det < filter.rows ? max_det : filter.rows) * (size_t)extra;
+    const size_t gx = (items + 255) / 256;
+    hipLaunchKernelGGL(detect_gather_kernel, dim3((unsigned)(gx > 64 ? 64 : gx), n), dim3(256), 0, s, (const unsigned*)filter.pred, filter.image_ld,
+                       filter.rows, filter.ld, layout, first, extra, counts, max_det, drow, (unsigned*)extras);
+    return (int)hipGetLastError();
+}
 
 extern "C" {
 

@@ -2366,6 +2366,68 @@ def detect_masks(protos, extras, net_boxes, counts, ratio_w=0.25, ratio_h=0.25, 
     return [DeviceBuffer.view(dmask.ptr + b * max_det * mh * mw, max(kept[b] * mh * mw, 16)).to_numpy((kept[b], mh, mw), np.uint8, stream) for b in range(n)]
 
 
+# ---- include/si_obb.h: oriented boxes, rotated NMS by ProbIoU ----------------------------------------------------------------------------------
+def detect_obb_desc(n, rows, classes, extra=1, angle_off=0, objectness=False, layout="rows", prob_threshold=0.25, nms_threshold=0.45,
+                    agnostic=False, max_det=None, ld=None, image_ld=None):
+    """SiDetectObbDesc; ld / image_ld default to the dense strides of the layout, max_det to rows"""
+    p = detect_desc(n, rows, classes, objectness, extra, layout, "cxcywh", prob_threshold, nms_threshold, agnostic, max_det, ld, image_ld)
+    return _native.SiDetectObbDesc(p.n, p.rows, p.classes, p.objectness, p.extra, p.layout, p.ld, p.image_ld, int(angle_off), p.prob_threshold,
+                                   p.nms_threshold, p.agnostic, p.max_det)
+
+
+def detect_obb_workspace_bytes(d) -> int:
+    return int(_native.hip().si_hip_detect_obb_postprocess_workspace_bytes(C.byref(d)))
+
+
+class DetectObbResult:
+    """what detect_obb_postprocess returns: per-image lists cut to min(counts[b], max_det) (obbs [k][7] = cx, cy, w, h, angle, confidence,
+    label; src_rows [k]; extras [k][extra]; None for an output that was not asked for), counts [n], `full`: the whole output arrays as read
+    back, `dev`: their device buffers"""
+
+    def __init__(self, n, max_det, extra, counts, full, dev):
+        self.n, self.max_det, self.extra, self.counts, self.full, self.dev = n, max_det, extra, counts, full, dev
+        k = [min(int(c), max_det) for c in counts]
+        for name in ("obbs", "src_rows", "extras"):
+            a = full.get(name)
+            setattr(self, name, None if a is None else [a[b, :k[b]].copy() for b in range(n)])
+
+
+def detect_obb_postprocess(pred, classes, extra=1, angle_off=0, objectness=False, layout="rows", prob_threshold=0.25, nms_threshold=0.45,
+                           agnostic=False, adjust=None, max_det=None, pred_dev=None, ld=None, image_ld=None, workspace=None, shape=None, pred_off=0,
+                           in_fill=np.nan, want=("src_rows", "extras"), out_fill=0.0, stream=None):
+    """si_hip_detect_obb_postprocess_f32 (include/si_obb.h).  pred: the logical array, [n][rows][ne] for layout "rows" and [n][ne][rows] for
+    "channels", rows = cx, cy, w, h | class scores | payload, the angle (radians) at payload element angle_off; ld / image_ld / pred_off lay it
+    out with gaps (filled with in_fill).  pred_dev: a DeviceBuffer (or a view on an Engine.extract pointer with outputs_to_host=0) that already
+    holds the storage, with shape = (n, rows); pred is then not read.  Returns a DetectObbResult."""
+    H = _native.hip()
+    lay = DETECT_LAYOUTS[layout]
+    if pred_dev is None:
+        pred = _f32(pred)
+        n, rows = (pred.shape[0], pred.shape[2]) if lay == 1 else (pred.shape[0], pred.shape[1])
+        dbuf = DeviceBuffer.from_numpy(detect_storage(pred, layout, ld, image_ld, pred_off, in_fill))
+        pred_ptr = dbuf.ptr + 4 * pred_off
+    else:
+        n, rows = (int(v) for v in shape)
+        pred_ptr = pred_dev.ptr + 4 * pred_off
+    d = detect_obb_desc(n, rows, classes, extra, angle_off, objectness, layout, prob_threshold, nms_threshold, agnostic, max_det, ld, image_ld)
+    max_det = d.max_det
+    dadj = DeviceBuffer.from_numpy(_f32(adjust).reshape(n, 5)) if adjust is not None else None
+    wsb = detect_obb_workspace_bytes(d)
+    dws = workspace if workspace is not None else DeviceBuffer(max(wsb, 16))
+    assert wsb == 0 or dws.nbytes >= wsb, "workspace of %d bytes, the call needs %d" % (dws.nbytes, wsb)
+    shapes = {"obbs": ((n, max_det, 7), np.float32), "counts": ((n,), np.int32), "src_rows": ((n, max_det), np.int32),
+              "extras": ((n, max_det, int(extra)), np.float32)}
+    dev = {}
+    for name, (shp, dt) in shapes.items():
+        if name in ("obbs", "counts") or name in want:
+            dev[name] = DeviceBuffer.from_numpy(_full((max(int(np.prod(shp)), 4),), dt, out_fill), out=True)
+    out = _native.SiDetectObbOut(*[dev[k].ptr if k in dev else None for k in ("obbs", "counts", "src_rows", "extras")])
+    _chk(H.si_hip_detect_obb_postprocess_f32(C.byref(d), pred_ptr, dadj.ptr if dadj else None, C.byref(out), dws.ptr, dws.nbytes, stream),
+         "si_hip_detect_obb_postprocess_f32")
+    full = {k: b.to_numpy(shapes[k][0], shapes[k][1], stream) for k, b in dev.items()}
+    return DetectObbResult(n, max_det, int(extra), full["counts"].copy(), full, dev)
+
+
 # ---------------------------------------------------------------------------
 # fp16 storage path (include/si_hip.h "fp16 storage path").  Activations travel as numpy float16 (IEEE binary16, the
 # device's _Float16); results come back as float16 unless noted.
