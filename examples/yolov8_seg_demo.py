@@ -4,9 +4,10 @@ detect_masks (coefficients x prototypes, cropped to the box), with synthetic "ph
 (modelgen.build_toy_yolov8_seg: the boxes mean nothing, and the threshold is set where its scores leave a few per cent of the rows -- the
 point is the data flow).  Both graph outputs stay in HBM (outputs_to_host=0): the channel-major head [N, 4 + nc + nm, cells] is read where
 the engine left it, without a permute, and so are the prototypes; only dets, counts and the mask planes of the kept detections are copied
-to the host.
+to the host.  With --source-masks the planes come at each photo's own size instead (detect_image_masks, include/si_imgmask.h: product, bilinear
+upsample of the un-padded window, crop by the un-letterboxed boxes and threshold in one launch; ultralytics' retina_masks).
 
-    python examples/yolov8_seg_demo.py [--size 256] [--images 4] [--rows]
+    python examples/yolov8_seg_demo.py [--size 256] [--images 4] [--rows] [--source-masks]
 """
 import argparse
 import os
@@ -20,7 +21,8 @@ import simpleinfer_amd as si  # noqa: E402
 from simpleinfer_amd import hipops  # noqa: E402
 
 
-def run(size=256, images=((480, 640), (1080, 810), (375, 500), (720, 1280)), nc=5, nm=32, channels_first=True, prob_threshold=0.45, max_det=100, seed=0):
+def run(size=256, images=((480, 640), (1080, 810), (375, 500), (720, 1280)), nc=5, nm=32, channels_first=True, prob_threshold=0.45, max_det=100, seed=0,
+        source_masks=False):
     mg = si.modelgen
     n = len(images)
     rng = np.random.Generator(np.random.Philox(seed))
@@ -48,8 +50,15 @@ def run(size=256, images=((480, 640), (1080, 810), (375, 500), (720, 1280)), nc=
                                         nms_threshold=0.45, adjust=adjust, max_det=max_det, pred_dev=head, shape=(n, cells), host=("dets", "counts"), stream=e.stream())
         mh, mw = proto_shape[1], proto_shape[2]
         protos = hipops.DeviceBuffer.view(pptr, int(np.prod(proto_shape)) * 4)
-        masks = hipops.detect_masks(None, res, None, None, np.float32(mw) / np.float32(size), np.float32(mh) / np.float32(size), protos_dev=protos,
-                                    shape=proto_shape, stream=e.stream())
+        if source_masks:
+            # the dets rows are already in the source frame (adjust): they are the boxes of crop "after"; planes are sized for the largest photo
+            geom = [hipops.letterbox_window(hw, (mh, mw), (size, size)).geom for hw in images]
+            out_hw = (max(h for h, _ in images), max(w for _, w in images))
+            masks = hipops.detect_image_masks(None, res, None, None, geom, out_hw, "after", protos_dev=protos, shape=proto_shape, stream=e.stream())
+            masks = [m[:, :h, :w] for m, (h, w) in zip(masks, images)]
+        else:
+            masks = hipops.detect_masks(None, res, None, None, np.float32(mw) / np.float32(size), np.float32(mh) / np.float32(size), protos_dev=protos,
+                                        shape=proto_shape, stream=e.stream())
     return res, masks, cells
 
 
@@ -58,9 +67,10 @@ if __name__ == "__main__":
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--images", type=int, default=4)
     ap.add_argument("--rows", action="store_true", help="the export with the closing permute: [N, cells, no]")
+    ap.add_argument("--source-masks", action="store_true", help="masks at each photo's own size (detect_image_masks) instead of the prototypes'")
     a = ap.parse_args()
     shapes = ((480, 640), (1080, 810), (375, 500), (720, 1280))[:a.images]
-    res, masks, cells = run(a.size, shapes, channels_first=not a.rows)
+    res, masks, cells = run(a.size, shapes, channels_first=not a.rows, source_masks=a.source_masks)
     for b, d in enumerate(res.dets):
         print("image %d (%dx%d): %d boxes kept of %d predictions (%d stored); mask pixels per box: %s; first: %s" % (
             b, shapes[b][1], shapes[b][0], res.counts[b], cells, len(d), [int(m.sum()) for m in masks[b]][:8],

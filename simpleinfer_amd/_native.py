@@ -215,6 +215,12 @@ class SiDetectObbOut(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("obbs", "counts", "src_rows", "extras")]
 
 
+class SiImageMaskDesc(C.Structure):
+    """include/si_imgmask.h; the prototype / payload fields of SiDetectMaskDesc, then the output planes [oh][ow], the stride of the box rows, the
+    crop (0: after the upsample, boxes in the output frame; 1: first, boxes in the window's frame) and flags (1: force the direct arm)"""
+    _fields_ = [(k, C.c_int) for k in ("n", "mh", "mw", "nm", "proto_ld", "max_det", "extra", "coef_off", "oh", "ow", "box_ld", "crop", "flags")]
+
+
 class SiBinaryDesc(C.Structure):
     """include/si_binary.h; d: extents of x / out in storage order, c0_stride / c1_stride: element strides of the constants (0: broadcast)"""
     _fields_ = [("d", C.c_int * 4), ("x_ld", C.c_int), ("out_ld", C.c_int), ("stages", C.c_int), ("op", C.c_int * 2), ("c0_stride", C.c_int * 4),
@@ -545,7 +551,12 @@ def hip():
         "si_hip_detect_obb_postprocess_workspace_bytes": (sz, [C.POINTER(SiDetectObbDesc)]),
         "si_hip_detect_obb_postprocess_f32": (i, [C.POINTER(SiDetectObbDesc), vp, vp, C.POINTER(SiDetectObbOut), vp, sz, vp]),
     }
-    for name, (res, args) in (list(obb_.items()) + list(border_.items()) + list(sig.items()) + list(norm.items()) + list(pad.items()) + list(pool.items()) + list(softmax.items()) +
+    # include/si_imgmask.h: instance masks at image size (product, upsample, crop and threshold fused)
+    imgmask_ = {
+        "si_hip_detect_image_masks_f32": (i, [C.POINTER(SiImageMaskDesc), vp, vp, vp, vp, vp, vp, vp]),
+        "si_hip_detect_image_masks_kernel_name": (C.c_char_p, [C.POINTER(SiImageMaskDesc), vp, vp]),
+    }
+    for name, (res, args) in (list(imgmask_.items()) + list(obb_.items()) + list(border_.items()) + list(sig.items()) + list(norm.items()) + list(pad.items()) + list(pool.items()) + list(softmax.items()) +
                               list(superres.items()) + list(slice_.items()) + list(reduce_.items()) + list(act.items()) + list(permute_.items()) +
                               list(attention_.items()) + list(deform_.items()) + list(grid_.items()) + list(roi_.items()) + list(rnn_.items()) +
                               list(binary_.items()) + list(conv1d_.items()) + list(xcorr_.items()) + list(detect_.items()) + list(lpnorm_.items()) +
@@ -576,6 +587,7 @@ def hip():
     L._si_layernorm_signatures = layernorm_
     L._si_border_signatures = border_
     L._si_obb_signatures = obb_
+    L._si_imgmask_signatures = imgmask_
     _hip = L
     return L
 

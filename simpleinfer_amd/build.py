@@ -31,9 +31,10 @@ ARCH = "gfx950"
 # (include/si_layernorm.h).  activation_param.hip: the GELU operators' compensated arithmetic stays scalar (the build without the switch pairs
 # 28 of its operations); the instructions of the clamp / softplus / mish kernels are the same with and without it (disassembly).
 # detect_obb.hip: the pair arithmetic of include/si_obb.h is stated operation by operation and stays scalar.
+# detect_image_masks.hip: likewise the dot and the blend of include/si_imgmask.h; a byte must not depend on which of a lane's four pixels pair up.
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 FILE_FLAGS = {"conv_border.hip": _NO_PACKED_FP32, "layernorm.hip": _NO_PACKED_FP32, "activation_param.hip": _NO_PACKED_FP32,
-              "detect_obb.hip": _NO_PACKED_FP32}
+              "detect_obb.hip": _NO_PACKED_FP32, "detect_image_masks.hip": _NO_PACKED_FP32}
 
 
 def _newest(paths):

@@ -7,7 +7,7 @@ computation happens in Python; without a HIP device every call raises HipError.
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import numpy as np
 
@@ -2364,6 +2364,95 @@ def detect_masks(protos, extras, net_boxes, counts, ratio_w=0.25, ratio_h=0.25, 
     # the planes of the kept detections alone leave the device
     kept = [min(int(cnt[b]), max_det) for b in range(n)]
     return [DeviceBuffer.view(dmask.ptr + b * max_det * mh * mw, max(kept[b] * mh * mw, 16)).to_numpy((kept[b], mh, mw), np.uint8, stream) for b in range(n)]
+
+
+# ---- include/si_imgmask.h: instance masks at image size ---------------------------------------------------------------------------------------
+IMGMASK_CROPS = {"after": 0, "first": 1}
+
+
+def image_mask_desc(n, mh, mw, nm, max_det, extra, oh, ow, coef_off=0, proto_ld=None, box_ld=4, crop="after", force_direct=False):
+    return _native.SiImageMaskDesc(int(n), int(mh), int(mw), int(nm), int(nm if proto_ld is None else proto_ld), int(max_det), int(extra),
+                                   int(coef_off), int(oh), int(ow), int(box_ld), IMGMASK_CROPS[crop], 1 if force_direct else 0)
+
+
+def detect_image_masks_kernel_name(d, protos_ptr=256, masks_ptr=256) -> str:
+    return _native.hip().si_hip_detect_image_masks_kernel_name(C.byref(d), C.c_void_p(protos_ptr), C.c_void_p(masks_ptr)).decode()
+
+
+class LetterboxWindow(NamedTuple):
+    geom: np.ndarray        # int32 [6]: win_x0, win_y0, win_w, win_h, out_w, out_h -- one record of detect_image_masks
+    ratio: tuple            # (ratio_w, ratio_h): prototype pixels per network pixel
+    origin: tuple           # (win_x0, win_y0): a network-frame box {x, y, w, h} is {x * ratio_w - win_x0, y * ratio_h - win_y0, w * ratio_w, h * ratio_h}
+                            # in the window's frame (crop "first"); crop "after" takes the source-frame boxes the post-processing's adjust makes
+
+
+def letterbox_window(src_hw, proto_hw, net_hw=None) -> LetterboxWindow:
+    """the window of a [mh][mw] prototype plane that a centred letterbox of a src_hw image covers, with the rounding of ultralytics' scale_masks
+    (top / left = int(round(pad - 0.1)), bottom / right = size - int(round(pad + 0.1))), and the source size as the output.  net_hw: the
+    network input's size (default: four times the prototypes), for the ratio"""
+    (sh, sw), (mh, mw) = (int(v) for v in src_hw), (int(v) for v in proto_hw)
+    nh, nw = (4 * mh, 4 * mw) if net_hw is None else (int(v) for v in net_hw)
+    gain = min(mh / sh, mw / sw)
+    pad_w, pad_h = (mw - sw * gain) / 2, (mh - sh * gain) / 2
+    top, left = int(round(pad_h - 0.1)), int(round(pad_w - 0.1))
+    bottom, right = mh - int(round(pad_h + 0.1)), mw - int(round(pad_w + 0.1))
+    return LetterboxWindow(np.asarray([left, top, right - left, bottom - top, sw, sh], np.int32), (mw / nw, mh / nh), (left, top))
+
+
+def detect_image_masks(protos, extras, boxes, counts, geom, out_hw, crop="after", coef_off=0, nm=None, proto_ld=None, protos_dev=None, shape=None,
+                       protos_off=0, box_ld=None, masks_off=0, in_fill=np.nan, out_fill=0, full=False, force_direct=False, stream=None):
+    """si_hip_detect_image_masks_f32 (include/si_imgmask.h).  protos / protos_dev / shape / proto_ld / protos_off and extras / counts as
+    detect_masks takes them; extras may be a DetectResult, whose device buffers are read where detect_postprocess left them, and boxes=None
+    then passes its dets rows as they are (box_ld 6: source-frame boxes when the post-processing had an adjust, for crop "after").  boxes
+    otherwise [n][max_det][>= 4] {x, y, w, h} in the output frame (crop "after") or in the window's frame (crop "first"), laid out with row
+    stride box_ld (gaps: in_fill).  geom [n][6] int32 (letterbox_window makes one record), out_hw = (OH, OW).  masks_off: leading bytes of the
+    mask buffer, so that its base is off a 4-byte boundary.  Returns, per image, the planes [min(counts[b], max_det)][OH][OW] uint8 -- or with
+    full=True the whole [n][max_det][OH][OW] buffer as read back (pre-filled with the byte out_fill)."""
+    H = _native.hip()
+    oh, ow = (int(v) for v in out_hw)
+    if isinstance(extras, DetectResult):
+        res = extras
+        max_det, extra = res.max_det, res.extra
+        dext, dcnt, cnt = res.dev["extras"], res.dev["counts"], res.counts
+        n_img = res.n
+    else:
+        res = None
+        extras, cnt = _f32(extras), np.ascontiguousarray(counts, np.int32)
+        n_img, max_det, extra = int(extras.shape[0]), int(extras.shape[1]), int(extras.shape[2])
+        dext = DeviceBuffer.from_numpy(extras if extras.size else np.zeros(4, np.float32))
+        dcnt = DeviceBuffer.from_numpy(cnt)
+    if boxes is None:
+        assert res is not None and box_ld is None, "boxes=None reads the dets rows of a DetectResult"
+        dbox, ldb = res.dev["dets"], 6
+    else:
+        boxes = _f32(boxes)
+        ldb = int(boxes.shape[2]) if box_ld is None else int(box_ld)
+        store = _full((max(n_img * max_det, 1), ldb), np.float32, in_fill)
+        store[:n_img * max_det, :boxes.shape[2]] = boxes.reshape(-1, boxes.shape[2])
+        dbox = DeviceBuffer.from_numpy(store)
+    if protos_dev is None:
+        protos = _f32(protos)
+        n, mh, mw, pnm = (int(v) for v in protos.shape)
+        ldp = pnm if proto_ld is None else int(proto_ld)
+        store = _full((protos_off + n * mh * mw * ldp,), np.float32, in_fill)
+        store[protos_off:].reshape(n * mh * mw, ldp)[:, :pnm] = protos.reshape(-1, pnm)
+        dpro = DeviceBuffer.from_numpy(store)
+    else:
+        n, mh, mw, pnm = (int(v) for v in shape)
+        ldp = pnm if proto_ld is None else int(proto_ld)
+        dpro = protos_dev
+    nm = pnm if nm is None else int(nm)
+    dgeom = DeviceBuffer.from_numpy(np.ascontiguousarray(geom, np.int32).reshape(n, 6))
+    d = image_mask_desc(n, mh, mw, nm, max_det, extra, oh, ow, coef_off, ldp, ldb, crop, force_direct)
+    plane = oh * ow
+    dmask = DeviceBuffer.from_numpy(np.full(max(masks_off + n * max_det * plane, 16), out_fill, np.uint8), out=True)
+    _chk(H.si_hip_detect_image_masks_f32(C.byref(d), dpro.ptr + 4 * protos_off, dext.ptr, dbox.ptr, dcnt.ptr, dgeom.ptr, dmask.ptr + masks_off, stream),
+         "si_hip_detect_image_masks_f32")
+    if full:
+        return dmask.to_numpy((masks_off + n * max_det * plane,), np.uint8, stream)[masks_off:].reshape(n, max_det, oh, ow)
+    kept = [min(int(cnt[b]), max_det) for b in range(n)]
+    return [DeviceBuffer.view(dmask.ptr + masks_off + b * max_det * plane, max(kept[b] * plane, 16)).to_numpy((kept[b], oh, ow), np.uint8, stream)
+            for b in range(n)]
 
 
 # ---- include/si_obb.h: oriented boxes, rotated NMS by ProbIoU ----------------------------------------------------------------------------------
