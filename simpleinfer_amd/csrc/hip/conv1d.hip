@@ -54,9 +54,6 @@ struct Conv1dArgs {
     float act_param;
 };
 
-__device__ __forceinline__ f32x4 c1_mma(float w, float b, f32x4 acc) { return __builtin_amdgcn_mfma_f32_16x16x4f32(w, b, acc, 0, 0, 0); }
-__device__ __forceinline__ f32x4 c1_mma(f16x8 w, f16x8 b, f32x4 acc) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(w, b, acc, 0, 0, 0); }
-
 template <typename T>
 __global__ __launch_bounds__(C1_THREADS) void conv1d_dense_kernel(Conv1dArgs a) {
     constexpr bool HALF = sizeof(T) == 2;
@@ -159,12 +156,12 @@ __global__ __launch_bounds__(C1_THREADS) void conv1d_dense_kernel(Conv1dArgs a) 
 #pragma unroll
                 for (int u = 0; u < U; ++u)
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) acc[j] = c1_mma(wv[u], bp[bo[u] + j * col_step], acc[j]);
+                    for (int j = 0; j < 4; ++j) acc[j] = si_mma16(wv[u], bp[bo[u] + j * col_step], acc[j]);
             }
             for (; s < total; ++s) {
                 const Frag wv = wp[s * 64];
 #pragma unroll
-                for (int j = 0; j < 4; ++j) acc[j] = c1_mma(wv, bp[boff + j * col_step], acc[j]);
+                for (int j = 0; j < 4; ++j) acc[j] = si_mma16(wv, bp[boff + j * col_step], acc[j]);
                 boff += tap_step;
                 if (++k == a.k) {
                     k = 0;

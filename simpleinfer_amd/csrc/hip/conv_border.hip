@@ -8,7 +8,8 @@
 //      patch pixels 256 / (vectors per pixel) at a time -- global -> registers -> LDS through the tables; then every tap (ky, kx) reads
 //      its B fragment (16 bytes of consecutive channels of the lane's pixel) from the patch at row w sh + ky dh, position kpos[kx] + x,
 //      and its A fragments (the same channels of filter 16 t + x) from the weight image in global memory
-//   3. epilogue in registers: bias, act1, residual, act2; a lane holds four consecutive output channels of one pixel
+//   3. epilogue in registers: bias, act1, residual, act2; a lane holds four consecutive output channels of one pixel (si_mma_dev.h's
+//      pixel-on-x tile, shared with xcorr.hip: si_pix16_filters, si_frag16, si_pix16_store)
 // With lane = 16 g + x (g = 0..3, x = 0..15): fp32 fragments hold channels 16 q + 4 g + 0..3 of block q (four 16x16x4 steps, step j
 // taking element j), fp16 fragments channels 8 g + 0..7 of the chunk (one 16x16x32 step).  One integer division per thread (its first patch
 // pixel -> row, position) and one per workgroup (tile -> tile row, tile column), none in a loop; the tables need kw + sw more.
@@ -58,9 +59,6 @@ struct BorderArgs {
     float act_param;
 };
 
-__device__ __forceinline__ f32x4 bd_mma(float w, float b, f32x4 acc) { return __builtin_amdgcn_mfma_f32_16x16x4f32(w, b, acc, 0, 0, 0); }
-__device__ __forceinline__ f32x4 bd_mma(f16x8 w, f16x8 b, f32x4 acc) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(w, b, acc, 0, 0, 0); }
-
 template <typename T, int TILES>
 __global__ __launch_bounds__(BD_THREADS) void conv_border_kernel(BorderArgs a) {
     constexpr bool HALF = sizeof(T) == 2;
@@ -106,13 +104,7 @@ __global__ __launch_bounds__(BD_THREADS) void conv_border_kernel(BorderArgs a) {
     int wo_[TILES];
     bool wl[TILES];
     f32x4 acc[TILES];
-#pragma unroll
-    for (int t = 0; t < TILES; ++t) {
-        const int o = o0 + BD_TILE_OC * t + xl;
-        wl[t] = o < a.oc;
-        wo_[t] = wl[t] ? o * taps * a.icp : 0;
-        acc[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    }
+    si_pix16_filters(o0 + xl, a.oc, taps, a.icp, wo_, wl, acc);
     const bool wave_live = wave < a.th;
 
     for (int c0 = 0; c0 < a.ic; c0 += SI_BORDER_KC) {
@@ -161,13 +153,9 @@ __global__ __launch_bounds__(BD_THREADS) void conv_border_kernel(BorderArgs a) {
                         const bool live_c = c0 + cl < a.icp;
                         f16x8 wf[TILES];
 #pragma unroll
-                        for (int t = 0; t < TILES; ++t) {
-                            const bool live = wl[t] && live_c;
-                            wf[t] = *reinterpret_cast<const f16x8*>(wb + (live ? wo_[t] + woff + cl : 0));
-                            if (!live) wf[t] = f16x8{0, 0, 0, 0, 0, 0, 0, 0};
-                        }
+                        for (int t = 0; t < TILES; ++t) wf[t] = si_frag16(wb, wo_[t] + woff + cl, wl[t] && live_c);
 #pragma unroll
-                        for (int t = 0; t < TILES; ++t) acc[t] = bd_mma(wf[t], b, acc[t]);
+                        for (int t = 0; t < TILES; ++t) acc[t] = si_mma16_block(wf[t], b, acc[t]);
                     } else {
 #pragma unroll
                         for (int q = 0; q < SI_BORDER_KC / 16; ++q) {
@@ -177,15 +165,11 @@ __global__ __launch_bounds__(BD_THREADS) void conv_border_kernel(BorderArgs a) {
                             const bool live_c = c0 + cl < a.icp;
                             f32x4 wf[TILES];
 #pragma unroll
-                            for (int t = 0; t < TILES; ++t) {
-                                const bool live = wl[t] && live_c;
-                                wf[t] = *reinterpret_cast<const f32x4*>(wb + (live ? wo_[t] + woff + cl : 0));
-                                if (!live) wf[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-                            }
+                            for (int t = 0; t < TILES; ++t) wf[t] = si_frag16(wb, wo_[t] + woff + cl, wl[t] && live_c);
 #pragma unroll
-                            for (int t = 0; t < TILES; ++t)
+                            for (int t = 0; t < TILES; ++t)   // (si_mma16_block, written out: through the helper <float, 4> takes 4 more AGPRs and loses a wave)
 #pragma unroll
-                                for (int j = 0; j < 4; ++j) acc[t] = bd_mma(wf[t][j], b[j], acc[t]);
+                                for (int j = 0; j < 4; ++j) acc[t] = si_mma16(wf[t][j], b[j], acc[t]);
                         }
                     }
                 }
@@ -193,34 +177,13 @@ __global__ __launch_bounds__(BD_THREADS) void conv_border_kernel(BorderArgs a) {
         }
     }
 
-    // ---- 3. epilogue: register r of accumulator t is filter o0 + 16 t + 4 g + r at this lane's pixel
+    // ---- 3. epilogue (si_pix16_store): register r of accumulator t is filter o0 + 16 t + 4 g + r at this lane's pixel
     const int oy = oy0 + wave, ox = ox0 + xl;
     if (!wave_live || oy >= a.oh || ox >= a.ow) return;
     const int pix = oy * a.ow + ox;
     T* const yp = static_cast<T*>(a.y) + n * a.y_sn + pix * a.out_ld;
     const T* const rp = a.res ? static_cast<const T*>(a.res) + n * a.r_sn + pix * a.res_ld : nullptr;
-#pragma unroll
-    for (int t = 0; t < TILES; ++t) {
-        const int ob = o0 + BD_TILE_OC * t + 4 * g;
-        if (ob >= a.oc) continue;
-        T out[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const bool lo = ob + r < a.oc;
-            const float bv = (a.bias && lo) ? a.bias[ob + r] : 0.0f;
-            float val = si_act(a.act1, acc[t][r] + bv, a.act_param);
-            if (rp) val = val + (lo ? (float)rp[ob + r] : 0.0f);
-            out[r] = si_store_cast<T>(si_act(a.act2, val, a.act_param));
-        }
-        if (a.y_vec && ob + 3 < a.oc) {
-            typedef T V4 __attribute__((ext_vector_type(4)));
-            *reinterpret_cast<V4*>(yp + ob) = V4{out[0], out[1], out[2], out[3]};
-        } else {
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                if (ob + r < a.oc) yp[ob + r] = out[r];
-        }
-    }
+    si_pix16_store<T, TILES, true>(yp, rp, a.bias, acc, o0 + 4 * g, a.oc, a.y_vec != 0, a.act1, a.act2, a.act_param);
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------

@@ -19,11 +19,8 @@
 // Weights: [kh][kw][oc][icp] (icp = Cin rounded up to 4, zero filled), re-laid once on the host; for the one-tap path
 // that is exactly the [sh*sw*Cout][icp] B matrix.
 //
-// Tile: 64 x 64 per workgroup, four waves as 2 x 2, one 32x32 accumulator per wave, one LDS stage ([row][32 + 4]: 18 KB,
-// so many workgroups share a CU) with the next K-tile's global loads in flight during the MFMAs -- the form
-// conv_igemm.hip measured fastest for the fp32 MFMA (its 64x64 one-stage tiles).  Fragment reads: one ds_read_b128 per
-// lane of A[row][16p + 8h + 4(lane>>5) .. +3]; MFMA j of that group takes element j from A and B alike (a K permutation
-// inside the tile, the same products).
+// Tile, lane maps and epilogue: the 64 x 64 x 32 fp32 GEMM core of si_mma_dev.h (si_g64_*); the K loop around the loader is written out here.  This file produces its operands: the A vectors
+// of a phase's (pixel, tap, channels) with zeros outside the image, the B rows of the weight image, and the pixel of each tile row.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -35,8 +32,6 @@
 #include "si_hip_internal.h"
 
 namespace {
-
-constexpr int CT_BM = 64, CT_BN = 64, CT_BK = 32, CT_LDL = CT_BK + 4;
 
 struct CtArgs {
     const float* in;
@@ -53,33 +48,13 @@ struct CtArgs {
     float act_param;
 };
 
-// C/D map of the 32x32 tile: col = lane & 31 (GEMM column), row = Mma<32>::row(e) + 4 * (lane >> 5).
-// rows[]: the output pixel of each of the workgroup's 64 rows (-1 past M); col_pix: the pixel offset of this lane's
-// column (the one-tap path's ky * ow + kx, else 0); o: its output channel.
-template <int ACT>
-__device__ __forceinline__ void ct_store(const CtArgs& a, const f32x16& acc, const int* rows, int row0, bool live, int o, int col_pix) {
-    if (!live) return;
-    const float bv = a.bias ? a.bias[o] : 0.0f;
-    float* const ob = a.out + o;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-        const int pix = rows[row0 + Mma<32>::row(e)];
-        if (pix >= 0) ob[(size_t)(pix + col_pix) * a.out_ld] = si_act<ACT>(acc[e] + bv, a.act_param);
-    }
-}
-
 template <bool ONE_TAP, bool VEC_A>
 __global__ __launch_bounds__(256) void conv_transpose_f32_kernel(const CtArgs a) {
-    __shared__ __attribute__((aligned(16))) float lds[(CT_BM + CT_BN) * CT_LDL];
-    __shared__ int rows[CT_BM];
+    __shared__ __attribute__((aligned(16))) float lds[SI_G64_LDS_FLOATS];
+    __shared__ int rows[SI_G64_BM];   // the output pixel of each of the workgroup's 64 rows (-1 past M)
 
-    // tile mapping as conv_igemm.hip: the n_tiles workgroups that share one A panel get the same blockIdx % 8 (same XCD / L2)
-    const int per_chunk = 8 * a.n_tiles;
-    const int chunk = (int)blockIdx.x / per_chunk;
-    const int r = (int)blockIdx.x - chunk * per_chunk;
-    const int m_tile = chunk * 8 + (r & 7);
-    const int n_tile = r >> 3;
-    if (m_tile >= a.m_tiles) return;
+    const SiG64Tile tile = si_g64_tile(a.m_tiles, a.n_tiles);
+    if (tile.none) return;
 
     // ---- this workgroup's phase (wave-uniform scalar arithmetic)
     const int phase = blockIdx.z;
@@ -115,17 +90,17 @@ __global__ __launch_bounds__(256) void conv_transpose_f32_kernel(const CtArgs a)
         }
     }
     const int M = a.n * prow * pcol;
-    const int m0 = m_tile * CT_BM;
+    const int m0 = tile.m_tile * SI_G64_BM;
     if (m0 >= M) return;
-    const int n0 = n_tile * CT_BN;
+    const int n0 = tile.n_tile * SI_G64_BN;
     const int K = nty * ntx * a.icp;
 
     const int tid = threadIdx.x;
-    const int kv = tid & 7;   // 4-wide K vector of the 32-wide K-tile
-    const int r0 = tid >> 3;  // base row 0..31
+    const SiG64Stage st = si_g64_stage(tid);
+    const int kv = st.kv, r0 = st.r0;
 
     // ---- output pixel of each tile row
-    if (tid < CT_BM) {
+    if (tid < SI_G64_BM) {
         const int m = m0 + tid;
         int pix = -1;
         if (m < M) {
@@ -155,7 +130,7 @@ __global__ __launch_bounds__(256) void conv_transpose_f32_kernel(const CtArgs a)
 
     f32x4 pa[2], pb[2];
     auto load_tile = [&](int kt) {
-        const int k = kt * CT_BK + kv * 4;
+        const int k = kt * SI_G64_BK + kv * 4;
         const bool kvalid = k < K;
         int t = 0, c = k;
         if (!ONE_TAP) {
@@ -193,45 +168,28 @@ __global__ __launch_bounds__(256) void conv_transpose_f32_kernel(const CtArgs a)
         }
     };
 
-    const int wave = tid >> 6, lane = tid & 63;
-    const int wm = wave >> 1, wn = wave & 1;
-    const int l31 = lane & 31, lh = lane >> 5;
-
+    const SiG64Lane ln = si_g64_lane(tid);
     f32x16 acc;
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc[e] = 0.0f;
 
-    const int nk = (K + CT_BK - 1) / CT_BK;
+    const int nk = (K + SI_G64_BK - 1) / SI_G64_BK;
     if (nk > 0) load_tile(0);
     for (int kt = 0; kt < nk; ++kt) {
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
-            *reinterpret_cast<f32x4*>(lds + (r0 + 32 * q) * CT_LDL + kv * 4) = pa[q];
-            *reinterpret_cast<f32x4*>(lds + (CT_BM + r0 + 32 * q) * CT_LDL + kv * 4) = pb[q];
+            *reinterpret_cast<f32x4*>(lds + (r0 + 32 * q) * SI_G64_LDL + kv * 4) = pa[q];
+            *reinterpret_cast<f32x4*>(lds + (SI_G64_BM + r0 + 32 * q) * SI_G64_LDL + kv * 4) = pb[q];
         }
         __syncthreads();
         if (kt + 1 < nk) load_tile(kt + 1);   // in flight during the MFMAs
-        const float* As = lds + (wm * 32 + l31) * CT_LDL + lh * 4;
-        const float* Bs = lds + (CT_BM + wn * 32 + l31) * CT_LDL + lh * 4;
-#pragma unroll
-        for (int p = 0; p < CT_BK / 16; ++p) {
-            f32x4 fa[2], fb[2];
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                fa[h] = *reinterpret_cast<const f32x4*>(As + p * 16 + h * 8);
-                fb[h] = *reinterpret_cast<const f32x4*>(Bs + p * 16 + h * 8);
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int h = 0; h < 2; ++h) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[h][j], fb[h][j], acc, 0, 0, 0);
-        }
+        si_g64_mma(lds, ln, acc);
         __syncthreads();
     }
     if (nk == 0) __syncthreads();   // (rows[] is read below)
 
-    // ---- epilogue
-    const int col = n0 + wn * 32 + l31;
+    // ---- epilogue: the one-tap path's column j = (tap, oc) goes to pixel offset ky * ow + kx
+    const int col = ln.col(n0);
     const bool live = col < a.ncols;
     int o = col, col_pix = 0;
     if (ONE_TAP && live) {
@@ -240,16 +198,7 @@ __global__ __launch_bounds__(256) void conv_transpose_f32_kernel(const CtArgs a)
         const int ky = tap / a.sw;
         col_pix = ky * a.ow + (tap - ky * a.sw);
     }
-    const int row0 = wm * 32 + 4 * lh;
-    switch (a.act) {
-        case SI_ACT_RELU: ct_store<SI_ACT_RELU>(a, acc, rows, row0, live, o, col_pix); break;
-        case SI_ACT_SILU: ct_store<SI_ACT_SILU>(a, acc, rows, row0, live, o, col_pix); break;
-        case SI_ACT_SIGMOID: ct_store<SI_ACT_SIGMOID>(a, acc, rows, row0, live, o, col_pix); break;
-        case SI_ACT_HARDSIGMOID: ct_store<SI_ACT_HARDSIGMOID>(a, acc, rows, row0, live, o, col_pix); break;
-        case SI_ACT_HARDSWISH: ct_store<SI_ACT_HARDSWISH>(a, acc, rows, row0, live, o, col_pix); break;
-        case SI_ACT_LEAKYRELU: ct_store<SI_ACT_LEAKYRELU>(a, acc, rows, row0, live, o, col_pix); break;
-        default: ct_store<SI_ACT_NONE>(a, acc, rows, row0, live, o, col_pix); break;
-    }
+    si_g64_epilogue(a, acc, rows, ln.row0(), live, o, col_pix);
 }
 
 int ct_gcd(int x, int y) {
@@ -261,7 +210,7 @@ int ct_gcd(int x, int y) {
     return x;
 }
 
-int ct_icp(const SiConvTranspose2dDesc* d) { return (d->ic + 3) & ~3; }
+int ct_icp(const SiConvTranspose2dDesc* d) { return si_g64_pitch(d->ic); }
 
 bool ct_one_tap(const SiConvTranspose2dDesc* d) {
     return d->kh == d->sh && d->kw == d->sw && d->ph == 0 && d->pw == 0 && d->dh == 1 && d->dw == 1 && d->oph == 0 && d->opw == 0;
@@ -340,10 +289,10 @@ extern "C" int si_hip_conv_transpose2d_f32(const SiConvTranspose2dDesc* d, const
         mmax = (long long)d->n * ((d->oh + d->sh - 1) / d->sh) * ((d->ow + d->sw - 1) / d->sw);
         phases = d->sh * d->sw;
     }
-    a.m_tiles = (int)((mmax + CT_BM - 1) / CT_BM);
-    a.n_tiles = (a.ncols + CT_BN - 1) / CT_BN;
-    const long long gx_blocks = (long long)((a.m_tiles + 7) / 8) * 8 * a.n_tiles;
-    if (gx_blocks >= (1LL << 31) || phases > 65535) return SI_E_UNSUPPORTED;
+    a.m_tiles = (int)si_g64_tiles(mmax);
+    a.n_tiles = (int)si_g64_tiles(a.ncols);
+    const long long gx_blocks = si_g64_grid_x(a.m_tiles, a.n_tiles);
+    if (gx_blocks == 0 || phases > 65535) return SI_E_UNSUPPORTED;
     const bool vec = d->ic % 4 == 0 && d->in_ld % 4 == 0 && si_aligned_to(in, 16);
     const dim3 grid((unsigned)gx_blocks, 1, (unsigned)phases);
     hipStream_t s = (hipStream_t)stream;

@@ -2,16 +2,17 @@
 // (v_mfma_f32_32x32x2_f32: exact fp32, k-ordered fma chain, as conv_igemm.hip and conv_transpose.hip).
 //
 // An implicit GEMM per weight group: M = n * oh * ow output pixels, N = oc / groups, K = kh * kw * cgp (tap-major, the channels of the weight
-// group inside, cgp = ic / groups rounded up to 4 and zero filled in the weight image).  The B operand is conv_transpose.hip's: rows of the
-// packed weight [tap][oc][cgp].  The A operand is produced by the gather: for a tile row (an output pixel), a tap and an offset group the
+// group inside, cgp = ic / groups rounded up to 4 and zero filled in the weight image).  The B operand: rows of the packed weight
+// [tap][oc][cgp].  The A operand is produced by the gather: for a tile row (an output pixel), a tap and an offset group the
 // two offsets and the mask give a sampling record -- four corner element offsets (or "absent") and four weights -- and every 4-channel
 // vector of that (row, tap) is four corner loads, the blend in the order of the rule, the mask multiply, and a 16-byte LDS store.  The eight
 // threads that share a row each make the record from the offsets (which sit in L1 after the first of them) and keep it in registers for the
 // K-tiles of that tap; nothing is staged in LDS.
 //
-// Tile: conv_transpose.hip's -- 64 x 64 per workgroup, four waves as 2 x 2, one 32x32 accumulator per wave, one LDS stage ([row][32 + 4]),
-// the next K-tile's gather in flight during the MFMAs, the same XCD-aware tile mapping; the weight group is blockIdx.z.  Output-stationary:
-// exactly one lane computes and stores each output element, once -- no workspace, no atomics, the same bits from run to run.
+// Tile, lane maps and epilogue: the 64 x 64 x 32 fp32 GEMM core of si_mma_dev.h (si_g64_*); the K loop around the loader is written out here,
+// the next K-tile's gather in flight during the MFMAs;
+// the weight group is blockIdx.z.  Output-stationary: exactly one lane computes and stores each output element, once -- no workspace, no
+// atomics, the same bits from run to run.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -23,8 +24,6 @@
 #include "si_hip_internal.h"
 
 namespace {
-
-constexpr int DC_BM = 64, DC_BN = 64, DC_BK = 32, DC_LDL = DC_BK + 4;
 
 struct DcArgs {
     const float* in;
@@ -41,20 +40,6 @@ struct DcArgs {
     int act;
     float act_param;
 };
-
-// C/D map of the 32x32 tile: col = lane & 31 (GEMM column), row = Mma<32>::row(e) + 4 * (lane >> 5).
-// rows[]: the output pixel of each of the workgroup's 64 rows (-1 past M); o: this lane's output channel.
-template <int ACT>
-__device__ __forceinline__ void dc_store(const DcArgs& a, const f32x16& acc, const int* rows, int row0, bool live, int o) {
-    if (!live) return;
-    const float bv = a.bias ? a.bias[o] : 0.0f;
-    float* const ob = a.out + o;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-        const int pix = rows[row0 + Mma<32>::row(e)];
-        if (pix >= 0) ob[(size_t)pix * a.out_ld] = si_act<ACT>(acc[e] + bv, a.act_param);
-    }
-}
 
 // The sampling record of one (output pixel, tap, offset group).  kind: 0 the sample is 0, 1 the blend, 2 NaN.  o0 .. o3: the element offset of
 // each corner's pixel (channel 0), -1 for a corner outside the image; w0 .. w3: the corner weights; m: the mask value (1 without a mask).
@@ -129,30 +114,25 @@ __device__ __forceinline__ f32x4 dc_sample4(const DcArgs& a, const DcRecord& r, 
 
 template <bool VEC_A>
 __global__ __launch_bounds__(256) void deform_conv_f32_kernel(const DcArgs a) {
-    __shared__ __attribute__((aligned(16))) float lds[(DC_BM + DC_BN) * DC_LDL];
-    __shared__ int rows[DC_BM];
+    __shared__ __attribute__((aligned(16))) float lds[SI_G64_LDS_FLOATS];
+    __shared__ int rows[SI_G64_BM];   // the output pixel of each of the workgroup's 64 rows (-1 past M)
 
-    // tile mapping as conv_igemm.hip: the n_tiles workgroups that share one A panel get the same blockIdx % 8 (same XCD / L2)
-    const int per_chunk = 8 * a.n_tiles;
-    const int chunk = (int)blockIdx.x / per_chunk;
-    const int r = (int)blockIdx.x - chunk * per_chunk;
-    const int m_tile = chunk * 8 + (r & 7);
-    const int n_tile = r >> 3;
-    if (m_tile >= a.m_tiles) return;
+    const SiG64Tile tile = si_g64_tile(a.m_tiles, a.n_tiles);
+    if (tile.none) return;
 
     const int g = blockIdx.z;   // weight group
     const int opix = a.oh * a.ow;
     const int M = a.n * opix;
-    const int m0 = m_tile * DC_BM;
-    const int n0 = n_tile * DC_BN;
+    const int m0 = tile.m_tile * SI_G64_BM;
+    const int n0 = tile.n_tile * SI_G64_BN;
     const int taps = a.kh * a.kw;
     const int K = taps * a.cgp;
 
     const int tid = threadIdx.x;
-    const int kv = tid & 7;   // 4-wide K vector of the 32-wide K-tile
-    const int r0 = tid >> 3;  // base row 0..31
+    const SiG64Stage st = si_g64_stage(tid);
+    const int kv = st.kv, r0 = st.r0;
 
-    if (tid < DC_BM) rows[tid] = m0 + tid < M ? m0 + tid : -1;
+    if (tid < SI_G64_BM) rows[tid] = m0 + tid < M ? m0 + tid : -1;
 
     // ---- per-thread A rows (fixed for the whole K loop)
     int a_pix[2], a_img[2], a_by[2], a_bx[2];
@@ -177,7 +157,7 @@ __global__ __launch_bounds__(256) void deform_conv_f32_kernel(const DcArgs a) {
     int rec_ch = -1;
     f32x4 pa[2], pb[2];
     auto load_tile = [&](int kt) {
-        const int k = kt * DC_BK + kv * 4;
+        const int k = kt * SI_G64_BK + kv * 4;
         const bool kvalid = k < K;
         const int t = kvalid ? k / a.cgp : 0;
         const int c = k - t * a.cgp;      // channel inside the weight group
@@ -226,59 +206,33 @@ __global__ __launch_bounds__(256) void deform_conv_f32_kernel(const DcArgs a) {
         }
     };
 
-    const int wave = tid >> 6, lane = tid & 63;
-    const int wm = wave >> 1, wn = wave & 1;
-    const int l31 = lane & 31, lh = lane >> 5;
-
+    // the loader is called once per K-tile in ascending order, which the records above rely on
+    const SiG64Lane ln = si_g64_lane(tid);
     f32x16 acc;
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc[e] = 0.0f;
 
-    const int nk = (K + DC_BK - 1) / DC_BK;
+    const int nk = (K + SI_G64_BK - 1) / SI_G64_BK;
     load_tile(0);   // (K >= 4: nk >= 1)
     for (int kt = 0; kt < nk; ++kt) {
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
-            *reinterpret_cast<f32x4*>(lds + (r0 + 32 * q) * DC_LDL + kv * 4) = pa[q];
-            *reinterpret_cast<f32x4*>(lds + (DC_BM + r0 + 32 * q) * DC_LDL + kv * 4) = pb[q];
+            *reinterpret_cast<f32x4*>(lds + (r0 + 32 * q) * SI_G64_LDL + kv * 4) = pa[q];
+            *reinterpret_cast<f32x4*>(lds + (SI_G64_BM + r0 + 32 * q) * SI_G64_LDL + kv * 4) = pb[q];
         }
         __syncthreads();
         if (kt + 1 < nk) load_tile(kt + 1);   // in flight during the MFMAs
-        const float* As = lds + (wm * 32 + l31) * DC_LDL + lh * 4;
-        const float* Bs = lds + (DC_BM + wn * 32 + l31) * DC_LDL + lh * 4;
-#pragma unroll
-        for (int p = 0; p < DC_BK / 16; ++p) {
-            f32x4 fa[2], fb[2];
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                fa[h] = *reinterpret_cast<const f32x4*>(As + p * 16 + h * 8);
-                fb[h] = *reinterpret_cast<const f32x4*>(Bs + p * 16 + h * 8);
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int h = 0; h < 2; ++h) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[h][j], fb[h][j], acc, 0, 0, 0);
-        }
+        si_g64_mma(lds, ln, acc);
         __syncthreads();
     }
 
+
     // ---- epilogue
-    const int col = n0 + wn * 32 + l31;
-    const bool live = col < a.cog;
-    const int o = g * a.cog + col;
-    const int row0 = wm * 32 + 4 * lh;
-    switch (a.act) {
-        case SI_ACT_RELU: dc_store<SI_ACT_RELU>(a, acc, rows, row0, live, o); break;
-        case SI_ACT_SILU: dc_store<SI_ACT_SILU>(a, acc, rows, row0, live, o); break;
-        case SI_ACT_SIGMOID: dc_store<SI_ACT_SIGMOID>(a, acc, rows, row0, live, o); break;
-        case SI_ACT_HARDSIGMOID: dc_store<SI_ACT_HARDSIGMOID>(a, acc, rows, row0, live, o); break;
-        case SI_ACT_HARDSWISH: dc_store<SI_ACT_HARDSWISH>(a, acc, rows, row0, live, o); break;
-        case SI_ACT_LEAKYRELU: dc_store<SI_ACT_LEAKYRELU>(a, acc, rows, row0, live, o); break;
-        default: dc_store<SI_ACT_NONE>(a, acc, rows, row0, live, o); break;
-    }
+    const int col = ln.col(n0);
+    si_g64_epilogue(a, acc, rows, ln.row0(), col < a.cog, g * a.cog + col, 0);
 }
 
-int dc_cgp(const SiDeformConv2dDesc* d) { return (d->ic / d->groups + 3) & ~3; }
+int dc_cgp(const SiDeformConv2dDesc* d) { return si_g64_pitch(d->ic / d->groups); }
 
 // what the weight functions need of the descriptor
 bool dc_weight_ok(const SiDeformConv2dDesc* d) {
@@ -306,8 +260,7 @@ int dc_check(const SiDeformConv2dDesc* d) {
         (d->has_mask && opix * d->mask_ld > (long long)SI_INDEX_LIMIT))
         return SI_E_UNSUPPORTED;
     if (taps * d->oc * dc_cgp(d) > (long long)SI_INDEX_LIMIT) return SI_E_UNSUPPORTED;
-    const long long m_tiles = (opix + DC_BM - 1) / DC_BM, n_tiles = (d->oc / d->groups + DC_BN - 1) / DC_BN;
-    if ((m_tiles + 7) / 8 * 8 * n_tiles > (long long)SI_INDEX_LIMIT || d->groups > 65535) return SI_E_UNSUPPORTED;
+    if (si_g64_grid_x(si_g64_tiles(opix), si_g64_tiles(d->oc / d->groups)) == 0 || d->groups > 65535) return SI_E_UNSUPPORTED;
     return 0;
 }
 
@@ -369,11 +322,9 @@ extern "C" int si_hip_deform_conv2d_f32(const SiDeformConv2dDesc* d, const float
     a.kh = d->kh; a.kw = d->kw; a.sh = d->sh; a.sw = d->sw; a.ph = d->ph; a.pw = d->pw; a.dh = d->dh; a.dw = d->dw;
     a.cg = d->ic / d->groups; a.cgp = dc_cgp(d); a.cog = d->oc / d->groups; a.cpo = d->ic / d->offset_groups;
     a.act = d->act; a.act_param = d->act_param;
-    const long long opix = (long long)d->n * d->oh * d->ow;
-    a.m_tiles = (int)((opix + DC_BM - 1) / DC_BM);
-    a.n_tiles = (a.cog + DC_BN - 1) / DC_BN;
-    const long long gx_blocks = (long long)((a.m_tiles + 7) / 8) * 8 * a.n_tiles;
-    const dim3 grid((unsigned)gx_blocks, 1, (unsigned)d->groups);
+    a.m_tiles = (int)si_g64_tiles((long long)d->n * d->oh * d->ow);
+    a.n_tiles = (int)si_g64_tiles(a.cog);
+    const dim3 grid((unsigned)si_g64_grid_x(a.m_tiles, a.n_tiles), 1, (unsigned)d->groups);   // (dc_check: it fits)
     hipStream_t s = (hipStream_t)stream;
     if (dc_vec(d, x)) hipLaunchKernelGGL((deform_conv_f32_kernel<true>), grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL((deform_conv_f32_kernel<false>), grid, dim3(256), 0, s, a);

@@ -61,9 +61,6 @@ __device__ __forceinline__ void load4(const T* p, int u, int h, float (&v)[4]) {
     }
 }
 
-__device__ __forceinline__ f32x4 rnn_mma(float w, float h, f32x4 acc) { return __builtin_amdgcn_mfma_f32_16x16x4f32(w, h, acc, 0, 0, 0); }
-__device__ __forceinline__ f32x4 rnn_mma(f16x8 w, f16x8 h, f32x4 acc) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(w, h, acc, 0, 0, 0); }
-
 template <typename T>
 __device__ __forceinline__ void store4(T* p, int u, int h, const float (&v)[4]) {
     if constexpr (sizeof(T) == 2) {
@@ -173,12 +170,12 @@ __global__ __launch_bounds__(RNN_THREADS) void rnn_step_kernel(RnnArgs a) {
 #pragma unroll
                 for (int j = 0; j < U; ++j)
 #pragma unroll
-                    for (int q = 0; q < G; ++q) acc[q] = rnn_mma(wv[j][q], hb[j], acc[q]);
+                    for (int q = 0; q < G; ++q) acc[q] = si_mma16(wv[j][q], hb[j], acc[q]);
             }
             for (; s < ks; ++s, wp += G * 64) {
                 const Frag hb = img[4 * s * PITCH];
 #pragma unroll
-                for (int q = 0; q < G; ++q) acc[q] = rnn_mma(wp[q * 64], hb, acc[q]);
+                for (int q = 0; q < G; ++q) acc[q] = si_mma16(wp[q * 64], hb, acc[q]);
             }
         }
     }

@@ -349,6 +349,9 @@ __device__ __forceinline__ void si_yolo_tile_one_image(const Args& a, float* out
 #include "si_reduce_dev.h"
 static_assert(SI_PLAN_BADARG == SI_E_BADARG && SI_PLAN_UNSUPPORTED == SI_E_UNSUPPORTED, "si_reduce_plan.h returns the C-ABI's codes");
 
+// ---- matrix-core operators: the 16x16 MFMA steps, the 64 x 64 fp32 GEMM core and the pixel-on-x 16-filter tile
+#include "si_mma_dev.h"
+
 // ---- diagnostic build only (-DSI_DIAG_STAMPS; tools/conv_diag.py): per-workgroup s_memtime / s_memrealtime stamps at the phase
 // boundaries of a kernel, written to a __device__ array of their own that nothing else reads.  In the product build no stamp
 // executes and every macro expands to nothing.  Slots: [0] realtime at start, [1..5] cycle stamps, [6] realtime at end, [7] hw id.

@@ -9,7 +9,8 @@
 //        forward, so there is no image to pack it into
 //     B  the input: lane holds x[n][oy sh - pt + ky dh][ox sw - pl + kx dw][the same channels] of ITS pixel, a real zero when the tap lies
 //        outside the image (never read)
-// The C/D map puts the PIXEL on x and filter 4 g + r in register r: a lane stores four consecutive channels of one NHWC pixel at once.
+// The C/D map puts the PIXEL on x and filter 4 g + r in register r: a lane stores four consecutive channels of one NHWC pixel at once
+// (the steps, the per-lane filter setup, the 16-byte fragment and the epilogue of this tile: si_mma_dev.h, shared with conv_border.hip).
 // A fragment is one 16-byte read where the view is aligned; the element path loads the same elements one by one, in the same order.
 //
 // Depthwise.  One item = 16 bytes of consecutive channels of one output pixel; a lane walks the taps in ascending (ky, kx) order with one
@@ -34,7 +35,7 @@ namespace {
 namespace plan = si_xcorr_plan;
 
 constexpr int XC_THREADS = plan::kThreads;
-static_assert(plan::kBlockPix == plan::kWavePix * (XC_THREADS / 64), "a wave owns 16 output pixels");
+static_assert(plan::kBlockPix == plan::kWavePix * (XC_THREADS / 64) && plan::kTileOc == 16, "a wave owns 16 output pixels; si_pix16_*'s tile");
 
 struct XcorrArgs {
     const void* x;
@@ -49,48 +50,28 @@ struct XcorrArgs {
     float act_param;
 };
 
-__device__ __forceinline__ f32x4 xc_mma(float w, float b, f32x4 acc) { return __builtin_amdgcn_mfma_f32_16x16x4f32(w, b, acc, 0, 0, 0); }
-__device__ __forceinline__ f32x4 xc_mma(f16x8 w, f16x8 b, f32x4 acc) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(w, b, acc, 0, 0, 0); }
-
-// A lane's fragment of one channel block: CH_LANE consecutive channels starting at `c`, 16 bytes of the storage type.  The load itself is
-// unconditional -- a fragment that is not live reads element 0 of its view, which always exists, and is then replaced by zeros -- so that the
-// loads of several blocks can be in flight before the first MFMA needs one; what lies outside the image or beyond the channels is never read.
+// A lane's fragment of one channel block: CH_LANE consecutive channels starting at `c`, 16 bytes of the storage type, loaded unconditionally and
+// zeroed where not live (si_frag16): what lies outside the image or beyond the channels is never read.
 // `vec`: one 16-byte read; else the same elements one by one (any alignment, any channel stride, a ragged last block).
 __device__ __forceinline__ f32x4 xc_frag(const float* p, int off, int c, int sc, int cmax, bool live, bool vec) {
+    if (vec) return si_frag16(p, off + c, live);
     f32x4 v;
-    if (vec) {
-        v = *reinterpret_cast<const f32x4*>(p + (live ? off + c : 0));
-        if (!live) v = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    } else {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const bool lj = live && c + j < cmax;
-            const float e = p[lj ? off + (c + j) * sc : 0];
-            v[j] = lj ? e : 0.0f;
-        }
+    for (int j = 0; j < 4; ++j) {
+        const bool lj = live && c + j < cmax;
+        const float e = p[lj ? off + (c + j) * sc : 0];
+        v[j] = lj ? e : 0.0f;
     }
     return v;
 }
 __device__ __forceinline__ f16x8 xc_frag(const _Float16* p, int off, int c, int sc, int /*cmax*/, bool live, bool vec) {
+    if (vec) return si_frag16(p, off + c, live);
     f16x8 v;
-    if (vec) {
-        v = *reinterpret_cast<const f16x8*>(p + (live ? off + c : 0));
-    } else {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = p[live ? off + (c + j) * sc : 0];   // (c % 8 == 0: the 8 channels are in or out together)
-    }
+    for (int j = 0; j < 8; ++j) v[j] = p[live ? off + (c + j) * sc : 0];   // (c % 8 == 0: the 8 channels are in or out together)
     if (!live) v = f16x8{0, 0, 0, 0, 0, 0, 0, 0};
     return v;
 }
-
-// one channel block into an accumulator: fp16 is ONE 16x16x32 step; fp32 four 16x16x4 steps, step j holding element j of every lane's
-// fragment -- channels 4 g + j, g = 0..3, of the block of 16
-__device__ __forceinline__ f32x4 xc_block(f32x4 w, f32x4 b, f32x4 acc) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc = xc_mma(w[j], b[j], acc);
-    return acc;
-}
-__device__ __forceinline__ f32x4 xc_block(f16x8 w, f16x8 b, f32x4 acc) { return xc_mma(w, b, acc); }
 
 // VEC: x and w are both read in 16-byte fragments; TILES: the filter tiles a wave keeps accumulators for (the host asks for no more than the
 // filters need: O = 1 .. 16 is one tile).  Both are compile-time so that the block loop is straight-line code.
@@ -112,16 +93,10 @@ __global__ __launch_bounds__(XC_THREADS) void xcorr_dense_kernel(XcorrArgs a) {
 
     const T* const xn = static_cast<const T*>(a.x) + n * a.x_sn;
     const T* const wb = static_cast<const T*>(a.w);
-    int wo_[TILES];   // this lane's filter of tile t: its element offset, 0 (never dereferenced as live) beyond the filters
+    int wo_[TILES];   // this lane's filter of tile t: its element offset
     bool wl[TILES];
     f32x4 acc[TILES];
-#pragma unroll
-    for (int t = 0; t < TILES; ++t) {
-        const int o = o0 + plan::kTileOc * t + xl;
-        wl[t] = o < a.oc;
-        wo_[t] = wl[t] ? o * a.w_sn : 0;
-        acc[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    }
+    si_pix16_filters(o0 + xl, a.oc, 1, a.w_sn, wo_, wl, acc);
 
     const int iy0 = oy * a.sh - a.pt, ix0 = ox * a.sw - a.pl;
     const int blocks = (a.c + CH_BLOCK - 1) / CH_BLOCK;
@@ -149,7 +124,7 @@ __global__ __launch_bounds__(XC_THREADS) void xcorr_dense_kernel(XcorrArgs a) {
 #pragma unroll
                 for (int u = 0; u < 2; ++u)
 #pragma unroll
-                    for (int t = 0; t < TILES; ++t) acc[t] = xc_block(wfr[u][t], b[u], acc[t]);
+                    for (int t = 0; t < TILES; ++t) acc[t] = si_mma16_block(wfr[u][t], b[u], acc[t]);
             }
             if (q < blocks) {
                 const int c = CH_BLOCK * q + cl0;
@@ -159,7 +134,7 @@ __global__ __launch_bounds__(XC_THREADS) void xcorr_dense_kernel(XcorrArgs a) {
 #pragma unroll
                 for (int t = 0; t < TILES; ++t) wfr[t] = xc_frag(wb, wo_[t] + woff, c, a.w_sc, a.c, wl[t] && cl, VEC);
 #pragma unroll
-                for (int t = 0; t < TILES; ++t) acc[t] = xc_block(wfr[t], b, acc[t]);
+                for (int t = 0; t < TILES; ++t) acc[t] = si_mma16_block(wfr[t], b, acc[t]);
             }
         }
     }
@@ -167,25 +142,7 @@ __global__ __launch_bounds__(XC_THREADS) void xcorr_dense_kernel(XcorrArgs a) {
     // epilogue: register r of accumulator t is filter o0 + 16 t + 4 g + r at this lane's pixel
     if (!pix_live) return;
     T* const yp = static_cast<T*>(a.y) + n * a.y_sn + oy * a.y_sh + ox * a.y_sp;
-#pragma unroll
-    for (int t = 0; t < TILES; ++t) {
-        const int ob = o0 + plan::kTileOc * t + 4 * g;
-        if (ob >= a.oc) continue;
-        T out[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float bv = (a.bias && ob + r < a.oc) ? a.bias[ob + r] : 0.0f;
-            out[r] = si_store_cast<T>(si_act(a.act, acc[t][r] + bv, a.act_param));
-        }
-        if (a.y_vec && ob + 3 < a.oc) {
-            typedef T V4 __attribute__((ext_vector_type(4)));
-            *reinterpret_cast<V4*>(yp + ob) = V4{out[0], out[1], out[2], out[3]};
-        } else {
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                if (ob + r < a.oc) yp[ob + r] = out[r];
-        }
-    }
+    si_pix16_store<T, TILES, false>(yp, nullptr, a.bias, acc, o0 + 4 * g, a.oc, a.y_vec != 0, a.act, SI_ACT_NONE, a.act_param);
 }
 
 template <typename T>
