@@ -112,6 +112,11 @@ class SiLayerNormDesc(C.Structure):
     _fields_ = [(k, C.c_int) for k in ("rows", "c", "in_ld", "out_ld")] + [("eps", C.c_float)]
 
 
+class SiCdistDesc(C.Structure):
+    """include/si_cdist.h: x1 [b1, p, m], x2 [b2, r, m], out [max(b1, b2), p, r]; row and batch strides in elements"""
+    _fields_ = [(k, C.c_int) for k in ("b1", "b2", "p", "r", "m", "x1_ld", "x2_ld", "out_ld", "x1_sb", "x2_sb", "out_sb", "norm", "mode")]
+
+
 class SiPixelShuffleDesc(C.Structure):
     """include/si_superres.h"""
     _fields_ = [(k, C.c_int) for k in ("n", "ih", "iw", "ic", "in_ld", "oh", "ow", "oc", "out_ld", "r", "inverse")]
@@ -556,7 +561,13 @@ def hip():
         "si_hip_detect_image_masks_f32": (i, [C.POINTER(SiImageMaskDesc), vp, vp, vp, vp, vp, vp, vp]),
         "si_hip_detect_image_masks_kernel_name": (C.c_char_p, [C.POINTER(SiImageMaskDesc), vp, vp]),
     }
-    for name, (res, args) in (list(imgmask_.items()) + list(obb_.items()) + list(border_.items()) + list(sig.items()) + list(norm.items()) + list(pad.items()) + list(pool.items()) + list(softmax.items()) +
+    # include/si_cdist.h: torch.cdist, the distance between every row of x1 and every row of x2
+    cdist_ = {
+        "si_hip_cdist_f32": (i, [C.POINTER(SiCdistDesc), vp, vp, vp, vp]),
+        "si_hip_cdist_f16": (i, [C.POINTER(SiCdistDesc), vp, vp, vp, vp]),
+        "si_hip_cdist_kernel_name": (C.c_char_p, [C.POINTER(SiCdistDesc), vp, vp, vp, i]),
+    }
+    for name, (res, args) in (list(cdist_.items()) + list(imgmask_.items()) + list(obb_.items()) + list(border_.items()) + list(sig.items()) + list(norm.items()) + list(pad.items()) + list(pool.items()) + list(softmax.items()) +
                               list(superres.items()) + list(slice_.items()) + list(reduce_.items()) + list(act.items()) + list(permute_.items()) +
                               list(attention_.items()) + list(deform_.items()) + list(grid_.items()) + list(roi_.items()) + list(rnn_.items()) +
                               list(binary_.items()) + list(conv1d_.items()) + list(xcorr_.items()) + list(detect_.items()) + list(lpnorm_.items()) +
@@ -588,6 +599,7 @@ def hip():
     L._si_border_signatures = border_
     L._si_obb_signatures = obb_
     L._si_imgmask_signatures = imgmask_
+    L._si_cdist_signatures = cdist_
     _hip = L
     return L
 

@@ -127,6 +127,7 @@ enum class BatchFamily {
     kConstant,      // pnnx.Attribute: a tensor of the file, the same for every image -- always per-image
     kRecurrent,     // nn.LSTM / nn.GRU: reads the batch from dimension 0 (batch_first) or 1; y keeps it there, the state outputs carry it in 1
     kXcorr,         // F.conv2d: kSpatial on x while the filter (and bias) are graph constants; with a filter computed from a graph input never per-image
+    kCdist,         // torch.cdist: dimension 0 is the batch of rank-3 operands (a rank-2 constant meets every image); two rank-2 activations never per-image
 };
 
 // why an operator of the family kRoi is never per-image (also the engine's reason for refusing to re-batch a graph that holds one)
@@ -137,6 +138,19 @@ inline const char* RoiBatchReason() {
 // why F.conv2d with a filter computed from a graph input is never per-image (also the engine's reason for refusing to re-batch such a graph)
 inline const char* XcorrBatchReason() {
     return "the filter is computed from a graph input: its dimension 0 counts filters, not images, and every image of x meets every filter";
+}
+
+// why torch.cdist of two rank-2 activations is never per-image (also the engine's reason for refusing to re-batch such a graph)
+inline const char* CdistBatchReason() {
+    return "both operands are rank-2 activations: their dimension 0 counts points, not images, and every point of one meets every point of the other";
+}
+
+// torch.cdist (kCdist) whose two operands are rank-2 tensors neither of which is a graph constant; `constants`: ConstantOperands of the graph
+inline bool HasPointSets(const pnnx::Operator* op, const std::set<const pnnx::Operand*>& constants) {
+    if (op->type != "torch.cdist" || op->inputs.size() != 2) return false;
+    for (const pnnx::Operand* in : op->inputs)
+        if (!in || in->shape.size() != 2 || constants.count(in)) return false;
+    return true;
 }
 
 // F.conv2d (kXcorr) whose filter, or bias, is no graph constant; `constants`: ConstantOperands of the graph
@@ -239,6 +253,7 @@ inline BatchFamily BatchFamilyOf(const std::string& type) {
         {"torchvision.ops.roi_align", BatchFamily::kRoi},
         {"nn.LSTM", BatchFamily::kRecurrent},
         {"nn.GRU", BatchFamily::kRecurrent},
+        {"torch.cdist", BatchFamily::kCdist},
     };
     auto it = table.find(type);
     return it == table.end() ? BatchFamily::kUnknown : it->second;
@@ -286,6 +301,44 @@ inline bool PerImageOperator(const pnnx::Operator* op, const std::vector<BatchOp
         if (in[0].axis != 0) {
             why = "the operator works image by image over dimension 0, but its input carries the batch in " + dim_text(in[0].axis);
             return false;
+        }
+        for (size_t i = 0; i < out.size(); ++i)
+            if (out[i].axis != 0) {
+                why = "output " + std::to_string(i) + " does not carry the batch in dimension 0";
+                return false;
+            }
+        return true;
+    }
+    if (family == BatchFamily::kCdist) {
+        // [B, P, M] against [B, R, M]: only the dimensions in FRONT of the last two broadcast, so the right-aligned check below does not
+        // apply -- a codebook [Kc, M] has Kc where rows [N, M] have the batch and still meets every image
+        if (in.size() != 2) {
+            why = "torch.cdist takes two operands";
+            return false;
+        }
+        if (in[0].shape.size() == 2 && in[1].shape.size() == 2 && !in[0].constant && !in[1].constant) {
+            // whatever the shapes say: P == N is a coincidence, and a slab of one point set still meets every point of the other
+            why = CdistBatchReason();
+            return false;
+        }
+        if (in[0].axis < 0 && in[1].axis < 0) return true;
+        for (size_t i = 0; i < 2; ++i) {
+            if (in[i].constant) {
+                if (batch > 1 && in[i].shape.size() == 3 && in[i].shape[0] != 1) {
+                    why = "the constant input " + std::to_string(i) + " has " + std::to_string(in[i].shape[0]) + " batch items: it pairs one slice of itself with each image";
+                    return false;
+                }
+                continue;
+            }
+            if (in[i].axis < 0 && batch > 1) {
+                why = "input " + std::to_string(i) + " has no batch dimension while the other operand carries " + std::to_string(batch) +
+                      " images: one point set is combined with every image";
+                return false;
+            }
+            if (in[i].axis > 0) {
+                why = "the operator works image by image over dimension 0, but input " + std::to_string(i) + " carries the batch in " + dim_text(in[i].axis);
+                return false;
+            }
         }
         for (size_t i = 0; i < out.size(); ++i)
             if (out[i].axis != 0) {
@@ -471,6 +524,7 @@ inline std::vector<BatchMixingEntry> FindBatchMixing(const std::vector<pnnx::Ope
         for (const pnnx::Operator* op : ops) {
             if (BatchFamilyOf(op->type) == BatchFamily::kRoi) found.push_back({op->name, op->type, RoiBatchReason()});
             else if (HasTensorFilter(op, consts)) found.push_back({op->name, op->type, XcorrBatchReason()});
+            else if (HasPointSets(op, consts)) found.push_back({op->name, op->type, CdistBatchReason()});
         }
         return found;
     }

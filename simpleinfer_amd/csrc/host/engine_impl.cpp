@@ -200,6 +200,12 @@ Status EngineImpl::CreateTensorNodes() {
                 LOG(ERROR) << "re-batch: [" << op->name << "] (" << op->type << "): " << XcorrBatchReason() << ": served at the file's batch only";
                 return Status::kUnsupport;
             }
+        // a point matcher: torch.cdist of two rank-2 activations, whose dimension 0 counts points.  Not re-batched either
+        for (const pnnx::Operator* op : graph_->ops)
+            if (HasPointSets(op, consts)) {
+                LOG(ERROR) << "re-batch: [" << op->name << "] (" << op->type << "): " << CdistBatchReason() << ": served at the file's batch only";
+                return Status::kUnsupport;
+            }
         for (pnnx::Operand* opd : graph_->operands)
             if (opd->producer && opd->producer->inputs.empty() && !IsAttributeOp(opd->producer) && !opd->shape.empty()) {
                 if (file_batch != 0 && file_batch != opd->shape[0]) {

@@ -15,6 +15,7 @@ SI_DECLARE_LAYER(AvgPool2d)
 SI_DECLARE_LAYER(BatchNorm2d)
 SI_DECLARE_LAYER(BinaryOp)
 SI_DECLARE_LAYER(Cat)
+SI_DECLARE_LAYER(Cdist)
 SI_DECLARE_LAYER(Conv1d)
 SI_DECLARE_LAYER(Conv2d)
 SI_DECLARE_LAYER(ConvTranspose2d)
@@ -75,7 +76,8 @@ static std::map<std::string, LayerRegistryEntry>& Table() {
     // F.normalize / torch.norm (one class, layer/lp_norm.h: the Lp-norm kernels of include/si_lpnorm.h);
     // F.layer_norm (layer/layer_norm.h: the row kernels of include/si_layernorm.h) and F.gelu (ParamActivation: the two GELU operators of
     // include/si_act.h).  Their module spellings nn.LayerNorm / nn.GELU are NOT registered yet: the classes read the module form too, so each is
-    // one line here and one row in batch_rule.h once the tests that pin those strings as absent may change.
+    // one line here and one row in batch_rule.h once the tests that pin those strings as absent may change;
+    // torch.cdist (layer/cdist.h: the pairwise-distance kernels of include/si_cdist.h; either operand may be a graph constant).
     static std::map<std::string, LayerRegistryEntry> table = {
         SI_ENTRY("nn.AdaptiveAvgPool2d", AdaptiveAvgPool2d),
         SI_ENTRY("nn.AvgPool2d", AvgPool2d),
@@ -164,6 +166,7 @@ static std::map<std::string, LayerRegistryEntry>& Table() {
         SI_ENTRY("torch.norm", LpNorm),
         SI_ENTRY("F.layer_norm", LayerNorm),
         SI_ENTRY("F.gelu", ParamActivation),
+        SI_ENTRY("torch.cdist", Cdist),
     };
     return table;
 }

@@ -1827,6 +1827,43 @@ def layernorm_kernel_name(rows, c, half=False, in_ld=None, out_ld=None) -> str:
     return _desc_kernel_name("layernorm", layernorm_desc(rows, c, 1e-5, in_ld, out_ld), half)
 
 
+CDIST_NORMS = {1.0: 1, 2.0: 2, float("inf"): 3}   # SI_CDIST_NORM_*; any other p has no code (0: the entries refuse it)
+CDIST_MODES = {None: 0, "use_mm_for_euclid_dist_if_necessary": 0, "use_mm_for_euclid_dist": 1, "donot_use_mm_for_euclid_dist": 2}
+
+
+def cdist_desc(x1_shape, x2_shape, p=2.0, compute_mode=None, x1_ld=None, x2_ld=None, out_ld=None):
+    """SiCdistDesc (include/si_cdist.h) of operands [P, M] / [B, P, M] and [R, M] / [B, R, M]: dense batch items of rows ld apart"""
+    (b1, np_, m), (b2, nr, _) = [((1,) * (3 - len(s)) + tuple(int(v) for v in s)) for s in (x1_shape, x2_shape)]
+    x1_ld, x2_ld, out_ld = int(x1_ld or m), int(x2_ld or m), int(out_ld or nr)
+    return _native.SiCdistDesc(b1, b2, np_, nr, m, x1_ld, x2_ld, out_ld, np_ * x1_ld, nr * x2_ld, np_ * out_ld, CDIST_NORMS.get(float(p), 0),
+                               CDIST_MODES[compute_mode])
+
+
+def cdist(x1, x2, p=2.0, compute_mode=None, x1_ld=None, x1_off=0, x1_fill=0.0, x2_ld=None, x2_off=0, x2_fill=0.0, out_ld=None, out_off=0,
+          out_fill=0.0, full=False):
+    """si_hip_cdist_f32 / _f16 (by x1's dtype): torch.cdist of rank-2 / rank-3 arrays.  The view hooks are the common ones, per operand: rows
+    of `ld` elements with the operand `off` elements into each row and `fill` elsewhere."""
+    H = _native.hip()
+    x1 = _float_storage(x1)
+    x2 = np.ascontiguousarray(x2, dtype=x1.dtype)
+    half = x1.dtype == np.float16
+    assert x1.ndim in (2, 3) and x2.ndim in (2, 3) and x1.shape[-1] == x2.shape[-1], (x1.shape, x2.shape)
+    d = cdist_desc(x1.shape, x2.shape, p, compute_mode, x1_ld, x2_ld, out_ld)
+    lead = (max(d.b1, d.b2),) if max(x1.ndim, x2.ndim) == 3 else ()
+    (da, pa), (db, pb) = _view_in(x1, x1_ld, x1_off, x1_fill), _view_in(x2, x2_ld, x2_off, x2_fill)
+    dy, py = _view_out(lead + (d.p,), d.r, out_ld, out_off, out_fill, x1.dtype)
+    LAST_KERNEL_NAME["si_hip_cdist"] = H.si_hip_cdist_kernel_name(C.byref(d), C.c_void_p(pa), C.c_void_p(pb), C.c_void_p(py), 1 if half else 0).decode()
+    name = "si_hip_cdist_f16" if half else "si_hip_cdist_f32"
+    _chk(getattr(H, name)(C.byref(d), pa, pb, py, None), name)
+    return _ret(dy.to_numpy(lead + (d.p, out_ld or d.r), x1.dtype), d.r, out_off, full)
+
+
+def cdist_kernel_name(x1_shape, x2_shape, p=2.0, compute_mode=None, half=False, x1_ld=None, x2_ld=None, out_ld=None) -> str:
+    """the kernel for 16-byte aligned, disjoint buffers of these shapes ("none": a descriptor the launch refuses)"""
+    d = cdist_desc(x1_shape, x2_shape, p, compute_mode, x1_ld, x2_ld, out_ld)
+    return _native.hip().si_hip_cdist_kernel_name(C.byref(d), C.c_void_p(1 << 40), C.c_void_p(1 << 41), C.c_void_p(1 << 42), 1 if half else 0).decode()
+
+
 def pixel_shuffle_desc(x_shape, r, inverse=False, in_ld=None, out_ld=None):
     """SiPixelShuffleDesc (include/si_superres.h) of an NHWC input; the output shape is the rule's (floor division: a height, width or
     channel count the factor does not divide gives a descriptor the entry refuses)"""

@@ -414,6 +414,18 @@ class PnnxBuilder:
         self._emit("F.layer_norm", name, ins, [out], params)
         return out
 
+    def cdist(self, x1: str, x2: str, p: float = 2.0, compute_mode=None) -> str:
+        """pnnx's torch.cdist line: `torch.cdist name 2 1 x1 x2 out compute_mode=None p=2.000000e+00`; compute_mode None or one of torch's
+        three strings, p a float (float("inf") is written inf).  Operands of rank 2 / 3; either may come from attribute()."""
+        s1, s2 = self.shapes[x1], self.shapes[x2]
+        lead = s1[:-2] if len(s1) >= len(s2) else s2[:-2]     # (shapes the engine refuses are written too)
+        if len(s1) == len(s2):
+            lead = tuple(max(a, b) for a, b in zip(s1[:-2], s2[:-2]))
+        out = self._new_operand(tuple(lead) + (s1[-2], s2[-2]))
+        self._emit("torch.cdist", self._opname("torch_cdist"), [x1, x2], [out],
+                   dict(compute_mode="None" if compute_mode is None else str(compute_mode), p=float(p)))
+        return out
+
     def gelu(self, x: str, approximate: str = "none") -> str:
         """pnnx's F.gelu line: approximate=none | tanh, the bare text"""
         return self._unary("F.gelu", "F_gelu", x, dict(approximate=str(approximate)))
@@ -1355,6 +1367,36 @@ def build_toy_vit_block(batch: int = 2, tokens: int = 16, e: int = 32, heads: in
         x = b.add(b.multihead_attention(b.layer_norm(x), num_heads=heads, batch_first=True), x)
         x = b.add(b.linear(b.gelu(b.linear(b.layer_norm(x), 2 * e)), e), x)
     b.output(b.linear(b.layer_norm(x), 10))
+    return b
+
+
+def build_toy_descriptor_matcher(batch: int = 2, size: int = 16, d: int = 32, p: float = 2.0, compute_mode=None, seed: int = 0) -> PnnxBuilder:
+    """A descriptor matcher in small: two image inputs through one conv trunk (3 -> 16 + ReLU, stride 2, then 16 -> d; pnnx writes a shared
+    module once per call, so the second stack is written with the first one's weights) -> F.normalize over the channels ->
+    permute(0, 2, 3, 1) -> view(N, L, D) (a view, not a launch) -> torch.cdist of the two descriptor sets: [N, L, L]"""
+    b = PnnxBuilder(seed)
+    sets, trunk = [], None
+    for img in (b.input((batch, 3, size, size)), b.input((batch, 3, size, size))):
+        first = len(b.lines)
+        x = b.normalize(b.conv(b.relu(b.conv(img, 16, 3, 2)), d, 3, 1), dim=1)
+        sets.append(b.view(b.permute(x, (0, 2, 3, 1)), (batch, -1, d)))
+        convs = [ln.split()[1] for ln in b.lines[first:] if ln.startswith("nn.Conv2d")]
+        trunk = trunk or convs
+        for mine, shared in zip(convs, trunk):
+            for key in ("weight", "bias"):
+                b.attrs["%s.%s" % (mine, key)] = b.attrs["%s.%s" % (shared, key)]
+    b.output(b.cdist(sets[0], sets[1], p, compute_mode))
+    return b
+
+
+def build_toy_vq_encoder(batch: int = 2, size: int = 8, d: int = 16, codes: int = 40, p: float = 2.0, seed: int = 0) -> PnnxBuilder:
+    """The codebook lookup of a VQ-VAE / VQGAN encoder up to the argmin: conv 3 -> d -> permute(0, 2, 3, 1) -> view(N, HW, D) (a view) ->
+    torch.cdist against the codebook [Kc, D], a constant of the file: [N, HW, Kc]"""
+    b = PnnxBuilder(seed)
+    z = b.conv(b.input((batch, 3, size, size)), d, 3, 1)
+    z = b.view(b.permute(z, (0, 2, 3, 1)), (batch, -1, d))
+    codebook = b.attribute(seeded_uniform("codebook", (codes, d), -1.0, 1.0, seed))
+    b.output(b.cdist(z, codebook, p))
     return b
 
 
