@@ -203,6 +203,12 @@ class SiDetectPostOut(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("dets", "counts", "src_rows", "net_boxes", "extras")]
 
 
+class SiDetectTopkDesc(C.Structure):
+    """include/si_topk.h; ne = 4 + classes + extra, the layouts, strides and box formats of SiDetectPostDesc"""
+    _fields_ = [(k, C.c_int) for k in ("n", "rows", "classes", "extra", "layout", "ld")] + [("image_ld", C.c_longlong), ("box_format", C.c_int),
+                ("prob_threshold", C.c_float), ("multi_label", C.c_int), ("max_det", C.c_int)]
+
+
 class SiDetectMaskDesc(C.Structure):
     """include/si_detect.h; prototypes [n][mh][mw][nm] with pixels proto_ld apart, the coefficients at extras[b][d][coef_off .. coef_off + nm)"""
     _fields_ = [(k, C.c_int) for k in ("n", "mh", "mw", "nm", "proto_ld", "max_det", "extra", "coef_off")] + [
@@ -567,7 +573,13 @@ def hip():
         "si_hip_cdist_f16": (i, [C.POINTER(SiCdistDesc), vp, vp, vp, vp]),
         "si_hip_cdist_kernel_name": (C.c_char_p, [C.POINTER(SiCdistDesc), vp, vp, vp, i]),
     }
-    for name, (res, args) in (list(cdist_.items()) + list(imgmask_.items()) + list(obb_.items()) + list(border_.items()) + list(sig.items()) + list(norm.items()) + list(pad.items()) + list(pool.items()) + list(softmax.items()) +
+    # include/si_topk.h: NMS-free post-processing, the max_det best (row, class) pairs by a device radix select
+    topk_ = {
+        "si_hip_detect_topk_workspace_bytes": (sz, [C.POINTER(SiDetectTopkDesc)]),
+        "si_hip_detect_topk_postprocess_f32": (i, [C.POINTER(SiDetectTopkDesc), vp, vp, C.POINTER(SiDetectPostOut), vp, sz, vp]),
+        "si_hip_detect_topk_kernel_name": (C.c_char_p, [C.POINTER(SiDetectTopkDesc), vp]),
+    }
+    for name, (res, args) in (list(topk_.items()) + list(cdist_.items()) + list(imgmask_.items()) + list(obb_.items()) + list(border_.items()) + list(sig.items()) + list(norm.items()) + list(pad.items()) + list(pool.items()) + list(softmax.items()) +
                               list(superres.items()) + list(slice_.items()) + list(reduce_.items()) + list(act.items()) + list(permute_.items()) +
                               list(attention_.items()) + list(deform_.items()) + list(grid_.items()) + list(roi_.items()) + list(rnn_.items()) +
                               list(binary_.items()) + list(conv1d_.items()) + list(xcorr_.items()) + list(detect_.items()) + list(lpnorm_.items()) +
@@ -600,6 +612,7 @@ def hip():
     L._si_obb_signatures = obb_
     L._si_imgmask_signatures = imgmask_
     L._si_cdist_signatures = cdist_
+    L._si_topk_signatures = topk_
     _hip = L
     return L
 

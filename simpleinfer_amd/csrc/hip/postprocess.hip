@@ -131,6 +131,10 @@ namespace plan = si_detect_plan;
 using si_post::FilterArgs;
 using si_post::PostWs;
 using si_post::post_ws_bind;
+using si_post::PostAdjust;
+using si_post::post_adjust;
+using si_post::post_box;
+using si_post::post_store_det;
 
 // what the general entry adds to the NMS / compaction kernels' outputs: each pointer may be null (all are for si_hip_yolo_postprocess_f32)
 struct PostMore {
@@ -154,17 +158,10 @@ constexpr int RPB = plan::kStageRows;
 // a kept row: its box from the four raw elements, its label, its sort key
 __device__ __forceinline__ void post_emit(const PostWs& ws, int b, int rows, int e, float r0, float r1, float r2, float r3, int box_format,
                                           int class_index, float confidence) {
-    float x0, y0, x1, y1;
-    if (box_format == plan::kCxCyWh) {
-        x0 = r0 - r2 * 0.5f; y0 = r1 - r3 * 0.5f;
-        x1 = r0 + r2 * 0.5f; y1 = r1 + r3 * 0.5f;
-    } else {
-        x0 = r0; y0 = r1; x1 = r2; y1 = r3;
-    }
     const int slot = atomicAdd(&ws.count[b], 1);
     atomicAdd(&ws.bin_count[(size_t)b * ws.nbins + class_index + 1], 1);
     const size_t o = (size_t)b * rows + slot;
-    ws.box[o] = make_float4(x0, y0, x1 - x0, y1 - y0);
+    ws.box[o] = post_box(r0, r1, r2, r3, box_format);
     ws.label[o] = class_index;
     // descending (prob, then earlier element first): larger key sorts first
     ws.key[o] = ((unsigned long long)ordered_bits(confidence) << 32) | (unsigned)(0xffffffffu - (unsigned)e);
@@ -311,14 +308,6 @@ __device__ __forceinline__ float inter_area(const float4 a, const float4 b) {
     return w * h;
 }
 
-// the reference's clip, (std::max)(lower, (std::min)(n, upper)) (test_yolo.cpp:188-191), spelled out: std::min(a, b) is `b < a ? b : a`,
-// std::max(a, b) is `a < b ? b : a`, each its FIRST argument when the compare is false.  So a NaN coordinate clips to lo (fmaxf / fminf
-// sent it to hi) and -0.0 to +0.0 (geometry with adjust holds both).
-__device__ __forceinline__ float clipf(float v, float lo, float hi) {
-    const float m = hi < v ? hi : v;
-    return lo < m ? m : lo;
-}
-
 // the general entry's outputs for the candidate at confidence rank `idx`, stored as detection `pos` (< max_det) of image b
 __device__ __forceinline__ void post_more(const PostMore& more, const PostWs& ws, int b, int rows, int max_det, int idx, int pos, const float4 box) {
     if (more.drow || more.src_rows) {
@@ -347,15 +336,7 @@ __global__ __launch_bounds__(256) void yolo_nms_kernel(int rows, float nms_thres
     if (threadIdx.x == 0) picked_n = 0;
     __syncthreads();
 
-    float pad_l = 0.0f, pad_t = 0.0f, scale = 1.0f, xmax = 0.0f, ymax = 0.0f;
-    const bool adj = adjust != nullptr;
-    if (adj) {
-        pad_l = adjust[b * 5 + 0];
-        pad_t = adjust[b * 5 + 1];
-        scale = adjust[b * 5 + 2];
-        xmax = adjust[b * 5 + 3] - 1.0f;
-        ymax = adjust[b * 5 + 4] - 1.0f;
-    }
+    const PostAdjust adj = post_adjust(adjust, b);
 
     for (int c0 = 0; c0 < count; c0 += 64) {
         const int idx = c0 + lane;
@@ -403,19 +384,7 @@ __global__ __launch_bounds__(256) void yolo_nms_kernel(int rows, float nms_thres
                 ws.plabel[base + pos] = label;
                 ws.parea[base + pos] = area;
                 if (pos < max_det) {
-                    float x0 = box.x, y0 = box.y, x1 = box.x + box.z, y1 = box.y + box.w;
-                    if (adj) {
-                        x0 = clipf((x0 - pad_l) / scale, 0.0f, xmax);
-                        y0 = clipf((y0 - pad_t) / scale, 0.0f, ymax);
-                        x1 = clipf((x1 - pad_l) / scale, 0.0f, xmax);
-                        y1 = clipf((y1 - pad_t) / scale, 0.0f, ymax);
-                    }
-                    float* d = dets + ((size_t)b * max_det + pos) * 6;
-                    d[0] = x0; d[1] = y0;
-                    d[2] = adj ? x1 - x0 : box.z;
-                    d[3] = adj ? y1 - y0 : box.w;
-                    d[4] = ws.sprob[base + idx];
-                    d[5] = (float)label;
+                    post_store_det(dets + ((size_t)b * max_det + pos) * 6, box, adj, ws.sprob[base + idx], (float)label);
                     post_more(more, ws, b, rows, max_det, idx, pos, box);
                 }
             }
@@ -494,15 +463,7 @@ __global__ __launch_bounds__(256) void yolo_compact_kernel(int rows, const float
     const int count = ws.count[b];
     const size_t base = (size_t)b * rows;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    float pad_l = 0.0f, pad_t = 0.0f, scale = 1.0f, xmax = 0.0f, ymax = 0.0f;
-    const bool adj = adjust != nullptr;
-    if (adj) {
-        pad_l = adjust[b * 5 + 0];
-        pad_t = adjust[b * 5 + 1];
-        scale = adjust[b * 5 + 2];
-        xmax = adjust[b * 5 + 3] - 1.0f;
-        ymax = adjust[b * 5 + 4] - 1.0f;
-    }
+    const PostAdjust adj = post_adjust(adjust, b);
     int total = 0;
     for (int g0 = 0; g0 < count; g0 += 256) {
         const int g = g0 + threadIdx.x;
@@ -516,19 +477,7 @@ __global__ __launch_bounds__(256) void yolo_compact_kernel(int rows, const float
         total += wsum[0] + wsum[1] + wsum[2] + wsum[3];
         if (f && pos < max_det) {
             const float4 box = ws.sbox[base + g];
-            float x0 = box.x, y0 = box.y, x1 = box.x + box.z, y1 = box.y + box.w;
-            if (adj) {
-                x0 = clipf((x0 - pad_l) / scale, 0.0f, xmax);
-                y0 = clipf((y0 - pad_t) / scale, 0.0f, ymax);
-                x1 = clipf((x1 - pad_l) / scale, 0.0f, xmax);
-                y1 = clipf((y1 - pad_t) / scale, 0.0f, ymax);
-            }
-            float* d = dets + ((size_t)b * max_det + pos) * 6;
-            d[0] = x0; d[1] = y0;
-            d[2] = adj ? x1 - x0 : box.z;
-            d[3] = adj ? y1 - y0 : box.w;
-            d[4] = ws.sprob[base + g];
-            d[5] = (float)ws.slabel[base + g];
+            post_store_det(dets + ((size_t)b * max_det + pos) * 6, box, adj, ws.sprob[base + g], (float)ws.slabel[base + g]);
             post_more(more, ws, b, rows, max_det, g, pos, box);
         }
     }

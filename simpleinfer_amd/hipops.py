@@ -2554,6 +2554,68 @@ def detect_obb_postprocess(pred, classes, extra=1, angle_off=0, objectness=False
     return DetectObbResult(n, max_det, int(extra), full["counts"].copy(), full, dev)
 
 
+# ---- include/si_topk.h: NMS-free post-processing, the max_det best (row, class) pairs ------------------------------------------------------------
+DETECT_TOPK_MAX_DET = 1024
+
+
+def detect_topk_desc(n, rows, classes, extra=0, layout="rows", box_format="cxcywh", prob_threshold=0.25, multi_label=True, max_det=300, ld=None,
+                     image_ld=None):
+    """SiDetectTopkDesc; ld / image_ld default to the dense strides of the layout"""
+    ne = 4 + int(classes) + int(extra)
+    lay = DETECT_LAYOUTS[layout] if isinstance(layout, str) else int(layout)
+    fmt = DETECT_BOX_FORMATS[box_format] if isinstance(box_format, str) else int(box_format)
+    if ld is None:
+        ld = rows if lay == 1 else ne
+    if image_ld is None:
+        image_ld = ne * ld if lay == 1 else rows * ld
+    return _native.SiDetectTopkDesc(int(n), int(rows), int(classes), int(extra), lay, int(ld), int(image_ld), fmt, float(prob_threshold),
+                                    int(multi_label), int(max_det))
+
+
+def detect_topk_kernel_name(d, pred_ptr=256) -> str:
+    return _native.hip().si_hip_detect_topk_kernel_name(C.byref(d), C.c_void_p(pred_ptr)).decode()
+
+
+def detect_topk_workspace_bytes(d) -> int:
+    return int(_native.hip().si_hip_detect_topk_workspace_bytes(C.byref(d)))
+
+
+def detect_topk_postprocess(pred, classes, extra=0, layout="rows", box_format="cxcywh", prob_threshold=0.25, multi_label=True, adjust=None,
+                            max_det=300, pred_dev=None, ld=None, image_ld=None, workspace=None, shape=None, pred_off=0, in_fill=np.nan,
+                            want=("src_rows", "net_boxes", "extras"), host=None, out_fill=0.0, stream=None):
+    """si_hip_detect_topk_postprocess_f32 (include/si_topk.h): the max_det best candidates of each image by (score descending, flat index
+    ascending), no NMS.  The arguments are detect_postprocess's: pred the logical array ([n][rows][ne] for "rows", [n][ne][rows] for
+    "channels"), or pred_dev a DeviceBuffer (a view on an Engine.extract pointer with outputs_to_host=0) with shape = (n, rows).  Returns a
+    DetectResult."""
+    H = _native.hip()
+    lay = DETECT_LAYOUTS[layout]
+    if pred_dev is None:
+        pred = _f32(pred)
+        n, rows = (pred.shape[0], pred.shape[2]) if lay == 1 else (pred.shape[0], pred.shape[1])
+        dbuf = DeviceBuffer.from_numpy(detect_storage(pred, layout, ld, image_ld, pred_off, in_fill))
+        pred_ptr = dbuf.ptr + 4 * pred_off
+    else:
+        n, rows = (int(v) for v in shape)
+        pred_ptr = pred_dev.ptr + 4 * pred_off
+    d = detect_topk_desc(n, rows, classes, extra, layout, box_format, prob_threshold, multi_label, max_det, ld, image_ld)
+    LAST_KERNEL_NAME["si_hip_detect_topk"] = H.si_hip_detect_topk_kernel_name(C.byref(d), C.c_void_p(pred_ptr)).decode()
+    dadj = DeviceBuffer.from_numpy(_f32(adjust).reshape(n, 5)) if adjust is not None else None
+    wsb = detect_topk_workspace_bytes(d)
+    dws = workspace if workspace is not None else DeviceBuffer(max(wsb, 16))
+    assert wsb == 0 or dws.nbytes >= wsb, "workspace of %d bytes, the call needs %d" % (dws.nbytes, wsb)
+    shapes = {"dets": ((n, max_det, 6), np.float32), "counts": ((n,), np.int32), "src_rows": ((n, max_det), np.int32),
+              "net_boxes": ((n, max_det, 4), np.float32), "extras": ((n, max_det, int(extra)), np.float32)}
+    dev = {}
+    for name, (shp, dt) in shapes.items():
+        if name in ("dets", "counts") or name in want:
+            dev[name] = DeviceBuffer.from_numpy(_full((max(int(np.prod(shp)), 4),), dt, out_fill), out=True)
+    out = _native.SiDetectPostOut(*[dev[k].ptr if k in dev else None for k in ("dets", "counts", "src_rows", "net_boxes", "extras")])
+    _chk(H.si_hip_detect_topk_postprocess_f32(C.byref(d), pred_ptr, dadj.ptr if dadj else None, C.byref(out), dws.ptr, dws.nbytes, stream),
+         "si_hip_detect_topk_postprocess_f32")
+    full = {k: b.to_numpy(shapes[k][0], shapes[k][1], stream) for k, b in dev.items() if host is None or k in host or k == "counts"}
+    return DetectResult(n, max_det, int(extra), full["counts"].copy(), full, dev)
+
+
 # ---------------------------------------------------------------------------
 # fp16 storage path (include/si_hip.h "fp16 storage path").  Activations travel as numpy float16 (IEEE binary16, the
 # device's _Float16); results come back as float16 unless noted.

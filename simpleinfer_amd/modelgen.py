@@ -1309,6 +1309,23 @@ def build_toy_yolov8_seg(batch: int = 2, size: int = 64, nc: int = 5, nm: int = 
     return b
 
 
+def build_toy_yolov10_head(batch: int = 2, size: int = 64, nc: int = 5, channels_first: bool = True, seed: int = 0) -> PnnxBuilder:
+    """An end-to-end (NMS-free) head exported raw, as YOLOv10's one2one head is: per level a box conv (cx cy w h) and a class conv behind a
+    sigmoid, cat(dim=1) -> view(N, 4 + nc, -1); cat(dim=2) over the levels: [N, 4 + nc, cells] -- or [N, cells, 4 + nc] behind the closing
+    permute(0,2,1) when channels_first is False.  The top-k of its post-processing is not in the graph: hipops.detect_topk_postprocess."""
+    b = PnnxBuilder(seed)
+    rows = []
+    for lv, f in enumerate(_toy_pyramid(b, batch, size)):
+        name = "e2e_box_%d" % lv
+        box = b.conv(f, 4, 1, name=name)
+        b.attrs[name + ".weight"] *= size / 2.0
+        b.attrs[name + ".bias"][:] = (size / 2.0, size / 2.0, size / 3.0, size / 3.0)
+        rows.append(b.view(b.cat([box, b.sigmoid(b.conv(f, nc, 1))], 1), (batch, 4 + nc, -1)))
+    y = b.cat(rows, 2)
+    b.output(y if channels_first else b.permute(y, (0, 2, 1)))
+    return b
+
+
 def build_toy_yolov5_raw_head(batch: int = 2, size: int = 32, na: int = 3, no: int = 7, seed: int = 0) -> PnnxBuilder:
     """A raw YOLOv5 export's head: per level conv to na * no channels -> view(N, na, no, H, W) -> permute(0,1,3,4,2) -> view(N, -1, no) (the
     rank-5 route), sigmoid, cat(dim=1) over the levels: [N, na * cells, no]."""
