@@ -117,6 +117,11 @@ class SiCdistDesc(C.Structure):
     _fields_ = [(k, C.c_int) for k in ("b1", "b2", "p", "r", "m", "x1_ld", "x2_ld", "out_ld", "x1_sb", "x2_sb", "out_sb", "norm", "mode")]
 
 
+class SiNearestDesc(C.Structure):
+    """include/si_nearest.h: x1 [b1, p, m], x2 [b2, r, m]; idx / dist [B, p, k], rows [B, p, m]; row and batch strides in elements"""
+    _fields_ = [(k, C.c_int) for k in ("b1", "b2", "p", "r", "m", "x1_ld", "x2_ld", "rows_ld", "x1_sb", "x2_sb", "rows_sb", "k", "splits")]
+
+
 class SiPixelShuffleDesc(C.Structure):
     """include/si_superres.h"""
     _fields_ = [(k, C.c_int) for k in ("n", "ih", "iw", "ic", "in_ld", "oh", "ow", "oc", "out_ld", "r", "inverse")]
@@ -579,7 +584,14 @@ def hip():
         "si_hip_detect_topk_postprocess_f32": (i, [C.POINTER(SiDetectTopkDesc), vp, vp, C.POINTER(SiDetectPostOut), vp, sz, vp]),
         "si_hip_detect_topk_kernel_name": (C.c_char_p, [C.POINTER(SiDetectTopkDesc), vp]),
     }
-    for name, (res, args) in (list(topk_.items()) + list(cdist_.items()) + list(imgmask_.items()) + list(obb_.items()) + list(border_.items()) + list(sig.items()) + list(norm.items()) + list(pad.items()) + list(pool.items()) + list(softmax.items()) +
+    # include/si_nearest.h: the fused nearest-row search (cdist + argmin + the codebook row as one launch)
+    nearest_ = {
+        "si_hip_nearest_workspace_bytes": (sz, [C.POINTER(SiNearestDesc)]),
+        "si_hip_nearest_f32": (i, [C.POINTER(SiNearestDesc), vp, vp, vp, vp, vp, vp, sz, vp]),
+        "si_hip_nearest_f16": (i, [C.POINTER(SiNearestDesc), vp, vp, vp, vp, vp, vp, sz, vp]),
+        "si_hip_nearest_kernel_name": (C.c_char_p, [C.POINTER(SiNearestDesc), vp, vp, vp, i]),
+    }
+    for name, (res, args) in (list(nearest_.items()) + list(topk_.items()) + list(cdist_.items()) + list(imgmask_.items()) + list(obb_.items()) + list(border_.items()) + list(sig.items()) + list(norm.items()) + list(pad.items()) + list(pool.items()) + list(softmax.items()) +
                               list(superres.items()) + list(slice_.items()) + list(reduce_.items()) + list(act.items()) + list(permute_.items()) +
                               list(attention_.items()) + list(deform_.items()) + list(grid_.items()) + list(roi_.items()) + list(rnn_.items()) +
                               list(binary_.items()) + list(conv1d_.items()) + list(xcorr_.items()) + list(detect_.items()) + list(lpnorm_.items()) +
@@ -613,6 +625,7 @@ def hip():
     L._si_imgmask_signatures = imgmask_
     L._si_cdist_signatures = cdist_
     L._si_topk_signatures = topk_
+    L._si_nearest_signatures = nearest_
     _hip = L
     return L
 

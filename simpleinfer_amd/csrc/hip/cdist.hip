@@ -21,6 +21,7 @@
 #include "si_hip.h"
 #include "si_hip_internal.h"
 
+#include "cdist_dev.h"
 #include "cdist_plan.h"
 
 namespace {
@@ -36,50 +37,6 @@ struct CdArgs {
     int x1_sb, x2_sb, out_sb;   // x1_sb / x2_sb: 0 for a broadcast operand
     int p_tiles, r_tiles;
 };
-
-// ---- the mm kernel's geometry per storage type: elements of an item (the 16-byte K vector), of a K-tile (8 items) and the LDS row pitch
-template <typename T> struct CdMm;
-template <> struct CdMm<float> {
-    typedef f32x4 item_t;
-    static constexpr int VW = 4, BK = SI_G64_BK, LDL = SI_G64_LDL, LDS_ELEMS = SI_G64_LDS_FLOATS;
-};
-template <> struct CdMm<_Float16> {
-    typedef f16x8 item_t;
-    // 64 + 8 halves: rows 144 bytes apart, so the 16 rows of a fragment read start 36 words apart (4 banks) and a 16-byte read per lane
-    // covers the banks evenly
-    static constexpr int VW = 8, BK = 64, LDL = 64 + 8, LDS_ELEMS = (SI_G64_BM + SI_G64_BN) * LDL;
-};
-
-// one item of row `row` (of `rows`) at element k: zeros beyond the rows, and element by element beyond m in the single-element form
-template <typename T, bool VEC>
-__device__ __forceinline__ typename CdMm<T>::item_t cd_load_item(const T* base, int row, int rows, int ld, int k, int m) {
-    typedef typename CdMm<T>::item_t item_t;
-    item_t v;
-#pragma unroll
-    for (int j = 0; j < CdMm<T>::VW; ++j) v[j] = (T)0;
-    if (row < rows && k < m) {
-        const T* const p = base + (size_t)row * ld + k;
-        if (VEC) {
-            v = *reinterpret_cast<const item_t*>(p);
-        } else {
-#pragma unroll
-            for (int j = 0; j < CdMm<T>::VW; ++j)
-                if (k + j < m) v[j] = p[j];
-        }
-    }
-    return v;
-}
-
-// q += the squares of an item's elements, in k order, each square rounded on its own
-template <typename Item, int VW>
-__device__ __forceinline__ float cd_add_squares(float q, const Item& v) {
-#pragma unroll
-    for (int j = 0; j < VW; ++j) {
-        const float e = (float)v[j];
-        q = q + e * e;
-    }
-    return q;
-}
 
 // the epilogue of one output: contraction is off, so the sum, the difference and the root round as written; a NaN passes the clamp
 __device__ __forceinline__ float cd_mm_result(float n1, float n2, float acc) {

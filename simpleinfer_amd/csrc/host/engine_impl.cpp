@@ -11,6 +11,7 @@
 #include "layer_registry.h"
 #include "pnnx/expand_expression.h"
 #include "pnnx/lower_functional_conv.h"
+#include "pnnx/lower_nearest_rows.h"
 
 namespace SimpleInfer {
 
@@ -154,6 +155,13 @@ Status EngineImpl::CreateGraph(const std::string& parampath, const std::string& 
     // F.conv2d whose filter and bias are constants of the file with no other reader is nn.Conv2d written as a function: it becomes that
     // operator here, before layers exist and before the batch rule looks at the graph
     pnnx::lower_functional_conv(*graph_);
+    // torch.cdist -> torch.argmin -> F.embedding / nn.Embedding against one constant table is one torch.cdist with nearest_rows=1; an argmin
+    // or an embedding outside such a chain has no layer (the engine has no integer tensors)
+    std::string why;
+    if (pnnx::lower_nearest_rows(*graph_, &why) < 0) {
+        LOG(ERROR) << "load graph fail [" << why << "]";
+        return Status::kUnsupport;
+    }
     return Status::kSuccess;
 }
 

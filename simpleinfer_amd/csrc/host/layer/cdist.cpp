@@ -36,7 +36,22 @@ Status Cdist::Init(const pnnx::Operator* op) {
         else if (mode == "donot_use_mm_for_euclid_dist") mode_ = SI_CDIST_MODE_NO_MM;
         else return Refuse("compute_mode=" + mode + " is none of torch's three", Status::kUnsupport);
     }
+    int rows = 0;
+    if (FindParam(op, "nearest_rows")) CHECK_BOOL(Get(op, "nearest_rows", rows));
+    nearest_rows_ = rows != 0;
+    if (nearest_rows_ && norm_ != SI_CDIST_NORM_2) return Refuse("nearest_rows with p != 2: the fused search is Euclidean", Status::kUnsupport);
     return Status::kSuccess;
+}
+
+SiNearestDesc Cdist::NearestDesc(const SiCdistDesc& d) {
+    SiNearestDesc n;
+    memset(&n, 0, sizeof(n));
+    n.b1 = d.b1; n.b2 = d.b2; n.p = d.p; n.r = d.r; n.m = d.m;
+    n.x1_ld = d.x1_ld; n.x2_ld = d.x2_ld; n.rows_ld = d.out_ld;
+    n.x1_sb = d.x1_sb; n.x2_sb = d.x2_sb; n.rows_sb = d.out_sb;
+    n.k = 1;
+    n.splits = 1;
+    return n;
 }
 
 bool Cdist::MakeDesc(const Tensor& x1, const Tensor& x2, const Tensor& out, SiCdistDesc& d, std::string* why) const {
@@ -61,7 +76,7 @@ bool Cdist::MakeDesc(const Tensor& x1, const Tensor& x2, const Tensor& out, SiCd
     if (d.b1 != d.b2 && d.b1 != 1 && d.b2 != 1)
         return fail("batch dimensions " + std::to_string(d.b1) + " and " + std::to_string(d.b2) + ": equal, or one of them 1");
     const int batch = d.b1 > d.b2 ? d.b1 : d.b2;
-    std::vector<int> want = {d.p, d.r};
+    std::vector<int> want = {d.p, nearest_rows_ ? d.m : d.r};   // the winning rows of x2, or the distances
     if (s1.size() == 3 || s2.size() == 3) want.insert(want.begin(), batch);
     if (so != want) return fail("the output is " + ShapeString(so) + ", the operands " + ShapeString(s1) + " and " + ShapeString(s2) + " give " + ShapeString(want));
     d.x1_ld = x1.PixelStride();
@@ -87,7 +102,10 @@ Status Cdist::Validate() {
         return Refuse(why, Status::kErrorShape);
     // (the pointers are compared, never followed: three aligned addresses far apart)
     const uintptr_t base = (uintptr_t)1 << 40, apart = (uintptr_t)1 << 34;
-    if (0 == strcmp("none", si_hip_cdist_kernel_name(&d, (const void*)base, (const void*)(base + apart), (const void*)(base + 2 * apart), 0)))
+    const SiNearestDesc n = NearestDesc(d);
+    const char* const name = nearest_rows_ ? si_hip_nearest_kernel_name(&n, (const void*)base, (const void*)(base + apart), (const void*)(base + 2 * apart), 0)
+                                           : si_hip_cdist_kernel_name(&d, (const void*)base, (const void*)(base + apart), (const void*)(base + 2 * apart), 0);
+    if (0 == strcmp("none", name))
         return Refuse("the kernels refuse these tensors (element offsets beyond 31 bits)", Status::kUnsupport);
     return Status::kSuccess;
 }
@@ -99,6 +117,12 @@ Status Cdist::Forward(const std::vector<Tensor>& inputs, Tensor& output) {
         if (IsHalf(in[1]) != half || IsHalf(out[0]) != half) return Status::kUnsupport;
         SiCdistDesc d;
         if (!MakeDesc(in[0], in[1], out[0], d)) return Status::kErrorShape;
+        if (nearest_rows_) {
+            const SiNearestDesc n = NearestDesc(d);
+            const int rc = half ? si_hip_nearest_f16(&n, in[0].RawData(), in[1].RawData(), nullptr, nullptr, out[0].RawData(), nullptr, 0, Stream())
+                                : si_hip_nearest_f32(&n, in[0].Data<float>(), in[1].Data<float>(), nullptr, nullptr, out[0].Data<float>(), nullptr, 0, Stream());
+            return CheckHip(rc, "Cdist (nearest rows)");
+        }
         const int rc = half ? si_hip_cdist_f16(&d, in[0].RawData(), in[1].RawData(), out[0].RawData(), Stream())
                             : si_hip_cdist_f32(&d, in[0].Data<float>(), in[1].Data<float>(), out[0].Data<float>(), Stream());
         return CheckHip(rc, "Cdist");
@@ -110,6 +134,10 @@ const char* Cdist::KernelName() const {
     const Tensor &x1 = input_tensor_nodes_[0]->tensor, &x2 = input_tensor_nodes_[1]->tensor, &out = output_tensor_nodes_[0]->tensor;
     SiCdistDesc d;
     if (!MakeDesc(x1, x2, out, d) || !x1.RawData() || !x2.RawData() || !out.RawData()) return "cdist";
+    if (nearest_rows_) {
+        const SiNearestDesc n = NearestDesc(d);
+        return si_hip_nearest_kernel_name(&n, x1.RawData(), x2.RawData(), out.RawData(), IsHalf(x1) ? 1 : 0);
+    }
     return si_hip_cdist_kernel_name(&d, x1.RawData(), x2.RawData(), out.RawData(), IsHalf(x1) ? 1 : 0);
 }
 
@@ -119,7 +147,7 @@ double Cdist::Flops() const {
     SiCdistDesc d;
     if (!MakeDesc(input_tensor_nodes_[0]->tensor, input_tensor_nodes_[1]->tensor, output_tensor_nodes_[0]->tensor, d)) return 0.0;
     const double pairs = (double)(d.b1 > d.b2 ? d.b1 : d.b2) * d.p * d.r;
-    const bool mm = d.norm == SI_CDIST_NORM_2 && d.mode != SI_CDIST_MODE_NO_MM &&
+    const bool mm = nearest_rows_ || d.norm == SI_CDIST_NORM_2 && d.mode != SI_CDIST_MODE_NO_MM &&
                     (d.mode == SI_CDIST_MODE_MM || d.p > SI_CDIST_MM_THRESHOLD || d.r > SI_CDIST_MM_THRESHOLD);
     return (mm ? 2.0 : 3.0) * pairs * d.m;
 }

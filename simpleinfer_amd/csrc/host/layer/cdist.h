@@ -8,12 +8,17 @@
 // a graph constant (pnnx.Attribute): the codebook of a VQ encoder, bound like any tensor and read with batch stride 0.  Another rank, or
 // shapes that do not fit, are kErrorShape at LoadModel.  What the batch means (images, or points when both operands are rank-2
 // activations) is batch_rule.h's family kCdist.
+//
+// nearest_rows=1 (written by pnnx/lower_nearest_rows.cpp, never by pnnx): the operator stands for cdist -> argmin -> embedding against the
+// constant codebook x2.  The output is [.., P, M], the nearest codebook row of every row of x1, from one launch of si_hip_nearest_f32 / _f16
+// (include/si_nearest.h) with the rows output alone and one split -- no workspace, so lanes on two streams share nothing.  p must be 2.
 #ifndef SIMPLE_INFER_SRC_LAYER_CDIST_H_
 #define SIMPLE_INFER_SRC_LAYER_CDIST_H_
 
 #include "layer.h"
 #include "layer_util.h"
 #include "si_cdist.h"
+#include "si_nearest.h"
 
 namespace SimpleInfer {
 
@@ -33,11 +38,14 @@ public:
 public:
     int norm_ = SI_CDIST_NORM_2;
     int mode_ = SI_CDIST_MODE_MM_IF_NECESSARY;
+    bool nearest_rows_ = false;
 
 private:
     // the descriptor for a pair of operands and the output; false with `why`: the shapes do not make a cdist
     bool MakeDesc(const Tensor& x1, const Tensor& x2, const Tensor& out, SiCdistDesc& d, std::string* why = nullptr) const;
     Status Refuse(const std::string& why, Status status) const;
+    // the search's descriptor from the cdist one of a nearest_rows operator (out's strides are the rows')
+    static SiNearestDesc NearestDesc(const SiCdistDesc& d);
 };
 
 }  // namespace SimpleInfer

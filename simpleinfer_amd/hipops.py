@@ -1864,6 +1864,52 @@ def cdist_kernel_name(x1_shape, x2_shape, p=2.0, compute_mode=None, half=False, 
     return _native.hip().si_hip_cdist_kernel_name(C.byref(d), C.c_void_p(1 << 40), C.c_void_p(1 << 41), C.c_void_p(1 << 42), 1 if half else 0).decode()
 
 
+def nearest_desc(x1_shape, x2_shape, k=1, splits=0, x1_ld=None, x2_ld=None, rows_ld=None):
+    """SiNearestDesc (include/si_nearest.h) of operands [P, M] / [B, P, M] and [R, M] / [B, R, M]: dense batch items of rows ld apart"""
+    (b1, np_, m), (b2, nr, _) = [((1,) * (3 - len(s)) + tuple(int(v) for v in s)) for s in (x1_shape, x2_shape)]
+    x1_ld, x2_ld, rows_ld = int(x1_ld or m), int(x2_ld or m), int(rows_ld or m)
+    return _native.SiNearestDesc(b1, b2, np_, nr, m, x1_ld, x2_ld, rows_ld, np_ * x1_ld, nr * x2_ld, np_ * rows_ld, int(k), int(splits))
+
+
+def nearest(x1, x2, k=1, want=("idx", "dist", "rows"), splits=0, x1_ld=None, x1_off=0, x1_fill=0.0, x2_ld=None, x2_off=0, x2_fill=0.0,
+            rows_ld=None, rows_off=0, rows_fill=0.0, full=False):
+    """si_hip_nearest_f32 / _f16 (by x1's dtype): per row of x1 the k nearest rows of x2 as one launch (two with a split over R).  Returns a
+    dict of the outputs named in `want`: idx int32 [.., P, k], dist float32 [.., P, k], rows [.., P, M] = x2[idx[..., 0]] in the storage type.
+    The view hooks are the common ones, per operand and for rows."""
+    H = _native.hip()
+    x1 = _float_storage(x1)
+    x2 = np.ascontiguousarray(x2, dtype=x1.dtype)
+    half = x1.dtype == np.float16
+    assert x1.ndim in (2, 3) and x2.ndim in (2, 3) and x1.shape[-1] == x2.shape[-1], (x1.shape, x2.shape)
+    assert want and set(want) <= {"idx", "dist", "rows"}, want
+    d = nearest_desc(x1.shape, x2.shape, k, splits, x1_ld, x2_ld, rows_ld)
+    lead = (max(d.b1, d.b2),) if max(x1.ndim, x2.ndim) == 3 else ()
+    (da, pa), (db, pb) = _view_in(x1, x1_ld, x1_off, x1_fill), _view_in(x2, x2_ld, x2_off, x2_fill)
+    small = lead + (d.p, max(d.k, 1))
+    di = DeviceBuffer.from_numpy(np.full(small, -1, np.int32), out=True) if "idx" in want else None
+    dd = DeviceBuffer.from_numpy(np.full(small, -1.0, np.float32), out=True) if "dist" in want else None
+    dr, pr = _view_out(lead + (d.p,), d.m, rows_ld, rows_off, rows_fill, x1.dtype) if "rows" in want else (None, None)
+    nbytes = H.si_hip_nearest_workspace_bytes(C.byref(d))
+    ws = DeviceBuffer(nbytes) if nbytes else None
+    LAST_KERNEL_NAME["si_hip_nearest"] = H.si_hip_nearest_kernel_name(C.byref(d), C.c_void_p(pa), C.c_void_p(pb), C.c_void_p(pr), 1 if half else 0).decode()
+    name = "si_hip_nearest_f16" if half else "si_hip_nearest_f32"
+    _chk(getattr(H, name)(C.byref(d), pa, pb, di.ptr if di else None, dd.ptr if dd else None, pr, ws.ptr if ws else None, nbytes, None), name)
+    out = {}
+    if di:
+        out["idx"] = di.to_numpy(small, np.int32)
+    if dd:
+        out["dist"] = dd.to_numpy(small, np.float32)
+    if dr:
+        out["rows"] = _ret(dr.to_numpy(lead + (d.p, rows_ld or d.m), x1.dtype), d.m, rows_off, full)
+    return out
+
+
+def nearest_kernel_name(x1_shape, x2_shape, k=1, half=False, splits=0, x1_ld=None, x2_ld=None, rows_ld=None) -> str:
+    """the kernel for 16-byte aligned, disjoint buffers of these shapes ("none": a descriptor the launch refuses)"""
+    d = nearest_desc(x1_shape, x2_shape, k, splits, x1_ld, x2_ld, rows_ld)
+    return _native.hip().si_hip_nearest_kernel_name(C.byref(d), C.c_void_p(1 << 40), C.c_void_p(1 << 41), C.c_void_p(1 << 42), 1 if half else 0).decode()
+
+
 def pixel_shuffle_desc(x_shape, r, inverse=False, in_ld=None, out_ld=None):
     """SiPixelShuffleDesc (include/si_superres.h) of an NHWC input; the output shape is the rule's (floor division: a height, width or
     channel count the factor does not divide gives a descriptor the entry refuses)"""

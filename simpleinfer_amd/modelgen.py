@@ -426,6 +426,31 @@ class PnnxBuilder:
                    dict(compute_mode="None" if compute_mode is None else str(compute_mode), p=float(p)))
         return out
 
+    def argmin(self, x: str, dim: int = -1, keepdim: bool = False) -> str:
+        """pnnx's torch.argmin line: `torch.argmin name 1 1 x out dim=-1 keepdim=False` (the output holds indices; its shape line is written
+        like every other, the engine never makes a tensor of it -- pnnx/lower_nearest_rows.h)"""
+        s = list(self.shapes[x])
+        if keepdim:
+            s[dim] = 1
+        else:
+            del s[dim]
+        out = self._new_operand(s)
+        self._emit("torch.argmin", self._opname("torch_argmin"), [x], [out], dict(dim=int(dim), keepdim=bool(keepdim)))
+        return out
+
+    def embedding(self, idx: str, table) -> str:
+        """table the name of an operand: pnnx's `F.embedding name 2 1 idx table out ...`; an array: the module nn.Embedding with @weight"""
+        if isinstance(table, str):
+            out = self._new_operand(self.shapes[idx] + (self.shapes[table][-1],))
+            self._emit("F.embedding", self._opname("F_embedding"), [idx, table], [out],
+                       dict(max_norm="None", norm_type=2.0, padding_idx="None", scale_grad_by_freq=False, sparse=False))
+        else:
+            w = np.ascontiguousarray(table, dtype=np.float32)
+            out = self._new_operand(self.shapes[idx] + (w.shape[1],))
+            self._emit("nn.Embedding", self._opname("embedding"), [idx], [out],
+                       dict(embedding_dim=int(w.shape[1]), num_embeddings=int(w.shape[0]), padding_idx="None", sparse=False), attrs={"weight": w})
+        return out
+
     def gelu(self, x: str, approximate: str = "none") -> str:
         """pnnx's F.gelu line: approximate=none | tanh, the bare text"""
         return self._unary("F.gelu", "F_gelu", x, dict(approximate=str(approximate)))
@@ -1414,6 +1439,19 @@ def build_toy_vq_encoder(batch: int = 2, size: int = 8, d: int = 16, codes: int 
     z = b.view(b.permute(z, (0, 2, 3, 1)), (batch, -1, d))
     codebook = b.attribute(seeded_uniform("codebook", (codes, d), -1.0, 1.0, seed))
     b.output(b.cdist(z, codebook, p))
+    return b
+
+
+def build_toy_vq(batch: int = 2, size: int = 8, d: int = 16, codes: int = 40, module: bool = False, p: float = 2.0, seed: int = 0) -> PnnxBuilder:
+    """A VQ-VAE / VQGAN quantiser: conv 3 -> d -> permute(0, 2, 3, 1) -> view(N, HW, D) (a view) -> torch.cdist against the codebook
+    [Kc, D] -> torch.argmin(-1) -> F.embedding with the same constant (module: nn.Embedding holding the same bytes): [N, HW, D], every
+    row a row of the codebook.  The engine runs the last three as one launch (pnnx/lower_nearest_rows.h)."""
+    b = PnnxBuilder(seed)
+    z = b.conv(b.input((batch, 3, size, size)), d, 3, 1)
+    z = b.view(b.permute(z, (0, 2, 3, 1)), (batch, -1, d))
+    table = seeded_uniform("codebook", (codes, d), -1.0, 1.0, seed)
+    codebook = b.attribute(table)
+    b.output(b.embedding(b.argmin(b.cdist(z, codebook, p)), table if module else codebook))
     return b
 
 
